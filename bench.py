@@ -11,6 +11,11 @@ the packed detections per step).
 A step = one pass of the whole hot path over one batch that is already resident in HBM:
 yl_predict (36 fused conv launches per batch chunk, decode inside the head-output convs, NMS) [+ all-gather].  Synthetic data, seeded
 synthetic weights (no checkpoints exist in this environment).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line.  --full adds everything else
+the benchmark measures: the per-layer pass and the roofline / traffic / network figures, the one-batch-in-flight loop,
+repeated timed blocks (--min-seconds), BASELINE configs 3 and 4, the GPU batch-1 flow and the CPU baseline.
+--dump-outputs DIR writes the last timed step's results as DIR/*.npy (dump_outputs).
 """
 import argparse
 import json
@@ -453,11 +458,39 @@ def traffic_per_step(model_name, seg, B, prog, S, max_out):
     return out
 
 
-def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seconds, max_blocks=60):
+def dump_outputs(out_dir, dets, counts, masks=None, budget_bytes=48 << 20):
+    """--dump-outputs: what a caller of the timed path receives from its last step, as float32 / float64 .npy files.
+    dets.npy [B, max_out, 6] float32 with the rows past counts[b] zeroed (the packed buffer holds no result there),
+    counts.npy [B] float64.  Seg runs add masks.npy: the bit-packed image masks of detection slots 0..3, the 32-bit words
+    as float64 (exact), [n_img, 4, h, words] -- every image while that fits budget_bytes, else a fixed seeded sample of
+    images listed in mask_images.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    cn = counts.cpu().numpy().astype(np.int64)
+    d = dets.cpu().numpy().astype(np.float32)
+    slot = np.arange(d.shape[1])[None, :]
+    d[slot >= cn[:, None]] = 0.0
+    np.save(os.path.join(out_dir, "dets.npy"), d)
+    np.save(os.path.join(out_dir, "counts.npy"), cn.astype(np.float64))
+    if masks is not None:
+        B = masks.shape[0]
+        words = masks[:, :4].contiguous().view(torch.int32)                     # [B, 4, h, row / 4]
+        per_img = int(words[0].numel()) * 8
+        n_img = max(1, min(B, budget_bytes // per_img))
+        imgs = np.arange(B) if n_img == B else np.sort(np.random.RandomState(0).choice(B, n_img, replace=False))
+        w = words[torch.as_tensor(imgs, device=words.device)].cpu().numpy().view(np.uint32).astype(np.float64)
+        w[np.arange(4)[None, :] >= cn[imgs][:, None]] = 0.0
+        np.save(os.path.join(out_dir, "masks.npy"), w)
+        np.save(os.path.join(out_dir, "mask_images.npy"), imgs.astype(np.float64))
+
+
+def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seconds, max_blocks=60, full=True, dump_dir=None):
     """One configuration of the hot path: build the workload, time per-layer durations eagerly (HIP events around every
     launch), then time BLOCKS of exactly args.steps steps each -- every block bracketed by barrier +
     torch.cuda.synchronize() on both sides, max over ranks -- until >= min_seconds of timed steps (the first block alone
-    is ~40 ms at the headline configuration: too short against the DVFS ramp).  Returns the JSON fields."""
+    is ~40 ms at the headline configuration: too short against the DVFS ramp).  Returns the JSON fields.
+    full=False (a plain bench run): no per-layer pass, no one-batch-in-flight loop, no exchange-alone timing and no
+    roofline / traffic / network figures; min_seconds 0 times one block of exactly args.steps steps.
+    dump_dir: write the last timed step's results there (dump_outputs)."""
     import torch.distributed as dist
     from yololite_amd import _lib, dist as ydist
     S = args.img
@@ -499,9 +532,11 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
                   for _ in range(K)]
     gat = gats[0] if gats else None
     dets, counts = lane_dets[0], lane_counts[0]
+    last = {}
 
     def lane_work(c, k):
         """ONE step = the complete hot path over one batch on context c (lane k)"""
+        last["lane"] = k
         if seg:
             _, _, idx = c.predict(xs[k], _lib.POST_MAIN, args.conf, args.iou, per_class_cap=300, max_out=max_out,
                                   out=(lane_dets[k], lane_counts[k]), want_idx=True)
@@ -525,7 +560,7 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
     for _ in range(2):
         step()
     torch.cuda.synchronize()
-    reps = args.layer_reps
+    reps = args.layer_reps if full else 0
     if reps > 0:
         for _ in range(3):                                   # the eager timed path itself, untimed: clocks / caches settle
             ctx.forward(x, timed=True)
@@ -538,7 +573,7 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
     # ---- the serial loop (ONE batch in flight: calls back to back on one context, two chunk streams) next to the
     # pipelined one, same process, same clocks: reported as `one_batch_in_flight` so that the gain is visible
     serial = None
-    if K > 1:
+    if K > 1 and full:
         # same protocol as the headline below: blocks of exactly args.steps steps, barrier + synchronize on
         # both sides, max over ranks, repeated to >= min_seconds, the MEDIAN block reported; under --gpus N the exchange
         # of every step is inside the block as well
@@ -630,6 +665,15 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
     els = np.asarray(els)
     rates = world * B * args.steps / els
     k_med = int(np.argsort(els)[len(els) // 2])          # the median block: value and ms_per_step come from ONE block
+    if dump_dir is not None and rank == 0:
+        k = last["lane"]                                  # the lane of the last timed step
+        if gats is not None:                              # what the caller receives: the gathered rows of every rank
+            gd, gc = gats[k].flush()
+            dump_outputs(dump_dir, gd.reshape(-1, max_out, 6), gc.reshape(-1))
+        else:
+            row = ((S + 31) // 32) * 4
+            masks = lane_arena[k][:B * max_out * S * row].view(B, max_out, S, row) if seg else None
+            dump_outputs(dump_dir, lane_dets[k], lane_counts[k], masks)
     if gat is not None:
         counts = gat.flush()[1][rank if world > 1 else 0]
         drows = gat.flush()[0][rank if world > 1 else 0]
@@ -647,7 +691,7 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
     extra = {}
     if world > 1 or gat is not None:
         extra["rccl_ranks"] = dist.get_world_size() if dist.is_initialized() else 1
-        if dist.is_initialized():
+        if dist.is_initialized() and full:
             t = torch.tensor([el_locals[k_med] / args.steps * 1e3], device=dev, dtype=torch.float64)
             allt = [torch.zeros_like(t) for _ in range(dist.get_world_size())]
             dist.all_gather(allt, t)
@@ -704,30 +748,9 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
         roof["algorithmic_bytes_per_launch"] = byts
         return roof
 
-    # dominant kernel = the fused layer with the largest median duration; worst = the layer furthest below its roof among
-    # those that take >= 3 % of the forward pass
-    k = int(np.argmax(lay))
-    L = prog.layers[k]
-    roof = roofline_of(k)
-    # (head-output layers are left out: under yl_predict they do not run as the launches the eager per-layer pass times --
-    # detectors: fused with the trunk and the decode (yl_conv_dpp_kernel) or decode in the epilogue; seg models: the split
-    # det-rows + mask-coefficient launches -- VERDICT r04 item 6)
-    heavy = [i for i in range(len(lay)) if lay[i] >= 0.03 * lay.sum() and prog.layers[i].macs > 0 and prog.layers[i].head_level < 0]
-    roof_worst = min((roofline_of(i) for i in heavy), key=lambda r: r["frac"]) if heavy else None
-    if roof_worst is not None:
-        roof_worst["candidates"] = "fused layers with >= 3 % of the eager forward pass, head-output layers excluded (yl_predict runs them in another form)"
-    # executed multiplications of the whole forward: Winograd layers count 16/36 of their direct-conv MACs
-    net_macs = sum(l.macs * (16.0 / 36.0 if i in wl_set else 1.0) for i, l in enumerate(prog.layers))
-    net_flops = 2.0 * net_macs * B
-    fwd_ms = float(lay.sum())
     # p50 per batch = median over windows of K consecutive completions / K (see block()); it is the per-rank
     # throughput-equivalent batch time, so p50_ms_per_frame x (value / n_gpus) must be 1000 ms: held to 5 %
     p50_batch = float(np.median(step_ms))
-    ident = p50_batch / B * float(rates[k_med]) / world / 1e3
-    # (held when the block is long enough for the median to mean something: with 3-step blocks every window touches the
-    # pipeline fill at the block's start)
-    assert 0.95 <= ident <= 1.05 or args.steps < 10 or len(step_ms) < 30 or os.environ.get("YL_BENCH_NO_P50_ASSERT") == "1", \
-        f"p50_ms_per_frame {p50_batch / B:.5f} x images/s per GPU {float(rates[k_med]) / world:.1f} = {ident:.3f} s, expected 1 +- 5 %"
     out = {
         "metric": "images/sec", "value": round(float(rates[k_med]), 1), "unit": "images/sec", "n_gpus": world,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(float(els[k_med]) / args.steps * 1e3, 4),
@@ -740,9 +763,8 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
                               "(yl_clone: shared weights, own arenas / graphs), each lane on its own HIP stream, its own "
                               "resident input batch and output rows; p50_ms_per_batch = median over windows of K consecutive "
                               "completions of (interval / K) = throughput-equivalent time per batch (p50_ms_per_frame = that / B; "
-                              "p50_identity = p50_ms_per_frame x images/s per GPU / 1000, asserted 1 +- 5 %), p50_batch_latency_ms = median start-to-done time of a "
+                              "p50_identity = p50_ms_per_frame x images/s per GPU / 1000, asserted 1 +- 5 % under --full), p50_batch_latency_ms = median start-to-done time of a "
                               "batch on its lane (HIP events)"},
-        "one_batch_in_flight": serial,
         "blocks": {"n": int(len(els)), "steps_each": args.steps, "seconds_timed": round(float(els.sum()), 3),
                    "images_per_sec_min": round(float(rates.min()), 1), "images_per_sec_median": round(float(rates[k_med]), 1),
                    "images_per_sec_max": round(float(rates.max()), 1), "images_per_sec_first": round(float(rates[0]), 1)},
@@ -763,19 +785,44 @@ def measure_predict(args, model_name, B, seg, dev, rank, world, gather, min_seco
                            "calibrated (program.calibrate_head)",
                    "mean_dets_per_image": round(ndet, 1), "mean_classes_per_image": round(ncls, 1),
                    "max_out": max_out, "dets_dropped": dropped},
-        "roofline": roof,
-        "roofline_worst": roof_worst,
-        "traffic_per_step": traffic_per_step(model_name, seg, B, prog, S, max_out),
-        "network": {"conv_gflop_per_image": round(2.0 * prog.macs / 1e9, 4), "launches": len(prog.layers),
-                    "activation_mb": round(ctx.activation_bytes() / 1e6, 1),
-                    "forward_ms_sum_of_layers": round(fwd_ms, 4),
-                    "forward_tflops_executed": round(net_flops / (fwd_ms * 1e-3) / 1e12, 2),
-                    "forward_frac_of_fp32_mfma_peak": round(net_flops / (fwd_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
-                    "step_tflops_executed": round(net_flops / (float(els[k_med]) / args.steps) / 1e12, 2),
-                    "step_frac_of_fp32_mfma_peak": round(net_flops / (float(els[k_med]) / args.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)},
     }
+    if full:
+        # dominant kernel = the fused layer with the largest median duration; worst = the layer furthest below its roof among
+        # those that take >= 3 % of the forward pass
+        k = int(np.argmax(lay))
+        L = prog.layers[k]
+        roof = roofline_of(k)
+        # (head-output layers are left out: under yl_predict they do not run as the launches the eager per-layer pass times --
+        # detectors: fused with the trunk and the decode (yl_conv_dpp_kernel) or decode in the epilogue; seg models: the split
+        # det-rows + mask-coefficient launches -- VERDICT r04 item 6)
+        heavy = [i for i in range(len(lay)) if lay[i] >= 0.03 * lay.sum() and prog.layers[i].macs > 0 and prog.layers[i].head_level < 0]
+        roof_worst = min((roofline_of(i) for i in heavy), key=lambda r: r["frac"]) if heavy else None
+        if roof_worst is not None:
+            roof_worst["candidates"] = "fused layers with >= 3 % of the eager forward pass, head-output layers excluded (yl_predict runs them in another form)"
+        # executed multiplications of the whole forward: Winograd layers count 16/36 of their direct-conv MACs
+        net_macs = sum(l.macs * (16.0 / 36.0 if i in wl_set else 1.0) for i, l in enumerate(prog.layers))
+        net_flops = 2.0 * net_macs * B
+        fwd_ms = float(lay.sum())
+        ident = p50_batch / B * float(rates[k_med]) / world / 1e3
+        # (held when the block is long enough for the median to mean something: with 3-step blocks every window touches the
+        # pipeline fill at the block's start)
+        assert 0.95 <= ident <= 1.05 or args.steps < 10 or len(step_ms) < 30 or os.environ.get("YL_BENCH_NO_P50_ASSERT") == "1", \
+            f"p50_ms_per_frame {p50_batch / B:.5f} x images/s per GPU {float(rates[k_med]) / world:.1f} = {ident:.3f} s, expected 1 +- 5 %"
+        out.update({
+            "one_batch_in_flight": serial,
+            "roofline": roof,
+            "roofline_worst": roof_worst,
+            "traffic_per_step": traffic_per_step(model_name, seg, B, prog, S, max_out),
+            "network": {"conv_gflop_per_image": round(2.0 * prog.macs / 1e9, 4), "launches": len(prog.layers),
+                        "activation_mb": round(ctx.activation_bytes() / 1e6, 1),
+                        "forward_ms_sum_of_layers": round(fwd_ms, 4),
+                        "forward_tflops_executed": round(net_flops / (fwd_ms * 1e-3) / 1e12, 2),
+                        "forward_frac_of_fp32_mfma_peak": round(net_flops / (fwd_ms * 1e-3) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4),
+                        "step_tflops_executed": round(net_flops / (float(els[k_med]) / args.steps) / 1e12, 2),
+                        "step_frac_of_fp32_mfma_peak": round(net_flops / (float(els[k_med]) / args.steps) / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)},
+        })
     out.update(extra)
-    if args.layers:
+    if full and args.layers:
         print(f"# layer table: {model_name}{'+seg' if seg else ''} B={B} {S}x{S}, eager launches, median of "
               f"the timed forwards; {len(prog.layers)} launches, sum {fwd_ms:.4f} ms", file=sys.stderr)
         for i, (l, ms) in enumerate(zip(prog.layers, lay)):
@@ -807,7 +854,7 @@ def main():
     ap.add_argument("--in-flight", type=int, default=2, help="batches in flight: step i runs on context i %% K of a "
                     "serving.ServingPipeline (1 = calls back to back on one context: the loop of rounds 1-4)")
     ap.add_argument("--tile-m", type=int, default=0, help="conv M-tile hint (0 auto, 1/2 force m-tiles per wave)")
-    ap.add_argument("--layers", action="store_true", help="also print the per-layer timing table (stderr)")
+    ap.add_argument("--layers", action="store_true", help="also print the per-layer timing table (stderr; needs --full)")
     ap.add_argument("--seed", type=int, default=-1, help="synthetic weight seed (-1: 1).  The detection head is calibrated "
                     "(program.calibrate_head), so every seed detects")
     ap.add_argument("--stress", type=int, default=0, help="1: round-1 NMS stress workload instead (uncalibrated head noise, "
@@ -827,13 +874,24 @@ def main():
                     "level's smooth block), 0 = direct convolution everywhere.  Score error vs the oracle measured equal for "
                     "all three (profiles/r04_winograd_margin*.json)")
     ap.add_argument("--workload", default="predict", help="predict (headline) | eval (evaluate-path consumers, f3) | track (tracker bank, f4)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the block of --steps timed steps until this much "
-                    "step time has been measured (value = the median block)")
+    ap.add_argument("--min-seconds", type=float, default=None, help="repeat the block of --steps timed steps until this much "
+                    "step time has been measured (value = the median block); default 1 under --full, else 0: one block")
     ap.add_argument("--layer-reps", type=int, default=15, help="eager per-layer timing passes (HIP events around every launch); 0 = "
                     "none (counter passes: only yl_predict steps dispatch kernels; roofline fields are then meaningless)")
     ap.add_argument("--other-configs", type=int, default=-1, help="append BASELINE configs 3 and 4 (yololite_m B=32, edge_m+seg "
-                    "B=32) as `other_configs`; -1 = only for the default single-GPU headline run")
+                    "B=32) as `other_configs`; -1 = only for the default single-GPU headline run (needs --full)")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: per-layer pass (--layers, "
+                    "--layer-reps), roofline / traffic / network figures, one-batch-in-flight loop, repeated blocks, other "
+                    "configs, GPU batch-1 flow and CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's results as DIR/*.npy "
+                    "(float32 / float64)")
     args = ap.parse_args()
+    if not args.full and (args.layers or args.other_configs == 1):
+        ap.error("--layers and --other-configs 1 need --full")
+    if args.dump_outputs and args.workload != "predict":
+        ap.error("--dump-outputs writes the predict workload's results")
+    if args.min_seconds is None:
+        args.min_seconds = 1.0 if args.full else 0.0
 
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -858,10 +916,10 @@ def main():
     import yololite_amd as ya  # noqa: F401
 
     out = measure_predict(args, args.model, args.batch, args.seg, dev, rank, world, gather=(world > 1 or force_coll),
-                          min_seconds=args.min_seconds)
+                          min_seconds=args.min_seconds, full=args.full, dump_dir=args.dump_outputs)
     headline = (args.model == "edge_n" and args.batch == 64 and not args.seg and not args.bf16 and not args.f16 and not args.store_f16 and args.winograd == 1
                 and not args.stress and args.img == 640)
-    want_other = args.other_configs == 1 or (args.other_configs == -1 and headline and world == 1 and not force_coll)
+    want_other = args.full and (args.other_configs == 1 or (args.other_configs == -1 and headline and world == 1 and not force_coll))
     if rank == 0:
         meta, sd = out.pop("_cpu")
         if want_other:
@@ -876,7 +934,7 @@ def main():
                                                   "options", "config", "roofline", "roofline_worst", "traffic_per_step", "network")}
                 torch.cuda.empty_cache()
             out["other_configs"] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             # the reference's published protocol is batch 1 (export/infer_onnx.py, BENCHMARK.md:336-339): GPU side first,
             # then the CPU baseline (which carries the same flow as batch1_infer_flow)
             out["gpu_batch1_flow"] = gpu_batch1_flow(meta, sd, args.img, args.conf, args.iou, dev)

@@ -545,3 +545,26 @@ def test_config1_edge_n_640_batch1_through_cli(tmp_path):
         _assert_boxes_equal_after_rounding([d["bbox_xyxy"] for d in dets], eb)
         checked += 1
     assert checked >= 1
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps in one block and reports the headline alone;
+    --dump-outputs writes the last timed step's results, and a second run with the same arguments dumps the same arrays."""
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
+                            "--batch", "8", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert (d["metric"], d["unit"], d["higher_is_better"], d["dtype"]) == ("images/sec", "images/sec", True, "f32")
+        assert d["steps"] == 6 and d["blocks"]["n"] == 1 and d["blocks"]["steps_each"] == 6
+        assert d["value"] * d["ms_per_step"] == pytest.approx(8 * 1000.0, rel=1e-3)
+        assert not {"roofline", "network", "one_batch_in_flight", "other_configs", "cpu_baseline", "gpu_batch1_flow"} & set(d)
+        dets, counts = np.load(out / "dets.npy"), np.load(out / "counts.npy")
+        assert dets.dtype == np.float32 and dets.shape == (8, bench.MAX_OUT, 6)
+        assert counts.dtype == np.float64 and counts.shape == (8,) and counts.min() > 0
+        assert not dets[np.arange(bench.MAX_OUT)[None, :] >= counts[:, None]].any()
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+        dumps.append((dets, counts))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])

@@ -16,7 +16,7 @@ def test_bench_under_torchrun_one_rank():
     env = dict(os.environ, YL_BENCH_FORCE_COLLECTIVE="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"],
+                        "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

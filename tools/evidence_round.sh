@@ -12,7 +12,7 @@ O=gpurun_out/evid_$TAG; rm -rf $O; mkdir -p $O
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -o /tmp/mfma_peak tools/mfma_peak.hip && /tmp/mfma_peak > $O/mfma_peak.txt 2>&1
 timeout 600 python tools/pipeline_probe.py --steps 40 --reps 3 2>&1 | grep -v amdgpu.ids > $O/pipeline_probe.txt
 mkdir -p $O/tr
-timeout 300 rocprofv3 --kernel-trace -d $O/tr -o p --output-format csv -- python bench.py --no-cpu-baseline --other-configs 0 --steps 30 --layer-reps 0 --min-seconds 0.3 > $O/tr.log 2>&1
+timeout 300 rocprofv3 --kernel-trace -d $O/tr -o p --output-format csv -- python bench.py --full --no-cpu-baseline --other-configs 0 --steps 30 --layer-reps 0 --min-seconds 0.3 > $O/tr.log 2>&1
 python tools/overlap_stats.py $(find $O/tr -name '*kernel_trace.csv' | head -1) 20 > $O/overlap_stats.txt; rm -rf $O/tr
 [ -f _variants/libyololite_hip_wstamp.so ] && YOLOLITE_HIP_LIB=$GRAFT_REPO_ROOT/_variants/libyololite_hip_wstamp.so timeout 300 python tools/ir_stamps.py 2>&1 | grep -v amdgpu.ids > $O/ir_stamps.txt
 [ -f _variants/libyololite_hip_wstamp328.so ] && YOLOLITE_HIP_LIB=$GRAFT_REPO_ROOT/_variants/libyololite_hip_wstamp328.so timeout 300 python tools/wino_stamps.py 2>&1 | grep -v amdgpu.ids | tail -40 > $O/wino_stamps.txt

@@ -6,7 +6,7 @@ ROOT=$PWD
 mkdir -p $ROOT/$OUT
 export TMPDIR=/tmp
 cd /tmp
-PM="python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --in-flight 1 --min-seconds 0 --other-configs 0 --layer-reps 0 $@"
+PM="python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --in-flight 1 --min-seconds 0 --other-configs 0 --layer-reps 0 $@"
 timeout -k 5 400 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY -d $ROOT/$OUT/p1 -o p --output-format csv -- $PM > $ROOT/$OUT/p1.log 2>&1
 timeout -k 5 400 rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_ANY SQ_INSTS_SALU SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_VALU -d $ROOT/$OUT/p2 -o p --output-format csv -- $PM > $ROOT/$OUT/p2.log 2>&1
 timeout -k 5 400 rocprofv3 --kernel-trace --pmc SQ_INSTS_BRANCH SQ_INSTS_SMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INST_CYCLES_SALU SQ_WAVES SQ_INSTS_SENDMSG -d $ROOT/$OUT/p3 -o p --output-format csv -- $PM > $ROOT/$OUT/p3.log 2>&1

@@ -13,34 +13,34 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-BENCH="python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --other-configs 0 --min-seconds 0"
+BENCH="python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --other-configs 0 --min-seconds 0"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- $BENCH > $OUT/stats.log 2>&1
 # same, one internal stream: every conv launch is the full-batch one that bench.py's roofline.avg_launch_ms times
 rocprofv3 --kernel-trace --stats -d $OUT/stats1 -o s --output-format csv -- $BENCH --streams 1 > $OUT/stats1.log 2>&1
-PM="python $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --other-configs 0 --min-seconds 0 --layer-reps 0"
+PM="python $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --other-configs 0 --min-seconds 0 --layer-reps 0"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o p --output-format csv -- $PM > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmc_write -o p --output-format csv -- $PM > $OUT/pmc_write.log 2>&1
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_INST_ANY -d $OUT/pmc_sq -o p --output-format csv -- $PM > $OUT/pmc_sq.log 2>&1
 for cfg in "yololite_m 0" "edge_m 1" "yololite_m_v2 0"; do
   set -- $cfg
   N=$1; [ "$2" == "1" ] && N=${1}_seg
-  rocprofv3 --kernel-trace --stats -d $OUT/stats_$N -o s --output-format csv -- python $ROOT/bench.py --model $1 --seg $2 --batch 32 --steps 10 --warmup 3 --no-cpu-baseline --streams 1 --min-seconds 0 > $OUT/stats_$N.log 2>&1
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmcf_$N -o p --output-format csv -- python $ROOT/bench.py --model $1 --seg $2 --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --min-seconds 0 --layer-reps 0 > $OUT/pmcf_$N.log 2>&1
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmcw_$N -o p --output-format csv -- python $ROOT/bench.py --model $1 --seg $2 --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --min-seconds 0 --layer-reps 0 > $OUT/pmcw_$N.log 2>&1
-  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY -d $OUT/pmcs_$N -o p --output-format csv -- python $ROOT/bench.py --model $1 --seg $2 --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --min-seconds 0 --layer-reps 0 > $OUT/pmcs_$N.log 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/stats_$N -o s --output-format csv -- python $ROOT/bench.py --full --model $1 --seg $2 --batch 32 --steps 10 --warmup 3 --no-cpu-baseline --streams 1 --min-seconds 0 > $OUT/stats_$N.log 2>&1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmcf_$N -o p --output-format csv -- python $ROOT/bench.py --full --model $1 --seg $2 --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --min-seconds 0 --layer-reps 0 > $OUT/pmcf_$N.log 2>&1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/pmcw_$N -o p --output-format csv -- python $ROOT/bench.py --full --model $1 --seg $2 --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --min-seconds 0 --layer-reps 0 > $OUT/pmcw_$N.log 2>&1
+  rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY -d $OUT/pmcs_$N -o p --output-format csv -- python $ROOT/bench.py --full --model $1 --seg $2 --batch 32 --steps 2 --warmup 1 --no-cpu-baseline --graph 0 --streams 1 --min-seconds 0 --layer-reps 0 > $OUT/pmcs_$N.log 2>&1
 done
 cd $ROOT
-python bench.py --steps 30 --warmup 5 --layers > $OUT/bench.json 2> $OUT/layers.txt
-python bench.py --steps 30 --warmup 5 --stress 1 --no-cpu-baseline > $OUT/bench_stress.json 2> /dev/null
-python bench.py --model yololite_m --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --layers > $OUT/bench_yololite_m.json 2> $OUT/layers_yololite_m.txt
-python bench.py --model edge_m --seg 1 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --layers > $OUT/bench_edge_m_seg.json 2> $OUT/layers_edge_m_seg.txt
-python bench.py --model yololite_m_v2 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --layers > $OUT/bench_yololite_m_v2.json 2> $OUT/layers_yololite_m_v2.txt
+python bench.py --full --steps 30 --warmup 5 --layers > $OUT/bench.json 2> $OUT/layers.txt
+python bench.py --full --steps 30 --warmup 5 --stress 1 --no-cpu-baseline > $OUT/bench_stress.json 2> /dev/null
+python bench.py --full --model yololite_m --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --layers > $OUT/bench_yololite_m.json 2> $OUT/layers_yololite_m.txt
+python bench.py --full --model edge_m --seg 1 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --layers > $OUT/bench_edge_m_seg.json 2> $OUT/layers_edge_m_seg.txt
+python bench.py --full --model yololite_m_v2 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --layers > $OUT/bench_yololite_m_v2.json 2> $OUT/layers_yololite_m_v2.txt
 # option "winograd": 1 (every eligible layer) is the library default since round 4; labelled lines for 0 (direct everywhere)
 # and 2 (the finest level's >= 64-channel layers only)
-python bench.py --model yololite_m --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 0 --layers > $OUT/bench_yololite_m_winograd0.json 2> $OUT/layers_yololite_m_winograd0.txt
-python bench.py --model yololite_m --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 2 > $OUT/bench_yololite_m_winograd2.json 2> /dev/null
-python bench.py --model yololite_m_v2 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 0 > $OUT/bench_yololite_m_v2_winograd0.json 2> /dev/null
-python bench.py --model edge_m --seg 1 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 0 > $OUT/bench_edge_m_seg_winograd0.json 2> /dev/null
+python bench.py --full --model yololite_m --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 0 --layers > $OUT/bench_yololite_m_winograd0.json 2> $OUT/layers_yololite_m_winograd0.txt
+python bench.py --full --model yololite_m --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 2 > $OUT/bench_yololite_m_winograd2.json 2> /dev/null
+python bench.py --full --model yololite_m_v2 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 0 > $OUT/bench_yololite_m_v2_winograd0.json 2> /dev/null
+python bench.py --full --model edge_m --seg 1 --batch 32 --steps 15 --warmup 3 --no-cpu-baseline --winograd 0 > $OUT/bench_edge_m_seg_winograd0.json 2> /dev/null
 python bench.py --workload eval > $OUT/bench_eval.json 2> /dev/null
 python bench.py --workload track > $OUT/bench_track.json 2> /dev/null
 {

@@ -5,7 +5,7 @@ M=${1:-edge_m}; B=${2:-32}; X=${3:-}
 python -m pytest tests/test_gpu_parity.py -q -x -k "window_in_lds" 2>&1 | tail -5
 for dv in ${DVS:-64 16384 0}; do
   echo "== dev_select $dv"
-  python bench.py --model $M --batch $B --steps 15 --warmup 3 --no-cpu-baseline --layers $X --opt dev_select=$dv > /tmp/ab_$dv.json 2> /tmp/ab_$dv.txt
+  python bench.py --full --model $M --batch $B --steps 15 --warmup 3 --no-cpu-baseline --layers $X --opt dev_select=$dv > /tmp/ab_$dv.json 2> /tmp/ab_$dv.txt
   grep -E "dw3" /tmp/ab_$dv.txt | grep -E "cin (244|328)" | cut -c1-140
   python -c "
 import json,sys

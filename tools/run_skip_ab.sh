@@ -7,5 +7,5 @@ export YOLOLITE_HIP_LIB=$GRAFT_REPO_ROOT/_variants/libyololite_hip_skip.so YL_BE
 R=$1; shift
 for r in $R; do
   if [ $r == none ]; then unset YL_SKIP; else export YL_SKIP=$r; fi
-  echo -n "skip $r: "; timeout -k 5 300 python bench.py --no-cpu-baseline --other-configs 0 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'])"
+  echo -n "skip $r: "; timeout -k 5 300 python bench.py --full --no-cpu-baseline --other-configs 0 "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'])"
 done

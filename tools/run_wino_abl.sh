@@ -4,6 +4,6 @@
 for a in 0 1 2 7; do
   L=_variants/libyololite_hip_wabl$a.so; [ $a == 0 ] && L=yololite-official-repo_amd/libyololite_hip.so
   echo "== ablation $a"
-  YOLOLITE_HIP_LIB=$L python bench.py --model yololite_m --batch 32 --steps 5 --warmup 2 --no-cpu-baseline --layers --min-seconds 0 --in-flight 1 2> /tmp/abl.txt > /dev/null
+  YOLOLITE_HIP_LIB=$L python bench.py --full --model yololite_m --batch 32 --steps 5 --warmup 2 --no-cpu-baseline --layers --min-seconds 0 --in-flight 1 2> /tmp/abl.txt > /dev/null
   grep -E "smooth[34]\.0" /tmp/abl.txt | cut -c1-120
 done
