@@ -389,6 +389,11 @@ void plan_slots(yl_ctx* c, bool reuse) {
   c->arena_unit = peak;
 }
 
+// bytes of detection level l for B images
+size_t level_bytes(const yl_ctx* c, int l, int B) {
+  return (size_t)B * c->level_A[l] * c->level_S[l] * c->level_S[l] * c->E * sizeof(float);
+}
+
 // number of batch chunks a job of B images is split into (submit / walk_plan)
 int chunks_for(const yl_ctx* c, int B) {
   if (c->opt_time_split) return 1;          // the infer / post split is defined on ONE stream
@@ -437,30 +442,52 @@ yl_status ensure_act(yl_ctx* c, int B, int n) {
     free_act(c);                                             // also drops the cached graphs (addresses change)
     c->plan_reuse = reuse;
     plan_slots(c, reuse);
+    // The arenas and pinned slots carry 256 spare bytes and start out as zeros (0xFF bytes under YL_DEV_POISON).  No kernel
+    // needs either: the channel tail of a tensor's last k-block is masked in every conv kernel (those lanes load zeros, not the
+    // next pixel's channels), so a result depends on nothing but its own image -- the isolation tests fill every byte here
+    // with NaN and compare bitwise.
+    const int fill = (c->opt_dev & YL_DEV_POISON) ? 0xFF : 0;
     for (int i = 0; i < newn; ++i) {
-      // + 256 spare bytes, and the arena starts out as zeros: the kernels that read through buffer descriptors do not mask the
-      // channel tail of a tensor's last k-block -- those lanes read up to 48 bytes behind the pixel (the next pixel, the next slot,
-      // at the very end the spare bytes) and meet zero weights; 0 x garbage must not be 0 x NaN on the first run after an allocation
       if (c->arena_unit) {
         HIPCHK(c, hipMalloc((void**)&c->arena[i], c->arena_unit * (size_t)capi[i] + 256));
-        HIPCHK(c, hipMemset(c->arena[i], 0, c->arena_unit * (size_t)capi[i] + 256));
+        HIPCHK(c, hipMemset(c->arena[i], fill, c->arena_unit * (size_t)capi[i] + 256));
       }
-      if (c->se_unit) HIPCHK(c, hipMalloc((void**)&c->se_scratch[i], c->se_unit * sizeof(float) * (size_t)capi[i]));
+      if (c->se_unit) {
+        HIPCHK(c, hipMalloc((void**)&c->se_scratch[i], c->se_unit * sizeof(float) * (size_t)capi[i]));
+        if (fill) HIPCHK(c, hipMemset(c->se_scratch[i], fill, c->se_unit * sizeof(float) * (size_t)capi[i]));
+      }
       c->arena_capi[i] = capi[i];
     }
     for (auto& s : c->slots)
       if (s.pinned) {
         HIPCHK(c, hipMalloc((void**)&s.pin, s.sz * (size_t)newB + 256));
-        HIPCHK(c, hipMemset(s.pin, 0, s.sz * (size_t)newB + 256));
+        HIPCHK(c, hipMemset(s.pin, fill, s.sz * (size_t)newB + 256));
       }
-    for (int l = 0; l < c->L; ++l)
-      HIPCHK(c, hipMalloc((void**)&c->level_buf[l],
-                          (size_t)newB * c->level_A[l] * c->level_S[l] * c->level_S[l] * c->E * sizeof(float)));
+    for (int l = 0; l < c->L; ++l) {
+      HIPCHK(c, hipMalloc((void**)&c->level_buf[l], level_bytes(c, l, newB)));
+      if (fill) HIPCHK(c, hipMemset(c->level_buf[l], fill, level_bytes(c, l, newB)));
+    }
     c->cap_batch = newB; c->arena_n = newn; c->arena_cap = newcap;
   }
   c->plan_n = n; c->plan_cap = cap;
   for (int i = 0; i <= n; ++i) c->plan_b0[i] = b0s[i];
   c->act_batch = B;
+  return YL_OK;
+}
+
+// YL_DEV_POISON: refill every activation buffer ensure_act allocated with 0xFF bytes on the call's stream, ahead of the call's
+// first launch (the chunk streams and side lanes fork from `st` after this), so that no call sees what an earlier one wrote.
+// Float / fp16 storage only: the post-processing workspaces (counts, indices, NMS keys) are never poisoned.
+yl_status poison_act(yl_ctx* c, hipStream_t st) {
+  if (!(c->opt_dev & YL_DEV_POISON)) return YL_OK;
+  for (int i = 0; i < c->arena_n; ++i) {
+    if (c->arena[i]) HIPCHK(c, hipMemsetAsync(c->arena[i], 0xFF, c->arena_unit * (size_t)c->arena_capi[i] + 256, st));
+    if (c->se_scratch[i]) HIPCHK(c, hipMemsetAsync(c->se_scratch[i], 0xFF, c->se_unit * sizeof(float) * (size_t)c->arena_capi[i], st));
+  }
+  for (auto& s : c->slots)
+    if (s.pinned && s.pin) HIPCHK(c, hipMemsetAsync(s.pin, 0xFF, s.sz * (size_t)c->cap_batch + 256, st));
+  for (int l = 0; l < c->L; ++l)
+    if (c->level_buf[l]) HIPCHK(c, hipMemsetAsync(c->level_buf[l], 0xFF, level_bytes(c, l, c->cap_batch), st));
   return YL_OK;
 }
 
@@ -1191,16 +1218,16 @@ yl_status submit(yl_ctx* c, const Job& j, hipStream_t st, bool allow_graph = tru
     return walk_plan(c, j, st, n, segs, nseg, [&](int g, int i, int b0, int bn, hipStream_t ws) -> yl_status {
       return run_piece(c, j, segs[g], b0, bn, ws, i);
     });
-  std::vector<unsigned char> key(sizeof(Job) + sizeof(yl_post_cfg) + 3 * sizeof(int), 0);
+  // every option that shapes the launch list is an int field of its own (no packed bit fields: "dev_select" uses the whole
+  // YL_DEV_MASK, and a flag packed beside it once made time_split 0 and 1 share a key -- the replay then indexed the exec list
+  // of another segment plan)
+  const int opts[] = {c->opt_streams, c->opt_lanes, c->opt_bf16, c->opt_fuse_decode, c->opt_batch_levels, c->opt_hybrid,
+                      c->opt_nms_groups, c->opt_winograd, c->opt_fuse_head, c->opt_tile_m, c->opt_dev, c->opt_time_split,
+                      c->opt_split_k};
+  std::vector<unsigned char> key(sizeof(Job) + sizeof(yl_post_cfg) + sizeof(opts), 0);
   memcpy(key.data(), &j, sizeof(Job));
   if (j.cfg) memcpy(key.data() + sizeof(Job), j.cfg, sizeof(yl_post_cfg));
-  const int optkey = c->opt_streams | (c->opt_lanes << 8) | ((c->opt_bf16 & 1) << 9) | ((c->opt_bf16 >> 1) << 25) | (c->opt_fuse_decode << 10) |
-                     (c->opt_batch_levels << 11) | ((c->opt_hybrid & 1) << 12) | (c->opt_nms_groups << 13) | ((c->opt_hybrid >> 1) << 24) |
-                     (c->opt_winograd << 17) | (c->opt_fuse_head << 19);
-  const int devkey = c->opt_dev | (c->opt_time_split << 16) | (c->opt_split_k << 17);
-  memcpy(key.data() + sizeof(Job) + sizeof(yl_post_cfg), &optkey, sizeof(int));
-  memcpy(key.data() + sizeof(Job) + sizeof(yl_post_cfg) + sizeof(int), &c->opt_tile_m, sizeof(int));
-  memcpy(key.data() + sizeof(Job) + sizeof(yl_post_cfg) + 2 * sizeof(int), &devkey, sizeof(int));
+  memcpy(key.data() + sizeof(Job) + sizeof(yl_post_cfg), opts, sizeof(opts));
   // the cfg POINTER is part of Job but not of the identity of the work: blank it in the key
   memset(key.data() + offsetof(Job, cfg), 0, sizeof(void*));
   yl_ctx::GraphEntry* ge = nullptr;
@@ -1724,7 +1751,7 @@ yl_status yl_set_option(yl_ctx* c, const char* name, int32_t value) {
   if (!strcmp(name, "tile_m")) { c->opt_tile_m = value; drop_graph(c); return YL_OK; }
   if (!strcmp(name, "streams")) { c->opt_streams = value < 1 ? 1 : (value > 4 ? 4 : value); drop_graph(c); return YL_OK; }
   if (!strcmp(name, "split_k")) { c->opt_split_k = value ? 1 : 0; drop_graph(c); return YL_OK; }
-  if (!strcmp(name, "dev_select")) { c->opt_dev = value & 0x3ffffff; drop_graph(c); return YL_OK; }
+  if (!strcmp(name, "dev_select")) { c->opt_dev = value & (int)YL_DEV_MASK; drop_graph(c); return YL_OK; }
   return fail(c, YL_ERR_INVALID, std::string("unknown option ") + name);
 }
 
@@ -1765,6 +1792,7 @@ static yl_status forward_impl(yl_ctx* c, const float* x, int B, float* const* le
   yl_status s = ensure_act(c, B, layer_ms ? 1 : chunks_for(c, B));
   if (s != YL_OK) return s;
   if (cfg && (s = ensure_post(c, B)) != YL_OK) return s;
+  if ((s = poison_act(c, st)) != YL_OK) return s;
   Job j;
   j.x = x; j.B = B; j.cfg = cfg; j.dets = dets; j.counts = counts; j.keep_idx = keep_idx;
   for (int l = 0; l < c->L; ++l) j.outs[l] = (level_out && level_out[l]) ? level_out[l] : c->level_buf[l];

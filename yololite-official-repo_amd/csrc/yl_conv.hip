@@ -631,7 +631,8 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
           }
         }
       }
-      // channel tail (c >= Cin): the packed 1x1 weights of those k slots are zero, no select needed
+      // channel tail (c >= Cin): stage_load gave those lanes the out-of-range offset, so the halo holds zeros there (never the
+      // next pixel's channels) and the packed 1x1 weights of those k slots are zero as well
       f32x4 xq[1];
       xq[0] = yl_actc(s, p.dw_act, dlo, dhi);
       const f32x4* wrow = wl + (size_t)kb * NT * 64 + lane;

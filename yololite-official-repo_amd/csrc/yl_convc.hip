@@ -305,7 +305,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
                 }
             }
             // B fragment of channel block kb: lane (kq = c8 & 3, pixel py*4 + 2*xh + j).  Blocks beyond KB (group
-            // tail) are not stored; channels beyond Cin inside a block meet zero 1x1 weights.
+            // tail) are not stored; channels beyond Cin inside a block were loaded from the zero buffer (load_half) and
+            // meet zero 1x1 weights.
             if (it == 2 && gi == 0) { asm volatile("" :: "v"(o[0].x), "v"(o[1].x)); DWC_STAMP(23 + 5 * h); }
             const int kb = 4 * g + 2 * h + (c8 >> 2);
             if (kb < KB) {
@@ -615,8 +616,9 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlCon
   const int Cin = p.Cin, H = p.H, W = p.W, OH = p.OH, OW = p.OW, N = p.N, NTtot = p.NTtot, KB = p.KB;
   const yl_act_t* const xin = p.x;
   // staging loads through a raw buffer descriptor (round 6, see yl_conv_dws_kernel): 32-bit byte offset per slot + scalar k-block
-  // offset, zeros outside the image from the hardware range check; the channel tail is not masked (the 1x1 weights of those k
-  // slots are zeros, the tap weights are clamped to the last channels, the arenas end in 256 spare bytes)
+  // offset, zeros outside the image from the hardware range check.  The channel tail of the last k-block stages the next
+  // pixel's channels (the tap weights are clamped to the last channels); its depthwise results are replaced by zeros before
+  // the 1x1 (see the k-loop), so nothing past the pixel reaches the output
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(p.x), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   constexpr unsigned OOB = 0x80000000u;
@@ -795,9 +797,10 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlCon
           }
         }
       }
+      // channel tail (c >= Cin): the staged halo holds the next pixel's channels there -- zeros into the MFMA (0 x inf / NaN
+      // would be NaN against the zero 1x1 weights of those k slots)
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) xq[mt] = yl_actc(xq[mt], dw_act, dlo, dhi);
-      // channel tail (c >= Cin): the packed 1x1 weights of those k slots are zero, no select needed
+      for (int mt = 0; mt < MT; ++mt) xq[mt] = yl_sel4(c < Cin, yl_actc(xq[mt], dw_act, dlo, dhi));
       if (WL) {
         const f32x4* wrow = wl + (size_t)kb * NTtot * 64 + lane;
 #pragma unroll
@@ -1640,7 +1643,9 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) xq[mt] = yl_actc(xq[mt], dw_act, dlo, dhi);
       WINO_STAMP(kb * 5 + 3);
-      // channel tail (c >= Cmid): the packed projection weights of those k slots are zero, no select needed
+      // channel tail (c >= Cmid): the packed projection weights of those k slots are zero, no select needed.  The slab channels
+      // there are computed from the block input with zero expansion weights and bias; that input is masked at C1 and the halo
+      // stays inside the tile's image (h_in), so they can only carry this image's own non-finite values, never a neighbour's
       // ---- P: projection
       f32x4 wq[NT];
       const f32x4* wrow = wpl + (size_t)buf * NT * 64 + lane;
@@ -1748,7 +1753,8 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
   const yl_act_t* const xin = p.x;
   // tap loads through a raw buffer descriptor (round 6, see yl_conv_dws_kernel): a 32-bit byte offset per tap fixed for the item +
   // a scalar k-block offset (the loop carried a select, a conditional add and a 64-bit add per tap); taps outside the image carry
-  // an out-of-range offset (zeros from the range check); the channel tail is not masked (its 1x1 weights are zeros)
+  // an out-of-range offset (zeros from the range check).  The channel tail of the last k-block loads the next pixel's channels
+  // (no per-tap mask in the loop); its depthwise results are replaced by zeros before the 1x1
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(xin), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);            // [2][S][GW][NT][64] float4
@@ -1871,7 +1877,7 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
             xq[0].x = fmaf(xt[tap].x, w.x, xq[0].x); xq[0].y = fmaf(xt[tap].y, w.y, xq[0].y);
             xq[0].z = fmaf(xt[tap].z, w.z, xq[0].z); xq[0].w = fmaf(xt[tap].w, w.w, xq[0].w);
           }
-          xq[0] = yl_actc(xq[0], dw_act, dlo, dhi);
+          xq[0] = yl_sel4(cc < Cin, yl_actc(xq[0], dw_act, dlo, dhi));   // channel tail: zeros, not the next pixel's channels
           if (kb + 1 < KB) fetch(xt, kb + 1);
 #pragma unroll
           for (int gw = 0; gw < GW; ++gw) {
@@ -2006,8 +2012,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
   }
   // Operand streams through raw buffer descriptors (as yl_conv_wino2_kernel, round 6): the lane's part of an address is a 32-bit
   // byte offset fixed for the item (window) or the launch (weights), the k-block part is scalar; lanes outside the image carry an
-  // out-of-range offset and the copy writes zeros.  The channel tail of the last k-block is not masked: those lanes copy the next
-  // pixel's first channels (the arenas end in 256 spare bytes), their tap weights here and their 1x1 weights are zeros.
+  // out-of-range offset and the copy writes zeros.  The channel tail of the last k-block copies the next pixel's first channels
+  // (the next image's behind an image's last pixel); make_b hands zeros to the MFMA for those lanes (0 x inf / NaN would be NaN).
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(xin), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
@@ -2050,7 +2056,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
       xq.x = fmaf(x.x, w.x, xq.x); xq.y = fmaf(x.y, w.y, xq.y);
       xq.z = fmaf(x.z, w.z, xq.z); xq.w = fmaf(x.w, w.w, xq.w);
     }
-    return yl_actc(xq, dw_act, dlo, dhi);
+    return yl_sel4(kb * 16 + 4 * kq < p.Cin, yl_actc(xq, dw_act, dlo, dhi));   // channel tail: zeros (see the window copy)
   };
 
   for (int item = band0 + slot, wi = 0; item < band1; item += per, ++wi) {   // (wi: the stamp builds' item counter)
@@ -2176,7 +2182,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
 #else
           for (int t = 0; t < 3; ++t) xn = yl_pk_fma4(tx[t], tw[t], xn);     // two v_pk_fma_f32 by name: the same fma per component
 #endif
-          if (c == 2) xn = yl_actc(xn, dw_act, dlo, dhi);
+          if (c == 2) xn = yl_sel4((kb + 1) * 16 + 4 * kq < p.Cin, yl_actc(xn, dw_act, dlo, dhi));
         }
         __builtin_amdgcn_sched_barrier(0);
         if (c < 4) WINO_STAMP(kb * 7 + 3 + c);
@@ -2257,8 +2263,8 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
   const yl_act_t* const xin = p.x;
   // staging loads through a raw buffer descriptor (round 6, as yl_conv_wino2_kernel): a 32-bit byte offset per slot fixed for the
   // item + a scalar k-block offset -- the loop carried 8 64-bit adds and 16 selects per k-block for its four loads; slots outside
-  // the image carry an out-of-range offset (the load returns zeros); the channel tail is not masked (tap weights and 1x1 weights
-  // of those channels are zeros, the arenas end in 256 spare bytes)
+  // the image carry an out-of-range offset (the load returns zeros).  The channel tail of the last k-block stages the next
+  // pixel's channels; its depthwise results are replaced by zeros before the 1x1 (0 x inf / NaN would be NaN)
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(xin), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   constexpr unsigned OOB = 0x80000000u;
@@ -2419,8 +2425,9 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
 #endif
             }
           }
-          xq[0] = yl_actc(xq[0], dw_act, dlo, dhi);
-          // channel tail (c >= Cin): the packed 1x1 weights of those k slots are zero (and the taps were copied from zeros)
+          // channel tail (c >= Cin): the staged halo holds the next pixel's channels there -- zeros into the MFMA (0 x inf / NaN
+          // would be NaN against the zero 1x1 weights of those k slots)
+          xq[0] = yl_sel4(kb * 16 + 4 * kq < Cin, yl_actc(xq[0], dw_act, dlo, dhi));
           const f32x4* wb = wl + (size_t)(buf * S + j) * NTW * 64 + lane;
 #pragma unroll
           for (int gw = 0; gw < GW; ++gw) {
@@ -2588,7 +2595,9 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
   // that the lane's part of every address -- the patch origin, which may lie one row and one column outside the image -- is ONE
   // non-negative 32-bit byte offset for the tile and the element / k-block part is a scalar offset; elements outside the image
   // take an out-of-range offset (one select each; the loop carried a select pair, a compare and a 64-bit add per element: 85
-  // vector instructions per k-block for 16 loads).  The channel tail is not masked (U is zero there, pack_wino).
+  // vector instructions per k-block for 16 loads).  Lanes of the channel tail of the last k-block take the out-of-range offset
+  // for every element (one select per k-block on the in-image mask): they would load the next pixel's channels, and U being
+  // zero there (pack_wino) does not make 0 x inf / NaN zero.
   const int borg = (W + 1) * Cin * (int)sizeof(yl_act_t);
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(xin) - borg), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)) + borg, 0x00020000);
@@ -2629,10 +2638,11 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
     const int vbase = pbase * (int)sizeof(yl_act_t) + borg;       // >= 0: the patch origin seen from the descriptor's base
     auto load_row = [&](int kb, int r, f32x4 (&dst)[16]) {
       if (!SH && !defined_YL_F16S) {
+        const unsigned inbk = kb * 16 + 4 * kq < Cin ? inb : 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int e = r * 4 + q;
-          dst[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, ((inb >> e) & 1u) ? vbase : (int)0x80000000u,
+          dst[e] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, ((inbk >> e) & 1u) ? vbase : (int)0x80000000u,
                                                                                  ((r * W + q) * Cin + kb * 16) * (int)sizeof(yl_act_t), 0));
         }
         return;
@@ -2840,9 +2850,9 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
   // Both operand streams go through raw buffer descriptors (round 6): the per-lane part of an address is ONE 32-bit byte
   // offset fixed for the whole item, the k-block part is a scalar offset -- no vector instruction in the loop computes an
   // address (the loop carried 14 64-bit adds and 8 selects for its ten requests).  Window lanes outside the image carry an
-  // offset beyond num_records: the hardware range check makes the copy write zeros.  The channel tail of the last k-block is
-  // not masked: those lanes copy the first channels of the next pixel (finite values; the context's arenas end in 256 spare
-  // bytes) and U is zero there (pack_wino pads with zeros), so the products are zeros as before.
+  // offset beyond num_records: the hardware range check makes the copy write zeros.  So do the lanes of the channel tail of
+  // the last k-block (one select per copy): they would copy the first channels of the next pixel -- the next image's behind
+  // an image's last pixel -- and U being zero there (pack_wino) does not make 0 x inf / NaN zero.
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(xin), 0, (int)((long)p.B * Hs * Ws * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
@@ -2869,7 +2879,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(Rl + (buf * MT + mt) * RM + wave * 64), 16,
-                                               (int)voff[mt], kb * 16 * (int)sizeof(yl_act_t), 0, 0);
+                                               kb * 16 + 4 * rkq < Cin ? (int)voff[mt] : (int)OOB, kb * 16 * (int)sizeof(yl_act_t), 0, 0);
   };
   // Parity: the loop below is unrolled by two so that the window buffer and the U register set of a block are compile-time
   // (LDS read offsets become immediates, no register renaming at the block's end).  Block kb uses buffer / set

@@ -115,7 +115,7 @@ __device__ __forceinline__ void yl_epi_generic(const YlConvP& p, f32x4 (&acc)[MT
 //            (which lane evaluates an expression does not change its bits): bit-identical.
 // The tie path (a wave-uniform branch, rare) is the first form's.
 __device__ __forceinline__ float yl_vmax(float a, float b) {   // v_max_f32 without the canonicalising self-max that fmaxf
-  float d;                                                     // emits in IEEE mode (logits are never NaN here)
+  float d;                                                     // emits in IEEE mode (NaN class logits are detected separately)
   asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
   return d;
 }
@@ -135,11 +135,13 @@ __device__ __forceinline__ void yl_epi_decode(const YlConvP& p, f32x4 (&acc)[MT]
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) v[nt] = BIASED ? acc[mt][nt] : acc[mt][nt] + yl_ld4(bias + (nt0 + nt) * 16 + 4 * kq);
     float lmax = 0.0f, cand = NINF;
+    bool cnan = false;                                        // a NaN class logit: score -inf (never passes `> conf`, as the reference's NaN)
     int first = 0x7fffffff;
     float cl[NT][4];                                          // class view of the row: everything else is -inf
     if (C > 1) {
       // ---- pass 1: largest / second largest class logit of the lane
       float m1 = NINF, m2 = NINF;
+      int hn = 0;                                             // a NaN class logit (v_max drops NaN operands)
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
@@ -151,11 +153,15 @@ __device__ __forceinline__ void yl_epi_decode(const YlConvP& p, f32x4 (&acc)[MT]
           if (!TIGHT || nt == 0) x = e >= rlo ? x : NINF;
           if (!TIGHT || nt >= NT - 2) x = e < rhi ? x : NINF;
           cl[nt][r] = x;
+          hn |= x != x;
           m2 = __builtin_amdgcn_fmed3f(x, m1, m2);
           m1 = yl_vmax(m1, x);
         }
       lmax = yl_vmax(m1, __shfl_xor(m1, 16, 64));
       lmax = yl_vmax(lmax, __shfl_xor(lmax, 32, 64));
+      hn |= __shfl_xor(hn, 16, 64);
+      hn |= __shfl_xor(hn, 32, 64);
+      cnan = hn != 0;
       // ---- pass 2: first class of the lane whose logit EQUALS the maximum (descending scan: the smallest survives)
       int fe = 0x7fffff00;
 #pragma unroll
@@ -209,7 +215,7 @@ __device__ __forceinline__ void yl_epi_decode(const YlConvP& p, f32x4 (&acc)[MT]
       first = min(first, __shfl_xor(first, 16, 64));
       first = min(first, __shfl_xor(first, 32, 64));
       ci = first;
-      score = obj * best;
+      score = cnan ? NINF : obj * best;
     } else if (C == 1 && p.dec_mode == YL_POST_FALLBACK) {
       score = obj * best;
     } else {

@@ -157,6 +157,13 @@ struct YlConvP {
 #define YL_DEV_DWL_ALL (1u << 15)      // ... yl_conv_dwl_kernel on every grid it supports (partial windows, few items: the bitwise test)
 #define YL_DEV_DPW_OFF (1u << 16)      // fused head launch: yl_conv_dpp_kernel (taps from L1/L2) instead of yl_conv_dpw_kernel (window in LDS)
 #define YL_DEV_K3W_OFF (1u << 17)     // small-channel dense 3x3: the Winograd / direct kernels instead of yl_conv_k3w_kernel (bitwise A/B)
+#define YL_DEV_POISON (1u << 18)      // workspace poison (isolation tests): activation storage is allocated as 0xFF bytes (a NaN in fp32
+                                      // and fp16) and refilled with them at the start of every forward / predict call; no kernel reads it
+#define YL_DEV_MASK 0x3ffffffu        // the bits "dev_select" keeps
+static_assert(YL_DEV_MASK <= 0x7fffffffu, "dev_select is stored in an int (and an int field of the graph key)");
+static_assert(((YL_DEV_DW_TILE_OFF | YL_DEV_PWS_OFF | YL_DEV_S2C_OFF | YL_DEV_DWC_ALL | YL_DEV_DWT_OFF | (3u << 5) | (3u << 7) |
+                YL_DEV_KXK_MT2 | YL_DEV_DWT_NOSPLIT | YL_DEV_WINO_V1 | (3u << 12) | YL_DEV_DWL_OFF | YL_DEV_DWL_ALL | YL_DEV_DPW_OFF |
+                YL_DEV_K3W_OFF | YL_DEV_POISON) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
 
 // squeeze-excite gate (yl_se.hip): fixed-order two-pass spatial mean + the two FCs + sigmoid
 struct YlSeP {

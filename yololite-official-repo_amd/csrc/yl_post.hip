@@ -98,9 +98,13 @@ __global__ __launch_bounds__(128) void yl_decode_score_kernel(YlLevels lv, int B
     // conf = sigmoid(max logit); the index can only differ from the logit arg-max when an EARLIER class
     // has a (slightly) smaller logit whose sigmoid rounds to the same float (saturation / <1 ulp):
     // only those candidates get their own sigmoid.  1-2 expf per candidate instead of C.
+    // A NaN class logit makes the reference's max NaN, and so its score: the candidate never passes `> conf`.  Its score
+    // here is -inf (what the fallback's min-side filter writes): the same outcome, and no NaN key for the NMS sort
     float lmax = row[5];
+    bool cnan = lmax != lmax;
     for (int c = 1; c < C; ++c) {
       const float l = row[5 + c];
+      cnan |= l != l;
       if (l > lmax) { lmax = l; ci = c; }
     }
     const float best = yl_sigmoid(lmax);
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(128) void yl_decode_score_kernel(YlLevels lv, int B
       const float l = row[5 + c];
       if ((wide || l >= band || l > 10.0f) && yl_sigmoid(l) == best) { ci = c; break; }
     }
-    score = obj * best;
+    score = cnan ? -INFINITY : obj * best;
   } else if (C == 1 && p.mode == YL_POST_FALLBACK) {
     score = obj * yl_sigmoid(row[5]);             // tools/infer.py:316-320
   } else {
