@@ -303,7 +303,9 @@ yl_status yl_set_option(yl_ctx* ctx, const char* name, int32_t value);
  * window-in-LDS form (yl_conv_dpw_kernel), 17: small-channel dense 3x3 layers without the window-in-LDS kernel
  * (yl_conv_k3w_kernel), 18: workspace poison for the isolation tests -- the activation arenas, pinned slots, squeeze-excite
  * scratch and level buffers are allocated filled with 0xFF bytes (a NaN in fp32 and fp16) instead of zeros and refilled
- * with them, on the call's stream, at the start of every yl_forward* / yl_predict call: no result may depend on them). */
+ * with them, on the call's stream, at the start of every yl_forward* / yl_predict call: no result may depend on them),
+ * 19: a UIB projection and the next block's 1x1 expansion as two launches instead of one chained launch
+ * (yl_conv_dwx_kernel).  Read-only: "chain_launches", the number of chained launches the context has enqueued. */
 yl_status yl_get_option(const yl_ctx* ctx, const char* name, int32_t* value);
 /* Host-side query, no device needed: would yl_create accept a fused inverted-residual block (yl_layer with c2 > 0:
  * 1x1 expand c_in -> c_mid, depthwise dw_k x dw_k stride dw_stride, 1x1 project c_mid -> c_out) producing an

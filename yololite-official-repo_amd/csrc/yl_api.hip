@@ -117,6 +117,7 @@ struct yl_ctx {
   int opt_split_k = 0; // depthwise -> 1x1 layers on <= 20x20 grids in the split-K form (yl_conv_dwt_kernel<.., SK = 4>): -9 % batch-1
                       // latency, -0.7 % throughput at B = 64 (measured, edge_n) -> off by default, the pip API turns it on
   int opt_dev = 0;    // developer kernel-selection word (YL_DEV_*, "dev_select"); rides in every YlConvP
+  int chain_launches = 0;   // yl_conv_dwx_kernel launches enqueued so far (yl_get_option "chain_launches", read-only)
   int opt_bf16 = 0;   // reduced-precision MFMA mode: 1 = conv / stem-block launches use the bf16-MFMA builds, 2 = the fp16-MFMA
                       // builds (fp32 storage, fp32 accumulate either way); 0 = fp32 (the parity path)
   // batch chunks run on `opt_streams` internal streams (fork/join around every call): the
@@ -329,6 +330,7 @@ size_t layer_group_end(const yl_ctx* c, size_t i, size_t lend) {
 // all of its layers' tensors at once): slot s is live from the group that produces it to the group of its last
 // consumer, inclusive; first-fit over the gaps of the live set.  reuse == false: every slot gets its own range.
 bool pair_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options);
+bool chain_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options);
 
 void plan_slots(yl_ctx* c, bool reuse) {
   const size_t NL = c->layers.size(), NS = c->slots.size();
@@ -341,7 +343,9 @@ void plan_slots(yl_ctx* c, bool reuse) {
     // over them (whatever the options say when the plan is made)
     // (also when the first layer of the pair is the LAST member of a level-batched run -- with "batch_levels"
     // 0 run_layers sees it alone and may fuse it with its successor)
-    if (pair_fusable(c, e - 1, NL, true)) e = e + 1;
+    // (the same for a projection with the next block's expansion chained behind it, yl_conv_dwx_kernel: the expanded
+    // tensor must not be placed over the projection's depthwise input or residual)
+    if (pair_fusable(c, e - 1, NL, true) || chain_fusable(c, e - 1, NL, true)) e = e + 1;
     for (size_t q = i; q < e; ++q) grp[q] = g;
     i = e;
   }
@@ -655,6 +659,30 @@ bool pair_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options) {
   return true;
 }
 
+// UIB projection -> the next block's expansion as ONE launch (yl_conv_dwx_kernel): layer i is a 1x1 conv with a stride-1
+// depthwise prologue (optional residual) writing slot S, layer i + 1 a plain 1x1 conv (no prologue, residual, upsample,
+// gate or head) reading S.  S is still written -- the next block reads it as its residual.  Options: fp32 mode, split-K
+// off (its form keeps the two launches), the automatic kernel choice, the depthwise -> 1x1 kernel and the chaining not
+// switched off
+bool chain_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options) {
+  if (!ignore_options && (c->opt_bf16 || c->opt_split_k || c->opt_tile_m || (c->opt_dev & (YL_DEV_CHAIN_OFF | YL_DEV_DWT_OFF))))
+    return false;
+  if (i + 1 >= lend) return false;
+  const DevLayer& T = c->layers[i];
+  const DevLayer& O = c->layers[i + 1];
+  const yl_layer& t = T.d; const yl_layer& o = O.d;
+  if (t.op != YL_OP_CONV || t.k != 1 || t.stride != 1 || t.dw_k <= 0 || t.dw_stride != 1 || t.c2 > 0 || t.c3 > 0 ||
+      t.head_level >= 0 || t.up_slot >= 0 || t.scale_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || t.out_slot < 0 ||
+      (t.res_slot >= 0 && t.act != YL_ACT_NONE))
+    return false;
+  if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.stride != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 ||
+      o.in_slot != t.out_slot || o.cin != t.cout || YL_SMOOTH(o.act) || o.res_slot >= 0 || o.up_slot >= 0 ||
+      o.scale_slot >= 0 || o.in_shift || o.out_slot < 0)
+    return false;
+  return T.in_h == T.out_h && T.in_w == T.out_w && O.in_h == T.out_h && O.in_w == T.out_w && O.out_h == T.out_h &&
+         O.out_w == T.out_w && yl_dwx_supported(t.cin, t.cout, t.dw_k, t.dw_stride, o.cout, T.out_h, T.out_w);
+}
+
 hipError_t conv_multi(const yl_ctx* c, const YlConvP* ps, int n, hipStream_t st) {
   switch (c->opt_bf16) {
     case 1: return yl_launch_conv_multi_bf16(ps, n, c->opt_tile_m, st);
@@ -760,6 +788,19 @@ yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* lev
       if (e != hipErrorNotSupported) {
         char b[256];
         snprintf(b, sizeof(b), "layers %zu..%zu fused launch failed: %s", i, i + 1, hipGetErrorString(e));
+        return fail(c, YL_ERR_HIP, b);
+      }
+    }
+    if (!evs && !lanes && gend == i + 1 && d.op == YL_OP_CONV && d.dw_k > 0 && chain_fusable(c, i, lend, false)) {
+      YlConvP pt, po;
+      params(i, pt);
+      params(i + 1, po);
+      pt.w3p = po.wp; pt.b3 = po.bias; pt.C3 = po.N; pt.act3 = po.act;
+      const hipError_t e = yl_launch_conv_dwx(pt, po.out, st);
+      if (e == hipSuccess) { ++c->chain_launches; i += 2; continue; }
+      if (e != hipErrorNotSupported) {
+        char b[256];
+        snprintf(b, sizeof(b), "layers %zu..%zu chained launch failed: %s", i, i + 1, hipGetErrorString(e));
         return fail(c, YL_ERR_HIP, b);
       }
     }
@@ -1761,7 +1802,8 @@ yl_status yl_get_option(const yl_ctx* c, const char* name, int32_t* value) {
       {"graph", c->opt_graph}, {"mfma_bf16", c->opt_bf16 == 1}, {"mfma_f16", c->opt_bf16 == 2}, {"store_f16", c->opt_bf16 == 3}, {"nms_groups", c->opt_nms_groups}, {"time_split", c->opt_time_split},
       {"pre_norm", c->opt_pre_norm}, {"reuse_slots", c->opt_reuse}, {"hybrid", c->opt_hybrid}, {"batch_levels", c->opt_batch_levels},
       {"fuse_decode", c->opt_fuse_decode}, {"fuse_head", c->opt_fuse_head}, {"winograd", c->opt_winograd}, {"lanes", c->opt_lanes},
-      {"tile_m", c->opt_tile_m}, {"streams", c->opt_streams}, {"dev_select", c->opt_dev}, {"split_k", c->opt_split_k}};
+      {"tile_m", c->opt_tile_m}, {"streams", c->opt_streams}, {"dev_select", c->opt_dev}, {"split_k", c->opt_split_k},
+      {"chain_launches", c->chain_launches}};
   for (const auto& t : tab)
     if (!strcmp(name, t.n)) { *value = t.v; return YL_OK; }
   return YL_ERR_INVALID;

@@ -583,6 +583,61 @@ hipError_t yl_launch_conv_pwt_multi(const YlConvP* ps, int n, hipStream_t st) {
 
 hipError_t yl_launch_conv_pwt(const YlConvP& p, hipStream_t st) { return yl_launch_conv_pwt_multi(&p, 1, st); }
 
+// Chained tail of yl_conv_dwx_kernel (see there): the projection's epilogue as yl_epi_fast (bias, clamp; every pixel of a
+// tile is valid, N == 16 NT), whose stored values are, lane for lane, the B fragments of k-block nt of the next layer's
+// 1x1 (channels 16 nt + 4 kq .. + 3 of pixel pl), then that 1x1 in chunks of CX n-tiles: k-blocks ascending, four k-steps
+// each, accumulators from zero, + bias, clamp -- the arithmetic of yl_conv_pwt_kernel.  Its A fragments come from L1/L2
+// through a buffer descriptor (lane offset in a VGPR, fragment offset as a constant), the next chunk's requested before
+// the current chunk's MFMAs; the expanded rows are stored the same way.
+template <int NT, int NX>
+__device__ __forceinline__ void yl_dwx_tail(const YlConvP& p, const f32x4 (&acc)[NT], size_t lin, int kq, int lane, float lo,
+                                            float hi, yl_act_t* const out3) {
+#if !YL_BF16
+  constexpr int CX = 2, NC = NX / CX;
+  static_assert(NX % CX == 0, "chained n-tiles come in chunks of CX");
+  const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w3p), 0, NT * NX * 1024, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ors =
+      __builtin_amdgcn_make_buffer_rsrc(out3, 0, (int)((long)p.B * p.OH * p.OW * NX * 64), 0x00020000);
+  f32x4 w[2][NT][CX];
+  auto wload = [&](int c, f32x4 (&d)[NT][CX]) {
+#pragma unroll
+    for (int kb = 0; kb < NT; ++kb)
+#pragma unroll
+      for (int j = 0; j < CX; ++j)
+        d[kb][j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane * 16 + (c * CX + j) * 1024, kb * NX * 1024, 0));
+  };
+  wload(0, w[0]);                                                    // in flight under the projection's stores
+  f32x4 hq[NT][1];
+  const size_t orow = lin * (size_t)p.N;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int n = nt * 16 + 4 * kq;
+    hq[nt][0] = yl_clamp4(acc[nt] + yl_ld4(p.bias + n), lo, hi);
+    yl_out4(p, orow + n, hq[nt][0]);
+  }
+  const float lo3 = (p.act3 == YL_ACT_RELU || p.act3 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
+  const float hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const int ob = (int)lin * (NX * 64) + kq * 16;                    // byte offset of the lane's first expanded quad
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    if (c + 1 < NC) wload(c + 1, w[(c + 1) & 1]);
+    f32x4 a[1][CX];
+#pragma unroll
+    for (int j = 0; j < CX; ++j) a[0][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kb = 0; kb < NT; ++kb) yl_mma_step<CX, 1>(w[c & 1][kb], hq[kb], a);
+#pragma unroll
+    for (int j = 0; j < CX; ++j) {
+      const f32x4 v = yl_clamp4(a[0][j] + yl_ld4(p.b3 + (c * CX + j) * 16 + 4 * kq), lo3, hi3);
+      __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, v), ors,
+                                             ob + (c * CX + j) * 64, 0, 0);
+    }
+  }
+#else
+  (void)p; (void)acc; (void)lin; (void)kq; (void)lane; (void)lo; (void)hi; (void)out3;
+#endif
+}
+
 // ------------------------------------------------------------------------------------------------
 // Wave-autonomous depthwise -> 1x1 convolution: the depthwise counterpart of yl_conv_pwt_kernel and the successor of
 // yl_conv_dwh_kernel (same per-wave algorithm: 4x4-pixel m-tiles, per 16-channel block the halo patch goes through
@@ -602,8 +657,9 @@ hipError_t yl_launch_conv_pwt(const YlConvP& p, hipStream_t st) { return yl_laun
 //        barrier per tile, buffers alternate) and wave w finishes n-tile w (+4): partials added in wave order 0..3, then
 //        the usual epilogue.  Chosen by the LAYER SHAPE only (never by the batch): results stay batch-invariant and
 //        bitwise repeatable, but are another fp32 summation order of the same products than SK = 1 / yl_conv_dwh_kernel.
-template <int NT, int DK, int DS, int MT, bool WL, int SK = 1>
-__global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlConvMulti mp) {
+//   NX   (yl_conv_dwx_kernel, fp32 unit only) n-tiles of the NEXT layer's plain 1x1, chained behind the epilogue: see there.
+template <int NT, int DK, int DS, int MT, bool WL, int SK, int NX>
+__device__ __forceinline__ void yl_dwt_body(const YlConvMulti& mp, yl_act_t* const out3) {
   YL_SELECT_PROBLEM_C(mp)
   constexpr int HPY = 3 * DS + DK, HPX = (4 * MT - 1) * DS + DK;     // halo patch rows / columns
   constexpr int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;            // row pitch in floats (see yl_conv_dwh_kernel)
@@ -751,7 +807,8 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlCon
     // the next block's plain 1x1 `pw_exp` behind this kernel's epilogue with both outputs written, for the five
     // `pw_proj` -> `pw_exp` pairs of edge_n's 20x20 stage: one-stream launch times at B = 64, 45.4 us chained against
     // 29.4 + 20.2 for the 5x5 pairs, 53.6 against 23.7 + 20.2 for the 3x3 pairs (one of them feeds 64 -> 480); headline
-    // unchanged at 38.8k with five launches fewer per chunk -- not kept.)
+    // unchanged at 38.8k with five launches fewer per chunk -- not kept then.  Round 7: yl_conv_dwx_kernel, the four 64 -> 192 / 256
+    // pairs only, the expansion's A fragments through a buffer descriptor with the next chunk in flight: 0.85x of the two launches.)
     for (int kb = kb0; kb < KB; kb += SK) {
       const bool more = kb + SK < KB;
       if (more) stage_load(kb + SK, stg);
@@ -829,6 +886,8 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlCon
         if (!pre_add && (p.res || p.up || YL_SMOOTH(p.act))) yl_epi_generic<1, 1>(p, one, px1, nt, kq);
         else yl_epi_fast<1, 1>(p, one, px1, nt, kq, lo, hi, true);
       }
+    } else if constexpr (NX > 0) {
+      yl_dwx_tail<NT, NX>(p, acc[0], px[0].lin, kq, lane, lo, hi, out3);
     } else {
       if (!pre_add && (p.res || p.up || YL_SMOOTH(p.act))) yl_epi_generic<NT, MT>(p, acc, px, 0, kq);
       else yl_epi_fast<NT, MT>(p, acc, px, 0, kq, lo, hi, true);
@@ -839,6 +898,11 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlCon
     if (tyi >= thn) { tyi -= thn; ++tb; }
     tb += sdb;
   }
+}
+
+template <int NT, int DK, int DS, int MT, bool WL, int SK = 1>
+__global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlConvMulti mp) {
+  yl_dwt_body<NT, DK, DS, MT, WL, SK, 0>(mp, nullptr);
 }
 
 template <int NT, int DK, int DS, int MT, bool WL, int SK = 1>
@@ -961,6 +1025,80 @@ hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st) {
   }
   return dwt_any(m, NT, st, two, wl, false);
 }
+
+#if !YL_BF16
+// ------------------------------------------------------------------------------------------------
+// UIB projection (depthwise DK x DK stride 1 -> 1x1 -> 64 channels, + residual) with the NEXT block's expansion (plain 1x1
+// 64 -> 16 NX, + ReLU) chained behind it in the same launch: edge_n's 20x20 stage, blocks.3.1-3.4 pw_proj + blocks.3.2-3.5
+// pw_exp.  Two launches before (yl_conv_dwt_kernel<4, DK, 1, 1, false, 1> + yl_conv_pwt_kernel<4, 1>), each bound by
+// latency and launch count, not by MFMA work or HBM.  The projection runs as in yl_conv_dwt_kernel (same
+// body: one 4x4 tile per wave, halo through LDS, 1x1 A fragments from L1/L2) and stores its 64-channel output as before --
+// the next block reads it as its residual; the accumulators of its epilogue are the B fragments of the expansion, which
+// then runs from registers (yl_dwx_tail): no LDS transpose, no halo, no pixel computed twice.  Bit-identical to the two
+// launches.  Only the shapes edge_n needs: Cin 192 / 256, N = 64, DK 3 / 5, NX = 12 / 16.
+template <int DK, int NX>
+__global__ __launch_bounds__(256, 3) void yl_conv_dwx_kernel(YlConvMulti mp, float* out3) {
+  yl_dwt_body<4, DK, 1, 1, false, 1, NX>(mp, out3);
+}
+
+template <int DK, int NX>
+static hipError_t dwx_go(YlConvMulti& m, float* out3, hipStream_t st, bool attr_only) {
+  if (attr_only)
+    return hipFuncSetAttribute((const void*)yl_conv_dwx_kernel<DK, NX>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+  constexpr int HPY = 3 + DK, HPX = 3 + DK;
+  constexpr int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
+  YlConvP& p = m.p[0];
+  const size_t lds = ((((size_t)(DK * DK + 1) * p.Cin + 3) & ~(size_t)3) + (size_t)4 * HPY * PITCHF) * 4;
+  const int res = yl_resident_blocks_n(yl_conv_dwx_kernel<DK, NX>, 256, lds);
+  // persistent workgroups as dwt_go: a multiple of 8 (XCD bands), at most one wave per tile
+  const long tiles = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
+  long g = ((long)res + 7) & ~7L;
+  const long cap = ((tiles + 3) / 4 + 7) & ~7L;
+  if (g > cap) g = cap;
+  if (g < 8) g = 8;
+  p.blk0 = 0; p.nblk = 0;
+  hipLaunchKernelGGL((yl_conv_dwx_kernel<DK, NX>), dim3((unsigned)g), dim3(256), lds, st, m, out3);
+  return hipGetLastError();
+}
+
+bool yl_dwx_supported(int cin, int cout, int dw_k, int dw_stride, int cout1, int oh, int ow) {
+  return (cin == 192 || cin == 256) && cout == 64 && (dw_k == 3 || dw_k == 5) && dw_stride == 1 && (cout1 == 192 || cout1 == 256) &&
+         (oh & 3) == 0 && (ow & 3) == 0;
+}
+
+// pd: the depthwise -> 1x1 projection layer with w3p / b3 / C3 / act3 of the plain 1x1 behind it, whose output is out3.
+// hipErrorNotSupported for every other shape or configuration (the two launches then run).
+hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st) {
+  const YlConvP& p = pd;
+  if (p.k != 1 || p.stride != 1 || p.C1 > 0 || p.up || p.scale || p.dec_boxes || p.ldo || p.in_shift || !p.w3p || !out3 ||
+      YL_SMOOTH(p.act) || YL_SMOOTH(p.act3) || (p.res && p.act != YL_ACT_NONE) || p.H != p.OH || p.W != p.OW ||
+      !yl_dwx_supported(p.Cin, p.N, p.dw_k, p.dw_stride, p.C3, p.OH, p.OW))
+    return hipErrorNotSupported;
+  // the two-launch form these replace: yl_conv_dwt_kernel, one wave per tile (split-K off), A fragments from L1/L2
+  if ((p.dev & (YL_DEV_DWT_OFF | YL_DEV_CHAIN_OFF)) || !(p.dev & YL_DEV_DWT_NOSPLIT) || p.KB * p.NTtot <= 36) return hipErrorNotSupported;
+  if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(float) >= ((size_t)1 << 31) ||
+      (size_t)p.B * p.OH * p.OW * p.C3 * sizeof(float) >= ((size_t)1 << 31))
+    return hipErrorNotSupported;                                     // 32-bit byte offsets
+  YlConvMulti m = {};
+  m.n = 1;
+  m.p[0] = p;
+  const int nx = p.C3 / 16;
+  if (p.dw_k == 5 && nx == 16) return dwx_go<5, 16>(m, out3, st, false);
+  if (p.dw_k == 5 && nx == 12) return dwx_go<5, 12>(m, out3, st, false);
+  if (p.dw_k == 3 && nx == 16) return dwx_go<3, 16>(m, out3, st, false);
+  if (p.dw_k == 3 && nx == 12) return dwx_go<3, 12>(m, out3, st, false);
+  return hipErrorNotSupported;
+}
+
+static hipError_t yl_dwx_init() {
+  YlConvMulti m = {};
+  hipError_t e = dwx_go<5, 16>(m, nullptr, nullptr, true);
+  if (e == hipSuccess) e = dwx_go<5, 12>(m, nullptr, nullptr, true);
+  if (e == hipSuccess) e = dwx_go<3, 16>(m, nullptr, nullptr, true);
+  if (e == hipSuccess) e = dwx_go<3, 12>(m, nullptr, nullptr, true);
+  return e;
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------
 // Dense k x k convolution whose weights do not fit LDS (yololite_m's FPN: 3x3, 328 -> 328 channels = 3.9 MB packed,
@@ -3208,6 +3346,9 @@ hipError_t yl_convc_init() {
   if (e == hipSuccess) e = dwl_go<16>(q, nullptr, true);
   if (e == hipSuccess) e = dwl_go<21>(q, nullptr, true);
   if (e == hipSuccess) e = yl_dws_init();
+#if !YL_BF16
+  if (e == hipSuccess) e = yl_dwx_init();
+#endif
   if (e != hipSuccess) return e;
   return dwc_any(m, 0, 0, 0, 0, 0, nullptr, true, nullptr);
 }

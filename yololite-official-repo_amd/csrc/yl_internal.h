@@ -159,11 +159,12 @@ struct YlConvP {
 #define YL_DEV_K3W_OFF (1u << 17)     // small-channel dense 3x3: the Winograd / direct kernels instead of yl_conv_k3w_kernel (bitwise A/B)
 #define YL_DEV_POISON (1u << 18)      // workspace poison (isolation tests): activation storage is allocated as 0xFF bytes (a NaN in fp32
                                       // and fp16) and refilled with them at the start of every forward / predict call; no kernel reads it
+#define YL_DEV_CHAIN_OFF (1u << 19)   // UIB projection + next block's 1x1 expansion: two launches instead of yl_conv_dwx_kernel
 #define YL_DEV_MASK 0x3ffffffu        // the bits "dev_select" keeps
 static_assert(YL_DEV_MASK <= 0x7fffffffu, "dev_select is stored in an int (and an int field of the graph key)");
 static_assert(((YL_DEV_DW_TILE_OFF | YL_DEV_PWS_OFF | YL_DEV_S2C_OFF | YL_DEV_DWC_ALL | YL_DEV_DWT_OFF | (3u << 5) | (3u << 7) |
                 YL_DEV_KXK_MT2 | YL_DEV_DWT_NOSPLIT | YL_DEV_WINO_V1 | (3u << 12) | YL_DEV_DWL_OFF | YL_DEV_DWL_ALL | YL_DEV_DPW_OFF |
-                YL_DEV_K3W_OFF | YL_DEV_POISON) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
+                YL_DEV_K3W_OFF | YL_DEV_POISON | YL_DEV_CHAIN_OFF) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
 
 // squeeze-excite gate (yl_se.hip): fixed-order two-pass spatial mean + the two FCs + sigmoid
 struct YlSeP {
@@ -267,6 +268,10 @@ hipError_t yl_launch_conv_kxk_bf16(const YlConvP& p, hipStream_t st);
 // wave-autonomous depthwise -> 1x1 kernel (yl_convc.hip); hipErrorNotSupported = shape outside its limits
 hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st);
 hipError_t yl_launch_conv_dwt_bf16(YlConvMulti& m, hipStream_t st);
+// the same projection (depthwise stride 1 -> 64 channels) with the next layer's plain 1x1 (out3) chained behind it
+// (yl_convc.hip, fp32 unit only); hipErrorNotSupported = shape / configuration not instantiated
+hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st);
+bool yl_dwx_supported(int cin, int cout, int dw_k, int dw_stride, int cout1, int oh, int ow);
 // streamed-weight depthwise 3x3 -> 1x1 kernel for K >= 192 and more than 8 n-tiles (yl_convc.hip)
 hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st);
 hipError_t yl_launch_conv_dwk_bf16(const YlConvP& p, hipStream_t st);
