@@ -454,6 +454,48 @@ yl_status yl_eval_confusion(const float* det_xyxy_dev, const int32_t* det_cls_de
                             int32_t num_images, int32_t num_gt, int32_t num_classes, float iou_thr,
                             int32_t* cm_dev, uint8_t* gt_matched_dev, void* stream);
 
+/* ---- COCO bbox mAP (pycocotools 2.0 COCOeval, iouType="bbox"; the reference's _coco_eval_from_lists,
+ * scripts/helpers/helpers.py:155-227).  evaluateImg + accumulate on the device; the host groups, sorts and
+ * counts, and summarize() stays a numpy mean over the returned arrays.  Behaviour restated (boxes [x,y,w,h]
+ * float64 exactly as given, finite):
+ *   IoU = maskApi bbIou: w = fmin(dw+dx, gw+gx) - fmax(dx,gx) (0 if <= 0), h likewise, i = w*h,
+ *         u = crowd ? dw*dh : (dw*dh + gw*gh) - i, iou = i/u
+ *   gtIg(a) = crowd || area < lo || area > hi (both bounds inclusive; area = the annotation's field)
+ *   per threshold t, detections in order: among the unmatched (or crowd) ground truths with IoU >=
+ *   min(t, 1-1e-10), the non-ignored ones with the largest IoU, LAST index on ties; only if there is none,
+ *   the same among the ignored ones.  dtm != 0 iff a ground truth with a nonzero id was taken;
+ *   dtIg = gtIg[m] if one was taken, or (dtm == 0 and the detection's w*h is outside [lo, hi]). */
+#define YL_COCO_GT_CROWD 1u       /* gt_flags: iscrowd                                        */
+#define YL_COCO_GT_ID_NONZERO 2u  /* gt_flags: annotation id != 0 (pycocotools tests dtm != 0) */
+#define YL_COCO_DT_MATCHED 1u     /* dt_flags: dtm != 0                                       */
+#define YL_COCO_DT_IGNORED 2u     /* dt_flags: dtIgnore                                       */
+/* evaluateImg for every key k = 0..num_keys-1 (an (image, category) pair with detections) and every
+ * (area range a, threshold t).  Detections of key k are rows det_off[k]..det_off[k+1]-1 of det_xywh, sorted
+ * by -score (stable) and already truncated to maxDets[-1]; its ground truths are rows gt_off[k].. in list
+ * order, with gt_area and gt_flags (YL_COCO_GT_*).  area_rng[num_areas][2], iou_thrs[num_thrs] (<= 32) are
+ * the COCOeval Params arrays as the host holds them.
+ *   dt_flags_dev[num_areas][num_thrs][num_det]  YL_COCO_DT_* bits per detection
+ *   gt_matched_dev[num_areas][num_gt]           uint32 scratch, zeroed by the call                          */
+yl_status yl_eval_coco_match(const double* det_xywh_dev, const int32_t* det_off_dev, const double* gt_xywh_dev,
+                             const double* gt_area_dev, const uint8_t* gt_flags_dev, const int32_t* gt_off_dev,
+                             int32_t num_keys, int32_t num_det, int32_t num_gt, const double* area_rng_dev,
+                             int32_t num_areas, const double* iou_thrs_dev, int32_t num_thrs, uint8_t* dt_flags_dev,
+                             uint32_t* gt_matched_dev, void* stream);
+/* accumulate for every (category k, area a, maxDet m, threshold t).  Entries cat_off[k]..cat_off[k+1]-1 of
+ * order_dev are the detections (rows of yl_eval_coco_match) of category k in accumulate order: -score, then
+ * image id, then rank within the key (a stable sort); rank_dev[i] is entry i's rank within its key, and an
+ * entry counts for maxDets[m] iff rank < maxDets[m].  npig[k][a] = non-ignored ground truths.  With
+ * tp/fp = prefix counts of (matched, not ignored) / (not matched, not ignored):
+ *   rc = tp/npig, pr = tp/((fp+tp) + 2^-52), recall = rc[-1] (0 without detections),
+ *   precision[r] = max{pr[i] : rc[i] >= rec_thrs[r]} (0 if none)   == the envelope + searchsorted of COCOeval
+ *   precision_dev[num_thrs][num_rec][num_cats][num_areas][num_max_dets], recall_dev[num_thrs][num_cats][num_areas]
+ *   [num_max_dets] float64, -1 where npig == 0.  rec_thrs ascending, num_rec <= 256.                       */
+yl_status yl_eval_coco_accumulate(const int32_t* order_dev, const int32_t* rank_dev, const int32_t* cat_off_dev,
+                                  const uint8_t* dt_flags_dev, int32_t num_det, const int32_t* npig_dev,
+                                  int32_t num_cats, int32_t num_areas, int32_t num_thrs, const int32_t* max_dets_dev,
+                                  int32_t num_max_dets, const double* rec_thrs_dev, int32_t num_rec,
+                                  double* precision_dev, double* recall_dev, void* stream);
+
 /* ---- Kalman-SORT tracker bank (reference tools/tracker.py:9-326) -------------
  * The reference's KalmanSortTracker follows ONE stream on the host.  A yl_tracker holds `num_streams`
  * independent trackers on the device (capacity `max_tracks` tracks each); yl_track_update advances all of

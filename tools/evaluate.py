@@ -3,8 +3,9 @@
 the part of evaluate_model that is on the hot path (/root/reference/scripts/helpers/evaluate.py:421-429,
 253-303): batched forward -> _decode_batch_to_coco_dets(conf 0.001, iou 0.65) -> detections JSON, plus
 the forward-only latency bench (2 warm-up + 10 timed batches, ms/img = sum ms / sum images).
-COCOeval / curves / confusion matrix / summary image are unchanged CPU consumers of the detections
-list and are out of scope.
+With labels, the evaluate consumers run on the device as well: COCO bbox mAP (_coco_eval_from_lists,
+evaluate.py:475-577 -> summary["coco"], coco_eval.json, coco_summary.txt), P/R/F1 curves and the confusion
+matrix.  The summary image is not drawn.
 
     python tools/evaluate.py --weights W.pt --test_folder D [--img_size S] [--batch_size 8] [--device 0]
 D holds images/ (or the images directly); labels are not needed for this part."""
@@ -52,7 +53,7 @@ def main():
     run_dir = next_run_dir(args.out)
     ctx = model._ctx_for(S)
     lab_dir = root / "labels"
-    coco_dets, coco_anns, fwd_ms, fwd_imgs = [], [], [], 0
+    coco_images, coco_dets, coco_anns, fwd_ms, fwd_imgs = [], [], [], [], 0
     for i in range(0, len(paths), args.batch_size):
         chunk = paths[i:i + args.batch_size]
         imgs = [imread_bgr(p) for p in chunk]
@@ -61,6 +62,7 @@ def main():
         x, bms = ya.preprocess_batch(ctx, imgs, letterbox=not args.no_letterbox, norm="albumentations")
         for j, p in enumerate(chunk):
             padx, pady, scale, w0, h0 = bms[j]
+            coco_images.append({"id": i + j, "file_name": os.path.basename(p), "width": int(w0), "height": int(h0)})
             lab = lab_dir / (Path(p).stem + ".txt")
             if lab.exists():
                 # YOLO rows "cls xc yc w h" (normalised, scripts/data/dataset.py:94-112) -> letterbox pixels ->
@@ -104,6 +106,18 @@ def main():
                         if k in cur})
         with open(Path(run_dir) / "curves.json", "w") as f:
             json.dump({k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in cur.items()}, f)
+        # evaluate.py:475-477: the COCO numbers (pycocotools COCOeval in the reference) -- on the device
+        summary["coco"] = evalops._coco_eval_from_lists(coco_images, coco_anns, coco_dets, iouType="bbox",
+                                                        num_classes=len(names), device=device)
+        ce = evalops.coco_eval(coco_images, coco_anns, coco_dets, num_classes=len(names), device=device)
+        per_class = evalops.coco_per_class(ce["precision"], ce["params"])
+        for pc in per_class:
+            pc["name"] = str(list(names)[pc["category_id"] - 1])
+        lines = evalops.coco_summary_lines(ce["stats"], ce["params"])
+        with open(Path(run_dir) / "coco_eval.json", "w") as f:
+            json.dump({"stats": [float(v) for v in ce["stats"]], "per_class": per_class}, f, indent=1)
+        with open(Path(run_dir) / "coco_summary.txt", "w") as f:
+            f.write("\n".join(lines) + "\n")
     with open(Path(run_dir) / "summary.json", "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

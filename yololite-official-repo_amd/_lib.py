@@ -125,6 +125,10 @@ SYMBOLS = [
     ("yl_eval_sweep", C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("yl_eval_confusion", C.c_int32, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                       _vp, _vp, _vp]),
+    ("yl_eval_coco_match", C.c_int32, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32,
+                                       _vp, C.c_int32, _vp, _vp, _vp]),
+    ("yl_eval_coco_accumulate", C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                            C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("yl_track_create", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(_vp)]),
     ("yl_track_destroy", None, [_vp]),
