@@ -496,6 +496,38 @@ yl_status yl_eval_coco_accumulate(const int32_t* order_dev, const int32_t* rank_
                                   int32_t num_max_dets, const double* rec_thrs_dev, int32_t num_rec,
                                   double* precision_dev, double* recall_dev, void* stream);
 
+/* ---- validation loss: the forward of the reference's LossAF (scripts/loss/loss.py:283-436), fp32 ------------
+ * SimOTA-style assignment (centre mask AND level gate, orphan rescue, six-term cost, dynamic k from the topk_limit
+ * largest IoUs, conflicts to the smallest cost / lowest box), then per image box = lambda_box * mean(1 - CIoU),
+ * cls = lambda_cls * mean(cross-entropy with label smoothing) over the positives, obj = lambda_obj * (mean BCE of
+ * the positives against clamp(IoU, 0, 1) + mean of the K = min(max(64, 3 * positives), negatives) largest BCE of
+ * the rest against 0); images without boxes or without positives contribute the hard-negative term only.  The
+ * batch result is the SUM over images; pos = images with positives / batch.  No backward pass.
+ * cfg carries the constructor's arguments as given (area_cells_min / area_cells_max BEFORE area_tol is applied).
+ * topk_limit must be 1..YL_LOSS_MAX_TOPK; one anchor per cell only (the reference's anchor grid has no room for
+ * more): YL_ERR_UNSUPPORTED otherwise.  The reference's focal / gamma / alpha arguments have no effect in its
+ * forward and no field here. */
+#define YL_LOSS_MAX_TOPK 64
+typedef struct yl_loss_cfg {
+  int32_t num_classes;        /* must equal the context's                                         */
+  int32_t img_size;           /* must equal the context's                                         */
+  int32_t center_mode;        /* YL_CENTER_*  (train-time decode, unclamped: LossAF._decode)      */
+  int32_t wh_mode;            /* YL_WH_*                                                          */
+  int32_t topk_limit;
+  float lambda_box, lambda_obj, lambda_cls, assign_cls_weight, center_radius_cells, cls_smoothing, area_cells_min,
+      area_cells_max, area_tol, size_prior_w, ar_prior_w, iou_cost_w, center_cost_w;
+} yl_loss_cfg;
+/* levels_dev: the raw level tensors as yl_forward writes them.  Ground truths of the batch as one flat list:
+ * gt_xyxy_dev[num_gt][4] in network-input pixels, gt_label_dev[num_gt] in [0, num_classes), gt_off_dev[batch + 1]
+ * ascending with gt_off[0] = 0 and gt_off[batch] = num_gt (image b owns rows gt_off[b] .. gt_off[b+1]-1; the three
+ * may be NULL when num_gt == 0).  Outputs (device): per_image_dev[batch][3] = box, obj, cls of each image and
+ * assign_dev[batch][N] = matched row of gt_* or -1 (either may be NULL), out4_dev[4] = box, obj, cls, pos.
+ * Enqueues three kernels and one memset on `stream`; no synchronisation, no copy to the host.  Sums run in an
+ * order fixed by the data: equal inputs give equal bits, and an image's parts do not depend on its batch. */
+yl_status yl_loss_af(yl_ctx* ctx, const float* const* levels_dev, int32_t batch, const float* gt_xyxy_dev,
+                     const int32_t* gt_label_dev, const int32_t* gt_off_dev, int32_t num_gt, const yl_loss_cfg* cfg,
+                     float* per_image_dev, int32_t* assign_dev, float* out4_dev, void* stream);
+
 /* ---- Kalman-SORT tracker bank (reference tools/tracker.py:9-326) -------------
  * The reference's KalmanSortTracker follows ONE stream on the host.  A yl_tracker holds `num_streams`
  * independent trackers on the device (capacity `max_tracks` tracks each); yl_track_update advances all of

@@ -5,9 +5,10 @@ the part of evaluate_model that is on the hot path (/root/reference/scripts/help
 the forward-only latency bench (2 warm-up + 10 timed batches, ms/img = sum ms / sum images).
 With labels, the evaluate consumers run on the device as well: COCO bbox mAP (_coco_eval_from_lists,
 evaluate.py:475-577 -> summary["coco"], coco_eval.json, coco_summary.txt), P/R/F1 curves and the confusion
-matrix.  The summary image is not drawn.
+matrix.  With --val-loss also the reference's validation loss (LossAF forward on the raw level tensors, accumulated as
+its validation loop does: summary["val_loss"], val_loss.json).  The summary image is not drawn.
 
-    python tools/evaluate.py --weights W.pt --test_folder D [--img_size S] [--batch_size 8] [--device 0]
+    python tools/evaluate.py --weights W.pt --test_folder D [--img_size S] [--batch_size 8] [--device 0] [--val-loss]
 D holds images/ (or the images directly); labels are not needed for this part."""
 import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")   # also the package default (yololite_amd._lib); here before torch is imported
@@ -38,6 +39,9 @@ def main():
     ap.add_argument("--out", default="runs/evaluate")
     ap.add_argument("--debug-levels", action="store_true", help="model(x) then _decode_batch_to_coco_dets (raw level "
                     "tensors materialised, as the reference does) instead of ONE fused yl_predict call; same detections")
+    ap.add_argument("--val-loss", action="store_true", help="also compute the reference's validation loss (LossAF forward, "
+                    "the val_loss column of its metrics.csv) on the device from the labels; needs the raw level tensors, "
+                    "so one extra forward per batch outside the timed call (none with --debug-levels)")
     args = ap.parse_args()
 
     import yololite_amd as ya
@@ -54,14 +58,26 @@ def main():
     ctx = model._ctx_for(S)
     lab_dir = root / "labels"
     coco_images, coco_dets, coco_anns, fwd_ms, fwd_imgs = [], [], [], [], 0
+    criterion, vb, vo, vc, vpos, vbatches = None, 0.0, 0.0, 0.0, 0.0, 0
+    if args.val_loss:
+        # tools/train.py:207-232 of the reference: hyper-parameters from the training config, its defaults otherwise
+        # (lambda_cls 1.0 there, not the class's 0.5)
+        lc = dict(((getattr(model, "meta", None) or {}).get("config") or {}).get("loss") or {})
+        kw = {k: lc.get(k, d) for k, d in dict(
+            lambda_box=5.0, lambda_obj=1.0, lambda_cls=1.0, focal=False, gamma=2.0, alpha=0.25, cls_smoothing=0.05,
+            assign_cls_weight=0.5, center_radius_cells=2.0, topk_limit=20, area_cells_min=4, area_cells_max=256,
+            area_tol=1.25, size_prior_w=0.2, ar_prior_w=0.1, iou_cost_w=3.0, center_cost_w=0.5).items()}
+        criterion = ya.LossAF(len(names), S, ctx=ctx, **kw)
     for i in range(0, len(paths), args.batch_size):
         chunk = paths[i:i + args.batch_size]
         imgs = [imread_bgr(p) for p in chunk]
         # the evaluate path's pre-processing (scripts/data/augment.py:153-171 through YoloDataset), on the device:
         # LongestMaxSize + PadIfNeeded (= the letterbox geometry) or Resize with --no_letterbox, A.Normalize arithmetic
         x, bms = ya.preprocess_batch(ctx, imgs, letterbox=not args.no_letterbox, norm="albumentations")
+        targets = []
         for j, p in enumerate(chunk):
             padx, pady, scale, w0, h0 = bms[j]
+            tb, tl = [], []
             coco_images.append({"id": i + j, "file_name": os.path.basename(p), "width": int(w0), "height": int(h0)})
             lab = lab_dir / (Path(p).stem + ".txt")
             if lab.exists():
@@ -74,8 +90,11 @@ def main():
                     x1 = (r[1] - r[3] / 2) * w0 * sx + padx; x2 = (r[1] + r[3] / 2) * w0 * sx + padx
                     y1 = (r[2] - r[4] / 2) * h0 * sy + pady; y2 = (r[2] + r[4] / 2) * h0 * sy + pady
                     bb = [float(np.float32(v)) for v in ((x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1)]
+                    tb.append([x1, y1, x2, y2]); tl.append(int(r[0]))
                     coco_anns.append({"id": len(coco_anns) + 1, "image_id": i + j, "category_id": int(r[0]) + 1,
                                       "bbox": bb, "area": float(max(0.0, bb[2] * bb[3])), "iscrowd": 0})
+            # pixel xyxy on the letterboxed input, class = first column (what the reference's val loader hands its loss)
+            targets.append({"boxes": np.asarray(tb, np.float32).reshape(-1, 4), "labels": np.asarray(tl, np.int64)})
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         if args.debug_levels:       # the reference's two calls: raw level tensors, then _decode_batch_to_coco_dets
@@ -88,6 +107,12 @@ def main():
             t1 = time.perf_counter()
         if i // args.batch_size >= 2 and len(fwd_ms) < 10:          # evaluate.py:253-303 protocol
             fwd_ms.append((t1 - t0) * 1e3); fwd_imgs += len(chunk)
+        if criterion is not None:
+            # tools/train.py:417-424: per batch, each part divided by the batch size; averaged over batches below
+            lv = preds if args.debug_levels else ctx.forward(x)
+            _, vd = criterion(lv[0] if isinstance(lv, tuple) else lv, targets)      # (levels, prototypes) of a seg model
+            vb += vd["box"] / len(chunk); vo += vd["obj"] / len(chunk); vc += vd["cls"] / len(chunk)
+            vpos += vd["pos"]; vbatches += 1
         for j, dl in enumerate(dets):
             for d in dl:
                 coco_dets.append(dict(d, image_id=i + j, file_name=os.path.basename(chunk[j])))
@@ -118,6 +143,12 @@ def main():
             json.dump({"stats": [float(v) for v in ce["stats"]], "per_class": per_class}, f, indent=1)
         with open(Path(run_dir) / "coco_summary.txt", "w") as f:
             f.write("\n".join(lines) + "\n")
+    if criterion is not None:
+        nb = max(1, vbatches)                                   # train.py:487: v_running / len(val_loader)
+        summary["val_loss"] = {"total": (vb + vo + vc) / nb, "box": vb / nb, "obj": vo / nb, "cls": vc / nb,
+                               "pos": vpos / nb}
+        with open(Path(run_dir) / "val_loss.json", "w") as f:
+            json.dump(summary["val_loss"], f, indent=1)
     with open(Path(run_dir) / "summary.json", "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

@@ -91,6 +91,16 @@ class yl_post_cfg(C.Structure):
                 ("fallback_nms", C.c_int32)]
 
 
+YL_LOSS_MAX_TOPK = 64
+
+
+class yl_loss_cfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("num_classes", "img_size", "center_mode", "wh_mode", "topk_limit")] + [
+        (n, C.c_float) for n in ("lambda_box", "lambda_obj", "lambda_cls", "assign_cls_weight", "center_radius_cells",
+                                 "cls_smoothing", "area_cells_min", "area_cells_max", "area_tol", "size_prior_w",
+                                 "ar_prior_w", "iou_cost_w", "center_cost_w")]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -129,6 +139,7 @@ SYMBOLS = [
                                        _vp, C.c_int32, _vp, _vp, _vp]),
     ("yl_eval_coco_accumulate", C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
                                             C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
+    ("yl_loss_af", C.c_int32, [_vp, _vpp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.POINTER(yl_loss_cfg), _vp, _vp, _vp, _vp]),
     ("yl_track_create", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(_vp)]),
     ("yl_track_destroy", None, [_vp]),

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-ten translation units (three of them compiled three times: fp32, bf16-MFMA and fp16-MFMA builds), one shared library with a plain C ABI (include/yololite_hip.h).
+eleven translation units (three of them compiled three times: fp32, bf16-MFMA and fp16-MFMA builds), one shared library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
 """
@@ -41,6 +41,8 @@ UNITS = [   # (source, extra flags, object name)
     ("yl_eval.hip", ["-ffp-contract=off"], "yl_eval.o"),
     # tracker: float32 scalar arithmetic of the reference's bbox conversions / IoU, op by op
     ("yl_track.hip", ["-ffp-contract=off"], "yl_track.o"),
+    # validation loss (LossAF forward): torch's fp32 operations one by one, so the discrete assignment falls the same way
+    ("yl_loss.hip", ["-ffp-contract=off"], "yl_loss.o"),
 ]
 DEPS = ["yl_internal.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 

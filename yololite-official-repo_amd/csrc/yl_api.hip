@@ -90,6 +90,12 @@ struct yl_ctx {
   float* ws_tmp_dets = nullptr;
   int* ws_tmp_idx = nullptr;
   int post_cap_batch = 0;
+  // validation-loss scratch (yl_loss_af), sized on first use
+  unsigned long long* ws_loss_keys = nullptr;   // [B][N]
+  float* ws_loss_neg = nullptr;                 // [B][N]
+  float* ws_loss_pi = nullptr;                  // [B][3]
+  int* ws_loss_pos = nullptr;                   // [B]
+  int loss_cap_batch = 0;
   // standalone nms scratch
   int* ws_nms_clsws = nullptr;
   unsigned long long* ws_nms_gkeys = nullptr;
@@ -1357,6 +1363,7 @@ void yl_destroy(yl_ctx* c) {
   free_act(c);
   free_post_ws(c);
   hipFree(c->ws_nms_clsws);
+  hipFree(c->ws_loss_keys); hipFree(c->ws_loss_neg); hipFree(c->ws_loss_pi); hipFree(c->ws_loss_pos);
   for (int i = 0; i < 4; ++i) {
     if (c->work[i]) hipStreamDestroy(c->work[i]);
     if (c->ev_join[i]) hipEventDestroy(c->ev_join[i]);
@@ -2047,6 +2054,49 @@ yl_status yl_nms(yl_ctx* c, const float* boxes, const float* scores, int32_t n, 
   hipError_t e = yl_launch_nms(np, 1, st);
   hipFreeAsync(scratch, st);
   HIPCHK(c, e);
+  return YL_OK;
+}
+
+yl_status yl_loss_af(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy, const int32_t* gt_label,
+                     const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg, float* per_image, int32_t* assign,
+                     float* out4, void* stream) {
+  if (!c || !levels || !cfg || !out4 || B < 1 || num_gt < 0) return YL_ERR_INVALID;
+  if (num_gt > 0 && (!gt_xyxy || !gt_label || !gt_off)) return fail(c, YL_ERR_INVALID, "ground-truth arrays are NULL");
+  if (cfg->num_classes != c->C || cfg->img_size != c->img_size)
+    return fail(c, YL_ERR_INVALID, "yl_loss_cfg num_classes / img_size differ from the context's");
+  if (c->C < 1) return fail(c, YL_ERR_INVALID, "the loss needs at least one class");
+  if (cfg->center_mode < 0 || cfg->center_mode > 1 || cfg->wh_mode < 0 || cfg->wh_mode > 2)
+    return fail(c, YL_ERR_INVALID, "bad mode");
+  for (int l = 0; l < c->L; ++l)
+    if (c->level_A[l] != 1)
+      return fail(c, YL_ERR_UNSUPPORTED, "LossAF is defined for one anchor per cell (the reference builds h*w anchors per level)");
+  if (cfg->topk_limit < 1 || cfg->topk_limit > YL_LOSS_MAX_TOPK)
+    return fail(c, YL_ERR_UNSUPPORTED, "topk_limit must be 1.." + std::to_string(YL_LOSS_MAX_TOPK));
+  if (!(cfg->area_tol > 0.0f)) return fail(c, YL_ERR_INVALID, "area_tol must be positive");
+  HIPCHK(c, hipSetDevice(c->device));
+  if (B > c->loss_cap_batch) {
+    hipFree(c->ws_loss_keys); hipFree(c->ws_loss_neg); hipFree(c->ws_loss_pi); hipFree(c->ws_loss_pos);
+    c->ws_loss_keys = nullptr; c->ws_loss_neg = nullptr; c->ws_loss_pi = nullptr; c->ws_loss_pos = nullptr;
+    c->loss_cap_batch = 0;
+    HIPCHK(c, hipMalloc((void**)&c->ws_loss_keys, (size_t)B * c->N * sizeof(unsigned long long)));
+    HIPCHK(c, hipMalloc((void**)&c->ws_loss_neg, (size_t)B * c->N * sizeof(float)));
+    HIPCHK(c, hipMalloc((void**)&c->ws_loss_pi, (size_t)B * 3 * sizeof(float)));
+    HIPCHK(c, hipMalloc((void**)&c->ws_loss_pos, (size_t)B * sizeof(int)));
+    c->loss_cap_batch = B;
+  }
+  YlLevels lv;
+  fill_levels(c, levels, lv);
+  YlLossP p;
+  memset(&p, 0, sizeof(p));
+  p.cfg = *cfg;
+  // LossAF.__init__ folds area_tol into the bounds as Python floats; the comparison rounds them to fp32
+  p.area_min = (float)((double)cfg->area_cells_min / (double)cfg->area_tol);
+  p.area_max = (float)((double)cfg->area_cells_max * (double)cfg->area_tol);
+  p.gt = gt_xyxy; p.label = gt_label; p.off = gt_off; p.T = num_gt; p.B = B;
+  p.keys = c->ws_loss_keys; p.negv = c->ws_loss_neg;
+  p.per_image = per_image ? per_image : c->ws_loss_pi;
+  p.has_pos = c->ws_loss_pos; p.assign = assign; p.out4 = out4;
+  HIPCHK(c, yl_launch_loss_af(lv, p, (hipStream_t)stream));
   return YL_OK;
 }
 

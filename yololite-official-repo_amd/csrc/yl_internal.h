@@ -60,6 +60,23 @@ struct YlNmsP {
   int* done;             // [B][64 ints = 256 bytes]: class -> group table written by group 0 for the merge kernel
 };
 
+// validation loss (yl_loss.hip): one memset + three launches on `st`
+struct YlLossP {
+  yl_loss_cfg cfg;
+  float area_min, area_max;     // level-gate bounds with area_tol applied (LossAF.__init__), rounded to fp32
+  const float* gt;              // [T][4]
+  const int* label;             // [T]
+  const int* off;               // [B+1]
+  int T, B;
+  unsigned long long* keys;     // [B][N] scratch: (order-preserving cost bits) << 32 | box, all ones = unmatched
+  float* negv;                  // [B][N] scratch: BCE-against-zero of the non-positives, -1 for positives
+  float* per_image;             // [B][3]
+  int* has_pos;                 // [B]
+  int* assign;                  // [B][N] or nullptr
+  float* out4;
+};
+hipError_t yl_launch_loss_af(const YlLevels& lv, const YlLossP& p, hipStream_t st);
+
 // ---- activation element type of a translation unit.  fp32 everywhere except the FOURTH compilation of the conv units
 // (-DYL_BF16=1 -DYL_F16=1 -DYL_F16S=1, option "store_f16", round 6): activation tensors live in HBM as fp16 -- the storage side
 // of the reference's fp16 autocast (scripts/helpers/evaluate.py:399,415).  The struct layout is the same in every unit (these

@@ -252,6 +252,30 @@ class HipContext:
                                            _stream_ptr(self.device)), self.handle, "yl_postprocess")
         return (dets, counts, idx) if want_idx else (dets, counts)
 
+    def loss_af(self, levels, gt_xyxy: torch.Tensor, gt_label: torch.Tensor, gt_off: torch.Tensor, cfg,
+                want_per_image: bool = False, want_assign: bool = False):
+        """yl_loss_af: the forward of the reference's LossAF on raw level tensors.  gt_xyxy [T,4] float32 (network-input
+        pixels), gt_label [T] int32, gt_off [B+1] int32 on this device; cfg a _lib.yl_loss_cfg (lossops.LossAF fills
+        one).  Returns device tensors: out4 = (box, obj, cls, pos) and, when asked for, per_image [B,3] / assign [B,N];
+        nothing is synchronised or copied to the host."""
+        lv = self._check_levels(levels)
+        B = lv[0].shape[0]
+        T = int(gt_xyxy.shape[0])
+        if gt_off.numel() != B + 1 or gt_label.numel() != T:
+            raise ValueError("gt_off must have B+1 entries and gt_label one per box")
+        for t, dt in ((gt_xyxy, torch.float32), (gt_label, torch.int32), (gt_off, torch.int32)):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError("ground-truth tensors must be contiguous float32 / int32 / int32 tensors on the context's device")
+        out4 = torch.empty((4,), device=self.device, dtype=torch.float32)
+        per = torch.empty((B, 3), device=self.device, dtype=torch.float32) if want_per_image else None
+        asg = torch.empty((B, self.N), device=self.device, dtype=torch.int32) if want_assign else None
+        _lib.check(self.lib.yl_loss_af(self.handle, self._ptr_array(lv), B, gt_xyxy.data_ptr() if T else None,
+                                       gt_label.data_ptr() if T else None, gt_off.data_ptr(), T, C.byref(cfg),
+                                       per.data_ptr() if per is not None else None,
+                                       asg.data_ptr() if asg is not None else None, out4.data_ptr(),
+                                       _stream_ptr(self.device)), self.handle, "yl_loss_af")
+        return out4, per, asg
+
     def prototypes(self, B: int) -> torch.Tensor:
         """mask prototypes of the last forward/predict as [B,NM,PH,PW] (the device tensor is NHWC)."""
         if self.proto_slot < 0:
