@@ -423,6 +423,19 @@ def test_lanes_and_chunk_graphs_are_bitwise_the_plain_path():
                         k = int(c0[b])
                         assert torch.equal(d[b, :k], d0[b, :k]), (graph, streams, lanes, batch, b)
     ctx.set_option("lanes", 0); ctx.set_option("batch_levels", 1)
+    # "hybrid" 1 / 2: segment plans (full-batch launches for one layer range, batch chunks for the others) -- two streams
+    # and no side lane, so that the segments are actually taken
+    ctx.set_option("streams", 2)
+    for graph in (0, 1):
+        for hybrid in (1, 2):
+            ctx.set_option("graph", graph); ctx.set_option("hybrid", hybrid)
+            for _ in range(2):
+                d, c = ctx.predict(x, _lib.POST_MAIN, 0.4, 0.5, per_class_cap=300, max_out=300)
+                assert torch.equal(c, c0), (graph, hybrid)
+                for b in range(16):
+                    k = int(c0[b])
+                    assert torch.equal(d[b, :k], d0[b, :k]), (graph, hybrid, b)
+    ctx.set_option("hybrid", 0)
 
 
 @pytest.mark.parametrize("name,B,S", [("edge_n", 3, 320), ("edge_n", 2, 640), ("edge_n", 3, 384), ("edge_n", 5, 128),

@@ -137,11 +137,11 @@ struct yl_ctx {
   // gets CUs at the tail of the first
   int opt_lanes = 0;
   std::vector<unsigned char> lane;
+  std::vector<int> readers;  // per slot: layer operands that read it (count_readers, yl_create) -- 1 = a single consumer
   hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_la[4] = {nullptr, nullptr, nullptr, nullptr}, ev_lb[4] = {nullptr, nullptr, nullptr, nullptr};
-  // single-entry hipGraph cache keyed on everything baked into the captured launches
-  // hipGraph cache: up to YL_GRAPH_SLOTS jobs (a serving loop alternates between a few input / output buffers,
-  // e.g. the two slots of the pipelined all-gather), least recently used evicted
+  // hipGraph cache keyed on everything baked into the captured launches: up to YL_GRAPH_SLOTS jobs (a serving loop alternates
+  // between a few input / output buffers, e.g. the two slots of the pipelined all-gather), least recently used evicted
   struct GraphEntry {
     std::vector<hipGraphExec_t> execs;   // one graph per (segment, chunk) piece, in launch order
     int n = 0;
@@ -308,7 +308,14 @@ void free_act(yl_ctx* c) {
 
 int pow2ceil(int v) { int p = 64; while (p < v) p <<= 1; return p; }
 
-// layers [i, end) that run_layers sends out as ONE launch (level-batched heads / smooth blocks): same kernel
+// ---- what the next launch is.  One owner: run_layers emits what next_step says, plan_slots groups by it.
+
+enum LaunchForm { F_LAYER, F_BATCHED, F_HEAD_RUN, F_DPQ_EXPAND, F_DPQ_PAIR, F_DWX_CHAIN, F_SPLIT_HEAD };
+// first: the step's first program layer; width: members of the level-batched run (1..4); layers: program layers consumed
+struct LaunchStep { LaunchForm form; size_t first; int width; int layers; };
+constexpr unsigned form_bit(LaunchForm f) { return 1u << f; }
+
+// layers [i, end) that go out as ONE launch (level-batched heads / smooth blocks): same kernel
 // configuration, no residual / upsample operands, no dependency inside the run
 size_t layer_group_end(const yl_ctx* c, size_t i, size_t lend) {
   auto same_shape = [&](size_t x, size_t y) {
@@ -332,26 +339,124 @@ size_t layer_group_end(const yl_ctx* c, size_t i, size_t lend) {
   return gend;
 }
 
+// The shape predicates know nothing of the options (allowed_forms).
+// The first layer of a head run or a dpq pair: depthwise 3x3 stride 1 -> 1x1 on an unchanged grid, no other operand, written to
+// a slot with a single reader (the caller checks that it is the step's second layer's input)
+bool dw3_trunk(const yl_ctx* c, const DevLayer& T) {
+  const yl_layer& t = T.d;
+  return t.op == YL_OP_CONV && t.k == 1 && t.dw_k == 3 && t.dw_stride == 1 && t.c2 == 0 && t.c3 == 0 && t.head_level < 0 &&
+         t.res_slot < 0 && t.up_slot < 0 && !t.in_shift && !YL_SMOOTH(t.act) && !YL_SMOOTH(t.dw_act) && t.out_slot >= 0 &&
+         T.in_h == T.out_h && T.in_w == T.out_w && c->readers[t.out_slot] == 1;
+}
+
+// Head branches as ONE launch (yl_conv_dpp_kernel): the level-batched run [i, i + n) of head trunks (depthwise 3x3 -> 1x1)
+// is followed by the run of their head-output convs in the same order, nothing else reads the trunk tensors, no mask
+// coefficients and the shape is instantiated
+bool head_run_fusable(const yl_ctx* c, size_t i, size_t n, size_t lend) {
+  if (c->NM > 0 || i + 2 * n > lend) return false;
+  for (size_t q = 0; q < n; ++q) {
+    const DevLayer& T = c->layers[i + q];
+    const DevLayer& O = c->layers[i + n + q];
+    const yl_layer& t = T.d; const yl_layer& o = O.d;
+    if (o.op != YL_OP_CONV || o.head_level < 0 || o.k != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 || o.in_slot != t.out_slot ||
+        o.cin != t.cout || o.act != YL_ACT_NONE || o.res_slot >= 0 || o.up_slot >= 0 || o.in_shift)
+      return false;
+    if (!dw3_trunk(c, T) || !yl_dpp_supported(t.cin, t.cout, o.cout, T.out_h, T.out_w)) return false;
+  }
+  return true;
+}
+
+// depthwise 3x3 -> 1x1 expand -> 1x1 project (+residual) as ONE launch (yl_conv_dpq_kernel): layer i is the depthwise +
+// expand conv, layer i + 1 the plain 1x1 that consumes it, nothing else reads the expanded tensor, shape instantiated
+bool pair_fusable(const yl_ctx* c, size_t i, size_t lend) {
+  if (i + 1 >= lend) return false;
+  const DevLayer& T = c->layers[i];
+  const yl_layer& t = T.d; const yl_layer& o = c->layers[i + 1].d;
+  if (!dw3_trunk(c, T)) return false;
+  if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 || o.in_slot != t.out_slot ||
+      o.cin != t.cout || YL_SMOOTH(o.act) || o.up_slot >= 0 || o.in_shift || o.res_slot == t.out_slot ||
+      o.scale_slot >= 0 || t.scale_slot >= 0)
+    return false;
+  return yl_dpq_supported(t.cin, t.cout, o.cout, T.out_h, T.out_w);
+}
+
+// wide depthwise 3x3 -> 1x1 layer (more than 96 outputs) on its own: yl_conv_dpq_kernel's expand-only form computes the
+// depthwise part once per pixel
+bool expand_fusable(const yl_ctx* c, size_t i) {
+  const DevLayer& T = c->layers[i];
+  const yl_layer& d = T.d;
+  return d.op == YL_OP_CONV && d.dw_k == 3 && d.dw_stride == 1 && d.k == 1 && d.c2 == 0 && d.c3 == 0 && d.head_level < 0 &&
+         d.res_slot < 0 && d.up_slot < 0 && !d.in_shift && d.cout > 96 && T.in_h == T.out_h &&
+         yl_dpq_supported(d.cin, d.cout, 0, T.out_h, T.out_w);
+}
+
+// UIB projection -> the next block's expansion as ONE launch (yl_conv_dwx_kernel): layer i is a 1x1 conv with a stride-1
+// depthwise prologue (optional residual) writing slot S, layer i + 1 a plain 1x1 conv (no prologue, residual, upsample,
+// gate or head) reading S.  S is still written -- the next block reads it as its residual.
+bool chain_fusable(const yl_ctx* c, size_t i, size_t lend) {
+  if (i + 1 >= lend) return false;
+  const DevLayer& T = c->layers[i];
+  const DevLayer& O = c->layers[i + 1];
+  const yl_layer& t = T.d; const yl_layer& o = O.d;
+  if (t.op != YL_OP_CONV || t.k != 1 || t.stride != 1 || t.dw_k <= 0 || t.dw_stride != 1 || t.c2 > 0 || t.c3 > 0 ||
+      t.head_level >= 0 || t.up_slot >= 0 || t.scale_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || t.out_slot < 0 ||
+      (t.res_slot >= 0 && t.act != YL_ACT_NONE))
+    return false;
+  if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.stride != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 ||
+      o.in_slot != t.out_slot || o.cin != t.cout || YL_SMOOTH(o.act) || o.res_slot >= 0 || o.up_slot >= 0 ||
+      o.scale_slot >= 0 || o.in_shift || o.out_slot < 0)
+    return false;
+  return T.in_h == T.out_h && T.in_w == T.out_w && O.in_h == T.out_h && O.in_w == T.out_w && O.out_h == T.out_h &&
+         O.out_w == T.out_w && yl_dwx_supported(t.cin, t.cout, t.dw_k, t.dw_stride, o.cout, T.out_h, T.out_w);
+}
+
+// The forms the options allow a run_layers call (F_LAYER always is): the option tests, here and nowhere else.
+// per_layer: per-layer timing or side lanes; fuse: yl_predict with decode in the head-output epilogue
+unsigned allowed_forms(const yl_ctx* c, bool per_layer, bool fuse) {
+  if (per_layer) return 0;
+  unsigned f = c->opt_batch_levels ? form_bit(F_BATCHED) : 0;
+  if (c->opt_fuse_head && !c->opt_bf16) f |= form_bit(F_DPQ_EXPAND) | form_bit(F_DPQ_PAIR) | (fuse ? form_bit(F_HEAD_RUN) : 0);
+  if (c->opt_fuse_head && fuse) f |= form_bit(F_SPLIT_HEAD);
+  // fp32 mode, split-K off (its form keeps the two launches), the automatic kernel choice, the depthwise -> 1x1 kernel and the
+  // chaining not switched off
+  if (!(c->opt_bf16 || c->opt_split_k || c->opt_tile_m || (c->opt_dev & (YL_DEV_CHAIN_OFF | YL_DEV_DWT_OFF)))) f |= form_bit(F_DWX_CHAIN);
+  return f;
+}
+
+// The launch that starts at layer i of [.., lend): the first of `forms` (form_bit set) that applies, in the order head run,
+// expand-only dpq, dpq pair, dwx chain, split head, level-batched run, else the single layer.  Without F_BATCHED layer i is
+// looked at on its own, as "batch_levels" 0 does.
+LaunchStep next_step(const yl_ctx* c, size_t i, size_t lend, unsigned forms) {
+  if (c->layers[i].d.op != YL_OP_CONV) return {F_LAYER, i, 1, 1};
+  auto may = [&](LaunchForm f) { return (forms & form_bit(f)) != 0; };
+  const size_t n = may(F_BATCHED) ? layer_group_end(c, i, lend) - i : 1;
+  if (may(F_HEAD_RUN) && head_run_fusable(c, i, n, lend)) return {F_HEAD_RUN, i, (int)n, (int)(2 * n)};
+  if (n == 1) {
+    const bool pair = (may(F_DPQ_EXPAND) || may(F_DPQ_PAIR)) && pair_fusable(c, i, lend);
+    if (may(F_DPQ_EXPAND) && !pair && expand_fusable(c, i)) return {F_DPQ_EXPAND, i, 1, 1};
+    if (may(F_DPQ_PAIR) && pair) return {F_DPQ_PAIR, i, 1, 2};
+    if (may(F_DWX_CHAIN) && chain_fusable(c, i, lend)) return {F_DWX_CHAIN, i, 1, 2};
+  }
+  // head-output convs of a model with mask coefficients, every one packed as two weight images
+  if (may(F_SPLIT_HEAD) && c->layers[i].d.head_level >= 0 &&
+      std::all_of(c->layers.begin() + i, c->layers.begin() + i + n, [](const DevLayer& L) { return L.wp_det != nullptr; }))
+    return {F_SPLIT_HEAD, i, (int)n, (int)n};
+  return {n > 1 ? F_BATCHED : F_LAYER, i, (int)n, (int)n};
+}
+
 // Place the slots inside a chunk arena.  Liveness is tracked per LAUNCH GROUP (a level-batched run reads and writes
 // all of its layers' tensors at once): slot s is live from the group that produces it to the group of its last
 // consumer, inclusive; first-fit over the gaps of the live set.  reuse == false: every slot gets its own range.
-bool pair_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options);
-bool chain_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options);
-
 void plan_slots(yl_ctx* c, bool reuse) {
   const size_t NL = c->layers.size(), NS = c->slots.size();
   std::vector<int> grp(NL, 0);
   int g = 0;
+  // A group is whatever next_step could send out as one launch under ANY setting of the options (a fused launch writes its
+  // last layer's output while other tiles still read its first layer's inputs): the level-batched run at i, plus one more
+  // layer when the run's last member, on its own, can head a two-layer step.
   for (size_t i = 0; i < NL; ++g) {
-    size_t e = layer_group_end(c, i, NL);
-    // two layers that run_layers may send out as ONE launch (yl_conv_dpq_kernel) are one group: the second layer's
-    // output is written while the first layer's inputs are still being read by other tiles, so it must not be placed
-    // over them (whatever the options say when the plan is made)
-    // (also when the first layer of the pair is the LAST member of a level-batched run -- with "batch_levels"
-    // 0 run_layers sees it alone and may fuse it with its successor)
-    // (the same for a projection with the next block's expansion chained behind it, yl_conv_dwx_kernel: the expanded
-    // tensor must not be placed over the projection's depthwise input or residual)
-    if (pair_fusable(c, e - 1, NL, true) || chain_fusable(c, e - 1, NL, true)) e = e + 1;
+    size_t e = i + (size_t)next_step(c, i, NL, form_bit(F_BATCHED)).width;
+    if (next_step(c, e - 1, NL, form_bit(F_DPQ_PAIR) | form_bit(F_DWX_CHAIN)).layers == 2) e = e + 1;
     for (size_t q = i; q < e; ++q) grp[q] = g;
     i = e;
   }
@@ -501,13 +606,25 @@ yl_status poison_act(yl_ctx* c, hipStream_t st) {
   return YL_OK;
 }
 
+// the planned chunk (and with it the arena) that image b lives in
+int chunk_of(const yl_ctx* c, int b) {
+  int ch = 0;
+  while (ch + 1 < c->plan_n && b >= c->plan_b0[ch + 1]) ++ch;
+  return ch;
+}
+
 // image b of slot `sl` (b must lie in the planned chunk that contains it)
 float* slot_addr(const yl_ctx* c, int sl, int b) {
   const Slot& t = c->slots[sl];
   if (t.pinned) return (float*)((char*)t.pin + (size_t)b * t.sz);
-  int ch = 0;
-  while (ch + 1 < c->plan_n && b >= c->plan_b0[ch + 1]) ++ch;
+  const int ch = chunk_of(c, b);
   return (float*)(c->arena[ch] + t.off * (size_t)c->plan_cap + (size_t)(b - c->plan_b0[ch]) * t.sz);
+}
+
+// image b's part of its chunk's partial-sum scratch (squeeze-excite / GRN pooling)
+float* se_partial(const yl_ctx* c, int b) {
+  const int ch = chunk_of(c, b);
+  return c->se_scratch[ch] + (size_t)(b - c->plan_b0[ch]) * c->se_unit;
 }
 
 yl_status ensure_post(yl_ctx* c, int B) {
@@ -615,87 +732,208 @@ bool can_fuse_decode(const yl_ctx* c) {
   return any;
 }
 
-// Head branches as ONE launch (yl_conv_dpp_kernel): the level-batched run [i, gend) of head trunks (depthwise 3x3 -> 1x1)
-// is followed by the run of their head-output convs in the same order, nothing else reads the trunk tensors, decode is
-// fused (yl_predict, no mask coefficients) and the shape is instantiated
-bool head_run_fusable(const yl_ctx* c, size_t i, size_t gend, size_t lend) {
-  const size_t n = gend - i;
-  if (!c->opt_fuse_head || c->opt_bf16 || c->NM > 0 || gend + n > lend) return false;
-  for (size_t q = 0; q < n; ++q) {
-    const DevLayer& T = c->layers[i + q];
-    const DevLayer& O = c->layers[gend + q];
-    const yl_layer& t = T.d; const yl_layer& o = O.d;
-    if (t.op != YL_OP_CONV || t.k != 1 || t.dw_k != 3 || t.dw_stride != 1 || t.c2 > 0 || t.c3 > 0 || t.head_level >= 0 ||
-        t.res_slot >= 0 || t.up_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || YL_SMOOTH(t.dw_act) || t.out_slot < 0)
-      return false;
-    if (o.op != YL_OP_CONV || o.head_level < 0 || o.k != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 || o.in_slot != t.out_slot ||
-        o.cin != t.cout || o.act != YL_ACT_NONE || o.res_slot >= 0 || o.up_slot >= 0 || o.in_shift)
-      return false;
-    if (T.in_h != T.out_h || T.in_w != T.out_w || !yl_dpp_supported(t.cin, t.cout, o.cout, T.out_h, T.out_w)) return false;
-    for (size_t r = 0; r < c->layers.size(); ++r) {
-      if (r == gend + q) continue;
-      const yl_layer& e = c->layers[r].d;
-      const bool reads_in = e.op != YL_OP_STEM && e.op != YL_OP_STEMBLOCK && e.in_slot == t.out_slot;
-      if (reads_in || e.res_slot == t.out_slot || e.up_slot == t.out_slot) return false;
+// Launchers that exist once per precision mode, indexed by opt_bf16: 0 fp32, 1 bf16-MFMA, 2 fp16-MFMA, 3 fp16 storage.
+// There is no bf16 / fp16-MFMA stem or depthwise launcher: those modes keep fp32 tensors and use the fp32 one.
+struct ModeLaunchers {
+  hipError_t (*conv)(const YlConvP&, int, hipStream_t);
+  hipError_t (*conv_multi)(const YlConvP*, int, int, hipStream_t);
+  hipError_t (*stem)(const YlConvP&, hipStream_t), (*dw)(const YlConvP&, hipStream_t);
+  hipError_t (*stemblock)(const YlConvP&, hipStream_t), (*stemdw)(const YlConvP&, hipStream_t);
+};
+const ModeLaunchers kLaunch[4] = {
+    {yl_launch_conv, yl_launch_conv_multi, yl_launch_stem, yl_launch_dw, yl_launch_stemblock, yl_launch_stemdw},
+    {yl_launch_conv_bf16, yl_launch_conv_multi_bf16, yl_launch_stem, yl_launch_dw, yl_launch_stemblock_bf16, yl_launch_stemdw_bf16},
+    {yl_launch_conv_f16, yl_launch_conv_multi_f16, yl_launch_stem, yl_launch_dw, yl_launch_stemblock_f16, yl_launch_stemdw_f16},
+    {yl_launch_conv_f16s, yl_launch_conv_multi_f16s, yl_launch_stem_f16s, yl_launch_dw_f16s, yl_launch_stemblock_f16s, yl_launch_stemdw_f16s},
+};
+
+yl_status launch_failed(yl_ctx* c, const LaunchStep& s, hipError_t e) {
+  static const char* const what[] = {"", "batched ", "head ", "expand-only ", "fused ", "chained ", "split head "};   // by LaunchForm
+  char b[256];
+  snprintf(b, sizeof(b), "layers %zu..%zu %slaunch failed: %s", s.first, s.first + s.layers - 1, what[s.form], hipGetErrorString(e));
+  return fail(c, YL_ERR_HIP, b);
+}
+
+// One run_layers call: what it was asked for and what it carries from launch to launch.
+struct LayerRun {
+  yl_ctx* c;
+  const float* x; int b0, B; float* const* level_out;
+  hipStream_t st; hipEvent_t* evs; int chunk; const yl_post_cfg* fuse; size_t lend;
+  bool lanes = false;                        // two lanes (see yl_ctx::lane): lane-1 layers go to the chunk's side stream `sd`
+  hipStream_t sd = nullptr;
+  std::vector<unsigned char> prod;           // lane that produced each slot
+  bool side_used = false;
+  int pooled_slot = -1, pooled_P = 0;        // slot whose partial channel sums the last depthwise launch left
+
+  // where the launch that computes head-output layer i decodes to (fuse != nullptr)
+  void decode_targets(size_t i, YlConvP& p) const {
+    const int l = c->layers[i].d.head_level, S = c->level_S[l];
+    const size_t o = (size_t)b0 * c->N;
+    p.dec_boxes = c->ws_boxes + o; p.dec_scores = c->ws_scores + o; p.dec_cls = c->ws_cls + o;
+    p.dec_N = c->N; p.dec_off = c->level_off[l] + c->layers[i].head_anchor * S * S; p.dec_C = c->C;
+    p.dec_mode = fuse->mode; p.dec_center = fuse->center_mode; p.dec_wh = fuse->wh_mode;
+    p.dec_raw = c->NM > 0 ? 1 : 0;                          // mask coefficients are read from the raw rows
+    p.dec_stride = (float)((double)c->img_size / (double)S);   // utils_ms.py:71, as fill_levels
+    p.dec_hi = (float)(c->img_size - 1);
+  }
+  void params(size_t i, YlConvP& p) const {
+    layer_params(c, c->layers[i], b0, B, x, level_out, p);
+    if (fuse && c->layers[i].d.head_level >= 0) decode_targets(i, p);
+  }
+};
+
+// F_LAYER: layer i by its own launcher (+ the activation pass behind it), on its lane's stream
+yl_status run_layer(LayerRun& r, size_t i) {
+  yl_ctx* c = r.c;
+  const DevLayer& L = c->layers[i];
+  const yl_layer& d = L.d;
+  const int b0 = r.b0, B = r.B;
+  const ModeLaunchers& ml = kLaunch[c->opt_bf16];
+  YlConvP p;
+  r.params(i, p);
+  const int ln = (r.lanes && c->lane[i]) ? 1 : 0;
+  hipStream_t ls = ln ? r.sd : r.st;
+  if (r.lanes) {
+    // an event edge wherever a layer reads a slot produced on the other lane
+    bool cross = false;
+    const int ins[4] = {d.in_slot, d.res_slot, d.up_slot, d.scale_slot};
+    for (int k = 0; k < 4; ++k)
+      if (ins[k] >= 0 && d.op != YL_OP_STEM && d.op != YL_OP_STEMBLOCK && d.op != YL_OP_NHWC4 && r.prod[ins[k]] != ln) cross = true;
+    if (ln == 1 && !r.side_used) cross = true;             // first side launch: order after everything enqueued so far
+    if (cross) {
+      hipEvent_t ev = ln ? c->ev_la[r.chunk] : c->ev_lb[r.chunk];
+      HIPCHK(c, hipEventRecord(ev, ln ? r.st : r.sd));
+      HIPCHK(c, hipStreamWaitEvent(ls, ev, 0));
     }
+    if (ln) r.side_used = true;
+    if (d.head_level < 0 && d.out_slot >= 0) r.prod[d.out_slot] = (unsigned char)ln;
   }
-  return true;
+  hipError_t e;
+  switch (d.op) {
+    case YL_OP_SE: {
+      YlSeP sp;
+      sp.x = p.x; sp.gate = p.out;
+      sp.w1 = L.wp; sp.b1 = L.bias; sp.w2 = L.w2p; sp.b2 = L.b2;
+      sp.B = B; sp.HW = L.in_h * L.in_w; sp.C = d.cin; sp.RD = d.cout; sp.act = d.act;
+      const bool pooled = r.pooled_slot == d.in_slot;      // the depthwise launch in front left the partial sums
+      sp.P = pooled ? r.pooled_P : yl_se_parts(sp.HW, sp.C);
+      sp.partial = se_partial(c, b0);
+      if (c->opt_bf16 == 3 && !pooled) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: squeeze-excite pooling needs the pooled depthwise launch in front of it");
+      e = yl_launch_se(sp, pooled, ls);
+      break;
+    }
+    case YL_OP_DW: {
+      // feeding a squeeze-excite gate next (efficientnetv2 MBConv): pool in the same launch
+      r.pooled_slot = -1;
+      if (i + 1 < r.lend && c->layers[i + 1].d.op == YL_OP_SE && c->layers[i + 1].d.in_slot == d.out_slot && d.res_slot < 0 &&
+          (!c->opt_bf16 || c->opt_bf16 == 3) && !(c->opt_dev & YL_DEV_DW_TILE_OFF)) {
+        const int wpi = yl_dw_pool_wpi(d.k, d.stride, d.cin, d.cout, L.out_h, L.out_w);
+        if (wpi > 0 && c->se_unit >= (size_t)wpi * d.cin) {
+          p.pool = se_partial(c, b0);
+          p.pool_wpi = wpi;
+          r.pooled_slot = d.out_slot; r.pooled_P = wpi;
+        }
+      }
+      e = ml.dw(p, ls);
+      break;
+    }
+    case YL_OP_POOL: case YL_OP_COPY: case YL_OP_LN: case YL_OP_GRN: case YL_OP_NHWC4: {
+      if (c->opt_bf16 == 3) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: the element-wise ops of the hgnetv2 / convnextv2 backbones are fp32-storage only");
+      YlOpP q;
+      memset(&q, 0, sizeof(q));
+      q.x = p.x; q.out = p.out; q.w = L.wp; q.b = L.bias;
+      q.B = B; q.H = L.in_h; q.W = L.in_w; q.C = d.cin;
+      q.OH = d.op == YL_OP_GRN ? L.in_h : L.out_h; q.OW = d.op == YL_OP_GRN ? L.in_w : L.out_w;
+      q.k = d.k; q.stride = d.stride; q.pad_t = d.pad_t; q.pad_l = d.pad_l;
+      q.ldo = d.op == YL_OP_COPY ? c->slots[d.out_slot].c : d.cin; q.ch_off = d.out_ch_off;
+      q.eps = d.eps;
+      if (d.op == YL_OP_GRN) {
+        q.P = yl_grn_parts(L.in_h * L.in_w);
+        q.partial = se_partial(c, b0);
+      }
+      e = yl_launch_op(d.op, q, ls);
+      break;
+    }
+    case YL_OP_STEM: e = ml.stem(p, ls); break;
+    case YL_OP_CONV:
+      // small-channel dense 3x3 on large grids: window-in-LDS kernel (fp32 units only; "tile_m" 6 keeps the generic kernel)
+      e = (!c->opt_bf16 && c->opt_tile_m != 6) ? yl_launch_conv_k3w(p, ls) : hipErrorNotSupported;
+      if (e == hipErrorNotSupported) e = ml.conv(p, c->opt_tile_m, ls);
+      break;
+    case YL_OP_STEMBLOCK: e = d.dw_k == 3 ? ml.stemdw(p, ls) : ml.stemblock(p, ls); break;
+    default: e = ml.dw(p, ls); break;
+  }
+  if (e == hipSuccess && YL_ACT_POSTPASS(d.act) && c->opt_bf16 == 3) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: GELU / ReLU + affine passes are fp32-storage only");
+  if (e == hipSuccess && YL_ACT_POSTPASS(d.act)) {
+    // GELU / ReLU + learnable affine (+ the residual behind it): element-wise pass over the layer's output, in place
+    YlOpP q;
+    memset(&q, 0, sizeof(q));
+    q.x = p.out; q.out = p.out;
+    q.B = B; q.OH = L.out_h; q.OW = L.out_w; q.C = d.cout;
+    q.act = d.act; q.lab_s = d.lab_scale; q.lab_b = d.lab_bias;
+    if (d.res_slot >= 0) q.res = slot_addr(c, d.res_slot, b0);
+    e = yl_launch_op(YL_OP_ACTPASS, q, ls);
+  }
+  if (e != hipSuccess) return launch_failed(c, {F_LAYER, i, 1, 1}, e);
+  if (r.evs) HIPCHK(c, hipEventRecord(r.evs[i + 1], r.st));
+  return YL_OK;
 }
 
-// depthwise 3x3 -> 1x1 expand -> 1x1 project (+residual) as ONE launch (yl_conv_dpq_kernel): layer i is the depthwise +
-// expand conv, layer i + 1 the plain 1x1 that consumes it, nothing else reads the expanded tensor, shape instantiated
-bool pair_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options) {
-  if ((!ignore_options && (!c->opt_fuse_head || c->opt_bf16)) || i + 1 >= lend) return false;
-  const DevLayer& T = c->layers[i];
-  const yl_layer& t = T.d; const yl_layer& o = c->layers[i + 1].d;
-  if (t.op != YL_OP_CONV || t.k != 1 || t.dw_k != 3 || t.dw_stride != 1 || t.c2 > 0 || t.c3 > 0 || t.head_level >= 0 ||
-      t.res_slot >= 0 || t.up_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || YL_SMOOTH(t.dw_act) || t.out_slot < 0)
-    return false;
-  if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 || o.in_slot != t.out_slot ||
-      o.cin != t.cout || YL_SMOOTH(o.act) || o.up_slot >= 0 || o.in_shift || o.res_slot == t.out_slot ||
-      o.scale_slot >= 0 || t.scale_slot >= 0)
-    return false;
-  if (T.in_h != T.out_h || T.in_w != T.out_w || !yl_dpq_supported(t.cin, t.cout, o.cout, T.out_h, T.out_w)) return false;
-  for (size_t r = 0; r < c->layers.size(); ++r) {
-    if (r == i + 1) continue;
-    const yl_layer& e = c->layers[r].d;
-    const bool reads_in = e.op != YL_OP_STEM && e.op != YL_OP_STEMBLOCK && e.in_slot == t.out_slot;
-    if (reads_in || e.res_slot == t.out_slot || e.up_slot == t.out_slot) return false;
+// Sends out one step.  *refused: the form's launcher answered hipErrorNotSupported and nothing was enqueued -- the fused
+// forms only (their 32-bit byte-offset guards depend on the batch); from any other form that answer is an error
+yl_status emit(LayerRun& r, const LaunchStep& s, bool* refused) {
+  yl_ctx* c = r.c;
+  const size_t i = s.first, n = (size_t)s.width;
+  hipError_t e = hipSuccess;
+  YlConvP ps[4];
+  switch (s.form) {
+    case F_LAYER: return run_layer(r, i);
+    case F_HEAD_RUN:                          // trunks [i, i + n), their head-output convs [i + n, i + 2n)
+      for (size_t q = 0; q < n; ++q) {
+        const DevLayer& O = c->layers[i + n + q];            // the head-output conv: weights, bias, decode targets
+        r.params(i + q, ps[q]);
+        ps[q].w3p = O.wp; ps[q].b3 = O.bias; ps[q].C3 = O.d.cout;
+        r.decode_targets(i + n + q, ps[q]);
+      }
+      e = yl_launch_conv_dpp(ps, (int)n, r.st);
+      break;
+    case F_DPQ_EXPAND:
+      r.params(i, ps[0]);
+      ps[0].w3p = nullptr;
+      e = yl_launch_conv_dpq(ps[0], r.st);
+      break;
+    case F_DPQ_PAIR: case F_DWX_CHAIN: {
+      YlConvP& pt = ps[0]; YlConvP& po = ps[1];
+      r.params(i, pt);
+      r.params(i + 1, po);
+      pt.w3p = po.wp; pt.b3 = po.bias; pt.C3 = po.N; pt.act3 = po.act;
+      if (s.form == F_DPQ_PAIR) { pt.res = po.res; pt.out = po.out; }    // the expanded tensor is not written
+      e = s.form == F_DPQ_PAIR ? yl_launch_conv_dpq(pt, r.st) : yl_launch_conv_dwx(pt, po.out, r.st);
+      if (s.form == F_DWX_CHAIN && e == hipSuccess) ++c->chain_launches;
+      break;
+    }
+    case F_SPLIT_HEAD: case F_BATCHED:
+      for (size_t q = 0; q < n; ++q) {
+        r.params(i + q, ps[q]);
+        if (s.form == F_BATCHED) continue;
+        // head-output conv of a model with mask coefficients under yl_predict: det rows through the decode epilogue (no raw
+        // rows); the coefficient part rides along as the second weight image (yl_launch_conv_multi: one pass where it pays,
+        // else a second plain 1x1 launch) and its columns go into the level rows behind the detection columns
+        // (bit-identical values: same k order)
+        const DevLayer& L = c->layers[i + q];
+        YlConvP& a = ps[q];
+        const int nd = 5 + c->C;
+        a.wp = L.wp_det; a.bias = L.b_det; a.N = nd; a.NTtot = cdiv(nd, 16); a.dec_raw = 0;
+        a.w3p = L.wp_mc; a.b3 = L.b_mc; a.C3 = c->NM;
+        a.out += nd; a.ldo = c->E;
+      }
+      e = kLaunch[c->opt_bf16].conv_multi(ps, (int)n, c->opt_tile_m, r.st);
+      break;
   }
-  return true;
-}
-
-// UIB projection -> the next block's expansion as ONE launch (yl_conv_dwx_kernel): layer i is a 1x1 conv with a stride-1
-// depthwise prologue (optional residual) writing slot S, layer i + 1 a plain 1x1 conv (no prologue, residual, upsample,
-// gate or head) reading S.  S is still written -- the next block reads it as its residual.  Options: fp32 mode, split-K
-// off (its form keeps the two launches), the automatic kernel choice, the depthwise -> 1x1 kernel and the chaining not
-// switched off
-bool chain_fusable(const yl_ctx* c, size_t i, size_t lend, bool ignore_options) {
-  if (!ignore_options && (c->opt_bf16 || c->opt_split_k || c->opt_tile_m || (c->opt_dev & (YL_DEV_CHAIN_OFF | YL_DEV_DWT_OFF))))
-    return false;
-  if (i + 1 >= lend) return false;
-  const DevLayer& T = c->layers[i];
-  const DevLayer& O = c->layers[i + 1];
-  const yl_layer& t = T.d; const yl_layer& o = O.d;
-  if (t.op != YL_OP_CONV || t.k != 1 || t.stride != 1 || t.dw_k <= 0 || t.dw_stride != 1 || t.c2 > 0 || t.c3 > 0 ||
-      t.head_level >= 0 || t.up_slot >= 0 || t.scale_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || t.out_slot < 0 ||
-      (t.res_slot >= 0 && t.act != YL_ACT_NONE))
-    return false;
-  if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.stride != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 ||
-      o.in_slot != t.out_slot || o.cin != t.cout || YL_SMOOTH(o.act) || o.res_slot >= 0 || o.up_slot >= 0 ||
-      o.scale_slot >= 0 || o.in_shift || o.out_slot < 0)
-    return false;
-  return T.in_h == T.out_h && T.in_w == T.out_w && O.in_h == T.out_h && O.in_w == T.out_w && O.out_h == T.out_h &&
-         O.out_w == T.out_w && yl_dwx_supported(t.cin, t.cout, t.dw_k, t.dw_stride, o.cout, T.out_h, T.out_w);
-}
-
-hipError_t conv_multi(const yl_ctx* c, const YlConvP* ps, int n, hipStream_t st) {
-  switch (c->opt_bf16) {
-    case 1: return yl_launch_conv_multi_bf16(ps, n, c->opt_tile_m, st);
-    case 2: return yl_launch_conv_multi_f16(ps, n, c->opt_tile_m, st);
-    case 3: return yl_launch_conv_multi_f16s(ps, n, c->opt_tile_m, st);
-    default: return yl_launch_conv_multi(ps, n, c->opt_tile_m, st);
-  }
+  const unsigned fused = form_bit(F_HEAD_RUN) | form_bit(F_DPQ_EXPAND) | form_bit(F_DPQ_PAIR) | form_bit(F_DWX_CHAIN);
+  *refused = e == hipErrorNotSupported && (fused & form_bit(s.form));
+  if (e != hipSuccess && !*refused) return launch_failed(c, s, e);
+  return YL_OK;
 }
 
 yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* level_out, hipStream_t st,
@@ -703,37 +941,19 @@ yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* lev
                      const yl_post_cfg* fuse = nullptr /*non-null: head outputs decode in their epilogue*/,
                      int lo = 0, int hi = -1 /*layer range [lo, hi), -1 = to the end*/) {
   if (evs) HIPCHK(c, hipEventRecord(evs[0], st));
-  // two lanes (see yl_ctx::lane): lane-1 layers go to the chunk's side stream; an event edge is inserted
-  // wherever a layer reads a slot produced on the other lane, and the side stream is joined at the end.
-  // Per-layer timing (evs) keeps everything on one stream.
-  const bool lanes = !evs && c->opt_lanes && !c->lane.empty() && chunk >= 0 && chunk < 4;
-  hipStream_t sd = nullptr;
-  if (lanes) {
+  LayerRun r{c, x, b0, B, level_out, st, evs, chunk, fuse, hi < 0 ? c->layers.size() : (size_t)hi};
+  // side lanes: an event edge is inserted wherever a layer reads a slot produced on the other lane (run_layer), and the
+  // side stream is joined at the end.  Per-layer timing (evs) keeps everything on one stream.
+  r.lanes = !evs && c->opt_lanes && !c->lane.empty() && chunk >= 0 && chunk < 4;
+  if (r.lanes) {
     if (!c->side[chunk]) HIPCHK(c, hipStreamCreateWithFlags(&c->side[chunk], hipStreamNonBlocking));
     if (!c->ev_la[chunk]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_la[chunk], hipEventDisableTiming));
     if (!c->ev_lb[chunk]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_lb[chunk], hipEventDisableTiming));
-    sd = c->side[chunk];
+    r.sd = c->side[chunk];
   }
-  std::vector<unsigned char> prod(c->slots.size(), 0);     // lane that produced each slot
-  bool side_used = false;
-  int pooled_slot = -1, pooled_P = 0;                      // slot whose partial channel sums the last depthwise launch left
-  auto params = [&](size_t i, YlConvP& p) {
-    layer_params(c, c->layers[i], b0, B, x, level_out, p);
-    const yl_layer& d = c->layers[i].d;
-    if (fuse && d.head_level >= 0) {
-      const int l = d.head_level, S = c->level_S[l];
-      const size_t o = (size_t)b0 * c->N;
-      p.dec_boxes = c->ws_boxes + o; p.dec_scores = c->ws_scores + o; p.dec_cls = c->ws_cls + o;
-      p.dec_N = c->N; p.dec_off = c->level_off[l] + c->layers[i].head_anchor * S * S; p.dec_C = c->C;
-      p.dec_mode = fuse->mode; p.dec_center = fuse->center_mode; p.dec_wh = fuse->wh_mode;
-      p.dec_raw = c->NM > 0 ? 1 : 0;                          // mask coefficients are read from the raw rows
-      p.dec_stride = (float)((double)c->img_size / (double)S);   // utils_ms.py:71, as fill_levels
-      p.dec_hi = (float)(c->img_size - 1);
-    }
-  };
-  const size_t lend = hi < 0 ? c->layers.size() : (size_t)hi;
-  for (size_t i = (size_t)lo; i < lend;) {
-    const yl_layer& d = c->layers[i].d;
+  r.prod.assign(c->slots.size(), 0);
+  const unsigned allowed = allowed_forms(c, evs != nullptr || r.lanes, fuse != nullptr);
+  for (size_t i = (size_t)lo; i < r.lend;) {
 #ifdef YL_VARIANT_SKIP_LAYERS
     // VARIANT BUILDS ONLY (tools/build_variant.sh ... -DYL_VARIANT_SKIP_LAYERS; never in libyololite_hip.so): leave out the
     // layers YL_SKIP="lo-hi" -- results are WRONG; answers "what would the step be if these launches were free"
@@ -743,235 +963,23 @@ yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* lev
       if ((int)i >= slo && (int)i <= shi) { if (evs) hipEventRecord(evs[i + 1], st); ++i; continue; }
     }
 #endif
-    // ---- level-batched run starting at i (not under per-layer timing, not with side lanes)
-    size_t gend = i + 1;
-    if (!evs && !lanes && c->opt_batch_levels && d.op == YL_OP_CONV) gend = layer_group_end(c, i, lend);
-    if (fuse && !evs && !lanes && d.op == YL_OP_CONV && d.dw_k == 3 && head_run_fusable(c, i, gend, lend)) {
-      YlConvP ps[4];
-      const size_t n = gend - i;
-      for (size_t q = 0; q < n; ++q) {
-        YlConvP o;
-        params(i + q, ps[q]);
-        params(gend + q, o);                               // the head-output conv: weights, bias, decode targets
-        ps[q].w3p = o.wp; ps[q].b3 = o.bias; ps[q].C3 = o.N;
-        ps[q].dec_boxes = o.dec_boxes; ps[q].dec_scores = o.dec_scores; ps[q].dec_cls = o.dec_cls;
-        ps[q].dec_N = o.dec_N; ps[q].dec_off = o.dec_off; ps[q].dec_C = o.dec_C; ps[q].dec_mode = o.dec_mode;
-        ps[q].dec_center = o.dec_center; ps[q].dec_wh = o.dec_wh; ps[q].dec_raw = o.dec_raw;
-        ps[q].dec_stride = o.dec_stride; ps[q].dec_hi = o.dec_hi;
-      }
-      const hipError_t e = yl_launch_conv_dpp(ps, (int)n, st);
-      if (e == hipSuccess) { i = gend + n; continue; }
-      if (e != hipErrorNotSupported) {
-        char b[256];
-        snprintf(b, sizeof(b), "layers %zu..%zu head launch failed: %s", i, gend + n - 1, hipGetErrorString(e));
-        return fail(c, YL_ERR_HIP, b);
-      }
+    LaunchStep step;
+    for (unsigned forms = allowed;; forms &= ~form_bit(step.form)) {      // a refused form: ask again without it
+      step = next_step(c, i, r.lend, forms);
+      bool refused = false;
+      const yl_status s = emit(r, step, &refused);
+      if (s != YL_OK) return s;
+      if (!refused) break;
     }
-    // wide depthwise 3x3 -> 1x1 layer (more than 96 outputs) on its own: yl_conv_dpq_kernel's expand-only form computes
-    // the depthwise part once per pixel
-    if (!evs && !lanes && gend == i + 1 && d.op == YL_OP_CONV && d.dw_k == 3 && d.dw_stride == 1 && d.k == 1 && d.c2 == 0 &&
-        d.c3 == 0 && c->opt_fuse_head && !c->opt_bf16 && d.head_level < 0 && d.res_slot < 0 && d.up_slot < 0 && !d.in_shift &&
-        d.cout > 96 && !pair_fusable(c, i, lend, false) && c->layers[i].in_h == c->layers[i].out_h &&
-        yl_dpq_supported(d.cin, d.cout, 0, c->layers[i].out_h, c->layers[i].out_w)) {
-      YlConvP pt;
-      params(i, pt);
-      pt.w3p = nullptr;
-      const hipError_t e = yl_launch_conv_dpq(pt, st);
-      if (e == hipSuccess) { ++i; continue; }
-      if (e != hipErrorNotSupported) {
-        char b[256];
-        snprintf(b, sizeof(b), "layer %zu launch failed: %s", i, hipGetErrorString(e));
-        return fail(c, YL_ERR_HIP, b);
-      }
-    }
-    if (!evs && !lanes && gend == i + 1 && d.op == YL_OP_CONV && d.dw_k == 3 && pair_fusable(c, i, lend, false)) {
-      YlConvP pt, po;
-      params(i, pt);
-      params(i + 1, po);
-      pt.w3p = po.wp; pt.b3 = po.bias; pt.C3 = po.N; pt.act3 = po.act; pt.res = po.res; pt.out = po.out;
-      const hipError_t e = yl_launch_conv_dpq(pt, st);
-      if (e == hipSuccess) { i += 2; continue; }
-      if (e != hipErrorNotSupported) {
-        char b[256];
-        snprintf(b, sizeof(b), "layers %zu..%zu fused launch failed: %s", i, i + 1, hipGetErrorString(e));
-        return fail(c, YL_ERR_HIP, b);
-      }
-    }
-    if (!evs && !lanes && gend == i + 1 && d.op == YL_OP_CONV && d.dw_k > 0 && chain_fusable(c, i, lend, false)) {
-      YlConvP pt, po;
-      params(i, pt);
-      params(i + 1, po);
-      pt.w3p = po.wp; pt.b3 = po.bias; pt.C3 = po.N; pt.act3 = po.act;
-      const hipError_t e = yl_launch_conv_dwx(pt, po.out, st);
-      if (e == hipSuccess) { ++c->chain_launches; i += 2; continue; }
-      if (e != hipErrorNotSupported) {
-        char b[256];
-        snprintf(b, sizeof(b), "layers %zu..%zu chained launch failed: %s", i, i + 1, hipGetErrorString(e));
-        return fail(c, YL_ERR_HIP, b);
-      }
-    }
-    // head-output conv(s) of a model with mask coefficients under yl_predict: det rows through the decode epilogue (no raw
-    // rows), the mask coefficients as a second plain 1x1 launch into the level rows (bit-identical values: same k order)
-    if (fuse && !evs && !lanes && d.op == YL_OP_CONV && d.head_level >= 0 && c->layers[i].wp_det && c->opt_fuse_head) {
-      bool all = true;
-      for (size_t q = i; q < gend; ++q) all = all && c->layers[q].wp_det != nullptr;
-      if (all) {
-        YlConvP pd[4];
-        const int nd = 5 + c->C;
-        for (size_t q = i; q < gend; ++q) {
-          YlConvP o;
-          params(q, o);
-          YlConvP& a = pd[q - i];
-          a = o; a.wp = c->layers[q].wp_det; a.bias = c->layers[q].b_det; a.N = nd; a.NTtot = cdiv(nd, 16); a.dec_raw = 0;
-          // the coefficient part rides along as the second weight image (yl_launch_conv_multi: one pass where it pays, else a
-          // second plain 1x1 launch): its columns go into the level rows behind the detection columns
-          a.w3p = c->layers[q].wp_mc; a.b3 = c->layers[q].b_mc; a.C3 = c->NM;
-          a.out = o.out + nd; a.ldo = c->E;
-        }
-        const int n = (int)(gend - i);
-        const hipError_t e = conv_multi(c, pd, n, st);
-        if (e != hipSuccess) {
-          char b[256];
-          snprintf(b, sizeof(b), "layers %zu..%zu split head launch failed: %s", i, gend - 1, hipGetErrorString(e));
-          return fail(c, YL_ERR_HIP, b);
-        }
-        i = gend;
-        continue;
-      }
-    }
-    if (gend - i > 1) {
-      YlConvP ps[4];
-      for (size_t q = i; q < gend; ++q) params(q, ps[q - i]);
-      const hipError_t e = conv_multi(c, ps, (int)(gend - i), st);
-      if (e != hipSuccess) {
-        char b[256];
-        snprintf(b, sizeof(b), "layers %zu..%zu batched launch failed: %s", i, gend - 1, hipGetErrorString(e));
-        return fail(c, YL_ERR_HIP, b);
-      }
-      i = gend;
-      continue;
-    }
-    YlConvP p;
-    params(i, p);
-    const int ln = (lanes && c->lane[i]) ? 1 : 0;
-    hipStream_t ls = ln ? sd : st;
-    if (lanes) {
-      bool cross = false;
-      const int ins[4] = {d.in_slot, d.res_slot, d.up_slot, d.scale_slot};
-      for (int k = 0; k < 4; ++k)
-        if (ins[k] >= 0 && d.op != YL_OP_STEM && d.op != YL_OP_STEMBLOCK && d.op != YL_OP_NHWC4 && prod[ins[k]] != ln) cross = true;
-      if (ln == 1 && !side_used) cross = true;             // first side launch: order after everything enqueued so far
-      if (cross) {
-        hipEvent_t ev = ln ? c->ev_la[chunk] : c->ev_lb[chunk];
-        HIPCHK(c, hipEventRecord(ev, ln ? st : sd));
-        HIPCHK(c, hipStreamWaitEvent(ls, ev, 0));
-      }
-      if (ln) side_used = true;
-      if (d.head_level < 0 && d.out_slot >= 0) prod[d.out_slot] = (unsigned char)ln;
-    }
-    hipError_t e;
-    switch (d.op) {
-      case YL_OP_SE: {
-        const DevLayer& L = c->layers[i];
-        YlSeP sp;
-        sp.x = p.x; sp.gate = p.out;
-        sp.w1 = L.wp; sp.b1 = L.bias; sp.w2 = L.w2p; sp.b2 = L.b2;
-        sp.B = B; sp.HW = L.in_h * L.in_w; sp.C = d.cin; sp.RD = d.cout; sp.act = d.act;
-        const bool pooled = pooled_slot == d.in_slot;        // the depthwise launch in front left the partial sums
-        sp.P = pooled ? pooled_P : yl_se_parts(sp.HW, sp.C);
-        int ch = 0;                                          // the chunk arena these images live in
-        while (ch + 1 < c->plan_n && b0 >= c->plan_b0[ch + 1]) ++ch;
-        sp.partial = c->se_scratch[ch] + (size_t)(b0 - c->plan_b0[ch]) * c->se_unit;
-        if (c->opt_bf16 == 3 && !pooled) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: squeeze-excite pooling needs the pooled depthwise launch in front of it");
-        e = yl_launch_se(sp, pooled, ls);
-        break;
-      }
-      case YL_OP_DW: {
-        // feeding a squeeze-excite gate next (efficientnetv2 MBConv): pool in the same launch
-        pooled_slot = -1;
-        if (i + 1 < lend && c->layers[i + 1].d.op == YL_OP_SE && c->layers[i + 1].d.in_slot == d.out_slot && d.res_slot < 0 &&
-            (!c->opt_bf16 || c->opt_bf16 == 3) && !(c->opt_dev & YL_DEV_DW_TILE_OFF)) {
-          const int wpi = yl_dw_pool_wpi(d.k, d.stride, d.cin, d.cout, c->layers[i].out_h, c->layers[i].out_w);
-          if (wpi > 0 && c->se_unit >= (size_t)wpi * d.cin) {
-            int ch = 0;
-            while (ch + 1 < c->plan_n && b0 >= c->plan_b0[ch + 1]) ++ch;
-            p.pool = c->se_scratch[ch] + (size_t)(b0 - c->plan_b0[ch]) * c->se_unit;
-            p.pool_wpi = wpi;
-            pooled_slot = d.out_slot; pooled_P = wpi;
-          }
-        }
-        e = c->opt_bf16 == 3 ? yl_launch_dw_f16s(p, ls) : yl_launch_dw(p, ls);
-        break;
-      }
-      case YL_OP_POOL: case YL_OP_COPY: case YL_OP_LN: case YL_OP_GRN: case YL_OP_NHWC4: {
-        if (c->opt_bf16 == 3) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: the element-wise ops of the hgnetv2 / convnextv2 backbones are fp32-storage only");
-        const DevLayer& L = c->layers[i];
-        YlOpP q;
-        memset(&q, 0, sizeof(q));
-        q.x = p.x; q.out = p.out; q.w = L.wp; q.b = L.bias;
-        q.B = B; q.H = L.in_h; q.W = L.in_w; q.C = d.cin;
-        q.OH = d.op == YL_OP_GRN ? L.in_h : L.out_h; q.OW = d.op == YL_OP_GRN ? L.in_w : L.out_w;
-        q.k = d.k; q.stride = d.stride; q.pad_t = d.pad_t; q.pad_l = d.pad_l;
-        q.ldo = d.op == YL_OP_COPY ? c->slots[d.out_slot].c : d.cin; q.ch_off = d.out_ch_off;
-        q.eps = d.eps;
-        if (d.op == YL_OP_GRN) {
-          q.P = yl_grn_parts(L.in_h * L.in_w);
-          int ch = 0;                                          // the chunk arena these images live in
-          while (ch + 1 < c->plan_n && b0 >= c->plan_b0[ch + 1]) ++ch;
-          q.partial = c->se_scratch[ch] + (size_t)(b0 - c->plan_b0[ch]) * c->se_unit;
-        }
-        e = yl_launch_op(d.op, q, ls);
-        break;
-      }
-      case YL_OP_STEM: e = c->opt_bf16 == 3 ? yl_launch_stem_f16s(p, ls) : yl_launch_stem(p, ls); break;
-      case YL_OP_CONV:
-        // small-channel dense 3x3 on large grids: window-in-LDS kernel (fp32 units only; "tile_m" 6 keeps the generic kernel)
-        e = (!c->opt_bf16 && c->opt_tile_m != 6) ? yl_launch_conv_k3w(p, ls) : hipErrorNotSupported;
-        if (e != hipErrorNotSupported) break;
-        e = c->opt_bf16 == 1 ? yl_launch_conv_bf16(p, c->opt_tile_m, ls)
-            : c->opt_bf16 == 2 ? yl_launch_conv_f16(p, c->opt_tile_m, ls)
-            : c->opt_bf16 == 3 ? yl_launch_conv_f16s(p, c->opt_tile_m, ls) : yl_launch_conv(p, c->opt_tile_m, ls);
-        break;
-      case YL_OP_STEMBLOCK:
-        if (d.dw_k == 3)
-          e = c->opt_bf16 == 1 ? yl_launch_stemdw_bf16(p, ls) : c->opt_bf16 == 2 ? yl_launch_stemdw_f16(p, ls)
-              : c->opt_bf16 == 3 ? yl_launch_stemdw_f16s(p, ls) : yl_launch_stemdw(p, ls);
-        else
-        e = c->opt_bf16 == 1 ? yl_launch_stemblock_bf16(p, ls) : c->opt_bf16 == 2 ? yl_launch_stemblock_f16(p, ls)
-            : c->opt_bf16 == 3 ? yl_launch_stemblock_f16s(p, ls) : yl_launch_stemblock(p, ls);
-        break;
-      default: e = c->opt_bf16 == 3 ? yl_launch_dw_f16s(p, ls) : yl_launch_dw(p, ls); break;
-    }
-    if (e == hipSuccess && YL_ACT_POSTPASS(d.act) && c->opt_bf16 == 3) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: GELU / ReLU + affine passes are fp32-storage only");
-    if (e == hipSuccess && YL_ACT_POSTPASS(d.act)) {
-      // GELU / ReLU + learnable affine (+ the residual behind it): element-wise pass over the layer's output, in place
-      const DevLayer& L = c->layers[i];
-      YlOpP q;
-      memset(&q, 0, sizeof(q));
-      q.x = p.out; q.out = p.out;
-      q.B = B; q.OH = L.out_h; q.OW = L.out_w; q.C = d.cout;
-      q.act = d.act; q.lab_s = d.lab_scale; q.lab_b = d.lab_bias;
-      if (d.res_slot >= 0) q.res = slot_addr(c, d.res_slot, b0);
-      e = yl_launch_op(YL_OP_ACTPASS, q, ls);
-    }
-    if (e != hipSuccess) {
-      char b[256];
-      snprintf(b, sizeof(b), "layer %zu launch failed: %s", i, hipGetErrorString(e));
-      return fail(c, YL_ERR_HIP, b);
-    }
-    if (evs) HIPCHK(c, hipEventRecord(evs[i + 1], st));
-    ++i;
+    i += (size_t)step.layers;
   }
-  if (side_used) {                                          // join: decode / the caller see both lanes
-    HIPCHK(c, hipEventRecord(c->ev_lb[chunk], sd));
+  if (r.side_used) {                                          // join: decode / the caller see both lanes
+    HIPCHK(c, hipEventRecord(c->ev_lb[chunk], r.sd));
     HIPCHK(c, hipStreamWaitEvent(st, c->ev_lb[chunk], 0));
   }
   return YL_OK;
 }
 
-// lane assignment from the slot graph: a layer goes to lane 1 iff everything it feeds ends in head outputs of
-// levels >= 1 only (the finest level's chain, the backbone, the top-down laterals and the prototype branch stay
-// on lane 0)
 // the longest run of consecutive layers whose input AND output grids are <= 1/16 of the image (the 40x40 / 20x20
 // stages of the backbone and the coarse part of the top-down pass): the part of the network that is chunked over
 // the internal streams by the hybrid plan
@@ -1003,6 +1011,18 @@ void assign_small_run(yl_ctx* c) {
   c->tiny_lo = best_lo; c->tiny_hi = best_hi;
 }
 
+// readers[s]: layer operands that read slot s -- the input (the stem-type ops read the caller's image instead), the
+// residual and the upsampled operand (not scale_slot: gates are written by YL_OP_SE, never by a layer a fused step swallows)
+void count_readers(yl_ctx* c) {
+  c->readers.assign(c->slots.size(), 0);
+  for (const DevLayer& L : c->layers)
+    for (int s : {(L.d.op == YL_OP_STEM || L.d.op == YL_OP_STEMBLOCK) ? -1 : L.d.in_slot, L.d.res_slot, L.d.up_slot})
+      if (s >= 0 && (size_t)s < c->readers.size()) ++c->readers[s];   // (YL_OP_NHWC4's in_slot is not validated: unused)
+}
+
+// lane assignment from the slot graph: a layer goes to lane 1 iff everything it feeds ends in head outputs of
+// levels >= 1 only (the finest level's chain, the backbone, the top-down laterals and the prototype branch stay
+// on lane 0)
 void assign_lanes(yl_ctx* c) {
   const size_t n = c->layers.size();
   c->lane.assign(n, 0);
@@ -1407,6 +1427,7 @@ yl_status yl_clone(const yl_ctx* src, yl_ctx** out) {
   c->se_unit = src->se_unit;
   c->wino_max_hw = src->wino_max_hw;
   c->lane = src->lane;
+  c->readers = src->readers;
   c->small_lo = src->small_lo; c->small_hi = src->small_hi; c->tiny_lo = src->tiny_lo; c->tiny_hi = src->tiny_hi;
   // the options as they are now; activation arenas, workspaces, streams, events and cached graphs are the clone's own
   c->opt_reuse = src->opt_reuse; c->opt_pre_norm = src->opt_pre_norm; c->opt_graph = src->opt_graph; c->opt_tile_m = src->opt_tile_m;
@@ -1766,6 +1787,7 @@ yl_status yl_create(const yl_model_desc* d, int32_t device_id, yl_ctx** out) {
   }
   assign_lanes(c);
   assign_small_run(c);
+  count_readers(c);
   return YL_OK;
 }
 
