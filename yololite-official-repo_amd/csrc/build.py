@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-eleven translation units (three of them compiled three times: fp32, bf16-MFMA and fp16-MFMA builds), one shared library with a plain C ABI (include/yololite_hip.h).
+twelve translation units (three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
 """

@@ -739,13 +739,14 @@ struct ModeLaunchers {
   hipError_t (*conv_multi)(const YlConvP*, int, int, hipStream_t);
   hipError_t (*stem)(const YlConvP&, hipStream_t), (*dw)(const YlConvP&, hipStream_t);
   hipError_t (*stemblock)(const YlConvP&, hipStream_t), (*stemdw)(const YlConvP&, hipStream_t);
+  hipError_t (*conv_init)(), (*convc_init)(), (*stemblock_init)();      // dynamic-LDS limits of the mode's kernels (yl_create)
 };
-const ModeLaunchers kLaunch[4] = {
-    {yl_launch_conv, yl_launch_conv_multi, yl_launch_stem, yl_launch_dw, yl_launch_stemblock, yl_launch_stemdw},
-    {yl_launch_conv_bf16, yl_launch_conv_multi_bf16, yl_launch_stem, yl_launch_dw, yl_launch_stemblock_bf16, yl_launch_stemdw_bf16},
-    {yl_launch_conv_f16, yl_launch_conv_multi_f16, yl_launch_stem, yl_launch_dw, yl_launch_stemblock_f16, yl_launch_stemdw_f16},
-    {yl_launch_conv_f16s, yl_launch_conv_multi_f16s, yl_launch_stem_f16s, yl_launch_dw_f16s, yl_launch_stemblock_f16s, yl_launch_stemdw_f16s},
-};
+// S: the mode's symbol suffix; SD: the suffix of its stem / depthwise launchers
+#define YL_MODE_LAUNCHERS(S, SD)                                                                             \
+  {yl_launch_conv##S, yl_launch_conv_multi##S, yl_launch_stem##SD, yl_launch_dw##SD, yl_launch_stemblock##S, \
+   yl_launch_stemdw##S, yl_conv_init##S, yl_convc_init##S, yl_stemblock_init##S}
+const ModeLaunchers kLaunch[4] = {YL_MODE_LAUNCHERS(, ), YL_MODE_LAUNCHERS(_bf16, ), YL_MODE_LAUNCHERS(_f16, ),
+                                  YL_MODE_LAUNCHERS(_f16s, _f16s)};
 
 yl_status launch_failed(yl_ctx* c, const LaunchStep& s, hipError_t e) {
   static const char* const what[] = {"", "batched ", "head ", "expand-only ", "fused ", "chained ", "split head "};   // by LaunchForm
@@ -1459,12 +1460,9 @@ yl_status yl_create(const yl_model_desc* d, int32_t device_id, yl_ctx** out) {
   if (hipSetDevice(device_id) != hipSuccess) return YL_ERR_HIP;
   if (device_id >= 64) return YL_ERR_UNSUPPORTED;
   if (!g_inited[device_id]) {
-    if (yl_post_init() != hipSuccess || yl_conv_init() != hipSuccess || yl_stemblock_init() != hipSuccess ||
-        yl_conv_init_bf16() != hipSuccess || yl_stemblock_init_bf16() != hipSuccess || yl_convc_init() != hipSuccess ||
-        yl_convc_init_bf16() != hipSuccess || yl_dpp_init() != hipSuccess || yl_conv_init_f16() != hipSuccess ||
-        yl_stemblock_init_f16() != hipSuccess || yl_convc_init_f16() != hipSuccess || yl_conv_init_f16s() != hipSuccess ||
-        yl_stemblock_init_f16s() != hipSuccess || yl_convc_init_f16s() != hipSuccess)
-      return YL_ERR_HIP;
+    for (const ModeLaunchers& ml : kLaunch)
+      if (ml.conv_init() != hipSuccess || ml.convc_init() != hipSuccess || ml.stemblock_init() != hipSuccess) return YL_ERR_HIP;
+    if (yl_post_init() != hipSuccess || yl_dpp_init() != hipSuccess) return YL_ERR_HIP;     // (fp32-only units)
     g_inited[device_id] = true;
   }
   yl_ctx* c = new (std::nothrow) yl_ctx();

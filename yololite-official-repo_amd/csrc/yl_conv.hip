@@ -50,9 +50,6 @@
 #endif
 #include <stdio.h>
 #include <stdlib.h>
-#include <map>
-#include <mutex>
-#include <utility>
 #include "yl_internal.h"
 #include <math.h>
 
@@ -1060,105 +1057,57 @@ __global__ __launch_bounds__(256, 2) void yl_dw_tile_kernel(YlConvP p) {
 // ------------------------------------------------------------------------------------------------
 #define YL_CONV_LDS_MAX (128 * 1024)
 
-template <int NT, int MT, int MODE>
-static hipError_t yl_conv_attr() {
-  return hipFuncSetAttribute((const void*)yl_conv_mfma_kernel<NT, MT, MODE>,
-                             hipFuncAttributeMaxDynamicSharedMemorySize, YL_CONV_LDS_MAX);
-}
-template <int NT, int MT>
-static hipError_t yl_conv_attr_modes() {
-  hipError_t e;
-  if ((e = yl_conv_attr<NT, MT, YL_CM_PW>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr<NT, MT, YL_CM_KXK>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr<NT, MT, YL_CM_DW3>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr<NT, MT, YL_CM_DW5>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr<NT, MT, YL_CM_PWSC>()) != hipSuccess) return e;
-  return yl_conv_attr<NT, MT, YL_CM_DWPRO>();
-}
-template <int MT>
-static hipError_t yl_conv_attr_nt() {
-  hipError_t e;
-  if ((e = yl_conv_attr_modes<1, MT>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr_modes<2, MT>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr_modes<3, MT>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr_modes<4, MT>()) != hipSuccess) return e;
-  if ((e = yl_conv_attr_modes<6, MT>()) != hipSuccess) return e;
-  return yl_conv_attr_modes<8, MT>();
-}
 #define YL_DWH_LDS_MAX (144 * 1024)
-// persistent grids are sized to what is co-resident (blocks/CU from the occupancy query x 256 CUs): a
-// block that has to queue behind another one re-stages the whole weight chunk into LDS for nothing
-template <typename K>
-static int yl_resident_blocks(K kernel, size_t lds) {
-  // the occupancy query costs the host ~10 us: asked once per (kernel, LDS size), then served from a small cache
-  // (eager launches of the 20-70 us layers were host-bound otherwise; graph replays never come here)
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> cache;
-  const std::pair<const void*, size_t> key((const void*)kernel, lds);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kernel, 256, lds) != hipSuccess || nb < 1) nb = 1;
-  if (nb > 4) nb = 4;
-  cache[key] = nb * YL_NUM_CU;
-  return nb * YL_NUM_CU;
+
+// The instantiations of the three kernel families of this unit, each written once; yl_conv_init, the occupancy query
+// and the launch all go through these tables.
+// n-tiles per workgroup of the persistent kernels: NT in {1, 2, 3, 4, 6, 8}, as the first index of their tables
+#define YL_NT_LIST(X) {X(1), X(2), X(3), X(4), X(6), X(8)}
+static int yl_nt_index(int NT) { return NT <= 4 ? NT - 1 : NT == 6 ? 4 : 5; }
+
+// yl_conv_mfma_kernel<NT, MT, MODE>: every NT x MT in {1, 2} x the six modes, as [nt index][MT - 1][YL_CM_*] (no mode 4)
+#define YL_MFMA_MODES(NT, MT)                                                                                            \
+  {yl_conv_mfma_kernel<NT, MT, YL_CM_PW>, yl_conv_mfma_kernel<NT, MT, YL_CM_KXK>, yl_conv_mfma_kernel<NT, MT, YL_CM_DWPRO>, \
+   yl_conv_mfma_kernel<NT, MT, YL_CM_DW3>, nullptr, yl_conv_mfma_kernel<NT, MT, YL_CM_DW5>, yl_conv_mfma_kernel<NT, MT, YL_CM_PWSC>}
+#define YL_MFMA_MTS(NT) {YL_MFMA_MODES(NT, 1), YL_MFMA_MODES(NT, 2)}
+static const YlMultiKernel yl_mfma_kernels[6][2][7] = YL_NT_LIST(YL_MFMA_MTS);
+
+// yl_conv_dwh_kernel<NT, DK, DS>: every NT x depthwise 3x3 / 5x5 x stride 1 / 2, as [nt index][DK == 5][DS == 2]
+#define YL_DWH_SHAPES(NT) \
+  {{yl_conv_dwh_kernel<NT, 3, 1>, yl_conv_dwh_kernel<NT, 3, 2>}, {yl_conv_dwh_kernel<NT, 5, 1>, yl_conv_dwh_kernel<NT, 5, 2>}}
+static const YlMultiKernel yl_dwh_kernels[6][2][2] = YL_NT_LIST(YL_DWH_SHAPES);
+
+// yl_uib_kernel<NT, DK, KBI>: NT (projection n-tiles) x DK x KBI (input k-blocks)
+#define YL_UIB_SHAPES(X)                                                           \
+  X(1, 3, 1) X(2, 3, 1) X(1, 5, 1) X(2, 5, 2)          /* tiny test nets */            \
+  X(3, 3, 3) X(4, 3, 4) X(4, 5, 4) X(3, 5, 3)          /* mobilenetv4_conv_small_050 */ \
+  X(6, 3, 6) X(8, 3, 8) X(8, 5, 8) X(6, 5, 6)          /* mobilenetv4_conv_small */     \
+  X(2, 3, 2) X(2, 5, 1)
+static YlConvKernel yl_uib_kernel_of(int NT, int DK, int KBI) {
+#define YL_UIB_PICK(A, B, C) if (NT == A && DK == B && KBI == C) return yl_uib_kernel<A, B, C>;
+  YL_UIB_SHAPES(YL_UIB_PICK)
+#undef YL_UIB_PICK
+  return nullptr;
 }
 
-static hipError_t yl_uib_dispatch(const YlConvP& p, size_t lds, hipStream_t st, bool attr_only, int NT, int DK, int KBI);
-template <int NT, int DK, int DS>
-static hipError_t yl_dwh_attr() {
-  return hipFuncSetAttribute((const void*)yl_conv_dwh_kernel<NT, DK, DS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             YL_DWH_LDS_MAX);
-}
-template <int NT>
-static hipError_t yl_dwh_attr_all() {
-  hipError_t e;
-  if ((e = yl_dwh_attr<NT, 3, 1>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr<NT, 3, 2>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr<NT, 5, 1>()) != hipSuccess) return e;
-  return yl_dwh_attr<NT, 5, 2>();
-}
 hipError_t yl_conv_init() {
-  hipError_t e = yl_conv_attr_nt<1>();
-  if (e != hipSuccess) return e;
-  if ((e = yl_conv_attr_nt<2>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr_all<1>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr_all<2>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr_all<3>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr_all<4>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr_all<6>()) != hipSuccess) return e;
-  if ((e = yl_dwh_attr_all<8>()) != hipSuccess) return e;
-  YlConvP dummy{};
-  return yl_uib_dispatch(dummy, 0, nullptr, true, 0, 0, 0);
+  hipError_t e = yl_set_lds_cap(yl_mfma_kernels, YL_CONV_LDS_MAX);
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_dwh_kernels, YL_DWH_LDS_MAX);
+#define YL_UIB_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(yl_uib_kernel<A, B, C>, YL_DWH_LDS_MAX);
+  YL_UIB_SHAPES(YL_UIB_CAP)
+#undef YL_UIB_CAP
+  return e;
 }
 
-template <int NT, int DK, int KBI>
-static hipError_t yl_uib_one(const YlConvP& p, size_t lds, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_uib_kernel<NT, DK, KBI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               YL_DWH_LDS_MAX);
+// hipErrorInvalidValue: shape not instantiated (yl_uib_supported tells the host compiler beforehand)
+static hipError_t yl_uib_go(const YlConvP& p, size_t lds, hipStream_t st, int NT, int DK, int KBI) {
+  const YlConvKernel kern = yl_uib_kernel_of(NT, DK, KBI);
+  if (!kern) return hipErrorInvalidValue;
   const long wtiles = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
-  int gx = yl_resident_blocks(yl_uib_kernel<NT, DK, KBI>, lds);
+  int gx = yl_resident_blocks((const void*)kern, 256, lds, 4);
   if (gx > (wtiles + 3) / 4) gx = (int)((wtiles + 3) / 4);
-  hipLaunchKernelGGL((yl_uib_kernel<NT, DK, KBI>), dim3(gx), dim3(256), lds, st, p);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(256), lds, st, p);
   return hipGetLastError();
-}
-// instantiated shapes: NT (projection n-tiles) x DK x KBI (input k-blocks)
-static hipError_t yl_uib_dispatch(const YlConvP& p, size_t lds, hipStream_t st, bool attr_only, int NT, int DK, int KBI) {
-  hipError_t e = hipSuccess;
-  bool hit = false;
-#define UIB_CASE(A, B, C)                                                         \
-  if (attr_only || (NT == A && DK == B && KBI == C)) {                            \
-    hit = true;                                                                   \
-    if ((e = yl_uib_one<A, B, C>(p, lds, st, attr_only)) != hipSuccess) return e; \
-  }
-  UIB_CASE(1, 3, 1) UIB_CASE(2, 3, 1) UIB_CASE(1, 5, 1) UIB_CASE(2, 5, 2)          // tiny test nets
-  UIB_CASE(3, 3, 3) UIB_CASE(4, 3, 4) UIB_CASE(4, 5, 4) UIB_CASE(3, 5, 3)          // mobilenetv4_conv_small_050
-  UIB_CASE(6, 3, 6) UIB_CASE(8, 3, 8) UIB_CASE(8, 5, 8) UIB_CASE(6, 5, 6)          // mobilenetv4_conv_small
-  UIB_CASE(2, 3, 2) UIB_CASE(2, 5, 1)
-#undef UIB_CASE
-  return hit ? e : hipErrorInvalidValue;
 }
 
 size_t yl_uib_lds_bytes(int Cmid, int NT, int dk) {
@@ -1174,73 +1123,7 @@ bool yl_uib_supported(int c1, int cmid, int n, int dk) {
   for (int i = 0; i < 6; ++i) if (nts[i] >= ntt) { NT = nts[i]; break; }
   if (!NT || (dk != 3 && dk != 5)) return false;
   if (yl_uib_lds_bytes(cmid, NT, dk) > YL_DWH_LDS_MAX) return false;
-  YlConvP p{};
-  // shape table of yl_uib_dispatch
-  const int T[][3] = {{1,3,1},{2,3,1},{1,5,1},{2,5,2},{3,3,3},{4,3,4},{4,5,4},{3,5,3},{6,3,6},{8,3,8},{8,5,8},{6,5,6},{2,3,2},{2,5,1}};
-  for (auto& t : T) if (t[0] == NT && t[1] == dk && t[2] == kbi) return true;
-  (void)p;
-  return false;
-}
-
-template <int NT>
-static int yl_dwh_resident(const YlConvP& p, size_t lds) {
-  if (p.dw_k == 3 && p.dw_stride == 1) return yl_resident_blocks(yl_conv_dwh_kernel<NT, 3, 1>, lds);
-  if (p.dw_k == 3 && p.dw_stride == 2) return yl_resident_blocks(yl_conv_dwh_kernel<NT, 3, 2>, lds);
-  if (p.dw_k == 5 && p.dw_stride == 1) return yl_resident_blocks(yl_conv_dwh_kernel<NT, 5, 1>, lds);
-  return yl_resident_blocks(yl_conv_dwh_kernel<NT, 5, 2>, lds);
-}
-
-template <int NT>
-static bool yl_dwh_go(const YlConvMulti& m, dim3 grid, size_t lds, hipStream_t st) {
-  const YlConvP& p = m.p[0];
-  if (p.dw_k == 3 && p.dw_stride == 1) hipLaunchKernelGGL((yl_conv_dwh_kernel<NT, 3, 1>), grid, dim3(256), lds, st, m);
-  else if (p.dw_k == 3 && p.dw_stride == 2) hipLaunchKernelGGL((yl_conv_dwh_kernel<NT, 3, 2>), grid, dim3(256), lds, st, m);
-  else if (p.dw_k == 5 && p.dw_stride == 1) hipLaunchKernelGGL((yl_conv_dwh_kernel<NT, 5, 1>), grid, dim3(256), lds, st, m);
-  else if (p.dw_k == 5 && p.dw_stride == 2) hipLaunchKernelGGL((yl_conv_dwh_kernel<NT, 5, 2>), grid, dim3(256), lds, st, m);
-  else return false;
-  return true;
-}
-
-template <int NT, int MT>
-static int yl_conv_resident(int mode, size_t lds) {
-  if (mode == YL_CM_PW) return yl_resident_blocks(yl_conv_mfma_kernel<NT, MT, YL_CM_PW>, lds);
-  if (mode == YL_CM_KXK) return yl_resident_blocks(yl_conv_mfma_kernel<NT, MT, YL_CM_KXK>, lds);
-  if (mode == YL_CM_DW3) return yl_resident_blocks(yl_conv_mfma_kernel<NT, MT, YL_CM_DW3>, lds);
-  if (mode == YL_CM_DW5) return yl_resident_blocks(yl_conv_mfma_kernel<NT, MT, YL_CM_DW5>, lds);
-  if (mode == YL_CM_PWSC) return yl_resident_blocks(yl_conv_mfma_kernel<NT, MT, YL_CM_PWSC>, lds);
-  return yl_resident_blocks(yl_conv_mfma_kernel<NT, MT, YL_CM_DWPRO>, lds);
-}
-template <int MT>
-static int yl_conv_resident_nt(int NT, int mode, size_t lds) {
-  switch (NT) {
-    case 1: return yl_conv_resident<1, MT>(mode, lds);
-    case 2: return yl_conv_resident<2, MT>(mode, lds);
-    case 3: return yl_conv_resident<3, MT>(mode, lds);
-    case 4: return yl_conv_resident<4, MT>(mode, lds);
-    case 6: return yl_conv_resident<6, MT>(mode, lds);
-    default: return yl_conv_resident<8, MT>(mode, lds);
-  }
-}
-
-template <int NT, int MT>
-static void yl_conv_go(const YlConvMulti& m, int mode, dim3 grid, size_t lds, hipStream_t st) {
-  if (mode == YL_CM_PW) hipLaunchKernelGGL((yl_conv_mfma_kernel<NT, MT, YL_CM_PW>), grid, dim3(256), lds, st, m);
-  else if (mode == YL_CM_KXK) hipLaunchKernelGGL((yl_conv_mfma_kernel<NT, MT, YL_CM_KXK>), grid, dim3(256), lds, st, m);
-  else if (mode == YL_CM_DW3) hipLaunchKernelGGL((yl_conv_mfma_kernel<NT, MT, YL_CM_DW3>), grid, dim3(256), lds, st, m);
-  else if (mode == YL_CM_DW5) hipLaunchKernelGGL((yl_conv_mfma_kernel<NT, MT, YL_CM_DW5>), grid, dim3(256), lds, st, m);
-  else if (mode == YL_CM_PWSC) hipLaunchKernelGGL((yl_conv_mfma_kernel<NT, MT, YL_CM_PWSC>), grid, dim3(256), lds, st, m);
-  else hipLaunchKernelGGL((yl_conv_mfma_kernel<NT, MT, YL_CM_DWPRO>), grid, dim3(256), lds, st, m);
-}
-template <int MT>
-static void yl_conv_go_nt(const YlConvMulti& m, int NT, int mode, dim3 grid, size_t lds, hipStream_t st) {
-  switch (NT) {
-    case 1: yl_conv_go<1, MT>(m, mode, grid, lds, st); break;
-    case 2: yl_conv_go<2, MT>(m, mode, grid, lds, st); break;
-    case 3: yl_conv_go<3, MT>(m, mode, grid, lds, st); break;
-    case 4: yl_conv_go<4, MT>(m, mode, grid, lds, st); break;
-    case 6: yl_conv_go<6, MT>(m, mode, grid, lds, st); break;
-    default: yl_conv_go<8, MT>(m, mode, grid, lds, st); break;
-  }
+  return yl_uib_kernel_of(NT, dk, kbi) != nullptr;
 }
 
 // split `gx` blocks over the problems in proportion to their tile counts (every problem gets >= 1 block and
@@ -1326,7 +1209,7 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
       if (ei != hipErrorNotSupported) return ei;
     }
     if (n != 1 || gy != 1 || (p.OH & 3) || (p.OW & 3) || p.dw_stride != 1) return hipErrorInvalidValue;
-    return yl_uib_dispatch(p, yl_uib_lds_bytes(p.Cin, NT, p.dw_k), st, false, NT, p.dw_k, (p.C1 + 15) / 16);
+    return yl_uib_go(p, yl_uib_lds_bytes(p.Cin, NT, p.dw_k), st, NT, p.dw_k, (p.C1 + 15) / 16);
   }
   // plain 1x1 layers (N % 4 == 0, single problem): wave-autonomous kernel (yl_convc.hip) -- every wave an independent
   // 16/32-pixel x <= 4 n-tile item with operands straight from L1/L2, thousands of waves at 8 per SIMD, no LDS
@@ -1411,37 +1294,20 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
     const int PITCHF = ((HP * 16 + 7) / 64) * 64 + 56;
     const size_t lds = (size_t)p.KB * NT * 1024 + (size_t)(p.dw_k * p.dw_k + 1) * p.Cin * 4 + (size_t)4 * HP * PITCHF * 4;
     if (lds <= YL_DWH_LDS_MAX) {
+      const YlMultiKernel kern = yl_dwh_kernels[yl_nt_index(NT)][p.dw_k == 5][p.dw_stride == 2];   // (halo: 3 / 5, 1 / 2)
       long tiles[4], wtotal = 0;
       for (int k = 0; k < n; ++k) {
         const long wt = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW >> 2);
         tiles[k] = (wt + 3) / 4;                            // block-sized units (4 waves)
         wtotal += tiles[k];
       }
-      int res = 0;
-      switch (NT) {
-        case 1: res = yl_dwh_resident<1>(p, lds); break;
-        case 2: res = yl_dwh_resident<2>(p, lds); break;
-        case 3: res = yl_dwh_resident<3>(p, lds); break;
-        case 4: res = yl_dwh_resident<4>(p, lds); break;
-        case 6: res = yl_dwh_resident<6>(p, lds); break;
-        default: res = yl_dwh_resident<8>(p, lds); break;
-      }
-      int gx = res / gy;
+      int gx = yl_resident_blocks((const void*)kern, 256, lds, 4) / gy;
       if (gx < 8) gx = 8;
       gx &= ~7;
       if (gx > wtotal) gx = (int)wtotal;
       gx = yl_partition_blocks(m, tiles, gx);
-      dim3 grid(gx, gy);
-      bool ok = false;
-      switch (NT) {
-        case 1: ok = yl_dwh_go<1>(m, grid, lds, st); break;
-        case 2: ok = yl_dwh_go<2>(m, grid, lds, st); break;
-        case 3: ok = yl_dwh_go<3>(m, grid, lds, st); break;
-        case 4: ok = yl_dwh_go<4>(m, grid, lds, st); break;
-        case 6: ok = yl_dwh_go<6>(m, grid, lds, st); break;
-        default: ok = yl_dwh_go<8>(m, grid, lds, st); break;
-      }
-      if (ok) return hipGetLastError();
+      hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, st, m);
+      return hipGetLastError();
     }
   }
   long Mtot = 0;
@@ -1469,15 +1335,13 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
     tiles[k] = m.p[k].ntiles;
     ttotal += tiles[k];
   }
-  const int res = (MT == 2) ? yl_conv_resident_nt<2>(NT, mode, lds) : yl_conv_resident_nt<1>(NT, mode, lds);
-  int gx = res / gy;
+  const YlMultiKernel kern = yl_mfma_kernels[yl_nt_index(NT)][MT - 1][mode];
+  int gx = yl_resident_blocks((const void*)kern, 256, lds, 4) / gy;
   if (gx < 8) gx = 8;
   gx &= ~7;                         // multiple of 8: N-chunks of one M tile land on the same XCD/L2
   if (gx > ttotal) gx = (int)ttotal;
   gx = yl_partition_blocks(m, tiles, gx);
-  dim3 grid(gx, gy);
-  if (MT == 2) yl_conv_go_nt<2>(m, NT, mode, grid, lds, st);
-  else yl_conv_go_nt<1>(m, NT, mode, grid, lds, st);
+  hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, st, m);
   return hipGetLastError();
 }
 

@@ -50,10 +50,7 @@
 #define yl_ir_supported YL_LP_NAME(yl_ir_supported)
 #endif
 #include <stdlib.h>
-#include <map>
 #include <type_traits>
-#include <mutex>
-#include <utility>
 #include "yl_internal.h"
 #include "yl_dev.h"
 #include "yl_epi.h"
@@ -62,22 +59,6 @@
 #else
 #define defined_YL_F16S 0
 #endif
-
-// co-resident workgroups of `kernel` on the whole device (occupancy query cached per kernel and LDS size)
-template <typename K>
-static int yl_resident_blocks_n(K kernel, int threads, size_t lds) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> cache;
-  const std::pair<const void*, size_t> key((const void*)kernel, lds);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kernel, threads, lds) != hipSuccess || nb < 1) nb = 1;
-  if (nb > 8) nb = 8;
-  cache[key] = nb * YL_NUM_CU;
-  return nb * YL_NUM_CU;
-}
 
 #define YL_DWC_LDS_MAX (150 * 1024)
 
@@ -905,17 +886,31 @@ __global__ __launch_bounds__(256, MT == 2 ? 2 : 3) void yl_conv_dwt_kernel(YlCon
   yl_dwt_body<NT, DK, DS, MT, WL, SK, 0>(mp, nullptr);
 }
 
-template <int NT, int DK, int DS, int MT, bool WL, int SK = 1>
-static hipError_t dwt_go(YlConvMulti& m, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dwt_kernel<NT, DK, DS, MT, WL, SK>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  constexpr int HPY = 3 * DS + DK, HPX = (4 * MT - 1) * DS + DK;
-  constexpr int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
+// The instantiations of yl_conv_dwt_kernel<NT, DK, DS, MT, WL, SK>, written once (yl_convc_init and the launcher read these
+// tables).  One m-tile per wave (MT = 1: the 4x8-pixel tile of MT = 2 was measured slower, see yl_launch_conv_dwt); NT in
+// {1, 2, 3, 4, 6} x depthwise 3x3 / 5x5 x stride 1 / 2 x 1x1 weights from L1/L2 or from an LDS image (WL), as
+// [NT <= 4 ? NT - 1 : 4][DK == 5][DS == 2][WL]
+#define YL_DWT_WLS(NT, DK, DS) {yl_conv_dwt_kernel<NT, DK, DS, 1, false>, yl_conv_dwt_kernel<NT, DK, DS, 1, true>}
+#define YL_DWT_SHAPES(NT) {{YL_DWT_WLS(NT, 3, 1), YL_DWT_WLS(NT, 3, 2)}, {YL_DWT_WLS(NT, 5, 1), YL_DWT_WLS(NT, 5, 2)}}
+static const YlMultiKernel dwt_kernels[5][2][2][2] = {YL_DWT_SHAPES(1), YL_DWT_SHAPES(2), YL_DWT_SHAPES(3), YL_DWT_SHAPES(4),
+                                                      YL_DWT_SHAPES(6)};
+// split-K form (see the kernel: NT = 4, one n-tile per wave, SK = 4, weights from L1/L2): stride-1 3x3 / 5x5 and stride-2
+// 3x3 depthwise, as [DK == 5][DS == 2]
+static const YlMultiKernel dwt_splitk_kernels[2][2] = {
+    {yl_conv_dwt_kernel<4, 3, 1, 1, false, 4>, yl_conv_dwt_kernel<4, 3, 2, 1, false, 4>},
+    {yl_conv_dwt_kernel<4, 5, 1, 1, false, 4>, nullptr}};
+
+// NT, WL, SK: the template arguments of `kern` (DK and DS are the layer's)
+static hipError_t dwt_go(YlConvMulti& m, hipStream_t st, YlMultiKernel kern, int NT, bool WL, int SK) {
+  constexpr int MT = 1;
   const YlConvP& p = m.p[0];
+  const int DK = p.dw_k, DS = p.dw_stride;
+  const int HPY = 3 * DS + DK, HPX = (4 * MT - 1) * DS + DK;
+  const int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
   const size_t lds = ((WL ? (size_t)p.KB * p.NTtot * 256 : 0) + (((size_t)(DK * DK + 1) * p.Cin + 3) & ~(size_t)3) +
                       (size_t)4 * HPY * PITCHF + (SK > 1 ? (size_t)2 * 4 * NT * 256 : 0)) * 4;
   if (lds > 96 * 1024) return hipErrorNotSupported;
-  const int res = yl_resident_blocks_n(yl_conv_dwt_kernel<NT, DK, DS, MT, WL, SK>, 256, lds);
+  const int res = yl_resident_blocks((const void*)kern, 256, lds, 8);
   long tiles[4], total = 0;
   for (int k = 0; k < m.n; ++k) {
     tiles[k] = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW / (4 * MT)) * (SK > 1 ? 4 : 1);     // SK: a workgroup per tile
@@ -934,68 +929,8 @@ static hipError_t dwt_go(YlConvMulti& m, hipStream_t st, bool attr_only) {
     at += (int)g;
   }
   if (m.n == 1) m.p[0].nblk = 0;
-  hipLaunchKernelGGL((yl_conv_dwt_kernel<NT, DK, DS, MT, WL, SK>), dim3((unsigned)at), dim3(256), lds, st, m);
+  hipLaunchKernelGGL(kern, dim3((unsigned)at), dim3(256), lds, st, m);
   return hipGetLastError();
-}
-
-// split-K form (see the kernel): single problem, N = 49..64 (4 n-tiles, one per wave), stride-1 3x3 / 5x5 or stride-2
-// 3x3 depthwise, weights from L1/L2, >= 8 k-blocks, a grid of at most 20 x 20 output pixels
-static hipError_t dwt_splitk(YlConvMulti& m, hipStream_t st, bool attr_only) {
-  if (attr_only) {
-    hipError_t e = dwt_go<4, 3, 1, 1, false, 4>(m, st, true);
-    if (e == hipSuccess) e = dwt_go<4, 5, 1, 1, false, 4>(m, st, true);
-    if (e == hipSuccess) e = dwt_go<4, 3, 2, 1, false, 4>(m, st, true);
-    return e;
-  }
-  const YlConvP& p = m.p[0];
-  if (p.dw_k == 3 && p.dw_stride == 1) return dwt_go<4, 3, 1, 1, false, 4>(m, st, false);
-  if (p.dw_k == 5 && p.dw_stride == 1) return dwt_go<4, 5, 1, 1, false, 4>(m, st, false);
-  if (p.dw_k == 3 && p.dw_stride == 2) return dwt_go<4, 3, 2, 1, false, 4>(m, st, false);
-  return hipErrorNotSupported;
-}
-
-template <int NT, int MT, bool WL>
-static hipError_t dwt_dk(YlConvMulti& m, hipStream_t st, bool attr_only) {
-  const YlConvP& p = m.p[0];
-  if (attr_only) {
-    hipError_t e = dwt_go<NT, 3, 1, MT, WL>(m, st, true);
-    if (e == hipSuccess) e = dwt_go<NT, 3, 2, MT, WL>(m, st, true);
-    if (e == hipSuccess) e = dwt_go<NT, 5, 1, MT, WL>(m, st, true);
-    if (e == hipSuccess) e = dwt_go<NT, 5, 2, MT, WL>(m, st, true);
-    return e;
-  }
-  if (p.dw_k == 3 && p.dw_stride == 1) return dwt_go<NT, 3, 1, MT, WL>(m, st, false);
-  if (p.dw_k == 3 && p.dw_stride == 2) return dwt_go<NT, 3, 2, MT, WL>(m, st, false);
-  if (p.dw_k == 5 && p.dw_stride == 1) return dwt_go<NT, 5, 1, MT, WL>(m, st, false);
-  if (p.dw_k == 5 && p.dw_stride == 2) return dwt_go<NT, 5, 2, MT, WL>(m, st, false);
-  return hipErrorNotSupported;
-}
-
-template <int NT>
-static hipError_t dwt_nt(YlConvMulti& m, hipStream_t st, bool two, bool wl, bool attr_only) {
-#ifdef YL_DWT_MT2          // 4x8-pixel wave tiles: measured slower (below), not compiled by default
-  if (attr_only) {
-    hipError_t e = dwt_dk<NT, 2, false>(m, st, true);
-    return e == hipSuccess ? dwt_dk<NT, 2, true>(m, st, true) : e;
-  }
-  if (two) return wl ? dwt_dk<NT, 2, true>(m, st, false) : dwt_dk<NT, 2, false>(m, st, false);
-#endif
-  (void)two;
-  if (attr_only) {
-    hipError_t e = dwt_dk<NT, 1, false>(m, st, true);
-    return e == hipSuccess ? dwt_dk<NT, 1, true>(m, st, true) : e;
-  }
-  return wl ? dwt_dk<NT, 1, true>(m, st, false) : dwt_dk<NT, 1, false>(m, st, false);
-}
-
-static hipError_t dwt_any(YlConvMulti& m, int NT, hipStream_t st, bool two, bool wl, bool attr_only) {
-  hipError_t e = hipSuccess;
-  if (attr_only || NT == 1) e = dwt_nt<1>(m, st, two, wl, attr_only);
-  if (attr_only ? e == hipSuccess : NT == 2) e = dwt_nt<2>(m, st, two, wl, attr_only);
-  if (attr_only ? e == hipSuccess : NT == 3) e = dwt_nt<3>(m, st, two, wl, attr_only);
-  if (attr_only ? e == hipSuccess : NT == 4) e = dwt_nt<4>(m, st, two, wl, attr_only);
-  if (attr_only ? e == hipSuccess : NT == 6) e = dwt_nt<6>(m, st, two, wl, attr_only);
-  return e;
 }
 
 // depthwise (3x3 / 5x5, stride 1 / 2) -> 1x1 with N % 4 == 0, N <= 96 (all n-tiles in one wave), OH % 4 == 0,
@@ -1003,27 +938,28 @@ static hipError_t dwt_any(YlConvMulti& m, int NT, hipStream_t st, bool two, bool
 hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st) {
   const YlConvP& p = m.p[0];
   if (p.dw_k == 0 || (p.N & 3) || p.NTtot > 6 || p.dec_boxes || p.C1 > 0) return hipErrorNotSupported;
+  if ((p.dw_k != 3 && p.dw_k != 5) || (p.dw_stride != 1 && p.dw_stride != 2)) return hipErrorNotSupported;
   // Per-layer measurements (edge_n, B = 64, us; dwh = yl_conv_dwh_kernel, <mt><wl> = this kernel):
   //   K=N=96 dw3 80x80:  dwh 143 | 10: 163 | 11: 137 | 20: 147 | 21: 141        K=96 N=48 dw3: dwh 32.9 | 11: 29.2
   //   K=256 N=64 dw5:    dwh 49.7 | 10: 35.1 | 11: 49.3 | 20: 34.9             K=32 N=96 dw5 s2: dwh 76 | 11: 70
   // -> one m-tile per wave (the 4x8 tile needs ~190 VGPRs: 2 waves per SIMD), LDS weight image while it is <= 36 KB.
   // ("dev_select" bit 4 disables the kernel: developer A/B)
   if (p.dev & YL_DEV_DWT_OFF) return hipErrorNotSupported;
-  bool two = false, wl = p.KB * p.NTtot <= 36;
+  const bool wl = p.KB * p.NTtot <= 36;
   for (int k = 0; k < m.n; ++k) {
     if ((m.p[k].OH & 3) || (m.p[k].OW & 3)) return hipErrorNotSupported;
     if ((size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
-    if (m.p[k].OW & 7) two = false;
   }
   const int nts[5] = {1, 2, 3, 4, 6};
   int NT = 6;
   for (int i = 0; i < 5; ++i) if (nts[i] >= p.NTtot) { NT = nts[i]; break; }
+  const int dk5 = p.dw_k == 5, ds2 = p.dw_stride == 2;
   // split-K: chosen by the layer's SHAPE only (batch-invariant results); "dev_select" bit 10 keeps the one-wave-per-tile form
-  if (m.n == 1 && NT == 4 && !wl && p.KB >= 8 && p.OH * p.OW <= 400 && !(p.dev & YL_DEV_DWT_NOSPLIT)) {
-    const hipError_t e = dwt_splitk(m, st, false);
+  if (m.n == 1 && NT == 4 && !wl && p.KB >= 8 && p.OH * p.OW <= 400 && !(p.dev & YL_DEV_DWT_NOSPLIT) && dwt_splitk_kernels[dk5][ds2]) {
+    const hipError_t e = dwt_go(m, st, dwt_splitk_kernels[dk5][ds2], 4, false, 4);
     if (e != hipErrorNotSupported) return e;
   }
-  return dwt_any(m, NT, st, two, wl, false);
+  return dwt_go(m, st, dwt_kernels[NT <= 4 ? NT - 1 : 4][dk5][ds2][wl], NT, wl, 1);
 }
 
 #if !YL_BF16
@@ -1041,15 +977,23 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwx_kernel(YlConvMulti mp, flo
   yl_dwt_body<4, DK, 1, 1, false, 1, NX>(mp, out3);
 }
 
-template <int DK, int NX>
-static hipError_t dwx_go(YlConvMulti& m, float* out3, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dwx_kernel<DK, NX>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  constexpr int HPY = 3 + DK, HPX = 3 + DK;
-  constexpr int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
+// instantiated: (depthwise k, n-tiles of the chained 1x1)
+#define YL_DWX_SHAPES(X) X(5, 16) X(5, 12) X(3, 16) X(3, 12)
+typedef void (*YlDwxKernel)(YlConvMulti, float*);
+static YlDwxKernel dwx_kernel_of(int dk, int nx) {
+#define YL_DWX_PICK(DK, NX) if (dk == DK && nx == NX) return yl_conv_dwx_kernel<DK, NX>;
+  YL_DWX_SHAPES(YL_DWX_PICK)
+#undef YL_DWX_PICK
+  return nullptr;
+}
+
+static hipError_t dwx_go(YlConvMulti& m, float* out3, hipStream_t st, YlDwxKernel kern) {
+  const int DK = m.p[0].dw_k;
+  const int HPY = 3 + DK, HPX = 3 + DK;
+  const int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
   YlConvP& p = m.p[0];
   const size_t lds = ((((size_t)(DK * DK + 1) * p.Cin + 3) & ~(size_t)3) + (size_t)4 * HPY * PITCHF) * 4;
-  const int res = yl_resident_blocks_n(yl_conv_dwx_kernel<DK, NX>, 256, lds);
+  const int res = yl_resident_blocks((const void*)kern, 256, lds, 8);
   // persistent workgroups as dwt_go: a multiple of 8 (XCD bands), at most one wave per tile
   const long tiles = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
   long g = ((long)res + 7) & ~7L;
@@ -1057,12 +1001,12 @@ static hipError_t dwx_go(YlConvMulti& m, float* out3, hipStream_t st, bool attr_
   if (g > cap) g = cap;
   if (g < 8) g = 8;
   p.blk0 = 0; p.nblk = 0;
-  hipLaunchKernelGGL((yl_conv_dwx_kernel<DK, NX>), dim3((unsigned)g), dim3(256), lds, st, m, out3);
+  hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), lds, st, m, out3);
   return hipGetLastError();
 }
 
 bool yl_dwx_supported(int cin, int cout, int dw_k, int dw_stride, int cout1, int oh, int ow) {
-  return (cin == 192 || cin == 256) && cout == 64 && (dw_k == 3 || dw_k == 5) && dw_stride == 1 && (cout1 == 192 || cout1 == 256) &&
+  return (cin == 192 || cin == 256) && cout == 64 && dw_stride == 1 && (cout1 & 15) == 0 && dwx_kernel_of(dw_k, cout1 / 16) &&
          (oh & 3) == 0 && (ow & 3) == 0;
 }
 
@@ -1082,21 +1026,7 @@ hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st) {
   YlConvMulti m = {};
   m.n = 1;
   m.p[0] = p;
-  const int nx = p.C3 / 16;
-  if (p.dw_k == 5 && nx == 16) return dwx_go<5, 16>(m, out3, st, false);
-  if (p.dw_k == 5 && nx == 12) return dwx_go<5, 12>(m, out3, st, false);
-  if (p.dw_k == 3 && nx == 16) return dwx_go<3, 16>(m, out3, st, false);
-  if (p.dw_k == 3 && nx == 12) return dwx_go<3, 12>(m, out3, st, false);
-  return hipErrorNotSupported;
-}
-
-static hipError_t yl_dwx_init() {
-  YlConvMulti m = {};
-  hipError_t e = dwx_go<5, 16>(m, nullptr, nullptr, true);
-  if (e == hipSuccess) e = dwx_go<5, 12>(m, nullptr, nullptr, true);
-  if (e == hipSuccess) e = dwx_go<3, 16>(m, nullptr, nullptr, true);
-  if (e == hipSuccess) e = dwx_go<3, 12>(m, nullptr, nullptr, true);
-  return e;
+  return dwx_go(m, out3, st, dwx_kernel_of(p.dw_k, p.C3 / 16));      // (instantiated: yl_dwx_supported above)
 }
 #endif
 
@@ -1264,23 +1194,24 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_kxk_kernel(Y
   }
 }
 
-template <int NT, int MT, int NW>
-static hipError_t kxk_go(const YlConvP& p0, int gy, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_kxk_kernel<NT, MT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+// instantiated: (n-tiles per workgroup, m-tiles per wave, waves per workgroup)
+#define YL_KXK_SHAPES(X) X(7, 1, 4) X(7, 2, 4) X(7, 1, 8) X(4, 1, 8) X(4, 2, 4)
+static YlConvKernel kxk_kernel_of(int NT, int MT, int NW) {
+#define YL_KXK_PICK(A, B, C) if (NT == A && MT == B && NW == C) return yl_conv_kxk_kernel<A, B, C>;
+  YL_KXK_SHAPES(YL_KXK_PICK)
+#undef YL_KXK_PICK
+  return nullptr;
+}
+
+static hipError_t kxk_go(const YlConvP& p0, int NT, int MT, int NW, int gy, hipStream_t st) {
+  const YlConvKernel kern = kxk_kernel_of(NT, MT, NW);
+  if (!kern) return hipErrorNotSupported;
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW * MT - 1) / (16 * NW * MT));
   const size_t lds = (size_t)2 * 3 * NT * 1024;
-  static int res = 0;
-  if (!res) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)yl_conv_kxk_kernel<NT, MT, NW>, NW * 64, lds) != hipSuccess || nb < 1) nb = 1;
-    if (nb > 4) nb = 4;
-    res = nb * YL_NUM_CU;
-  }
-  int gx = res & ~7;
+  int gx = yl_resident_blocks((const void*)kern, NW * 64, lds, 4) & ~7;
   while (gx > 8 && gx - 8 >= p.ntiles * gy) gx -= 8;       // gy = n-groups: (m-tile, n-group) items
-  hipLaunchKernelGGL((yl_conv_kxk_kernel<NT, MT, NW>), dim3(gx), dim3(NW * 64), lds, st, p);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
 }
 
@@ -1294,7 +1225,7 @@ hipError_t yl_launch_conv_kxk(const YlConvP& p, hipStream_t st) {
   const int MTsel = (p.dev & YL_DEV_KXK_MT2) ? 2 : 1;
   if (p.NTtot == 4) {
     if ((size_t)p.TK * 4 * 1024 <= 96 * 1024 || NWsel < 0) return hipErrorNotSupported;
-    return NWsel == 8 ? kxk_go<4, 1, 8>(p, 1, st, false) : kxk_go<4, 2, 4>(p, 1, st, false);
+    return NWsel == 8 ? kxk_go(p, 4, 1, 8, 1, st) : kxk_go(p, 4, 2, 4, 1, st);
   }
   if (p.NTtot % 7 != 0) return hipErrorNotSupported;
   if ((size_t)p.TK * 7 * 1024 <= 96 * 1024) return hipErrorNotSupported;      // small enough to stay resident: other kernel
@@ -1302,8 +1233,7 @@ hipError_t yl_launch_conv_kxk(const YlConvP& p, hipStream_t st) {
   // yololite_m's 80x80 level) when there are enough 128-pixel items to keep the tail short; 4 otherwise
   const int gy = p.NTtot / 7;
   const bool eight = NWsel ? NWsel == 8 : ((long)p.M / 128) * gy >= 2 * 2 * YL_NUM_CU;
-  if (eight) return kxk_go<7, 1, 8>(p, gy, st, false);
-  return MTsel == 1 ? kxk_go<7, 1, 4>(p, gy, st, false) : kxk_go<7, 2, 4>(p, gy, st, false);
+  return eight ? kxk_go(p, 7, 1, 8, gy, st) : kxk_go(p, 7, MTsel, 4, gy, st);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1493,46 +1423,39 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_pws_kernel(Y
   }
 }
 
-template <int NT, int NW>
-static hipError_t pws_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  if (attr_only) {
-    hipError_t e = hipFuncSetAttribute((const void*)yl_conv_pws_kernel<NT, NW, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-    if (e != hipSuccess) return e;
-    if (NT == 6) {
-      e = hipFuncSetAttribute((const void*)yl_conv_pws_kernel<NT == 6 ? 6 : 6, NW, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute((const void*)yl_conv_pws_kernel<NT == 6 ? 6 : 6, NW, false, true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    return hipFuncSetAttribute((const void*)yl_conv_pws_kernel<NT, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-  }
+// The instantiations of yl_conv_pws_kernel<NT, NW, SC, DEC, NT2>, written once: NT (n-tiles per item, the candidates of
+// yl_launch_conv_pws in its order of preference) x 4 / 8 waves x plain / gated input (SC), as [candidate][NW == 8][SC] ...
+#define YL_PWS_NTS(X) X(13) X(11) X(9) X(8) X(7) X(6)
+#define YL_PWS_NT_VALUE(NT) NT,
+#define YL_PWS_NT_KERNELS(NT) \
+  {{yl_conv_pws_kernel<NT, 4>, yl_conv_pws_kernel<NT, 4, true>}, {yl_conv_pws_kernel<NT, 8>, yl_conv_pws_kernel<NT, 8, true>}},
+static const int pws_nts[6] = {YL_PWS_NTS(YL_PWS_NT_VALUE)};
+static const YlConvKernel pws_kernels[6][2][2] = {YL_PWS_NTS(YL_PWS_NT_KERNELS)};
+// ... and the decode forms (NT = 6, one n-group), as [NW == 8][with the mask coefficients of the second weight image]
+static const YlConvKernel pws_dec_kernels[2][2] = {{yl_conv_pws_kernel<6, 4, false, true>, yl_conv_pws_kernel<6, 4, false, true, 2>},
+                                                   {yl_conv_pws_kernel<6, 8, false, true>, yl_conv_pws_kernel<6, 8, false, true, 2>}};
+
+// cand: index into pws_nts
+static hipError_t pws_go(const YlConvP& p0, hipStream_t st, int cand, bool eight) {
+  const int NT = pws_nts[cand], NW = eight ? 8 : 4;
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW - 1) / (16 * NW));
   const size_t lds = (size_t)2 * 2 * NT * 1024;
-  int gx = yl_resident_blocks_n(yl_conv_pws_kernel<NT, NW>, NW * 64, lds) & ~7;
+  int gx = yl_resident_blocks((const void*)pws_kernels[cand][eight][0], NW * 64, lds, 8) & ~7;
   const int gy = (p.NTtot + NT - 1) / NT;
   while (gx > 8 && gx - 8 >= p.ntiles * gy) gx -= 8;
   if (p.dec_boxes) {
     if (NT != 6 || p.scale) return hipErrorNotSupported;
     if (p.w3p) {                                              // + the mask coefficients (32 columns) from the second weight image
       const size_t lds2 = (size_t)2 * 2 * 8 * 1024;
-      int gx2 = yl_resident_blocks_n(yl_conv_pws_kernel<6, NW, false, true, 2>, NW * 64, lds2) & ~7;
+      int gx2 = yl_resident_blocks((const void*)pws_dec_kernels[eight][1], NW * 64, lds2, 8) & ~7;
       while (gx2 > 8 && gx2 - 8 >= p.ntiles * gy) gx2 -= 8;
-      hipLaunchKernelGGL((yl_conv_pws_kernel<6, NW, false, true, 2>), dim3(gx2), dim3(NW * 64), lds2, st, p);
+      hipLaunchKernelGGL(pws_dec_kernels[eight][1], dim3(gx2), dim3(NW * 64), lds2, st, p);
     } else
-      hipLaunchKernelGGL((yl_conv_pws_kernel<6, NW, false, true>), dim3(gx), dim3(NW * 64), lds, st, p);
-  } else if (p.scale) hipLaunchKernelGGL((yl_conv_pws_kernel<NT, NW, true>), dim3(gx), dim3(NW * 64), lds, st, p);
-  else hipLaunchKernelGGL((yl_conv_pws_kernel<NT, NW>), dim3(gx), dim3(NW * 64), lds, st, p);
+      hipLaunchKernelGGL(pws_dec_kernels[eight][0], dim3(gx), dim3(NW * 64), lds, st, p);
+  } else
+    hipLaunchKernelGGL(pws_kernels[cand][eight][p.scale != nullptr], dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
-}
-
-template <int NT>
-static hipError_t pws_nw(const YlConvP& p, hipStream_t st, bool eight, bool attr_only) {
-  if (attr_only) {
-    const hipError_t e = pws_go<NT, 4>(p, st, true);
-    return e != hipSuccess ? e : pws_go<NT, 8>(p, st, true);
-  }
-  return eight ? pws_go<NT, 8>(p, st, false) : pws_go<NT, 4>(p, st, false);
 }
 
 // plain 1x1 stride-1 layers (N % 4 == 0, no decode epilogue) with enough channels on both sides that the weight
@@ -1546,27 +1469,19 @@ hipError_t yl_launch_conv_pws(const YlConvP& p, hipStream_t st) {
   // to 1024 SIMDs, each NT x KB x 4 MFMAs long -- with a penalty when fewer than 1.5 waves per SIMD exist (one wave
   // alone cannot keep a matrix pipe busy); ties go to the larger NT (fewer passes over the activations).  E.g. 1248 ->
   // 208 at 20x20 x 32 images (13 n-tiles, 800 pixel tiles): NT = 7 in two groups (116 -> 90 us), not 13 in one.
-  static const int cand[6] = {13, 11, 9, 8, 7, 6};
-  int NT = 0;
+  int NT = 0, cand = 0;
   double best = 1e30;
   long best_wi = 0;
   const long mt16 = ((long)p.M + 15) / 16;
   for (int i = dec ? 5 : 0; i < 6; ++i) {
-    const long wi = mt16 * ((p.NTtot + cand[i] - 1) / cand[i]);
-    const double sc = (double)((wi + 1023) / 1024) * cand[i] * (wi < 1536 ? 1.25 : 1.0);
-    if (sc < best) { best = sc; NT = cand[i]; best_wi = wi; }
+    const long wi = mt16 * ((p.NTtot + pws_nts[i] - 1) / pws_nts[i]);
+    const double sc = (double)((wi + 1023) / 1024) * pws_nts[i] * (wi < 1536 ? 1.25 : 1.0);
+    if (sc < best) { best = sc; NT = pws_nts[i]; cand = i; best_wi = wi; }
   }
   if (best_wi < 1536) return hipErrorNotSupported;      // too few items for workgroup-shared weights: wave-autonomous kernel
   const int gy = (p.NTtot + NT - 1) / NT;
   const bool eight = ((long)p.M / 128) * gy >= 2 * 2 * YL_NUM_CU;          // enough 128-pixel items for 8-wave workgroups
-  switch (NT) {
-    case 6: return pws_nw<6>(p, st, eight, false);
-    case 7: return pws_nw<7>(p, st, eight, false);
-    case 8: return pws_nw<8>(p, st, eight, false);
-    case 9: return pws_nw<9>(p, st, eight, false);
-    case 11: return pws_nw<11>(p, st, eight, false);
-    default: return pws_nw<13>(p, st, eight, false);
-  }
+  return pws_go(p, st, cand, eight);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1808,12 +1723,10 @@ static size_t yl_ir_lds(int dk, int ds, int mt, int rbn, int cbn, int nt, int cm
 }
 
 template <int KBI, int NT, int DK, int DS, int MT, int RBN, int CBN>
-static hipError_t ir_go(const YlConvP& p, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+static hipError_t ir_go(const YlConvP& p, hipStream_t st) {
   const size_t lds = yl_ir_lds(DK, DS, MT, RBN, CBN, NT, p.Cin);
   const long ntiles = (long)p.B * (p.OH / (4 * RBN)) * (p.OW / (4 * MT * CBN));
-  int gx = yl_resident_blocks_n(yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>, RBN * CBN * 64, lds);
+  int gx = yl_resident_blocks((const void*)yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>, RBN * CBN * 64, lds, 8);
   if (gx > ntiles) gx = (int)ntiles;
   if (gx >= 8) gx &= ~7;
   hipLaunchKernelGGL((yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>), dim3(gx), dim3(RBN * CBN * 64), lds, st, p);
@@ -1848,19 +1761,10 @@ hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st) {
 #define YL_IR_RUN(A, B, C, D, E, R, S)                                                                               \
   if (kbi == A && nt <= B && nt > YL_IR_BUCKET_LO(B) && p.dw_k == C && p.dw_stride == D && (p.OH % (4 * R)) == 0 &&     \
       (p.OW % (4 * E * S)) == 0 && yl_ir_lds(C, D, E, R, S, B, p.Cin) <= 150 * 1024)                                    \
-    return ir_go<A, B, C, D, E, R, S>(p, st, false);
+    return ir_go<A, B, C, D, E, R, S>(p, st);
   YL_IR_SHAPES(YL_IR_RUN)
 #undef YL_IR_RUN
   return hipErrorNotSupported;
-}
-
-static hipError_t yl_ir_init() {
-  YlConvP q = {};
-  hipError_t e = hipSuccess;
-#define YL_IR_ATTR(A, B, C, D, E, R, S) if (e == hipSuccess) e = ir_go<A, B, C, D, E, R, S>(q, nullptr, true);
-  YL_IR_SHAPES(YL_IR_ATTR)
-#undef YL_IR_ATTR
-  return e;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2036,24 +1940,33 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
   }
 }
 
-template <int NT, int GW, int NW>
-static hipError_t dwk_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dwk_kernel<NT, GW, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+// instantiated: (n-tiles per accumulator set, sets a wave holds, waves per workgroup)
+#define YL_DWK_SHAPES(X) X(7, 1, 4) X(7, 3, 4) X(8, 1, 4) X(8, 2, 4)
+static YlConvKernel dwk_kernel_of(int NT, int GW, int NW) {
+#define YL_DWK_PICK(A, B, C) if (NT == A && GW == B && NW == C) return yl_conv_dwk_kernel<A, B, C>;
+  YL_DWK_SHAPES(YL_DWK_PICK)
+#undef YL_DWK_PICK
+  return nullptr;
+}
+
+static hipError_t dwk_go(const YlConvP& p0, hipStream_t st, int NT, int GW) {
+  constexpr int NW = 4;
+  const YlConvKernel kern = dwk_kernel_of(NT, GW, NW);
+  if (!kern) return hipErrorNotSupported;
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW - 1) / (16 * NW));
   const size_t lds = (size_t)2 * (GW == 1 ? 3 : (GW * NT <= 16 ? 2 : 1)) * GW * NT * 1024 + (((size_t)10 * p.Cin + 3) & ~(size_t)3) * 4;
   if (lds > 96 * 1024) return hipErrorNotSupported;
-  const int res = yl_resident_blocks_n(yl_conv_dwk_kernel<NT, GW, NW>, NW * 64, lds);
+  const int res = yl_resident_blocks((const void*)kern, NW * 64, lds, 8);
   const int G = p.NTtot / (NT * GW);
   int gx = res & ~7;
   while (gx > 8 && gx - 8 >= p.ntiles * G) gx -= 8;
-  hipLaunchKernelGGL((yl_conv_dwk_kernel<NT, GW, NW>), dim3(gx), dim3(NW * 64), lds, st, p);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
 }
 
-template <int NTT>
-static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, bool attr_only);
+static YlConvKernel dwl_kernel_of(int NTT);
+static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, YlConvKernel kern);
 
 // depthwise 3x3 (stride 1 / 2) -> 1x1 with K >= 192, N % 4 == 0 and an n-tile count that is a multiple of 7 or 8,
 // single problem.  hipErrorNotSupported otherwise (yl_conv_mfma_kernel's streamed mode then runs the layer).
@@ -2071,14 +1984,13 @@ hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st) {
       (size_t)p.B * p.H * p.W * p.Cin < ((size_t)1 << 31)) {
     const long wins = (long)p.B * ((p.OW + 7) >> 3) * ((p.OH + 7) >> 3);
     if (((long)p.B * p.OH * p.OW * 10 >= wins * 64 * 8 && wins >= 3 * YL_NUM_CU) || (p.dev & YL_DEV_DWL_ALL)) {
-      if (p.NTtot == 16) return dwl_go<16>(p, st, false);
-      if (p.NTtot == 21) return dwl_go<21>(p, st, false);
+      if (const YlConvKernel kl = dwl_kernel_of(p.NTtot)) return dwl_go(p, st, kl);
     }
   }
-  if (p.NTtot == 21) return sel == 2 ? dwk_go<7, 3, 4>(p, st, false) : dwk_go<7, 1, 4>(p, st, false);
-  if (p.NTtot == 16) return sel == 2 ? dwk_go<8, 2, 4>(p, st, false) : dwk_go<8, 1, 4>(p, st, false);
-  if (p.NTtot % 7 == 0) return dwk_go<7, 1, 4>(p, st, false);
-  if (p.NTtot % 8 == 0) return dwk_go<8, 1, 4>(p, st, false);
+  if (p.NTtot == 21) return dwk_go(p, st, 7, sel == 2 ? 3 : 1);
+  if (p.NTtot == 16) return dwk_go(p, st, 8, sel == 2 ? 2 : 1);
+  if (p.NTtot % 7 == 0) return dwk_go(p, st, 7, 1);
+  if (p.NTtot % 8 == 0) return dwk_go(p, st, 8, 1);
   return hipErrorNotSupported;
 }
 
@@ -2346,22 +2258,28 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
   }
 }
 
-template <int NTT>
-static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  constexpr int NTP = (NTT + 7) & ~7;
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dwl_kernel<NTT>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
+// instantiated: n-tiles of the layer (244 / 328 output channels)
+#define YL_DWL_SHAPES(X) X(16) X(21)
+static YlConvKernel dwl_kernel_of(int NTT) {
+#define YL_DWL_PICK(A) if (NTT == A) return yl_conv_dwl_kernel<A>;
+  YL_DWL_SHAPES(YL_DWL_PICK)
+#undef YL_DWL_PICK
+  return nullptr;
+}
+
+static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, YlConvKernel kern) {
+  const int NTP = (p0.NTtot + 7) & ~7;
   YlConvP p = p0;
   const long WTOT = (long)p.B * ((p.OW + 7) >> 3) * ((p.OH + 7) >> 3);
   p.ntiles = (int)((WTOT + 1) / 2);
   const size_t lds = ((size_t)3 * NTP * 64 + 4 * 512) * 16 + (size_t)p.KB * 160 * 4;
   if (lds > 128 * 1024) return hipErrorNotSupported;
   if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
-  const int res = yl_resident_blocks_n(yl_conv_dwl_kernel<NTT>, 512, lds);
+  const int res = yl_resident_blocks((const void*)kern, 512, lds, 8);
   int gx = res & ~7;
   if (gx < 8) gx = 8;
   while (gx > 8 && gx - 8 >= p.ntiles) gx -= 8;
-  hipLaunchKernelGGL((yl_conv_dwl_kernel<NTT>), dim3(gx), dim3(512), lds, st, p);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
 }
 
@@ -2597,14 +2515,12 @@ static size_t yl_dws_lds(int ntw, int dk, int ds, int nw) {
 }
 
 template <int NT, int GW, int DK, int DS, int NW>
-static hipError_t dws_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dws_kernel<NT, GW, DK, DS, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+static hipError_t dws_go(const YlConvP& p0, hipStream_t st) {
   YlConvP p = p0;
   const long t4 = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
   p.ntiles = (int)((t4 + NW - 1) / NW);
   const size_t lds = yl_dws_lds(NT * GW, DK, DS, NW);
-  const int res = yl_resident_blocks_n(yl_conv_dws_kernel<NT, GW, DK, DS, NW>, NW * 64, lds);
+  const int res = yl_resident_blocks((const void*)yl_conv_dws_kernel<NT, GW, DK, DS, NW>, NW * 64, lds, 8);
   int gx = res & ~7;
   if (gx < 8) gx = 8;                                            // (occupancy query below 8: never a grid of 0 -- ADVICE r05)
   while (gx > 8 && gx - 8 >= p.ntiles) gx -= 8;
@@ -2643,19 +2559,10 @@ hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st) {
     return hipErrorNotSupported;
   const int ntt = p.NTtot;
 #define YL_DWS_RUN(A, G, K, S_) \
-  if (p.dw_k == K && p.dw_stride == S_ && ntt <= A * G && ntt > (A * G == 8 ? 6 : A * G == 13 ? 8 : 13)) return dws_go<A, G, K, S_, 4>(p, st, false);
+  if (p.dw_k == K && p.dw_stride == S_ && ntt <= A * G && ntt > (A * G == 8 ? 6 : A * G == 13 ? 8 : 13)) return dws_go<A, G, K, S_, 4>(p, st);
   YL_DWS_SHAPES(YL_DWS_RUN)
 #undef YL_DWS_RUN
   return hipErrorNotSupported;
-}
-
-static hipError_t yl_dws_init() {
-  YlConvP q = {};
-  hipError_t e = hipSuccess;
-#define YL_DWS_ATTR(A, G, K, S_) if (e == hipSuccess) e = dws_go<A, G, K, S_, 4>(q, nullptr, true);
-  YL_DWS_SHAPES(YL_DWS_ATTR)
-#undef YL_DWS_ATTR
-  return e;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2873,22 +2780,18 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
   if (grp == 0) __syncthreads();   // group 1's last slot
 }
 
-static hipError_t wino_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  if (attr_only) {
-    const hipError_t e = hipFuncSetAttribute((const void*)yl_conv_wino_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)yl_conv_wino_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-  }
+static const YlConvKernel wino_kernels[2] = {yl_conv_wino_kernel<0>, yl_conv_wino_kernel<1>};   // [input upsampled 2x (in_shift)]
+
+static hipError_t wino_go(const YlConvP& p0, hipStream_t st) {
   YlConvP p = p0;
   const long T = (long)p.B * ((p.OH + 1) >> 1) * ((p.OW + 1) >> 1);
   p.ntiles = (int)((T + 127) / 128);
   const size_t lds = (size_t)2 * 16 * 2 * 1024;
-  const int res = yl_resident_blocks_n(yl_conv_wino_kernel<0>, 512, lds);
+  const int res = yl_resident_blocks((const void*)wino_kernels[0], 512, lds, 8);
   const int G = (p.NTtot + 1) / 2;
   int gx = res & ~7;
   while (gx > 8 && gx - 8 >= p.ntiles * G) gx -= 8;
-  if (p.in_shift) hipLaunchKernelGGL(yl_conv_wino_kernel<1>, dim3(gx), dim3(512), lds, st, p);
-  else hipLaunchKernelGGL(yl_conv_wino_kernel<0>, dim3(gx), dim3(512), lds, st, p);
+  hipLaunchKernelGGL(wino_kernels[p.in_shift ? 1 : 0], dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
 }
 
@@ -3201,25 +3104,28 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
   }
 }
 
-template <int MT, int NT>
-static hipError_t wino2_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  const size_t lds = ((size_t)2 * MT * 512 + (size_t)16 * MT * 64) * 16;      // two window buffers + the epilogue exchange
-  if (attr_only) {
-    const hipError_t e = hipFuncSetAttribute((const void*)yl_conv_wino2_kernel<MT, NT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)yl_conv_wino2_kernel<MT, NT, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
+// instantiated: (m-tiles, n-tiles per item), each for a plain and a 2x upsampled input (in_shift)
+#define YL_WINO2_SHAPES(X) X(4, 3) X(4, 4) X(2, 3) X(2, 4) X(2, 7)
+static YlConvKernel wino2_kernel_of(int MT, int NT, int in_shift) {
+#define YL_WINO2_PICK(A, B) if (MT == A && NT == B) return in_shift ? yl_conv_wino2_kernel<A, B, 1> : yl_conv_wino2_kernel<A, B, 0>;
+  YL_WINO2_SHAPES(YL_WINO2_PICK)
+#undef YL_WINO2_PICK
+  return nullptr;
+}
+static size_t wino2_lds(int MT) { return ((size_t)2 * MT * 512 + (size_t)16 * MT * 64) * 16; }   // two window buffers + the epilogue exchange
+
+static hipError_t wino2_go(const YlConvP& p0, hipStream_t st, int MT, int NT) {
+  const size_t lds = wino2_lds(MT);
   YlConvP p = p0;
   const int TW = (p.OW + 1) >> 1, TH = (p.OH + 1) >> 1;
   const long MTOT = (long)p.B * ((TW + 3) >> 2) * ((TH + 3) >> 2);
   p.ntiles = (int)((MTOT + MT - 1) / MT);
-  const int res = yl_resident_blocks_n(yl_conv_wino2_kernel<MT, NT, 0>, 512, lds);
+  const int res = yl_resident_blocks((const void*)wino2_kernel_of(MT, NT, 0), 512, lds, 8);
   const int G = (p.NTtot + NT - 1) / NT;
   int gx = res & ~7;
   if (gx < 8) gx = 8;
   while (gx > 8 && gx - 8 >= p.ntiles * G) gx -= 8;
-  if (p.in_shift) hipLaunchKernelGGL((yl_conv_wino2_kernel<MT, NT, 1>), dim3(gx), dim3(512), lds, st, p);
-  else hipLaunchKernelGGL((yl_conv_wino2_kernel<MT, NT, 0>), dim3(gx), dim3(512), lds, st, p);
+  hipLaunchKernelGGL(wino2_kernel_of(MT, NT, p.in_shift), dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
 }
 
@@ -3246,111 +3152,51 @@ hipError_t yl_launch_conv_wino(const YlConvP& p, hipStream_t st) {
       int mt = nt == 3 && (MTOT / 4) * ((p.NTtot + nt - 1) / nt) >= 3 * YL_NUM_CU ? 4 : 2;
       const unsigned v = YL_DEV_WINO_SHAPE(p.dev);
       if (v == 1) { mt = 4; nt = 4; } else if (v == 2) { mt = 2; nt = 7; } else if (v == 3) { mt = 2; }
-      if (mt == 4 && nt == 3) return wino2_go<4, 3>(p, st, false);
-      if (mt == 4 && nt == 4) return wino2_go<4, 4>(p, st, false);
-      if (mt == 2 && nt == 3) return wino2_go<2, 3>(p, st, false);
-      if (mt == 2 && nt == 4) return wino2_go<2, 4>(p, st, false);
-      if (mt == 2 && nt == 7) return wino2_go<2, 7>(p, st, false);
+      if (wino2_kernel_of(mt, nt, 0)) return wino2_go(p, st, mt, nt);
     }
   }
-  return wino_go(p, st, false);
-}
-
-static hipError_t yl_wino2_init() {
-  YlConvP q = {};
-  hipError_t e = wino2_go<4, 3>(q, nullptr, true);
-  if (e == hipSuccess) e = wino2_go<4, 4>(q, nullptr, true);
-  if (e == hipSuccess) e = wino2_go<2, 3>(q, nullptr, true);
-  if (e == hipSuccess) e = wino2_go<2, 4>(q, nullptr, true);
-  if (e == hipSuccess) e = wino2_go<2, 7>(q, nullptr, true);
-  return e;
+  return wino_go(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-template <typename K>
-int yl_resident_blocks_c(K kernel, size_t lds) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, size_t>, int> cache;
-  const std::pair<const void*, size_t> key((const void*)kernel, lds);
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)kernel, 512, lds) != hipSuccess || nb < 1) nb = 1;
-  if (nb > 4) nb = 4;
-  cache[key] = nb * YL_NUM_CU;
-  return nb * YL_NUM_CU;
-}
-
-template <int DK, int DS, int NTW>
-hipError_t dwc_one(const YlConvMulti& m, int gx, size_t lds, hipStream_t st, bool attr_only, int* resident) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dwc_kernel<DK, DS, NTW>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               YL_DWC_LDS_MAX);
-  if (resident) { *resident = yl_resident_blocks_c(yl_conv_dwc_kernel<DK, DS, NTW>, lds); return hipSuccess; }
-  hipLaunchKernelGGL((yl_conv_dwc_kernel<DK, DS, NTW>), dim3(gx), dim3(512), lds, st, m);
-  return hipGetLastError();
-}
-
-template <int NTW>
-hipError_t dwc_dk(const YlConvMulti& m, int dk, int ds, int gx, size_t lds, hipStream_t st, bool attr_only,
-                  int* resident) {
-  hipError_t e = hipSuccess;
-  if (attr_only || (dk == 3 && ds == 1)) { e = dwc_one<3, 1, NTW>(m, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || (dk == 3 && ds == 2)) { e = dwc_one<3, 2, NTW>(m, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || (dk == 5 && ds == 1)) { e = dwc_one<5, 1, NTW>(m, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || (dk == 5 && ds == 2)) { e = dwc_one<5, 2, NTW>(m, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  return attr_only ? hipSuccess : hipErrorInvalidValue;
-}
-
-hipError_t dwc_any(const YlConvMulti& m, int ntw, int dk, int ds, int gx, size_t lds, hipStream_t st,
-                   bool attr_only, int* resident) {
-  hipError_t e = hipSuccess;
-  if (attr_only || ntw == 1) { e = dwc_dk<1>(m, dk, ds, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || ntw == 2) { e = dwc_dk<2>(m, dk, ds, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || ntw == 3) { e = dwc_dk<3>(m, dk, ds, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || ntw == 4) { e = dwc_dk<4>(m, dk, ds, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  if (attr_only || ntw == 5) { e = dwc_dk<5>(m, dk, ds, gx, lds, st, attr_only, resident); if (!attr_only || e != hipSuccess) return e; }
-  return attr_only ? hipSuccess : hipErrorInvalidValue;
-}
+// yl_conv_dwc_kernel<DK, DS, NTW>: depthwise 3x3 / 5x5 x stride 1 / 2 x NTW (n-tiles per GEMM wave) 1..5, as [NTW - 1][DK == 5][DS == 2]
+#define YL_DWC_SHAPES(NTW) \
+  {{yl_conv_dwc_kernel<3, 1, NTW>, yl_conv_dwc_kernel<3, 2, NTW>}, {yl_conv_dwc_kernel<5, 1, NTW>, yl_conv_dwc_kernel<5, 2, NTW>}}
+const YlMultiKernel dwc_kernels[5][2][2] = {YL_DWC_SHAPES(1), YL_DWC_SHAPES(2), YL_DWC_SHAPES(3), YL_DWC_SHAPES(4), YL_DWC_SHAPES(5)};
 
 int kbmax_of(int ntw) { return ntw == 1 ? 18 : ntw == 2 ? 9 : ntw == 3 ? 6 : 4; }
 
 }  // namespace
 
+// dynamic-LDS limit of every instantiation of this unit: one walk per family over its list
 hipError_t yl_convc_init() {
-  YlConvMulti m = {};
-  YlConvP q = {};
-  hipError_t e = kxk_go<7, 1, 4>(q, 1, nullptr, true);
-  if (e == hipSuccess) e = kxk_go<7, 2, 4>(q, 1, nullptr, true);
-  if (e == hipSuccess) e = kxk_go<7, 1, 8>(q, 1, nullptr, true);
-  if (e == hipSuccess) e = kxk_go<4, 1, 8>(q, 1, nullptr, true);
-  if (e == hipSuccess) e = kxk_go<4, 2, 4>(q, 1, nullptr, true);
-  if (e == hipSuccess) e = yl_ir_init();
-  if (e == hipSuccess) e = pws_nw<6>(q, nullptr, false, true);
-  if (e == hipSuccess) e = pws_nw<7>(q, nullptr, false, true);
-  if (e == hipSuccess) e = pws_nw<8>(q, nullptr, false, true);
-  if (e == hipSuccess) e = pws_nw<9>(q, nullptr, false, true);
-  if (e == hipSuccess) e = pws_nw<11>(q, nullptr, false, true);
-  if (e == hipSuccess) e = pws_nw<13>(q, nullptr, false, true);
-  if (e == hipSuccess) e = dwt_any(m, 0, nullptr, false, false, true);
-  if (e == hipSuccess) e = dwt_splitk(m, nullptr, true);
-  if (e == hipSuccess) e = wino_go(q, nullptr, true);
-  if (e == hipSuccess) e = yl_wino2_init();
-  if (e == hipSuccess) e = dwk_go<7, 1, 4>(q, nullptr, true);
-  if (e == hipSuccess) e = dwk_go<7, 3, 4>(q, nullptr, true);
-  if (e == hipSuccess) e = dwk_go<8, 1, 4>(q, nullptr, true);
-  if (e == hipSuccess) e = dwk_go<8, 2, 4>(q, nullptr, true);
-  if (e == hipSuccess) e = dwl_go<16>(q, nullptr, true);
-  if (e == hipSuccess) e = dwl_go<21>(q, nullptr, true);
-  if (e == hipSuccess) e = yl_dws_init();
+  hipError_t e = hipSuccess;
+  const auto cap = [&e](const auto& kernels, size_t bytes) { if (e == hipSuccess) e = yl_set_lds_cap(kernels, bytes); };
+#define YL_KXK_CAP(A, B, C) cap(yl_conv_kxk_kernel<A, B, C>, 96 * 1024);
+  YL_KXK_SHAPES(YL_KXK_CAP)
+#define YL_IR_CAP(A, B, C, D, E, R, S) cap(yl_ir_kernel<A, B, C, D, E, R, S>, 150 * 1024);
+  YL_IR_SHAPES(YL_IR_CAP)
+  cap(pws_kernels, 64 * 1024);
+  cap(pws_dec_kernels, 64 * 1024);
+  cap(dwt_kernels, 96 * 1024);
+  cap(dwt_splitk_kernels, 96 * 1024);
+  cap(wino_kernels, 96 * 1024);
+#define YL_WINO2_CAP(A, B) cap(yl_conv_wino2_kernel<A, B, 1>, wino2_lds(A)); cap(yl_conv_wino2_kernel<A, B, 0>, wino2_lds(A));
+  YL_WINO2_SHAPES(YL_WINO2_CAP)
+#define YL_DWK_CAP(A, B, C) cap(yl_conv_dwk_kernel<A, B, C>, 96 * 1024);
+  YL_DWK_SHAPES(YL_DWK_CAP)
+#define YL_DWL_CAP(A) cap(yl_conv_dwl_kernel<A>, 128 * 1024);
+  YL_DWL_SHAPES(YL_DWL_CAP)
+#define YL_DWS_CAP(A, G, K, S_) cap(yl_conv_dws_kernel<A, G, K, S_, 4>, 96 * 1024);
+  YL_DWS_SHAPES(YL_DWS_CAP)
 #if !YL_BF16
-  if (e == hipSuccess) e = yl_dwx_init();
+#define YL_DWX_CAP(A, B) cap(yl_conv_dwx_kernel<A, B>, 96 * 1024);
+  YL_DWX_SHAPES(YL_DWX_CAP)
 #endif
-  if (e != hipSuccess) return e;
-  return dwc_any(m, 0, 0, 0, 0, 0, nullptr, true, nullptr);
+  cap(dwc_kernels, YL_DWC_LDS_MAX);
+  return e;
 }
 
 // n problems of identical configuration (m.p[0..n-1] filled like for yl_conv_dwh_kernel).  Returns
@@ -3379,9 +3225,8 @@ hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st) {
     tiles[k] = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW >> 2);
     total += tiles[k];
   }
-  int res = 0;
-  hipError_t e = dwc_any(m, ntw, p.dw_k, p.dw_stride, 0, lds, st, false, &res);
-  if (e != hipSuccess) return e;
+  const YlMultiKernel kern = dwc_kernels[ntw - 1][p.dw_k == 5][p.dw_stride == 2];
+  const int res = yl_resident_blocks((const void*)kern, 512, lds, 4);
   // grid: a multiple of 8 workgroups (XCD-aware tile bands, see the kernel), at most what is co-resident
   long gx = (total + 7) & ~7L;
   if (gx > res) gx = res & ~7L;
@@ -3398,5 +3243,6 @@ hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st) {
     }
     gx = at;
   }
-  return dwc_any(m, ntw, p.dw_k, p.dw_stride, (int)gx, lds, st, false, nullptr);
+  hipLaunchKernelGGL(kern, dim3((unsigned)gx), dim3(512), lds, st, m);
+  return hipGetLastError();
 }

@@ -607,12 +607,13 @@ bool yl_dpq_supported(int cin, int cmid, int cout, int oh, int ow) {
   return false;
 }
 
+static size_t dpq_lds_bytes(int kb, int nc1, int nt3) {
+  return (size_t)(kb * nc1 * 6 + nc1 * 6 * nt3) * 1024 + (size_t)(10 * kb * 16 + nc1 * 96) * 4;
+}
+
 template <int KB, int NC1, int NT3>
-static hipError_t dpq_go(const YlConvP& p, hipStream_t st, bool attr_only) {
-  const size_t lds = (size_t)(KB * NC1 * 6 + NC1 * 6 * NT3) * 1024 + (size_t)(10 * KB * 16 + NC1 * 96) * 4;
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_conv_dpq_kernel<KB, NC1, NT3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds);
+static hipError_t dpq_go(const YlConvP& p, hipStream_t st) {
+  const size_t lds = dpq_lds_bytes(KB, NC1, NT3);
   const long t = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
   long nb = YL_NUM_CU * (DPP_WPE * 4 / DPP_NW);
   if (nb > (t + DPP_NW - 1) / DPP_NW) nb = (t + DPP_NW - 1) / DPP_NW;
@@ -629,7 +630,7 @@ hipError_t yl_launch_conv_dpq(const YlConvP& p, hipStream_t st) {
       p.H != p.OH || p.W != p.OW || !yl_dpq_supported(p.Cin, p.N, c3, p.OH, p.OW))
     return hipErrorNotSupported;
   const int kb = p.Cin / 16, nc1 = p.N / 96, nt3 = (c3 + 15) / 16;
-#define YL_DPQ_RUN(A, B, C) if (kb == A && nc1 == B && nt3 == C) return dpq_go<A, B, C>(p, st, false);
+#define YL_DPQ_RUN(A, B, C) if (kb == A && nc1 == B && nt3 == C) return dpq_go<A, B, C>(p, st);
   YL_DPQ_SHAPES(YL_DPQ_RUN)
 #undef YL_DPQ_RUN
   return hipErrorNotSupported;
@@ -776,9 +777,12 @@ __global__ __launch_bounds__(DPP_NW * 64, 2) void yl_conv_s2c_kernel(YlConvP p) 
   flush_out();
 }
 
-static size_t s2c_lds_bytes(int nt, int nt3) {
+static constexpr size_t s2c_lds_bytes(int nt, int nt3) {
   return (size_t)(9 * nt + nt * nt3) * 1024 + (size_t)(nt + nt3) * 64 + (size_t)DPP_NW * 2 * 6 * 1024;
 }
+// the one instantiation: 3 n-tiles (48 channels) out of the 3x3, <= 2 (32 channels) out of the chained 1x1
+static const YlConvKernel s2c_kernel = yl_conv_s2c_kernel<3, 2>;
+static constexpr size_t s2c_lds = s2c_lds_bytes(3, 2);
 
 bool yl_s2c_supported(int cin, int cout, int c3, int oh, int ow) {
   return cin == 16 && cout == 48 && c3 > 16 && c3 <= 32 && (c3 & 3) == 0 && (oh & 1) == 0 && (ow & 7) == 0;
@@ -794,12 +798,15 @@ hipError_t yl_launch_conv_s2c(const YlConvP& p, hipStream_t st) {
   long nb = YL_NUM_CU;
   if (nb > (t + DPP_NW - 1) / DPP_NW) nb = (t + DPP_NW - 1) / DPP_NW;
   if (nb >= 8) nb &= ~7L;
-  hipLaunchKernelGGL((yl_conv_s2c_kernel<3, 2>), dim3((unsigned)nb), dim3(DPP_NW * 64), s2c_lds_bytes(3, 2), st, p);
+  hipLaunchKernelGGL(s2c_kernel, dim3((unsigned)nb), dim3(DPP_NW * 64), s2c_lds, st, p);
   return hipGetLastError();
 }
 
 static size_t dpp_lds_bytes(int kb, int nt1, int nt3) {
   return (size_t)(kb * nt1 + nt1 * nt3) * 1024 + (size_t)(10 * kb * 16 + nt1 * 16 + nt3 * 16) * 4;
+}
+static size_t dpw_lds_bytes(int kb, int nt1, int nt3) {   // yl_conv_dpw_kernel: + the waves' window rings
+  return dpp_lds_bytes(kb, nt1, nt3) + (size_t)DPW_NW * ((kb % 3 == 0) ? 3 : 2) * (DPW_NW > 8 ? 144 : 192) * 16;
 }
 
 // shapes instantiated: (Cin/16, trunk n-tiles, head-output n-tiles)
@@ -814,16 +821,8 @@ bool yl_dpp_supported(int cin, int cout, int c3, int oh, int ow) {
 }
 
 template <int KB, int NT1, int NT3>
-static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st, bool attr_only) {
-  const size_t lds = dpp_lds_bytes(KB, NT1, NT3);
-  const size_t ldsw = lds + (size_t)DPW_NW * ((KB % 3 == 0) ? 3 : 2) * (DPW_NW > 8 ? 144 : 192) * 16;   // + the waves' window rings
-  if (attr_only) {
-    const hipError_t e = hipFuncSetAttribute((const void*)yl_conv_dpw_kernel<KB, NT1, NT3>,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)yl_conv_dpp_kernel<KB, NT1, NT3>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds);
-  }
+static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st) {
+  const size_t lds = dpp_lds_bytes(KB, NT1, NT3), ldsw = dpw_lds_bytes(KB, NT1, NT3);
   // window-in-LDS form (round 6): depthwise pad 1 on every side; "dev_select" bit 16 keeps the tap-load kernel
   bool win = !(ps[0].dev & YL_DEV_DPW_OFF);
   for (int k = 0; k < n; ++k) win = win && ps[k].dw_pad_t == 1 && ps[k].dw_pad_l == 1;
@@ -865,7 +864,7 @@ hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st) {
         (size_t)ps[k].B * ps[k].H * ps[k].W * ps[k].Cin * 4 >= ((size_t)1 << 31))        // (32-bit byte offsets of the window copies)
       return hipErrorNotSupported;
   const int kb = q.Cin / 16, nt1 = q.N / 16, nt3 = (q.C3 + 15) / 16;
-#define YL_DPP_RUN(A, B, C) if (kb == A && nt1 == B && nt3 == C) return dpp_go<A, B, C>(ps, n, st, false);
+#define YL_DPP_RUN(A, B, C) if (kb == A && nt1 == B && nt3 == C) return dpp_go<A, B, C>(ps, n, st);
   YL_DPP_SHAPES(YL_DPP_RUN)
 #undef YL_DPP_RUN
   return hipErrorNotSupported;
@@ -999,21 +998,17 @@ __global__ __launch_bounds__(K3W_NW * 64, 2) void yl_conv_k3w_kernel(YlConvP p) 
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // no copy may land in LDS after the wave has ended
 }
 
-template <int KB>
+static const YlConvKernel k3w_kernels[2] = {yl_conv_k3w_kernel<1>, yl_conv_k3w_kernel<2>};   // [Cin / 16 - 1]
+
 static hipError_t k3w_go(const YlConvP& p, hipStream_t st) {
+  const int KB = p.Cin / 16;                                          // 1 or 2 (yl_launch_conv_k3w)
+  const YlConvKernel kern = k3w_kernels[KB - 1];
   const size_t lds = (size_t)K3W_NW * KB * 192 * 16;
   const long t = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
-  static int res = 0;
-  if (!res) {
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)yl_conv_k3w_kernel<KB>, K3W_NW * 64, lds) != hipSuccess || nb < 1) nb = 1;
-    if (nb > 2) nb = 2;
-    res = nb * YL_NUM_CU;
-  }
-  long nb = res;
+  long nb = yl_resident_blocks((const void*)kern, K3W_NW * 64, lds, 2);
   if (nb > (t + K3W_NW - 1) / K3W_NW) nb = (t + K3W_NW - 1) / K3W_NW;
   if (nb >= 8) nb &= ~7L;
-  hipLaunchKernelGGL((yl_conv_k3w_kernel<KB>), dim3((unsigned)nb), dim3(K3W_NW * 64), lds, st, p);
+  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(K3W_NW * 64), lds, st, p);
   return hipGetLastError();
 }
 
@@ -1030,18 +1025,18 @@ hipError_t yl_launch_conv_k3w(const YlConvP& p, hipStream_t st) {
   if (p.wino) return hipErrorNotSupported;
   if ((p.OH >> 2) * (p.OW >> 2) < 1600) return hipErrorNotSupported;    // grids below 160 x 160: the other kernels (by SHAPE, not by batch: batch-invariant results)
   if ((size_t)p.B * p.H * p.W * p.Cin * 4 >= ((size_t)1 << 31)) return hipErrorNotSupported;            // 32-bit byte offsets
-  return p.Cin == 16 ? k3w_go<1>(p, st) : k3w_go<2>(p, st);
+  return k3w_go(p, st);
 }
 
 hipError_t yl_dpp_init() {
-  hipError_t e = hipFuncSetAttribute((const void*)yl_conv_s2c_kernel<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)s2c_lds_bytes(3, 2));
-  YlConvP q0{};
-#define YL_DPQ_ATTR(A, B, C) if (e == hipSuccess) e = dpq_go<A, B, C>(q0, nullptr, true);
-  YL_DPQ_SHAPES(YL_DPQ_ATTR)
-#undef YL_DPQ_ATTR
-#define YL_DPP_ATTR(A, B, C) if (e == hipSuccess) e = dpp_go<A, B, C>(nullptr, 0, nullptr, true);
-  YL_DPP_SHAPES(YL_DPP_ATTR)
-#undef YL_DPP_ATTR
+  hipError_t e = yl_set_lds_cap(s2c_kernel, s2c_lds);
+#define YL_DPQ_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpq_kernel<A, B, C>, dpq_lds_bytes(A, B, C));
+  YL_DPQ_SHAPES(YL_DPQ_CAP)
+#undef YL_DPQ_CAP
+#define YL_DPP_CAP(A, B, C)                                                                     \
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpw_kernel<A, B, C>, dpw_lds_bytes(A, B, C)); \
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpp_kernel<A, B, C>, dpp_lds_bytes(A, B, C));
+  YL_DPP_SHAPES(YL_DPP_CAP)
+#undef YL_DPP_CAP
   return e;
 }

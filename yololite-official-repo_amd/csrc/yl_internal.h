@@ -2,6 +2,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <map>
+#include <mutex>
+#include <type_traits>
+#include <utility>
 #include "../../include/yololite_hip.h"
 
 // activations that are not a clamp: SiLU runs in the conv kernels' generic epilogue (the fast clamp epilogues refuse it);
@@ -243,13 +247,67 @@ hipError_t yl_launch_masks_image(const YlLevels& lv, int B, const float* proto, 
                                  int packed, unsigned char* masks, hipStream_t st);
 hipError_t yl_post_init();   // one-time function attributes (large dynamic LDS)
 
-hipError_t yl_launch_stem(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv(const YlConvP& p, int tile_hint, hipStream_t st);
-hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStream_t st);   // n <= 4, same config
-hipError_t yl_launch_dw(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_stemblock(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_stemdw(const YlConvP& p, hipStream_t st);   // stem -> depthwise 3x3 s1 -> 1x1 (EfficientNet-Lite entry, round 6)
-hipError_t yl_stemblock_init();
+// ---- host-side launch helpers of the conv units (yl_conv.hip, yl_convc.hip, yl_dpp.hip, yl_stemblock.hip) ----------
+// Every kernel of a family has one signature, so a family's instantiation list hands out plain function pointers: the
+// same pointer serves the LDS-limit pass (yl_*_init), the occupancy query and the launch.
+typedef void (*YlConvKernel)(YlConvP);
+typedef void (*YlMultiKernel)(YlConvMulti);
+
+// raise the dynamic-LDS limit of a kernel, or of every kernel of a table of them (nullptr: no such instantiation).  For the
+// yl_*_init passes: once per device, eagerly from yl_create -- never from a launcher, which may run inside a stream capture
+template <typename T>
+hipError_t yl_set_lds_cap(const T& kernels, size_t bytes) {
+  if constexpr (std::is_array<T>::value) {
+    for (const auto& k : kernels) {
+      const hipError_t e = yl_set_lds_cap(k, bytes);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  } else {
+    const void* const f = (const void*)kernels;
+    return f ? hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipSuccess;
+  }
+}
+
+// persistent grids are sized to what is co-resident (workgroups per CU from the occupancy query, at most `cap`, x 256
+// CUs): a workgroup that has to queue behind another one re-stages its weights into LDS for nothing.
+// The occupancy query costs the host ~10 us: asked once per (kernel, LDS size), then served from a small cache
+// (eager launches of the 20-70 us layers were host-bound otherwise; graph replays never come here).  One cache for all
+// conv units (inline: the copies of the translation units are merged at link time), guarded for contexts on several threads.
+inline int yl_resident_blocks(const void* kernel, int threads, size_t lds, int cap) {
+  static std::mutex mu;
+  static std::map<std::pair<const void*, size_t>, int> cache;
+  const std::pair<const void*, size_t> key(kernel, lds);
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  int nb = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, threads, lds) != hipSuccess || nb < 1) nb = 1;
+  if (nb > cap) nb = cap;
+  cache[key] = nb * YL_NUM_CU;
+  return nb * YL_NUM_CU;
+}
+
+// Launchers and LDS-limit passes that exist once per precision mode: fp32 (no suffix), _bf16 (bf16-MFMA: second compilation of
+// yl_conv.hip / yl_convc.hip / yl_stemblock.hip with -DYL_BF16=1, see yl_lp.h), _f16 (fp16-MFMA: + -DYL_F16=1, option "mfma_f16")
+// and _f16s (fp16 STORAGE: + -DYL_F16S=1, option "store_f16": YlConvP's activation pointers are _Float16* in those units, same
+// struct layout).  In the reduced-precision units the plain names are renamed before this header is read, so the launchers
+// of yl_convc.hip below need no suffixed twins.
+#define YL_MODE_PROTOTYPES(S)                                                                                           \
+  hipError_t yl_launch_conv##S(const YlConvP& p, int tile_hint, hipStream_t st);                                        \
+  hipError_t yl_launch_conv_multi##S(const YlConvP* ps, int n, int tile_hint, hipStream_t st); /* n <= 4, same config */ \
+  hipError_t yl_launch_stem##S(const YlConvP& p, hipStream_t st);                                                       \
+  hipError_t yl_launch_dw##S(const YlConvP& p, hipStream_t st);                                                         \
+  hipError_t yl_launch_stemblock##S(const YlConvP& p, hipStream_t st);                                                  \
+  hipError_t yl_launch_stemdw##S(const YlConvP& p, hipStream_t st); /* stem -> depthwise 3x3 s1 -> 1x1 (EfficientNet-Lite entry) */ \
+  hipError_t yl_conv_init##S();                                                                                         \
+  hipError_t yl_convc_init##S();                                                                                        \
+  hipError_t yl_stemblock_init##S();
+YL_MODE_PROTOTYPES()
+YL_MODE_PROTOTYPES(_bf16)
+YL_MODE_PROTOTYPES(_f16)
+YL_MODE_PROTOTYPES(_f16s)
+
 // depthwise 3x3 -> 1x1 -> 1x1 head output + decode as one launch (yl_dpp.hip)
 hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st);
 bool yl_dpp_supported(int cin, int cout, int c3, int oh, int ow);
@@ -262,70 +320,30 @@ hipError_t yl_launch_conv_dpq(const YlConvP& p, hipStream_t st);
 hipError_t yl_launch_conv_k3w(const YlConvP& p, hipStream_t st);
 bool yl_dpq_supported(int cin, int cmid, int cout, int oh, int ow);
 bool yl_stemblock_supported(int c1, int c2, int c3);
-hipError_t yl_conv_init();
 bool yl_uib_supported(int c1, int cmid, int n, int dk);
 // block-cooperative depthwise -> 1x1 kernel (yl_convc.hip); hipErrorNotSupported = shape outside its limits
 hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st);
-hipError_t yl_launch_conv_dwc_bf16(YlConvMulti& m, hipStream_t st);
 // wave-autonomous 1x1 conv for small pixel counts (yl_convc.hip); hipErrorNotSupported = not a plain 1x1 layer
 hipError_t yl_launch_conv_pwt(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_pwt_bf16(const YlConvP& p, hipStream_t st);
 hipError_t yl_launch_conv_pwt_multi(const YlConvP* ps, int n, hipStream_t st);
-hipError_t yl_launch_conv_pwt_multi_bf16(const YlConvP* ps, int n, hipStream_t st);
 // fused inverted-residual block with a workgroup-level halo (yl_convc.hip, round 3); hipErrorNotSupported = yl_uib_kernel
 hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_ir_bf16(const YlConvP& p, hipStream_t st);
 bool yl_ir_supported(int c1, int cmid, int n, int dk, int ds, int oh, int ow);
 // plain 1x1 conv with a double-buffered weight stream for wide layers (yl_convc.hip); hipErrorNotSupported = pwt runs it
 hipError_t yl_launch_conv_pws(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_pws_bf16(const YlConvP& p, hipStream_t st);
 // dense k x k conv with a double-buffered weight stream (yl_convc.hip); hipErrorNotSupported = other kernel runs it
 hipError_t yl_launch_conv_kxk(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_kxk_bf16(const YlConvP& p, hipStream_t st);
 // wave-autonomous depthwise -> 1x1 kernel (yl_convc.hip); hipErrorNotSupported = shape outside its limits
 hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st);
-hipError_t yl_launch_conv_dwt_bf16(YlConvMulti& m, hipStream_t st);
 // the same projection (depthwise stride 1 -> 64 channels) with the next layer's plain 1x1 (out3) chained behind it
 // (yl_convc.hip, fp32 unit only); hipErrorNotSupported = shape / configuration not instantiated
 hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st);
 bool yl_dwx_supported(int cin, int cout, int dw_k, int dw_stride, int cout1, int oh, int ow);
 // streamed-weight depthwise 3x3 -> 1x1 kernel for K >= 192 and more than 8 n-tiles (yl_convc.hip)
 hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_dwk_bf16(const YlConvP& p, hipStream_t st);
 // depthwise k x k -> 1x1 for >= 192 depthwise channels: streamed 1x1 weights AND tap weights, halo patch through LDS (yl_convc.hip,
 // round 5); hipErrorNotSupported = shape not instantiated
 hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_dws_bf16(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_dws_f16(const YlConvP& p, hipStream_t st);
 bool yl_dws_supported(int cin, int n, int dk, int ds, int oh, int ow);
 // Winograd F(2x2,3x3) dense 3x3 (yl_convc.hip); hipErrorNotSupported = not this layer
 hipError_t yl_launch_conv_wino(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_conv_wino_bf16(const YlConvP& p, hipStream_t st);
-hipError_t yl_convc_init();
-hipError_t yl_convc_init_bf16();
-// bf16-MFMA builds of yl_conv.hip / yl_stemblock.hip (compiled a second time with -DYL_BF16=1, see yl_dev.h)
-hipError_t yl_launch_conv_bf16(const YlConvP& p, int tile_hint, hipStream_t st);
-hipError_t yl_launch_conv_multi_bf16(const YlConvP* ps, int n, int tile_hint, hipStream_t st);
-hipError_t yl_conv_init_bf16();
-hipError_t yl_launch_stemblock_bf16(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_stemdw_bf16(const YlConvP& p, hipStream_t st);
-hipError_t yl_stemblock_init_bf16();
-// fp16-MFMA builds (third compilation, -DYL_BF16=1 -DYL_F16=1: option "mfma_f16")
-hipError_t yl_launch_conv_f16(const YlConvP& p, int tile_hint, hipStream_t st);
-hipError_t yl_launch_conv_multi_f16(const YlConvP* ps, int n, int tile_hint, hipStream_t st);
-hipError_t yl_conv_init_f16();
-hipError_t yl_convc_init_f16();
-hipError_t yl_launch_stemblock_f16(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_stemdw_f16(const YlConvP& p, hipStream_t st);
-hipError_t yl_stemblock_init_f16();
-// fp16-STORAGE builds (fourth compilation, -DYL_BF16=1 -DYL_F16=1 -DYL_F16S=1: option "store_f16"): fp16 operands and fp16
-// activation tensors in HBM; YlConvP's activation pointers are _Float16* in those units (same struct layout)
-hipError_t yl_launch_conv_f16s(const YlConvP& p, int tile_hint, hipStream_t st);
-hipError_t yl_launch_conv_multi_f16s(const YlConvP* ps, int n, int tile_hint, hipStream_t st);
-hipError_t yl_launch_stem_f16s(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_dw_f16s(const YlConvP& p, hipStream_t st);
-hipError_t yl_conv_init_f16s();
-hipError_t yl_convc_init_f16s();
-hipError_t yl_launch_stemblock_f16s(const YlConvP& p, hipStream_t st);
-hipError_t yl_launch_stemdw_f16s(const YlConvP& p, hipStream_t st);
-hipError_t yl_stemblock_init_f16s();

@@ -673,17 +673,19 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemdw_kernel(YlConvP p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // no copy may land in LDS after the wave has ended
 }
 
-template <int NT3>
-static hipError_t sd_go(const YlConvP& p, hipStream_t st, bool attr_only) {
-  constexpr int NWV = 4;
-  const size_t lds = (size_t)NWV * (SD_NP * 36 + SD_NSEG * SD_SP) * 4;                 // 81792 B: two workgroups per CU
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_stemdw_kernel<NT3, NWV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+// yl_stemdw_kernel<NT3, 4 waves per workgroup>: one or two n-tiles out of the 1x1, as [C3 > 16]
+#define SD_NWV 4
+static const YlConvKernel sd_kernels[2] = {yl_stemdw_kernel<1, SD_NWV>, yl_stemdw_kernel<2, SD_NWV>};
+static constexpr size_t sd_lds = (size_t)SD_NWV * (SD_NP * 36 + SD_NSEG * SD_SP) * 4;               // 81792 B: two workgroups per CU
+
+static hipError_t sd_go(const YlConvP& p, hipStream_t st) {
+  constexpr int NWV = SD_NWV;
+  const size_t lds = sd_lds;
   const long ntiles = (long)p.B * ((p.OW + SD_T - 1) / SD_T) * ((p.OH + SD_T - 1) / SD_T);
   long gx = 2 * YL_NUM_CU;                                            // two 4-wave workgroups per CU (82 KB of LDS each)
   if (gx > (ntiles + NWV - 1) / NWV) gx = (ntiles + NWV - 1) / NWV;
   if (gx >= 8) gx &= ~7L;
-  hipLaunchKernelGGL((yl_stemdw_kernel<NT3, NWV>), dim3((unsigned)gx), dim3(NWV * 64), lds, st, p);
+  hipLaunchKernelGGL(sd_kernels[p.C3 > 16], dim3((unsigned)gx), dim3(NWV * 64), lds, st, p);
   return hipGetLastError();
 }
 
@@ -692,14 +694,32 @@ static hipError_t sd_go(const YlConvP& p, hipStream_t st, bool attr_only) {
 hipError_t yl_launch_stemdw(const YlConvP& p, hipStream_t st) {
   if (p.stride != 2 || p.k != 3 || p.C1 != 32 || p.C2 != 32 || p.C3 < 4 || p.C3 > 32 || (p.C3 & 3) || p.OH != p.SH || p.OW != p.SW)
     return hipErrorInvalidValue;
-  return p.C3 <= 16 ? sd_go<1>(p, st, false) : sd_go<2>(p, st, false);
+  return sd_go(p, st);
 }
 
-template <int NT1, int NT2, int NT3, int NWV>
-static hipError_t sb_launch(const YlConvP& p0, hipStream_t st, bool attr_only, size_t lds) {
-  if (attr_only)
-    return hipFuncSetAttribute((const void*)yl_stemblock_kernel<NT1, NT2, NT3, NWV>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+// An instantiation of yl_stemblock_kernel<NT1, NT2, NT3, NWV>: one 8-wave workgroup per CU shares ONE copy of the conv2 / conv3
+// weights where that fits the 160 KB of LDS next to the eight wave-private patches and stages; otherwise 4 waves.
+struct SbForm { YlConvKernel kern; int nwv; size_t lds; };
+template <int NT1, int NT2, int NT3>
+static SbForm sb_form() {
+  constexpr int P1 = NT1 * 16 + 4;
+  constexpr size_t wave_b = (size_t)(SB_NPATCH * P1 + SB_NSTG * 256) * 4;
+  constexpr size_t w_b = (size_t)(9 * NT1 * NT2 + NT2 * NT3) * 1024;
+  if constexpr (8 * wave_b + w_b <= 160 * 1024) return {yl_stemblock_kernel<NT1, NT2, NT3, 8>, 8, 8 * wave_b + w_b};
+  else return {yl_stemblock_kernel<NT1, NT2, NT3, 4>, 4, 4 * wave_b + w_b};
+}
+// instantiated: (C1 / 16, ceil(C2 / 16), ceil(C3 / 16) -- 0 = no 1x1)
+#define YL_SB_SHAPES_OF(X, NT1) X(NT1, 1, 0) X(NT1, 1, 1) X(NT1, 2, 0) X(NT1, 2, 2) X(NT1, 1, 2) X(NT1, 2, 1)
+#define YL_SB_SHAPES(X) YL_SB_SHAPES_OF(X, 1) YL_SB_SHAPES_OF(X, 2)
+static SbForm sb_form_of(int nt1, int nt2, int nt3) {
+#define YL_SB_PICK(A, B, C) if (nt1 == A && nt2 == B && nt3 == C) return sb_form<A, B, C>();
+  YL_SB_SHAPES(YL_SB_PICK)
+#undef YL_SB_PICK
+  return {nullptr, 0, 0};
+}
+
+static hipError_t sb_launch(const YlConvP& p0, hipStream_t st, const SbForm& f) {
+  const int NWV = f.nwv;
   YlConvP p = p0;
   if (p.stride != 2 || p.k != 3) return hipErrorInvalidValue;   // the staged input block is 11 x 35 per channel
   // strips of ~10 tiles: long enough that the one extra m-tile of a strip's first tile is noise (1.4 of 147 MFMAs per
@@ -723,43 +743,16 @@ static hipError_t sb_launch(const YlConvP& p0, hipStream_t st, bool attr_only, s
   int gx = (8 / NWV) * YL_NUM_CU;
   if (gx > (nstrips + NWV - 1) / NWV) gx = (int)((nstrips + NWV - 1) / NWV);
   if (gx >= 8) gx &= ~7;                                  // multiple of 8: XCD-aware strip ranges (see the kernel)
-  hipLaunchKernelGGL((yl_stemblock_kernel<NT1, NT2, NT3, NWV>), dim3(gx), dim3(NWV * 64), lds, st, p);
+  hipLaunchKernelGGL(f.kern, dim3(gx), dim3(NWV * 64), f.lds, st, p);
   return hipGetLastError();
 }
 
-// One 8-wave workgroup per CU shares ONE copy of the conv2 / conv3 weights where that fits the 160 KB of LDS next to
-// the eight wave-private patches and stages; otherwise 4 waves.
-template <int NT1, int NT2, int NT3>
-static hipError_t sb_go(const YlConvP& p0, hipStream_t st, bool attr_only) {
-  constexpr int P1 = NT1 * 16 + 4;
-  constexpr size_t wave_b = (size_t)(SB_NPATCH * P1 + SB_NSTG * 256) * 4;
-  constexpr size_t w_b = (size_t)(9 * NT1 * NT2 + NT2 * NT3) * 1024;
-  if constexpr (8 * wave_b + w_b <= 160 * 1024) return sb_launch<NT1, NT2, NT3, 8>(p0, st, attr_only, 8 * wave_b + w_b);
-  else return sb_launch<NT1, NT2, NT3, 4>(p0, st, attr_only, 4 * wave_b + w_b);
-}
-
-template <int NT1>
-static hipError_t sb_dispatch(const YlConvP& p, hipStream_t st, bool attr_only) {
-  const int nt2 = (p.C2 + 15) / 16, nt3 = (p.C3 + 15) / 16;
-  hipError_t e = hipSuccess;
-  bool hit = false;
-#define SB_CASE(A, B)                                                     \
-  if (attr_only || (nt2 == A && nt3 == B)) {                              \
-    hit = true;                                                           \
-    if ((e = sb_go<NT1, A, B>(p, st, attr_only)) != hipSuccess) return e; \
-  }
-  SB_CASE(1, 0) SB_CASE(1, 1) SB_CASE(2, 0) SB_CASE(2, 2) SB_CASE(1, 2) SB_CASE(2, 1)
-#undef SB_CASE
-  return hit ? e : hipErrorInvalidValue;
-}
-
 hipError_t yl_stemblock_init() {
-  YlConvP p{};
-  hipError_t e = sb_dispatch<1>(p, nullptr, true);
-  if (e != hipSuccess) return e;
-  if ((e = sd_go<1>(p, nullptr, true)) != hipSuccess) return e;
-  if ((e = sd_go<2>(p, nullptr, true)) != hipSuccess) return e;
-  return sb_dispatch<2>(p, nullptr, true);
+  hipError_t e = yl_set_lds_cap(sd_kernels, sd_lds);
+#define YL_SB_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(sb_form<A, B, C>().kern, 160 * 1024);
+  YL_SB_SHAPES(YL_SB_CAP)
+#undef YL_SB_CAP
+  return e;
 }
 
 bool yl_stemblock_supported(int c1, int c2, int c3) {
@@ -768,7 +761,7 @@ bool yl_stemblock_supported(int c1, int c2, int c3) {
 }
 
 hipError_t yl_launch_stemblock(const YlConvP& p, hipStream_t st) {
-  if (p.C1 == 32) return sb_dispatch<2>(p, st, false);
-  if (p.C1 == 16) return sb_dispatch<1>(p, st, false);
-  return hipErrorInvalidValue;
+  if (p.C1 != 16 && p.C1 != 32) return hipErrorInvalidValue;
+  const SbForm f = sb_form_of(p.C1 / 16, (p.C2 + 15) / 16, (p.C3 + 15) / 16);
+  return f.kern ? sb_launch(p, st, f) : hipErrorInvalidValue;
 }
