@@ -496,13 +496,14 @@ yl_status yl_eval_coco_accumulate(const int32_t* order_dev, const int32_t* rank_
                                   int32_t num_max_dets, const double* rec_thrs_dev, int32_t num_rec,
                                   double* precision_dev, double* recall_dev, void* stream);
 
-/* ---- validation loss: the forward of the reference's LossAF (scripts/loss/loss.py:283-436), fp32 ------------
+/* ---- the reference's LossAF (scripts/loss/loss.py:283-436), fp32: the forward, and its backward further down --
  * SimOTA-style assignment (centre mask AND level gate, orphan rescue, six-term cost, dynamic k from the topk_limit
  * largest IoUs, conflicts to the smallest cost / lowest box), then per image box = lambda_box * mean(1 - CIoU),
  * cls = lambda_cls * mean(cross-entropy with label smoothing) over the positives, obj = lambda_obj * (mean BCE of
  * the positives against clamp(IoU, 0, 1) + mean of the K = min(max(64, 3 * positives), negatives) largest BCE of
  * the rest against 0); images without boxes or without positives contribute the hard-negative term only.  The
- * batch result is the SUM over images; pos = images with positives / batch.  No backward pass.
+ * batch result is the SUM over images; pos = images with positives / batch.  yl_loss_af itself keeps no state
+ * for a backward pass (yl_loss_af_train does).
  * cfg carries the constructor's arguments as given (area_cells_min / area_cells_max BEFORE area_tol is applied).
  * topk_limit must be 1..YL_LOSS_MAX_TOPK; one anchor per cell only (the reference's anchor grid has no room for
  * more): YL_ERR_UNSUPPORTED otherwise.  The reference's focal / gamma / alpha arguments have no effect in its
@@ -527,6 +528,37 @@ typedef struct yl_loss_cfg {
 yl_status yl_loss_af(yl_ctx* ctx, const float* const* levels_dev, int32_t batch, const float* gt_xyxy_dev,
                      const int32_t* gt_label_dev, const int32_t* gt_off_dev, int32_t num_gt, const yl_loss_cfg* cfg,
                      float* per_image_dev, int32_t* assign_dev, float* out4_dev, void* stream);
+
+/* ---- the loss's backward pass: d(box + obj + cls)/d(level tensors), in the level tensors' own layout ---------
+ * Nothing of the assignment is differentiated in the reference (top-k indices, .int() and boolean masks carry no
+ * gradient, the objectness target is detached), so the gradient is closed-form per anchor:
+ *   positive, columns 0-3      lambda_box / npos * d(1 - CIoU)/d(x1,y1,x2,y2) chained through the train-time decode
+ *                              (alpha of CIoU is a constant; an exp size outside its clamp [-10, 8] has derivative 0)
+ *   positive, column 4         lambda_obj / npos * (sigmoid(x) - clamp(IoU, 0, 1))
+ *   positive, columns 5..5+C-1 lambda_cls / npos * (softmax(z) - ((1 - e) * onehot + e / C));  +0 when C = 1
+ *   selected negative, col 4   lambda_obj / K * sigmoid(x)
+ *   every other element        +0.0 (unselected negatives, mask-coefficient columns)
+ * all times grad_out.  The selected negatives are the K = min(max(64, 3 * npos), N - npos) largest BCE(x, 0) of the
+ * non-positives, decided by the same fp32 term the forward's radix select saw.  TIES: of the entries whose term equals
+ * the K-th largest bit for bit, the ones with the lowest anchor index are selected (torch.topk leaves that choice
+ * unspecified).  KINKS follow torch: clamp passes the gradient at its boundary, binary max / min split it between
+ * equal arguments.  The non-zero rows are evaluated in float64 from the fp32 logits and rounded once.
+ *
+ * yl_loss_af_train is yl_loss_af with two REQUIRED outputs that the backward needs: assign_dev[batch][N] and
+ * sel_dev[batch][4] int32 = npos, K, the bits of the K-th largest negative term, and the tie cut (entries equal to the
+ * K-th term are selected when their anchor index is below it).  Same numbers as yl_loss_af, bit for bit.
+ * yl_loss_af_backward reads those two, the same levels / ground truths / cfg, and grad_out_dev (ONE float in device
+ * memory, never read on the host) and writes grad_levels_dev[l], one tensor per level shaped like levels_dev[l]: every
+ * element exactly once, none read.  One kernel on `stream`; no synchronisation, no atomics: equal inputs give equal
+ * bits, and an image's rows do not depend on its batch. */
+yl_status yl_loss_af_train(yl_ctx* ctx, const float* const* levels_dev, int32_t batch, const float* gt_xyxy_dev,
+                           const int32_t* gt_label_dev, const int32_t* gt_off_dev, int32_t num_gt,
+                           const yl_loss_cfg* cfg, float* per_image_dev, int32_t* assign_dev, int32_t* sel_dev,
+                           float* out4_dev, void* stream);
+yl_status yl_loss_af_backward(yl_ctx* ctx, const float* const* levels_dev, int32_t batch, const float* gt_xyxy_dev,
+                              const int32_t* gt_label_dev, const int32_t* gt_off_dev, int32_t num_gt,
+                              const yl_loss_cfg* cfg, const int32_t* assign_dev, const int32_t* sel_dev,
+                              const float* grad_out_dev, float* const* grad_levels_dev, void* stream);
 
 /* ---- Kalman-SORT tracker bank (reference tools/tracker.py:9-326) -------------
  * The reference's KalmanSortTracker follows ONE stream on the host.  A yl_tracker holds `num_streams`

@@ -140,6 +140,10 @@ SYMBOLS = [
     ("yl_eval_coco_accumulate", C.c_int32, [_vp, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, _vp,
                                             C.c_int32, _vp, C.c_int32, _vp, _vp, _vp]),
     ("yl_loss_af", C.c_int32, [_vp, _vpp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.POINTER(yl_loss_cfg), _vp, _vp, _vp, _vp]),
+    ("yl_loss_af_train", C.c_int32, [_vp, _vpp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.POINTER(yl_loss_cfg), _vp, _vp, _vp,
+                                     _vp, _vp]),
+    ("yl_loss_af_backward", C.c_int32, [_vp, _vpp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.POINTER(yl_loss_cfg), _vp, _vp,
+                                        _vp, _vpp, _vp]),
     ("yl_track_create", C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_int32,
                                     C.POINTER(_vp)]),
     ("yl_track_destroy", None, [_vp]),

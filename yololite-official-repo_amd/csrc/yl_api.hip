@@ -2077,10 +2077,10 @@ yl_status yl_nms(yl_ctx* c, const float* boxes, const float* scores, int32_t n, 
   return YL_OK;
 }
 
-yl_status yl_loss_af(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy, const int32_t* gt_label,
-                     const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg, float* per_image, int32_t* assign,
-                     float* out4, void* stream) {
-  if (!c || !levels || !cfg || !out4 || B < 1 || num_gt < 0) return YL_ERR_INVALID;
+// argument checks shared by the three loss entries
+static yl_status loss_check(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy, const int32_t* gt_label,
+                            const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg) {
+  if (!c || !levels || !cfg || B < 1 || num_gt < 0) return YL_ERR_INVALID;
   if (num_gt > 0 && (!gt_xyxy || !gt_label || !gt_off)) return fail(c, YL_ERR_INVALID, "ground-truth arrays are NULL");
   if (cfg->num_classes != c->C || cfg->img_size != c->img_size)
     return fail(c, YL_ERR_INVALID, "yl_loss_cfg num_classes / img_size differ from the context's");
@@ -2093,6 +2093,16 @@ yl_status yl_loss_af(yl_ctx* c, const float* const* levels, int32_t B, const flo
   if (cfg->topk_limit < 1 || cfg->topk_limit > YL_LOSS_MAX_TOPK)
     return fail(c, YL_ERR_UNSUPPORTED, "topk_limit must be 1.." + std::to_string(YL_LOSS_MAX_TOPK));
   if (!(cfg->area_tol > 0.0f)) return fail(c, YL_ERR_INVALID, "area_tol must be positive");
+  return YL_OK;
+}
+
+// yl_loss_af (sel == nullptr) and yl_loss_af_train
+static yl_status loss_forward(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy, const int32_t* gt_label,
+                              const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg, float* per_image,
+                              int32_t* assign, int32_t* sel, float* out4, void* stream) {
+  if (!out4) return YL_ERR_INVALID;
+  const yl_status chk = loss_check(c, levels, B, gt_xyxy, gt_label, gt_off, num_gt, cfg);
+  if (chk != YL_OK) return chk;
   HIPCHK(c, hipSetDevice(c->device));
   if (B > c->loss_cap_batch) {
     hipFree(c->ws_loss_keys); hipFree(c->ws_loss_neg); hipFree(c->ws_loss_pi); hipFree(c->ws_loss_pos);
@@ -2115,8 +2125,43 @@ yl_status yl_loss_af(yl_ctx* c, const float* const* levels, int32_t B, const flo
   p.gt = gt_xyxy; p.label = gt_label; p.off = gt_off; p.T = num_gt; p.B = B;
   p.keys = c->ws_loss_keys; p.negv = c->ws_loss_neg;
   p.per_image = per_image ? per_image : c->ws_loss_pi;
-  p.has_pos = c->ws_loss_pos; p.assign = assign; p.out4 = out4;
+  p.has_pos = c->ws_loss_pos; p.assign = assign; p.out4 = out4; p.sel = sel;
   HIPCHK(c, yl_launch_loss_af(lv, p, (hipStream_t)stream));
+  return YL_OK;
+}
+
+
+yl_status yl_loss_af(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy, const int32_t* gt_label,
+                     const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg, float* per_image, int32_t* assign,
+                     float* out4, void* stream) {
+  return loss_forward(c, levels, B, gt_xyxy, gt_label, gt_off, num_gt, cfg, per_image, assign, nullptr, out4, stream);
+}
+
+yl_status yl_loss_af_train(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy,
+                           const int32_t* gt_label, const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg,
+                           float* per_image, int32_t* assign, int32_t* sel, float* out4, void* stream) {
+  if (!assign || !sel) return c ? fail(c, YL_ERR_INVALID, "yl_loss_af_train needs assign_dev and sel_dev") : YL_ERR_INVALID;
+  return loss_forward(c, levels, B, gt_xyxy, gt_label, gt_off, num_gt, cfg, per_image, assign, sel, out4, stream);
+}
+
+yl_status yl_loss_af_backward(yl_ctx* c, const float* const* levels, int32_t B, const float* gt_xyxy,
+                              const int32_t* gt_label, const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg,
+                              const int32_t* assign, const int32_t* sel, const float* grad_out,
+                              float* const* grad_levels, void* stream) {
+  const yl_status chk = loss_check(c, levels, B, gt_xyxy, gt_label, gt_off, num_gt, cfg);
+  if (chk != YL_OK) return chk;
+  if (!assign || !sel || !grad_out || !grad_levels) return fail(c, YL_ERR_INVALID, "yl_loss_af_backward: a NULL argument");
+  for (int l = 0; l < c->L; ++l)
+    if (!grad_levels[l]) return fail(c, YL_ERR_INVALID, "yl_loss_af_backward: a NULL gradient tensor");
+  HIPCHK(c, hipSetDevice(c->device));
+  YlLevels lv;
+  fill_levels(c, levels, lv);
+  YlLossGradP p;
+  memset(&p, 0, sizeof(p));
+  p.cfg = *cfg;
+  p.gt = gt_xyxy; p.label = gt_label; p.assign = assign; p.sel = sel; p.gout = grad_out; p.B = B;
+  for (int l = 0; l < c->L; ++l) p.out[l] = grad_levels[l];
+  HIPCHK(c, yl_launch_loss_af_grad(lv, p, (hipStream_t)stream));
   return YL_OK;
 }
 

@@ -78,8 +78,21 @@ struct YlLossP {
   int* has_pos;                 // [B]
   int* assign;                  // [B][N] or nullptr
   float* out4;
+  int* sel;                     // [B][4] or nullptr: npos, K, bits of the K-th largest negative term, tie cut (the backward's state)
 };
 hipError_t yl_launch_loss_af(const YlLevels& lv, const YlLossP& p, hipStream_t st);
+// the loss's backward (yl_loss.hip): one launch on `st` that writes every element of the level gradients once
+struct YlLossGradP {
+  yl_loss_cfg cfg;
+  const float* gt;              // [T][4]
+  const int* label;             // [T]
+  const int* assign;            // [B][N] from the forward
+  const int* sel;               // [B][4] from the forward
+  const float* gout;            // one float: d(result)/d(loss)
+  float* out[YL_MAX_LEVELS];    // level l: [B, 1, S, S, E] contiguous, like YlLevels::ptr[l]
+  int B;
+};
+hipError_t yl_launch_loss_af_grad(const YlLevels& lv, const YlLossGradP& p, hipStream_t st);
 
 // ---- activation element type of a translation unit.  fp32 everywhere except the FOURTH compilation of the conv units
 // (-DYL_BF16=1 -DYL_F16=1 -DYL_F16S=1, option "store_f16", round 6): activation tensors live in HBM as fp16 -- the storage side

@@ -1,5 +1,6 @@
-// Validation loss on the device: the forward of the reference's LossAF (scripts/loss/loss.py:283-436), fp32, no
-// backward.  Three launches per batch, no host round trip, no floating-point atomics:
+// The reference's LossAF (scripts/loss/loss.py:283-436) on the device, fp32: the forward (validation loss and training
+// criterion) and, further down, its backward.  Forward: three launches per batch, no host round trip, no floating-point
+// atomics:
 //   yl_loss_assign_kernel   one workgroup per ground-truth box: SimOTA candidate set, dynamic k, matches
 //   yl_loss_reduce_kernel   one workgroup per image: positives (CIoU / cross-entropy / BCE), hard negatives
 //   yl_loss_sum_kernel      one thread: the per-image parts added in image order
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(YL_LOSS_RT) void yl_loss_reduce_kernel(YlLevels lv,
   __shared__ int s_wi[YL_LOSS_RT / 64];
   __shared__ int s_hist[256];
   __shared__ unsigned s_prefix;
-  __shared__ int s_need;
+  __shared__ int s_need, s_cut;
   const int tid = threadIdx.x, b = blockIdx.x, N = lv.N;
   const yl_loss_cfg& c = p.cfg;
   const unsigned long long* keys = p.keys + (size_t)b * N;
@@ -367,6 +368,8 @@ __global__ __launch_bounds__(YL_LOSS_RT) void yl_loss_reduce_kernel(YlLevels lv,
   const int nneg = N - npos;
   const int K = min(max(64, 3 * npos), nneg);
   double negmean = 0.0;
+  unsigned kthbits = 0u;
+  int cut = 0;
   if (K > 0) {
     // the K-th largest term by radix select, most significant byte first; negv was written by this workgroup
     if (tid == 0) { s_prefix = 0u; s_need = K; }
@@ -393,6 +396,7 @@ __global__ __launch_bounds__(YL_LOSS_RT) void yl_loss_reduce_kernel(YlLevels lv,
       __syncthreads();
     }
     const unsigned kth = s_prefix;                       // bits of the K-th largest term; s_need copies of it are taken
+    kthbits = kth;
     double sg = 0.0;
     for (int n = tid; n < N; n += YL_LOSS_RT) {
       const unsigned u = __float_as_uint(negv[n]);
@@ -400,6 +404,34 @@ __global__ __launch_bounds__(YL_LOSS_RT) void yl_loss_reduce_kernel(YlLevels lv,
     }
     sg = yl_block_sum(sg, s_wd, tid);
     negmean = (sg + (double)s_need * (double)__uint_as_float(kth)) / (double)K;
+    if (p.sel) {
+      // state for the backward only: which of the entries equal to the K-th term are the s_need selected ones -- the
+      // lowest anchor indices.  One ordered pass: count per chunk of YL_LOSS_RT anchors; inside the chunk where the
+      // running count reaches s_need, a ballot prefix finds the anchor that completes it.
+      const int need = s_need;
+      if (tid == 0) s_cut = N;
+      int run = 0;
+      for (int base = 0; base < N; base += YL_LOSS_RT) {
+        const int n = base + tid;
+        const int eq = (n < N && __float_as_uint(negv[n]) == kth) ? 1 : 0;
+        const unsigned long long bal = __ballot(eq);
+        const int below = __popcll(bal & ((1ull << (tid & 63)) - 1ull));
+        const int cnt = yl_block_isum(eq, s_wi, tid);     // leaves the per-wave counts in s_wi
+        if (run + cnt >= need) {                          // the same for every thread
+          int before = run;
+          for (int w = 0; w < (tid >> 6); ++w) before += s_wi[w];
+          if (eq && before + below + 1 == need) s_cut = n + 1;
+          break;
+        }
+        run += cnt;
+      }
+      __syncthreads();
+      cut = s_cut;
+    }
+  }
+  if (p.sel && tid == 0) {
+    int* sel = p.sel + 4 * b;
+    sel[0] = npos; sel[1] = K; sel[2] = (int)kthbits; sel[3] = cut;
   }
   if (tid == 0) {
     float box = 0.0f, obj, cls = 0.0f;
@@ -427,6 +459,204 @@ __global__ void yl_loss_sum_kernel(YlLossP p) {
   p.out4[3] = (float)((double)np / (double)p.B);
 }
 
+// ---- backward ------------------------------------------------------------------------------------------------
+// d(box + obj + cls)/d(level tensors), closed-form per anchor from the forward's state (assign, sel): see the header
+// for the semantics.  The gradient is as large as the level tensors and all but a few hundred rows per image are
+// zero, so the kernel is a streaming write: a workgroup owns YL_LOSS_GR consecutive rows of one level tensor (a
+// contiguous, 16-byte aligned range of YL_LOSS_GR * E floats) and
+//   1. one thread per row reads assign / sel, decides a negative with the forward's own yl_bce bits, and puts the
+//      row's columns 0-4 into LDS; a positive recomputes decode, IoU and the CIoU derivative from its logits;
+//   2. one wave per positive row reduces the class logits to max + log-sum-exp;
+//   3. all threads write the range once with 16-byte stores: columns 0-4 from LDS, the class columns of positives
+//      from softmax, +0.0 everywhere else.  Nothing is read back, no element has two writers, no atomics.
+// The few non-zero rows are evaluated in float64 from the fp32 logits (quantities of the ground truth alone stay
+// fp32, as the reference's fp32 targets make them in its own float64 run) and rounded once.
+#define YL_LOSS_GR 128        // rows per workgroup of the gradient kernel (64 / 128 / 256 measured: DESIGN 7c')
+#define YL_LOSS_GT 256        // its threads
+
+__device__ __forceinline__ double yl_dsigm(double x) { return 1.0 / (1.0 + exp(-x)); }
+// derivative of max(a, b) with respect to a (of min(b, a) with respect to b): torch splits a tie
+__device__ __forceinline__ double yl_dstep(double a, double b) { return a > b ? 1.0 : (a == b ? 0.5 : 0.0); }
+
+// centre / side of the train-time decode with its derivative by the logit
+__device__ __forceinline__ void yl_grad_ctr(double t, int cm, double a, double s, double& c, double& dc) {
+  const double q = yl_dsigm(t);
+  if (cm == YL_CENTER_V8) { c = (q * 2.0 - 0.5 + a) * s; dc = 2.0 * q * (1.0 - q) * s; }
+  else { c = (q + a) * s; dc = q * (1.0 - q) * s; }
+}
+__device__ __forceinline__ void yl_grad_side(double t, int wm, double s, double& w, double& dw) {
+  if (wm == YL_WH_V8) {
+    const double q = yl_dsigm(t);
+    w = (2.0 * q) * (2.0 * q) * s;
+    dw = 2.0 * (2.0 * q) * 2.0 * q * (1.0 - q) * s;
+  } else if (wm == YL_WH_SOFTPLUS) {
+    w = (t > 20.0 ? t : log1p(exp(t))) * s;
+    dw = (t > 20.0 ? 1.0 : yl_dsigm(t)) * s;
+  } else {
+    w = exp(fmin(fmax(t, -10.0), 8.0)) * s;
+    dw = (t >= -10.0 && t <= 8.0) ? w : 0.0;              // clamp passes the gradient at its boundary, none outside
+  }
+}
+
+// d(1 - CIoU)/d(x1, y1, x2, y2) of bbox_ciou_flat (:130); alpha is a constant (the reference's no_grad)
+__device__ __forceinline__ void yl_ciou_grad(double x1, double y1, double x2, double y2, const YlGt& g, double* gr) {
+  const double eps = 1e-7;
+  const double gx1 = g.x1, gy1 = g.y1, gx2 = g.x2, gy2 = g.y2;
+  const double wr = x2 - x1, hr = y2 - y1;
+  const double pw = fmax(wr, eps), ph = fmax(hr, eps);
+  const double mw = wr >= eps ? 1.0 : 0.0, mh = hr >= eps ? 1.0 : 0.0;
+  const float twf = fmaxf(g.x2 - g.x1, 1e-7f), thf = fmaxf(g.y2 - g.y1, 1e-7f);
+  const double tarea = (double)(twf * thf), tatan = (double)atanf(twf / thf);
+  const double iwr = fmin(x2, gx2) - fmax(x1, gx1), ihr = fmin(y2, gy2) - fmax(y1, gy1);
+  const double iw = fmax(iwr, 0.0), ih = fmax(ihr, 0.0);
+  const double miw = iwr >= 0.0 ? 1.0 : 0.0, mih = ihr >= 0.0 ? 1.0 : 0.0;
+  // derivatives by (x1, y1, x2, y2)
+  const double d_iw[4] = {-miw * yl_dstep(x1, gx1), 0.0, miw * yl_dstep(gx2, x2), 0.0};
+  const double d_ih[4] = {0.0, -mih * yl_dstep(y1, gy1), 0.0, mih * yl_dstep(gy2, y2)};
+  const double d_pw[4] = {-mw, 0.0, mw, 0.0}, d_ph[4] = {0.0, -mh, 0.0, mh};
+  const double inter = iw * ih;
+  const double uni = pw * ph + tarea - inter + eps;
+  const double iou = inter / uni;
+  const double dx = (x1 + x2) * 0.5 - (double)g.cx, dy = (y1 + y2) * 0.5 - (double)g.cy;
+  const double cd = dx * dx + dy * dy;
+  const double d_cd[4] = {dx, dy, dx, dy};
+  const double cw = fmax(x2, gx2) - fmin(x1, gx1), ch = fmax(y2, gy2) - fmin(y1, gy1);
+  const double d_cw[4] = {-yl_dstep(gx1, x1), 0.0, yl_dstep(x2, gx2), 0.0};
+  const double d_ch[4] = {0.0, -yl_dstep(gy1, y1), 0.0, yl_dstep(y2, gy2)};
+  const double c2 = cw * cw + ch * ch + eps;
+  const double k4 = 0.40528473456935108577551785283891;                   // 4 / pi^2
+  const double d = tatan - atan(pw / ph);
+  const double v = k4 * (d * d);
+  const double alpha = v / (v - iou + 1.0 + eps);
+  const double den = pw * pw + ph * ph;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double dinter = d_iw[k] * ih + iw * d_ih[k];
+    const double duni = d_pw[k] * ph + pw * d_ph[k] - dinter;
+    const double diou = (dinter * uni - inter * duni) / (uni * uni);
+    const double dc2 = 2.0 * cw * d_cw[k] + 2.0 * ch * d_ch[k];
+    const double dpen = (d_cd[k] * c2 - cd * dc2) / (c2 * c2);
+    const double dd = (-ph * d_pw[k] + pw * d_ph[k]) / den;              // d(-atan(pw / ph))
+    gr[k] = -(diou - dpen - alpha * (2.0 * k4 * d * dd));
+  }
+}
+
+__global__ __launch_bounds__(YL_LOSS_GT) void yl_loss_grad_kernel(YlLevels lv, YlLossGradP p) {
+  __shared__ float s_g[YL_LOSS_GR][5];        // columns 0-4 of the tile's rows
+  __shared__ int s_label[YL_LOSS_GR];         // class of a positive row's box, -1 for every other row
+  __shared__ double s_lse[YL_LOSS_GR];        // max + log-sum-exp of a positive row's class logits
+  __shared__ double s_scale[YL_LOSS_GR];      // grad_out * lambda_cls / npos of a positive row
+  const int tid = threadIdx.x, E = lv.E, C = lv.C;
+  const yl_loss_cfg& c = p.cfg;
+  // level and tile of this workgroup: tiles are numbered level by level
+  int l = 0, tile = blockIdx.x;
+  for (;;) {
+    const int nt = (int)(((long long)p.B * lv.S[l] * lv.S[l] + YL_LOSS_GR - 1) / YL_LOSS_GR);
+    if (tile < nt || l + 1 >= lv.L) break;
+    tile -= nt; ++l;
+  }
+  const int S = lv.S[l], S2 = S * S;
+  const long long rows = (long long)p.B * S2, row0 = (long long)tile * YL_LOSS_GR;
+  const int nr = (int)(rows - row0 < YL_LOSS_GR ? rows - row0 : YL_LOSS_GR);
+  if (nr <= 0) return;
+  const float* in = lv.ptr[l] + row0 * E;
+  float* out = p.out[l] + row0 * E;
+
+  if (tid < nr) {
+    const long long r = row0 + tid;
+    const int b = (int)(r / S2), cell = (int)(r - (long long)b * S2), n = lv.off[l] + cell;
+    const float* row = in + (size_t)tid * E;
+    const int* sel = p.sel + 4 * b;
+    const int npos = sel[0], K = sel[1], cut = sel[3];
+    const unsigned kth = (unsigned)sel[2];
+    const int t = p.assign[(size_t)b * lv.N + n];
+    const float xo = row[4];                                                // both kinds of row need it: no load waits for `t`
+    const double go = (double)p.gout[0];
+    double g0 = 0.0, g1 = 0.0, g2 = 0.0, g3 = 0.0, g4 = 0.0;
+    int label = -1;
+    if (t < 0) {
+      const unsigned u = __float_as_uint(yl_bce(xo, 0.0f));                 // the bits the forward's radix select saw
+      if (K > 0 && !(u & 0x80000000u) && (u > kth || (u == kth && n < cut)))
+        g4 = go * (double)c.lambda_obj / (double)K * yl_dsigm((double)xo);
+    } else {
+      const YlGt g = yl_gt(p.gt + 4 * (size_t)t);
+      const double s = (double)lv.stride[l];
+      double cx, cy, w, h, dcx, dcy, dw, dh, gr[4];
+      yl_grad_ctr((double)row[0], c.center_mode, (double)(cell % S), s, cx, dcx);
+      yl_grad_ctr((double)row[1], c.center_mode, (double)(cell / S), s, cy, dcy);
+      yl_grad_side((double)row[2], c.wh_mode, s, w, dw);
+      yl_grad_side((double)row[3], c.wh_mode, s, h, dh);
+      const double x1 = cx - 0.5 * w, y1 = cy - 0.5 * h, x2 = cx + 0.5 * w, y2 = cy + 0.5 * h;
+      yl_ciou_grad(x1, y1, x2, y2, g, gr);
+      const double sb = go * (double)c.lambda_box / (double)npos;
+      g0 = sb * (gr[0] + gr[2]) * dcx;
+      g1 = sb * (gr[1] + gr[3]) * dcy;
+      g2 = sb * 0.5 * (gr[2] - gr[0]) * dw;
+      g3 = sb * 0.5 * (gr[3] - gr[1]) * dh;
+      // objectness against the detached clamp(IoU, 0, 1) of bbox_iou_matrix (:107)
+      const double iw = fmax(fmin(x2, (double)g.x2) - fmax(x1, (double)g.x1), 0.0);
+      const double ih = fmax(fmin(y2, (double)g.y2) - fmax(y1, (double)g.y1), 0.0);
+      const double inter = iw * ih;
+      const double a1 = fmax(x2 - x1, 0.0) * fmax(y2 - y1, 0.0);
+      const double tgt = fmin(fmax(inter / (a1 + (double)g.area2 - inter + 1e-7), 0.0), 1.0);
+      g4 = go * (double)c.lambda_obj / (double)npos * (yl_dsigm((double)xo) - tgt);
+      if (C > 1) {
+        label = min(max(p.label[t], 0), C - 1);
+        s_scale[tid] = go * (double)c.lambda_cls / (double)npos;
+      }
+    }
+    // x + 0.0f: a product that came out as -0.0 is stored as +0.0
+    s_g[tid][0] = (float)g0 + 0.0f; s_g[tid][1] = (float)g1 + 0.0f; s_g[tid][2] = (float)g2 + 0.0f;
+    s_g[tid][3] = (float)g3 + 0.0f; s_g[tid][4] = (float)g4 + 0.0f;
+    s_label[tid] = label;
+  }
+  __syncthreads();
+  // max + log-sum-exp of the positive rows' class logits: wave w takes rows w, w + 4, ...
+  for (int r = tid >> 6; r < nr; r += YL_LOSS_GT / 64) {
+    if (s_label[r] < 0) continue;                                           // the same for the whole wave
+    const float* z = in + (size_t)r * E + 5;
+    const int lane = tid & 63;
+    double m = -INFINITY;
+    for (int k = lane; k < C; k += 64) m = fmax(m, (double)z[k]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    double se = 0.0;
+    for (int k = lane; k < C; k += 64) se += exp((double)z[k] - m);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o, 64);         // commutative pairs: the same bits in every lane
+    if (lane == 0) s_lse[r] = m + log(se);
+  }
+  __syncthreads();
+
+  const int total = nr * E;                                                 // floats of this tile
+  const double e = (double)c.cls_smoothing;
+  const double tg_other = e / (double)C, tg_label = (1.0 - e) + e / (double)C;
+  auto value = [&](int r, int col, int idx) -> float {
+    if (col < 5) return s_g[r][col];
+    const int label = s_label[r];
+    if (label < 0 || col >= 5 + C) return 0.0f;
+    const double pr = exp((double)in[idx] - s_lse[r]);
+    return (float)(s_scale[r] * (pr - (col - 5 == label ? tg_label : tg_other))) + 0.0f;
+  };
+  const bool vec = (((uintptr_t)out) & 15u) == 0;                           // the tile's byte offset is a multiple of 256
+  const int nvec = vec ? total >> 2 : 0;
+  for (int i = tid; i < nvec; i += YL_LOSS_GT) {
+    const int idx = 4 * i;
+    int r = idx / E, col = idx - r * E;
+    float q[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      q[j] = value(r, col, idx + j);
+      if (++col == E) { col = 0; ++r; }
+    }
+    *reinterpret_cast<float4*>(out + idx) = make_float4(q[0], q[1], q[2], q[3]);
+  }
+  for (int idx = 4 * nvec + tid; idx < total; idx += YL_LOSS_GT) {          // a last partial tile's tail (or an unaligned base)
+    const int r = idx / E;
+    out[idx] = value(r, idx - r * E, idx);
+  }
+}
+
 }  // namespace
 
 hipError_t yl_launch_loss_af(const YlLevels& lv, const YlLossP& p, hipStream_t st) {
@@ -435,5 +665,13 @@ hipError_t yl_launch_loss_af(const YlLevels& lv, const YlLossP& p, hipStream_t s
   if (p.T > 0) hipLaunchKernelGGL(yl_loss_assign_kernel, dim3(p.T), dim3(256), 0, st, lv, p);
   hipLaunchKernelGGL(yl_loss_reduce_kernel, dim3(p.B), dim3(YL_LOSS_RT), 0, st, lv, p);
   hipLaunchKernelGGL(yl_loss_sum_kernel, dim3(1), dim3(64), 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t yl_launch_loss_af_grad(const YlLevels& lv, const YlLossGradP& p, hipStream_t st) {
+  long long tiles = 0;
+  for (int l = 0; l < lv.L; ++l) tiles += ((long long)p.B * lv.S[l] * lv.S[l] + YL_LOSS_GR - 1) / YL_LOSS_GR;
+  if (tiles <= 0 || tiles > 0x7fffffffll) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(yl_loss_grad_kernel, dim3((unsigned)tiles), dim3(YL_LOSS_GT), 0, st, lv, p);
   return hipGetLastError();
 }

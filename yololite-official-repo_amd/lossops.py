@@ -1,13 +1,15 @@
-"""Validation loss on the device behind the reference's own class surface.
+"""The reference's loss on the device behind its own class surface: validation loss and training criterion.
 
     LossAF(num_classes, img_size, **kwargs)(preds, targets) -> (loss, {"box", "obj", "cls", "pos"})
         <- scripts/loss/loss.py:180-436 (same constructor arguments and defaults, same return)
 
-Forward only: the assignment and the three terms run in yl_loss_af (csrc/yl_loss.hip) on the raw level tensors
-`model(x)` returns; there is no backward pass, and an input that requires grad is refused rather than silently
-detached.  The host's part is the reference's target-format sniffing (_targets_to_xyxy_px: normalised xywh /
-normalised xyxy / pixel xyxy / pixel xywh, told apart by value range) and packing the batch's boxes into one flat
-list.  No CPU fallback: a HIP device is required.
+The assignment and the three terms run in yl_loss_af (csrc/yl_loss.hip) on the raw level tensors `model(x)` returns.
+By default the class is forward only: an input that requires grad is refused rather than silently detached.  With
+`grad=True` such a call goes through torch autograd instead: the forward keeps the assignment and the hard-negative
+selection (yl_loss_af_train), and `loss.backward()` runs yl_loss_af_backward, one kernel that writes the gradient of
+every level tensor (the network's own backward is not part of this package).  The host's part is the reference's
+target-format sniffing (_targets_to_xyxy_px: normalised xywh / normalised xyxy / pixel xyxy / pixel xywh, told apart
+by value range) and packing the batch's boxes into one flat list.  No CPU fallback: a HIP device is required.
 """
 from __future__ import annotations
 
@@ -67,18 +69,43 @@ def pack_targets(targets: Sequence[dict], img_size: int, num_classes: int) -> Tu
     return np.ascontiguousarray(gt), np.ascontiguousarray(lab), np.asarray(off, np.int32)
 
 
+class _LossAFFunction(torch.autograd.Function):
+    """loss = box + obj + cls as a function of the level tensors; targets, cfg and context ride along undifferentiated"""
+
+    @staticmethod
+    def forward(fctx, ctx, cfg, gt, lab, off, *levels):
+        lv = [l.detach() for l in levels]
+        out4, asg, sel = ctx.loss_af_train(lv, gt, lab, off, cfg)
+        fctx.save_for_backward(asg, sel, gt, lab, off, *levels)       # version counters catch an edit in between
+        fctx.yl, fctx.cfg = ctx, cfg
+        fctx.mark_non_differentiable(out4)
+        return (out4[0] + out4[1] + out4[2]).reshape(1), out4
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, grad_loss, _grad_out4):
+        asg, sel, gt, lab, off, *levels = fctx.saved_tensors
+        g = grad_loss.to(dtype=torch.float32).reshape(1).contiguous()
+        grads = fctx.yl.loss_af_backward(levels, gt, lab, off, fctx.cfg, asg, sel, g)
+        return (None, None, None, None, None) + tuple(gr.view(l.shape) for gr, l in zip(grads, levels))
+
+
 class LossAF:
-    """The reference's LossAF, forward only.  `focal`, `gamma` and `alpha` are accepted and ignored, as the reference's
-    forward ignores them.  `ctx`: the HipContext the level tensors came from (tools/evaluate.py passes the one it
-    holds); without it a context with no layers is made from the shapes of the first call's tensors."""
+    """The reference's LossAF.  `grad=False` (default): forward only.  `grad=True`: a call whose level tensors require
+    grad returns a loss with a grad_fn (see the module docstring); every other call behaves as with grad=False.  `focal`,
+    `gamma` and `alpha` are accepted and ignored, as the reference's forward ignores them.  `ctx`: the HipContext the
+    level tensors came from (tools/evaluate.py passes the one it holds); without it a context with no layers is made
+    from the shapes of the first call's tensors."""
 
     def __init__(self, num_classes: int, img_size: int, lambda_box: float = 5.0, lambda_obj: float = 1.0,
                  lambda_cls: float = 0.5, assign_cls_weight: float = 0.5, center_mode: str = "v8",
                  wh_mode: str = "softplus", center_radius_cells: float = 2.0, topk_limit: int = 20, focal: bool = False,
                  gamma: float = 2.0, alpha: float = 0.25, cls_smoothing: float = 0.05, area_cells_min: float = 4.0,
                  area_cells_max: float = 256.0, area_tol: float = 1.25, size_prior_w: float = 0.20,
-                 ar_prior_w: float = 0.10, iou_cost_w: float = 3.0, center_cost_w: float = 0.5, ctx=None):
+                 ar_prior_w: float = 0.10, iou_cost_w: float = 3.0, center_cost_w: float = 0.5, ctx=None,
+                 grad: bool = False):
         self.nc, self.img_size = int(num_classes), int(img_size)
+        self.grad = bool(grad)
         self.topk_limit = int(topk_limit)
         if not 1 <= self.topk_limit <= _lib.YL_LOSS_MAX_TOPK:
             raise _lib.YoloLiteHipError(f"topk_limit must be 1..{_lib.YL_LOSS_MAX_TOPK} (the kernel does not truncate)")
@@ -107,11 +134,11 @@ class LossAF:
                                   [int(p.shape[1]) for p in preds], device=dev or 0, num_masks=E - 5 - self.nc)
         return self.ctx
 
-    def _run(self, preds, targets, per=False, asg=False):
-        preds = list(preds)
-        if any(torch.is_tensor(p) and p.requires_grad for p in preds):
-            raise _lib.YoloLiteHipError("LossAF is forward only (no backward pass): an input requires grad; "
-                                        "call it under torch.no_grad() on detached tensors")
+    def _wants_grad(self, preds):
+        return torch.is_grad_enabled() and any(torch.is_tensor(p) and p.requires_grad for p in preds)
+
+    def _pack(self, preds, targets):
+        """-> context, device tensors gt [T,4] float32, labels [T] int32, offsets [B+1] int32 (one upload per batch)"""
         for t in targets:
             if any(torch.is_tensor(v) and v.requires_grad for v in t.values()):
                 raise _lib.YoloLiteHipError("LossAF is forward only (no backward pass): a target requires grad")
@@ -119,17 +146,39 @@ class LossAF:
             raise ValueError(f"{preds[0].shape[0]} images but {len(targets)} targets")
         ctx = self._context(preds)
         gt, lab, off = pack_targets(targets, self.img_size, self.nc)
-        packed = np.concatenate([gt.reshape(-1).view(np.int32), lab, off])          # one upload per batch
+        packed = np.concatenate([gt.reshape(-1).view(np.int32), lab, off])
         d = torch.from_numpy(packed).to(ctx.device, non_blocking=True)
         T = len(lab)
-        return ctx.loss_af(preds, d[:4 * T].view(torch.float32).view(T, 4), d[4 * T:5 * T], d[5 * T:], self.cfg,
-                           want_per_image=per, want_assign=asg)
+        return ctx, d[:4 * T].view(torch.float32).view(T, 4), d[4 * T:5 * T], d[5 * T:]
+
+    def _run(self, preds, targets, per=False, asg=False):
+        preds = list(preds)
+        if not self.grad and any(torch.is_tensor(p) and p.requires_grad for p in preds):
+            raise _lib.YoloLiteHipError("LossAF is forward only (no backward pass): an input requires grad; "
+                                        "call it under torch.no_grad() on detached tensors")
+        ctx, gt, lab, off = self._pack(preds, targets)
+        return ctx.loss_af([p.detach() for p in preds], gt, lab, off, self.cfg, want_per_image=per, want_assign=asg)
+
+    def _run_grad(self, preds, targets):
+        ctx, gt, lab, off = self._pack(preds, targets)
+        # fp32 arithmetic on contiguous tensors of the context's layout; autograd carries the gradient back through
+        # the cast and the copy, into the input's own dtype and strides
+        lv = []
+        for p, s, a in zip(preds, ctx.level_size, ctx.level_anchors):
+            if tuple(p.shape) not in ((p.shape[0], a, s, s, ctx.E), (p.shape[0], s, s, ctx.E)):
+                raise ValueError(f"level shape {tuple(p.shape)} != {(p.shape[0], a, s, s, ctx.E)}")
+            lv.append(p.float().contiguous())
+        return _LossAFFunction.apply(ctx, self.cfg, gt, lab, off, *lv)
 
     def __call__(self, preds, targets) -> Tuple[torch.Tensor, Dict[str, float]]:
-        out4, _, _ = self._run(preds, targets)
-        h = out4.cpu()
-        return (out4[0] + out4[1] + out4[2]).reshape(1), {"box": float(h[0]), "obj": float(h[1]), "cls": float(h[2]),
-                                                           "pos": float(h[3])}
+        preds = list(preds)
+        if self.grad and self._wants_grad(preds):
+            loss, out4 = self._run_grad(preds, targets)
+        else:
+            out4, _, _ = self._run(preds, targets)
+            loss = (out4[0] + out4[1] + out4[2]).reshape(1)
+        h = out4.detach().cpu()
+        return loss, {"box": float(h[0]), "obj": float(h[1]), "cls": float(h[2]), "pos": float(h[3])}
 
     forward = __call__
 

@@ -260,12 +260,7 @@ class HipContext:
         nothing is synchronised or copied to the host."""
         lv = self._check_levels(levels)
         B = lv[0].shape[0]
-        T = int(gt_xyxy.shape[0])
-        if gt_off.numel() != B + 1 or gt_label.numel() != T:
-            raise ValueError("gt_off must have B+1 entries and gt_label one per box")
-        for t, dt in ((gt_xyxy, torch.float32), (gt_label, torch.int32), (gt_off, torch.int32)):
-            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                raise ValueError("ground-truth tensors must be contiguous float32 / int32 / int32 tensors on the context's device")
+        T = self._check_gt(B, gt_xyxy, gt_label, gt_off)
         out4 = torch.empty((4,), device=self.device, dtype=torch.float32)
         per = torch.empty((B, 3), device=self.device, dtype=torch.float32) if want_per_image else None
         asg = torch.empty((B, self.N), device=self.device, dtype=torch.int32) if want_assign else None
@@ -275,6 +270,52 @@ class HipContext:
                                        asg.data_ptr() if asg is not None else None, out4.data_ptr(),
                                        _stream_ptr(self.device)), self.handle, "yl_loss_af")
         return out4, per, asg
+
+    def _check_gt(self, B, gt_xyxy, gt_label, gt_off):
+        T = int(gt_xyxy.shape[0])
+        if gt_off.numel() != B + 1 or gt_label.numel() != T:
+            raise ValueError("gt_off must have B+1 entries and gt_label one per box")
+        for t, dt in ((gt_xyxy, torch.float32), (gt_label, torch.int32), (gt_off, torch.int32)):
+            if t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError("ground-truth tensors must be contiguous float32 / int32 / int32 tensors on the context's device")
+        return T
+
+    def loss_af_train(self, levels, gt_xyxy: torch.Tensor, gt_label: torch.Tensor, gt_off: torch.Tensor, cfg):
+        """yl_loss_af_train: loss_af that also keeps what the backward needs.  Returns device tensors out4 (the same
+        bits as loss_af's), assign [B,N] int32 and sel [B,4] int32 (npos, K, bits of the K-th largest negative term,
+        tie cut); nothing is synchronised or copied to the host."""
+        lv = self._check_levels(levels)
+        B = lv[0].shape[0]
+        T = self._check_gt(B, gt_xyxy, gt_label, gt_off)
+        out4 = torch.empty((4,), device=self.device, dtype=torch.float32)
+        asg = torch.empty((B, self.N), device=self.device, dtype=torch.int32)
+        sel = torch.empty((B, 4), device=self.device, dtype=torch.int32)
+        _lib.check(self.lib.yl_loss_af_train(self.handle, self._ptr_array(lv), B, gt_xyxy.data_ptr() if T else None,
+                                             gt_label.data_ptr() if T else None, gt_off.data_ptr(), T, C.byref(cfg),
+                                             None, asg.data_ptr(), sel.data_ptr(), out4.data_ptr(),
+                                             _stream_ptr(self.device)), self.handle, "yl_loss_af_train")
+        return out4, asg, sel
+
+    def loss_af_backward(self, levels, gt_xyxy: torch.Tensor, gt_label: torch.Tensor, gt_off: torch.Tensor, cfg,
+                         assign: torch.Tensor, sel: torch.Tensor, grad_out: torch.Tensor):
+        """yl_loss_af_backward: d(box + obj + cls)/d(levels) times grad_out (one float32 on the device, read by the
+        kernel only), from the state loss_af_train returned for the same levels and ground truths.  Returns one new
+        tensor per level, shaped like it; every element is written by the one launch."""
+        lv = self._check_levels(levels)
+        B = lv[0].shape[0]
+        T = self._check_gt(B, gt_xyxy, gt_label, gt_off)
+        for t, shape in ((assign, (B, self.N)), (sel, (B, 4))):
+            if t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError("assign / sel must be the int32 tensors loss_af_train returned")
+        if grad_out.dtype != torch.float32 or grad_out.device != self.device or grad_out.numel() != 1:
+            raise ValueError("grad_out must be one float32 on the context's device")
+        grads = [torch.empty_like(l) for l in lv]
+        _lib.check(self.lib.yl_loss_af_backward(self.handle, self._ptr_array(lv), B, gt_xyxy.data_ptr() if T else None,
+                                                gt_label.data_ptr() if T else None, gt_off.data_ptr(), T,
+                                                C.byref(cfg), assign.data_ptr(), sel.data_ptr(), grad_out.data_ptr(),
+                                                self._ptr_array(grads), _stream_ptr(self.device)),
+                   self.handle, "yl_loss_af_backward")
+        return grads
 
     def prototypes(self, B: int) -> torch.Tensor:
         """mask prototypes of the last forward/predict as [B,NM,PH,PW] (the device tensor is NHWC)."""
