@@ -1,6 +1,8 @@
 #!/bin/bash
 # developer A/B on the GPU box, UNTRACED: bench.py headline (no CPU baseline, no other configs) alternating between the
-# in-tree library and an older one:  tools/run_bench_ab.sh _variants/libyololite_hip_head.so [rounds] [extra bench args]
+# in-tree library and the parent's:  tools/run_bench_ab.sh _variants/libyololite_hip_parent.so [rounds] [extra bench args]
+# (the parent's library: build the parent commit in a `git worktree` -- python yololite-official-repo_amd/csrc/build.py there --
+# and copy its libyololite_hip.so to _variants/, which git ignores)
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OLD=$1; R=${2:-3}; shift 2

@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
-"""Timeline of ONE benchmark step from a rocprofv3 --kernel-trace CSV: per kernel start/end relative to the step start,
-stream/queue, overlap statistics.   python tools/trace_step.py <kernel_trace.csv> [step_index_from_end]"""
+"""Timeline of ONE steady-state benchmark step from a rocprofv3 --kernel-trace CSV of bench.py: per kernel start / end /
+duration in us relative to the step's first kernel and its queue; kernel count, span, start of the next step, sum of the
+kernel durations, busy union and idle time inside the step.
+    python tools/trace_step.py <kernel_trace.csv> [step_index_from_end]
+CAUTION: tracing changes how the two chunk streams overlap (traced: chunk 1's entry kernel starts ~0.6 ms after chunk
+0's; three plan orderings derived from that picture were all slower than the unordered plan when timed WITHOUT the
+tracer, round 3) -- use it for per-kernel durations at the chunk batch size, not for the overlap structure."""
 import csv, sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 back = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 ev = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"], r.get("Queue_Id", "?")) for r in rows]
 ev.sort()
-# steps are delimited by the stem block launches of chunk 0: find stemblock kernels
-stems = [i for i, e in enumerate(ev) if "stemblock" in e[2]]
-nchunk = 2 if len(stems) >= 4 and (ev[stems[1]][0] - ev[stems[0]][0]) < (ev[stems[2]][0] - ev[stems[1]][0]) else 1
-starts = stems[::nchunk]
+# a step = from one entry kernel (stem block / stem) on a queue to the next one on the SAME queue (both queues' kernels)
+ent = [i for i, e in enumerate(ev) if "stem" in e[2]]
+q0 = ev[ent[0]][3]
+starts = [i for i in ent if ev[i][3] == q0]
 i0, i1 = starts[-back - 1], starts[-back]
 seg = ev[i0:i1]
 t0 = seg[0][0]
@@ -18,7 +23,6 @@ print(f"step: {len(seg)} kernels, span {(tend - t0) / 1e3:.1f} us, next step sta
 busy = 0; cur_end = t0; sum_dur = 0
 for s, e, n, q in seg:
     sum_dur += e - s
-    if s > cur_end: busy += 0; gap = s - cur_end
     if e > cur_end:
         busy += e - max(s, cur_end); cur_end = e
 print(f"sum of kernel durations {sum_dur / 1e3:.1f} us, union busy {busy / 1e3:.1f} us, idle inside step {(tend - t0 - busy) / 1e3:.1f} us")

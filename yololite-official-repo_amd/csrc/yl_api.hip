@@ -955,15 +955,6 @@ yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* lev
   r.prod.assign(c->slots.size(), 0);
   const unsigned allowed = allowed_forms(c, evs != nullptr || r.lanes, fuse != nullptr);
   for (size_t i = (size_t)lo; i < r.lend;) {
-#ifdef YL_VARIANT_SKIP_LAYERS
-    // VARIANT BUILDS ONLY (tools/build_variant.sh ... -DYL_VARIANT_SKIP_LAYERS; never in libyololite_hip.so): leave out the
-    // layers YL_SKIP="lo-hi" -- results are WRONG; answers "what would the step be if these launches were free"
-    {
-      static int slo = -2, shi = -2;
-      if (slo == -2) { slo = -1; const char* e = getenv("YL_SKIP"); if (e) sscanf(e, "%d-%d", &slo, &shi); }
-      if ((int)i >= slo && (int)i <= shi) { if (evs) hipEventRecord(evs[i + 1], st); ++i; continue; }
-    }
-#endif
     LaunchStep step;
     for (unsigned forms = allowed;; forms &= ~form_bit(step.form)) {      // a refused form: ask again without it
       step = next_step(c, i, r.lend, forms);

@@ -23,7 +23,7 @@
 // Second compilation with -DYL_BF16=1 (csrc/build.py) produces the bf16-MFMA variant of this translation unit
 // under distinct symbol names; yl_api.hip picks one per context (yl_set_option "mfma_bf16").
 #include "yl_lp.h"
-#if defined(YL_BF16) && YL_BF16
+#if YL_BF16
 #define yl_conv_mfma_kernel YL_LP_NAME(yl_conv_mfma_kernel)
 #define yl_conv_dwh_kernel YL_LP_NAME(yl_conv_dwh_kernel)
 #define yl_uib_kernel YL_LP_NAME(yl_uib_kernel)
@@ -222,9 +222,7 @@ __device__ __forceinline__ void yl_epi_scalar(const YlConvP& p, f32x4 (&acc)[MT]
 // grid.x: persistent over M tiles (4 waves x MT x 16 pixels each), grid.y: chunks of NT n-tiles.
 // LDS: weight chunk [CH][NT][64] float4 (n-tiles beyond the layer's last one are zero-filled so the
 // hot loop needs no tile predicate).
-#ifndef YL_PW_SCHED
-#define YL_PW_SCHED 24         // pin loads-before-MFMAs (A/B: 0 -> 29.33k, 12 -> 29.69k, 24 -> 29.75k img/s) in the 1x1/kxk loop (value = VALU ops in the address group)
-#endif
+constexpr int YL_PW_SCHED = 24; // pin loads-before-MFMAs (A/B: 0 -> 29.33k, 12 -> 29.69k, 24 -> 29.75k img/s) in the 1x1/kxk loop (value = VALU ops in the address group)
 // problem of this block in a level-batched launch (YlConvMulti) and the block's index / count inside it
 #define YL_SELECT_PROBLEM(m)                                                        \
   int yl_k = 0;                                                                     \
@@ -235,9 +233,7 @@ __device__ __forceinline__ void yl_epi_scalar(const YlConvP& p, f32x4 (&acc)[MT]
   const int bx = p.nblk ? (int)blockIdx.x - p.blk0 : (int)blockIdx.x;               \
   const int gx = p.nblk ? p.nblk : (int)gridDim.x;
 
-#ifndef YL_PW_WAVES
-#define YL_PW_WAVES 3
-#endif
+constexpr int YL_PW_WAVES = 3;  // waves per SIMD the register budget is set for
 template <int NT, int MT, int MODE>
 __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3) void yl_conv_mfma_kernel(YlConvMulti mp) {
   YL_SELECT_PROBLEM(mp)
@@ -274,9 +270,6 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
   // residual / upsample-add without activation: the addends initialise the accumulators (loads issued
   // with the first activation fetch instead of after the last MFMA)
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE && !(p.N & 3);
-  // (initialising the accumulators with the bias saves 2 VALU ops per float4, but sums bias + conv instead of
-  //  the reference's conv + shift: on the ill-conditioned golden checkpoint one score moved by 1.2e-4 -> off)
-  const bool bias0 = false;
   if (DWM) {
     const int nw = p.dw_k * p.dw_k * p.Cin;
     yl_glds_floats(p.dw_w, dwl, nw, tid, 256);
@@ -303,10 +296,10 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
     f32x4 acc[MT][NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-      // plain epilogue ahead: start from the bias (the epilogue is then clamp + store only)
-      const f32x4 b0 = bias0 ? yl_ld4(p.bias + (nt0 + nt) * 16 + 4 * kq) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      // from zero, not from the bias: that would save 2 VALU ops per float4 but sums bias + conv instead of the reference's
+      // conv + shift (on the ill-conditioned golden checkpoint one score moved by 1.2e-4)
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = b0;
+      for (int mt = 0; mt < MT; ++mt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     if (pre_add) {
 #pragma unroll
@@ -371,14 +364,12 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
         if (!DWM) {
 #pragma unroll
           for (int mt = 0; mt < MT; ++mt) xq[mt] = xn[mt];
-#if YL_PW_SCHED
           // pin the order: next step's address math + loads FIRST, then the weight reads, then the MFMAs (left
           // alone the scheduler sinks the loads behind most of the MFMAs and waits for them at the end of the step)
           __builtin_amdgcn_sched_group_barrier(0x002, YL_PW_SCHED, 0);
           __builtin_amdgcn_sched_group_barrier(0x020, MT, 0);
           __builtin_amdgcn_sched_group_barrier(0x100, NT, 0);
           __builtin_amdgcn_sched_group_barrier(0x008, YL_MFMA_PER_BLOCK * NT * MT, 0);
-#endif
         }
       }
     }
@@ -423,7 +414,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
     if (p.dec_boxes && !p.dec_raw) continue;
     if (p.N & 3) yl_epi_scalar<NT, MT>(p, acc, px, nt0, kq, lo, hi, stg, ((size_t)tile * 4 + wave) * (MT * 16), lane);
     else if (!pre_add && (p.res || p.up || YL_SMOOTH(p.act))) yl_epi_generic<NT, MT>(p, acc, px, nt0, kq);
-    else yl_epi_fast<NT, MT>(p, acc, px, nt0, kq, lo, hi, !bias0);
+    else yl_epi_fast<NT, MT>(p, acc, px, nt0, kq, lo, hi, true);
   }
 }
 
@@ -437,19 +428,8 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
 //   3. feeds 4 MFMA k-steps per n-tile,
 // so the depthwise input is fetched from L2/HBM once per tile instead of DK*DK times and the hot loop
 // has no bounds logic.  Requires OH % 4 == 0 and OW % 4 == 0 (else the DW3/DW5 global-tap modes run).
-// A/B switches (tools/build_variant.sh; measured on edge_n B=64, profiles/README.md):
-//   YL_DWH_XTILE  software-pipeline the halo staging across tile boundaries      (+0.5 %, within noise: off)
-//   YL_DWH_BUF    raw buffer loads (hardware range check) instead of address select (-3.7 %: off)
-//   YL_DWH_PREADD residual initialises the accumulators                            (-1.7 us per residual layer: on)
-#ifndef YL_DWH_XTILE
-#define YL_DWH_XTILE 0
-#endif
-#ifndef YL_DWH_BUF
-#define YL_DWH_BUF 0
-#endif
-#ifndef YL_DWH_PREADD
-#define YL_DWH_PREADD 1
-#endif
+// Measured and not taken (edge_n B=64, profiles/README.md "Retired instruments"): raw buffer loads with the hardware range
+// check instead of the address select -3.7 %; halo staging software-pipelined across tile boundaries +0.5 %, within noise.
 template <int NT, int DK, int DS>
 __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
   YL_SELECT_PROBLEM(mp)
@@ -496,13 +476,9 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
   const int rbase = ((pl >> 2) * DS) * PITCHF + ((pl & 3) * DS) * 16 + 4 * kq;
 
   // residual add without activation: the addend initialises the accumulators (loads issued at tile start)
-  const bool pre_add = YL_DWH_PREADD && p.res != nullptr && p.up == nullptr && p.act == YL_ACT_NONE;
-  const bool bias0 = false;                                           // see yl_conv_mfma_kernel
-  // The depthwise input is read through a raw buffer descriptor: 32-bit byte offsets, and an offset at or
-  // beyond num_records (image border, channel tail) returns 0 from the hardware range check -- no bounds
-  // selects, no 64-bit address arithmetic in the loop.  The launcher guarantees the tensor is < 2 GiB.
-  const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<yl_act_t*>(p.x), 0, (int)((long)p.B * p.H * p.W * p.Cin * (long)sizeof(yl_act_t)), 0x00020000);
+  const bool pre_add = p.res != nullptr && p.up == nullptr && p.act == YL_ACT_NONE;
+  // The depthwise input is addressed by 32-bit byte offsets (the launcher guarantees the tensor is < 2 GiB); a slot outside
+  // the image or in the channel tail carries OOB and reads the zero buffer instead (address select).
   constexpr unsigned OOB = 0x80000000u;
   unsigned goff[NSLOT];        // byte offsets of the lane's staging slots (channel block 0) for one tile
   auto tile_geom = [&](int tile) {
@@ -525,13 +501,7 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
 #pragma unroll
     for (int j = 0; j < NSLOT; ++j) {
       const unsigned off = cok ? goff[j] + (unsigned)kb * (16u * (unsigned)sizeof(yl_act_t)) : OOB;
-#if YL_DWH_BUF && !(defined(YL_F16S) && YL_F16S)
-      r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrsrc, (int)off, 0, 0));
-#elif YL_DWH_BUF
-      r[j] = __builtin_convertvector(__builtin_bit_cast(yl_h16x4, __builtin_amdgcn_raw_buffer_load_b64(xrsrc, (int)off, 0, 0)), f32x4);
-#else
       r[j] = yl_ld4(off < OOB ? p.x + off / (unsigned)sizeof(yl_act_t) : p.zeros);
-#endif
     }
   };
   auto stage_store = [&](const f32x4 (&r)[NSLOT]) {
@@ -562,14 +532,10 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
     else for (int i = tid; i < p.Cin; i += 256) dwl[nw + i] = 0.0f;
   }
   __syncthreads();
-#if YL_DWH_XTILE
-  if (tile < ntiles) stage_store(stg);
-#endif
   for (; tile < ntiles; tile += wstride) {
     const int b = tile / tiles_img;
     const int trem = tile - b * tiles_img;
     const int tyi = trem / tw, txi = trem - tyi * tw;
-    const int ntile = tile + wstride;
     YlPix px[MT];
     px[0].b = b;
     px[0].oy = 4 * tyi + (pl >> 2);
@@ -580,10 +546,9 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
       const int n = (nt0 + nt) * 16 + 4 * kq;
-      acc[0][nt] = bias0 ? yl_ld4(p.bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
+      acc[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};                       // (not the bias: see yl_conv_mfma_kernel)
       if (pre_add && n < p.N) acc[0][nt] = yl_ld4(p.res + px[0].lin * p.N + n);
     }
-#if !YL_DWH_XTILE
     if (!primed) {
       tile_geom(tile);
       stage_load(0, stg);
@@ -591,17 +556,10 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
     primed = false;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // previous tile's halo reads are complete
     stage_store(stg);
-#endif
     for (int kb = 0; kb < KB; ++kb) {
-      // next (tile, channel block) of the pipeline: loads in flight under this step's taps and MFMAs
-#if YL_DWH_XTILE
-      const bool more = kb + 1 < KB || ntile < ntiles;
-      if (kb + 1 < KB) stage_load(kb + 1, stg);
-      else if (ntile < ntiles) { tile_geom(ntile); stage_load(0, stg); }
-#else
+      // next channel block of the tile: loads in flight under this step's taps and MFMAs
       const bool more = kb + 1 < KB;
       if (more) stage_load(kb + 1, stg);
-#endif
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // halo writes (all lanes) -> tap reads
       const int c = kb * 16 + 4 * kq;
       const int cs = c < p.Cin ? c : p.Cin - 4;
@@ -643,7 +601,7 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
       }
     }
     if (!pre_add && (p.res || p.up || YL_SMOOTH(p.act))) yl_epi_generic<NT, MT>(p, acc, px, nt0, kq);
-    else yl_epi_fast<NT, MT>(p, acc, px, nt0, kq, lo, hi, !bias0);
+    else yl_epi_fast<NT, MT>(p, acc, px, nt0, kq, lo, hi, true);
   }
 }
 

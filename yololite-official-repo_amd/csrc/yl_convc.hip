@@ -25,7 +25,7 @@
 // Limits (launcher falls back to yl_conv_dwh_kernel otherwise): OH, OW multiples of 4, N % 4 == 0,
 // NTW = ceil(ceil(N/16)/4) <= 5 and ceil(Cin/16) <= KBMAX(NTW) (the register budget of the resident weights).
 #include "yl_lp.h"
-#if defined(YL_BF16) && YL_BF16
+#if YL_BF16
 #define yl_conv_dwc_kernel YL_LP_NAME(yl_conv_dwc_kernel)
 #define yl_launch_conv_dwc YL_LP_NAME(yl_launch_conv_dwc)
 #define yl_convc_init YL_LP_NAME(yl_convc_init)
@@ -54,47 +54,9 @@
 #include "yl_internal.h"
 #include "yl_dev.h"
 #include "yl_epi.h"
-#if defined(YL_F16S) && YL_F16S
-#define defined_YL_F16S 1
-#else
-#define defined_YL_F16S 0
-#endif
 
 #define YL_DWC_LDS_MAX (150 * 1024)
 
-// profiling aid (variant builds only: tools/build_variant.sh stamp yl_convc.hip -DYL_DWC_STAMP=<Cin>): shader-clock
-// stamps of the launches whose Cin matches, [block][wave][32], read back by tools/dwc_stamps.py
-#ifdef YL_DWC_STAMP
-__device__ unsigned long long yl_dwc_stamps[1024 * 8 * 32];
-#define DWC_STAMP(i)                                                                                             \
-  do {                                                                                                           \
-    if (p.Cin == YL_DWC_STAMP && lane == 0 && blockIdx.x < 1024 && (i) < 32)                                     \
-      yl_dwc_stamps[((size_t)blockIdx.x * 8 + wave) * 32 + (i)] = __builtin_readcyclecounter();                 \
-  } while (0)
-extern "C" int yl_debug_dwc_stamps(void* host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(yl_dwc_stamps), sizeof(yl_dwc_stamps)) == hipSuccess ? 0 : -1;
-}
-#else
-#define DWC_STAMP(i) do {} while (0)
-#endif
-// the same aid for yl_conv_wino2_kernel / yl_conv_dwl_kernel / yl_ir_kernel (-DYL_WINO_STAMP=<Cin> [-DYL_STAMP_OH=<min grid>];
-// tools/wino_stamps.py, tools/ir_stamps.py): stamps per k-block of the workgroup's second item
-#ifdef YL_WINO_STAMP
-#ifndef YL_STAMP_OH
-#define YL_STAMP_OH 80
-#endif
-__device__ unsigned long long yl_wino_stamps[256 * 8 * 64];
-#define WINO_STAMP(i)                                                                                            \
-  do {                                                                                                           \
-    if (p.Cin == YL_WINO_STAMP && p.OH >= YL_STAMP_OH && lane == 0 && blockIdx.x < 256 && wi == 1 && (i) < 64)     \
-      yl_wino_stamps[((size_t)blockIdx.x * 8 + wave) * 64 + (i)] = __builtin_readcyclecounter();                \
-  } while (0)
-extern "C" int yl_debug_wino_stamps(void* host) {
-  return hipMemcpyFromSymbol(host, HIP_SYMBOL(yl_wino_stamps), sizeof(yl_wino_stamps)) == hipSuccess ? 0 : -1;
-}
-#else
-#define WINO_STAMP(i) do {} while (0)
-#endif
 
 template <int NTW>
 struct YlDwcCfg {
@@ -165,7 +127,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
     nmine = bx < ntiles ? (ntiles - 1 - bx) / gx + 1 : 0;
   }
 
-  DWC_STAMP(0);
   {                                                              // depthwise taps + bias -> LDS (asynchronous)
     const int nw = DK * DK * Cin;
     yl_glds_floats(p.dw_w, dwl, nw, tid, 512);
@@ -235,7 +196,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
     };
     if (step_valid()) { load_half(t0 + st_it * tstride, step_c0()); step_advance(); }
     __syncthreads();                                              // taps are in LDS (drains the copy queue once)
-    DWC_STAMP(1);
     for (int it = 0; it <= nmine; ++it) {
       if (it < nmine) {
         f32x4* bb = bbuf + (size_t)(it & 1) * KB * 64;
@@ -243,12 +203,10 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
           const int g = wave + 4 * gi;
           const int nh = halves_of(g);
           for (int h = 0; h < nh; ++h) {
-            if (it == 2 && gi == 0) DWC_STAMP(20 + 5 * h);
             store_half(hreg);                                       // this step's patch: registers -> LDS (after the
-            if (it == 2 && gi == 0) DWC_STAMP(21 + 5 * h);          // previous step's tap reads, in LDS order)
+                                                                    // previous step's tap reads, in LDS order)
             if (step_valid()) { load_half(t0 + st_it * tstride, step_c0()); step_advance(); }   // next step's patch: in flight under the taps
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // patch writes (all lanes) -> tap reads
-            if (it == 2 && gi == 0) DWC_STAMP(22 + 5 * h);
             const float* hp_ = hreg;
             const int c = g * 64 + h * 32 + c8 * 4;
             const int cs = c < Cin ? c : Cin - 4;
@@ -288,21 +246,18 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
             // B fragment of channel block kb: lane (kq = c8 & 3, pixel py*4 + 2*xh + j).  Blocks beyond KB (group
             // tail) are not stored; channels beyond Cin inside a block were loaded from the zero buffer (load_half) and
             // meet zero 1x1 weights.
-            if (it == 2 && gi == 0) { asm volatile("" :: "v"(o[0].x), "v"(o[1].x)); DWC_STAMP(23 + 5 * h); }
+            if (it == 2 && gi == 0) asm volatile("" :: "v"(o[0].x), "v"(o[1].x));   // (no-op anchor: see the GEMM waves)
             const int kb = 4 * g + 2 * h + (c8 >> 2);
             if (kb < KB) {
 #pragma unroll
               for (int j = 0; j < 2; ++j)
                 bb[kb * 64 + (c8 & 3) * 16 + py * 4 + 2 * xh + j] = yl_actc(o[j], dw_act, dlo, dhi);
             }
-            if (it == 2 && gi == 0) DWC_STAMP(24 + 5 * h);
           }
         }
       }
-      DWC_STAMP(2 + 2 * it);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // B fragments written; the patch copy stays in flight
       __builtin_amdgcn_s_barrier();
-      DWC_STAMP(3 + 2 * it);
     }
   } else {
     // =================================================================================== GEMM waves
@@ -330,7 +285,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
     const bool pre_add = p.res != nullptr && p.up == nullptr && p.act == YL_ACT_NONE;
     const bool generic = !pre_add && (p.res || p.up || YL_SMOOTH(p.act));
     __syncthreads();
-    DWC_STAMP(1);
     for (int it = 0; it <= nmine; ++it) {
       if (it >= 1 && p2) {
         const int tile = t0 + (it - 1) * tstride;
@@ -351,7 +305,9 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
           acc[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
           if (pre_add && n < N) acc[0][nt] = yl_ld4(resp + px[0].lin * N + n);
         }
-        if (it == 3) { asm volatile("" :: "v"(acc[0][0].x)); DWC_STAMP(20); }
+        // (The empty asm statements of this kernel are no-ops left from a retired measurement.  Register allocation differs
+        // without them; they stay until the kernel's code is next allowed to change.)
+        if (it == 3) asm volatile("" :: "v"(acc[0][0].x));
         // B fragments are read PF channel blocks ahead of their MFMAs (one ds_read_b128 each; the depthwise waves
         // keep the LDS pipe busy, so a read issued one block ahead returned too late)
         constexpr int PF = KBMAX < 4 ? KBMAX : 4;
@@ -367,7 +323,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
             yl_mma_step<NTW, 1>(wreg[kb], xq, acc);
           }
         }
-        if (it == 3) { asm volatile("" :: "v"(acc[0][0].x)); DWC_STAMP(21); }
+        if (it == 3) asm volatile("" :: "v"(acc[0][0].x));
         if (generic) yl_epi_generic<NTW, 1>(p, acc, px, nt0, kq);
         else {                                                      // == yl_epi_fast with the bias from registers
           yl_act_t* orow = outp + px[0].lin * N;
@@ -379,10 +335,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
           }
         }
       }
-      DWC_STAMP(2 + 2 * it);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // this tile's B-fragment reads are complete
       __builtin_amdgcn_s_barrier();
-      DWC_STAMP(3 + 2 * it);
     }
   }
 }
@@ -720,7 +674,7 @@ __device__ __forceinline__ void yl_dwt_body(const YlConvMulti& mp, yl_act_t* con
   auto stage_load = [&](int kb, f32x4 (&r)[NSLOT]) {
 #pragma unroll
     for (int j = 0; j < NSLOT; ++j) {
-#if defined_YL_F16S
+#if YL_F16S
       r[j] = __builtin_convertvector(__builtin_bit_cast(yl_h16x4, __builtin_amdgcn_raw_buffer_load_b64(xrs, (int)goff[j], kb * 32, 0)), f32x4);
 #else
       r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)goff[j], kb * 64, 0));
@@ -1587,7 +1541,9 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
   if (tile < tend) load_proj(0, 0);
   __syncthreads();
 
-  for (int wi = 0; tile < tend; tile += tstride, ++wi) {             // (wi: the stamp builds' tile counter)
+  // (wi is never read.  Without this second induction variable the compiler emits the loop differently; it stays until the
+  // kernel's code is next allowed to change.)
+  for (int wi = 0; tile < tend; tile += tstride, ++wi) {
     const int b = tile / tiles_img;
     const int trem = tile - b * tiles_img;
     const int tyi = trem / twn, txi = trem - tyi * twn;
@@ -1650,7 +1606,6 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
 #pragma unroll
         for (int kbi = 0; kbi < KBI; ++kbi) wn[kbi] = w2g[((size_t)kbi * KB + kb + 1) * 64 + lane];
       }
-      WINO_STAMP(kb * 5 + 0);
       // ---- E: expansion slab on the wave's halo m-tiles -> LDS
       const f32x4 eb = yl_ld4(b2l + kb * 16 + 4 * kq);
       float* sb = slab + buf * SLAB;
@@ -1669,9 +1624,7 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
         const f32x4 v = yl_sel4(h_in[j], yl_actc(e[0][0] + eb, act2, elo, ehi));   // zero padding of the EXPANDED tensor
         if (h_ok[j]) *reinterpret_cast<f32x4*>(sb + h_lo[j]) = v;
       }
-      WINO_STAMP(kb * 5 + 1);
       __syncthreads();                 // slab `buf` complete; the projection weights of this slab have landed
-      WINO_STAMP(kb * 5 + 2);
       if (kb + 1 < KB) load_proj(kb + 1, buf ^ 1);
       else if (tile + tstride < tend) load_proj(0, buf ^ 1);        // first slab of the workgroup's next tile
       // ---- D: depthwise on the slab -> B fragments
@@ -1695,7 +1648,6 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
       for (int dy = 0; dy < DK; ++dy) tap_row(dy);                   // one tap row at a time bounds the register footprint
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) xq[mt] = yl_actc(xq[mt], dw_act, dlo, dhi);
-      WINO_STAMP(kb * 5 + 3);
       // channel tail (c >= Cmid): the packed projection weights of those k slots are zero, no select needed.  The slab channels
       // there are computed from the block input with zero expansion weights and bias; that input is masked at C1 and the halo
       // stays inside the tile's image (h_in), so they can only carry this image's own non-finite values, never a neighbour's
@@ -1705,12 +1657,7 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) wq[nt] = wrow[nt * 64];
       yl_mma_step<NT, MT>(wq, xq, acc);
-#ifdef YL_WINO_STAMP
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      WINO_STAMP(kb * 5 + 4);
     }
-    WINO_STAMP(KB * 5);
     if (!pre_add && (p.res || YL_SMOOTH(p.act))) yl_epi_generic<NT, MT>(p, acc, px, 0, kq);
     else yl_epi_fast<NT, MT>(p, acc, px, 0, kq, lo, hi, true);
   }
@@ -1887,7 +1834,7 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
     auto fetch = [&](f32x4 (&dst)[9], int kb) {
 #pragma unroll
       for (int tap = 0; tap < 9; ++tap) {
-#if defined_YL_F16S
+#if YL_F16S
         dst[tap] = __builtin_convertvector(__builtin_bit_cast(yl_h16x4, __builtin_amdgcn_raw_buffer_load_b64(xrs, (int)tp[tap], kb * 32, 0)), f32x4);
 #else
         dst[tap] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)tp[tap], kb * 64, 0));
@@ -1980,7 +1927,7 @@ hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st) {
   // window-in-LDS form (yl_conv_dwl_kernel): stride 1, pad 1, grids that fill the 8 x 8-pixel windows to >= 80 % (20 x 20: 69 %, slower than the tap-load kernel), >= 1.5 items
   // per CU (40 x 40 at B = 32: 0.116 -> 0.098 ms); "dev_select" bit 14 = off, bit 15 = on every grid (the bitwise test)
   // (the fp16-storage unit keeps the tap-load kernel: the windows are raw LDS-DMA copies of the tensor's bytes)
-  if (!(defined_YL_F16S) && !(p.dev & YL_DEV_DWL_OFF) && p.dw_stride == 1 && p.dw_pad_t == 1 && p.dw_pad_l == 1 && !p.scale &&
+  if (!YL_F16S && !(p.dev & YL_DEV_DWL_OFF) && p.dw_stride == 1 && p.dw_pad_t == 1 && p.dw_pad_l == 1 && !p.scale &&
       (size_t)p.B * p.H * p.W * p.Cin < ((size_t)1 << 31)) {
     const long wins = (long)p.B * ((p.OW + 7) >> 3) * ((p.OH + 7) >> 3);
     if (((long)p.B * p.OH * p.OW * 10 >= wins * 64 * 8 && wins >= 3 * YL_NUM_CU) || (p.dev & YL_DEV_DWL_ALL)) {
@@ -2109,7 +2056,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
     return yl_sel4(kb * 16 + 4 * kq < p.Cin, yl_actc(xq, dw_act, dlo, dhi));   // channel tail: zeros (see the window copy)
   };
 
-  for (int item = band0 + slot, wi = 0; item < band1; item += per, ++wi) {   // (wi: the stamp builds' item counter)
+  for (int item = band0 + slot; item < band1; item += per) {
     // the two windows of the item, the lane's output pixel, the lane's copy sources
     YlPix px[1];
     {
@@ -2186,15 +2133,12 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
       // the wave's own copies first: the compiler's wait-count pass does not carry the LDS-DMA requests of the previous
       // iteration across the loop's back edge (the barrier here came out with lgkmcnt(0) only, and two runs of edge_m at
       // B = 32 differed in a few bits)
-      WINO_STAMP(kb * 7 + 0);
       __builtin_amdgcn_s_waitcnt(0x0F70);                         // vmcnt(0)
       __syncthreads();
-      WINO_STAMP(kb * 7 + 1);
       if (MODE == 0) {
         issue_win(kb + 2, PAR);
         issue_wts(kb + 2, wb >= 1 ? wb - 1 : 2);                  // (wb + 2) % 3
       }
-      WINO_STAMP(kb * 7 + 2);
       const float* const tapw = dwl + (kb + 1) * 160 + 4 * kq;
       const f32x4* const win = Rl + (PAR ^ 1) * 2 * RM;
       f32x4 xn = xq[0];
@@ -2227,15 +2171,11 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
         __builtin_amdgcn_sched_barrier(0);                        // (else the fma chain moves up to the group's first MFMA and waits there
         if (MODE < 2 && c < 3) {                                  //  for the reads issued a moment before)
 #pragma unroll
-#if defined(YL_DWL_PK) && !YL_DWL_PK                                 // (A/B builds)
-          for (int t = 0; t < 3; ++t) xn = __builtin_elementwise_fma(tx[t], tw[t], xn);
-#else
           for (int t = 0; t < 3; ++t) xn = yl_pk_fma4(tx[t], tw[t], xn);     // two v_pk_fma_f32 by name: the same fma per component
-#endif
+                                                                             // (pinned packed form: +0.2 %, profiles/r06_pinned_pk_chains_ab.txt)
           if (c == 2) xn = yl_sel4((kb + 1) * 16 + 4 * kq < p.Cin, yl_actc(xn, dw_act, dlo, dhi));
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (c < 4) WINO_STAMP(kb * 7 + 3 + c);
       }
       xq[0] = xn;
       wb = wb1;
@@ -2429,7 +2369,7 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
     auto stage_load = [&](int kb, f32x4 (&r)[NSLOT]) {
 #pragma unroll
       for (int j = 0; j < NSLOT; ++j) {
-#if defined_YL_F16S
+#if YL_F16S
         r[j] = __builtin_convertvector(__builtin_bit_cast(yl_h16x4, __builtin_amdgcn_raw_buffer_load_b64(xrs, (int)goff[j], kb * 32, 0)), f32x4);
 #else
         r[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, (int)goff[j], kb * 64, 0));
@@ -2462,23 +2402,10 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
           for (int dy = 0; dy < DK; ++dy) {                          // one tap row at a time bounds the register footprint
 #pragma unroll
             for (int dx = 0; dx < DK; ++dx) {
-              // (ablation builds, results wrong: -DYL_DWS_ABL=1 one tap-weight read per row, =2 one tap read per row, =3 both, =4 no fma chain)
-#if defined(YL_DWS_ABL) && (YL_DWS_ABL & 1)
-              const f32x4 w = tw[(dy * DK) * 4];
-#else
               const f32x4 w = tw[(dy * DK + dx) * 4];
-#endif
-#if defined(YL_DWS_ABL) && (YL_DWS_ABL & 2)
-              const f32x4 v = *reinterpret_cast<const f32x4*>(halo + rbase + dy * PITCHF);
-#else
               const f32x4 v = *reinterpret_cast<const f32x4*>(halo + rbase + dy * PITCHF + dx * 16);
-#endif
-#if defined(YL_DWS_ABL) && (YL_DWS_ABL & 4)
-              if (dx == 0) { xq[0] += v * w; }
-#else
               xq[0].x = fmaf(v.x, w.x, xq[0].x); xq[0].y = fmaf(v.y, w.y, xq[0].y);
               xq[0].z = fmaf(v.z, w.z, xq[0].z); xq[0].w = fmaf(v.w, w.w, xq[0].w);
-#endif
             }
           }
           // channel tail (c >= Cin): the staged halo holds the next pixel's channels there -- zeros into the MFMA (0 x inf / NaN
@@ -2682,7 +2609,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
       }
     const int vbase = pbase * (int)sizeof(yl_act_t) + borg;       // >= 0: the patch origin seen from the descriptor's base
     auto load_row = [&](int kb, int r, f32x4 (&dst)[16]) {
-      if (!SH && !defined_YL_F16S) {
+      if (!SH && !YL_F16S) {
         const unsigned inbk = kb * 16 + 4 * kq < Cin ? inb : 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -2811,7 +2738,7 @@ static hipError_t wino_go(const YlConvP& p0, hipStream_t st) {
 //           x 3 columns), 3 row combinations X + s Y, 2 column combinations -- 10 packed VALU operations between the MFMAs.
 //           No transformed image in LDS, no second barrier.  (A first version wrote V = B^T d B to LDS with all 512
 //           threads and read it back as B fragments: two barriers per k-block, a 16-read / 8-write LDS round trip per
-//           thread and a 160 KB footprint; tools/wino_stamps.py and the ablation builds priced that round trip at 0.24 ms
+//           thread and a 160 KB footprint; in-kernel cycle stamps and ablation builds priced that round trip at 0.24 ms
 //           of a 1.98 ms launch and the bare MFMA + barrier skeleton at 1.45 ms.)
 //   A       NT 1-KB fragment loads of U_xi straight from L1/L2 per position, requested one position ahead -- U of a
 //           position is used by one wave only, LDS would not share anything
@@ -2914,9 +2841,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
     }
   };
   auto issue_raw = [&](int kb, int buf) {                        // branch-free: it is scheduled between MFMAs
-#if defined(YL_WINO_ABL) && (YL_WINO_ABL & 1)                    // ablation builds (tools/run_wino_abl.sh): results wrong
-    if (kb > 0) return;
-#endif
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
       __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)(Rl + (buf * MT + mt) * RM + wave * 64), 16,
@@ -2940,9 +2864,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
       ubs[nt] = (((ntg >> 1) * KB * 32 + (ntg & 1)) * 64 + 2 * wave * 128) * 16;
     }
     auto load_u = [&](int kb, int ps, f32x4 (&dst)[NT]) {
-#if defined(YL_WINO_ABL) && (YL_WINO_ABL & 2)
-      if (kb > 0) return;
-#endif
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt)
         dst[nt] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(urs, lane16, ubs[nt] + (kb * 16 + ps) * 2048, 0));
@@ -2959,15 +2880,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
       const f32x4* const wb = Rl + (buf * MT + mt) * RM;
       x[0] = wb[sX0]; x[1] = wb[sX1]; x[2] = wb[sX2];
       y[0] = wb[sY0]; y[1] = wb[sY1]; y[2] = wb[sY2];
-    };
-    auto make_b = [&](const f32x4 (&x)[3], const f32x4 (&y)[3], f32x4& b0, f32x4& b1) {
-#if defined(YL_WINO_PK) && !YL_WINO_PK                               // (A/B builds)
-      const f32x4 u0 = y[0] * sr4 + x[0], u1 = y[1] * sr4 + x[1], u2 = y[2] * sr4 + x[2];
-      b0 = u0 - u1;
-      b1 = u2 * sc4 + u1;
-#else
-      yl_wino_b(x, y, sr4, sc4, b0, b1);
-#endif
     };
     auto mma_mt = [&](const f32x4 (&a)[NT], const f32x4& b, f32x4 (&c)[NT]) {    // one m-tile: the 4 steps x NT n-tiles
 #if YL_BF16
@@ -3000,22 +2912,18 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
     auto kblock = [&](int kb, auto par, auto mode) {
       constexpr int PAR = decltype(par)::value;
       constexpr int MODE = decltype(mode)::value;
-      WINO_STAMP(kb * 7 + 0);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) {
         if (mt + 1 < MT) load_win(PAR, mt + 1, x[(mt + 1) & 1], y[(mt + 1) & 1]);
         f32x4 b0, b1;
-        make_b(x[mt & 1], y[mt & 1], b0, b1);
+        yl_wino_b(x[mt & 1], y[mt & 1], sr4, sc4, b0, b1);       // (pinned packed form: +1.1 %, profiles/r06_pinned_pk_chains_ab.txt)
         if (mt == MT - 1 && MODE < 2) {
           __builtin_amdgcn_sched_barrier(0);
-          WINO_STAMP(kb * 7 + 4);
           __builtin_amdgcn_s_waitcnt(0x0070);                     // vmcnt(0) lgkmcnt(0): the wave's own window copies and reads (not left to the
           __syncthreads();                                        // compiler: LDS-DMA requests of the previous iteration are not carried over the back edge)
-          WINO_STAMP(kb * 7 + 5);
           if (MODE == 0) issue_raw(kb + 2, PAR);
           load_win(PAR ^ 1, 0, x[0], y[0]);
           __builtin_amdgcn_sched_barrier(0);
-          WINO_STAMP(kb * 7 + 6);
         }
         mma_mt(ua[PAR][0], b0, acc[0][mt]);
         if (MODE < 2 && mt == 0) load_u(kb + 1, 0, ua[PAR ^ 1][0]);
@@ -3024,7 +2932,6 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
         // m-tile by m-tile: left alone the scheduler gathered all window reads at the top (spills) and pushed the U
         // requests behind the last MFMA
         __builtin_amdgcn_sched_barrier(0);
-        if (mt < 3) WINO_STAMP(kb * 7 + 1 + mt);
       }
     };
     using I0 = std::integral_constant<int, 0>;

@@ -102,12 +102,6 @@ __device__ __forceinline__ f32x4 yl_clamp4(f32x4 v, float lo, float hi) {
 //   YL_F16 (third compilation, -DYL_BF16=1 -DYL_F16=1: everything the reduced-precision build shares, plus): operands rounded to
 //   fp16 (RNE) and multiplied on v_mfma_f32_16x16x16_f16 -- the counterpart of the reference's fp16 autocast in evaluate_model
 //   (scripts/helpers/evaluate.py:399,415).  Selected with yl_set_option("mfma_f16", 1).  Symbols carry _f16 (yl_lp.h).
-#ifndef YL_BF16
-#define YL_BF16 0
-#endif
-#ifndef YL_F16
-#define YL_F16 0
-#endif
 #include "yl_lp.h"
 typedef short yl_s16x4 __attribute__((ext_vector_type(4)));
 // the lane's four consecutive channels packed to the 16-bit operand type of the reduced-precision build (bf16 or fp16, RNE)

@@ -22,12 +22,8 @@
 #include "yl_dev.h"
 #include "yl_epi.h"
 
-#ifndef DPP_NW
-#define DPP_NW 8                       // waves per workgroup
-#endif
-#ifndef DPP_WPE
-#define DPP_WPE 2                      // waves per SIMD the register budget is set for
-#endif
+constexpr int DPP_NW = 8;              // waves per workgroup
+constexpr int DPP_WPE = 2;             // waves per SIMD the register budget is set for
 
 template <int KB /*Cin/16*/, int NT1 /*trunk n-tiles*/, int NT3 /*head-output n-tiles*/>
 __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlConvMulti mp) {
@@ -200,12 +196,7 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlCon
 //            fma chain of those taps -- no LDS round trip is waited for in front of an MFMA.
 // Same tap order, fma chain, k order and epilogue as yl_conv_dpp_kernel: BIT-IDENTICAL to it ("dev_select" bit 16 keeps
 // the tap-load kernel; tests/test_gpu_parity.py).
-#ifndef DPW_NW
-#define DPW_NW 8
-#endif
-#ifndef DPW_ABL
-#define DPW_ABL 0                      // VARIANT BUILDS ONLY (tools/build_variant.sh ... -DDPW_ABL=<bits>; results WRONG, timing only):
-#endif                                 // 1 no decode, 2 no second GEMM, 4 no first-GEMM MFMAs, 8 no window copies, 16 no tap reads / fma, 32 no per-tile setup
+constexpr int DPW_NW = 8;              // waves per workgroup
 template <int KB /*Cin/16*/, int NT1 /*trunk n-tiles*/, int NT3 /*head-output n-tiles*/>
 __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(YlConvMulti mp) {
   int yl_k = 0;
@@ -216,7 +207,7 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
   const int bx = (int)blockIdx.x - p.blk0, gx = p.nblk;
   constexpr int Cin = KB * 16;
   constexpr int NBUF = (KB % 3 == 0) ? 3 : 2;                        // ring of window buffers (KB % NBUF == 0)
-  constexpr int WSL = DPW_NW > 8 ? 144 : 192;                        // float4 slots per buffer: three copies, 144 used (12 waves: the third copy is 16 lanes wide)
+  constexpr int WSL = 192;                                           // float4 slots per buffer: three copies, 144 used
   constexpr int G = NT1 / 2;                                         // MFMA groups of two n-tiles per block
   constexpr int TPG = (9 + G - 1) / G;                               // taps whose reads ride in front of one group
   static_assert(NT1 % 2 == 0 && KB % NBUF == 0 && NBUF + 1 <= KB, "yl_conv_dpw_kernel shape");
@@ -300,10 +291,9 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
     }
   };
   auto request = [&](const Src& src, int kb, int buf) {
-    if (DPW_ABL & 8) return;
 #pragma unroll
     for (int j = 0; j < 3; ++j)
-      if (j < 2 || WSL == 192 || lane < 16) yl_glds16(src.s[j] + kb * 16, winl + buf * WSL + j * 64);
+      yl_glds16(src.s[j] + kb * 16, winl + buf * WSL + j * 64);
   };
 
   Src cs, ns;
@@ -331,7 +321,6 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
   wq[0][1] = w1l[1 * 64 + lane];
   while (tile < r1) {
     const int next = tile + DPW_NW;
-    if (DPW_ABL & 32) { ns = cs; pxn = pxc; pxn.valid = next < r1; } else
     setup(next, ns, pxn);
     f32x4 acc1[1][NT1];
 #pragma unroll
@@ -358,21 +347,20 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
         }
 #pragma unroll
         for (int t = 0; t < TPG; ++t)
-          if (g * TPG + t < 9 && !(DPW_ABL & 16)) {
+          if (g * TPG + t < 9) {
             tx[t] = tap_at(bufn, g * TPG + t);
             tv[t] = *reinterpret_cast<const f32x4*>(tapw + (g * TPG + t) * Cin + kbn * 16);
           }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int st = 0; st < ((DPW_ABL & 4) ? 0 : 4); ++st) {
+        for (int st = 0; st < 4; ++st) {
           acc1[0][2 * g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][0][st], xq[0][st], acc1[0][2 * g], 0, 0, 0);
           acc1[0][2 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][1][st], xq[0][st], acc1[0][2 * g + 1], 0, 0, 0);
         }
-        if (DPW_ABL & 4) { acc1[0][2 * g] += wq[cur][0] * xq[0]; acc1[0][2 * g + 1] += wq[cur][1] * xq[0]; }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < TPG; ++t)
-          if (g * TPG + t < 9 && !(DPW_ABL & 16)) xn = yl_fma4(tx[t], tv[t], xn);
+          if (g * TPG + t < 9) xn = yl_fma4(tx[t], tv[t], xn);
         __builtin_amdgcn_sched_barrier(0);
       }
       xq[0] = yl_clamp4(xn, dlo, dhi);
@@ -404,7 +392,6 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
           wq[cur ^ 1][1] = w1l[1 * 64 + lane];
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (DPW_ABL & 2) { acc3[0][2 * g] += wq[cur][0] * hq[0]; acc3[0][2 * g + 1] += wq[cur][1] * hq[0]; } else
 #pragma unroll
         for (int st = 0; st < 4; ++st) {
           acc3[0][2 * g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][0][st], hq[0][st], acc3[0][2 * g], 0, 0, 0);
@@ -416,11 +403,6 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
     const YlPix pxd[1] = {pxc};
 #pragma unroll
     for (int nt = 0; nt < NT3; ++nt) acc3[0][nt] += *reinterpret_cast<const f32x4*>(b3l + nt * 16 + 4 * kq);
-    if (DPW_ABL & 1) {
-      f32x4 t = acc3[0][0];
-      for (int nt = 1; nt < NT3; ++nt) t += acc3[0][nt];
-      if (kq == 0 && pxd[0].valid) p.dec_scores[(size_t)pxd[0].b * p.dec_N + p.dec_off + pxd[0].oy * p.OW + pxd[0].ox] = t.x + t.y + t.z + t.w;
-    } else
     yl_epi_decode<NT3, 1, true, true>(p, acc3, pxd, 0, kq, lane);
     tile = next;
     cs = ns; pxc = pxn;
@@ -806,7 +788,7 @@ static size_t dpp_lds_bytes(int kb, int nt1, int nt3) {
   return (size_t)(kb * nt1 + nt1 * nt3) * 1024 + (size_t)(10 * kb * 16 + nt1 * 16 + nt3 * 16) * 4;
 }
 static size_t dpw_lds_bytes(int kb, int nt1, int nt3) {   // yl_conv_dpw_kernel: + the waves' window rings
-  return dpp_lds_bytes(kb, nt1, nt3) + (size_t)DPW_NW * ((kb % 3 == 0) ? 3 : 2) * (DPW_NW > 8 ? 144 : 192) * 16;
+  return dpp_lds_bytes(kb, nt1, nt3) + (size_t)DPW_NW * ((kb % 3 == 0) ? 3 : 2) * 192 * 16;
 }
 
 // shapes instantiated: (Cin/16, trunk n-tiles, head-output n-tiles)

@@ -15,13 +15,13 @@ struct YlPix {
 // store 4 consecutive channels / one channel at ELEMENT offset e of the layer's output tensor.  In the fp16-storage unit the
 // tensor is fp16 unless the layer says out_f32 (head outputs -> the fp32 detection levels, the mask prototypes)
 __device__ __forceinline__ void yl_out4(const YlConvP& p, size_t e, f32x4 v) {
-#if defined(YL_F16S) && YL_F16S
+#if YL_F16S
   if (p.out_f32) { yl_st4(reinterpret_cast<float*>(p.out) + e, v); return; }
 #endif
   yl_st4(p.out + e, v);
 }
 __device__ __forceinline__ void yl_out1(const YlConvP& p, size_t e, float v) {
-#if defined(YL_F16S) && YL_F16S
+#if YL_F16S
   if (p.out_f32) { reinterpret_cast<float*>(p.out)[e] = v; return; }
 #endif
   p.out[e] = (yl_act_t)v;

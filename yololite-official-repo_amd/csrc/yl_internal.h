@@ -7,6 +7,7 @@
 #include <type_traits>
 #include <utility>
 #include "../../include/yololite_hip.h"
+#include "yl_lp.h"
 
 // activations that are not a clamp: SiLU runs in the conv kernels' generic epilogue (the fast clamp epilogues refuse it);
 // GELU and ReLU + learnable affine (ABI v5: YL_ACT_POSTPASS) never reach a conv kernel -- the executor launches the layer with
@@ -98,7 +99,7 @@ hipError_t yl_launch_loss_af_grad(const YlLevels& lv, const YlLossGradP& p, hipS
 // (-DYL_BF16=1 -DYL_F16=1 -DYL_F16S=1, option "store_f16", round 6): activation tensors live in HBM as fp16 -- the storage side
 // of the reference's fp16 autocast (scripts/helpers/evaluate.py:399,415).  The struct layout is the same in every unit (these
 // are pointers); the element type only decides pointer arithmetic and the load / store helpers (yl_dev.h: yl_ld4 / yl_st4).
-#if defined(YL_F16S) && YL_F16S
+#if YL_F16S
 typedef _Float16 yl_act_t;
 #else
 typedef float yl_act_t;
@@ -175,7 +176,7 @@ struct YlConvP {
 };
 
 // YlConvP::dev -- developer kernel-selection switches (A/B runs, bitwise kernel-equivalence tests); per context, never
-// process-wide (the launchers used to read getenv switches)
+// process-wide (the launchers used to read environment switches)
 #define YL_DEV_DW_TILE_OFF (1u << 0)   // stand-alone depthwise: yl_dw_kernel instead of yl_dw_tile_kernel
 #define YL_DEV_PWS_OFF (1u << 1)       // wide 1x1 layers: yl_conv_pwt_kernel instead of yl_conv_pws_kernel
 #define YL_DEV_S2C_OFF (1u << 2)       // 3x3 s2 + chained 1x1: yl_conv_mfma_kernel instead of yl_conv_s2c_kernel

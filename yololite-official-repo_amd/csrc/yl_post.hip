@@ -219,24 +219,6 @@ __device__ __forceinline__ float4 yl_shfl4(const float4& v, int src) {
   return r;
 }
 
-#ifdef YL_NMS_STAMP
-// profiling aid (variant builds only, tools/build_variant.sh ... -DYL_NMS_STAMP): wall-clock ticks (100 MHz) at the
-// phase boundaries of block 0
-__device__ unsigned long long yl_nms_stamps[64];     // [workgroup of image 0 (blockIdx.y)][16]
-__device__ unsigned long long yl_nms_tstamps[128];
-__device__ int yl_nms_tcount;
-#define YL_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) yl_nms_stamps[(blockIdx.y & 3) * 16 + (i)] = wall_clock64(); } while (0)
-extern "C" int yl_debug_nms_stamps(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(yl_nms_stamps), sizeof(unsigned long long) * 64);
-}
-extern "C" int yl_debug_nms_tstamps(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(yl_nms_tstamps), sizeof(unsigned long long) * 128);
-}
-#define YL_TSTAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0 && (i) < 128 && yl_nms_tstamps[i] == 0) yl_nms_tstamps[i] = wall_clock64(); } while (0)
-#else
-#define YL_STAMP(i) do {} while (0)
-#define YL_TSTAMP(i) do {} while (0)
-#endif
 // Scalar pass of the in-tile resolution: candidate i (alive mask `am`, ascending = score order) is kept iff
 // none of its suppressors (per-lane mask M, bits < lane only) is kept.  Candidates nobody can suppress
 // (M == 0) are kept unconditionally, so only the "suspects" are walked -- usually a handful.
@@ -291,9 +273,7 @@ __device__ __forceinline__ bool yl_tile_resolve(const float4& bj, float aj, bool
 }
 
 // class segments above YL_NMS_BIG survivors are handled by the whole workgroup (yl_nms_segment_block)
-#ifndef YL_NMS_BIG
 #define YL_NMS_BIG 64
-#endif
 #define YL_NMS_BIGQ 200
 #define YL_NMS_SCRATCH 2560          // bytes of LDS behind the keys: ints [0..3] counters, [8..209] big-class queue,
                                      // byte 1024..2063: 2 x 65 u64 OR scratch of the cooperative pass,
@@ -439,7 +419,6 @@ __device__ __forceinline__ int yl_nms_segment_block(K32Ptr k32, int s, int e, co
   int nk = 0, par = 0;
   for (int cs = s; cs < e && nk < cap; cs += 64, par ^= 1) {
     const int ci = (cs - s) >> 6;
-    YL_TSTAMP(6 * ci);
     u64* s_dead = s_or + par * 65;
     u64* s_M = s_dead + 1;
     const int pos = cs + lane;
@@ -470,9 +449,7 @@ __device__ __forceinline__ int yl_nms_segment_block(K32Ptr k32, int s, int e, co
       const u64 dm = __ballot(valid && !alive);
       if (lane == 0 && dm) atomicOr((unsigned long long*)s_dead, (unsigned long long)dm);
     }
-    YL_TSTAMP(6 * ci + 1);
     __syncthreads();
-    YL_TSTAMP(6 * ci + 2);
     if (wave == 0) {                                        // zero the other parity's scratch for the next chunk
       if (lane == 0) s_or[(par ^ 1) * 65] = 0ull;
       s_or[(par ^ 1) * 65 + 1 + lane] = 0ull;
@@ -508,9 +485,7 @@ __device__ __forceinline__ int yl_nms_segment_block(K32Ptr k32, int s, int e, co
       }
       if (M) atomicOr((unsigned long long*)&s_M[lane], (unsigned long long)M);
     }
-    YL_TSTAMP(6 * ci + 3);
     __syncthreads();
-    YL_TSTAMP(6 * ci + 4);
     // ---- scan (every wave, identical result)
     const u64 kept = yl_tile_scan(am, s_M[lane]);
     {
@@ -520,7 +495,6 @@ __device__ __forceinline__ int yl_nms_segment_block(K32Ptr k32, int s, int e, co
       if (((kept >> lane) & 1ull) && slot < cap && (slot % nwaves) == wave) k32[2 * (s + slot) + 1] = (u32)pos;
     }
     nk += __popcll(kept);
-    YL_TSTAMP(6 * ci + 5);
   }
   __syncthreads();                                          // kept list complete; scratch of the last parity:
   if (wave == 0) {
@@ -563,7 +537,6 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
   u32* k32 = (u32*)keys;
   const int G = p.G > 1 ? p.G : 1, g = G > 1 ? (int)blockIdx.y : 0;     // my class group: owner[c] == g
 
-  YL_STAMP(1);
   if (tid == 0) s_misc[1] = 0;
   for (int c = tid; c < C; c += blockDim.x)
     if (G == 1 || owner[c] == g) { ws_start[c] = -1; ws_end[c] = 0; ws_kept[c] = 0; ws_off[c] = 0; }
@@ -586,7 +559,6 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
   }
   for (int i = nsurv + tid; i < P; i += blockDim.x) keys[i] = ~0ull;
   __syncthreads();
-  YL_STAMP(2);
   if (LDS_KEYS && blockDim.x == 1024 && P >= 1024) {
     u64* lk = (u64*)keys;
     switch (P >> 10) {
@@ -599,7 +571,6 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
   } else {
     yl_bitonic_sort(keys, P, tid, blockDim.x);
   }
-  YL_STAMP(3);
 
   for (int pos = tid; pos < nsurv; pos += blockDim.x) {
     const int c = (int)(keys[pos] >> 52);
@@ -613,7 +584,6 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
     if (SBOX) sbox[pos] = boxes[idx];                      // all gathers in flight at once
   }
   __syncthreads();
-  YL_STAMP(4);
 
   // small classes: one wave per class; large classes (> YL_NMS_BIG survivors) are queued for the cooperative pass
   int* s_big = s_misc + 8;                                    // [0] count, [1..] class ids (YL_NMS_BIGQ entries)
@@ -648,7 +618,6 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
     }
   }
   __syncthreads();
-  YL_STAMP(5);
 
   if (G > 1) {
     // ---- class-group split: publish my classes' kept candidates (per-class start / count are already in cls_ws)
@@ -666,10 +635,6 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
       unsigned char* ow = reinterpret_cast<unsigned char*>(p.done) + (size_t)b * 256;
       for (int c = tid; c < C; c += blockDim.x) ow[c] = owner[c];
     }
-    YL_STAMP(6);
-#ifdef YL_NMS_STAMP
-    if (blockIdx.x == 0 && tid == 0) yl_nms_stamps[(blockIdx.y & 3) * 16 + 7] = (unsigned long long)nsurv;
-#endif
     return;
   }
 
@@ -709,11 +674,7 @@ __device__ __forceinline__ void yl_nms_run(const YlNmsP& p, u64* keys, int P, in
     }
   }
   if (!do_topk) {
-    YL_STAMP(6);
     if (tid == 0) { p.counts[b] = total; }
-#ifdef YL_NMS_STAMP
-    if (blockIdx.x == 0 && tid == 0) { yl_nms_stamps[7] = (unsigned long long)nsurv; yl_nms_stamps[8] = (unsigned long long)total; }
-#endif
     return;
   }
   // -- fallback global top-k (tools/infer.py:377-379): sort kept rows by score desc, take topk
@@ -742,7 +703,6 @@ __global__ __launch_bounds__(1024) void yl_nms_kernel(YlNmsP p) {
   int* s_misc = (int*)(yl_smem_raw + (size_t)p.lds_cap * 8);
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* scores = p.scores + (size_t)b * p.N;
-  YL_STAMP(0);
   if (tid == 0) s_misc[0] = 0;
   __syncthreads();
   const int G = p.G > 1 ? p.G : 1, g = G > 1 ? (int)blockIdx.y : 0;
@@ -980,21 +940,6 @@ __device__ __forceinline__ void yl_mi_zero(unsigned char* g, size_t len, int tid
   if ((size_t)tid < tail) g[head + (body << 4) + tid] = 0;
 }
 
-#ifdef YL_MI_STAMP
-// profiling aid (variant builds only: tools/build_variant.sh mistamp yl_post.hip -DYL_MI_STAMP): 100 MHz wall-clock ticks
-// at the phase boundaries of the first items of ONE box-role and ONE fill-role workgroup
-__device__ unsigned long long yl_mi_stamps[2 * 16 * 12];
-__device__ unsigned long long yl_mi_blk[4096 * 2];        // start / end of every workgroup
-extern "C" int yl_debug_mi_stamps(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(yl_mi_stamps), sizeof(yl_mi_stamps));
-}
-extern "C" int yl_debug_mi_blocks(unsigned long long* host) {
-  return (int)hipMemcpyFromSymbol(host, HIP_SYMBOL(yl_mi_blk), sizeof(yl_mi_blk));
-}
-#define YL_MIS(i) do { if (tid == 0 && role_i == 7 && nit < 16) yl_mi_stamps[((BOXES ? 0 : 1) * 16 + nit) * 12 + (i)] = wall_clock64(); } while (0)
-#else
-#define YL_MIS(i) do { } while (0)
-#endif
 // level tables of yl_masks_image_kernel in LDS: lptr[YL_MAX_LEVELS] (pointers), lnl[YL_MAX_LEVELS], loff[YL_MAX_LEVELS + 1];
 // ONE definition for the kernel's carve-up and the launcher's dynamic-LDS request (a hand-counted
 // "YL_MAX_LEVELS * 12 + 8" was 28 bytes short and pre[B-6..B] lay past the request)
@@ -1023,9 +968,6 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
     for (int l = lv.L + 1; l <= YL_MAX_LEVELS; ++l) loff[l] = 0x7fffffff;
   }
   const int tid = threadIdx.x, lane = tid & 63;
-#ifdef YL_MI_STAMP
-  if (tid == 0 && blockIdx.x < 2048) yl_mi_blk[2 * (blockIdx.x + (BOXES ? 2048 : 0))] = wall_clock64();
-#endif
   const int NM = p.NM, PW = p.PW, PH = p.PH;
   const float kx = (float)PW / (float)p.S, ky = (float)PH / (float)p.S;
   // items of every image -> exclusive prefix in LDS (one wave scans it; B is small).  Walking the images one scalar
@@ -1074,10 +1016,7 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
   constexpr bool boxes = BOXES, fill = !BOXES;
   const long long role_i = blockIdx.x, role_n = gridDim.x;
   {
-  int nit = -1;
   for (long long it = role_i; it < total; it += role_n) {
-    ++nit;
-    YL_MIS(0);
     if (b < 0 || it >= pre[b + 1]) {            // another image: its geometry through the scalar cache
       do { ++b; } while (it >= pre[b + 1]);
       base = pre[b];
@@ -1107,7 +1046,6 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
     const int ylo = (int)fminf(fmaxf(floorf(y1), 0.0f), (float)H), yhi = (int)fminf(fmaxf(floorf(y2), -1.0f), (float)(H - 1));
     const int ya = max(R0, ylo), yb = min(R1 - 1, yhi);
     const bool hit = ya <= yb && xlo <= xhi;
-    YL_MIS(1);
     if (fill) {
       if (!hit) {                                                                // no box pixel in these rows
         yl_mi_zero(md + (size_t)R0 * wrow, (size_t)(R1 - R0) * wrow, tid);
@@ -1116,7 +1054,6 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
         if (yb + 1 < R1) yl_mi_zero(md + (size_t)(yb + 1) * wrow, (size_t)(R1 - 1 - yb) * wrow, tid);
       }
     }
-    YL_MIS(2);
     if (!boxes || !hit) continue;
     if (tid < NM) {           // safe: every earlier read of coef[] is followed by a workgroup barrier
       const int cand = yl_as_const(p.keep_idx)[(size_t)b * p.max_out + d];
@@ -1150,9 +1087,7 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
         unsigned char* g0 = md + (size_t)t0 * wrow + c0;
         const int len = nsegs > 1 ? (c1 - c0 + 1) : (t1 - t0 + 1) * wrow;
         const int mis = (int)((uintptr_t)g0 & 15u);
-        YL_MIS(3);
         __syncthreads();                                  // A: the previous tile has left LDS; coef[] is written
-        YL_MIS(4);
         for (int i = tid; i < ((mis + len + 15) >> 4); i += 256) reinterpret_cast<uint4*>(tile)[i] = make_uint4(0u, 0u, 0u, 0u);
         if (tid < t1 - t0 + 1) {                          // vertical taps of the tile's rows, as pbuf row offsets
           int v0, v1; float lvw;
@@ -1190,9 +1125,7 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
             pbuf[t] = yl_sigmoid(acc);
           }
         }
-        YL_MIS(5);
         __syncthreads();                                  // B: probabilities + zeroed tile visible
-        YL_MIS(6);
         const int nunits = (t1 - t0 + 1) * nw;
         // half-wave h of wave w takes the units 2w + h, 2w + h + 8, ...: (row q, word r) advanced incrementally
         int u = (tid >> 6) * 2 + (lane >> 5);
@@ -1223,9 +1156,7 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
           u += 8; q += dq; r += dr_;
           if (r >= nw) { r -= nw; ++q; }
         }
-        YL_MIS(7);
         __syncthreads();                                  // C: tile complete
-        YL_MIS(8);
         // Only wave 3 stores (and it never issues a vector load): vmcnt counts loads and stores in ONE in-order
         // counter, so a wave that waits for a load also waits for the acknowledgement of its earlier stores.
         if (tid >= 192) {
@@ -1239,15 +1170,11 @@ __global__ __launch_bounds__(256, BOXES ? 5 : 8) void yl_masks_image_kernel(YlLe
           const int tail = len - head - (body << 4);
           if (l < tail) g0[head + (body << 4) + l] = tile[mis + head + (body << 4) + l];
         }
-        YL_MIS(9);
         t0 = t1 + 1;
       }
     }
   }
   }
-#ifdef YL_MI_STAMP
-  if (tid == 0 && blockIdx.x < 2048) yl_mi_blk[2 * (blockIdx.x + (BOXES ? 2048 : 0)) + 1] = wall_clock64();
-#endif
 }
 
 hipError_t yl_launch_masks_image(const YlLevels& lv, int B, const float* proto, int PH, int PW, int NM, int S,

@@ -18,7 +18,7 @@
 // first three conv/BN/ReLU triples behind model_v2.py:94-100,266-272.
 // bf16-MFMA variant: second compilation with -DYL_BF16=1 under distinct symbol names (see yl_dev.h: yl_mma_step)
 #include "yl_lp.h"
-#if defined(YL_BF16) && YL_BF16
+#if YL_BF16
 #define yl_stemblock_kernel YL_LP_NAME(yl_stemblock_kernel)
 #define yl_launch_stemblock YL_LP_NAME(yl_launch_stemblock)
 #define yl_stemblock_init YL_LP_NAME(yl_stemblock_init)
@@ -224,9 +224,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemblock_kernel(YlConvP p) {
       }
     }
   };
-#ifdef SB_STAGGER
-  if (blockIdx.x >= gridDim.x / 2) __builtin_amdgcn_s_sleep(SB_STAGGER);   // de-phase the two co-resident blocks of a CU
-#endif
   decode_strip();
   if (g_valid) {
     gather();
