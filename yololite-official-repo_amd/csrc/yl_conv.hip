@@ -154,8 +154,7 @@ __device__ __forceinline__ f32x4 yl_fetch(const YlConvP& p, const YlPix& px, int
         }
       }
     }
-    const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-    const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+    const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
     s = yl_actc(s, p.dw_act, dlo, dhi);
     return yl_sel4(cin_ok, s);
   }
@@ -234,6 +233,21 @@ constexpr int YL_PW_SCHED = 24; // pin loads-before-MFMAs (A/B: 0 -> 29.33k, 12 
   const int gx = p.nblk ? p.nblk : (int)gridDim.x;
 
 constexpr int YL_PW_WAVES = 3;  // waves per SIMD the register budget is set for
+// dynamic LDS of yl_conv_mfma_kernel, its regions in order and their floats: [CH][NT][64] float4 weight chunk | depthwise
+// prologue: [dw_k*dw_k][Cin] taps, [Cin] bias | N % 4 != 0 (head rows): store staging per wave.  (Region sizes, which the kernel
+// adds up as it walks the regions, not offsets: precomputed offsets hand the optimizer the same sums in another order -- and for
+// the same reason functions of their arguments, not of a struct the kernel would fill from its parameters up front.)
+struct YlMfmaLds {
+  static constexpr size_t LIMIT = 128 * 1024;
+  static constexpr size_t STREAM_CHUNK = 48 * 1024;               // weight chunk of a layer whose whole K does not fit
+  static constexpr __host__ __device__ size_t chunk(int CH, int NT) { return (size_t)CH * NT * 256; }
+  static constexpr __host__ __device__ size_t taps(int dw_k, int Cin) { return yl_taps_floats(dw_k, Cin); }   // (dw_k = 0: none)
+  static constexpr __host__ __device__ size_t staging(int MT, int N) { return (N & 3) ? (size_t)4 * MT * 16 * N : 0; }
+  static constexpr __host__ __device__ size_t bytes(int CH, int NT, int MT, int dw_k, int Cin, int N) {
+    return (chunk(CH, NT) + (dw_k > 0 ? taps(dw_k, Cin) : 0) + staging(MT, N)) * 4;
+  }
+};
+
 template <int NT, int MT, int MODE>
 __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3) void yl_conv_mfma_kernel(YlConvMulti mp) {
   YL_SELECT_PROBLEM(mp)
@@ -247,8 +261,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
   f32x4* wl = reinterpret_cast<f32x4*>(yl_wlds);
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
   const int ohw = p.OH * p.OW;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
 
   auto load_chunk = [&](int c0, int c1) {          // asynchronous (yl_glds16): complete at the next barrier
     for (int t = c0 + wave; t < c1; t += 4) {
@@ -260,13 +273,9 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
     }
   };
   constexpr bool DWM = (MODE == YL_CM_DWPRO || MODE == YL_CM_DW3 || MODE == YL_CM_DW5);
-  // LDS carve: [CH*NT*64 float4 weight chunk][dw taps*Cin + Cin floats][per-wave store staging (N%4 != 0)]
-  float* dwl = yl_wlds + (size_t)CH * NT * 256;
+  float* dwl = yl_wlds + YlMfmaLds::chunk(CH, NT);
   float* stg = nullptr;
-  if (p.N & 3) {
-    const size_t dwf = DWM ? (size_t)(p.dw_k * p.dw_k + 1) * p.Cin : 0;
-    stg = dwl + ((dwf + 3) & ~(size_t)3) + (size_t)wave * (MT * 16 * p.N);
-  }
+  if (p.N & 3) stg = dwl + (DWM ? YlMfmaLds::taps(p.dw_k, p.Cin) : 0) + (size_t)wave * (MT * 16 * p.N);
   // residual / upsample-add without activation: the addends initialise the accumulators (loads issued
   // with the first activation fetch instead of after the last MFMA)
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE && !(p.N & 3);
@@ -283,15 +292,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
     YlPix px[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      size_t lin = ((size_t)tile * 4 + wave) * (MT * 16) + mt * 16 + pl;
-      px[mt].valid = lin < (size_t)p.M;
-      if (!px[mt].valid) lin = (size_t)p.M - 1;
-      px[mt].lin = lin;
-      const int b = (int)(lin / ohw);
-      const int rem = (int)(lin - (size_t)b * ohw);
-      px[mt].b = b;
-      px[mt].oy = rem / p.OW;
-      px[mt].ox = rem - px[mt].oy * p.OW;
+      px[mt] = yl_pix(((size_t)tile * 4 + wave) * (MT * 16) + mt * 16 + pl, p.M, ohw, p.OW);
     }
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -381,8 +382,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
       // re-read at B = 64, one launch).  <= 2 n-tiles out; k-blocks beyond this conv's n-tiles meet zero weights.
       const f32x4* w3g = reinterpret_cast<const f32x4*>(p.w3p);      // [NTtot of this conv][NT3][64] float4
       const int NT3 = (p.C3 + 15) >> 4;
-      const float lo3 = (p.act3 == YL_ACT_RELU || p.act3 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-      const float hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+      const float lo3 = yl_act_lo(p.act3), hi3 = yl_act_hi(p.act3);
       f32x4 a3[MT][2];
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt) { a3[mt][0] = (f32x4){0.f, 0.f, 0.f, 0.f}; a3[mt][1] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
@@ -430,14 +430,27 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 && MODE <= 1) ? YL_PW_WAVES : 3)
 // has no bounds logic.  Requires OH % 4 == 0 and OW % 4 == 0 (else the DW3/DW5 global-tap modes run).
 // Measured and not taken (edge_n B=64, profiles/README.md "Retired instruments"): raw buffer loads with the hardware range
 // check instead of the address select -3.7 %; halo staging software-pipelined across tile boundaries +0.5 %, within noise.
+constexpr __host__ __device__ int yl_dwh_hp(int dk, int ds) { return 3 * ds + dk; }                                  // halo edge in pixels
+constexpr __host__ __device__ int yl_dwh_pitch(int dk, int ds) { return ((yl_dwh_hp(dk, ds) * 16 + 7) / 64) * 64 + 56; }   // see the kernel
+// dynamic LDS of yl_conv_dwh_kernel, its regions in order and their floats (sizes, not offsets: see YlMfmaLds): [KB][NT][64]
+// float4 weights (whole K) | [DK*DK][Cin] taps, [Cin] bias | one halo patch per wave
+struct YlDwhLds {
+  static constexpr size_t LIMIT = 144 * 1024;
+  int NT, dk, ds, KB, Cin;
+  constexpr __host__ __device__ size_t weights() const { return (size_t)KB * NT * 256; }
+  constexpr __host__ __device__ size_t taps() const { return (size_t)(dk * dk + 1) * Cin; }
+  constexpr __host__ __device__ size_t halos() const { return (size_t)4 * yl_dwh_hp(dk, ds) * yl_dwh_pitch(dk, ds); }
+  constexpr __host__ __device__ size_t bytes() const { return (weights() + taps() + halos()) * 4; }
+};
+
 template <int NT, int DK, int DS>
 __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
   YL_SELECT_PROBLEM(mp)
-  constexpr int HP = 3 * DS + DK;                         // halo edge in pixels
+  constexpr int HP = yl_dwh_hp(DK, DS);
   // row pitch in floats, == 56 (mod 64): consecutive patch rows start 32 B "earlier" modulo the 256-B LDS
   // row, which makes the 16 lanes of every ds_read_b128 group (2 tile rows x 4 pixels x 2 channel quads)
   // hit 16 distinct 16-B slots -- conflict-free tap reads for stride 1
-  constexpr int PITCHF = ((HP * 16 + 7) / 64) * 64 + 56;
+  constexpr int PITCHF = yl_dwh_pitch(DK, DS);
   constexpr int HF4 = HP * HP * 4;                        // float4 elements of one halo patch (16 ch)
   constexpr int NSLOT = (HF4 + 63) / 64;                  // staging float4 per lane
   constexpr int MT = 1;
@@ -447,14 +460,13 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
   const int nt0 = blockIdx.y * NT;
   const int ntc = (p.NTtot - nt0) < NT ? (p.NTtot - nt0) : NT;
   const int KB = p.KB;
-  f32x4* wl = reinterpret_cast<f32x4*>(yl_wlds);          // [KB][NT][64] float4 (whole K: checked by the launcher)
-  float* dwl = yl_wlds + (size_t)KB * NT * 256;           // [DK*DK][Cin] taps, [Cin] bias
-  float* halo = dwl + (size_t)(DK * DK + 1) * p.Cin + wave * (HP * PITCHF);
+  const YlDwhLds L = {NT, DK, DS, KB, p.Cin};
+  f32x4* wl = reinterpret_cast<f32x4*>(yl_wlds);          // (whole K: checked by the launcher)
+  float* dwl = yl_wlds + L.weights();
+  float* halo = dwl + L.taps() + wave * (HP * PITCHF);
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
 
 
   const int tw = p.OW >> 2, th = p.OH >> 2;
@@ -615,10 +627,23 @@ __global__ __launch_bounds__(256, 3) void yl_conv_dwh_kernel(YlConvMulti mp) {
 // in exchange for one launch instead of two and no expanded-tensor traffic -- these blocks live at
 // 40x40 / 20x20 where launches are latency-bound, not FLOP-bound.
 // Projection weights: LDS.  Expansion weights: A fragments straight from L2 (prefetched one slab ahead).
+constexpr __host__ __device__ int yl_uib_pitch(int dk) { return ((3 + dk) % 4 == 1 || (3 + dk) % 4 == 3) ? 3 + dk : 3 + dk + 1; }   // halo row pitch in pixels
+// dynamic LDS of yl_uib_kernel, its regions in order and their floats (sizes, not offsets: see YlMfmaLds): [KB][NT][64] float4
+// projection weights | [DK*DK][Cmid] taps, [Cmid] dw bias | [KB*16] expansion bias | one expanded halo slab per wave
+struct YlUibLds {
+  static constexpr size_t LIMIT = YlDwhLds::LIMIT;
+  int NT, dk, KB, Cmid;
+  constexpr __host__ __device__ size_t weights() const { return (size_t)KB * NT * 256; }
+  constexpr __host__ __device__ size_t taps() const { return (size_t)(dk * dk + 1) * Cmid; }
+  constexpr __host__ __device__ size_t bias2() const { return (size_t)KB * 16; }
+  constexpr __host__ __device__ size_t halos() const { return (size_t)4 * (3 + dk) * yl_uib_pitch(dk) * 16; }
+  constexpr __host__ __device__ size_t bytes() const { return (weights() + taps() + bias2() + halos()) * 4; }
+};
+
 template <int NT, int DK, int KBI /*ceil(C1/16)*/>
 __global__ __launch_bounds__(256) void yl_uib_kernel(YlConvP p) {
   constexpr int HP = 3 + DK;                               // halo edge (stride 1)
-  constexpr int PITCH = (HP % 4 == 1 || HP % 4 == 3) ? HP : HP + 1;
+  constexpr int PITCH = yl_uib_pitch(DK);
   constexpr int HM = (HP * HP + 15) / 16;                  // halo m-tiles (3 for 3x3, 4 for 5x5)
   constexpr int MT = 1;
   extern __shared__ __attribute__((aligned(16))) float yl_wlds[];
@@ -626,18 +651,16 @@ __global__ __launch_bounds__(256) void yl_uib_kernel(YlConvP p) {
   const int kq = lane >> 4, pl = lane & 15;
   const int nt0 = 0;
   const int KB = p.KB;                                     // 16-channel slabs of the expanded tensor
-  f32x4* wl = reinterpret_cast<f32x4*>(yl_wlds);           // projection weights [KB][NT][64] float4
-  float* dwl = yl_wlds + (size_t)KB * NT * 256;            // [DK*DK][Cmid] taps, [Cmid] dw bias, [KB*16] expansion bias
-  float* b2l = dwl + (size_t)(DK * DK + 1) * p.Cin;
-  float* halo = b2l + (size_t)KB * 16 + wave * (HP * PITCH * 16);
+  const YlUibLds L = {NT, DK, KB, p.Cin};
+  f32x4* wl = reinterpret_cast<f32x4*>(yl_wlds);
+  float* dwl = yl_wlds + L.weights();
+  float* b2l = dwl + L.taps();
+  float* halo = b2l + L.bias2() + wave * (HP * PITCH * 16);
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
   const f32x4* w2g = reinterpret_cast<const f32x4*>(p.w2p);  // [KBI][KB][64] float4
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float elo = (p.act2 == YL_ACT_RELU || p.act2 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float ehi = (p.act2 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
+  const float elo = yl_act_lo(p.act2), ehi = yl_act_hi(p.act2);
 
   for (int t = wave; t < KB; t += 4) {
 #pragma unroll
@@ -795,8 +818,7 @@ __global__ __launch_bounds__(256) void yl_stem_mfma_kernel(YlConvP p) {
   }
   const int ohw = p.OH * p.OW;
   const size_t plane = (size_t)p.H * p.W;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
   for (int tile = blockIdx.x; tile < p.ntiles; tile += gridDim.x) {
     float xv[MT][KS];
     size_t lins[MT];
@@ -1013,10 +1035,6 @@ __global__ __launch_bounds__(256, 2) void yl_dw_tile_kernel(YlConvP p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-#define YL_CONV_LDS_MAX (128 * 1024)
-
-#define YL_DWH_LDS_MAX (144 * 1024)
-
 // The instantiations of the three kernel families of this unit, each written once; yl_conv_init, the occupancy query
 // and the launch all go through these tables.
 // n-tiles per workgroup of the persistent kernels: NT in {1, 2, 3, 4, 6, 8}, as the first index of their tables
@@ -1049,9 +1067,9 @@ static YlConvKernel yl_uib_kernel_of(int NT, int DK, int KBI) {
 }
 
 hipError_t yl_conv_init() {
-  hipError_t e = yl_set_lds_cap(yl_mfma_kernels, YL_CONV_LDS_MAX);
-  if (e == hipSuccess) e = yl_set_lds_cap(yl_dwh_kernels, YL_DWH_LDS_MAX);
-#define YL_UIB_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(yl_uib_kernel<A, B, C>, YL_DWH_LDS_MAX);
+  hipError_t e = yl_set_lds_cap(yl_mfma_kernels, YlMfmaLds::LIMIT);
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_dwh_kernels, YlDwhLds::LIMIT);
+#define YL_UIB_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(yl_uib_kernel<A, B, C>, YlUibLds::LIMIT);
   YL_UIB_SHAPES(YL_UIB_CAP)
 #undef YL_UIB_CAP
   return e;
@@ -1069,9 +1087,7 @@ static hipError_t yl_uib_go(const YlConvP& p, size_t lds, hipStream_t st, int NT
 }
 
 size_t yl_uib_lds_bytes(int Cmid, int NT, int dk) {
-  const int KB = (Cmid + 15) / 16, HP = 3 + dk;
-  const int PITCH = (HP % 4 == 1 || HP % 4 == 3) ? HP : HP + 1;
-  return (size_t)KB * NT * 1024 + (size_t)(dk * dk + 1) * Cmid * 4 + (size_t)KB * 64 + (size_t)4 * HP * PITCH * 64;
+  return YlUibLds{NT, dk, (Cmid + 15) / 16, Cmid}.bytes();
 }
 
 bool yl_uib_supported(int c1, int cmid, int n, int dk) {
@@ -1080,7 +1096,7 @@ bool yl_uib_supported(int c1, int cmid, int n, int dk) {
   int NT = 0;
   for (int i = 0; i < 6; ++i) if (nts[i] >= ntt) { NT = nts[i]; break; }
   if (!NT || (dk != 3 && dk != 5)) return false;
-  if (yl_uib_lds_bytes(cmid, NT, dk) > YL_DWH_LDS_MAX) return false;
+  if (yl_uib_lds_bytes(cmid, NT, dk) > YlUibLds::LIMIT) return false;
   return yl_uib_kernel_of(NT, dk, kbi) != nullptr;
 }
 
@@ -1248,10 +1264,8 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
     if (ec != hipErrorNotSupported) return ec;
   }
   if (halo) {
-    const int HP = 3 * p.dw_stride + p.dw_k;
-    const int PITCHF = ((HP * 16 + 7) / 64) * 64 + 56;
-    const size_t lds = (size_t)p.KB * NT * 1024 + (size_t)(p.dw_k * p.dw_k + 1) * p.Cin * 4 + (size_t)4 * HP * PITCHF * 4;
-    if (lds <= YL_DWH_LDS_MAX) {
+    const size_t lds = YlDwhLds{NT, p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes();
+    if (lds <= YlDwhLds::LIMIT) {
       const YlMultiKernel kern = yl_dwh_kernels[yl_nt_index(NT)][p.dw_k == 5][p.dw_stride == 2];   // (halo: 3 / 5, 1 / 2)
       long tiles[4], wtotal = 0;
       for (int k = 0; k < n; ++k) {
@@ -1275,15 +1289,14 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
   if (tile_hint == 1 || (tile_hint == 0 && tiles2 * gy < 2 * YL_NUM_CU)) MT = 1;
   if (p.dw_k > 0) MT = 1;           // depthwise prologue: one m-tile per wave (register budget -> occupancy)
   // LDS weight chunk: whole K if it fits, else stream 48 KiB chunks
-  const size_t step_bytes = (size_t)NT * 1024;
-  size_t extra = p.dw_k > 0 ? (((size_t)(p.dw_k * p.dw_k + 1) * p.Cin * sizeof(float) + 15) & ~(size_t)15) : 0;
-  if (p.N & 3) extra += (size_t)4 * MT * 16 * p.N * sizeof(float);     // store staging (head rows)
-  if (extra + step_bytes > YL_CONV_LDS_MAX) return hipErrorInvalidValue;
-  const size_t budget = YL_CONV_LDS_MAX - extra;
+  const size_t step_bytes = YlMfmaLds::chunk(1, NT) * 4;               // one k-step of weights
+  const size_t extra = YlMfmaLds::bytes(0, NT, MT, p.dw_k, p.Cin, p.N);   // taps + store staging (head rows)
+  if (extra + step_bytes > YlMfmaLds::LIMIT) return hipErrorInvalidValue;
+  const size_t budget = YlMfmaLds::LIMIT - extra;
   int CH;
   if ((size_t)p.TK * step_bytes <= budget) CH = p.TK;                  // whole K resident
-  else CH = (int)((budget < 48 * 1024 ? budget : 48 * 1024) / step_bytes);   // stream K in chunks
-  const size_t lds = (size_t)CH * step_bytes + extra;
+  else CH = (int)((budget < YlMfmaLds::STREAM_CHUNK ? budget : YlMfmaLds::STREAM_CHUNK) / step_bytes);   // stream K in chunks
+  const size_t lds = YlMfmaLds::bytes(CH, NT, MT, p.dw_k, p.Cin, p.N);
   const int mode = p.dw_k == 3 ? YL_CM_DW3 : p.dw_k == 5 ? YL_CM_DW5 : p.dw_k > 0 ? YL_CM_DWPRO
                    : ((p.k == 1 && p.stride == 1) ? (p.scale ? YL_CM_PWSC : YL_CM_PW) : YL_CM_KXK);
   long tiles[4], ttotal = 0;

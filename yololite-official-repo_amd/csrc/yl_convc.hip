@@ -55,8 +55,6 @@
 #include "yl_dev.h"
 #include "yl_epi.h"
 
-#define YL_DWC_LDS_MAX (150 * 1024)
-
 
 template <int NTW>
 struct YlDwcCfg {
@@ -74,13 +72,30 @@ struct YlDwcCfg {
 
 // patch row pitch in floats (32 channels per pixel): HP pixels + padding chosen so that the 16 lanes of every
 // ds_read_b128 service group -- (row py, pixel pair xh, channel half) combinations -- hit 16 distinct 16-byte slots
+constexpr __host__ __device__ int yl_dwc_hp(int dk, int ds) { return 3 * ds + dk; }
+constexpr __host__ __device__ int yl_dwc_pitch(int dk, int ds) {
+  const int hp = yl_dwc_hp(dk, ds);
+  return ds == 1 ? hp * 32 + ((hp * 128) % 256 == 128 ? 0 : 32) : hp * 32 + 16;
+}
 template <int DK, int DS>
 struct YlDwcGeo {
-  static constexpr int HP = 3 * DS + DK;
-  static constexpr int PITCH = DS == 1 ? HP * 32 + ((HP * 128) % 256 == 128 ? 0 : 32) : HP * 32 + 16;
+  static constexpr int HP = yl_dwc_hp(DK, DS);
+  static constexpr int PITCH = yl_dwc_pitch(DK, DS);
   static constexpr int HALF_F = HP * PITCH;                    // floats of one half patch (32 channels)
   static constexpr int RI = (HP + 7) / 8;                      // LDS-DMA instructions per patch row (8 pixels x 128 B each)
   static constexpr int NDMA = HP * RI;                         // instructions per half patch
+};
+
+// dynamic LDS of yl_conv_dwc_kernel, its regions in order and their floats: [2][KB][64] float4 B fragments | [DK*DK][Cin] taps,
+// [Cin] bias | one half patch per producer wave that has a 64-channel group to stage (at most 4).  (Region sizes, which the kernel
+// adds up as it walks the regions, not offsets: with the offsets precomputed the kernels came out with another schedule.)
+struct YlDwcLds {
+  static constexpr size_t LIMIT = 150 * 1024;
+  int dk, ds, KB, Cin;
+  constexpr __host__ __device__ size_t bfrag() const { return (size_t)2 * KB * 256; }
+  constexpr __host__ __device__ size_t taps() const { return yl_taps_floats(dk, Cin); }
+  constexpr __host__ __device__ size_t halo() const { return (size_t)((KB + 3) / 4 < 4 ? (KB + 3) / 4 : 4) * yl_dwc_hp(dk, ds) * yl_dwc_pitch(dk, ds); }
+  constexpr __host__ __device__ size_t bytes() const { return (bfrag() + taps() + halo()) * 4; }
 };
 
 template <int DK, int DS, int NTW>
@@ -95,10 +110,10 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
   const bool producer = wave < 4;
   const int KB = p.KB;
   const int NG = (KB + 3) >> 2;                                 // 64-channel groups
-  // LDS carve: [2][KB][64] float4 B fragments | [DK*DK][Cin] taps, [Cin] bias | one half patch per producer wave
+  const YlDwcLds L = {DK, DS, KB, p.Cin};
   f32x4* bbuf = reinterpret_cast<f32x4*>(yl_clds);
-  float* dwl = yl_clds + (size_t)2 * KB * 256;
-  float* halo0 = dwl + (((size_t)(DK * DK + 1) * p.Cin + 3) & ~(size_t)3);
+  float* dwl = yl_clds + L.bfrag();
+  float* halo0 = dwl + L.taps();
   // every parameter the loops need, read ONCE: `p` points into the kernel-argument segment (problem selected at
   // run time), and the compiler re-reads such fields with s_load + s_waitcnt lgkmcnt(0) wherever it runs short of
   // SGPRs -- inside the tap / copy loops that was most of their time
@@ -115,6 +130,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
   // XCD x owns the contiguous band [x*U/8, (x+1)*U/8) of the U = B * th tile rows -- whole images for B % 8 == 0, the
   // SAME images in every layer, so the halo overlap of neighbouring tiles and the producer layer's output are found
   // in this XCD's L2 instead of crossing the fabric from another XCD's.
+  // (Neither yl_band_split nor yl_xcd_range: the bands are cut between tile ROWS, U of them, and dealt tile by tile.)
   int t0, tstride, nmine;
   if ((gx & 7) == 0 && ((int)blockIdx.x & 7) == (bx & 7)) {
     const int U = p.B * th, x = bx & 7, j = bx >> 3, nj = gx >> 3;
@@ -140,8 +156,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
     // patch reads + DK tap reads per tap row.  Steps of a tile: (group g = wave, wave + 4, ...) x (half 0, 1).
     const int py = lane >> 4, xh = (lane >> 3) & 1, c8 = lane & 7;
     float* hreg = halo0 + wave * G::HALF_F;
-    const float dlo = (dw_act == YL_ACT_RELU || dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-    const float dhi = (dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+    const float dlo = yl_act_lo(dw_act), dhi = yl_act_hi(dw_act);
     // half patch (32 channels from c0) of a tile: HP rows x RI float4 per lane (lane = (pixel column lane >> 3 [+ 8q],
     // 4 channels)), fetched into registers one step ahead and written to the wave's LDS patch right before its taps.
     // (Asynchronous global->LDS copies were measured first: ~150-230 issue cycles per 1-KiB piece on the issuing wave,
@@ -267,8 +282,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwc_kernel(YlConvMulti mp) {
     const bool p2 = nt0 < NTtot;                                   // this wave owns output channels
     const yl_act_t* const resp = p.res;
     yl_act_t* const outp = p.out;
-    const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-    const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+    const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
     f32x4 wreg[KBMAX][NTW], breg[NTW];
     {
       const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
@@ -373,6 +387,8 @@ __global__ __launch_bounds__(256) void yl_conv_pwt_kernel(YlConvMulti mp, int nc
   const float* srow[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
+    // yl_pix written out: ohw is formed only where coordinates are wanted, and the kernels come out with another schedule
+    // when the helper takes it as an argument
     size_t lin = (size_t)mg * (MT * 16) + mt * 16 + pl;
     px[mt].valid = lin < (size_t)M;
     if (!px[mt].valid) lin = (size_t)M - 1;
@@ -441,8 +457,7 @@ __global__ __launch_bounds__(256) void yl_conv_pwt_kernel(YlConvMulti mp, int nc
     for (int u = 0; u < UK; ++u)
       if (kb0 + u < KB) yl_mma_step<NTW, MT>(a[u], bq[u], acc);
   }
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
   if (DEC) { yl_epi_decode<NTW, MT, false, true>(p, acc, px, 0, kq, lane); return; }   // (nchunk == 1: nt0 == 0)
     // head output under yl_predict (one wave = whole rows)
   if (!pre_add && (p.res || p.up || YL_SMOOTH(p.act))) yl_epi_generic<NTW, MT>(p, acc, px, nt0, kq);
@@ -550,8 +565,7 @@ __device__ __forceinline__ void yl_dwx_tail(const YlConvP& p, const f32x4 (&acc)
     hq[nt][0] = yl_clamp4(acc[nt] + yl_ld4(p.bias + n), lo, hi);
     yl_out4(p, orow + n, hq[nt][0]);
   }
-  const float lo3 = (p.act3 == YL_ACT_RELU || p.act3 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo3 = yl_act_lo(p.act3), hi3 = yl_act_hi(p.act3);
   const int ob = (int)lin * (NX * 64) + kq * 16;                    // byte offset of the lane's first expanded quad
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -593,11 +607,28 @@ __device__ __forceinline__ void yl_dwx_tail(const YlConvP& p, const f32x4 (&acc)
 //        the usual epilogue.  Chosen by the LAYER SHAPE only (never by the batch): results stay batch-invariant and
 //        bitwise repeatable, but are another fp32 summation order of the same products than SK = 1 / yl_conv_dwh_kernel.
 //   NX   (yl_conv_dwx_kernel, fp32 unit only) n-tiles of the NEXT layer's plain 1x1, chained behind the epilogue: see there.
+// halo patch of a 4 x 4 MT-pixel tile: rows, columns, row pitch in floats (see yl_conv_dwh_kernel)
+constexpr __host__ __device__ int yl_dwt_hpy(int dk, int ds) { return 3 * ds + dk; }
+constexpr __host__ __device__ int yl_dwt_hpx(int dk, int ds, int mt) { return (4 * mt - 1) * ds + dk; }
+constexpr __host__ __device__ int yl_dwt_pitch(int dk, int ds, int mt) { return ((yl_dwt_hpx(dk, ds, mt) * 16 + 7) / 64) * 64 + 56; }
+// dynamic LDS of yl_dwt_body (yl_conv_dwt_kernel, yl_conv_dwx_kernel), its regions in order and their floats: WL: [KB][NTtot][64]
+// float4 1x1 weights | [DK*DK][Cin] taps, [Cin] bias | one halo patch per wave | SK > 1: [2][4][NT][64] float4 partial accumulators
+// (region sizes, not offsets: see YlDwcLds)
+struct YlDwtLds {
+  static constexpr size_t LIMIT = 96 * 1024;
+  int dk, ds, mt, sk, nt, KB, Cin;
+  int NTl;                                                           // n-tiles of the weight image in LDS: NTtot (WL) or 0
+  constexpr __host__ __device__ size_t weights() const { return (size_t)(KB * NTl) * 256; }
+  constexpr __host__ __device__ size_t taps() const { return yl_taps_floats(dk, Cin); }
+  constexpr __host__ __device__ int halos() const { return 4 * (yl_dwt_hpy(dk, ds) * yl_dwt_pitch(dk, ds, mt)); }
+  constexpr __host__ __device__ size_t partials() const { return sk > 1 ? (size_t)2 * 4 * nt * 256 : 0; }
+  constexpr __host__ __device__ size_t bytes() const { return (weights() + taps() + halos() + partials()) * 4; }
+};
+
 template <int NT, int DK, int DS, int MT, bool WL, int SK, int NX>
 __device__ __forceinline__ void yl_dwt_body(const YlConvMulti& mp, yl_act_t* const out3) {
   YL_SELECT_PROBLEM_C(mp)
-  constexpr int HPY = 3 * DS + DK, HPX = (4 * MT - 1) * DS + DK;     // halo patch rows / columns
-  constexpr int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;            // row pitch in floats (see yl_conv_dwh_kernel)
+  constexpr int HPY = yl_dwt_hpy(DK, DS), HPX = yl_dwt_hpx(DK, DS, MT), PITCHF = yl_dwt_pitch(DK, DS, MT);
   constexpr int HF4 = HPY * HPX * 4;
   constexpr int NSLOT = (HF4 + 63) / 64;
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
@@ -613,10 +644,11 @@ __device__ __forceinline__ void yl_dwt_body(const YlConvMulti& mp, yl_act_t* con
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(p.x), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   constexpr unsigned OOB = 0x80000000u;
-  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);                     // WL: [KB][NTtot][64] float4
-  float* dwl = yl_clds + (WL ? (size_t)KB * NTtot * 256 : 0);        // [DK*DK][Cin] taps, [Cin] bias
-  float* halo = dwl + (((size_t)(DK * DK + 1) * Cin + 3) & ~(size_t)3) + wave * (HPY * PITCHF);
-  f32x4* red = reinterpret_cast<f32x4*>(dwl + (((size_t)(DK * DK + 1) * Cin + 3) & ~(size_t)3) + 4 * (HPY * PITCHF));   // SK: [2][4][NT][64]
+  const YlDwtLds L = {DK, DS, MT, SK, NT, KB, Cin, WL ? NTtot : 0};
+  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);
+  float* dwl = yl_clds + L.weights();
+  float* halo = dwl + L.taps() + wave * (HPY * PITCHF);
+  f32x4* red = reinterpret_cast<f32x4*>(dwl + L.taps() + L.halos());
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
   const int twn = OW / (4 * MT), thn = OH >> 2;
   const int tiles_img = twn * thn;
@@ -626,6 +658,8 @@ __device__ __forceinline__ void yl_dwt_body(const YlConvMulti& mp, yl_act_t* con
   int tile, tend, wstride;
   constexpr int WPT = SK > 1 ? 1 : 4;                                // tiles a workgroup works on at a time
   if ((gx & 7) == 0) {
+    // yl_band_split's bands, written out: its slots are dealt WPT tiles and a wave at a time here, not item by item, next to
+    // a branch for grids without bands -- through the helper the kernels came out with another control flow
     const int tpx = (ntiles + 7) >> 3;
     const int band0 = (bx & 7) * tpx;
     tend = (band0 + tpx) < ntiles ? (band0 + tpx) : ntiles;
@@ -703,10 +737,8 @@ __device__ __forceinline__ void yl_dwt_body(const YlConvMulti& mp, yl_act_t* con
     else for (int i = tid; i < Cin; i += 256) dwl[nw + i] = 0.0f;
   }
   __syncthreads();                                                   // the only workgroup barrier
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const int dw_act = p.dw_act;
   const bool pre_add = p.res != nullptr && p.up == nullptr && p.act == YL_ACT_NONE;
   const int rbase = ((pl >> 2) * DS) * PITCHF + ((pl & 3) * DS) * 16 + 4 * kq;
@@ -858,31 +890,14 @@ static const YlMultiKernel dwt_splitk_kernels[2][2] = {
 static hipError_t dwt_go(YlConvMulti& m, hipStream_t st, YlMultiKernel kern, int NT, bool WL, int SK) {
   constexpr int MT = 1;
   const YlConvP& p = m.p[0];
-  const int DK = p.dw_k, DS = p.dw_stride;
-  const int HPY = 3 * DS + DK, HPX = (4 * MT - 1) * DS + DK;
-  const int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
-  const size_t lds = ((WL ? (size_t)p.KB * p.NTtot * 256 : 0) + (((size_t)(DK * DK + 1) * p.Cin + 3) & ~(size_t)3) +
-                      (size_t)4 * HPY * PITCHF + (SK > 1 ? (size_t)2 * 4 * NT * 256 : 0)) * 4;
-  if (lds > 96 * 1024) return hipErrorNotSupported;
+  const size_t lds = YlDwtLds{p.dw_k, p.dw_stride, MT, SK, NT, p.KB, p.Cin, WL ? p.NTtot : 0}.bytes();
+  if (lds > YlDwtLds::LIMIT) return hipErrorNotSupported;
   const int res = yl_resident_blocks((const void*)kern, 256, lds, 8);
-  long tiles[4], total = 0;
-  for (int k = 0; k < m.n; ++k) {
+  long tiles[4];
+  for (int k = 0; k < m.n; ++k)
     tiles[k] = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW / (4 * MT)) * (SK > 1 ? 4 : 1);     // SK: a workgroup per tile
-    total += tiles[k];
-  }
-  // persistent workgroups: the co-resident count shared between the problems in proportion to their tiles, each
-  // share a multiple of 8 (XCD bands) and at most one wave per tile
-  int at = 0;
-  for (int k = 0; k < m.n; ++k) {
-    long g = ((long)res * tiles[k] / total + 7) & ~7L;
-    const long cap = ((tiles[k] + 3) / 4 + 7) & ~7L;
-    if (g > cap) g = cap;
-    if (g < 8) g = 8;
-    m.p[k].blk0 = at;
-    m.p[k].nblk = (int)g;
-    at += (int)g;
-  }
-  if (m.n == 1) m.p[0].nblk = 0;
+  // persistent workgroups: at most one wave per tile (four per workgroup)
+  const int at = yl_multi_shares(m, tiles, res, 4);
   hipLaunchKernelGGL(kern, dim3((unsigned)at), dim3(256), lds, st, m);
   return hipGetLastError();
 }
@@ -942,19 +957,12 @@ static YlDwxKernel dwx_kernel_of(int dk, int nx) {
 }
 
 static hipError_t dwx_go(YlConvMulti& m, float* out3, hipStream_t st, YlDwxKernel kern) {
-  const int DK = m.p[0].dw_k;
-  const int HPY = 3 + DK, HPX = 3 + DK;
-  const int PITCHF = ((HPX * 16 + 7) / 64) * 64 + 56;
-  YlConvP& p = m.p[0];
-  const size_t lds = ((((size_t)(DK * DK + 1) * p.Cin + 3) & ~(size_t)3) + (size_t)4 * HPY * PITCHF) * 4;
+  const YlConvP& p = m.p[0];
+  const size_t lds = YlDwtLds{p.dw_k, 1, 1, 1, 4, p.KB, p.Cin, 0}.bytes();   // the body's <4, DK, 1, 1, false, 1>
   const int res = yl_resident_blocks((const void*)kern, 256, lds, 8);
   // persistent workgroups as dwt_go: a multiple of 8 (XCD bands), at most one wave per tile
   const long tiles = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
-  long g = ((long)res + 7) & ~7L;
-  const long cap = ((tiles + 3) / 4 + 7) & ~7L;
-  if (g > cap) g = cap;
-  if (g < 8) g = 8;
-  p.blk0 = 0; p.nblk = 0;
+  const int g = yl_multi_shares(m, &tiles, res, 4);
   hipLaunchKernelGGL(kern, dim3((unsigned)g), dim3(256), lds, st, m, out3);
   return hipGetLastError();
 }
@@ -994,6 +1002,14 @@ hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st) {
 // buffers, the asynchronous global->LDS copies of chunk c+1 issued before the MFMAs of chunk c (ONE barrier per
 // chunk, which is also where the copies are waited for), the chunk pipeline running on across tile boundaries.
 // Same transposed GEMM, k order and epilogues as yl_conv_mfma_kernel: bit-identical results.
+// dynamic LDS of yl_conv_kxk_kernel: two buffers of one weight chunk = 3 taps x NT pieces of 1 KiB.  Layers whose whole weight
+// image fits LIMIT are not this kernel's (yl_launch_conv_kxk)
+struct YlKxkLds {
+  static constexpr size_t LIMIT = 96 * 1024;
+  static constexpr __host__ __device__ size_t bytes(int NT) { return (size_t)2 * 3 * NT * 1024; }   // [2][3][NT][64] float4 at 0
+  static constexpr size_t image_bytes(int TK, int NT) { return (size_t)TK * NT * 1024; }   // the resident form (yl_conv_mfma_kernel)
+};
+
 template <int NT, int MT, int NW>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_kxk_kernel(YlConvP p) {
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
@@ -1015,13 +1031,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_kxk_kernel(Y
   // coming from HBM/MALL again (20x the algorithmic bytes).  The m-tiles of an XCD (workgroup b -> XCD b % 8) are
   // one contiguous band of the output, so the 3x3 halo rows of neighbouring tiles hit the same L2 as well.
   const int bx = blockIdx.x, gx = gridDim.x;                 // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
-  const int bt = band1 > band0 ? band1 - band0 : 0;          // (n-group, m-tile) items of the band, group-major;
-  const int nitems = bt * G;                                 // workgroup `slot` of the XCD takes items slot, slot+per, ...
-  const int nmine = slot < nitems ? (nitems - 1 - slot) / per + 1 : 0;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles, G);   // XCD bands, strided items
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, bt = ws.bt, nmine = ws.nmine;
   const long total_chunks = (long)nmine * NC;
 
   // asynchronous copy of one chunk = the three taps (ky = cc, kx = 0..2) of channel block kb, n-group g, into buffer
@@ -1038,8 +1049,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_kxk_kernel(Y
   long gchunk = 0;                                            // chunks consumed so far (buffer = gchunk & 1)
   __syncthreads();
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
 
   for (int wi = 0; wi < nmine; ++wi) {
     const int item = slot + wi * per;
@@ -1049,15 +1059,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_kxk_kernel(Y
     YlPix px[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) {
-      size_t lin = ((size_t)tile * NW + wave) * (MT * 16) + mt * 16 + pl;
-      px[mt].valid = lin < (size_t)M;
-      if (!px[mt].valid) lin = (size_t)M - 1;
-      px[mt].lin = lin;
-      const int b = (int)(lin / ohw);
-      const int rem = (int)(lin - (size_t)b * ohw);
-      px[mt].b = b;
-      px[mt].oy = rem / OW;
-      px[mt].ox = rem - px[mt].oy * OW;
+      px[mt] = yl_pix(((size_t)tile * NW + wave) * (MT * 16) + mt * 16 + pl, M, ohw, OW);
     }
     f32x4 acc[MT][NT];
 #pragma unroll
@@ -1162,9 +1164,8 @@ static hipError_t kxk_go(const YlConvP& p0, int NT, int MT, int NW, int gy, hipS
   if (!kern) return hipErrorNotSupported;
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW * MT - 1) / (16 * NW * MT));
-  const size_t lds = (size_t)2 * 3 * NT * 1024;
-  int gx = yl_resident_blocks((const void*)kern, NW * 64, lds, 4) & ~7;
-  while (gx > 8 && gx - 8 >= p.ntiles * gy) gx -= 8;       // gy = n-groups: (m-tile, n-group) items
+  const size_t lds = YlKxkLds::bytes(NT);
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)kern, NW * 64, lds, 4), (long)p.ntiles * gy);   // gy = n-groups: (m-tile, n-group) items
   hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
 }
@@ -1178,11 +1179,11 @@ hipError_t yl_launch_conv_kxk(const YlConvP& p, hipStream_t st) {
   const int NWsel = nwtab[YL_DEV_KXK_NW(p.dev)];
   const int MTsel = (p.dev & YL_DEV_KXK_MT2) ? 2 : 1;
   if (p.NTtot == 4) {
-    if ((size_t)p.TK * 4 * 1024 <= 96 * 1024 || NWsel < 0) return hipErrorNotSupported;
+    if (YlKxkLds::image_bytes(p.TK, 4) <= YlKxkLds::LIMIT || NWsel < 0) return hipErrorNotSupported;
     return NWsel == 8 ? kxk_go(p, 4, 1, 8, 1, st) : kxk_go(p, 4, 2, 4, 1, st);
   }
   if (p.NTtot % 7 != 0) return hipErrorNotSupported;
-  if ((size_t)p.TK * 7 * 1024 <= 96 * 1024) return hipErrorNotSupported;      // small enough to stay resident: other kernel
+  if (YlKxkLds::image_bytes(p.TK, 7) <= YlKxkLds::LIMIT) return hipErrorNotSupported;      // small enough to stay resident: other kernel
   // 8 waves per workgroup share each weight chunk (half the LDS-DMA issue work per MFMA: 107 -> 114 TFLOP/s on
   // yololite_m's 80x80 level) when there are enough 128-pixel items to keep the tail short; 4 otherwise
   const int gy = p.NTtot / 7;
@@ -1208,9 +1209,16 @@ hipError_t yl_launch_conv_kxk(const YlConvP& p, hipStream_t st) {
 // NT2 > 0 (with DEC): NT2 more n-tiles from a SECOND weight image (YlConvP::w3p / b3 / C3: the mask coefficients of a segmentation
 // head, model_v2.py head output split into 5 + C detection columns and NM coefficient columns) ride in the same launch -- the wave's
 // rows are read once instead of once per part; the extra columns are stored plain into the level rows (p.out, p.ldo).
+// dynamic LDS of yl_conv_pws_kernel: two buffers of one weight chunk = CH k-steps x NTA pieces of 1 KiB, [2][CH][NTA][64] float4 at 0
+struct YlPwsLds {
+  static constexpr size_t LIMIT = 64 * 1024;
+  static constexpr int CH = 2;                               // k-steps per weight chunk
+  static constexpr __host__ __device__ size_t bytes(int NTA) { return (size_t)2 * CH * NTA * 1024; }
+};
+
 template <int NT, int NW, bool SC = false, bool DEC = false, int NT2 = 0>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_pws_kernel(YlConvP p) {
-  constexpr int CH = 2;                                      // k-steps per weight chunk
+  constexpr int CH = YlPwsLds::CH;
   constexpr int NTA = NT + NT2;                              // n-tiles a wave accumulates
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1225,13 +1233,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_pws_kernel(Y
   // work order as in yl_conv_kxk_kernel: XCD x (workgroup b -> XCD b % 8) owns a contiguous band of m-tiles and runs
   // its (n-group, m-tile) items group-major, so that at any time an XCD streams 1/G of the weights out of its own L2
   const int bx = blockIdx.x, gx = gridDim.x;                 // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
-  const int bt = band1 > band0 ? band1 - band0 : 0;
-  const int nitems = bt * G;
-  const int nmine = slot < nitems ? (nitems - 1 - slot) / per + 1 : 0;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles, G);   // XCD bands, strided items
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, bt = ws.bt, nmine = ws.nmine;
   const long total_chunks = (long)nmine * NC;
   // asynchronous copy of chunk `c` (k-steps c*CH .. c*CH+CH-1, clamped) of n-group g into buffer `buf`
   auto load_chunk = [&](int g, int c, int buf) {
@@ -1252,8 +1255,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_pws_kernel(Y
   long gchunk = 0;                                            // chunks consumed so far (buffer = gchunk & 1)
   __syncthreads();
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
   const int ohw = p.OH * p.OW;
 
   for (int wi = 0; wi < nmine; ++wi) {
@@ -1262,7 +1264,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_pws_kernel(Y
     const int nt0 = g * NT;
     const int tile = band0 + item - g * bt;
     YlPix px[1];
-    {
+    {                                                        // (yl_pix written out, as in yl_conv_pwt_kernel)
       size_t lin = ((size_t)tile * NW + wave) * 16 + pl;
       px[0].valid = lin < (size_t)M;
       if (!px[0].valid) lin = (size_t)M - 1;
@@ -1394,21 +1396,19 @@ static hipError_t pws_go(const YlConvP& p0, hipStream_t st, int cand, bool eight
   const int NT = pws_nts[cand], NW = eight ? 8 : 4;
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW - 1) / (16 * NW));
-  const size_t lds = (size_t)2 * 2 * NT * 1024;
-  int gx = yl_resident_blocks((const void*)pws_kernels[cand][eight][0], NW * 64, lds, 8) & ~7;
   const int gy = (p.NTtot + NT - 1) / NT;
-  while (gx > 8 && gx - 8 >= p.ntiles * gy) gx -= 8;
+  // the occupancy question is put to the plain kernel of the candidate, also for its gated and its decode form (same LDS, same
+  // launch bounds); the form with the mask coefficients (+ 32 columns = 2 n-tiles from the second weight image) answers for itself
+  YlConvKernel kern = pws_kernels[cand][eight][p.scale != nullptr], asked = pws_kernels[cand][eight][0];
+  int NTA = NT;
   if (p.dec_boxes) {
     if (NT != 6 || p.scale) return hipErrorNotSupported;
-    if (p.w3p) {                                              // + the mask coefficients (32 columns) from the second weight image
-      const size_t lds2 = (size_t)2 * 2 * 8 * 1024;
-      int gx2 = yl_resident_blocks((const void*)pws_dec_kernels[eight][1], NW * 64, lds2, 8) & ~7;
-      while (gx2 > 8 && gx2 - 8 >= p.ntiles * gy) gx2 -= 8;
-      hipLaunchKernelGGL(pws_dec_kernels[eight][1], dim3(gx2), dim3(NW * 64), lds2, st, p);
-    } else
-      hipLaunchKernelGGL(pws_dec_kernels[eight][0], dim3(gx), dim3(NW * 64), lds, st, p);
-  } else
-    hipLaunchKernelGGL(pws_kernels[cand][eight][p.scale != nullptr], dim3(gx), dim3(NW * 64), lds, st, p);
+    kern = pws_dec_kernels[eight][p.w3p != nullptr];
+    if (p.w3p) { NTA = NT + 2; asked = kern; }
+  }
+  const size_t lds = YlPwsLds::bytes(NTA);
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)asked, NW * 64, lds, 8), (long)p.ntiles * gy);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
 }
 
@@ -1468,24 +1468,37 @@ hipError_t yl_launch_conv_pws(const YlConvP& p, hipStream_t st) {
 // computed per halo pixel from 25 x 2 float4 taps read straight from L1/L2, bit-identical, the 157 MB expanded tensor
 // never written): 35.4k against 40.0k images/s -- 300 dependent tap loads per lane and tile at two workgroups per CU;
 // it would need the block input staged in LDS (68 KB per 8x8 tile).  Not kept.)
+// expanded-halo slab of a workgroup tile of 4 RBN x 4 MT CBN output pixels: row pitch in floats (see yl_conv_dwh_kernel), floats
+constexpr __host__ __device__ int yl_ir_pitch(int dk, int ds, int mt, int cbn) { return ((((4 * mt * cbn - 1) * ds + dk) * 16 + 7) / 64) * 64 + 56; }
+constexpr __host__ __device__ int yl_ir_slab(int dk, int ds, int mt, int rbn, int cbn) { return ((4 * rbn - 1) * ds + dk) * yl_ir_pitch(dk, ds, mt, cbn); }
+// dynamic LDS of yl_ir_kernel (offsets in floats): [2] slabs | [2][NT][64] float4 projection weights of a slab | [KB][DK*DK + 1][16]
+// taps + dw bias of a slab's channels (zeros beyond Cmid; k-block-major, so that a lane's tap reads of a slab are ONE address +
+// immediates) | [KB*16] expansion bias
+struct YlIrLds {
+  static constexpr size_t LIMIT = 150 * 1024;
+  size_t wpl, dwl, b2l, bytes;
+  constexpr __host__ __device__ YlIrLds(int dk, int ds, int mt, int rbn, int cbn, int nt, int KB)
+      : wpl((size_t)2 * yl_ir_slab(dk, ds, mt, rbn, cbn)), dwl(wpl + (size_t)2 * nt * 256), b2l(dwl + (size_t)KB * (dk * dk + 1) * 16),
+        bytes((b2l + (size_t)KB * 16) * 4) {}
+};
+
 template <int KBI /*ceil(C1/16)*/, int NT, int DK, int DS, int MT, int RBN /*wave rows*/, int CBN /*wave columns*/>
 __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 3 && NT <= 3) ? 3 : 2) void yl_ir_kernel(YlConvP p) {
   constexpr int NWV = RBN * CBN, NTH = NWV * 64;                   // waves / threads per workgroup
   constexpr int TH = 4 * RBN, TW = 4 * MT * CBN;                   // workgroup tile: every wave a 4 x 4 MT block
   constexpr int HH = (TH - 1) * DS + DK, HW = (TW - 1) * DS + DK, HN = HH * HW;
   constexpr int HMT = (HN + 15) / 16, HMW = (HMT + NWV - 1) / NWV; // halo m-tiles: all, per wave
-  constexpr int PITCHF = ((HW * 16 + 7) / 64) * 64 + 56;           // slab row pitch in floats (see yl_conv_dwh_kernel)
-  constexpr int SLAB = HH * PITCHF;
+  constexpr int PITCHF = yl_ir_pitch(DK, DS, MT, CBN), SLAB = yl_ir_slab(DK, DS, MT, RBN, CBN);
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
   const int Cmid = p.Cin, KB = p.KB, NTtot = p.NTtot, C1 = p.C1, H = p.H, W = p.W, OH = p.OH, OW = p.OW, N = p.N;
-  float* slab = yl_clds;                                           // [2][SLAB]
-  f32x4* wpl = reinterpret_cast<f32x4*>(yl_clds + 2 * SLAB);       // [2][NT][64] float4: projection weights of a slab
-  float* dwl = yl_clds + 2 * SLAB + 2 * NT * 256;                  // [KB][DK*DK + 1][16]: taps + dw bias of a slab's channels (zeros beyond Cmid):
-                                                                   // k-block-major, so that a lane's tap reads of a slab are ONE address + immediates
-  float* b2l = dwl + (size_t)KB * (DK * DK + 1) * 16;              // [KB*16] expansion bias
+  const YlIrLds L(DK, DS, MT, RBN, CBN, NT, KB);
+  float* slab = yl_clds;
+  f32x4* wpl = reinterpret_cast<f32x4*>(yl_clds + L.wpl);
+  float* dwl = yl_clds + L.dwl;
+  float* b2l = yl_clds + L.b2l;
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);          // projection [KB][NTtot][64]
   const f32x4* w2g = reinterpret_cast<const f32x4*>(p.w2p);        // expansion [KBI][KB][64]
   const yl_act_t* const xin = p.x;
@@ -1498,12 +1511,9 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
     }
     for (int i = tid; i < KB * 16; i += NTH) b2l[i] = p.b2[i];
   }
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float elo = (p.act2 == YL_ACT_RELU || p.act2 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float ehi = (p.act2 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
+  const float elo = yl_act_lo(p.act2), ehi = yl_act_hi(p.act2);
   const int dw_act = p.dw_act, act2 = p.act2;
   // lane constants: the lane's halo pixel in each of the wave's halo m-tiles (m = wave + 4 j)
   int h_r[HMW], h_c[HMW], h_lo[HMW];
@@ -1525,7 +1535,7 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
   const int ntiles = p.B * tiles_img;
   int tile, tend, tstride;
   if ((gridDim.x & 7) == 0) {                                      // XCD bands, see yl_conv_dwt_kernel
-    const int tpx = (ntiles + 7) >> 3;
+    const int tpx = (ntiles + 7) >> 3;                             // (written out for the same reason)
     const int band0 = (blockIdx.x & 7) * tpx;
     tend = (band0 + tpx) < ntiles ? (band0 + tpx) : ntiles;
     tile = band0 + (blockIdx.x >> 3);
@@ -1663,15 +1673,9 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
   }
 }
 
-static size_t yl_ir_lds(int dk, int ds, int mt, int rbn, int cbn, int nt, int cmid) {
-  const int hh = (4 * rbn - 1) * ds + dk, hw = (4 * mt * cbn - 1) * ds + dk;
-  const int pitch = ((hw * 16 + 7) / 64) * 64 + 56;
-  return ((size_t)2 * hh * pitch + (size_t)2 * nt * 256 + (size_t)((cmid + 15) / 16) * 16 * (dk * dk + 1) + (size_t)((cmid + 15) / 16) * 16) * 4;
-}
-
 template <int KBI, int NT, int DK, int DS, int MT, int RBN, int CBN>
 static hipError_t ir_go(const YlConvP& p, hipStream_t st) {
-  const size_t lds = yl_ir_lds(DK, DS, MT, RBN, CBN, NT, p.Cin);
+  const size_t lds = YlIrLds(DK, DS, MT, RBN, CBN, NT, p.KB).bytes;
   const long ntiles = (long)p.B * (p.OH / (4 * RBN)) * (p.OW / (4 * MT * CBN));
   int gx = yl_resident_blocks((const void*)yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>, RBN * CBN * 64, lds, 8);
   if (gx > ntiles) gx = (int)ntiles;
@@ -1696,7 +1700,7 @@ bool yl_ir_supported(int c1, int cmid, int n, int dk, int ds, int oh, int ow) {
   const int kbi = (c1 + 15) / 16, nt = (n + 15) / 16;
 #define YL_IR_CHECK(A, B, C, D, E, R, S)                                                                             \
   if (kbi == A && nt <= B && nt > YL_IR_BUCKET_LO(B) && dk == C && ds == D && (oh % (4 * R)) == 0 &&                    \
-      (ow % (4 * E * S)) == 0 && yl_ir_lds(C, D, E, R, S, B, cmid) <= 150 * 1024) return true;
+      (ow % (4 * E * S)) == 0 && YlIrLds(C, D, E, R, S, B, (cmid + 15) / 16).bytes <= YlIrLds::LIMIT) return true;
   YL_IR_SHAPES(YL_IR_CHECK)
 #undef YL_IR_CHECK
   return false;
@@ -1707,7 +1711,7 @@ hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st) {
   const int kbi = (p.C1 + 15) / 16, nt = p.NTtot;
 #define YL_IR_RUN(A, B, C, D, E, R, S)                                                                               \
   if (kbi == A && nt <= B && nt > YL_IR_BUCKET_LO(B) && p.dw_k == C && p.dw_stride == D && (p.OH % (4 * R)) == 0 &&     \
-      (p.OW % (4 * E * S)) == 0 && yl_ir_lds(C, D, E, R, S, B, p.Cin) <= 150 * 1024)                                    \
+      (p.OW % (4 * E * S)) == 0 && YlIrLds(C, D, E, R, S, B, p.KB).bytes <= YlIrLds::LIMIT)                                 \
     return ir_go<A, B, C, D, E, R, S>(p, st);
   YL_IR_SHAPES(YL_IR_RUN)
 #undef YL_IR_RUN
@@ -1726,11 +1730,20 @@ hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st) {
 // 28-32 MFMAs).  Same k order and epilogues as the kernels it replaces: bit-identical.
 // GW = n-groups held by ONE wave (accumulators GW x NT x 4 VGPRs): 1 = every (n-group, m-tile) pair is its own item
 // and the depthwise part is recomputed per group; GW = all groups = no recomputation, 2 waves per SIMD.
-template <int NT, int GW, int NW>
-__global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(YlConvP p) {
+// dynamic LDS of yl_conv_dwk_kernel (offsets in floats): [2][S][GW][NT][64] float4 weight chunks | [9][Cin] taps, [Cin] bias
+struct YlDwkLds {
+  static constexpr size_t LIMIT = 96 * 1024;
   // k-steps per weight chunk (= per barrier): 3 when a wave holds one n-group; with all groups in one wave 2 where two
   // buffers of 2 x GW x NT KiB still leave two workgroups per CU (edge_m's 244 channels: 0.359 -> 0.341 ms), else 1
-  constexpr int S = GW == 1 ? 3 : (GW * NT <= 16 ? 2 : 1);
+  static constexpr __host__ __device__ int steps(int NT, int GW) { return GW == 1 ? 3 : (GW * NT <= 16 ? 2 : 1); }
+  size_t dwl, bytes;
+  constexpr __host__ __device__ YlDwkLds(int NT, int GW, int Cin)
+      : dwl((size_t)2 * steps(NT, GW) * GW * NT * 256), bytes((dwl + yl_taps_floats(3, Cin)) * 4) {}
+};
+
+template <int NT, int GW, int NW>
+__global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(YlConvP p) {
+  constexpr int S = YlDwkLds::steps(NT, GW);
   constexpr int PCS = S * GW * NT;                           // 1 KiB pieces per chunk
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1746,19 +1759,14 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
   // (no per-tap mask in the loop); its depthwise results are replaced by zeros before the 1x1
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(xin), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
-  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);            // [2][S][GW][NT][64] float4
-  float* dwl = yl_clds + (size_t)2 * PCS * 256;              // [9][Cin] taps, [Cin] bias
+  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);
+  float* dwl = yl_clds + YlDwkLds(NT, GW, Cin).dwl;
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
   const int NC = (KB + S - 1) / S;                           // chunks per item
   const int G = NTtot / (NT * GW);                           // item groups (1 when the wave holds every n-group)
   const int bx = blockIdx.x, gx = gridDim.x;                 // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
-  const int bt = band1 > band0 ? band1 - band0 : 0;
-  const int nitems = bt * G;
-  const int nmine = slot < nitems ? (nitems - 1 - slot) / per + 1 : 0;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles, G);   // XCD bands, strided items
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, bt = ws.bt, nmine = ws.nmine;
   const long total_chunks = (long)nmine * NC;
   auto load_chunk = [&](int g, int c, int buf) {
     for (int i = wave; i < PCS; i += NW) {
@@ -1777,10 +1785,8 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
   long gchunk = 0;
   __syncthreads();
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const int dw_act = p.dw_act;
 
   for (int wi = 0; wi < nmine; ++wi) {
@@ -1790,15 +1796,7 @@ __global__ __launch_bounds__(NW * 64, GW == 1 ? 3 : 2) void yl_conv_dwk_kernel(Y
     const int tile = band0 + item - g * bt;
     YlPix px[1];
     {
-      size_t lin = ((size_t)tile * NW + wave) * 16 + pl;
-      px[0].valid = lin < (size_t)M;
-      if (!px[0].valid) lin = (size_t)M - 1;
-      px[0].lin = lin;
-      const int b = (int)(lin / ohw);
-      const int rem = (int)(lin - (size_t)b * ohw);
-      px[0].b = b;
-      px[0].oy = rem / OW;
-      px[0].ox = rem - px[0].oy * OW;
+      px[0] = yl_pix(((size_t)tile * NW + wave) * 16 + pl, M, ohw, OW);
     }
     f32x4 acc[GW][1][NT];
 #pragma unroll
@@ -1902,12 +1900,10 @@ static hipError_t dwk_go(const YlConvP& p0, hipStream_t st, int NT, int GW) {
   if (!kern) return hipErrorNotSupported;
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW - 1) / (16 * NW));
-  const size_t lds = (size_t)2 * (GW == 1 ? 3 : (GW * NT <= 16 ? 2 : 1)) * GW * NT * 1024 + (((size_t)10 * p.Cin + 3) & ~(size_t)3) * 4;
-  if (lds > 96 * 1024) return hipErrorNotSupported;
-  const int res = yl_resident_blocks((const void*)kern, NW * 64, lds, 8);
+  const size_t lds = YlDwkLds(NT, GW, p.Cin).bytes;
+  if (lds > YlDwkLds::LIMIT) return hipErrorNotSupported;
   const int G = p.NTtot / (NT * GW);
-  int gx = res & ~7;
-  while (gx > 8 && gx - 8 >= p.ntiles * G) gx -= 8;
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)kern, NW * 64, lds, 8), (long)p.ntiles * G);
   hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
 }
@@ -1961,19 +1957,30 @@ hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st) {
 //            wave requests window(kb + 2) / weights(kb + 2) into the buffers of blocks kb / kb - 1, builds B(kb + 1) and goes
 //            on with the second half of block kb's MFMAs -- the MFMA stream runs on across k-blocks.
 // Same tap order, k order and epilogues as yl_conv_dwk_kernel: BIT-IDENTICAL to it ("dev_select" bit 14 keeps the old kernel).
+// dynamic LDS of yl_conv_dwl_kernel (offsets in float4s): [3][NTP][64] weight pieces | [2 buffers][2 windows][RM] window slots |
+// (floats) [KB][10][16]: taps 0..8 + bias of a k-block's channels (zeros beyond Cin)
+struct YlDwlLds {
+  static constexpr size_t LIMIT = 128 * 1024;
+  static constexpr int RP = 12, RM = 512;                        // window row pitch in pixels, 16-byte slots per window
+  int NTP;                                                       // weight pieces per buffer (8 waves x NTP / 8 copies)
+  size_t Rl, dwl, bytes;
+  constexpr __host__ __device__ YlDwlLds(int NTT, int KB)
+      : NTP((NTT + 7) & ~7), Rl((size_t)3 * NTP * 64), dwl(Rl + 2 * 2 * RM), bytes(dwl * 16 + (size_t)KB * 160 * 4) {}
+};
+
 template <int NTT>
 __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
-  constexpr int RP = 12, RM = 512;
-  constexpr int NTP = (NTT + 7) & ~7;                            // weight pieces per buffer (8 waves x NTP / 8 copies)
+  constexpr YlDwlLds L(NTT, 0);                                  // (the offsets do not depend on KB)
+  constexpr int RP = YlDwlLds::RP, RM = YlDwlLds::RM, NTP = L.NTP;
   // MFMA groups of <= 4 n-tiles, an even number of them (their A fragments alternate between two register sets across
   // k-blocks): 16 = 4 x 4, 21 = 3 x 4 + 3 x 3
   constexpr int NCH = NTT == 16 ? 4 : 6;
   static_assert(NTT == 16 || NTT == 21, "n-tile groups");
   auto c0of = [](int c) { return NTT == 16 ? 4 * c : (c <= 3 ? 4 * c : 12 + 3 * (c - 3)); };
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
-  f32x4* const Wl = reinterpret_cast<f32x4*>(yl_clds);           // [3][NTP][64]
-  f32x4* const Rl = Wl + 3 * NTP * 64;                           // [2 buffers][2 windows][RM]
-  float* const dwl = reinterpret_cast<float*>(Rl + 2 * 2 * RM);  // [KB][10][16]: taps 0..8 + bias of a k-block's channels (zeros beyond Cin)
+  f32x4* const Wl = reinterpret_cast<f32x4*>(yl_clds);
+  f32x4* const Rl = Wl + L.Rl;
+  float* const dwl = reinterpret_cast<float*>(Wl + L.dwl);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
@@ -1984,10 +1991,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
   const yl_act_t* const xin = p.x;
   const int wgmax = KB * NTtot - 1;                              // last weight piece
   const int bx = blockIdx.x, gx = gridDim.x;                     // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;                           // items per XCD band
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles);       // XCD bands, strided items (one n-group)
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, band1 = ws.band1;
   // copy role of the lane: slot rs = wave * 64 + lane of both windows
   const int rs = wave * 64 + lane;
   const int rP = rs >> 2, rkq = (rs & 3) ^ (((rP >> 2) & 1) << 1);
@@ -2019,10 +2024,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_dwl_kernel(YlConvP p) {
   const int lane16 = lane * 16;
   const int sh = KB & 1;                                         // window(kb) lives in buffer (kb + KB) & 1: see yl_conv_wino2_kernel
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const int dw_act = p.dw_act;
 
   unsigned voff[2];
@@ -2208,17 +2211,13 @@ static YlConvKernel dwl_kernel_of(int NTT) {
 }
 
 static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, YlConvKernel kern) {
-  const int NTP = (p0.NTtot + 7) & ~7;
   YlConvP p = p0;
   const long WTOT = (long)p.B * ((p.OW + 7) >> 3) * ((p.OH + 7) >> 3);
   p.ntiles = (int)((WTOT + 1) / 2);
-  const size_t lds = ((size_t)3 * NTP * 64 + 4 * 512) * 16 + (size_t)p.KB * 160 * 4;
-  if (lds > 128 * 1024) return hipErrorNotSupported;
+  const size_t lds = YlDwlLds(p.NTtot, p.KB).bytes;
+  if (lds > YlDwlLds::LIMIT) return hipErrorNotSupported;
   if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
-  const int res = yl_resident_blocks((const void*)kern, 512, lds, 8);
-  int gx = res & ~7;
-  if (gx < 8) gx = 8;
-  while (gx > 8 && gx - 8 >= p.ntiles) gx -= 8;
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)kern, 512, lds, 8), p.ntiles);
   hipLaunchKernelGGL(kern, dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
 }
@@ -2241,14 +2240,24 @@ static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, YlConvKernel kern) {
 //                            2 x S k-steps of them, whatever the channel count.
 // Same tap order (dy, dx), k order and epilogues as yl_dw_tile_kernel + yl_conv_pws_kernel: the depthwise value of a channel is
 // the same fmaf chain, the 1x1 sums its k blocks in ascending order -> bit-identical to the two launches it replaces.
+// dynamic LDS of yl_conv_dws_kernel (offsets in float4s): [2][S][NTW][64] weight chunks | [2][S][TQP] taps: row t = tap t (t = TAPS:
+// bias), 4 quads | (floats) one halo patch per wave
+struct YlDwsLds {
+  static constexpr size_t LIMIT = 96 * 1024;
+  int S;                                                             // k-steps per chunk (= per barrier)
+  int TQ, TQP;                                                       // float4s of taps + bias per k-step, padded to whole 64-lane copies
+  int HP, PITCHF;                                                    // halo patch rows = columns, row pitch in floats (see yl_conv_dwh_kernel)
+  size_t tl, halo, bytes;
+  constexpr __host__ __device__ YlDwsLds(int NTW, int DK, int DS, int NW)
+      : S(NTW <= 8 ? 2 : 1), TQ((DK * DK + 1) * 4), TQP(((TQ + 63) / 64) * 64), HP(3 * DS + DK), PITCHF(((HP * 16 + 7) / 64) * 64 + 56),
+        tl((size_t)2 * S * NTW * 64), halo(tl + (size_t)2 * S * TQP), bytes(halo * 16 + (size_t)NW * HP * PITCHF * 4) {}
+};
+
 template <int NT, int GW, int DK, int DS, int NW>
 __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
   constexpr int NTW = NT * GW;                                        // n-tiles a wave accumulates (all of the layer's)
-  constexpr int S = NTW <= 8 ? 2 : 1;                                // k-steps per chunk (= per barrier)
-  constexpr int TAPS = DK * DK, TQ = (TAPS + 1) * 4;                 // float4s of taps + bias per k-step
-  constexpr int TQP = ((TQ + 63) / 64) * 64;                         // ... padded to whole 64-lane copies
-  constexpr int HP = 3 * DS + DK;                                    // halo patch rows = columns
-  constexpr int PITCHF = ((HP * 16 + 7) / 64) * 64 + 56;             // row pitch in floats (see yl_conv_dwh_kernel)
+  constexpr YlDwsLds L(NTW, DK, DS, NW);
+  constexpr int S = L.S, TAPS = DK * DK, TQ = L.TQ, TQP = L.TQP, HP = L.HP, PITCHF = L.PITCHF;
   constexpr int HF4 = HP * HP * 4, NSLOT = (HF4 + 63) / 64;
   constexpr int PCS = S * NTW + S * (TQP / 64);                      // 1 KiB pieces per chunk: weights, then taps
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
@@ -2264,20 +2273,16 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<yl_act_t*>(xin), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)), 0x00020000);
   constexpr unsigned OOB = 0x80000000u;
-  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);                     // [2][S][NTW][64] float4
-  f32x4* tl = wl + (size_t)2 * S * NTW * 64;                         // [2][S][TQP] float4: row t = tap t (t = TAPS: bias), 4 quads
-  float* halo = reinterpret_cast<float*>(tl + (size_t)2 * S * TQP) + wave * (HP * PITCHF);
+  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);
+  f32x4* tl = wl + L.tl;
+  float* halo = reinterpret_cast<float*>(wl + L.halo) + wave * (HP * PITCHF);
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wp);
   const int NC = (KB + S - 1) / S;
   const int twn = OW >> 2, tiles_img = twn * (OH >> 2);
   const long ntiles4 = (long)p.B * tiles_img;                        // 4x4 tiles; p.ntiles = items of NW tiles
   const int bx = blockIdx.x, gx = gridDim.x;                         // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
-  const int bt = band1 > band0 ? band1 - band0 : 0;
-  const int nmine = slot < bt ? (bt - 1 - slot) / per + 1 : 0;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles);           // XCD bands, strided items (one n-group)
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, nmine = ws.nmine;
   const long total_chunks = (long)nmine * NC;
   auto load_chunk = [&](int c, int buf) {
     for (int i = wave; i < PCS; i += NW) {
@@ -2312,10 +2317,8 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
   }
   __syncthreads();
   const bool pre_add = (p.res || p.up) && p.act == YL_ACT_NONE;
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const int dw_act = p.dw_act;
   const int rbase = ((pl >> 2) * DS) * PITCHF + ((pl & 3) * DS) * 16 + 4 * kq;
 
@@ -2435,22 +2438,14 @@ __global__ __launch_bounds__(NW * 64, 2) void yl_conv_dws_kernel(YlConvP p) {
   }
 }
 
-static size_t yl_dws_lds(int ntw, int dk, int ds, int nw) {
-  const int s = ntw <= 8 ? 2 : 1, tqp = ((dk * dk + 1) * 4 + 63) / 64 * 64, hp = 3 * ds + dk;
-  const int pitch = ((hp * 16 + 7) / 64) * 64 + 56;
-  return ((size_t)2 * s * ntw * 256 + (size_t)2 * s * tqp * 4 + (size_t)nw * hp * pitch) * 4;
-}
-
 template <int NT, int GW, int DK, int DS, int NW>
 static hipError_t dws_go(const YlConvP& p0, hipStream_t st) {
   YlConvP p = p0;
   const long t4 = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
   p.ntiles = (int)((t4 + NW - 1) / NW);
-  const size_t lds = yl_dws_lds(NT * GW, DK, DS, NW);
-  const int res = yl_resident_blocks((const void*)yl_conv_dws_kernel<NT, GW, DK, DS, NW>, NW * 64, lds, 8);
-  int gx = res & ~7;
-  if (gx < 8) gx = 8;                                            // (occupancy query below 8: never a grid of 0 -- ADVICE r05)
-  while (gx > 8 && gx - 8 >= p.ntiles) gx -= 8;
+  constexpr size_t lds = YlDwsLds(NT * GW, DK, DS, NW).bytes;
+  static_assert(lds <= YlDwsLds::LIMIT, "yl_conv_dws_kernel: LDS of an instantiated shape");
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)yl_conv_dws_kernel<NT, GW, DK, DS, NW>, NW * 64, lds, 8), p.ntiles);
   hipLaunchKernelGGL((yl_conv_dws_kernel<NT, GW, DK, DS, NW>), dim3(gx), dim3(NW * 64), lds, st, p);
   return hipGetLastError();
 }
@@ -2509,9 +2504,16 @@ hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st) {
 // SH = 1 (round 4): the conv reads its input nearest-upsampled by 2 (yl_layer.in_shift, the prototype branch's second conv):
 // p.H / p.W are the dims of the VIRTUAL tensor; the 4x4 patch of a tile maps onto a 3x3 block of stored pixels
 // (rows / columns (2t-1+r) >> 1 = t-1, t, t, t+1).
+// dynamic LDS of yl_conv_wino_kernel: two buffers of one k-block's U = 16 positions x NT pieces of 1 KiB, [2][16][NT][64] float4 at 0
+struct YlWinoLds {
+  static constexpr size_t LIMIT = 96 * 1024;
+  static constexpr int NT = 2;                               // n-tiles per item
+  static constexpr size_t bytes = (size_t)2 * 16 * NT * 1024;
+};
+
 template <int SH>
 __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
-  constexpr int NW = 8, NT = 2;
+  constexpr int NW = 8, NT = YlWinoLds::NT;
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2526,13 +2528,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
   const f32x4* wg = reinterpret_cast<const f32x4*>(p.wino);
   const int G = (p.NTtot + NT - 1) / NT;
   const int bx = blockIdx.x, gx = gridDim.x;                 // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
-  const int bt = band1 > band0 ? band1 - band0 : 0;
-  const int nitems = bt * G;
-  const int nmine = slot < nitems ? (nitems - 1 - slot) / per + 1 : 0;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles, G);   // XCD bands, strided items
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, bt = ws.bt, nmine = ws.nmine;
   const long total_chunks = (long)nmine * KB;
   auto load_chunk = [&](int g, int kb, int buf) {
     for (int i = wave; i < 16 * NT; i += NW)
@@ -2573,8 +2570,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino_kernel(YlConvP p) {
   const int borg = (W + 1) * Cin * (int)sizeof(yl_act_t);
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<char*>(reinterpret_cast<const char*>(xin) - borg), 0, (int)((long)p.B * H * W * Cin * (long)sizeof(yl_act_t)) + borg, 0x00020000);
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
 
   for (int wi = 0; wi < nmine; ++wi) {
     const int item = slot + wi * per;
@@ -2713,11 +2709,9 @@ static hipError_t wino_go(const YlConvP& p0, hipStream_t st) {
   YlConvP p = p0;
   const long T = (long)p.B * ((p.OH + 1) >> 1) * ((p.OW + 1) >> 1);
   p.ntiles = (int)((T + 127) / 128);
-  const size_t lds = (size_t)2 * 16 * 2 * 1024;
-  const int res = yl_resident_blocks((const void*)wino_kernels[0], 512, lds, 8);
+  const size_t lds = YlWinoLds::bytes;
   const int G = (p.NTtot + 1) / 2;
-  int gx = res & ~7;
-  while (gx > 8 && gx - 8 >= p.ntiles * G) gx -= 8;
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)wino_kernels[0], 512, lds, 8), (long)p.ntiles * G);
   hipLaunchKernelGGL(wino_kernels[p.in_shift ? 1 : 0], dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
 }
@@ -2757,12 +2751,20 @@ static hipError_t wino_go(const YlConvP& p0, hipStream_t st) {
 // (tile rows {0,3}) and 8 with a ^ 1 (tile rows {1,2}) (MI355X_MICROARCH.md, LDS): P = ty4 * 12 + tx4 + const takes every
 // residue mod 4 twice per set, the two with bit 2 of P different (36 = 9 * 4, 12 = 3 * 4), so the low slot bits are
 // {a, a ^ 2} and {a ^ 1, a ^ 3}: sixteen distinct 16-byte bank groups, conflict-free.
+// dynamic LDS of yl_conv_wino2_kernel (offsets in float4s): [2][MT][RM] windows | [16][MT][64] accumulator exchange of the epilogue.
+// Every instantiation's limit is its exact size
+struct YlWino2Lds {
+  static constexpr int RP = 12, RM = 512;                       // window row pitch in pixels; slots per m-tile window (480 used: 8 full copy instructions)
+  size_t Xl, bytes;
+  constexpr __host__ __device__ YlWino2Lds(int MT) : Xl((size_t)2 * MT * RM), bytes((Xl + (size_t)16 * MT * 64) * 16) {}
+};
+
 template <int MT, int NT, int SH>
 __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
-  constexpr int RP = 12, RM = 512;                              // slots per m-tile window (480 used: 8 full copy instructions)
+  constexpr int RP = YlWino2Lds::RP, RM = YlWino2Lds::RM;
   extern __shared__ __attribute__((aligned(16))) float yl_clds[];
-  f32x4* const Rl = reinterpret_cast<f32x4*>(yl_clds);          // [2][MT][RM] windows
-  f32x4* const Xl = Rl + 2 * MT * RM;                           // [16][MT][64] accumulator exchange of the epilogue
+  f32x4* const Rl = reinterpret_cast<f32x4*>(yl_clds);
+  f32x4* const Xl = Rl + YlWino2Lds(MT).Xl;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;                      // MFMA lane: 4 channels 4kq.. of tile pl
@@ -2777,13 +2779,8 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
   const int NG2 = (p.NTtot + 1) >> 1;                           // n-tile pairs of the U image
   const int G = (p.NTtot + NT - 1) / NT;
   const int bx = blockIdx.x, gx = gridDim.x;                    // gx % 8 == 0
-  const int per = gx >> 3, slot = bx >> 3;
-  const int tpx = (p.ntiles + 7) >> 3;                          // m-blocks per XCD band
-  const int band0 = (bx & 7) * tpx;
-  const int band1 = (band0 + tpx) < p.ntiles ? (band0 + tpx) : p.ntiles;
-  const int bt = band1 > band0 ? band1 - band0 : 0;
-  const int nitems = bt * G;
-  const int nmine = slot < nitems ? (nitems - 1 - slot) / per + 1 : 0;
+  const YlBandSplit ws = yl_band_split(bx, gx, p.ntiles, G);   // XCD bands, strided items
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, bt = ws.bt, nmine = ws.nmine;
   // item -> (n-group, m-block): as in yl_conv_wino_kernel (the workgroups of an XCD walk GBS n-groups of one input window)
   constexpr int GBS = 4;
   const int nbf = G / GBS;
@@ -2812,8 +2809,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
   };
   const int sX0 = wslot(rowX, col0), sX1 = wslot(rowX, col1), sX2 = wslot(rowX, col2);
   const int sY0 = wslot(rowY, col0), sY1 = wslot(rowY, col1), sY2 = wslot(rowY, col2);
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
 
   // Both operand streams go through raw buffer descriptors (round 6): the per-lane part of an address is ONE 32-bit byte
   // offset fixed for the whole item, the k-block part is a scalar offset -- no vector instruction in the loop computes an
@@ -3019,19 +3015,14 @@ static YlConvKernel wino2_kernel_of(int MT, int NT, int in_shift) {
 #undef YL_WINO2_PICK
   return nullptr;
 }
-static size_t wino2_lds(int MT) { return ((size_t)2 * MT * 512 + (size_t)16 * MT * 64) * 16; }   // two window buffers + the epilogue exchange
-
 static hipError_t wino2_go(const YlConvP& p0, hipStream_t st, int MT, int NT) {
-  const size_t lds = wino2_lds(MT);
+  const size_t lds = YlWino2Lds(MT).bytes;
   YlConvP p = p0;
   const int TW = (p.OW + 1) >> 1, TH = (p.OH + 1) >> 1;
   const long MTOT = (long)p.B * ((TW + 3) >> 2) * ((TH + 3) >> 2);
   p.ntiles = (int)((MTOT + MT - 1) / MT);
-  const int res = yl_resident_blocks((const void*)wino2_kernel_of(MT, NT, 0), 512, lds, 8);
   const int G = (p.NTtot + NT - 1) / NT;
-  int gx = res & ~7;
-  if (gx < 8) gx = 8;
-  while (gx > 8 && gx - 8 >= p.ntiles * G) gx -= 8;
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)wino2_kernel_of(MT, NT, 0), 512, lds, 8), (long)p.ntiles * G);
   hipLaunchKernelGGL(wino2_kernel_of(MT, NT, p.in_shift), dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
 }
@@ -3081,28 +3072,28 @@ int kbmax_of(int ntw) { return ntw == 1 ? 18 : ntw == 2 ? 9 : ntw == 3 ? 6 : 4; 
 hipError_t yl_convc_init() {
   hipError_t e = hipSuccess;
   const auto cap = [&e](const auto& kernels, size_t bytes) { if (e == hipSuccess) e = yl_set_lds_cap(kernels, bytes); };
-#define YL_KXK_CAP(A, B, C) cap(yl_conv_kxk_kernel<A, B, C>, 96 * 1024);
+#define YL_KXK_CAP(A, B, C) cap(yl_conv_kxk_kernel<A, B, C>, YlKxkLds::LIMIT);
   YL_KXK_SHAPES(YL_KXK_CAP)
-#define YL_IR_CAP(A, B, C, D, E, R, S) cap(yl_ir_kernel<A, B, C, D, E, R, S>, 150 * 1024);
+#define YL_IR_CAP(A, B, C, D, E, R, S) cap(yl_ir_kernel<A, B, C, D, E, R, S>, YlIrLds::LIMIT);
   YL_IR_SHAPES(YL_IR_CAP)
-  cap(pws_kernels, 64 * 1024);
-  cap(pws_dec_kernels, 64 * 1024);
-  cap(dwt_kernels, 96 * 1024);
-  cap(dwt_splitk_kernels, 96 * 1024);
-  cap(wino_kernels, 96 * 1024);
-#define YL_WINO2_CAP(A, B) cap(yl_conv_wino2_kernel<A, B, 1>, wino2_lds(A)); cap(yl_conv_wino2_kernel<A, B, 0>, wino2_lds(A));
+  cap(pws_kernels, YlPwsLds::LIMIT);
+  cap(pws_dec_kernels, YlPwsLds::LIMIT);
+  cap(dwt_kernels, YlDwtLds::LIMIT);
+  cap(dwt_splitk_kernels, YlDwtLds::LIMIT);
+  cap(wino_kernels, YlWinoLds::LIMIT);
+#define YL_WINO2_CAP(A, B) cap(yl_conv_wino2_kernel<A, B, 1>, YlWino2Lds(A).bytes); cap(yl_conv_wino2_kernel<A, B, 0>, YlWino2Lds(A).bytes);
   YL_WINO2_SHAPES(YL_WINO2_CAP)
-#define YL_DWK_CAP(A, B, C) cap(yl_conv_dwk_kernel<A, B, C>, 96 * 1024);
+#define YL_DWK_CAP(A, B, C) cap(yl_conv_dwk_kernel<A, B, C>, YlDwkLds::LIMIT);
   YL_DWK_SHAPES(YL_DWK_CAP)
-#define YL_DWL_CAP(A) cap(yl_conv_dwl_kernel<A>, 128 * 1024);
+#define YL_DWL_CAP(A) cap(yl_conv_dwl_kernel<A>, YlDwlLds::LIMIT);
   YL_DWL_SHAPES(YL_DWL_CAP)
-#define YL_DWS_CAP(A, G, K, S_) cap(yl_conv_dws_kernel<A, G, K, S_, 4>, 96 * 1024);
+#define YL_DWS_CAP(A, G, K, S_) cap(yl_conv_dws_kernel<A, G, K, S_, 4>, YlDwsLds::LIMIT);
   YL_DWS_SHAPES(YL_DWS_CAP)
 #if !YL_BF16
-#define YL_DWX_CAP(A, B) cap(yl_conv_dwx_kernel<A, B>, 96 * 1024);
+#define YL_DWX_CAP(A, B) cap(yl_conv_dwx_kernel<A, B>, YlDwtLds::LIMIT);
   YL_DWX_SHAPES(YL_DWX_CAP)
 #endif
-  cap(dwc_kernels, YL_DWC_LDS_MAX);
+  cap(dwc_kernels, YlDwcLds::LIMIT);
   return e;
 }
 
@@ -3119,12 +3110,8 @@ hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st) {
   const bool all = (p.dev & YL_DEV_DWC_ALL) != 0;       // "dev_select" bit 3: the bitwise-equivalence test
   if (!all && (p.KB < 12 || p.dw_stride != 1)) return hipErrorNotSupported;
   if (!((p.dw_k == 3 || p.dw_k == 5) && (p.dw_stride == 1 || p.dw_stride == 2))) return hipErrorNotSupported;
-  const int HP = 3 * p.dw_stride + p.dw_k;
-  const int NG = (p.KB + 3) / 4;
-  const int PITCH = p.dw_stride == 1 ? HP * 32 + ((HP * 128) % 256 == 128 ? 0 : 32) : HP * 32 + 16;   // YlDwcGeo
-  const size_t lds = ((size_t)2 * p.KB * 256 + (((size_t)(p.dw_k * p.dw_k + 1) * p.Cin + 3) & ~(size_t)3) +
-                      (size_t)(NG < 4 ? NG : 4) * HP * PITCH) * 4;
-  if (lds > YL_DWC_LDS_MAX) return hipErrorNotSupported;
+  const size_t lds = YlDwcLds{p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes();
+  if (lds > YlDwcLds::LIMIT) return hipErrorNotSupported;
   long tiles[4], total = 0;
   for (int k = 0; k < m.n; ++k) {
     if ((m.p[k].OH & 3) || (m.p[k].OW & 3) || (size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * 4 >= ((size_t)1 << 31))
@@ -3134,12 +3121,12 @@ hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st) {
   }
   const YlMultiKernel kern = dwc_kernels[ntw - 1][p.dw_k == 5][p.dw_stride == 2];
   const int res = yl_resident_blocks((const void*)kern, 512, lds, 4);
-  // grid: a multiple of 8 workgroups (XCD-aware tile bands, see the kernel), at most what is co-resident
-  long gx = (total + 7) & ~7L;
-  if (gx > res) gx = res & ~7L;
-  if (gx < 8) gx = 8;
+  // grid: a multiple of 8 workgroups (XCD-aware tile bands, see the kernel), at most what is co-resident and one per tile
+  long gx = yl_band_grid(res, total);
   if (m.n == 1) { m.p[0].blk0 = 0; m.p[0].nblk = 0; }
   else {
+    // shares of the grid, not of the co-resident count, rounded to nearest and without a per-tile cap: not yl_multi_shares'
+    // rule (dwt, dwx), and other grids than it gives
     int at = 0;
     for (int k = 0; k < m.n; ++k) {
       long nb = ((tiles[k] * gx + total / 2) / total + 7) & ~7L;

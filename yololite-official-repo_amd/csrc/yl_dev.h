@@ -19,6 +19,85 @@ __device__ __forceinline__ f32x4 yl_act4(f32x4 v, int act) {
   r.x = yl_act1(v.x, act); r.y = yl_act1(v.y, act); r.z = yl_act1(v.z, act); r.w = yl_act1(v.w, act);
   return r;
 }
+// clamp bounds of a ReLU-family activation (yl_clamp4 below): lo = -inf / hi = +inf give the one-sided / identity cases.
+// Macros, not functions: an inlined function hands the optimizer the compares and the selects in another order than the statement
+// written in place did, and most conv kernels then come out with another instruction schedule (no instruction more or less)
+#define yl_act_lo(act) (((act) == YL_ACT_RELU || (act) == YL_ACT_RELU6) ? 0.0f : -INFINITY)
+#define yl_act_hi(act) (((act) == YL_ACT_RELU6) ? 6.0f : INFINITY)
+
+// ---- how a persistent grid deals its work.  Workgroup b runs on XCD b % 8 (observed dispatch order; another placement changes
+// speed only), so a grid of gx workgroups, gx % 8 == 0 (yl_internal.h: yl_band_grid), is gx / 8 workgroups on each of 8 XCDs, and
+// XCD x owns one contiguous band of the m-tiles: neighbouring tiles' halo rows and the weights an XCD streams stay in its own L2.
+// Strided form: band x = [x * ceil(ntiles / 8), ...) holds bt tiles = bt * G (n-group, tile) items; workgroup `slot` of the XCD
+// takes the band's items slot, slot + per, ... (nmine of them).  What (n-group, tile) an item is stays with each kernel.
+struct YlBandSplit {
+  int per, slot;         // workgroups per XCD, this workgroup's place among them
+  int band0, band1, bt;  // the XCD's band [band0, band1) of tiles and its length (0: an empty band)
+  int nitems, nmine;     // items of the band, items of this workgroup
+};
+constexpr __host__ __device__ __forceinline__ YlBandSplit yl_band_split(int bx, int gx, int ntiles, int G = 1) {
+  const int per = gx >> 3, slot = bx >> 3;
+  const int tpx = (ntiles + 7) >> 3;
+  const int band0 = (bx & 7) * tpx;
+  const int band1 = (band0 + tpx) < ntiles ? (band0 + tpx) : ntiles;
+  const int bt = band1 > band0 ? band1 - band0 : 0;
+  const int nitems = bt * G;
+  const int nmine = slot < nitems ? (nitems - 1 - slot) / per + 1 : 0;
+  return {per, slot, band0, band1, bt, nitems, nmine};
+}
+// Contiguous form: XCD x owns the band [x * T / 8, (x + 1) * T / 8) of the tiles, its gx / 8 workgroups split the band evenly;
+// workgroup bx runs the tiles [r0, r1).  yl_xcd_range: gx % 8 == 0 is the launcher's promise; yl_band_range: any grid (an even
+// split without bands otherwise)
+struct YlTileRange { int r0, r1; };
+constexpr __host__ __device__ __forceinline__ YlTileRange yl_xcd_range(int bx, int gx, int ntiles) {
+  const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
+  const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
+  return {(int)(b0 + ((b1 - b0) * j) / nj), (int)(b0 + ((b1 - b0) * (j + 1)) / nj)};
+}
+constexpr __host__ __device__ __forceinline__ YlTileRange yl_band_range(int bx, int gx, int ntiles) {
+  if ((gx & 7) == 0) return yl_xcd_range(bx, gx, ntiles);
+  return {(int)(((long)ntiles * bx) / gx), (int)(((long)ntiles * (bx + 1)) / gx)};
+}
+// every item / tile is taken exactly once: empty bands, ntiles no multiple of 8, more workgroups than items
+constexpr bool yl_band_split_exact(int ntiles, int G, int gx) {
+  int cnt[37 * 3] = {};
+  for (int bx = 0; bx < gx; ++bx) {
+    const YlBandSplit s = yl_band_split(bx, gx, ntiles, G);
+    for (int wi = 0; wi < s.nmine; ++wi) {
+      const int item = s.slot + wi * s.per, g = item / s.bt;       // group-major, as yl_conv_kxk_kernel reads an item
+      if (item >= s.nitems || s.band0 + s.bt > ntiles) return false;
+      ++cnt[g * ntiles + s.band0 + item - g * s.bt];
+    }
+  }
+  for (int i = 0; i < ntiles * G; ++i) if (cnt[i] != 1) return false;
+  return true;
+}
+constexpr bool yl_band_range_exact(int ntiles, int gx) {
+  int cnt[37] = {};
+  for (int bx = 0; bx < gx; ++bx) {
+    const YlTileRange r = yl_band_range(bx, gx, ntiles);
+    if (r.r0 < 0 || r.r1 > ntiles) return false;
+    for (int t = r.r0; t < r.r1; ++t) ++cnt[t];
+  }
+  for (int i = 0; i < ntiles; ++i) if (cnt[i] != 1) return false;
+  return true;
+}
+constexpr bool yl_split_checks() {
+  const int nts[5] = {1, 7, 8, 9, 37}, gxs[3] = {8, 16, 256};
+  for (int ntiles : nts)
+    for (int gx : gxs) {
+      if (!yl_band_split_exact(ntiles, 1, gx) || !yl_band_split_exact(ntiles, 3, gx)) return false;
+      if (!yl_band_range_exact(ntiles, gx) || !yl_band_range_exact(ntiles, gx - 3)) return false;   // gx - 3: the even split
+    }
+  return true;
+}
+static_assert(yl_split_checks(), "a work split leaves out an item or deals it twice");
+
+// floats of a depthwise tap image in LDS, [dk * dk][Cin] taps + [Cin] bias, rounded up to whole float4s
+constexpr __host__ __device__ __forceinline__ size_t yl_taps_floats(int dk, int Cin) {
+  return ((size_t)(dk * dk + 1) * Cin + 3) & ~(size_t)3;
+}
+
 __device__ __forceinline__ f32x4 yl_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void yl_st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 // fp16 activation tensors (the fp16-storage unit, yl_internal.h: yl_act_t): four consecutive channels are ONE 8-byte access;

@@ -23,7 +23,24 @@
 #include "yl_epi.h"
 
 constexpr int DPP_NW = 8;              // waves per workgroup
+constexpr int DPW_NW = 8;              // ... of yl_conv_dpw_kernel
 constexpr int DPP_WPE = 2;             // waves per SIMD the register budget is set for
+
+// dynamic LDS of yl_conv_dpp_kernel, yl_conv_dpw_kernel and yl_conv_dpq_kernel (offsets in floats): [KB][NT1][64] float4 weights of
+// the first 1x1 | [NT1][NT3][64] float4 weights of the second | [9][Cin] taps, [Cin] depthwise bias | [NT1 * 16] bias of the first
+// 1x1 (zero padded) | dpp, dpw: [NT3 * 16] bias of the second | dpw: per wave a ring of window buffers.  Every instantiation's
+// limit is its exact size
+struct YlDppLds {
+  static constexpr int WSL = 192;                                    // float4 slots per window buffer: three copies, 144 used
+  static constexpr __host__ __device__ int nbuf(int KB) { return (KB % 3 == 0) ? 3 : 2; }   // ring of window buffers (KB % NBUF == 0)
+  size_t w3, dw, b1, b3, win, bytes;
+  constexpr __host__ __device__ YlDppLds(int KB, int NT1, int NT3, bool bias3, int ring_f4)
+      : w3((size_t)KB * NT1 * 256), dw(w3 + (size_t)NT1 * NT3 * 256), b1(dw + 10 * KB * 16), b3(b1 + NT1 * 16),
+        win(b3 + (bias3 ? NT3 * 16 : 0)), bytes((win + (size_t)ring_f4 * 4) * 4) {}
+  static constexpr __host__ __device__ YlDppLds dpp(int KB, int NT1, int NT3) { return YlDppLds(KB, NT1, NT3, true, 0); }
+  static constexpr __host__ __device__ YlDppLds dpw(int KB, int NT1, int NT3) { return YlDppLds(KB, NT1, NT3, true, DPW_NW * nbuf(KB) * WSL); }
+  static constexpr __host__ __device__ YlDppLds dpq(int KB, int NC1, int NT3) { return YlDppLds(KB, NC1 * 6, NT3, false, 0); }
+};
 
 template <int KB /*Cin/16*/, int NT1 /*trunk n-tiles*/, int NT3 /*head-output n-tiles*/>
 __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlConvMulti mp) {
@@ -38,11 +55,12 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlCon
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
-  f32x4* w1l = reinterpret_cast<f32x4*>(dpp_lds);                    // [KB][NT1][64] float4
-  f32x4* w3l = w1l + KB * NT1 * 64;                                  // [NT1][NT3][64] float4
-  float* dwl = reinterpret_cast<float*>(w3l + NT1 * NT3 * 64);       // [9][Cin] taps, [Cin] depthwise bias
-  float* b1l = dwl + 10 * Cin;                                       // [NT1 * 16] trunk bias (zero padded)
-  float* b3l = b1l + NT1 * 16;                                       // [NT3 * 16] head-output bias (zero padded)
+  constexpr YlDppLds L = YlDppLds::dpp(KB, NT1, NT3);
+  f32x4* w1l = reinterpret_cast<f32x4*>(dpp_lds);
+  f32x4* w3l = reinterpret_cast<f32x4*>(dpp_lds + L.w3);
+  float* dwl = dpp_lds + L.dw;
+  float* b1l = dpp_lds + L.b1;                                       // trunk bias
+  float* b3l = dpp_lds + L.b3;                                       // head-output bias
   {
     const f32x4* g1 = reinterpret_cast<const f32x4*>(p.wp);
     for (int r = wave; r < KB * NT1; r += DPP_NW) yl_glds16(g1 + r * 64 + lane, w1l + r * 64);
@@ -62,19 +80,12 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlCon
   const int ntiles = p.B * tiles_img;
   // XCD-aware ranges (gx % 8 == 0 and blk0 % 8 == 0: workgroup b runs on XCD b % 8): XCD x owns the contiguous band
   // [x*T/8, (x+1)*T/8) of the tiles, its gx/8 workgroups split the band evenly
-  int r0, r1;
-  {
-    const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
-    const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
-    r0 = (int)(b0 + ((b1 - b0) * j) / nj);
-    r1 = (int)(b0 + ((b1 - b0) * (j + 1)) / nj);
-  }
+  const YlTileRange tr = yl_xcd_range(bx, gx, ntiles);
+  const int r0 = tr.r0, r1 = tr.r1;
   const float* const xin = p.x;
   const float* const zl = p.zeros + 4 * kq;                          // >= 1 KiB of zeros: the same kb offsets apply
-  const float lo1 = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi1 = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo1 = yl_act_lo(p.act), hi1 = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const float* const tapw = dwl + 4 * kq;                            // tap t of block kb: tapw[t * Cin + kb * 16]
 
   // Software pipeline over the tap loads: the taps of block kb + 2 are requested while block kb is multiplied (two
@@ -196,7 +207,6 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlCon
 //            fma chain of those taps -- no LDS round trip is waited for in front of an MFMA.
 // Same tap order, fma chain, k order and epilogue as yl_conv_dpp_kernel: BIT-IDENTICAL to it ("dev_select" bit 16 keeps
 // the tap-load kernel; tests/test_gpu_parity.py).
-constexpr int DPW_NW = 8;              // waves per workgroup
 template <int KB /*Cin/16*/, int NT1 /*trunk n-tiles*/, int NT3 /*head-output n-tiles*/>
 __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(YlConvMulti mp) {
   int yl_k = 0;
@@ -206,8 +216,7 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
   const YlConvP& p = mp.p[yl_k];
   const int bx = (int)blockIdx.x - p.blk0, gx = p.nblk;
   constexpr int Cin = KB * 16;
-  constexpr int NBUF = (KB % 3 == 0) ? 3 : 2;                        // ring of window buffers (KB % NBUF == 0)
-  constexpr int WSL = 192;                                           // float4 slots per buffer: three copies, 144 used
+  constexpr int NBUF = YlDppLds::nbuf(KB), WSL = YlDppLds::WSL;
   constexpr int G = NT1 / 2;                                         // MFMA groups of two n-tiles per block
   constexpr int TPG = (9 + G - 1) / G;                               // taps whose reads ride in front of one group
   static_assert(NT1 % 2 == 0 && KB % NBUF == 0 && NBUF + 1 <= KB, "yl_conv_dpw_kernel shape");
@@ -215,12 +224,13 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
-  f32x4* w1l = reinterpret_cast<f32x4*>(dpp_lds);                    // [KB][NT1][64] float4
-  f32x4* w3l = w1l + KB * NT1 * 64;                                  // [NT1][NT3][64] float4
-  float* dwl = reinterpret_cast<float*>(w3l + NT1 * NT3 * 64);       // [9][Cin] taps, [Cin] depthwise bias
-  float* b1l = dwl + 10 * Cin;                                       // [NT1 * 16] trunk bias (zero padded)
-  float* b3l = b1l + NT1 * 16;                                       // [NT3 * 16] head-output bias (zero padded)
-  f32x4* const winl = reinterpret_cast<f32x4*>(b3l + NT3 * 16) + wave * (NBUF * WSL);   // the wave's window ring
+  constexpr YlDppLds L = YlDppLds::dpw(KB, NT1, NT3);
+  f32x4* w1l = reinterpret_cast<f32x4*>(dpp_lds);
+  f32x4* w3l = reinterpret_cast<f32x4*>(dpp_lds + L.w3);
+  float* dwl = dpp_lds + L.dw;
+  float* b1l = dpp_lds + L.b1;                                       // trunk bias
+  float* b3l = dpp_lds + L.b3;                                       // head-output bias
+  f32x4* const winl = reinterpret_cast<f32x4*>(dpp_lds + L.win) + wave * (NBUF * WSL);   // the wave's window ring
   {
     const f32x4* g1 = reinterpret_cast<const f32x4*>(p.wp);
     for (int r = wave; r < KB * NT1; r += DPW_NW) yl_glds16(g1 + r * 64 + lane, w1l + r * 64);
@@ -239,18 +249,11 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
   const int tw = OW >> 2, th = OH >> 2;
   const int tiles_img = tw * th;
   const int ntiles = p.B * tiles_img;
-  int r0, r1;                                                        // XCD bands, see yl_conv_dpp_kernel
-  {
-    const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
-    const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
-    r0 = (int)(b0 + ((b1 - b0) * j) / nj);
-    r1 = (int)(b0 + ((b1 - b0) * (j + 1)) / nj);
-  }
+  const YlTileRange tr = yl_xcd_range(bx, gx, ntiles);   // XCD bands, see yl_conv_dpp_kernel
+  const int r0 = tr.r0, r1 = tr.r1;
   const float* const xin = p.x;
-  const float lo1 = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi1 = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo1 = yl_act_lo(p.act), hi1 = yl_act_hi(p.act);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const float* const tapw = dwl + 4 * kq;                            // tap t of block kb: tapw[t * Cin + kb * 16]
   // copy role of the lane in copy j: slot 64 j + lane = (pixel P = y * 6 + x of the window, stored quad)
   int cy[3], cx[3], cq[3];
@@ -427,10 +430,11 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpq_kernel(YlCon
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
-  f32x4* w1l = reinterpret_cast<f32x4*>(dpp_lds);                    // [KB][NT1][64] float4
-  f32x4* w3l = w1l + KB * NT1 * 64;                                  // [NT1][NT3][64] float4
-  float* dwl = reinterpret_cast<float*>(w3l + NT1 * NT3 * 64);       // [9][Cin] taps, [Cin] depthwise bias
-  float* b1l = dwl + 10 * Cin;                                       // [NT1 * 16] expand bias (zero padded)
+  constexpr YlDppLds L = YlDppLds::dpq(KB, NC1, NT3);
+  f32x4* w1l = reinterpret_cast<f32x4*>(dpp_lds);
+  f32x4* w3l = reinterpret_cast<f32x4*>(dpp_lds + L.w3);
+  float* dwl = dpp_lds + L.dw;
+  float* b1l = dpp_lds + L.b1;                                       // expand bias
   {
     const f32x4* g1 = reinterpret_cast<const f32x4*>(p.wp);
     for (int r = wave; r < KB * NT1; r += DPP_NW) yl_glds16(g1 + r * 64 + lane, w1l + r * 64);
@@ -448,23 +452,13 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpq_kernel(YlCon
   const int tw = OW >> 2, th = OH >> 2;
   const int tiles_img = tw * th;
   const int ntiles = p.B * tiles_img;
-  int r0, r1;
-  if ((gx & 7) == 0) {                                               // XCD bands, see yl_conv_dpp_kernel
-    const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
-    const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
-    r0 = (int)(b0 + ((b1 - b0) * j) / nj);
-    r1 = (int)(b0 + ((b1 - b0) * (j + 1)) / nj);
-  } else {
-    r0 = (int)(((long)ntiles * bx) / gx); r1 = (int)(((long)ntiles * (bx + 1)) / gx);
-  }
+  const YlTileRange tr = yl_band_range(bx, gx, ntiles);   // XCD bands, see yl_conv_dpp_kernel
+  const int r0 = tr.r0, r1 = tr.r1;
   const float* const xin = p.x;
   const float* const zl = p.zeros + 4 * kq;
-  const float lo1 = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi1 = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float lo3 = (p.act3 == YL_ACT_RELU || p.act3 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float dlo = (p.dw_act == YL_ACT_RELU || p.dw_act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float dhi = (p.dw_act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo1 = yl_act_lo(p.act), hi1 = yl_act_hi(p.act);
+  const float lo3 = yl_act_lo(p.act3), hi3 = yl_act_hi(p.act3);
+  const float dlo = yl_act_lo(p.dw_act), dhi = yl_act_hi(p.dw_act);
   const float* const tapw = dwl + 4 * kq;
   const bool pre_add = p.res != nullptr && p.act3 == YL_ACT_NONE;
 
@@ -589,13 +583,9 @@ bool yl_dpq_supported(int cin, int cmid, int cout, int oh, int ow) {
   return false;
 }
 
-static size_t dpq_lds_bytes(int kb, int nc1, int nt3) {
-  return (size_t)(kb * nc1 * 6 + nc1 * 6 * nt3) * 1024 + (size_t)(10 * kb * 16 + nc1 * 96) * 4;
-}
-
 template <int KB, int NC1, int NT3>
 static hipError_t dpq_go(const YlConvP& p, hipStream_t st) {
-  const size_t lds = dpq_lds_bytes(KB, NC1, NT3);
+  constexpr size_t lds = YlDppLds::dpq(KB, NC1, NT3).bytes;
   const long t = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
   long nb = YL_NUM_CU * (DPP_WPE * 4 / DPP_NW);
   if (nb > (t + DPP_NW - 1) / DPP_NW) nb = (t + DPP_NW - 1) / DPP_NW;
@@ -630,20 +620,31 @@ hipError_t yl_launch_conv_dpq(const YlConvP& p, hipStream_t st) {
 // in-order counter).  yl_conv_mfma_kernel<3,2,1> spent 4.5 VALU instructions per MFMA on per-tap address / bounds
 // arithmetic (SQ counters: 1.5e7 VALU instructions x 4 cycles against 1.08e8 MFMA cycles per B = 64 launch) -- and fp32
 // VALU time is MFMA time.  Same k order (tap-major), same epilogues: bit-identical.
+// dynamic LDS of yl_conv_s2c_kernel (offsets in floats): [9][NT][64] float4 weights of the 3x3 | [NT][NT3][64] float4 weights of the
+// 1x1 | [NT * 16], [NT3 * 16] their biases | per wave two buffers of the 5 x 17-pixel input patch.  The limit is the exact size
+struct YlS2cLds {
+  static constexpr int PR = 5, PC = 17, RCH = PC * 4, NCH = PR * RCH, NDMA = (NCH + 63) / 64;   // 340 16-byte chunks, 6 loads
+  static constexpr int BUF_F = NDMA * 256;                           // floats per patch buffer
+  size_t w3, b2, b3, patch, bytes;
+  constexpr __host__ __device__ YlS2cLds(int NT, int NT3)
+      : w3((size_t)9 * NT * 256), b2(w3 + (size_t)NT * NT3 * 256), b3(b2 + NT * 16), patch(b3 + NT3 * 16),
+        bytes((patch + (size_t)DPP_NW * 2 * BUF_F) * 4) {}
+};
+
 template <int NT /*n-tiles of the 3x3*/, int NT3 /*n-tiles of the chained 1x1*/>
 __global__ __launch_bounds__(DPP_NW * 64, 2) void yl_conv_s2c_kernel(YlConvP p) {
-  constexpr int PR = 5, PC = 17, RCH = PC * 4, NCH = PR * RCH, NDMA = (NCH + 63) / 64;   // 340 16-byte chunks, 6 loads
-  constexpr int BUF_F = NDMA * 256;                                  // floats per patch buffer
+  constexpr int PR = YlS2cLds::PR, PC = YlS2cLds::PC, RCH = YlS2cLds::RCH, NCH = YlS2cLds::NCH, NDMA = YlS2cLds::NDMA, BUF_F = YlS2cLds::BUF_F;
+  constexpr YlS2cLds L(NT, NT3);
   const int bx = (int)blockIdx.x, gx = (int)gridDim.x;
   extern __shared__ __attribute__((aligned(16))) float dpp_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
-  f32x4* w2l = reinterpret_cast<f32x4*>(dpp_lds);                    // [9][NT][64] float4
-  f32x4* w3l = w2l + 9 * NT * 64;                                    // [NT][NT3][64] float4
-  float* b2l = reinterpret_cast<float*>(w3l + NT * NT3 * 64);        // [NT * 16], [NT3 * 16]
-  float* b3l = b2l + NT * 16;
-  float* patch = b3l + NT3 * 16 + wave * 2 * BUF_F;                  // two buffers per wave
+  f32x4* w2l = reinterpret_cast<f32x4*>(dpp_lds);
+  f32x4* w3l = reinterpret_cast<f32x4*>(dpp_lds + L.w3);
+  float* b2l = dpp_lds + L.b2;
+  float* b3l = dpp_lds + L.b3;
+  float* patch = dpp_lds + L.patch + wave * 2 * BUF_F;               // two buffers per wave
   {
     const f32x4* g2 = reinterpret_cast<const f32x4*>(p.wp);
     for (int r = wave; r < 9 * NT; r += DPP_NW) yl_glds16(g2 + r * 64 + lane, w2l + r * 64);
@@ -657,19 +658,10 @@ __global__ __launch_bounds__(DPP_NW * 64, 2) void yl_conv_s2c_kernel(YlConvP p) 
   const int tw = OW >> 3, th = OH >> 1;
   const int tiles_img = tw * th;
   const int ntiles = p.B * tiles_img;
-  int r0, r1;
-  if ((gx & 7) == 0) {                                               // XCD bands, see yl_conv_dpp_kernel
-    const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
-    const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
-    r0 = (int)(b0 + ((b1 - b0) * j) / nj);
-    r1 = (int)(b0 + ((b1 - b0) * (j + 1)) / nj);
-  } else {
-    r0 = (int)(((long)ntiles * bx) / gx); r1 = (int)(((long)ntiles * (bx + 1)) / gx);
-  }
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float lo3 = (p.act3 == YL_ACT_RELU || p.act3 == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const YlTileRange tr = yl_band_range(bx, gx, ntiles);   // XCD bands, see yl_conv_dpp_kernel
+  const int r0 = tr.r0, r1 = tr.r1;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
+  const float lo3 = yl_act_lo(p.act3), hi3 = yl_act_hi(p.act3);
   // the lane's chunk of every DMA load: (patch row, pixel, 16-byte quarter of the pixel's 64 bytes)
   int crow[NDMA], cpx[NDMA], coff[NDMA];
 #pragma unroll
@@ -759,12 +751,9 @@ __global__ __launch_bounds__(DPP_NW * 64, 2) void yl_conv_s2c_kernel(YlConvP p) 
   flush_out();
 }
 
-static constexpr size_t s2c_lds_bytes(int nt, int nt3) {
-  return (size_t)(9 * nt + nt * nt3) * 1024 + (size_t)(nt + nt3) * 64 + (size_t)DPP_NW * 2 * 6 * 1024;
-}
 // the one instantiation: 3 n-tiles (48 channels) out of the 3x3, <= 2 (32 channels) out of the chained 1x1
 static const YlConvKernel s2c_kernel = yl_conv_s2c_kernel<3, 2>;
-static constexpr size_t s2c_lds = s2c_lds_bytes(3, 2);
+static constexpr size_t s2c_lds = YlS2cLds(3, 2).bytes;
 
 bool yl_s2c_supported(int cin, int cout, int c3, int oh, int ow) {
   return cin == 16 && cout == 48 && c3 > 16 && c3 <= 32 && (c3 & 3) == 0 && (oh & 1) == 0 && (ow & 7) == 0;
@@ -784,13 +773,6 @@ hipError_t yl_launch_conv_s2c(const YlConvP& p, hipStream_t st) {
   return hipGetLastError();
 }
 
-static size_t dpp_lds_bytes(int kb, int nt1, int nt3) {
-  return (size_t)(kb * nt1 + nt1 * nt3) * 1024 + (size_t)(10 * kb * 16 + nt1 * 16 + nt3 * 16) * 4;
-}
-static size_t dpw_lds_bytes(int kb, int nt1, int nt3) {   // yl_conv_dpw_kernel: + the waves' window rings
-  return dpp_lds_bytes(kb, nt1, nt3) + (size_t)DPW_NW * ((kb % 3 == 0) ? 3 : 2) * 192 * 16;
-}
-
 // shapes instantiated: (Cin/16, trunk n-tiles, head-output n-tiles)
 #define YL_DPP_SHAPES(X) X(6, 6, 6) X(4, 4, 6)
 
@@ -804,7 +786,7 @@ bool yl_dpp_supported(int cin, int cout, int c3, int oh, int ow) {
 
 template <int KB, int NT1, int NT3>
 static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st) {
-  const size_t lds = dpp_lds_bytes(KB, NT1, NT3), ldsw = dpw_lds_bytes(KB, NT1, NT3);
+  constexpr size_t lds = YlDppLds::dpp(KB, NT1, NT3).bytes, ldsw = YlDppLds::dpw(KB, NT1, NT3).bytes;
   // window-in-LDS form (round 6): depthwise pad 1 on every side; "dev_select" bit 16 keeps the tap-load kernel
   bool win = !(ps[0].dev & YL_DEV_DPW_OFF);
   for (int k = 0; k < n; ++k) win = win && ps[k].dw_pad_t == 1 && ps[k].dw_pad_l == 1;
@@ -865,9 +847,14 @@ hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st) {
 // vector instruction computes an address.  Same k order (tap-major, k-blocks inside), pre-add rule and epilogues as
 // yl_conv_mfma_kernel: BIT-IDENTICAL to the direct path ("dev_select" bit 17 switches the kernel off; tests/test_gpu_parity.py).
 #define K3W_NW 8
+// dynamic LDS of yl_conv_k3w_kernel: per wave the windows of its tile, [KB][WSL] float4 (yl_conv_dpw_kernel's window buffers)
+struct YlK3wLds {
+  static constexpr int WSL = YlDppLds::WSL;
+  static constexpr __host__ __device__ size_t bytes(int KB) { return (size_t)K3W_NW * KB * WSL * 16; }
+};
 template <int KB /*Cin/16*/>
 __global__ __launch_bounds__(K3W_NW * 64, 2) void yl_conv_k3w_kernel(YlConvP p) {
-  constexpr int Cin = KB * 16, WSL = 192;
+  constexpr int Cin = KB * 16, WSL = YlK3wLds::WSL;
   extern __shared__ __attribute__((aligned(16))) float dpp_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -886,20 +873,12 @@ __global__ __launch_bounds__(K3W_NW * 64, 2) void yl_conv_k3w_kernel(YlConvP p) 
   const int tiles_img = tw * th;
   const int ntiles = p.B * tiles_img;
   const int bx = blockIdx.x, gx = gridDim.x;
-  int r0, r1;                                                        // XCD bands, see yl_conv_dpp_kernel
-  if ((gx & 7) == 0) {
-    const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
-    const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
-    r0 = (int)(b0 + ((b1 - b0) * j) / nj);
-    r1 = (int)(b0 + ((b1 - b0) * (j + 1)) / nj);
-  } else {
-    r0 = (int)(((long)ntiles * bx) / gx); r1 = (int)(((long)ntiles * (bx + 1)) / gx);
-  }
+  const YlTileRange tr = yl_band_range(bx, gx, ntiles);   // XCD bands, see yl_conv_dpp_kernel
+  const int r0 = tr.r0, r1 = tr.r1;
   const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float*>(p.x), 0, (int)((long)p.B * H * W * Cin * 4), 0x00020000);
   const bool pre_add = p.res != nullptr && p.act == YL_ACT_NONE;     // (as yl_conv_mfma_kernel: the addend initialises the accumulator)
-  const float lo = (p.act == YL_ACT_RELU || p.act == YL_ACT_RELU6) ? 0.0f : -INFINITY;
-  const float hi = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo = yl_act_lo(p.act), hi = yl_act_hi(p.act);
   // copy role of the lane in copy j: slot 64 j + lane = (pixel P = y * 6 + x of the window, stored quad) -- yl_conv_dpw_kernel's layout
   int cy[3], cx[3], cq[3];
 #pragma unroll
@@ -985,7 +964,7 @@ static const YlConvKernel k3w_kernels[2] = {yl_conv_k3w_kernel<1>, yl_conv_k3w_k
 static hipError_t k3w_go(const YlConvP& p, hipStream_t st) {
   const int KB = p.Cin / 16;                                          // 1 or 2 (yl_launch_conv_k3w)
   const YlConvKernel kern = k3w_kernels[KB - 1];
-  const size_t lds = (size_t)K3W_NW * KB * 192 * 16;
+  const size_t lds = YlK3wLds::bytes(KB);
   const long t = (long)p.B * (p.OH >> 2) * (p.OW >> 2);
   long nb = yl_resident_blocks((const void*)kern, K3W_NW * 64, lds, 2);
   if (nb > (t + K3W_NW - 1) / K3W_NW) nb = (t + K3W_NW - 1) / K3W_NW;
@@ -1012,12 +991,12 @@ hipError_t yl_launch_conv_k3w(const YlConvP& p, hipStream_t st) {
 
 hipError_t yl_dpp_init() {
   hipError_t e = yl_set_lds_cap(s2c_kernel, s2c_lds);
-#define YL_DPQ_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpq_kernel<A, B, C>, dpq_lds_bytes(A, B, C));
+#define YL_DPQ_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpq_kernel<A, B, C>, YlDppLds::dpq(A, B, C).bytes);
   YL_DPQ_SHAPES(YL_DPQ_CAP)
 #undef YL_DPQ_CAP
 #define YL_DPP_CAP(A, B, C)                                                                     \
-  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpw_kernel<A, B, C>, dpw_lds_bytes(A, B, C)); \
-  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpp_kernel<A, B, C>, dpp_lds_bytes(A, B, C));
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpw_kernel<A, B, C>, YlDppLds::dpw(A, B, C).bytes); \
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpp_kernel<A, B, C>, YlDppLds::dpp(A, B, C).bytes);
   YL_DPP_SHAPES(YL_DPP_CAP)
 #undef YL_DPP_CAP
   return e;

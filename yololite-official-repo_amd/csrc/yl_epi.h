@@ -12,6 +12,25 @@ struct YlPix {
   size_t lin;        // linear output pixel index (clamped)
 };
 
+// the lane's pixel from its linear index `lin` over the M = B * ohw output pixels of an OW-wide grid; lanes past the last pixel
+// (the padding of the last tile) are clamped to it.  want_coords = false leaves b / oy / ox at 0 (two divisions saved where no
+// epilogue reads them)
+__device__ __forceinline__ YlPix yl_pix(size_t lin, int M, int ohw, int OW, bool want_coords = true) {
+  YlPix px;
+  px.valid = lin < (size_t)M;
+  if (!px.valid) lin = (size_t)M - 1;
+  px.lin = lin;
+  px.b = 0; px.oy = 0; px.ox = 0;
+  if (want_coords) {
+    const int b = (int)(lin / ohw);
+    const int rem = (int)(lin - (size_t)b * ohw);
+    px.b = b;
+    px.oy = rem / OW;
+    px.ox = rem - px.oy * OW;
+  }
+  return px;
+}
+
 // store 4 consecutive channels / one channel at ELEMENT offset e of the layer's output tensor.  In the fp16-storage unit the
 // tensor is fp16 unless the layer says out_f32 (head outputs -> the fp32 detection levels, the mask prototypes)
 __device__ __forceinline__ void yl_out4(const YlConvP& p, size_t e, f32x4 v) {

@@ -302,6 +302,36 @@ inline int yl_resident_blocks(const void* kernel, int threads, size_t lds, int c
   return nb * YL_NUM_CU;
 }
 
+// grid of a kernel that deals its work in XCD bands (yl_dev.h: yl_band_split / yl_xcd_range): the co-resident count rounded down
+// to a multiple of 8, never below 8 (yl_resident_blocks returns multiples of YL_NUM_CU: the floor only says that no grid is 0 --
+// ADVICE r05), shrunk in steps of 8 while a whole step of workgroups would find no item
+inline int yl_band_grid(int resident, long items) {
+  int gx = resident & ~7;
+  if (gx < 8) gx = 8;
+  while (gx > 8 && gx - 8 >= items) gx -= 8;
+  return gx;
+}
+
+// blocks of a level-batched launch (YlConvMulti) whose kernel deals tiles to waves: the co-resident count shared between the
+// problems in proportion to their tiles, each share a multiple of 8 (XCD bands), at least 8 and at most one workgroup per
+// `per_tile_cap` tiles.  Sets blk0 / nblk of every problem (nblk = 0 for a single one: the whole grid) and returns the grid.
+inline int yl_multi_shares(YlConvMulti& m, const long* tiles, int resident, int per_tile_cap) {
+  long total = 0;
+  for (int k = 0; k < m.n; ++k) total += tiles[k];
+  int at = 0;
+  for (int k = 0; k < m.n; ++k) {
+    long g = ((long)resident * tiles[k] / total + 7) & ~7L;
+    const long cap = ((tiles[k] + per_tile_cap - 1) / per_tile_cap + 7) & ~7L;
+    if (g > cap) g = cap;
+    if (g < 8) g = 8;
+    m.p[k].blk0 = at;
+    m.p[k].nblk = (int)g;
+    at += (int)g;
+  }
+  if (m.n == 1) m.p[0].nblk = 0;
+  return at;
+}
+
 // Launchers and LDS-limit passes that exist once per precision mode: fp32 (no suffix), _bf16 (bf16-MFMA: second compilation of
 // yl_conv.hip / yl_convc.hip / yl_stemblock.hip with -DYL_BF16=1, see yl_lp.h), _f16 (fp16-MFMA: + -DYL_F16=1, option "mfma_f16")
 // and _f16s (fp16 STORAGE: + -DYL_F16S=1, option "store_f16": YlConvP's activation pointers are _Float16* in those units, same

@@ -56,19 +56,30 @@
 #define SB_NCH (SB_NSEG * SB_SP / 4)       // 16-byte chunks: 297
 #define SB_NSTG ((SB_NCH + 63) / 64)       // LDS-DMA instructions (64 lanes x 16 bytes) per tile: 5
 #define SB_NSTG1 ((SB_NSEG * SB_SP + 63) / 64)   // dword-granular rows (image-border tiles): 19
+// dynamic LDS of yl_stemblock_kernel (offsets in floats): per wave its [5][17][P1] patch + the staged input of the tile's new
+// pixels ([33 segments][36 columns] + tail of the 5th KB) | [9][NT1][NT2][64] float4 conv2 weights | [NT2][NT3][64] float4 conv3 weights
+struct YlSbLds {
+  static constexpr size_t LIMIT = 160 * 1024;
+  int patch_f, wave_f;                                               // floats per wave patch, per wave region
+  size_t w2, w3, bytes;
+  constexpr __host__ __device__ YlSbLds(int NT1, int NT2, int NT3, int NWV)
+      : patch_f(SB_NPATCH * (NT1 * 16 + 4)), wave_f(patch_f + SB_NSTG * 256), w2((size_t)NWV * wave_f),
+        w3(w2 + (size_t)9 * NT1 * NT2 * 256), bytes((w3 + (size_t)NT2 * NT3 * 256) * 4) {}
+};
+
 template <int NT1 /*C1/16*/, int NT2 /*ceil(C2/16)*/, int NT3 /*ceil(C3/16), 0 = no 1x1*/, int NWV /*waves per workgroup*/>
 __global__ __launch_bounds__(NWV * 64, 2) void yl_stemblock_kernel(YlConvP p) {
   constexpr int C1 = NT1 * 16, P1 = C1 + 4, KS = 7, KB1 = NT1;
-  constexpr int PATCH_F = SB_NPATCH * P1;                            // floats per wave patch
-  constexpr int WAVE_F = PATCH_F + SB_NSTG * 256;                     // + the staged input of the tile's new pixels
+  constexpr YlSbLds L(NT1, NT2, NT3, NWV);
+  constexpr int PATCH_F = L.patch_f, WAVE_F = L.wave_f;
   extern __shared__ __attribute__((aligned(16))) float sb_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kq = lane >> 4, pl = lane & 15;
-  float* patch = sb_lds + wave * WAVE_F;                             // [5][17][P1], wave private
-  float* stage = patch + PATCH_F;                                    // [33 segments][36 columns] (+ tail of the 5th KB)
-  f32x4* w2l = reinterpret_cast<f32x4*>(sb_lds + NWV * WAVE_F);
-  f32x4* w3l = w2l + 9 * KB1 * NT2 * 64;
+  float* patch = sb_lds + wave * WAVE_F;                             // wave private
+  float* stage = patch + PATCH_F;
+  f32x4* w2l = reinterpret_cast<f32x4*>(sb_lds + L.w2);
+  f32x4* w3l = reinterpret_cast<f32x4*>(sb_lds + L.w3);
 
   // ---- once per block: stem A fragments -> registers, conv2 / conv3 weights -> LDS
   float wa[KS][NT1];
@@ -150,9 +161,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemblock_kernel(YlConvP p) {
 #pragma unroll
   for (int nt = 0; nt < NT2; ++nt) bias2[nt] = yl_ld4(p.b2 + nt * 16 + 4 * kq);
   // ReLU-family activations as branch-free clamps (SiLU is rejected for this op at yl_create)
-  const float lo1 = (p.act == YL_ACT_NONE) ? -INFINITY : 0.0f, hi1 = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float lo2 = (p.act2 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi2 = (p.act2 == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float lo3 = (p.act3 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo1 = (p.act == YL_ACT_NONE) ? -INFINITY : 0.0f, hi1 = yl_act_hi(p.act);
+  const float lo2 = (p.act2 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi2 = yl_act_hi(p.act2);
+  const float lo3 = (p.act3 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi3 = yl_act_hi(p.act3);
   auto clamp4 = [](f32x4 v, float lo, float hi) { return yl_clamp4(v, lo, hi); };
   f32x4 bias3[NT3 > 0 ? NT3 : 1];
 #pragma unroll
@@ -436,12 +447,19 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemblock_kernel(YlConvP p) {
 #define SD_NCH (SD_NSEG * SD_SP / 4)
 #define SD_NSTG ((SD_NCH + 63) / 64)
 #define SD_NSTG1 ((SD_NSEG * SD_SP + 63) / 64)
+// dynamic LDS of yl_stemdw_kernel (floats): per wave its [10][10][P1] patch + the stage.  The stage holds exactly the 63 x 24
+// staged floats (the last copy is masked to its 58 live lanes): 20448 B per wave, so that TWO 4-wave workgroups fit the 160 KiB
+// of a CU (with whole 1 KiB copies: 2 x 82176 B = 512 B too many -- one wave per SIMD).  The limit is the exact size
+struct YlSdLds {
+  static constexpr int P1 = 32 + 4;                                  // patch pixel pitch: the stem's 32 channels + 4
+  static constexpr int PATCH_F = SD_NP * P1, WAVE_F = PATCH_F + SD_NSEG * SD_SP;
+  static constexpr __host__ __device__ size_t bytes(int NWV) { return (size_t)NWV * WAVE_F * 4; }
+};
+
 template <int NT3 /*ceil(C3/16)*/, int NWV>
 __global__ __launch_bounds__(NWV * 64, 2) void yl_stemdw_kernel(YlConvP p) {
-  constexpr int NT1 = 2, C1 = 32, P1 = C1 + 4, KS = 7;
-  // the stage holds exactly the 63 x 24 staged floats (the last copy is masked to its 58 live lanes): 20448 B per wave, so that
-  // TWO 4-wave workgroups fit the 160 KiB of a CU (with whole 1 KiB copies: 2 x 82176 B = 512 B too many -- one wave per SIMD)
-  constexpr int PATCH_F = SD_NP * P1, WAVE_F = PATCH_F + SD_NSEG * SD_SP;
+  constexpr int NT1 = 2, C1 = 32, P1 = YlSdLds::P1, KS = 7;
+  constexpr int PATCH_F = YlSdLds::PATCH_F, WAVE_F = YlSdLds::WAVE_F;
   extern __shared__ __attribute__((aligned(16))) float sb_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -515,25 +533,16 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemdw_kernel(YlConvP p) {
     mdst[m] = qq * P1 + 4 * kq;
     mrc[m] = (q < SD_NP ? 0 : (1 << 16)) | (r << 8) | c;
   }
-  const float lo1 = (p.act == YL_ACT_NONE) ? -INFINITY : 0.0f, hi1 = (p.act == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float lo2 = (p.act2 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi2 = (p.act2 == YL_ACT_RELU6) ? 6.0f : INFINITY;
-  const float lo3 = (p.act3 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi3 = (p.act3 == YL_ACT_RELU6) ? 6.0f : INFINITY;
+  const float lo1 = (p.act == YL_ACT_NONE) ? -INFINITY : 0.0f, hi1 = yl_act_hi(p.act);
+  const float lo2 = (p.act2 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi2 = yl_act_hi(p.act2);
+  const float lo3 = (p.act3 == YL_ACT_NONE) ? -INFINITY : 0.0f, hi3 = yl_act_hi(p.act3);
   const int ty = pl >> 3, tx = pl & 7;                               // lane's pixel inside an output m-tile (2 rows x 8 columns)
   const int lr = (ty * SD_P + tx) * P1 + 4 * kq;                     // lane part of the patch read offset (+ (2 j + dy) rows, dx, kb)
   const int C3 = p.C3;
   const int tpr = (p.OW + SD_T - 1) / SD_T, tpc = (p.OH + SD_T - 1) / SD_T;
   const int tiles_img = tpr * tpc, ntiles = p.B * tiles_img;
-  int r0, r1;                                                        // XCD bands (gridDim.x % 8 == 0), contiguous range per workgroup
-  {
-    const int gx = gridDim.x, bx = blockIdx.x;
-    if ((gx & 7) == 0) {
-      const int x = bx & 7, j = bx >> 3, nj = gx >> 3;
-      const long b0 = ((long)ntiles * x) >> 3, b1 = ((long)ntiles * (x + 1)) >> 3;
-      r0 = (int)(b0 + ((b1 - b0) * j) / nj); r1 = (int)(b0 + ((b1 - b0) * (j + 1)) / nj);
-    } else {
-      r0 = (int)(((long)ntiles * bx) / gx); r1 = (int)(((long)ntiles * (bx + 1)) / gx);
-    }
-  }
+  const YlTileRange tr = yl_band_range(blockIdx.x, gridDim.x, ntiles);   // XCD bands (gridDim.x % 8 == 0), contiguous range per workgroup
+  const int r0 = tr.r0, r1 = tr.r1;
   const float* const xnet = reinterpret_cast<const float*>(p.x);     // the network input: fp32 NCHW in every build
   const float* const zf = reinterpret_cast<const float*>(p.zeros);
   auto gather = [&](int tile) {                                      // stage the input block under `tile`'s stem patch
@@ -673,7 +682,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemdw_kernel(YlConvP p) {
 // yl_stemdw_kernel<NT3, 4 waves per workgroup>: one or two n-tiles out of the 1x1, as [C3 > 16]
 #define SD_NWV 4
 static const YlConvKernel sd_kernels[2] = {yl_stemdw_kernel<1, SD_NWV>, yl_stemdw_kernel<2, SD_NWV>};
-static constexpr size_t sd_lds = (size_t)SD_NWV * (SD_NP * 36 + SD_NSEG * SD_SP) * 4;               // 81792 B: two workgroups per CU
+static constexpr size_t sd_lds = YlSdLds::bytes(SD_NWV);                                           // 81792 B: two workgroups per CU
 
 static hipError_t sd_go(const YlConvP& p, hipStream_t st) {
   constexpr int NWV = SD_NWV;
@@ -699,11 +708,9 @@ hipError_t yl_launch_stemdw(const YlConvP& p, hipStream_t st) {
 struct SbForm { YlConvKernel kern; int nwv; size_t lds; };
 template <int NT1, int NT2, int NT3>
 static SbForm sb_form() {
-  constexpr int P1 = NT1 * 16 + 4;
-  constexpr size_t wave_b = (size_t)(SB_NPATCH * P1 + SB_NSTG * 256) * 4;
-  constexpr size_t w_b = (size_t)(9 * NT1 * NT2 + NT2 * NT3) * 1024;
-  if constexpr (8 * wave_b + w_b <= 160 * 1024) return {yl_stemblock_kernel<NT1, NT2, NT3, 8>, 8, 8 * wave_b + w_b};
-  else return {yl_stemblock_kernel<NT1, NT2, NT3, 4>, 4, 4 * wave_b + w_b};
+  constexpr size_t lds8 = YlSbLds(NT1, NT2, NT3, 8).bytes, lds4 = YlSbLds(NT1, NT2, NT3, 4).bytes;
+  if constexpr (lds8 <= YlSbLds::LIMIT) return {yl_stemblock_kernel<NT1, NT2, NT3, 8>, 8, lds8};
+  else return {yl_stemblock_kernel<NT1, NT2, NT3, 4>, 4, lds4};
 }
 // instantiated: (C1 / 16, ceil(C2 / 16), ceil(C3 / 16) -- 0 = no 1x1)
 #define YL_SB_SHAPES_OF(X, NT1) X(NT1, 1, 0) X(NT1, 1, 1) X(NT1, 2, 0) X(NT1, 2, 2) X(NT1, 1, 2) X(NT1, 2, 1)
@@ -746,7 +753,7 @@ static hipError_t sb_launch(const YlConvP& p0, hipStream_t st, const SbForm& f) 
 
 hipError_t yl_stemblock_init() {
   hipError_t e = yl_set_lds_cap(sd_kernels, sd_lds);
-#define YL_SB_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(sb_form<A, B, C>().kern, 160 * 1024);
+#define YL_SB_CAP(A, B, C) if (e == hipSuccess) e = yl_set_lds_cap(sb_form<A, B, C>().kern, YlSbLds::LIMIT);
   YL_SB_SHAPES(YL_SB_CAP)
 #undef YL_SB_CAP
   return e;
