@@ -305,7 +305,12 @@ yl_status yl_set_option(yl_ctx* ctx, const char* name, int32_t value);
  * scratch and level buffers are allocated filled with 0xFF bytes (a NaN in fp32 and fp16) instead of zeros and refilled
  * with them, on the call's stream, at the start of every yl_forward* / yl_predict call: no result may depend on them),
  * 19: a UIB projection and the next block's 1x1 expansion as two launches instead of one chained launch
- * (yl_conv_dwx_kernel).  Read-only: "chain_launches", the number of chained launches the context has enqueued. */
+ * (yl_conv_dwx_kernel), 20: the fused head launch without the objectness skip -- every 4x4 tile runs the whole head-output
+ * GEMM and the class scan, also where no candidate's sigmoid(objectness) exceeds conf_thr (same results bit for bit).
+ * Read-only: "chain_launches", the number of chained launches the context has enqueued; "head_skip_launches", the number
+ * of fused head launches enqueued in the objectness-skip form; "head_skipped_tiles", the tiles those launches skipped since
+ * "head_skip_count" (0/1, default 0, settable) was first switched on -- the kernel counts only while it is 1, and reading the
+ * count waits for the device. */
 yl_status yl_get_option(const yl_ctx* ctx, const char* name, int32_t* value);
 /* Host-side query, no device needed: would yl_create accept a fused inverted-residual block (yl_layer with c2 > 0:
  * 1x1 expand c_in -> c_mid, depthwise dw_k x dw_k stride dw_stride, 1x1 project c_mid -> c_out) producing an

@@ -124,6 +124,9 @@ struct yl_ctx {
                       // latency, -0.7 % throughput at B = 64 (measured, edge_n) -> off by default, the pip API turns it on
   int opt_dev = 0;    // developer kernel-selection word (YL_DEV_*, "dev_select"); rides in every YlConvP
   int chain_launches = 0;   // yl_conv_dwx_kernel launches enqueued so far (yl_get_option "chain_launches", read-only)
+  int head_skip_launches = 0;       // fused head launches enqueued in the objectness-skip form ("head_skip_launches", read-only)
+  int opt_head_skip_count = 0;      // "head_skip_count": those launches count their skipped tiles into head_skip_cnt
+  unsigned* head_skip_cnt = nullptr;   // device counter ("head_skipped_tiles", read-only), allocated when the option is first set
   int opt_bf16 = 0;   // reduced-precision MFMA mode: 1 = conv / stem-block launches use the bf16-MFMA builds, 2 = the fp16-MFMA
                       // builds (fp32 storage, fp32 accumulate either way); 0 = fp32 (the parity path)
   // batch chunks run on `opt_streams` internal streams (fork/join around every call): the
@@ -776,6 +779,8 @@ struct LayerRun {
     p.dec_raw = c->NM > 0 ? 1 : 0;                          // mask coefficients are read from the raw rows
     p.dec_stride = (float)((double)c->img_size / (double)S);   // utils_ms.py:71, as fill_levels
     p.dec_hi = (float)(c->img_size - 1);
+    p.dec_conf = fuse->conf_thr;
+    p.dec_skip_cnt = c->opt_head_skip_count ? c->head_skip_cnt : nullptr;
   }
   void params(size_t i, YlConvP& p) const {
     layer_params(c, c->layers[i], b0, B, x, level_out, p);
@@ -896,7 +901,11 @@ yl_status emit(LayerRun& r, const LaunchStep& s, bool* refused) {
         ps[q].w3p = O.wp; ps[q].b3 = O.bias; ps[q].C3 = O.d.cout;
         r.decode_targets(i + n + q, ps[q]);
       }
-      e = yl_launch_conv_dpp(ps, (int)n, r.st);
+      {
+        bool skip_form = false;
+        e = yl_launch_conv_dpp(ps, (int)n, r.st, &skip_form);
+        if (e == hipSuccess && skip_form) ++c->head_skip_launches;
+      }
       break;
     case F_DPQ_EXPAND:
       r.params(i, ps[0]);
@@ -1375,6 +1384,7 @@ void yl_destroy(yl_ctx* c) {
   free_act(c);
   free_post_ws(c);
   hipFree(c->ws_nms_clsws);
+  hipFree(c->head_skip_cnt);
   hipFree(c->ws_loss_keys); hipFree(c->ws_loss_neg); hipFree(c->ws_loss_pi); hipFree(c->ws_loss_pos);
   for (int i = 0; i < 4; ++i) {
     if (c->work[i]) hipStreamDestroy(c->work[i]);
@@ -1811,6 +1821,14 @@ yl_status yl_set_option(yl_ctx* c, const char* name, int32_t value) {
   if (!strcmp(name, "streams")) { c->opt_streams = value < 1 ? 1 : (value > 4 ? 4 : value); drop_graph(c); return YL_OK; }
   if (!strcmp(name, "split_k")) { c->opt_split_k = value ? 1 : 0; drop_graph(c); return YL_OK; }
   if (!strcmp(name, "dev_select")) { c->opt_dev = value & (int)YL_DEV_MASK; drop_graph(c); return YL_OK; }
+  if (!strcmp(name, "head_skip_count")) {   // (the counter pointer rides in the launch parameters: cached graphs are dropped)
+    if (value && !c->head_skip_cnt) {
+      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, hipMalloc((void**)&c->head_skip_cnt, sizeof(unsigned)));
+      HIPCHK(c, hipMemset(c->head_skip_cnt, 0, sizeof(unsigned)));
+    }
+    c->opt_head_skip_count = value ? 1 : 0; drop_graph(c); return YL_OK;
+  }
   return fail(c, YL_ERR_INVALID, std::string("unknown option ") + name);
 }
 
@@ -1821,9 +1839,19 @@ yl_status yl_get_option(const yl_ctx* c, const char* name, int32_t* value) {
       {"pre_norm", c->opt_pre_norm}, {"reuse_slots", c->opt_reuse}, {"hybrid", c->opt_hybrid}, {"batch_levels", c->opt_batch_levels},
       {"fuse_decode", c->opt_fuse_decode}, {"fuse_head", c->opt_fuse_head}, {"winograd", c->opt_winograd}, {"lanes", c->opt_lanes},
       {"tile_m", c->opt_tile_m}, {"streams", c->opt_streams}, {"dev_select", c->opt_dev}, {"split_k", c->opt_split_k},
-      {"chain_launches", c->chain_launches}};
+      {"chain_launches", c->chain_launches}, {"head_skip_launches", c->head_skip_launches},
+      {"head_skip_count", c->opt_head_skip_count}};
   for (const auto& t : tab)
     if (!strcmp(name, t.n)) { *value = t.v; return YL_OK; }
+  if (!strcmp(name, "head_skipped_tiles")) {   // tiles skipped since "head_skip_count" was first set (waits for the device)
+    unsigned v = 0;
+    if (c->head_skip_cnt &&
+        (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+         hipMemcpy(&v, c->head_skip_cnt, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess))
+      return YL_ERR_HIP;
+    *value = (int32_t)(v & 0x7fffffffu);
+    return YL_OK;
+  }
   return YL_ERR_INVALID;
 }
 

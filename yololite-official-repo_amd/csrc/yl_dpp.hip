@@ -207,7 +207,26 @@ __global__ __launch_bounds__(DPP_NW * 64, DPP_WPE) void yl_conv_dpp_kernel(YlCon
 //            fma chain of those taps -- no LDS round trip is waited for in front of an MFMA.
 // Same tap order, fma chain, k order and epilogue as yl_conv_dpp_kernel: BIT-IDENTICAL to it ("dev_select" bit 16 keeps
 // the tap-load kernel; tests/test_gpu_parity.py).
-template <int KB /*Cin/16*/, int NT1 /*trunk n-tiles*/, int NT3 /*head-output n-tiles*/>
+//
+// SKIP (the default form under yl_predict; "dev_select" bit 20 keeps SKIP = false, which is the code above unchanged): the only
+// reader of the candidates is yl_nms_kernel, whose first act is `scores[n] > conf_thr`, and objectness alone rules most tiles
+// out.  Per tile: the trunk results are finished in place (bias + clamp), then ONLY the MFMA groups of n-tiles 0 and 1 of the
+// head-output GEMM run, over all NT1 k-blocks in ascending order (n-tile 1 rides along as the second accumulator chain of the
+// group form; n-tile 0 alone in one 24-deep chain measured 0.4 % ahead on the headline, under the bar of a gain: DESIGN section 3); objectness is channel 4 = element 0 of n-tile 0 in the kq-1 lanes.  obj = yl_sigmoid(logit + bias) is the
+// epilogue's own expression on the epilogue's own input, and every dec_mode's score is bounded by it:
+//   MAIN / EVAL, C > 1   score = obj * best or -inf (NaN class logit); best = 1 / (1 + expf(-x)) <= 1 and rounding is monotonic,
+//                        so obj * best <= obj;
+//   FALLBACK             the same product (C == 1: obj * sigmoid(class logit)), or -inf for boxes under two pixels;
+//   C == 1 otherwise     score = obj -- and NT3 == 2 there: nothing to skip, SKIP is only instantiated for NT3 > 2.
+// So a tile in which no pixel has obj > dec_conf (a NaN objectness compares false, as its NaN score does in the NMS) holds no
+// survivor: its candidates get score -inf and class 0 (a valid class: poisoned workspaces stay harmless), the boxes stay
+// unwritten (yl_nms_kernel / yl_nms_merge_kernel gather boxes[idx] of survivors only, yl_masks* read boxes[keep_idx]), and the
+// remaining (NT3 / 2 - 1) * NT1 groups, the class scan and the box arithmetic do not run.  dec_conf <= 0 never skips (a zero
+// score may pass there).  A kept tile runs the remaining groups kb-major as before: every accumulator sees its products in the
+// same k order, so its row is bit-identical to the SKIP = false form.  The skip branch is wave-uniform and issues two stores
+// (three vector-memory operations with the optional counter) where the epilogue issues three: never more between a window
+// request and its partial vmcnt wait.  Both exits leave A-fragment set 0 holding w1l[0..1] for the next tile's first group.
+template <int KB /*Cin/16*/, int NT1 /*trunk n-tiles*/, int NT3 /*head-output n-tiles*/, bool SKIP = false>
 __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(YlConvMulti mp) {
   int yl_k = 0;
   if (mp.n > 1 && (int)blockIdx.x >= mp.p[1].blk0) yl_k = 1;
@@ -377,6 +396,73 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
 #pragma unroll
     for (int nt = 0; nt < NT3; ++nt) acc3[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
     static_assert(NT3 % 2 == 0 && (KB * G + NT1 * (NT3 / 2)) % 2 == 0, "A-fragment register sets alternate per group");
+    const YlPix pxd[1] = {pxc};
+    if constexpr (SKIP) {
+      // NT1 groups (an even number) in front of the test, NT1 * (NT3 / 2 - 1) behind it: the first group of either part uses set 0
+      static_assert(NT3 > 2 && NT1 % 2 == 0, "the skip form needs n-tiles behind the first group, and an even group count in front of them");
+#pragma unroll
+      for (int kb = 0; kb < NT1; ++kb)
+        acc1[0][kb] = yl_clamp4(acc1[0][kb] + *reinterpret_cast<const f32x4*>(b1l + kb * 16 + 4 * kq), lo1, hi1);
+#pragma unroll
+      for (int kb = 0; kb < NT1; ++kb) {                               // n-tiles 0 and 1 over every k-block
+        const int cur = (KB * G + kb) & 1;
+        if (kb + 1 < NT1) {
+          wq[cur ^ 1][0] = w3l[((kb + 1) * NT3 + 0) * 64 + lane];
+          wq[cur ^ 1][1] = w3l[((kb + 1) * NT3 + 1) * 64 + lane];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+          acc3[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][0][st], acc1[0][kb][st], acc3[0][0], 0, 0, 0);
+          acc3[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][1][st], acc1[0][kb][st], acc3[0][1], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      // objectness of the lane's pixel as the epilogue computes it: channel 4 = element 0 of n-tile 0 in the kq-1 lanes
+      const float conf = p.dec_conf;
+      const float obj = yl_sigmoid(acc3[0][0].x + b3l[4 * kq]);
+      const bool hit = kq == 1 && pxc.valid && obj > conf;
+      if (conf > 0.0f && !__any(hit)) {                                // wave-uniform
+        wq[0][0] = w1l[0 * 64 + lane];                                 // the next tile's first group
+        wq[0][1] = w1l[1 * 64 + lane];
+        if (kq == 0 && pxc.valid) {
+          const size_t o = (size_t)pxc.b * p.dec_N + p.dec_off + pxc.oy * p.OW + pxc.ox;
+          p.dec_scores[o] = -INFINITY;
+          p.dec_cls[o] = 0;
+        }
+        if (p.dec_skip_cnt != nullptr && lane == 0) atomicAdd(p.dec_skip_cnt, 1u);
+      } else {
+        wq[0][0] = w3l[2 * 64 + lane];
+        wq[0][1] = w3l[3 * 64 + lane];
+#pragma unroll
+        for (int kb = 0; kb < NT1; ++kb) {
+#pragma unroll
+          for (int g = 1; g < NT3 / 2; ++g) {                          // the remaining groups, A fragments one group ahead
+            const int cur = (kb * (NT3 / 2 - 1) + g - 1) & 1;
+            if (g + 1 < NT3 / 2) {
+              wq[cur ^ 1][0] = w3l[(kb * NT3 + 2 * g + 2) * 64 + lane];
+              wq[cur ^ 1][1] = w3l[(kb * NT3 + 2 * g + 3) * 64 + lane];
+            } else if (kb + 1 < NT1) {
+              wq[cur ^ 1][0] = w3l[((kb + 1) * NT3 + 2) * 64 + lane];
+              wq[cur ^ 1][1] = w3l[((kb + 1) * NT3 + 3) * 64 + lane];
+            } else {                                                   // the next tile's first group
+              wq[cur ^ 1][0] = w1l[0 * 64 + lane];
+              wq[cur ^ 1][1] = w1l[1 * 64 + lane];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int st = 0; st < 4; ++st) {
+              acc3[0][2 * g] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][0][st], acc1[0][kb][st], acc3[0][2 * g], 0, 0, 0);
+              acc3[0][2 * g + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wq[cur][1][st], acc1[0][kb][st], acc3[0][2 * g + 1], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT3; ++nt) acc3[0][nt] += *reinterpret_cast<const f32x4*>(b3l + nt * 16 + 4 * kq);
+        yl_epi_decode<NT3, 1, true, true>(p, acc3, pxd, 0, kq, lane);
+      }
+    } else {
 #pragma unroll
     for (int kb = 0; kb < NT1; ++kb) {
       f32x4 hq[1];
@@ -403,10 +489,10 @@ __global__ __launch_bounds__(DPW_NW * 64, DPW_NW / 4) void yl_conv_dpw_kernel(Yl
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    const YlPix pxd[1] = {pxc};
 #pragma unroll
     for (int nt = 0; nt < NT3; ++nt) acc3[0][nt] += *reinterpret_cast<const f32x4*>(b3l + nt * 16 + 4 * kq);
     yl_epi_decode<NT3, 1, true, true>(p, acc3, pxd, 0, kq, lane);
+    }
     tile = next;
     cs = ns; pxc = pxn;
   }
@@ -785,7 +871,7 @@ bool yl_dpp_supported(int cin, int cout, int c3, int oh, int ow) {
 }
 
 template <int KB, int NT1, int NT3>
-static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st) {
+static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st, bool* skip_form) {
   constexpr size_t lds = YlDppLds::dpp(KB, NT1, NT3).bytes, ldsw = YlDppLds::dpw(KB, NT1, NT3).bytes;
   // window-in-LDS form (round 6): depthwise pad 1 on every side; "dev_select" bit 16 keeps the tap-load kernel
   bool win = !(ps[0].dev & YL_DEV_DPW_OFF);
@@ -809,6 +895,16 @@ static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st) {
     m.p[k].nblk = (int)nb;
     at += (int)nb;
   }
+  // objectness-skip form: whenever the launch decodes for yl_predict (the launcher accepts nothing else) and "dev_select" bit
+  // 20 is clear; the kernel itself never skips at a threshold <= 0
+  const bool skip = win && NT3 > 2 && !(ps[0].dev & YL_DEV_HEAD_SKIP_OFF);
+  if (skip_form) *skip_form = skip;
+  if constexpr (NT3 > 2) {
+    if (skip) {
+      hipLaunchKernelGGL((yl_conv_dpw_kernel<KB, NT1, NT3, true>), dim3((unsigned)at), dim3(DPW_NW * 64), ldsw, st, m);
+      return hipGetLastError();
+    }
+  }
   if (win) hipLaunchKernelGGL((yl_conv_dpw_kernel<KB, NT1, NT3>), dim3((unsigned)at), dim3(DPW_NW * 64), ldsw, st, m);
   else hipLaunchKernelGGL((yl_conv_dpp_kernel<KB, NT1, NT3>), dim3((unsigned)at), dim3(DPP_NW * 64), lds, st, m);
   return hipGetLastError();
@@ -816,7 +912,8 @@ static hipError_t dpp_go(const YlConvP* ps, int n, hipStream_t st) {
 
 // n <= 4 head branches of identical configuration (ps[k]: the trunk layer's parameters with w3p / b3 / C3 and the dec_*
 // fields of its head-output layer).  hipErrorNotSupported: shape not instantiated (the two-launch form runs).
-hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st) {
+hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st, bool* skip_form) {
+  if (skip_form) *skip_form = false;
   if (n < 1 || n > 4) return hipErrorNotSupported;
   const YlConvP& q = ps[0];
   if (q.k != 1 || q.dw_k != 3 || q.dw_stride != 1 || q.C1 > 0 || q.res || q.up || !q.w3p || !q.dec_boxes || q.dec_raw ||
@@ -828,7 +925,7 @@ hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st) {
         (size_t)ps[k].B * ps[k].H * ps[k].W * ps[k].Cin * 4 >= ((size_t)1 << 31))        // (32-bit byte offsets of the window copies)
       return hipErrorNotSupported;
   const int kb = q.Cin / 16, nt1 = q.N / 16, nt3 = (q.C3 + 15) / 16;
-#define YL_DPP_RUN(A, B, C) if (kb == A && nt1 == B && nt3 == C) return dpp_go<A, B, C>(ps, n, st);
+#define YL_DPP_RUN(A, B, C) if (kb == A && nt1 == B && nt3 == C) return dpp_go<A, B, C>(ps, n, st, skip_form);
   YL_DPP_SHAPES(YL_DPP_RUN)
 #undef YL_DPP_RUN
   return hipErrorNotSupported;
@@ -996,6 +1093,7 @@ hipError_t yl_dpp_init() {
 #undef YL_DPQ_CAP
 #define YL_DPP_CAP(A, B, C)                                                                     \
   if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpw_kernel<A, B, C>, YlDppLds::dpw(A, B, C).bytes); \
+  if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpw_kernel<A, B, C, true>, YlDppLds::dpw(A, B, C).bytes); \
   if (e == hipSuccess) e = yl_set_lds_cap(yl_conv_dpp_kernel<A, B, C>, YlDppLds::dpp(A, B, C).bytes);
   YL_DPP_SHAPES(YL_DPP_CAP)
 #undef YL_DPP_CAP

@@ -152,6 +152,11 @@ struct YlConvP {
   int dec_mode, dec_center, dec_wh;
   int dec_raw;           // also write the raw rows
   float dec_stride, dec_hi;
+  // fused head launch (yl_conv_dpw_kernel<.., SKIP>): the confidence threshold of the call's NMS -- a 4x4 tile without a
+  // candidate whose sigmoid(objectness) exceeds it gets score -inf and no class GEMM / class scan (score = obj * best <= obj);
+  // dec_skip_cnt: device counter of the skipped tiles, nullptr unless option "head_skip_count" is on
+  float dec_conf;
+  unsigned* dec_skip_cnt;
   // level-batched launches (YlConvMulti): this problem owns blocks [blk0, blk0 + nblk) of grid.x; nblk == 0
   // means the whole grid (single-problem launch)
   int blk0, nblk;
@@ -195,11 +200,12 @@ struct YlConvP {
 #define YL_DEV_POISON (1u << 18)      // workspace poison (isolation tests): activation storage is allocated as 0xFF bytes (a NaN in fp32
                                       // and fp16) and refilled with them at the start of every forward / predict call; no kernel reads it
 #define YL_DEV_CHAIN_OFF (1u << 19)   // UIB projection + next block's 1x1 expansion: two launches instead of yl_conv_dwx_kernel
-#define YL_DEV_MASK 0x3ffffffu        // the bits "dev_select" keeps
+#define YL_DEV_HEAD_SKIP_OFF (1u << 20)   // fused head launch: every tile runs the whole head-output GEMM and the class scan (no objectness skip)
+#define YL_DEV_MASK 0x3ffffffu       // the bits "dev_select" keeps
 static_assert(YL_DEV_MASK <= 0x7fffffffu, "dev_select is stored in an int (and an int field of the graph key)");
 static_assert(((YL_DEV_DW_TILE_OFF | YL_DEV_PWS_OFF | YL_DEV_S2C_OFF | YL_DEV_DWC_ALL | YL_DEV_DWT_OFF | (3u << 5) | (3u << 7) |
                 YL_DEV_KXK_MT2 | YL_DEV_DWT_NOSPLIT | YL_DEV_WINO_V1 | (3u << 12) | YL_DEV_DWL_OFF | YL_DEV_DWL_ALL | YL_DEV_DPW_OFF |
-                YL_DEV_K3W_OFF | YL_DEV_POISON | YL_DEV_CHAIN_OFF) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
+                YL_DEV_K3W_OFF | YL_DEV_POISON | YL_DEV_CHAIN_OFF | YL_DEV_HEAD_SKIP_OFF) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
 
 // squeeze-excite gate (yl_se.hip): fixed-order two-pass spatial mean + the two FCs + sigmoid
 struct YlSeP {
@@ -353,7 +359,8 @@ YL_MODE_PROTOTYPES(_f16)
 YL_MODE_PROTOTYPES(_f16s)
 
 // depthwise 3x3 -> 1x1 -> 1x1 head output + decode as one launch (yl_dpp.hip)
-hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st);
+// *skip_form (optional): the launch went out in the objectness-skip form (yl_conv_dpw_kernel<.., SKIP = true>)
+hipError_t yl_launch_conv_dpp(const YlConvP* ps, int n, hipStream_t st, bool* skip_form = nullptr);
 bool yl_dpp_supported(int cin, int cout, int c3, int oh, int ow);
 hipError_t yl_dpp_init();
 // dense 3x3 stride-2 conv (16 -> 48) + chained 1x1 from an LDS-staged patch (yl_dpp.hip)
