@@ -595,6 +595,106 @@ yl_status yl_track_grow(yl_tracker* t, int32_t new_max_tracks);
 /* synchronises the device; host arrays [num_streams] (either may be NULL) */
 yl_status yl_track_stats(yl_tracker* t, int32_t* ntracks_host, int32_t* overflow_host);
 
+/* ---- the training step's tail (reference tools/train.py:352-359 and ModelEMA.update, :45-57) -----------------
+ * scaler.unscale_, clip_grad_norm_, scaler.step(AdamW | Adam | SGD), scaler.update and ema.update(model) for ALL
+ * tensors of a model as three launches.  A yl_train handle needs no yl_ctx.  fp32, contiguous tensors on one device
+ * only; every tensor may start at any 4-byte boundary (a pointer that does not: YL_ERR_UNSUPPORTED).
+ *
+ * One yl_train_segment per state_dict entry, in state_dict order:
+ *   parameter          param / grad (may be NULL) / state0 / state1 / ema (NULL = no EMA), count elements, group
+ *                      AdamW, Adam: state0 = exp_avg, state1 = exp_avg_sq.  SGD: state0 = momentum_buffer, state1 unused
+ *   YL_TRAIN_SEG_EMA_ONLY  floating buffer (BatchNorm running statistics): param = the model's buffer (read only),
+ *                      ema = the EMA's; no gradient, no state
+ *   YL_TRAIN_SEG_BYTES     non-floating entry (num_batches_tracked): `count` BYTES are copied from param to ema
+ * Update rules: torch 2.10's single-tensor implementations (torch/optim/adam.py, sgd.py; foreach=False, not
+ * capturable, no amsgrad / maximize / dampening), with g = fp32(grad * inv_scale) * clip,
+ * clip = min(1, max_norm / (norm + 1e-6)) or 1 when max_norm <= 0:
+ *   AdamW  p *= 1 - lr*wd;  m += (g - m)(1 - b1);  v = v*b2 + (1 - b2) g*g;
+ *          p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps)
+ *   Adam   g += wd*p, then as AdamW without the decay
+ *   SGD    g += wd*p;  buf = g on the tensor's first applied step, momentum*buf + g afterwards;
+ *          p -= lr * (nesterov ? g + momentum*buf : buf)        (momentum 0: p -= lr*g, the buffer is not touched)
+ *   EMA    ema = ema*d + value*(1 - d), value = the parameter just written, or the model's buffer
+ * Everything after the fp32 unscale product is evaluated in float64 from the fp32 operands and rounded once per
+ * stored value.  `step` is the TENSOR's own count (fp32, device memory), advanced only when that tensor has a
+ * gradient in a step that is not skipped.  Gradients are READ ONLY: unlike torch, the unscaled and clipped values are
+ * not written back into .grad.
+ * Skipped step (amp and a non-finite gradient element): parameters, states and step counts keep their bits; the EMA
+ * and the integer copies still run (the reference calls ema.update after scaler.step regardless); scale *= backoff,
+ * tracker = 0.  Otherwise tracker += 1 and, when it reaches growth_interval, scale *= growth (kept if not finite, as
+ * torch does), tracker = 0.  Without amp the scale is 1, stays 1, and nothing is skipped.
+ * Deterministic: the norm is a float64 sum in an order fixed by the segment table, rounded once to fp32; no atomics;
+ * equal inputs give equal bits. */
+enum { YL_TRAIN_ADAMW = 0, YL_TRAIN_ADAM = 1, YL_TRAIN_SGD = 2 };
+#define YL_TRAIN_SEG_EMA_ONLY 1u
+#define YL_TRAIN_SEG_BYTES 2u
+#define YL_TRAIN_MAX_GROUPS 8
+#define YL_TRAIN_CHUNK_DEFAULT 4096
+#define YL_TRAIN_STATE_WORDS 8
+typedef struct yl_train yl_train;
+typedef struct yl_train_segment {
+  void* param;
+  const void* grad;
+  void* state0;
+  void* state1;
+  void* ema;
+  int64_t count;
+  int32_t group;       /* index into yl_train_hyper.lr / weight_decay, < YL_TRAIN_MAX_GROUPS */
+  uint32_t flags;      /* YL_TRAIN_SEG_* */
+} yl_train_segment;
+typedef struct yl_train_chunk {
+  int32_t seg;         /* row of the segment table */
+  int32_t len;         /* 1..chunk_elems elements  */
+  int64_t off;         /* first element            */
+} yl_train_chunk;
+typedef struct yl_train_cfg {
+  int32_t kind;             /* YL_TRAIN_ADAMW / ADAM / SGD                                               */
+  int32_t amp;              /* 0: scale fixed at 1, no skipping                                          */
+  int32_t growth_interval;  /* torch.amp.GradScaler's arguments                                          */
+  int32_t chunk_elems;      /* 0 = YL_TRAIN_CHUNK_DEFAULT; a multiple of 4                               */
+  float init_scale;
+  double growth_factor, backoff_factor;
+} yl_train_cfg;
+typedef struct yl_train_hyper {     /* passed by value on every step: the scheduler and the EMA warm-up stay on the host */
+  double lr[YL_TRAIN_MAX_GROUPS], weight_decay[YL_TRAIN_MAX_GROUPS];
+  double beta1, beta2, eps;         /* AdamW, Adam   */
+  double momentum;                  /* SGD           */
+  double ema_decay;                 /* d of this step */
+  double max_norm;                  /* <= 0: no clipping (the norm is computed all the same) */
+  int32_t nesterov;
+  int32_t reserved0;
+} yl_train_hyper;
+/* The chunk list of a table whose rows hold counts_host[s] elements: rows in table order, each cut into pieces of at
+ * most chunk_elems (a multiple of 4); every element lies in exactly one chunk.  A pure host function.  Returns the
+ * number of chunks (out_host may be NULL to count), or a negative yl_status (YL_ERR_CAPACITY: more than `capacity`). */
+int64_t yl_train_plan(const int64_t* counts_host, int32_t nseg, int32_t chunk_elems, yl_train_chunk* out_host,
+                      int64_t capacity);
+/* Uploads the segment table and its chunk list, allocates the per-chunk partial buffers and the per-tensor step counts
+ * (zero).  state_dev: YL_TRAIN_STATE_WORDS 4-byte words of device memory, 8-byte aligned, owned by the caller and alive
+ * as long as the handle, so that a framework can view them as its own tensors: word 0 = scale (fp32), 1 = growth
+ * tracker (int32), 2 = norm of the last step (fp32), 3 = found_inf of the last step (int32), 4-7 private.  The call
+ * initialises them (scale = init_scale) and synchronises the device. */
+yl_status yl_train_create(int32_t device, const yl_train_cfg* cfg, const yl_train_segment* segments_host, int32_t nseg,
+                          void* state_dev, yl_train** out);
+void yl_train_destroy(yl_train* t);
+/* grad_ptrs_host[nseg]: this step's gradient of every row (NULL = the tensor takes no part in this step, as a None
+ * .grad in torch; ignored for EMA-only and byte rows).  When any differs from what the device holds, the column is
+ * copied from pinned memory on `stream` (asynchronous; the call waits only if the copy of four uploads ago has not run
+ * yet).  No change: no work. */
+yl_status yl_train_set_grads(yl_train* t, const void* const* grad_ptrs_host, void* stream);
+/* Enqueues three kernels on `stream`: gradient statistics (every gradient read once), one-workgroup reduce (norm,
+ * found_inf, scaler update, step counts), apply (optimizer, EMA, integer copies; reads norm / found_inf / scale from
+ * device memory).  No synchronisation, no copy to the host, no allocation. */
+yl_status yl_train_step(yl_train* t, const yl_train_hyper* hyper, void* stream);
+/* device pointer to the current scale (word 0 of state_dev), for loss * scale without a host round trip */
+float* yl_train_scale_ptr(yl_train* t);
+/* Synchronises the device.  Scale, tracker, norm and found_inf of the last step and steps_host[nseg] (any may be
+ * NULL): for logging, checkpoints and tests. */
+yl_status yl_train_read_state(yl_train* t, float* scale, int32_t* growth_tracker, float* norm, int32_t* found_inf,
+                              float* steps_host);
+/* Synchronises the device.  Resume: scale (> 0; ignored without amp), tracker, steps_host[nseg] (NULL = keep). */
+yl_status yl_train_write_state(yl_train* t, float scale, int32_t growth_tracker, const float* steps_host);
+
 #ifdef __cplusplus
 }
 #endif

@@ -102,6 +102,33 @@ class yl_loss_cfg(C.Structure):
                                  "ar_prior_w", "iou_cost_w", "center_cost_w")]
 
 
+YL_TRAIN_ADAMW, YL_TRAIN_ADAM, YL_TRAIN_SGD = 0, 1, 2
+YL_TRAIN_SEG_EMA_ONLY, YL_TRAIN_SEG_BYTES = 1, 2
+YL_TRAIN_MAX_GROUPS = 8
+YL_TRAIN_CHUNK_DEFAULT = 4096
+YL_TRAIN_STATE_WORDS = 8
+
+
+class yl_train_segment(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("state0", C.c_void_p), ("state1", C.c_void_p),
+                ("ema", C.c_void_p), ("count", C.c_int64), ("group", C.c_int32), ("flags", C.c_uint32)]
+
+
+class yl_train_chunk(C.Structure):
+    _fields_ = [("seg", C.c_int32), ("len", C.c_int32), ("off", C.c_int64)]
+
+
+class yl_train_cfg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("amp", C.c_int32), ("growth_interval", C.c_int32), ("chunk_elems", C.c_int32),
+                ("init_scale", C.c_float), ("growth_factor", C.c_double), ("backoff_factor", C.c_double)]
+
+
+class yl_train_hyper(C.Structure):
+    _fields_ = [("lr", C.c_double * YL_TRAIN_MAX_GROUPS), ("weight_decay", C.c_double * YL_TRAIN_MAX_GROUPS),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("momentum", C.c_double),
+                ("ema_decay", C.c_double), ("max_norm", C.c_double), ("nesterov", C.c_int32), ("reserved0", C.c_int32)]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -152,6 +179,15 @@ SYMBOLS = [
     ("yl_track_update", C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("yl_track_grow", C.c_int32, [_vp, C.c_int32]),
     ("yl_track_stats", C.c_int32, [_vp, _ip, _ip]),
+    ("yl_train_plan", C.c_int64, [C.POINTER(C.c_int64), C.c_int32, C.c_int32, C.POINTER(yl_train_chunk), C.c_int64]),
+    ("yl_train_create", C.c_int32, [C.c_int32, C.POINTER(yl_train_cfg), C.POINTER(yl_train_segment), C.c_int32, _vp,
+                                    C.POINTER(_vp)]),
+    ("yl_train_destroy", None, [_vp]),
+    ("yl_train_set_grads", C.c_int32, [_vp, _vpp, _vp]),
+    ("yl_train_step", C.c_int32, [_vp, C.POINTER(yl_train_hyper), _vp]),
+    ("yl_train_scale_ptr", _vp, [_vp]),
+    ("yl_train_read_state", C.c_int32, [_vp, _fp, _ip, _fp, _ip, _fp]),
+    ("yl_train_write_state", C.c_int32, [_vp, C.c_float, C.c_int32, _fp]),
 ]
 
 _lib = None
