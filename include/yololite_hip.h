@@ -695,6 +695,78 @@ yl_status yl_train_read_state(yl_train* t, float* scale, int32_t* growth_tracker
 /* Synchronises the device.  Resume: scale (> 0; ignored without amp), tracker, steps_host[nseg] (NULL = keep). */
 yl_status yl_train_write_state(yl_train* t, float scale, int32_t growth_tracker, const float* steps_host);
 
+/* ---- trainable detection heads (reference scripts/model/model_v2.py:23-53 make_head, :182-192 _forward_head) -----
+ * Forward and backward of ONE level's head on the device: head_depth blocks of depthwise 3x3 (pad 1, no bias) -> 1x1
+ * (no bias) -> BatchNorm2d -> ReLU, then the box / obj / cls 1x1 convolutions written straight as the level tensor
+ * [B, A, S, S, 5 + C] (anchor-major channels).  A yl_head handle needs no yl_ctx and holds no parameter: every call
+ * reads the caller's tensors in PyTorch layout (fp32, contiguous, any 4-byte boundary), so an optimizer may update them
+ * in place between two calls.  The input x is NHWC [B, S, S, F], 16-byte aligned; F a multiple of 4 (anything else,
+ * and num_masks != 0: YL_ERR_UNSUPPORTED).  fp32 storage and arithmetic; the GEMMs run on v_mfma_f32_16x16x4_f32.
+ * BatchNorm: YL_HEAD_TRAIN normalises with the batch statistics (biased variance, eps 1e-5), updates running_mean /
+ * running_var in place (momentum 0.1, unbiased variance) and adds 1 to num_batches_tracked; without it the running
+ * statistics are used and nothing is updated.  YL_HEAD_SAVE keeps d, z, h of every block and the statistics in the
+ * handle for ONE later yl_head_backward of the same (batch, size); a forward without it drops what is held, runs
+ * every block in one block's buffers and allocates no more than those (saved_bytes / head_depth).
+ * Deterministic: every sum over rows is written as per-tile partials and summed in tile order in float64 by a second
+ * kernel; no floating-point atomics; equal inputs give equal bits. */
+#define YL_HEAD_MAX_DEPTH 4
+#define YL_HEAD_TRAIN 1u
+#define YL_HEAD_SAVE 2u
+typedef struct yl_head yl_head;
+typedef struct yl_head_cfg {
+  int32_t channels;       /* F = fpn_channels */
+  int32_t num_classes;    /* C >= 1 */
+  int32_t num_anchors;    /* A of this level */
+  int32_t head_depth;     /* 1..YL_HEAD_MAX_DEPTH */
+  int32_t num_masks;      /* must be 0: mask-coefficient heads are not implemented */
+  int32_t reserved0;
+} yl_head_cfg;
+typedef struct yl_head_block {      /* trunk.t.block.{0,1,2} */
+  float* dw;                        /* [F][1][3][3] */
+  float* pw;                        /* [F][F][1][1] */
+  float* gamma;                     /* [F] BatchNorm weight */
+  float* beta;                      /* [F] BatchNorm bias */
+  float* running_mean;              /* [F] (ignored in a gradient table) */
+  float* running_var;               /* [F] (ignored in a gradient table) */
+  int64_t* num_batches_tracked;     /* one int64, 8-byte aligned (ignored in a gradient table) */
+} yl_head_block;
+typedef struct yl_head_tensors {    /* the parameters of a head, or where their gradients go (NULL = not wanted) */
+  yl_head_block block[YL_HEAD_MAX_DEPTH];
+  float *box_w, *box_b;             /* out.box [4A][F][1][1], [4A] */
+  float *obj_w, *obj_b;             /* out.obj [A][F][1][1], [A]  */
+  float *cls_w, *cls_b;             /* out.cls [A*C][F][1][1], [A*C] */
+} yl_head_tensors;
+typedef struct yl_head_plan_info {
+  int32_t rows;                       /* M = batch * size * size */
+  int32_t stat_rows, stat_tiles;      /* row reductions (BN statistics, dgamma / dbeta, depthwise weight gradient) */
+  int32_t gemm_rows, gemm_tiles;      /* X.W^T and dY.W: rows per workgroup */
+  int32_t wgrad_rows, wgrad_splits;   /* dY^T.X of a trunk 1x1: rows per split (a multiple of 16), splits */
+  int32_t ograd_rows, ograd_splits;   /* dY^T.X of the output convolutions */
+  int32_t reserved0;
+  int64_t saved_bytes;                /* activations and statistics kept between a YL_HEAD_SAVE forward and backward */
+  int64_t workspace_bytes;            /* two gradient tensors and the partial sums */
+} yl_head_plan_info;
+/* How a (cfg, batch, size) is cut and what it holds.  A pure host function: tile t of a cut covers the rows
+ * [t * rows_per_tile, min(M, (t + 1) * rows_per_tile)), every row exactly once. */
+yl_status yl_head_plan(const yl_head_cfg* cfg, int32_t batch, int32_t size, yl_head_plan_info* out);
+yl_status yl_head_create(int32_t device, const yl_head_cfg* cfg, yl_head** out);
+void yl_head_destroy(yl_head* h);
+/* Enqueues the forward on `stream`: per block 4 launches (5 with YL_HEAD_TRAIN), 1 for the outputs.  The handle's
+ * buffers grow (synchronising the device) when (batch, size) needs more than they hold.  launches (may be NULL): the
+ * number of kernels enqueued.  YL_HEAD_TRAIN with batch * size * size == 1: YL_ERR_INVALID. */
+yl_status yl_head_forward(yl_head* h, const yl_head_tensors* params, const float* x_dev, int32_t batch, int32_t size,
+                          uint32_t flags, float* y_dev, void* stream, int32_t* launches);
+/* Enqueues the backward of the forward the handle holds (YL_ERR_STATE if there is none of this batch and size).
+ * gy_dev: the gradient of the level tensor, [B, A, S, S, 5 + C].  Every non-NULL tensor of `grads` is OVERWRITTEN with
+ * that parameter's gradient; dx_dev (NHWC, 16-byte aligned, or NULL) with the input's.  What nobody asked for is not
+ * computed: the trunk is walked back only to the first block something is wanted of, and `launches` says how far. */
+yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_head_tensors* grads, const float* x_dev,
+                           const float* gy_dev, float* dx_dev, int32_t batch, int32_t size, void* stream,
+                           int32_t* launches);
+/* What the handle holds now (a host function; any out pointer may be NULL): the bytes of its two device buffers and
+ * whether a forward is held for yl_head_backward. */
+yl_status yl_head_held(const yl_head* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+
 #ifdef __cplusplus
 }
 #endif

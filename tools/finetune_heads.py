@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Fit the detection heads of a checkpoint to a label set, everything on the device and without a torch model:
+
+    backbone + FPN frozen in the executor (YOLOLiteHIP.pyramid) -> DetectHeads (forward + backward, csrc/yl_head.hip)
+    -> LossAF(grad=True) -> FusedTrainStep (clip, optimizer, EMA off)
+
+    python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
+                                   [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
+    python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
+
+DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
+`class cx cy w h` (normalised to the image).  Images are read with PIL, letterboxed by the library's preprocess path
+(yl_preprocess), the boxes follow the same geometry.  No augmentation.  With --num-classes other than the
+checkpoint's the heads start freshly initialised (torch's defaults plus the reference's init_detect_bias); otherwise
+they start from the checkpoint.  --synthetic NAME takes a zoo model with seeded synthetic weights and one random batch
+instead of --weights / --data.  The output is a checkpoint {"state_dict", "meta"}: the input's state_dict with the
+`head*.` entries replaced, meta.num_classes / names updated -- tools/infer.py runs it.
+"""
+import argparse
+import copy
+import glob
+import os
+import sys
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import yololite_amd as ya  # noqa: E402
+from yololite_amd.program import synth_state_dict, zoo_meta  # noqa: E402
+
+EXTS = (".jpg", ".jpeg", ".png", ".bmp")
+
+
+def read_dataset(root):
+    """-> [(image path, labels [n] int64, boxes [n,4] normalised cx cy w h)]"""
+    items = []
+    for p in sorted(glob.glob(os.path.join(root, "images", "*"))):
+        if not p.lower().endswith(EXTS):
+            continue
+        lab = os.path.join(root, "labels", os.path.splitext(os.path.basename(p))[0] + ".txt")
+        rows = []
+        if os.path.exists(lab):
+            with open(lab) as f:
+                rows = [[float(v) for v in ln.split()[:5]] for ln in f if len(ln.split()) >= 5]
+        a = np.asarray(rows, np.float64).reshape(-1, 5)
+        items.append((p, a[:, 0].astype(np.int64), a[:, 1:5]))
+    if not items:
+        raise SystemExit(f"no images under {os.path.join(root, 'images')}")
+    return items
+
+
+def load_batch(ctx, items, img_size):
+    """-> x [B,3,S,S] on the device, targets (pixel xyxy in the letterboxed image)"""
+    from PIL import Image
+    images, targets = [], []
+    for path, labels, boxes in items:
+        rgb = np.asarray(Image.open(path).convert("RGB"))
+        images.append(np.ascontiguousarray(rgb[:, :, ::-1]))          # the preprocess path takes BGR, as cv2 reads it
+        h, w = rgb.shape[:2]
+        scale, nh, nw, top, left = ya.letterbox_geometry(h, w, img_size)
+        cx, cy, bw, bh = (boxes[:, i] for i in range(4))
+        xyxy = np.stack([(cx - bw / 2) * w * scale + left, (cy - bh / 2) * h * scale + top,
+                         (cx + bw / 2) * w * scale + left, (cy + bh / 2) * h * scale + top], 1)
+        targets.append({"boxes": torch.from_numpy(xyxy.astype(np.float32)).reshape(-1, 4),
+                        "labels": torch.from_numpy(labels)})
+    x, _ = ya.preprocess_batch(ctx, images, letterbox=True, norm="infer")
+    return x, targets
+
+
+def synthetic_batch(img_size, batch, num_classes, device, seed=0):
+    rs = np.random.RandomState(seed)
+    x = torch.from_numpy(rs.standard_normal((batch, 3, img_size, img_size)).astype(np.float32)).to(device)
+    targets = []
+    for _ in range(batch):
+        n = int(rs.randint(1, 4))
+        c = rs.uniform(0.25, 0.75, (n, 2)) * img_size
+        wh = rs.uniform(0.15, 0.45, (n, 2)) * img_size
+        targets.append({"boxes": torch.from_numpy(np.concatenate([c - wh / 2, c + wh / 2], 1).astype(np.float32)),
+                        "labels": torch.from_numpy(rs.randint(0, num_classes, n).astype(np.int64))})
+    return x, targets
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--weights", default="")
+    ap.add_argument("--data", default="")
+    ap.add_argument("--synthetic", default="", help="zoo model name: synthetic weights and one random batch")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--num-classes", type=int, default=0)
+    ap.add_argument("--names", default="")
+    ap.add_argument("--img-size", type=int, default=0)
+    ap.add_argument("--epochs", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=20, help="--synthetic: steps on the one batch")
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--optimizer", default="adamw", choices=("adamw", "adam", "sgd"))
+    ap.add_argument("--grad-clip", type=float, default=10.0)
+    ap.add_argument("--device", default="cuda:0")
+    a = ap.parse_args()
+    if bool(a.synthetic) == bool(a.weights):
+        raise SystemExit("give either --weights (with --data) or --synthetic NAME")
+    if a.synthetic:
+        meta = zoo_meta(a.synthetic, num_classes=a.num_classes or 3, img_size=a.img_size or 128)
+        sd = synth_state_dict(meta, seed=1)
+    else:
+        if not a.data:
+            raise SystemExit("--weights needs --data")
+        ckpt = torch.load(a.weights, map_location="cpu", weights_only=False)
+        meta, sd = copy.deepcopy(ckpt["meta"] or {}), dict(ckpt["state_dict"])
+    img_size = int(a.img_size or meta.get("img_size", 640))
+    old_nc = int(meta.get("num_classes") or meta["config"]["model"].get("num_classes") or 80)
+    nc = int(a.num_classes or old_nc)
+
+    model = ya.build_model_from_meta(meta)
+    model.load_state_dict(sd)
+    model.to(a.device)
+    if nc == old_nc:
+        heads = ya.DetectHeads.from_state_dict(meta, sd)
+    else:
+        heads = ya.DetectHeads.from_meta(meta, num_classes=nc)
+        print(f"[finetune_heads] {old_nc} -> {nc} classes: heads freshly initialised")
+    heads.to(a.device).train()
+    crit = ya.LossAF(nc, img_size, grad=True)
+    fts = ya.FusedTrainStep(list(heads.parameters()), optimizer=a.optimizer, grad_clip=a.grad_clip, amp=False, lr=a.lr)
+
+    def step(x, targets):
+        feats = model.pyramid(x)                           # frozen trunk: plain tensors, nothing to backpropagate into
+        fts.zero_grad()
+        loss, parts = crit(heads(feats, layout="nhwc"), targets)
+        loss.backward()
+        norm = fts.step()
+        return float(loss), parts, float(norm)
+
+    if a.synthetic:
+        x, targets = synthetic_batch(img_size, min(a.batch, 8), nc, a.device)
+        for i in range(a.steps):
+            loss, parts, norm = step(x, targets)
+            print(f"step {i:3d}  loss {loss:.4f}  box {parts['box']:.4f} obj {parts['obj']:.4f} cls {parts['cls']:.4f}  "
+                  f"|g| {norm:.3f}")
+    else:
+        items = read_dataset(a.data)
+        ctx = model._ctx_for(img_size)
+        for ep in range(a.epochs):
+            order = np.random.RandomState(ep).permutation(len(items))
+            tot, n = 0.0, 0
+            for i in range(0, len(order), a.batch):
+                x, targets = load_batch(ctx, [items[j] for j in order[i:i + a.batch]], img_size)
+                if x.shape[0] * (img_size // 32) ** 2 < 2:
+                    continue                               # BatchNorm needs more than one value per channel
+                loss, _, _ = step(x, targets)
+                tot, n = tot + loss, n + 1
+            print(f"epoch {ep:3d}  mean loss {tot / max(n, 1):.4f}  ({n} batches)")
+
+    out_sd = dict(sd)
+    for k, v in heads.state_dict().items():
+        out_sd[k] = v.detach().cpu()
+    out_sd = {k: (torch.as_tensor(v) if not torch.is_tensor(v) else v) for k, v in out_sd.items()}
+    meta = copy.deepcopy(meta)
+    meta["num_classes"] = nc
+    meta.setdefault("config", {}).setdefault("model", {})["num_classes"] = nc
+    names = [s for s in a.names.split(",") if s]
+    if names and len(names) != nc:
+        raise SystemExit(f"--names has {len(names)} entries for {nc} classes")
+    if names or nc != old_nc or not meta.get("names"):
+        meta["names"] = names or [str(i) for i in range(nc)]
+    torch.save({"state_dict": out_sd, "meta": meta}, a.out)
+    print(f"[finetune_heads] wrote {a.out}")
+
+
+if __name__ == "__main__":
+    main()

@@ -129,6 +129,30 @@ class yl_train_hyper(C.Structure):
                 ("ema_decay", C.c_double), ("max_norm", C.c_double), ("nesterov", C.c_int32), ("reserved0", C.c_int32)]
 
 
+YL_HEAD_MAX_DEPTH = 4
+YL_HEAD_TRAIN, YL_HEAD_SAVE = 1, 2
+
+
+class yl_head_cfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("channels", "num_classes", "num_anchors", "head_depth", "num_masks", "reserved0")]
+
+
+class yl_head_block(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("dw", "pw", "gamma", "beta", "running_mean", "running_var",
+                                          "num_batches_tracked")]
+
+
+class yl_head_tensors(C.Structure):
+    _fields_ = [("block", yl_head_block * YL_HEAD_MAX_DEPTH)] + [
+        (n, C.c_void_p) for n in ("box_w", "box_b", "obj_w", "obj_b", "cls_w", "cls_b")]
+
+
+class yl_head_plan_info(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows", "stat_rows", "stat_tiles", "gemm_rows", "gemm_tiles", "wgrad_rows",
+                                         "wgrad_splits", "ograd_rows", "ograd_splits", "reserved0")] + [
+        ("saved_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -188,6 +212,14 @@ SYMBOLS = [
     ("yl_train_scale_ptr", _vp, [_vp]),
     ("yl_train_read_state", C.c_int32, [_vp, _fp, _ip, _fp, _ip, _fp]),
     ("yl_train_write_state", C.c_int32, [_vp, C.c_float, C.c_int32, _fp]),
+    ("yl_head_plan", C.c_int32, [C.POINTER(yl_head_cfg), C.c_int32, C.c_int32, C.POINTER(yl_head_plan_info)]),
+    ("yl_head_create", C.c_int32, [C.c_int32, C.POINTER(yl_head_cfg), C.POINTER(_vp)]),
+    ("yl_head_destroy", None, [_vp]),
+    ("yl_head_forward", C.c_int32, [_vp, C.POINTER(yl_head_tensors), _vp, C.c_int32, C.c_int32, C.c_uint32, _vp, _vp,
+                                    _ip]),
+    ("yl_head_backward", C.c_int32, [_vp, C.POINTER(yl_head_tensors), C.POINTER(yl_head_tensors), _vp, _vp, _vp,
+                                     C.c_int32, C.c_int32, _vp, _ip]),
+    ("yl_head_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
 ]
 
 _lib = None

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-thirteen translation units (three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+fourteen translation units (three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
 library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
@@ -46,6 +46,8 @@ UNITS = [   # (source, extra flags, object name)
     ("yl_loss.hip", ["-ffp-contract=off"], "yl_loss.o"),
     # training step tail (unscale, clip, optimizer, EMA): every product and sum rounded where it is written
     ("yl_train.hip", ["-ffp-contract=off"], "yl_train.o"),
+    # trainable detection heads (forward and backward): one rounding per written operation outside the MFMAs
+    ("yl_head.hip", ["-ffp-contract=off"], "yl_head.o"),
 ]
 DEPS = ["yl_internal.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 

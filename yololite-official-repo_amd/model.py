@@ -455,6 +455,7 @@ class YOLOLiteHIP:
         # options; set with set_context_options() so that contexts that already exist get them too
         self.context_options: Dict[str, int] = {}
         self._ctxs: Dict[int, tuple] = {}
+        self._pyramid_ctxs: Dict[int, tuple] = {}           # pyramid()'s own contexts, by input size ("reuse_slots" 0)
         self.program: Optional[Program] = None
         self.ctx: Optional[HipContext] = None
         self._sd = None
@@ -489,6 +490,7 @@ class YOLOLiteHIP:
             raise RuntimeError("load_state_dict() first")
         self._device_index = dev.index or 0
         self._ctxs = {}
+        self._pyramid_ctxs = {}
         self.ctx = self._ctx_for(self.program.img_size)
         return self
 
@@ -500,6 +502,10 @@ class YOLOLiteHIP:
         for _, ctx in self._ctxs.values():
             for k, v in opts.items():
                 ctx.set_option(k, int(v))
+        for _, ctx in self._pyramid_ctxs.values():          # the same options, but their slots stay apart
+            for k, v in opts.items():
+                if k != "reuse_slots":
+                    ctx.set_option(k, int(v))
 
     def _ctx_for(self, img_size: int) -> HipContext:
         """The reference module is input-size agnostic (tools/infer.py --img_size); the HIP program is
@@ -539,6 +545,27 @@ class YOLOLiteHIP:
         return outs
 
     forward = __call__
+
+    def pyramid(self, x: torch.Tensor) -> List[torch.Tensor]:
+        """The head inputs of a forward (program.feature_slots["p3"], ...) as NHWC tensors [B,S,S,F], smallest stride
+        first: what headops.DetectHeads takes.  They come from a context of their own that keeps every tensor in its
+        own memory (option "reuse_slots" 0), cached beside the others; the contexts __call__ uses are not touched."""
+        if self.ctx is None:
+            raise RuntimeError("model.to('cuda') first")
+        size = int(x.shape[-1])
+        if size not in self._pyramid_ctxs:
+            p = self.program if size == self.program.img_size else \
+                build_program(self.meta, self._sd, img_size=size, **self._fuse_kw)
+            ctx = HipContext(p.img_size, p.num_classes, p.level_size, p.level_anchors, p, self._device_index)
+            for k, v in self.context_options.items():
+                if k != "reuse_slots":
+                    ctx.set_option(k, v)
+            ctx.set_option("reuse_slots", 0)
+            self._pyramid_ctxs[size] = (p, ctx)
+        p, ctx = self._pyramid_ctxs[size]
+        ctx.forward(x)
+        names = sorted(n for n in p.feature_slots if n.startswith("p"))
+        return [ctx.read_slot(p.feature_slots[n], int(x.shape[0]), p.slots[p.feature_slots[n]]) for n in names]
 
     def forward_decoded(self, x: torch.Tensor, center_mode="v8", wh_mode="softplus"):
         """The reference's exported "decoded" outputs (export/export_onnx.py:283-296) straight from the input."""
