@@ -306,8 +306,10 @@ yl_status yl_set_option(yl_ctx* ctx, const char* name, int32_t value);
  * with them, on the call's stream, at the start of every yl_forward* / yl_predict call: no result may depend on them),
  * 19: a UIB projection and the next block's 1x1 expansion as two launches instead of one chained launch
  * (yl_conv_dwx_kernel), 20: the fused head launch without the objectness skip -- every 4x4 tile runs the whole head-output
- * GEMM and the class scan, also where no candidate's sigmoid(objectness) exceeds conf_thr (same results bit for bit).
- * Read-only: "chain_launches", the number of chained launches the context has enqueued; "head_skip_launches", the number
+ * GEMM and the class scan, also where no candidate's sigmoid(objectness) exceeds conf_thr (same results bit for bit),
+ * 21: two plain 1x1 convs around a tensor nothing else reads as two launches instead of one (yl_conv_pwx_kernel).
+ * Read-only: "chain_launches", the number of chained launches the context has enqueued; "pwx_launches", the number of
+ * 1x1-pair launches (yl_conv_pwx_kernel) enqueued; "head_skip_launches", the number
  * of fused head launches enqueued in the objectness-skip form; "head_skipped_tiles", the tiles those launches skipped since
  * "head_skip_count" (0/1, default 0, settable) was first switched on -- the kernel counts only while it is 1, and reading the
  * count waits for the device. */

@@ -60,6 +60,7 @@ DEV_K3W_OFF = 1 << 17             # small-channel dense 3x3: Winograd / direct k
 DEV_POISON = 1 << 18              # workspace poison (isolation tests): activation storage filled with 0xFF (NaN) before every call
 DEV_CHAIN_OFF = 1 << 19           # UIB projection + next block's 1x1 expansion: two launches instead of yl_conv_dwx_kernel
 DEV_HEAD_SKIP_OFF = 1 << 20       # fused head launch: no objectness skip (every tile runs the whole head-output GEMM and class scan)
+DEV_PWX_OFF = 1 << 21             # 1x1 -> 1x1 pair around a single-reader tensor: two launches instead of yl_conv_pwx_kernel
 DEV_WINO_SHAPE_SHIFT = 12        # yl_conv_wino2_kernel item shape (2 bits): 0 auto, 1 (4,4), 2 (2,7), 3 two m-tiles
 
 _fp = C.POINTER(C.c_float)

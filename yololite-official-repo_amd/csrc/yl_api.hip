@@ -124,6 +124,7 @@ struct yl_ctx {
                       // latency, -0.7 % throughput at B = 64 (measured, edge_n) -> off by default, the pip API turns it on
   int opt_dev = 0;    // developer kernel-selection word (YL_DEV_*, "dev_select"); rides in every YlConvP
   int chain_launches = 0;   // yl_conv_dwx_kernel launches enqueued so far (yl_get_option "chain_launches", read-only)
+  int pwx_launches = 0;     // yl_conv_pwx_kernel launches enqueued so far (yl_get_option "pwx_launches", read-only)
   int head_skip_launches = 0;       // fused head launches enqueued in the objectness-skip form ("head_skip_launches", read-only)
   int opt_head_skip_count = 0;      // "head_skip_count": those launches count their skipped tiles into head_skip_cnt
   unsigned* head_skip_cnt = nullptr;   // device counter ("head_skipped_tiles", read-only), allocated when the option is first set
@@ -313,7 +314,7 @@ int pow2ceil(int v) { int p = 64; while (p < v) p <<= 1; return p; }
 
 // ---- what the next launch is.  One owner: run_layers emits what next_step says, plan_slots groups by it.
 
-enum LaunchForm { F_LAYER, F_BATCHED, F_HEAD_RUN, F_DPQ_EXPAND, F_DPQ_PAIR, F_DWX_CHAIN, F_SPLIT_HEAD };
+enum LaunchForm { F_LAYER, F_BATCHED, F_HEAD_RUN, F_DPQ_EXPAND, F_DPQ_PAIR, F_DWX_CHAIN, F_PW_PAIR, F_SPLIT_HEAD };
 // first: the step's first program layer; width: members of the level-batched run (1..4); layers: program layers consumed
 struct LaunchStep { LaunchForm form; size_t first; int width; int layers; };
 constexpr unsigned form_bit(LaunchForm f) { return 1u << f; }
@@ -413,6 +414,25 @@ bool chain_fusable(const yl_ctx* c, size_t i, size_t lend) {
          O.out_w == T.out_w && yl_dwx_supported(t.cin, t.cout, t.dw_k, t.dw_stride, o.cout, T.out_h, T.out_w);
 }
 
+// Two plain 1x1 convs on one grid as ONE launch (yl_conv_pwx_kernel): layer i writes slot S (bias, ReLU-family activation or
+// none, no other operand), layer i + 1 is its only reader (no residual, upsample addend, gate or head).  S is not written.
+bool pwx_fusable(const yl_ctx* c, size_t i, size_t lend) {
+  if (i + 1 >= lend) return false;
+  const DevLayer& T = c->layers[i];
+  const DevLayer& O = c->layers[i + 1];
+  const yl_layer& t = T.d; const yl_layer& o = O.d;
+  if (t.op != YL_OP_CONV || t.k != 1 || t.stride != 1 || t.dw_k > 0 || t.c2 > 0 || t.c3 > 0 || t.head_level >= 0 ||
+      t.res_slot >= 0 || t.up_slot >= 0 || t.scale_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || t.out_slot < 0 ||
+      c->readers[t.out_slot] != 1)
+    return false;
+  if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.stride != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 ||
+      o.in_slot != t.out_slot || o.cin != t.cout || YL_SMOOTH(o.act) || o.res_slot >= 0 || o.up_slot >= 0 ||
+      o.scale_slot >= 0 || o.in_shift || o.out_slot < 0)
+    return false;
+  return T.in_h == T.out_h && T.in_w == T.out_w && O.in_h == T.out_h && O.in_w == T.out_w && O.out_h == T.out_h &&
+         O.out_w == T.out_w && yl_pwx_supported(t.cin, t.cout, o.cout);
+}
+
 // The forms the options allow a run_layers call (F_LAYER always is): the option tests, here and nowhere else.
 // per_layer: per-layer timing or side lanes; fuse: yl_predict with decode in the head-output epilogue
 unsigned allowed_forms(const yl_ctx* c, bool per_layer, bool fuse) {
@@ -423,11 +443,13 @@ unsigned allowed_forms(const yl_ctx* c, bool per_layer, bool fuse) {
   // fp32 mode, split-K off (its form keeps the two launches), the automatic kernel choice, the depthwise -> 1x1 kernel and the
   // chaining not switched off
   if (!(c->opt_bf16 || c->opt_split_k || c->opt_tile_m || (c->opt_dev & (YL_DEV_CHAIN_OFF | YL_DEV_DWT_OFF)))) f |= form_bit(F_DWX_CHAIN);
+  // the 1x1 pair: the same, its own switch
+  if (!(c->opt_bf16 || c->opt_split_k || c->opt_tile_m || (c->opt_dev & YL_DEV_PWX_OFF))) f |= form_bit(F_PW_PAIR);
   return f;
 }
 
 // The launch that starts at layer i of [.., lend): the first of `forms` (form_bit set) that applies, in the order head run,
-// expand-only dpq, dpq pair, dwx chain, split head, level-batched run, else the single layer.  Without F_BATCHED layer i is
+// expand-only dpq, dpq pair, dwx chain, 1x1 pair, split head, level-batched run, else the single layer.  Without F_BATCHED layer i is
 // looked at on its own, as "batch_levels" 0 does.
 LaunchStep next_step(const yl_ctx* c, size_t i, size_t lend, unsigned forms) {
   if (c->layers[i].d.op != YL_OP_CONV) return {F_LAYER, i, 1, 1};
@@ -439,6 +461,7 @@ LaunchStep next_step(const yl_ctx* c, size_t i, size_t lend, unsigned forms) {
     if (may(F_DPQ_EXPAND) && !pair && expand_fusable(c, i)) return {F_DPQ_EXPAND, i, 1, 1};
     if (may(F_DPQ_PAIR) && pair) return {F_DPQ_PAIR, i, 1, 2};
     if (may(F_DWX_CHAIN) && chain_fusable(c, i, lend)) return {F_DWX_CHAIN, i, 1, 2};
+    if (may(F_PW_PAIR) && pwx_fusable(c, i, lend)) return {F_PW_PAIR, i, 1, 2};
   }
   // head-output convs of a model with mask coefficients, every one packed as two weight images
   if (may(F_SPLIT_HEAD) && c->layers[i].d.head_level >= 0 &&
@@ -456,10 +479,13 @@ void plan_slots(yl_ctx* c, bool reuse) {
   int g = 0;
   // A group is whatever next_step could send out as one launch under ANY setting of the options (a fused launch writes its
   // last layer's output while other tiles still read its first layer's inputs): the level-batched run at i, plus one more
-  // layer when the run's last member, on its own, can head a two-layer step.
+  // layer while the group's last member, on its own, can head a two-layer step.
   for (size_t i = 0; i < NL; ++g) {
     size_t e = i + (size_t)next_step(c, i, NL, form_bit(F_BATCHED)).width;
-    if (next_step(c, e - 1, NL, form_bit(F_DPQ_PAIR) | form_bit(F_DWX_CHAIN)).layers == 2) e = e + 1;
+    // (again from the layer added: with the first pair's form off or refused, its second layer can head a pair of its own --
+    // a dwx chain's expansion and the plain 1x1 behind it as yl_conv_pwx_kernel -- whose output must not lie over the first
+    // layer's output, which that launch reads)
+    while (next_step(c, e - 1, NL, form_bit(F_DPQ_PAIR) | form_bit(F_DWX_CHAIN) | form_bit(F_PW_PAIR)).layers == 2) e = e + 1;
     for (size_t q = i; q < e; ++q) grp[q] = g;
     i = e;
   }
@@ -922,6 +948,15 @@ yl_status emit(LayerRun& r, const LaunchStep& s, bool* refused) {
       if (s.form == F_DWX_CHAIN && e == hipSuccess) ++c->chain_launches;
       break;
     }
+    case F_PW_PAIR: {
+      YlConvP& pt = ps[0]; YlConvP& po = ps[1];
+      r.params(i, pt);
+      r.params(i + 1, po);
+      pt.w3p = po.wp; pt.b3 = po.bias; pt.C3 = po.N; pt.act3 = po.act;
+      e = yl_launch_conv_pwx(pt, po.out, r.st);                          // the tensor between the two is not written
+      if (e == hipSuccess) ++c->pwx_launches;
+      break;
+    }
     case F_SPLIT_HEAD: case F_BATCHED:
       for (size_t q = 0; q < n; ++q) {
         r.params(i + q, ps[q]);
@@ -940,7 +975,7 @@ yl_status emit(LayerRun& r, const LaunchStep& s, bool* refused) {
       e = kLaunch[c->opt_bf16].conv_multi(ps, (int)n, c->opt_tile_m, r.st);
       break;
   }
-  const unsigned fused = form_bit(F_HEAD_RUN) | form_bit(F_DPQ_EXPAND) | form_bit(F_DPQ_PAIR) | form_bit(F_DWX_CHAIN);
+  const unsigned fused = form_bit(F_HEAD_RUN) | form_bit(F_DPQ_EXPAND) | form_bit(F_DPQ_PAIR) | form_bit(F_DWX_CHAIN) | form_bit(F_PW_PAIR);
   *refused = e == hipErrorNotSupported && (fused & form_bit(s.form));
   if (e != hipSuccess && !*refused) return launch_failed(c, s, e);
   return YL_OK;
@@ -1839,7 +1874,7 @@ yl_status yl_get_option(const yl_ctx* c, const char* name, int32_t* value) {
       {"pre_norm", c->opt_pre_norm}, {"reuse_slots", c->opt_reuse}, {"hybrid", c->opt_hybrid}, {"batch_levels", c->opt_batch_levels},
       {"fuse_decode", c->opt_fuse_decode}, {"fuse_head", c->opt_fuse_head}, {"winograd", c->opt_winograd}, {"lanes", c->opt_lanes},
       {"tile_m", c->opt_tile_m}, {"streams", c->opt_streams}, {"dev_select", c->opt_dev}, {"split_k", c->opt_split_k},
-      {"chain_launches", c->chain_launches}, {"head_skip_launches", c->head_skip_launches},
+      {"chain_launches", c->chain_launches}, {"pwx_launches", c->pwx_launches}, {"head_skip_launches", c->head_skip_launches},
       {"head_skip_count", c->opt_head_skip_count}};
   for (const auto& t : tab)
     if (!strcmp(name, t.n)) { *value = t.v; return YL_OK; }

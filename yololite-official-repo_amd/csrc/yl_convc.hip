@@ -990,6 +990,178 @@ hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st) {
   m.p[0] = p;
   return dwx_go(m, out3, st, dwx_kernel_of(p.dw_k, p.C3 / 16));      // (instantiated: yl_dwx_supported above)
 }
+
+// ------------------------------------------------------------------------------------------------
+// Two plain 1x1 convolutions as ONE launch, the tensor between them never written: L1 takes Cin <= 16 KB1 channels to Cmid
+// (= 16 NTm, + bias, clamp), L2 takes Cmid to N <= 16 NT2 (+ bias, clamp or nothing).  edge_n's backbone tail: blocks.4.0.conv
+// 64 -> 480 at 20x20 and lateral5 480 -> 96, the only reader of C5 -- 49 MB written and read again at B = 64 by two launches
+// that are bound by latency, not by MFMA work.  The MFMA D layout of L1's mid n-tile c (lane (kq, pl): channels
+// 16 c + 4 kq .. + 3 of pixel pl) is the B fragment of L2's k-block c, so per wave item of MT m-tiles: the KB1 B fragments of x
+// are loaded once; for every mid n-tile c ascending: a = 0, k-blocks ascending into a, h = clamp(a + b1[c]), then the NT2 n-tiles
+// of L2 take h as k-block c.  These are the k orders and epilogues of the two stand-alone launches (yl_conv_pws_kernel /
+// yl_conv_pwt_kernel: channel blocks ascending, four k-steps each, bias added after the products): bit-identical results.  Cmid is
+// never split between waves (that would be another fp32 summation order for L2).
+// Weights: KB1 + NT2 pieces of 1 KiB per mid n-tile (W1[.][c] and W2[c][.]), the same stream for every item, double-buffered through
+// LDS in chunks of CP mid n-tiles shared by the workgroup's NW waves -- the asynchronous copies of chunk c + 1 issued before the
+// MFMAs of chunk c, ONE barrier per chunk, the pipeline running on across items (the recipe of yl_conv_pws_kernel).  L1's bias
+// sits in LDS for the whole launch (an ordinary load inside the chunk loop would wait for the copies in flight).
+// dynamic LDS of yl_conv_pwx_kernel, regions in order (floats): [2][CP][KB1 + NT2][64] float4 weight chunks | [Cmid] bias of L1
+struct YlPwxLds {
+  static constexpr size_t LIMIT = 64 * 1024;
+  static constexpr int CP = 2;                               // mid n-tiles per weight chunk
+  int KB1, NT2, Cmid;
+  constexpr __host__ __device__ size_t weights() const { return (size_t)2 * CP * (KB1 + NT2) * 256; }
+  constexpr __host__ __device__ size_t bytes() const { return (weights() + (size_t)Cmid) * 4; }
+};
+
+template <int KB1, int NT2, int NW, int MT>
+__global__ __launch_bounds__(NW * 64, NW == 4 ? 3 : 4) void yl_conv_pwx_kernel(YlConvP p) {
+  constexpr int CP = YlPwxLds::CP, PC = KB1 + NT2;           // pieces of 1 KiB per mid n-tile
+  extern __shared__ __attribute__((aligned(16))) float yl_clds[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kq = lane >> 4, pl = lane & 15;
+  const int NTm = p.NTtot, Cin = p.Cin, M = p.M;
+  const YlPwxLds L = {KB1, NT2, NTm * 16};
+  const yl_act_t* const xin = p.x;
+  f32x4* wl = reinterpret_cast<f32x4*>(yl_clds);             // [2][CP][PC][64] float4
+  const float* b1l = yl_clds + L.weights();
+  const f32x4* w1g = reinterpret_cast<const f32x4*>(p.wp);   // [KB1][NTm][64] float4
+  const f32x4* w2g = reinterpret_cast<const f32x4*>(p.w3p);  // [NTm][NT2][64] float4
+  const int NC = (NTm + CP - 1) / CP;                         // chunks per item
+  // XCD x (workgroup b -> XCD b % 8) owns a contiguous band of the workgroup tiles (NW * MT m-tiles each), strided over its workgroups
+  const YlBandSplit ws = yl_band_split((int)blockIdx.x, (int)gridDim.x, p.ntiles);   // gridDim.x % 8 == 0
+  const int per = ws.per, slot = ws.slot, band0 = ws.band0, nmine = ws.nmine;
+  const long total_chunks = (long)nmine * NC;
+  // asynchronous copy of chunk `c` (mid n-tiles c*CP .. c*CP+CP-1, clamped) into buffer `buf`
+  auto load_chunk = [&](int c, int buf) {
+    for (int i = wave; i < CP * PC; i += NW) {
+      const int j = i / PC, q = i - j * PC;
+      int ct = c * CP + j;
+      ct = ct < NTm ? ct : NTm - 1;
+      const f32x4* src = q < KB1 ? w1g + ((size_t)q * NTm + ct) * 64 : w2g + ((size_t)ct * NT2 + (q - KB1)) * 64;   // (wave-uniform)
+      yl_glds16(src + lane, wl + ((size_t)buf * CP * PC + i) * 64);
+    }
+  };
+  if (total_chunks > 0) load_chunk(0, 0);
+  yl_glds_floats(p.bias, yl_clds + L.weights(), NTm * 16, tid, NW * 64);
+  long gchunk = 0;                                            // chunks consumed so far (buffer = gchunk & 1)
+  __syncthreads();
+  const float lo1 = yl_act_lo(p.act), hi1 = yl_act_hi(p.act);
+  const float lo2 = yl_act_lo(p.act3), hi2 = yl_act_hi(p.act3);
+  const int N2 = p.C3;
+  yl_act_t* const outp = p.out;                               // L2's output
+  f32x4 b2r[NT2];                                             // L2's bias (padded to whole n-tiles): read once, not per item
+#pragma unroll
+  for (int nt = 0; nt < NT2; ++nt) b2r[nt] = yl_ld4(p.b3 + nt * 16 + 4 * kq);
+
+  for (int wi = 0; wi < nmine; ++wi) {
+    const int tile = band0 + slot + wi * per;
+    bool valid[MT];
+    size_t pix[MT];                                           // linear pixel index (clamped)
+    f32x4 xq[KB1][MT];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      // the last m-tiles may be partial or empty: their lanes read the last pixel and store nothing
+      size_t lin = (((size_t)tile * NW + wave) * MT + mt) * 16 + pl;
+      valid[mt] = lin < (size_t)M;
+      if (!valid[mt]) lin = (size_t)M - 1;
+      pix[mt] = lin;
+      const yl_act_t* xrow = xin + lin * Cin + 4 * kq;
+#pragma unroll
+      for (int kb = 0; kb < KB1; ++kb)
+        xq[kb][mt] = yl_ld4(kb * 16 + 4 * kq < Cin ? xrow + kb * 16 : p.zeros);   // channel tail of the last block: zeros
+    }
+    f32x4 acc[MT][NT2];
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int nt = 0; nt < NT2; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int c = 0; c < NC; ++c) {
+      const int buf = (int)(gchunk & 1);
+      // next chunk of the stream (the same weights for every item) into the other buffer
+      if (gchunk + 1 < total_chunks) load_chunk(c + 1 < NC ? c + 1 : 0, buf ^ 1);
+      const f32x4* wb = wl + (size_t)buf * CP * PC * 64 + lane;
+      f32x4 a[MT][CP];                                        // L1: CP mid n-tiles, independent accumulator chains
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int j = 0; j < CP; ++j) a[mt][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kb = 0; kb < KB1; ++kb) {
+        f32x4 wq[CP];
+#pragma unroll
+        for (int j = 0; j < CP; ++j) wq[j] = wb[(j * PC + kb) * 64];
+        yl_mma_step<CP, MT>(wq, xq[kb], a);
+      }
+#pragma unroll
+      for (int j = 0; j < CP; ++j) {
+        const int ct = c * CP + j;
+        if (ct < NTm) {                                       // (workgroup-uniform) odd NTm: the last chunk is half empty
+          const f32x4 b1 = *reinterpret_cast<const f32x4*>(b1l + ct * 16 + 4 * kq);
+          f32x4 h[MT], wq[NT2];
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) h[mt] = yl_clamp4(a[mt][j] + b1, lo1, hi1);
+#pragma unroll
+          for (int nt = 0; nt < NT2; ++nt) wq[nt] = wb[(j * PC + KB1 + nt) * 64];
+          yl_mma_step<NT2, MT>(wq, h, acc);
+        }
+      }
+      __syncthreads();             // every wave is done with `buf`; the copies into the other buffer have landed
+      ++gchunk;
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {                         // == yl_epi_fast with the bias from registers
+      if (!valid[mt]) continue;
+      yl_act_t* orow = outp + pix[mt] * N2;
+#pragma unroll
+      for (int nt = 0; nt < NT2; ++nt) {
+        const int n = nt * 16 + 4 * kq;
+        const f32x4 v = yl_clamp4(acc[mt][nt] + b2r[nt], lo2, hi2);
+        if (n < N2) yl_st4(orow + n, v);
+      }
+    }
+  }
+}
+
+// instantiated: (k-blocks of L1's input, n-tiles of L2's output, waves per workgroup, m-tiles per wave)
+#define YL_PWX_SHAPES(X) X(4, 6, 4, 1)
+static YlConvKernel pwx_kernel_of(int kb1, int nt2, int* nw, int* mt) {
+#define YL_PWX_PICK(KB1, NT2, NW, MT) if (kb1 == KB1 && nt2 == NT2) { *nw = NW; *mt = MT; return yl_conv_pwx_kernel<KB1, NT2, NW, MT>; }
+  YL_PWX_SHAPES(YL_PWX_PICK)
+#undef YL_PWX_PICK
+  return nullptr;
+}
+
+bool yl_pwx_supported(int cin, int cmid, int cout) {
+  int nw, mt;
+  return cin > 0 && (cin & 3) == 0 && cmid > 0 && (cmid & 15) == 0 && cout > 0 && (cout & 3) == 0 &&
+         pwx_kernel_of((cin + 15) / 16, (cout + 15) / 16, &nw, &mt) &&
+         YlPwxLds{(cin + 15) / 16, (cout + 15) / 16, cmid}.bytes() <= YlPwxLds::LIMIT;
+}
+
+// p1: the first plain 1x1 layer with w3p / b3 / C3 / act3 of the plain 1x1 behind it, whose output is out3; p1's own output is
+// not written.  hipErrorNotSupported for every other shape or configuration (the two launches then run).
+hipError_t yl_launch_conv_pwx(const YlConvP& p1, float* out3, hipStream_t st) {
+  if (p1.k != 1 || p1.stride != 1 || p1.dw_k > 0 || p1.C1 > 0 || p1.res || p1.up || p1.scale || p1.dec_boxes || p1.ldo || p1.in_shift ||
+      !p1.bias || !p1.w3p || !p1.b3 || !out3 || YL_SMOOTH(p1.act) || YL_SMOOTH(p1.act3) || p1.H != p1.OH || p1.W != p1.OW ||
+      (p1.dev & YL_DEV_PWX_OFF) || !yl_pwx_supported(p1.Cin, p1.N, p1.C3))
+    return hipErrorNotSupported;
+  if ((size_t)p1.M * p1.Cin * sizeof(float) >= ((size_t)1 << 31) || (size_t)p1.M * p1.C3 * sizeof(float) >= ((size_t)1 << 31))
+    return hipErrorNotSupported;                                     // byte offsets of the input and the output below 2^31
+  int NW = 0, MT = 0;
+  const YlConvKernel kern = pwx_kernel_of(p1.KB, (p1.C3 + 15) / 16, &NW, &MT);
+  YlConvP p = p1;
+  p.out = out3;
+  p.ntiles = (int)(((long)p.M + 16 * NW * MT - 1) / (16 * NW * MT));
+  const size_t lds = YlPwxLds{p.KB, (p.C3 + 15) / 16, p.N}.bytes();
+  // Shape: 4 waves x 1 m-tile per wave (64 pixels per workgroup item; 94-118 VGPRs, 43 KB of LDS).  NOT MEASURED: the other
+  // candidates (8 waves x 1, 4 waves x 2 m-tiles, A fragments straight from L1/L2 through a buffer descriptor) and the one-stream
+  // launch time at B = 64 against the two launches (40.1 + 34.6 us, profiles/head_skip_kernel_stats_after.csv) have not been timed.
+  const int gx = yl_band_grid(yl_resident_blocks((const void*)kern, NW * 64, lds, 8), p.ntiles);
+  hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
+  return hipGetLastError();
+}
 #endif
 
 // ------------------------------------------------------------------------------------------------
@@ -3092,6 +3264,9 @@ hipError_t yl_convc_init() {
 #if !YL_BF16
 #define YL_DWX_CAP(A, B) cap(yl_conv_dwx_kernel<A, B>, YlDwtLds::LIMIT);
   YL_DWX_SHAPES(YL_DWX_CAP)
+#define YL_PWX_CAP(A, B, C, D) cap(yl_conv_pwx_kernel<A, B, C, D>, YlPwxLds::LIMIT);
+  YL_PWX_SHAPES(YL_PWX_CAP)
+#undef YL_PWX_CAP
 #endif
   cap(dwc_kernels, YlDwcLds::LIMIT);
   return e;

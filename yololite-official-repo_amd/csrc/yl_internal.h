@@ -201,11 +201,12 @@ struct YlConvP {
                                       // and fp16) and refilled with them at the start of every forward / predict call; no kernel reads it
 #define YL_DEV_CHAIN_OFF (1u << 19)   // UIB projection + next block's 1x1 expansion: two launches instead of yl_conv_dwx_kernel
 #define YL_DEV_HEAD_SKIP_OFF (1u << 20)   // fused head launch: every tile runs the whole head-output GEMM and the class scan (no objectness skip)
+#define YL_DEV_PWX_OFF (1u << 21)     // 1x1 -> 1x1 pair with a single-reader tensor between: two launches instead of yl_conv_pwx_kernel
 #define YL_DEV_MASK 0x3ffffffu       // the bits "dev_select" keeps
 static_assert(YL_DEV_MASK <= 0x7fffffffu, "dev_select is stored in an int (and an int field of the graph key)");
 static_assert(((YL_DEV_DW_TILE_OFF | YL_DEV_PWS_OFF | YL_DEV_S2C_OFF | YL_DEV_DWC_ALL | YL_DEV_DWT_OFF | (3u << 5) | (3u << 7) |
                 YL_DEV_KXK_MT2 | YL_DEV_DWT_NOSPLIT | YL_DEV_WINO_V1 | (3u << 12) | YL_DEV_DWL_OFF | YL_DEV_DWL_ALL | YL_DEV_DPW_OFF |
-                YL_DEV_K3W_OFF | YL_DEV_POISON | YL_DEV_CHAIN_OFF | YL_DEV_HEAD_SKIP_OFF) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
+                YL_DEV_K3W_OFF | YL_DEV_POISON | YL_DEV_CHAIN_OFF | YL_DEV_HEAD_SKIP_OFF | YL_DEV_PWX_OFF) & ~YL_DEV_MASK) == 0, "a YL_DEV_* bit lies outside the dev_select mask");
 
 // squeeze-excite gate (yl_se.hip): fixed-order two-pass spatial mean + the two FCs + sigmoid
 struct YlSeP {
@@ -390,6 +391,10 @@ hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st);
 // (yl_convc.hip, fp32 unit only); hipErrorNotSupported = shape / configuration not instantiated
 hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st);
 bool yl_dwx_supported(int cin, int cout, int dw_k, int dw_stride, int cout1, int oh, int ow);
+// two plain 1x1 convs as one launch, the tensor between them not written (yl_convc.hip, fp32 unit only): p1 carries the second
+// layer's weights as w3p / b3 / C3 / act3, out3 is its output; hipErrorNotSupported = shape / configuration not instantiated
+hipError_t yl_launch_conv_pwx(const YlConvP& p1, float* out3, hipStream_t st);
+bool yl_pwx_supported(int cin, int cmid, int cout);
 // streamed-weight depthwise 3x3 -> 1x1 kernel for K >= 192 and more than 8 n-tiles (yl_convc.hip)
 hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st);
 // depthwise k x k -> 1x1 for >= 192 depthwise channels: streamed 1x1 weights AND tap weights, halo patch through LDS (yl_convc.hip,
