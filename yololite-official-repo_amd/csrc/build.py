@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-fourteen translation units (three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+fifteen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
 library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
@@ -16,6 +16,8 @@ OBJ = os.path.join(HERE, "_obj")
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-unused-value"]
 UNITS = [   # (source, extra flags, object name)
     ("yl_api.hip", [], "yl_api.o"),
+    # host side of the layer program (validation, weight packing, derived tables): no HIP header, no device code
+    ("yl_program.cpp", [], "yl_program.o"),
     ("yl_conv.hip", [], "yl_conv.o"),
     ("yl_stemblock.hip", [], "yl_stemblock.o"),
     ("yl_convc.hip", [], "yl_convc.o"),
@@ -49,7 +51,7 @@ UNITS = [   # (source, extra flags, object name)
     # trainable detection heads (forward and backward): one rounding per written operation outside the MFMAs
     ("yl_head.hip", ["-ffp-contract=off"], "yl_head.o"),
 ]
-DEPS = ["yl_internal.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", os.path.join("..", "..", "include", "yololite_hip.h")]
+DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 
 
 def _hipcc():

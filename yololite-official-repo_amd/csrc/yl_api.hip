@@ -1,5 +1,6 @@
 // C ABI (include/yololite_hip.h): context, weight packing, forward executor, post-processing driver.
 #include "yl_internal.h"
+#include "yl_program.h"
 
 #include <dlfcn.h>
 #include <limits.h>
@@ -14,27 +15,13 @@
 #include <string>
 #include <vector>
 
-#define YL_DW_LDS_MAX (32 * 1024)
-
 namespace {
 
-struct DevLayer {
-  yl_layer d;            // host description (pointers nulled after packing)
-  float* wp = nullptr;   // packed weights (device)
-  float* bias = nullptr; // padded bias (device)
-  float* dw_w = nullptr; // [taps][Cin] (device)
-  float* dw_b = nullptr;
-  float* w2p = nullptr;  // stem block: packed second / third conv
-  float* b2 = nullptr;
-  float* w3p = nullptr;
-  float* b3 = nullptr;
-  float* wino = nullptr; // Winograd F(2x2,3x3) weight image of a dense 3x3 stride-1 conv (pack_wino), or nullptr
-  // head-output layer of a model with mask coefficients (round 4): the same 1x1 conv as TWO weight images -- rows [0, 5+C)
-  // (decode fused in the epilogue, no raw rows: the fast wave-autonomous path) and rows [5+C, 5+C+NM) (plain 1x1 whose 32
-  // columns land in the level rows the mask kernels read)
-  float* wp_det = nullptr; float* b_det = nullptr; float* wp_mc = nullptr; float* b_mc = nullptr;
-  int in_h = 0, in_w = 0, out_h = 0, out_w = 0;
-  int head_anchor = -1;  // head layers: anchor index handled by this layer
+// a validated layer (yl_program.h; its host weight pointers are nulled after packing) with its weight images on the device
+struct DevLayer : YlLayerInfo {
+#define YL_X(name) float* name = nullptr;
+  YL_LAYER_IMAGES(YL_X)
+#undef YL_X
 };
 
 struct Slot {
@@ -45,17 +32,35 @@ struct Slot {
   float* pin = nullptr;
 };
 
+// The model: everything yl_create derives from the description, and the packed weights on the device.  Immutable once
+// yl_create returns and SHARED by the contexts of one model (yl_clone: one context per batch in flight of a serving
+// pipeline); the last owner frees the device images.
+struct Model : YlGeometry, YlTables {
+  int device = 0;
+  std::vector<DevLayer> layers;
+  float* zeros = nullptr;                  // 1 KiB of zeros (padding source for the conv kernels)
+  Model() = default;
+  Model(const Model&) = delete;
+  Model& operator=(const Model&) = delete;
+  ~Model() {
+    if (!zeros && layers.empty()) return;
+    hipSetDevice(device);
+    hipFree(zeros);
+    for (DevLayer& L : layers) {
+#define YL_X(name) hipFree(L.name);
+      YL_LAYER_IMAGES(YL_X)
+#undef YL_X
+    }
+  }
+};
+
 }  // namespace
 
 #define YL_GRAPH_SLOTS 4
 #define YL_NMS_GROUPS 4
 struct yl_ctx {
-  int device = 0;
-  int img_size = 0, in_ch = 3, C = 0, L = 0, N = 0, E = 0, NM = 0, proto_slot = -1;
-  int level_S[YL_MAX_LEVELS] = {0}, level_A[YL_MAX_LEVELS] = {0}, level_off[YL_MAX_LEVELS + 1] = {0};
-  std::vector<Slot> slots;
-  std::vector<DevLayer> layers;
-  float* zeros = nullptr;                  // 1 KiB of zeros (padding source for the conv kernels)
+  std::shared_ptr<const Model> m;          // never null in a context yl_create / yl_clone handed out
+  std::vector<Slot> slots;                 // the model's slots (m->slot_dims) with this context's placement
   int cap_batch = 0;                       // images the pinned slots / level buffers are allocated for (capacity)
   int act_batch = 0;                       // batch of the last forward: what yl_masks* / yl_read_slot may address
   // Activation memory: ONE arena per batch chunk (chunks run concurrently on their own streams), slots placed by
@@ -64,8 +69,7 @@ struct yl_ctx {
   // a chance to meet in the 256 MB Infinity Cache instead of HBM.  "reuse_slots" 0 keeps every tensor (debugging).
   char* arena[4] = {nullptr, nullptr, nullptr, nullptr};
   int arena_capi[4] = {0, 0, 0, 0};        // images arena i is allocated for (a single-chunk call grows arena 0 only)
-  float* se_scratch[4] = {nullptr, nullptr, nullptr, nullptr};   // YL_OP_SE partial sums of a chunk: [capi][se_unit]
-  size_t se_unit = 0;                      // floats per image: max over the SE layers of P * C
+  float* se_scratch[4] = {nullptr, nullptr, nullptr, nullptr};   // YL_OP_SE partial sums of a chunk: [capi][m->se_unit]
   int plan_n = 0;                          // the current job's batch is split into this many chunks
   int arena_n = 0, arena_cap = 0;          // allocated: arenas, images of the largest one (plan_n / plan_cap <= these)
   int plan_b0[5] = {0, 0, 0, 0, 0};        // chunk i covers images [plan_b0[i], plan_b0[i + 1])
@@ -105,9 +109,9 @@ struct yl_ctx {
   int opt_nms_groups = 0;    // workgroups per image in the NMS kernel: 1..4, 0 = auto (by confidence threshold, see do_post)
   int opt_hybrid = 0;        // (off: measured -0.5 % at B=64) full-batch launches for the high-resolution layers, batch chunks on the internal streams only
                              // for the run of low-resolution (<= 1/16) layers, see plan_segments()
-  int small_lo = 0, small_hi = 0;   // that run: layers [small_lo, small_hi)
-  int tiny_lo = 0, tiny_hi = 0;     // "hybrid" 2 (the reverse plan): the run of <= 1/32-resolution layers goes out as FULL-batch
-                                    // launches between two chunked segments (half as many latency-bound launches)
+                             // (m->small_lo / small_hi: that run).  "hybrid" 2 (the reverse plan): the run of <= 1/32-resolution
+                             // layers (m->tiny_lo / tiny_hi) goes out as FULL-batch launches between two chunked segments (half as
+                             // many latency-bound launches)
   int opt_batch_levels = 1;  // runs of independent, identically shaped layers (FPN smooth / head trunk / head out of all
                              // levels) go out as ONE launch (YlConvMulti)
   int opt_winograd = 1;      // dense 3x3 stride-1 layers with >= 64 channels through Winograd F(2x2,3x3) (2.25x fewer MACs;
@@ -117,7 +121,6 @@ struct yl_ctx {
                              // error vs the oracle over 4 weight seeds x 32 images x 8400 candidates 0.9-1.6e-5 (yololite_m) /
                              // 0.7-1.2e-5 (yololite_m v2), no worse than the direct convolution's 1.4-1.7e-5 / 1.0-1.3e-5
                              // (profiles/r04_winograd_margin*.json)
-  int wino_max_hw = 0;       // that grid: max out_h * out_w over the layers that carry a Winograd weight image
   int opt_fuse_decode = 1;   // yl_predict: decode in the head-output conv's epilogue (no raw level tensor, no decode kernel)
   int opt_fuse_head = 1;     // ... and the head trunk (depthwise 3x3 -> 1x1) in the same launch (yl_conv_dpp_kernel)
   int opt_split_k = 0; // depthwise -> 1x1 layers on <= 20x20 grids in the split-K form (yl_conv_dwt_kernel<.., SK = 4>): -9 % batch-1
@@ -136,12 +139,10 @@ struct yl_ctx {
   hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
   // branch lanes inside a chunk: neck/head layers that only feed the heads of the coarser levels (smooth5,
   // head5, smooth4, head4, ...) run on a side stream next to the 80x80 chain (lateral3 -> smooth3 -> head3);
-  // lane[i] is derived from the slot graph at yl_create.  Off by default ("lanes" option): measured no gain
+  // m->lane[i] is derived from the slot graph at yl_create.  Off by default ("lanes" option): measured no gain
   // (29.3 k img/s either way) -- the conv grids are occupancy-sized persistent grids, so a second kernel only
   // gets CUs at the tail of the first
   int opt_lanes = 0;
-  std::vector<unsigned char> lane;
-  std::vector<int> readers;  // per slot: layer operands that read it (count_readers, yl_create) -- 1 = a single consumer
   hipStream_t side[4] = {nullptr, nullptr, nullptr, nullptr};
   hipEvent_t ev_la[4] = {nullptr, nullptr, nullptr, nullptr}, ev_lb[4] = {nullptr, nullptr, nullptr, nullptr};
   // hipGraph cache keyed on everything baked into the captured launches: up to YL_GRAPH_SLOTS jobs (a serving loop alternates
@@ -154,9 +155,6 @@ struct yl_ctx {
   };
   std::vector<GraphEntry> graphs;
   unsigned long long graph_clock = 0;
-  // The packed weights (every device pointer inside `layers`, and `zeros`) are immutable after yl_create and may be
-  // SHARED by several contexts (yl_clone: one context per batch in flight of a serving pipeline); the last owner frees them
-  std::shared_ptr<int> weights_owner;
   std::string err;
 };
 
@@ -192,91 +190,10 @@ yl_status upload(yl_ctx* c, const std::vector<T>& h, T** d) {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// MFMA fragment order: [tap][kblock][ntile][lane][s]  with
-//   n = ntile*16 + (lane & 15),  c = kblock*16 + 4*(lane >> 4) + s     (see yl_conv.hip)
-void pack_conv(const float* w, int cout, int cin, int k, std::vector<float>& out) {
-  const int KB = cdiv(cin, 16), NT = cdiv(cout, 16), taps = k * k;
-  out.assign((size_t)taps * KB * NT * 256, 0.0f);
-  for (int tap = 0; tap < taps; ++tap)
-    for (int kb = 0; kb < KB; ++kb)
-      for (int nt = 0; nt < NT; ++nt)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int s = 0; s < 4; ++s) {
-            const int n = nt * 16 + (lane & 15);
-            const int c = kb * 16 + 4 * (lane >> 4) + s;
-            if (n < cout && c < cin)
-              out[((((size_t)tap * KB + kb) * NT + nt) * 64 + lane) * 4 + s] =
-                  w[((size_t)n * cin + c) * taps + tap];
-          }
-}
-
-// Winograd F(2x2,3x3): U = G g G^T (4x4 per (cout, cin)), G = [[1,0,0],[.5,.5,.5],[.5,-.5,.5],[0,0,1]], in the MFMA
-// fragment order of pack_conv per transform position xi = 4i + j, grouped so that one (n-group of 2 n-tiles, k-block)
-// chunk is 32 KiB contiguous: [ngroup][kblock][xi][nt 0..1][lane][s]   (yl_conv_wino_kernel)
-void pack_wino(const float* w, int cout, int cin, std::vector<float>& out) {
-  const int KB = cdiv(cin, 16), NG = cdiv(cdiv(cout, 16), 2);
-  static const float G[4][3] = {{1.f, 0.f, 0.f}, {0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f}, {0.f, 0.f, 1.f}};
-  out.assign((size_t)NG * KB * 16 * 2 * 256, 0.0f);
-  for (int ng = 0; ng < NG; ++ng)
-    for (int kb = 0; kb < KB; ++kb)
-      for (int t = 0; t < 2; ++t)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int s = 0; s < 4; ++s) {
-            const int n = (ng * 2 + t) * 16 + (lane & 15);
-            const int c = kb * 16 + 4 * (lane >> 4) + s;
-            if (n >= cout || c >= cin) continue;
-            const float* g = w + ((size_t)n * cin + c) * 9;
-            float tmp[4][3];
-            for (int i = 0; i < 4; ++i)
-              for (int b = 0; b < 3; ++b) tmp[i][b] = G[i][0] * g[0 * 3 + b] + G[i][1] * g[1 * 3 + b] + G[i][2] * g[2 * 3 + b];
-            for (int i = 0; i < 4; ++i)
-              for (int j = 0; j < 4; ++j) {
-                const float u = tmp[i][0] * G[j][0] + tmp[i][1] * G[j][1] + tmp[i][2] * G[j][2];
-                out[(((((size_t)ng * KB + kb) * 16 + (i * 4 + j)) * 2 + t) * 64 + lane) * 4 + s] = u;
-              }
-          }
-}
-
-// depthwise [c][1][k][k] -> [tap][c]
-void pack_dw(const float* w, int ch, int k, std::vector<float>& out) {
-  out.assign((size_t)k * k * ch, 0.0f);
-  for (int c = 0; c < ch; ++c)
-    for (int t = 0; t < k * k; ++t) out[(size_t)t * ch + c] = w[(size_t)c * k * k + t];
-}
-
-// stem [cout][3][3][3] -> MFMA A fragments [kstep(7)][ntile][lane]: n = ntile*16 + (lane&15),
-// k = 4*kstep + (lane>>4) with k = c*9 + ky*3 + kx (PyTorch OIHW flattening), zero for k >= 27
-void pack_stem(const float* w, int cout, int cin, int k, std::vector<float>& out) {
-  const int K = cin * k * k, KS = cdiv(K, 4), NT = cdiv(cout, 16);
-  out.assign((size_t)KS * NT * 64, 0.0f);
-  for (int s = 0; s < KS; ++s)
-    for (int nt = 0; nt < NT; ++nt)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int n = nt * 16 + (lane & 15), kk = 4 * s + (lane >> 4);
-        if (n < cout && kk < K) out[((size_t)s * NT + nt) * 64 + lane] = w[(size_t)n * K + kk];
-      }
-}
-
-// stem of the fused entry block (3 input channels, 3x3): K order by input rows, see yl_stemblock.hip
-// bias (may be null): rides in the K = 27 -> 28 pad slot (s = 6, lane group 3) -- the kernel feeds 1.0 there, so the
-// shift is the LAST product of every output's fma chain (the rounding of conv + shift)
-void pack_stem_rows(const float* w, const float* bias, int cout, std::vector<float>& out) {
-  const int KS = 7, NT = cdiv(cout, 16);
-  out.assign((size_t)KS * NT * 64, 0.0f);
-  for (int s = 0; s < KS; ++s)
-    for (int nt = 0; nt < NT; ++nt)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int n = nt * 16 + (lane & 15), kq = lane >> 4;
-        int row, kx;
-        if (s < 3) { row = 2 * kq; kx = s; }
-        else if (s < 6) { row = 2 * kq + 1; kx = s - 3; }
-        else if (kq < 3) { row = 8; kx = kq; }
-        else {                                                       // pad slot: the bias
-          if (n < cout && bias) out[((size_t)s * NT + nt) * 64 + lane] = bias[n];
-          continue;
-        }
-        if (n < cout) out[((size_t)s * NT + nt) * 64 + lane] = w[(size_t)n * 27 + row * 3 + kx];
-      }
+// a context's slots: the model's dimensions, nothing placed yet
+void init_slots(yl_ctx* c) {
+  c->slots.assign(c->m->slot_dims.size(), Slot());
+  for (size_t i = 0; i < c->slots.size(); ++i) { c->slots[i].h = c->m->slot_dims[i].h; c->slots[i].w = c->m->slot_dims[i].w; c->slots[i].c = c->m->slot_dims[i].c; }
 }
 
 void drop_graph(yl_ctx* c);
@@ -323,7 +240,7 @@ constexpr unsigned form_bit(LaunchForm f) { return 1u << f; }
 // configuration, no residual / upsample operands, no dependency inside the run
 size_t layer_group_end(const yl_ctx* c, size_t i, size_t lend) {
   auto same_shape = [&](size_t x, size_t y) {
-    const yl_layer& a = c->layers[x].d; const yl_layer& e = c->layers[y].d;
+    const yl_layer& a = c->m->layers[x].d; const yl_layer& e = c->m->layers[y].d;
     return a.op == YL_OP_CONV && e.op == YL_OP_CONV && a.cin == e.cin && a.cout == e.cout && a.k == e.k &&
            a.stride == e.stride && a.pad_t == e.pad_t && a.pad_l == e.pad_l && a.act == e.act &&
            !YL_ACT_POSTPASS(a.act) && a.in_shift == e.in_shift && a.dw_k == e.dw_k && a.dw_stride == e.dw_stride && a.dw_pad_t == e.dw_pad_t &&
@@ -332,11 +249,11 @@ size_t layer_group_end(const yl_ctx* c, size_t i, size_t lend) {
            (a.cout + 15) / 16 <= 8;
   };
   size_t gend = i + 1;
-  if (c->layers[i].d.op != YL_OP_CONV) return gend;
+  if (c->m->layers[i].d.op != YL_OP_CONV) return gend;
   while (gend < lend && gend - i < 4 && same_shape(i, gend)) {
     bool dep = false;
     for (size_t q = i; q < gend; ++q)
-      if (c->layers[q].d.head_level < 0 && c->layers[q].d.out_slot == c->layers[gend].d.in_slot) dep = true;
+      if (c->m->layers[q].d.head_level < 0 && c->m->layers[q].d.out_slot == c->m->layers[gend].d.in_slot) dep = true;
     if (dep) break;
     ++gend;
   }
@@ -350,17 +267,17 @@ bool dw3_trunk(const yl_ctx* c, const DevLayer& T) {
   const yl_layer& t = T.d;
   return t.op == YL_OP_CONV && t.k == 1 && t.dw_k == 3 && t.dw_stride == 1 && t.c2 == 0 && t.c3 == 0 && t.head_level < 0 &&
          t.res_slot < 0 && t.up_slot < 0 && !t.in_shift && !YL_SMOOTH(t.act) && !YL_SMOOTH(t.dw_act) && t.out_slot >= 0 &&
-         T.in_h == T.out_h && T.in_w == T.out_w && c->readers[t.out_slot] == 1;
+         T.in_h == T.out_h && T.in_w == T.out_w && c->m->readers[t.out_slot] == 1;
 }
 
 // Head branches as ONE launch (yl_conv_dpp_kernel): the level-batched run [i, i + n) of head trunks (depthwise 3x3 -> 1x1)
 // is followed by the run of their head-output convs in the same order, nothing else reads the trunk tensors, no mask
 // coefficients and the shape is instantiated
 bool head_run_fusable(const yl_ctx* c, size_t i, size_t n, size_t lend) {
-  if (c->NM > 0 || i + 2 * n > lend) return false;
+  if (c->m->NM > 0 || i + 2 * n > lend) return false;
   for (size_t q = 0; q < n; ++q) {
-    const DevLayer& T = c->layers[i + q];
-    const DevLayer& O = c->layers[i + n + q];
+    const DevLayer& T = c->m->layers[i + q];
+    const DevLayer& O = c->m->layers[i + n + q];
     const yl_layer& t = T.d; const yl_layer& o = O.d;
     if (o.op != YL_OP_CONV || o.head_level < 0 || o.k != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 || o.in_slot != t.out_slot ||
         o.cin != t.cout || o.act != YL_ACT_NONE || o.res_slot >= 0 || o.up_slot >= 0 || o.in_shift)
@@ -374,8 +291,8 @@ bool head_run_fusable(const yl_ctx* c, size_t i, size_t n, size_t lend) {
 // expand conv, layer i + 1 the plain 1x1 that consumes it, nothing else reads the expanded tensor, shape instantiated
 bool pair_fusable(const yl_ctx* c, size_t i, size_t lend) {
   if (i + 1 >= lend) return false;
-  const DevLayer& T = c->layers[i];
-  const yl_layer& t = T.d; const yl_layer& o = c->layers[i + 1].d;
+  const DevLayer& T = c->m->layers[i];
+  const yl_layer& t = T.d; const yl_layer& o = c->m->layers[i + 1].d;
   if (!dw3_trunk(c, T)) return false;
   if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 || o.in_slot != t.out_slot ||
       o.cin != t.cout || YL_SMOOTH(o.act) || o.up_slot >= 0 || o.in_shift || o.res_slot == t.out_slot ||
@@ -387,7 +304,7 @@ bool pair_fusable(const yl_ctx* c, size_t i, size_t lend) {
 // wide depthwise 3x3 -> 1x1 layer (more than 96 outputs) on its own: yl_conv_dpq_kernel's expand-only form computes the
 // depthwise part once per pixel
 bool expand_fusable(const yl_ctx* c, size_t i) {
-  const DevLayer& T = c->layers[i];
+  const DevLayer& T = c->m->layers[i];
   const yl_layer& d = T.d;
   return d.op == YL_OP_CONV && d.dw_k == 3 && d.dw_stride == 1 && d.k == 1 && d.c2 == 0 && d.c3 == 0 && d.head_level < 0 &&
          d.res_slot < 0 && d.up_slot < 0 && !d.in_shift && d.cout > 96 && T.in_h == T.out_h &&
@@ -399,8 +316,8 @@ bool expand_fusable(const yl_ctx* c, size_t i) {
 // gate or head) reading S.  S is still written -- the next block reads it as its residual.
 bool chain_fusable(const yl_ctx* c, size_t i, size_t lend) {
   if (i + 1 >= lend) return false;
-  const DevLayer& T = c->layers[i];
-  const DevLayer& O = c->layers[i + 1];
+  const DevLayer& T = c->m->layers[i];
+  const DevLayer& O = c->m->layers[i + 1];
   const yl_layer& t = T.d; const yl_layer& o = O.d;
   if (t.op != YL_OP_CONV || t.k != 1 || t.stride != 1 || t.dw_k <= 0 || t.dw_stride != 1 || t.c2 > 0 || t.c3 > 0 ||
       t.head_level >= 0 || t.up_slot >= 0 || t.scale_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || t.out_slot < 0 ||
@@ -418,12 +335,12 @@ bool chain_fusable(const yl_ctx* c, size_t i, size_t lend) {
 // none, no other operand), layer i + 1 is its only reader (no residual, upsample addend, gate or head).  S is not written.
 bool pwx_fusable(const yl_ctx* c, size_t i, size_t lend) {
   if (i + 1 >= lend) return false;
-  const DevLayer& T = c->layers[i];
-  const DevLayer& O = c->layers[i + 1];
+  const DevLayer& T = c->m->layers[i];
+  const DevLayer& O = c->m->layers[i + 1];
   const yl_layer& t = T.d; const yl_layer& o = O.d;
   if (t.op != YL_OP_CONV || t.k != 1 || t.stride != 1 || t.dw_k > 0 || t.c2 > 0 || t.c3 > 0 || t.head_level >= 0 ||
       t.res_slot >= 0 || t.up_slot >= 0 || t.scale_slot >= 0 || t.in_shift || YL_SMOOTH(t.act) || t.out_slot < 0 ||
-      c->readers[t.out_slot] != 1)
+      c->m->readers[t.out_slot] != 1)
     return false;
   if (o.op != YL_OP_CONV || o.head_level >= 0 || o.k != 1 || o.stride != 1 || o.dw_k > 0 || o.c2 > 0 || o.c3 > 0 ||
       o.in_slot != t.out_slot || o.cin != t.cout || YL_SMOOTH(o.act) || o.res_slot >= 0 || o.up_slot >= 0 ||
@@ -452,7 +369,7 @@ unsigned allowed_forms(const yl_ctx* c, bool per_layer, bool fuse) {
 // expand-only dpq, dpq pair, dwx chain, 1x1 pair, split head, level-batched run, else the single layer.  Without F_BATCHED layer i is
 // looked at on its own, as "batch_levels" 0 does.
 LaunchStep next_step(const yl_ctx* c, size_t i, size_t lend, unsigned forms) {
-  if (c->layers[i].d.op != YL_OP_CONV) return {F_LAYER, i, 1, 1};
+  if (c->m->layers[i].d.op != YL_OP_CONV) return {F_LAYER, i, 1, 1};
   auto may = [&](LaunchForm f) { return (forms & form_bit(f)) != 0; };
   const size_t n = may(F_BATCHED) ? layer_group_end(c, i, lend) - i : 1;
   if (may(F_HEAD_RUN) && head_run_fusable(c, i, n, lend)) return {F_HEAD_RUN, i, (int)n, (int)(2 * n)};
@@ -464,8 +381,8 @@ LaunchStep next_step(const yl_ctx* c, size_t i, size_t lend, unsigned forms) {
     if (may(F_PW_PAIR) && pwx_fusable(c, i, lend)) return {F_PW_PAIR, i, 1, 2};
   }
   // head-output convs of a model with mask coefficients, every one packed as two weight images
-  if (may(F_SPLIT_HEAD) && c->layers[i].d.head_level >= 0 &&
-      std::all_of(c->layers.begin() + i, c->layers.begin() + i + n, [](const DevLayer& L) { return L.wp_det != nullptr; }))
+  if (may(F_SPLIT_HEAD) && c->m->layers[i].d.head_level >= 0 &&
+      std::all_of(c->m->layers.begin() + i, c->m->layers.begin() + i + n, [](const DevLayer& L) { return L.wp_det != nullptr; }))
     return {F_SPLIT_HEAD, i, (int)n, (int)n};
   return {n > 1 ? F_BATCHED : F_LAYER, i, (int)n, (int)n};
 }
@@ -474,7 +391,7 @@ LaunchStep next_step(const yl_ctx* c, size_t i, size_t lend, unsigned forms) {
 // all of its layers' tensors at once): slot s is live from the group that produces it to the group of its last
 // consumer, inclusive; first-fit over the gaps of the live set.  reuse == false: every slot gets its own range.
 void plan_slots(yl_ctx* c, bool reuse) {
-  const size_t NL = c->layers.size(), NS = c->slots.size();
+  const size_t NL = c->m->layers.size(), NS = c->slots.size();
   std::vector<int> grp(NL, 0);
   int g = 0;
   // A group is whatever next_step could send out as one launch under ANY setting of the options (a fused launch writes its
@@ -492,7 +409,7 @@ void plan_slots(yl_ctx* c, bool reuse) {
   const int INF = 1 << 30;
   std::vector<int> def(NS, INF), last(NS, -1);
   for (size_t i = 0; i < NL; ++i) {
-    const yl_layer& d = c->layers[i].d;
+    const yl_layer& d = c->m->layers[i].d;
     if (d.head_level < 0 && d.out_slot >= 0 && grp[i] < def[d.out_slot]) def[d.out_slot] = grp[i];
     const int ins[4] = {(d.op == YL_OP_STEM || d.op == YL_OP_STEMBLOCK || d.op == YL_OP_NHWC4) ? -1 : d.in_slot, d.res_slot, d.up_slot, d.scale_slot};
     for (int k = 0; k < 4; ++k)
@@ -500,11 +417,11 @@ void plan_slots(yl_ctx* c, bool reuse) {
   }
   for (size_t s = 0; s < NS; ++s) {
     Slot& t = c->slots[s];
-    t.pinned = (int)s == c->proto_slot;
+    t.pinned = (int)s == c->m->proto_slot;
     // fp16-storage mode ("store_f16"): activation tensors are fp16; the pinned prototypes (the mask kernels read them) and the
     // squeeze-excite gates (yl_se.hip writes them, the gated 1x1 convs read them: fp32 [B][C] vectors) stay fp32
     bool f32 = c->opt_bf16 != 3 || t.pinned;
-    for (size_t i = 0; i < NL && !f32; ++i) f32 = c->layers[i].d.op == YL_OP_SE && c->layers[i].d.out_slot == (int)s;
+    for (size_t i = 0; i < NL && !f32; ++i) f32 = c->m->layers[i].d.op == YL_OP_SE && c->m->layers[i].d.out_slot == (int)s;
     t.sz = (size_t)t.h * t.w * t.c * (f32 ? sizeof(float) : sizeof(_Float16));   // images of a slot are contiguous (a multiple of 8 B)
     if (last[s] < def[s]) last[s] = def[s] == INF ? -1 : def[s];     // produced, never consumed: live in its own group
   }
@@ -535,7 +452,7 @@ void plan_slots(yl_ctx* c, bool reuse) {
 
 // bytes of detection level l for B images
 size_t level_bytes(const yl_ctx* c, int l, int B) {
-  return (size_t)B * c->level_A[l] * c->level_S[l] * c->level_S[l] * c->E * sizeof(float);
+  return (size_t)B * c->m->level_A[l] * c->m->level_S[l] * c->m->level_S[l] * c->m->E * sizeof(float);
 }
 
 // number of batch chunks a job of B images is split into (submit / walk_plan)
@@ -596,9 +513,9 @@ yl_status ensure_act(yl_ctx* c, int B, int n) {
         HIPCHK(c, hipMalloc((void**)&c->arena[i], c->arena_unit * (size_t)capi[i] + 256));
         HIPCHK(c, hipMemset(c->arena[i], fill, c->arena_unit * (size_t)capi[i] + 256));
       }
-      if (c->se_unit) {
-        HIPCHK(c, hipMalloc((void**)&c->se_scratch[i], c->se_unit * sizeof(float) * (size_t)capi[i]));
-        if (fill) HIPCHK(c, hipMemset(c->se_scratch[i], fill, c->se_unit * sizeof(float) * (size_t)capi[i]));
+      if (c->m->se_unit) {
+        HIPCHK(c, hipMalloc((void**)&c->se_scratch[i], c->m->se_unit * sizeof(float) * (size_t)capi[i]));
+        if (fill) HIPCHK(c, hipMemset(c->se_scratch[i], fill, c->m->se_unit * sizeof(float) * (size_t)capi[i]));
       }
       c->arena_capi[i] = capi[i];
     }
@@ -607,7 +524,7 @@ yl_status ensure_act(yl_ctx* c, int B, int n) {
         HIPCHK(c, hipMalloc((void**)&s.pin, s.sz * (size_t)newB + 256));
         HIPCHK(c, hipMemset(s.pin, fill, s.sz * (size_t)newB + 256));
       }
-    for (int l = 0; l < c->L; ++l) {
+    for (int l = 0; l < c->m->L; ++l) {
       HIPCHK(c, hipMalloc((void**)&c->level_buf[l], level_bytes(c, l, newB)));
       if (fill) HIPCHK(c, hipMemset(c->level_buf[l], fill, level_bytes(c, l, newB)));
     }
@@ -626,11 +543,11 @@ yl_status poison_act(yl_ctx* c, hipStream_t st) {
   if (!(c->opt_dev & YL_DEV_POISON)) return YL_OK;
   for (int i = 0; i < c->arena_n; ++i) {
     if (c->arena[i]) HIPCHK(c, hipMemsetAsync(c->arena[i], 0xFF, c->arena_unit * (size_t)c->arena_capi[i] + 256, st));
-    if (c->se_scratch[i]) HIPCHK(c, hipMemsetAsync(c->se_scratch[i], 0xFF, c->se_unit * sizeof(float) * (size_t)c->arena_capi[i], st));
+    if (c->se_scratch[i]) HIPCHK(c, hipMemsetAsync(c->se_scratch[i], 0xFF, c->m->se_unit * sizeof(float) * (size_t)c->arena_capi[i], st));
   }
   for (auto& s : c->slots)
     if (s.pinned && s.pin) HIPCHK(c, hipMemsetAsync(s.pin, 0xFF, s.sz * (size_t)c->cap_batch + 256, st));
-  for (int l = 0; l < c->L; ++l)
+  for (int l = 0; l < c->m->L; ++l)
     if (c->level_buf[l]) HIPCHK(c, hipMemsetAsync(c->level_buf[l], 0xFF, level_bytes(c, l, c->cap_batch), st));
   return YL_OK;
 }
@@ -653,19 +570,19 @@ float* slot_addr(const yl_ctx* c, int sl, int b) {
 // image b's part of its chunk's partial-sum scratch (squeeze-excite / GRN pooling)
 float* se_partial(const yl_ctx* c, int b) {
   const int ch = chunk_of(c, b);
-  return c->se_scratch[ch] + (size_t)(b - c->plan_b0[ch]) * c->se_unit;
+  return c->se_scratch[ch] + (size_t)(b - c->plan_b0[ch]) * c->m->se_unit;
 }
 
 yl_status ensure_post(yl_ctx* c, int B) {
   if (B <= c->post_cap_batch) return YL_OK;
   free_post_ws(c);
-  const size_t n = (size_t)B * c->N;
+  const size_t n = (size_t)B * c->m->N;
   HIPCHK(c, hipMalloc((void**)&c->ws_boxes, n * sizeof(float4)));
   HIPCHK(c, hipMalloc((void**)&c->ws_scores, n * sizeof(float)));
   HIPCHK(c, hipMalloc((void**)&c->ws_cls, n * sizeof(int)));
-  const int Cw = c->C > 0 ? c->C : 1;
+  const int Cw = c->m->C > 0 ? c->m->C : 1;
   HIPCHK(c, hipMalloc((void**)&c->ws_clsws, (size_t)B * 4 * Cw * sizeof(int)));
-  c->gP = pow2ceil(c->N);
+  c->gP = pow2ceil(c->m->N);
   if (c->gP > YL_LDS_KEYS_MAX) HIPCHK(c, hipMalloc((void**)&c->ws_gkeys, (size_t)B * c->gP * 8));
   HIPCHK(c, hipMalloc((void**)&c->ws_tmp_dets, n * 6 * sizeof(float)));
   HIPCHK(c, hipMalloc((void**)&c->ws_tmp_idx, n * sizeof(int)));
@@ -677,16 +594,16 @@ yl_status ensure_post(yl_ctx* c, int B) {
 
 void fill_levels(const yl_ctx* c, const float* const* ptrs, YlLevels& lv) {
   memset(&lv, 0, sizeof(lv));
-  lv.L = c->L; lv.N = c->N; lv.E = c->E; lv.C = c->C;
-  lv.hi = (float)(c->img_size - 1);
-  for (int l = 0; l < c->L; ++l) {
+  lv.L = c->m->L; lv.N = c->m->N; lv.E = c->m->E; lv.C = c->m->C;
+  lv.hi = (float)(c->m->img_size - 1);
+  for (int l = 0; l < c->m->L; ++l) {
     lv.ptr[l] = ptrs[l];
-    lv.S[l] = c->level_S[l];
-    lv.A[l] = c->level_A[l];
-    lv.off[l] = c->level_off[l];
-    lv.stride[l] = (float)((double)c->img_size / (double)c->level_S[l]);   // utils_ms.py:71
+    lv.S[l] = c->m->level_S[l];
+    lv.A[l] = c->m->level_A[l];
+    lv.off[l] = c->m->level_off[l];
+    lv.stride[l] = (float)((double)c->m->img_size / (double)c->m->level_S[l]);   // utils_ms.py:71
   }
-  lv.off[c->L] = c->N;
+  lv.off[c->m->L] = c->m->N;
 }
 
 // builds the kernel parameter block of layer i for batch B
@@ -698,8 +615,8 @@ void layer_params(const yl_ctx* c, const DevLayer& L, int b0, int B, const float
   // fp32 only: the committed Winograd error margins (profiles/r04_winograd_margin*.json) were measured with fp32 operands; with
   // 16-bit operands the transformed inputs and U = G g G^T would be rounded before the multiply
   p.wino = !c->opt_bf16 && (c->opt_winograd == 1 ||
-            (c->opt_winograd == 2 && d.cin >= 64 && d.cout >= 64 && L.out_h * L.out_w >= c->wino_max_hw)) ? L.wino : nullptr;
-  p.zeros = c->zeros;
+            (c->opt_winograd == 2 && d.cin >= 64 && d.cout >= 64 && L.out_h * L.out_w >= c->m->wino_max_hw)) ? L.wino : nullptr;
+  p.zeros = c->m->zeros;
   p.B = B; p.H = L.in_h; p.W = L.in_w; p.Cin = d.cin;
   p.OH = L.out_h; p.OW = L.out_w; p.N = d.cout;
   p.k = d.k; p.stride = d.stride; p.pad_t = d.pad_t; p.pad_l = d.pad_l; p.act = d.act;
@@ -734,12 +651,12 @@ void layer_params(const yl_ctx* c, const DevLayer& L, int b0, int B, const float
     p.up = slot_ptr(d.up_slot);
     p.UH = c->slots[d.up_slot].h; p.UW = c->slots[d.up_slot].w;
   }
-  p.out_f32 = (c->opt_bf16 == 3 && (d.head_level >= 0 || d.out_slot == c->proto_slot)) ? 1 : 0;
+  p.out_f32 = (c->opt_bf16 == 3 && (d.head_level >= 0 || d.out_slot == c->m->proto_slot)) ? 1 : 0;
   if (d.head_level >= 0) {
     const int l = d.head_level;
-    const int ss = c->level_S[l] * c->level_S[l];
-    p.out_bstride = (long)c->level_A[l] * ss * c->E;
-    p.out = level_out[l] + (size_t)b0 * p.out_bstride + (size_t)L.head_anchor * ss * c->E;
+    const int ss = c->m->level_S[l] * c->m->level_S[l];
+    p.out_bstride = (long)c->m->level_A[l] * ss * c->m->E;
+    p.out = level_out[l] + (size_t)b0 * p.out_bstride + (size_t)L.head_anchor * ss * c->m->E;
   } else {
     p.out = slot_ptr(d.out_slot);
     p.out_bstride = (long)L.out_h * L.out_w * ((d.op == YL_OP_CONV && d.c3 > 0) ? d.c3 : d.cout);
@@ -751,9 +668,9 @@ void layer_params(const yl_ctx* c, const DevLayer& L, int b0, int B, const float
 bool can_fuse_decode(const yl_ctx* c) {
   if (!c->opt_fuse_decode) return false;
   bool any = false;
-  for (const auto& L : c->layers) {
+  for (const auto& L : c->m->layers) {
     if (L.d.head_level < 0) continue;
-    if (L.d.op != YL_OP_CONV || L.d.k != 1 || L.d.dw_k > 0 || L.d.c2 > 0 || L.d.cout > 128 || L.d.cout != c->E ||
+    if (L.d.op != YL_OP_CONV || L.d.k != 1 || L.d.dw_k > 0 || L.d.c2 > 0 || L.d.cout > 128 || L.d.cout != c->m->E ||
         L.d.act != YL_ACT_NONE || L.d.res_slot >= 0 || L.d.up_slot >= 0)
       return false;
     any = true;
@@ -797,33 +714,33 @@ struct LayerRun {
 
   // where the launch that computes head-output layer i decodes to (fuse != nullptr)
   void decode_targets(size_t i, YlConvP& p) const {
-    const int l = c->layers[i].d.head_level, S = c->level_S[l];
-    const size_t o = (size_t)b0 * c->N;
+    const int l = c->m->layers[i].d.head_level, S = c->m->level_S[l];
+    const size_t o = (size_t)b0 * c->m->N;
     p.dec_boxes = c->ws_boxes + o; p.dec_scores = c->ws_scores + o; p.dec_cls = c->ws_cls + o;
-    p.dec_N = c->N; p.dec_off = c->level_off[l] + c->layers[i].head_anchor * S * S; p.dec_C = c->C;
+    p.dec_N = c->m->N; p.dec_off = c->m->level_off[l] + c->m->layers[i].head_anchor * S * S; p.dec_C = c->m->C;
     p.dec_mode = fuse->mode; p.dec_center = fuse->center_mode; p.dec_wh = fuse->wh_mode;
-    p.dec_raw = c->NM > 0 ? 1 : 0;                          // mask coefficients are read from the raw rows
-    p.dec_stride = (float)((double)c->img_size / (double)S);   // utils_ms.py:71, as fill_levels
-    p.dec_hi = (float)(c->img_size - 1);
+    p.dec_raw = c->m->NM > 0 ? 1 : 0;                          // mask coefficients are read from the raw rows
+    p.dec_stride = (float)((double)c->m->img_size / (double)S);   // utils_ms.py:71, as fill_levels
+    p.dec_hi = (float)(c->m->img_size - 1);
     p.dec_conf = fuse->conf_thr;
     p.dec_skip_cnt = c->opt_head_skip_count ? c->head_skip_cnt : nullptr;
   }
   void params(size_t i, YlConvP& p) const {
-    layer_params(c, c->layers[i], b0, B, x, level_out, p);
-    if (fuse && c->layers[i].d.head_level >= 0) decode_targets(i, p);
+    layer_params(c, c->m->layers[i], b0, B, x, level_out, p);
+    if (fuse && c->m->layers[i].d.head_level >= 0) decode_targets(i, p);
   }
 };
 
 // F_LAYER: layer i by its own launcher (+ the activation pass behind it), on its lane's stream
 yl_status run_layer(LayerRun& r, size_t i) {
   yl_ctx* c = r.c;
-  const DevLayer& L = c->layers[i];
+  const DevLayer& L = c->m->layers[i];
   const yl_layer& d = L.d;
   const int b0 = r.b0, B = r.B;
   const ModeLaunchers& ml = kLaunch[c->opt_bf16];
   YlConvP p;
   r.params(i, p);
-  const int ln = (r.lanes && c->lane[i]) ? 1 : 0;
+  const int ln = (r.lanes && c->m->lane[i]) ? 1 : 0;
   hipStream_t ls = ln ? r.sd : r.st;
   if (r.lanes) {
     // an event edge wherever a layer reads a slot produced on the other lane
@@ -857,10 +774,10 @@ yl_status run_layer(LayerRun& r, size_t i) {
     case YL_OP_DW: {
       // feeding a squeeze-excite gate next (efficientnetv2 MBConv): pool in the same launch
       r.pooled_slot = -1;
-      if (i + 1 < r.lend && c->layers[i + 1].d.op == YL_OP_SE && c->layers[i + 1].d.in_slot == d.out_slot && d.res_slot < 0 &&
+      if (i + 1 < r.lend && c->m->layers[i + 1].d.op == YL_OP_SE && c->m->layers[i + 1].d.in_slot == d.out_slot && d.res_slot < 0 &&
           (!c->opt_bf16 || c->opt_bf16 == 3) && !(c->opt_dev & YL_DEV_DW_TILE_OFF)) {
         const int wpi = yl_dw_pool_wpi(d.k, d.stride, d.cin, d.cout, L.out_h, L.out_w);
-        if (wpi > 0 && c->se_unit >= (size_t)wpi * d.cin) {
+        if (wpi > 0 && c->m->se_unit >= (size_t)wpi * d.cin) {
           p.pool = se_partial(c, b0);
           p.pool_wpi = wpi;
           r.pooled_slot = d.out_slot; r.pooled_P = wpi;
@@ -922,7 +839,7 @@ yl_status emit(LayerRun& r, const LaunchStep& s, bool* refused) {
     case F_LAYER: return run_layer(r, i);
     case F_HEAD_RUN:                          // trunks [i, i + n), their head-output convs [i + n, i + 2n)
       for (size_t q = 0; q < n; ++q) {
-        const DevLayer& O = c->layers[i + n + q];            // the head-output conv: weights, bias, decode targets
+        const DevLayer& O = c->m->layers[i + n + q];            // the head-output conv: weights, bias, decode targets
         r.params(i + q, ps[q]);
         ps[q].w3p = O.wp; ps[q].b3 = O.bias; ps[q].C3 = O.d.cout;
         r.decode_targets(i + n + q, ps[q]);
@@ -965,12 +882,12 @@ yl_status emit(LayerRun& r, const LaunchStep& s, bool* refused) {
         // rows); the coefficient part rides along as the second weight image (yl_launch_conv_multi: one pass where it pays,
         // else a second plain 1x1 launch) and its columns go into the level rows behind the detection columns
         // (bit-identical values: same k order)
-        const DevLayer& L = c->layers[i + q];
+        const DevLayer& L = c->m->layers[i + q];
         YlConvP& a = ps[q];
-        const int nd = 5 + c->C;
+        const int nd = 5 + c->m->C;
         a.wp = L.wp_det; a.bias = L.b_det; a.N = nd; a.NTtot = cdiv(nd, 16); a.dec_raw = 0;
-        a.w3p = L.wp_mc; a.b3 = L.b_mc; a.C3 = c->NM;
-        a.out += nd; a.ldo = c->E;
+        a.w3p = L.wp_mc; a.b3 = L.b_mc; a.C3 = c->m->NM;
+        a.out += nd; a.ldo = c->m->E;
       }
       e = kLaunch[c->opt_bf16].conv_multi(ps, (int)n, c->opt_tile_m, r.st);
       break;
@@ -986,10 +903,10 @@ yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* lev
                      const yl_post_cfg* fuse = nullptr /*non-null: head outputs decode in their epilogue*/,
                      int lo = 0, int hi = -1 /*layer range [lo, hi), -1 = to the end*/) {
   if (evs) HIPCHK(c, hipEventRecord(evs[0], st));
-  LayerRun r{c, x, b0, B, level_out, st, evs, chunk, fuse, hi < 0 ? c->layers.size() : (size_t)hi};
+  LayerRun r{c, x, b0, B, level_out, st, evs, chunk, fuse, hi < 0 ? c->m->layers.size() : (size_t)hi};
   // side lanes: an event edge is inserted wherever a layer reads a slot produced on the other lane (run_layer), and the
   // side stream is joined at the end.  Per-layer timing (evs) keeps everything on one stream.
-  r.lanes = !evs && c->opt_lanes && !c->lane.empty() && chunk >= 0 && chunk < 4;
+  r.lanes = !evs && c->opt_lanes && !c->m->lane.empty() && chunk >= 0 && chunk < 4;
   if (r.lanes) {
     if (!c->side[chunk]) HIPCHK(c, hipStreamCreateWithFlags(&c->side[chunk], hipStreamNonBlocking));
     if (!c->ev_la[chunk]) HIPCHK(c, hipEventCreateWithFlags(&c->ev_la[chunk], hipEventDisableTiming));
@@ -1016,73 +933,6 @@ yl_status run_layers(yl_ctx* c, const float* x, int b0, int B, float* const* lev
   return YL_OK;
 }
 
-// the longest run of consecutive layers whose input AND output grids are <= 1/16 of the image (the 40x40 / 20x20
-// stages of the backbone and the coarse part of the top-down pass): the part of the network that is chunked over
-// the internal streams by the hybrid plan
-void assign_small_run(yl_ctx* c) {
-  const int lim = c->img_size / 16;
-  int best_lo = 0, best_hi = 0, lo = -1;
-  const int n = (int)c->layers.size();
-  for (int i = 0; i <= n; ++i) {
-    const bool small = i < n && c->layers[i].d.op == YL_OP_CONV && c->layers[i].in_h <= lim && c->layers[i].out_h <= lim &&
-                       c->layers[i].d.head_level < 0;
-    if (small && lo < 0) lo = i;
-    if (!small && lo >= 0) {
-      if (i - lo > best_hi - best_lo) { best_lo = lo; best_hi = i; }
-      lo = -1;
-    }
-  }
-  c->small_lo = best_lo; c->small_hi = best_hi;
-  const int lim2 = c->img_size / 32;
-  best_lo = best_hi = 0; lo = -1;
-  for (int i = 0; i <= n; ++i) {
-    const bool small = i < n && (c->layers[i].d.op == YL_OP_CONV || c->layers[i].d.op == YL_OP_DW || c->layers[i].d.op == YL_OP_SE) &&
-                       c->layers[i].in_h <= lim2 && c->layers[i].out_h <= lim2 && c->layers[i].d.head_level < 0;
-    if (small && lo < 0) lo = i;
-    if (!small && lo >= 0) {
-      if (i - lo > best_hi - best_lo) { best_lo = lo; best_hi = i; }
-      lo = -1;
-    }
-  }
-  c->tiny_lo = best_lo; c->tiny_hi = best_hi;
-}
-
-// readers[s]: layer operands that read slot s -- the input (the stem-type ops read the caller's image instead), the
-// residual and the upsampled operand (not scale_slot: gates are written by YL_OP_SE, never by a layer a fused step swallows)
-void count_readers(yl_ctx* c) {
-  c->readers.assign(c->slots.size(), 0);
-  for (const DevLayer& L : c->layers)
-    for (int s : {(L.d.op == YL_OP_STEM || L.d.op == YL_OP_STEMBLOCK) ? -1 : L.d.in_slot, L.d.res_slot, L.d.up_slot})
-      if (s >= 0 && (size_t)s < c->readers.size()) ++c->readers[s];   // (YL_OP_NHWC4's in_slot is not validated: unused)
-}
-
-// lane assignment from the slot graph: a layer goes to lane 1 iff everything it feeds ends in head outputs of
-// levels >= 1 only (the finest level's chain, the backbone, the top-down laterals and the prototype branch stay
-// on lane 0)
-void assign_lanes(yl_ctx* c) {
-  const size_t n = c->layers.size();
-  c->lane.assign(n, 0);
-  std::vector<unsigned> reach(n, 0u);
-  for (size_t ii = n; ii-- > 0;) {
-    const yl_layer& d = c->layers[ii].d;
-    unsigned r = 0;
-    if (d.head_level >= 0) r |= 1u << (d.head_level > 30 ? 30 : d.head_level);
-    if (d.out_slot >= 0 && d.out_slot == c->proto_slot) r |= 1u << 31;
-    if (d.head_level < 0 && d.out_slot >= 0)
-      for (size_t j = ii + 1; j < n; ++j) {
-        const yl_layer& e = c->layers[j].d;
-        if (e.in_slot == d.out_slot || e.res_slot == d.out_slot || e.up_slot == d.out_slot || e.scale_slot == d.out_slot) r |= reach[j];
-      }
-    reach[ii] = r;
-  }
-  bool any = false;
-  for (size_t i = 0; i < n; ++i) {
-    c->lane[i] = (reach[i] != 0 && (reach[i] & 1u) == 0 && (reach[i] >> 31) == 0) ? 1 : 0;
-    any |= c->lane[i] != 0;
-  }
-  if (!any) c->lane.clear();
-}
-
 yl_status check_cfg(yl_ctx* c, const yl_post_cfg* cfg) {
   if (!cfg) return fail(c, YL_ERR_INVALID, "cfg is NULL");
   if (cfg->mode < YL_POST_MAIN || cfg->mode > YL_POST_EVAL) return fail(c, YL_ERR_INVALID, "bad post mode");
@@ -1098,9 +948,9 @@ yl_status check_cfg(yl_ctx* c, const yl_post_cfg* cfg) {
 yl_status do_post(yl_ctx* c, const float* const* levels_all, int b0, int B, const yl_post_cfg* cfg, float* dets,
                   int* counts, int* keep_idx, hipStream_t st, bool decoded = false /*NMS inputs already written*/) {
   const float* levels[YL_MAX_LEVELS];
-  for (int l = 0; l < c->L; ++l)
-    levels[l] = levels_all[l] + (size_t)b0 * c->level_A[l] * c->level_S[l] * c->level_S[l] * c->E;
-  const size_t o = (size_t)b0 * c->N;
+  for (int l = 0; l < c->m->L; ++l)
+    levels[l] = levels_all[l] + (size_t)b0 * c->m->level_A[l] * c->m->level_S[l] * c->m->level_S[l] * c->m->E;
+  const size_t o = (size_t)b0 * c->m->N;
   YlLevels lv;
   fill_levels(c, levels, lv);
   YlDecodeP dp;
@@ -1110,7 +960,7 @@ yl_status do_post(yl_ctx* c, const float* const* levels_all, int b0, int B, cons
   YlNmsP np;
   memset(&np, 0, sizeof(np));
   np.boxes = c->ws_boxes + o; np.scores = c->ws_scores + o; np.cls = c->ws_cls + o;
-  np.N = c->N; np.C = c->C > 0 ? c->C : 1;
+  np.N = c->m->N; np.C = c->m->C > 0 ? c->m->C : 1;
   np.conf_thr = cfg->conf_thr; np.iou_thr = cfg->iou_thr;
   np.impl = (cfg->mode == YL_POST_FALLBACK && cfg->fallback_nms == YL_NMS_GREEDY) ? YL_NMS_GREEDY : YL_NMS_TORCHVISION;
   np.cap = (cfg->per_class_cap > 0) ? cfg->per_class_cap : INT_MAX;
@@ -1129,7 +979,7 @@ yl_status do_post(yl_ctx* c, const float* const* levels_all, int b0, int B, cons
   // survivors -- evaluation thresholds (conf 0.001: +2.7 % on a 2000-survivor workload) -- and costs 0.8 % at the
   // few hundred survivors of a detector operating point (conf 0.4, calibrated benchmark workload)
   const int groups = c->opt_nms_groups > 0 ? c->opt_nms_groups : (cfg->conf_thr < 0.05f ? YL_NMS_GROUPS : 1);
-  np.G = (groups > 1 && np.topk == 0 && c->C > 1 && c->C <= 256 && c->N <= YL_LDS_KEYS_MAX) ? groups : 1;
+  np.G = (groups > 1 && np.topk == 0 && c->m->C > 1 && c->m->C <= 256 && c->m->N <= YL_LDS_KEYS_MAX) ? groups : 1;
   np.kept_list = c->ws_kept_list + o * YL_NMS_GROUPS;
   np.done = c->ws_done + (size_t)b0 * 64;                              // 256 bytes per image
   HIPCHK(c, yl_launch_nms(np, B, st));
@@ -1158,25 +1008,25 @@ struct Job {
 struct Seg { int lo, hi; bool chunked, post; };
 
 int plan_segments(const yl_ctx* c, const Job& j, int n, Seg* segs) {
-  const int L = (int)c->layers.size();
+  const int L = (int)c->m->layers.size();
   if (!j.x) { segs[0] = {0, 0, n > 1, true}; return 1; }
   if (c->opt_time_split && j.cfg) {          // one chunk (chunks_for): conv layers | post-processing, an event between them
     segs[0] = {0, L, false, false};
     segs[1] = {L, L, false, true};
     return 2;
   }
-  if (n > 1 && c->opt_hybrid == 2 && !c->opt_lanes && c->tiny_hi - c->tiny_lo >= 6) {
+  if (n > 1 && c->opt_hybrid == 2 && !c->opt_lanes && c->m->tiny_hi - c->m->tiny_lo >= 6) {
     int k = 0;
-    if (c->tiny_lo > 0) segs[k++] = {0, c->tiny_lo, true, false};
-    segs[k++] = {c->tiny_lo, c->tiny_hi, false, false};
-    segs[k++] = {c->tiny_hi, L, true, j.cfg != nullptr};
+    if (c->m->tiny_lo > 0) segs[k++] = {0, c->m->tiny_lo, true, false};
+    segs[k++] = {c->m->tiny_lo, c->m->tiny_hi, false, false};
+    segs[k++] = {c->m->tiny_hi, L, true, j.cfg != nullptr};
     return k;
   }
-  if (n > 1 && c->opt_hybrid == 1 && !c->opt_lanes && c->small_hi - c->small_lo >= 6) {
+  if (n > 1 && c->opt_hybrid == 1 && !c->opt_lanes && c->m->small_hi - c->m->small_lo >= 6) {
     int k = 0;
-    if (c->small_lo > 0) segs[k++] = {0, c->small_lo, false, false};
-    segs[k++] = {c->small_lo, c->small_hi, true, false};
-    segs[k++] = {c->small_hi, L, false, j.cfg != nullptr};
+    if (c->m->small_lo > 0) segs[k++] = {0, c->m->small_lo, false, false};
+    segs[k++] = {c->m->small_lo, c->m->small_hi, true, false};
+    segs[k++] = {c->m->small_hi, L, false, j.cfg != nullptr};
     return k;
   }
   segs[0] = {0, L, n > 1, j.cfg != nullptr};
@@ -1415,7 +1265,7 @@ const char* yl_last_error(const yl_ctx* ctx) { return ctx ? ctx->err.c_str() : "
 
 void yl_destroy(yl_ctx* c) {
   if (!c) return;
-  hipSetDevice(c->device);
+  hipSetDevice(c->m->device);
   free_act(c);
   free_post_ws(c);
   hipFree(c->ws_nms_clsws);
@@ -1431,41 +1281,18 @@ void yl_destroy(yl_ctx* c) {
   if (c->ev_fork) hipEventDestroy(c->ev_fork);
   for (int i = 0; i < 3; ++i) if (c->ev_t[i]) hipEventDestroy(c->ev_t[i]);
   hipFree(c->ws_nms_gkeys);
-  if (c->weights_owner.use_count() <= 1) {                   // last context that shares these weights (yl_clone)
-    hipFree(c->zeros);
-    for (auto& L : c->layers) {
-      hipFree(L.wp); hipFree(L.bias); hipFree(L.dw_w); hipFree(L.dw_b);
-      hipFree(L.w2p); hipFree(L.b2); hipFree(L.w3p); hipFree(L.b3); hipFree(L.wino);
-      hipFree(L.wp_det); hipFree(L.b_det); hipFree(L.wp_mc); hipFree(L.b_mc);
-    }
-  }
-  delete c;
+  delete c;   // (the model and its device images go with the last context that shares them)
 }
 
 yl_status yl_clone(const yl_ctx* src, yl_ctx** out) {
   if (!src || !out) return YL_ERR_INVALID;
   *out = nullptr;
-  if (hipSetDevice(src->device) != hipSuccess) return YL_ERR_HIP;
+  if (hipSetDevice(src->m->device) != hipSuccess) return YL_ERR_HIP;
   yl_ctx* c = new (std::nothrow) yl_ctx();
   if (!c) return YL_ERR_NOMEM;
   *out = c;
-  // the model: geometry, layer program and the (shared, immutable) packed weights
-  c->device = src->device;
-  c->img_size = src->img_size; c->in_ch = src->in_ch; c->C = src->C; c->L = src->L; c->N = src->N; c->E = src->E;
-  c->NM = src->NM; c->proto_slot = src->proto_slot;
-  memcpy(c->level_S, src->level_S, sizeof(c->level_S));
-  memcpy(c->level_A, src->level_A, sizeof(c->level_A));
-  memcpy(c->level_off, src->level_off, sizeof(c->level_off));
-  c->slots.resize(src->slots.size());
-  for (size_t i = 0; i < src->slots.size(); ++i) { c->slots[i].h = src->slots[i].h; c->slots[i].w = src->slots[i].w; c->slots[i].c = src->slots[i].c; }
-  c->layers = src->layers;
-  c->zeros = src->zeros;
-  c->weights_owner = src->weights_owner;
-  c->se_unit = src->se_unit;
-  c->wino_max_hw = src->wino_max_hw;
-  c->lane = src->lane;
-  c->readers = src->readers;
-  c->small_lo = src->small_lo; c->small_hi = src->small_hi; c->tiny_lo = src->tiny_lo; c->tiny_hi = src->tiny_hi;
+  c->m = src->m;                           // the model, shared and immutable
+  init_slots(c);
   // the options as they are now; activation arenas, workspaces, streams, events and cached graphs are the clone's own
   c->opt_reuse = src->opt_reuse; c->opt_pre_norm = src->opt_pre_norm; c->opt_graph = src->opt_graph; c->opt_tile_m = src->opt_tile_m;
   c->opt_streams = src->opt_streams; c->opt_nms_groups = src->opt_nms_groups; c->opt_hybrid = src->opt_hybrid;
@@ -1485,12 +1312,23 @@ yl_status yl_streams_overlap(int32_t device_id, void* a, void* b, int32_t* overl
   return YL_OK;
 }
 
+// validate (host only, yl_program.cpp) -> touch the device -> pack and upload layer by layer
 yl_status yl_create(const yl_model_desc* d, int32_t device_id, yl_ctx** out) {
   if (!d || !out) return YL_ERR_INVALID;
   *out = nullptr;
-  if (d->abi_version != YL_ABI_VERSION) return YL_ERR_INVALID;
-  if (d->num_levels < 1 || d->num_levels > YL_MAX_LEVELS) return YL_ERR_INVALID;
-  if (d->num_classes < 0 || d->num_classes > 4096) return YL_ERR_UNSUPPORTED;
+  yl_status s = yl_program_check_args(d);
+  if (s != YL_OK) return s;
+  YlProgram prog;
+  std::string msg;
+  s = yl_program_validate(d, &prog, &msg);
+  if (s != YL_OK) {
+    // handed out so that yl_last_error() can be read; caller destroys it.  No device has been touched: its model is empty
+    yl_ctx* c = new (std::nothrow) yl_ctx();
+    if (!c) return YL_ERR_NOMEM;
+    *out = c;
+    c->m = std::make_shared<Model>();
+    return fail(c, s, msg);
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device_id < 0 || device_id >= ndev) return YL_ERR_HIP;
   if (hipSetDevice(device_id) != hipSuccess) return YL_ERR_HIP;
@@ -1504,324 +1342,29 @@ yl_status yl_create(const yl_model_desc* d, int32_t device_id, yl_ctx** out) {
   yl_ctx* c = new (std::nothrow) yl_ctx();
   if (!c) return YL_ERR_NOMEM;
   *out = c;   // handed out even on failure so that yl_last_error() can be read; caller destroys it
-  c->weights_owner = std::make_shared<int>(0);
-  c->device = device_id;
-  c->img_size = d->img_size; c->in_ch = d->in_channels; c->C = d->num_classes; c->L = d->num_levels;
-  c->NM = d->num_masks; c->proto_slot = d->proto_slot;
-  if (c->NM < 0 || c->NM > 64) return fail(c, YL_ERR_UNSUPPORTED, "num_masks must be in [0,64]");
-  c->E = 5 + c->C + c->NM;
-  int off = 0;
-  for (int l = 0; l < c->L; ++l) {
-    c->level_S[l] = d->level_size[l]; c->level_A[l] = d->level_anchors[l];
-    if (c->level_S[l] < 1 || c->level_A[l] < 1) return fail(c, YL_ERR_INVALID, "bad level geometry");
-    c->level_off[l] = off;
-    off += c->level_A[l] * c->level_S[l] * c->level_S[l];
-  }
-  c->level_off[c->L] = off;
-  c->N = off;
-  if (c->N >= (1 << 20)) return fail(c, YL_ERR_UNSUPPORTED, "more than 2^20 candidates per image");
-  if (d->num_layers == 0) return YL_OK;
-  HIPCHK(c, hipMalloc((void**)&c->zeros, 1024));
-  HIPCHK(c, hipMemset(c->zeros, 0, 1024));
-  if (d->in_channels != 3) return fail(c, YL_ERR_UNSUPPORTED, "network input must have 3 channels");
-  if (!d->layers || !d->slot_h || !d->slot_w || !d->slot_c) return fail(c, YL_ERR_INVALID, "null layer/slot arrays");
-  c->slots.resize(d->num_slots);
-  for (int i = 0; i < d->num_slots; ++i) {
-    c->slots[i].h = d->slot_h[i]; c->slots[i].w = d->slot_w[i]; c->slots[i].c = d->slot_c[i];
-    if (c->slots[i].h < 1 || c->slots[i].w < 1 || c->slots[i].c < 1 || (c->slots[i].c & 3))
-      return fail(c, YL_ERR_UNSUPPORTED, "slot channels must be a positive multiple of 4");
-  }
-  std::vector<int> head_seen(c->L, 0);
-  char msg[256];
-  for (int i = 0; i < d->num_layers; ++i) {
-    const yl_layer& l = d->layers[i];
-    DevLayer L;
-    L.d = l;
-    auto bad = [&](const char* what) {
-      snprintf(msg, sizeof(msg), "layer %d: %s", i, what);
-      return fail(c, YL_ERR_INVALID, msg);
-    };
-    if (l.op < YL_OP_STEM || l.op > YL_OP_NHWC4) return bad("unknown op");
-    if (l.reserved0 != 0) return bad("reserved0 must be 0");
-    if (l.act < YL_ACT_NONE || l.act > YL_ACT_RELU_LAB || l.dw_act < 0 || l.dw_act > YL_ACT_SILU || l.act2 < 0 || l.act2 > YL_ACT_SILU ||
-        l.act3 < 0 || l.act3 > YL_ACT_SILU)
-      return bad("unknown activation (GELU / ReLU+affine are valid as `act` only)");
-    if (YL_ACT_POSTPASS(l.act) && ((l.op != YL_OP_STEM && l.op != YL_OP_CONV && l.op != YL_OP_DW) || l.head_level >= 0 || l.up_slot >= 0 ||
-                                   l.c2 > 0 || l.c3 > 0 || (l.cout & 3)))
-      return bad("GELU / ReLU + learnable affine: plain STEM / CONV / DW layers with cout % 4 == 0 only");
-    if (l.out_ch_off != 0 && l.op != YL_OP_COPY) return bad("out_ch_off is a YL_OP_COPY field");
-    if (l.op >= YL_OP_POOL) {
-      // element-wise / reduction ops (ABI v5): in_slot -> out_slot, no conv fields
-      if (l.out_slot < 0 || l.out_slot >= d->num_slots) return bad("bad out_slot");
-      if (l.op != YL_OP_NHWC4 && (l.in_slot < 0 || l.in_slot >= d->num_slots)) return bad("bad in_slot");
-      if (l.res_slot >= 0 || l.up_slot >= 0 || l.scale_slot >= 0 || l.head_level >= 0 || l.dw_k || l.c2 || l.c3 || l.in_shift || l.act)
-        return bad("element-wise op: plain layer fields only");
-      const Slot& so = c->slots[l.out_slot];
-      if (l.op == YL_OP_NHWC4) {
-        if (so.h != d->img_size || so.w != d->img_size || so.c != 4 || l.cout != 4) return bad("NHWC4: out_slot must be [S,S,4]");
-        L.in_h = L.in_w = d->img_size; L.out_h = L.out_w = d->img_size;
-      } else {
-        const Slot& si = c->slots[l.in_slot];
-        if (si.c != l.cin || (l.cin & 3)) return bad("cin does not match the input slot / not a multiple of 4");
-        L.in_h = si.h; L.in_w = si.w; L.out_h = so.h; L.out_w = so.w;
-        if (l.op == YL_OP_POOL) {
-          if (l.k < 1 || l.stride < 1 || l.cout != l.cin || so.c != l.cin || l.pad_t < 0 || l.pad_l < 0 || l.pad_t >= l.k || l.pad_l >= l.k ||
-              (so.h - 1) * l.stride - l.pad_t >= si.h || (so.w - 1) * l.stride - l.pad_l >= si.w)
-            return bad("pool: bad geometry");
-        } else if (l.op == YL_OP_COPY) {
-          if (so.h != si.h || so.w != si.w || l.out_ch_off < 0 || (l.out_ch_off & 3) || l.out_ch_off + l.cin > so.c)
-            return bad("copy: channel slice outside the output slot");
-        } else if (l.op == YL_OP_LN) {
-          if (so.h != si.h || so.w != si.w || so.c != l.cin || l.cout != l.cin || !l.w || !l.b || !(l.eps > 0.0f)) return bad("layer norm: needs w, b [cin], eps > 0, same shape out");
-        } else {     // GRN
-          if (so.h != 1 || so.w != 1 || so.c != l.cin || !l.w || !(l.eps > 0.0f) || l.cin > 16384) return bad("GRN: out_slot must be [1,1,cin], needs w [cin], eps > 0");
-          const size_t unit = (size_t)64 * l.cin;
-          if (unit > c->se_unit) c->se_unit = unit;
-          L.out_h = L.out_w = 1;
-        }
-      }
-      yl_status s2;
-      if (l.w && (l.op == YL_OP_LN || l.op == YL_OP_GRN)) {
-        std::vector<float> wv(l.w, l.w + l.cin);
-        if ((s2 = upload(c, wv, &L.wp)) != YL_OK) return s2;
-      }
-      if (l.b && l.op == YL_OP_LN) {
-        std::vector<float> bv(l.b, l.b + l.cin);
-        if ((s2 = upload(c, bv, &L.bias)) != YL_OK) return s2;
-      }
-      L.d.w = L.d.b = L.d.dw_w = L.d.dw_b = nullptr;
-      L.d.w2 = L.d.b2 = L.d.w3 = L.d.b3 = nullptr;
-      c->layers.push_back(L);
-      continue;
-    }
-    if (!l.w) return bad("weights are NULL");
-    if (l.k < 1 || l.stride < 1) return bad("bad kernel geometry");
-    if (l.op == YL_OP_SE) {
-      // squeeze-excite gate: in_slot [H,W,cin] -> out_slot [1,1,cin]; w/b = conv_reduce [cout][cin], w2/b2 = conv_expand [cin][cout]
-      if (l.in_slot < 0 || l.in_slot >= d->num_slots || l.out_slot < 0 || l.out_slot >= d->num_slots) return bad("bad slot");
-      const Slot& si = c->slots[l.in_slot]; const Slot& so = c->slots[l.out_slot];
-      if (si.c != l.cin || so.c != l.cin || so.h != 1 || so.w != 1) return bad("squeeze-excite: out_slot must be [1,1,cin]");
-      if (!l.w2 || !l.b || !l.b2 || l.c2 != l.cin || l.cout < 1 || l.cout > 256 || l.cin > 4096 || (l.cin & 3))
-        return bad("squeeze-excite: needs w [cout][cin], b, w2 [cin][cout], b2, c2 == cin, cout <= 256, cin % 4 == 0 and <= 4096");
-      if (l.k != 1 || l.stride != 1 || l.dw_k || l.c3 || l.res_slot >= 0 || l.up_slot >= 0 || l.scale_slot >= 0 || l.head_level >= 0 ||
-          l.in_shift)
-        return bad("squeeze-excite: plain layer fields only");
-      L.in_h = si.h; L.in_w = si.w; L.out_h = L.out_w = 1;
-      std::vector<float> w1(l.w, l.w + (size_t)l.cout * l.cin), b1(l.b, l.b + l.cout);
-      std::vector<float> w2((size_t)l.cin * l.cout), b2(l.b2, l.b2 + l.cin);
-      for (int cc = 0; cc < l.cin; ++cc)                       // conv_expand [cin][cout] -> [cout][cin]
-        for (int j = 0; j < l.cout; ++j) w2[(size_t)j * l.cin + cc] = l.w2[(size_t)cc * l.cout + j];
-      yl_status s2;
-      if ((s2 = upload(c, w1, &L.wp)) != YL_OK || (s2 = upload(c, b1, &L.bias)) != YL_OK ||
-          (s2 = upload(c, w2, &L.w2p)) != YL_OK || (s2 = upload(c, b2, &L.b2)) != YL_OK)
-        return s2;
-      // scratch: partial sums of the stand-alone pool pass, or of the depthwise launch that produces the tensor (<= 64 each)
-      const size_t unit = (size_t)64 * l.cin;
-      if (unit > c->se_unit) c->se_unit = unit;
-      L.d.w = L.d.b = L.d.dw_w = L.d.dw_b = nullptr;
-      L.d.w2 = L.d.b2 = L.d.w3 = L.d.b3 = nullptr;
-      c->layers.push_back(L);
-      continue;
-    }
-    if (l.scale_slot >= 0) {
-      if (l.scale_slot >= d->num_slots || l.op != YL_OP_CONV || l.k != 1 || l.stride != 1 || l.dw_k || l.c2 || l.c3 || l.in_shift)
-        return bad("scale_slot needs a plain 1x1 stride-1 conv");
-      const Slot& g = c->slots[l.scale_slot];
-      if (g.h != 1 || g.w != 1 || g.c != l.cin) return bad("scale_slot must be [1,1,cin]");
-    }
-    if (l.op == YL_OP_STEMBLOCK) {
-      L.in_h = L.in_w = d->img_size;
-      if (l.cin != 3 || l.k != 3) return fail(c, YL_ERR_UNSUPPORTED, "stem must be 3x3 with 3 input channels");
-      if (!l.w2 || l.c2 < 1 || l.c3 < 0 || (l.c3 > 0 && !l.w3)) return bad("stem block needs w2 (and w3 when c3 > 0)");
-      if (YL_SMOOTH(l.act) || YL_SMOOTH(l.act2) || YL_SMOOTH(l.act3))
-        return fail(c, YL_ERR_UNSUPPORTED, "stem block: ReLU-family activations only");
-      if (l.dw_k == 3) {       // second conv DEPTHWISE 3x3 stride 1 pad 1, then the 1x1: the EfficientNet-Lite entry (yl_stemdw_kernel)
-        if (l.cout != 32 || l.c2 != 32 || l.c3 < 4 || l.c3 > 32 || (l.c3 & 3) || !l.w3 || l.dw_stride != 1 || l.dw_pad_t != 1 || l.dw_pad_l != 1)
-          return fail(c, YL_ERR_UNSUPPORTED, "stem block with a depthwise second conv: 3 -> 32 -> dw3x3 s1 pad 1 -> 1x1 (4..32 outputs)");
-      } else if (l.dw_k != 0) {
-        return fail(c, YL_ERR_UNSUPPORTED, "stem block: dw_k must be 0 (dense 3x3 s2 second conv) or 3 (depthwise 3x3 s1)");
-      } else if (!yl_stemblock_supported(l.cout, l.c2, l.c3))
-        return fail(c, YL_ERR_UNSUPPORTED, "stem block: c1 in {16,32}, c2,c3 <= 32 and multiples of 4");
-    } else if (l.op == YL_OP_STEM) {
-      L.in_h = L.in_w = d->img_size;
-      if (l.cin != 3 || l.k != 3) return fail(c, YL_ERR_UNSUPPORTED, "stem must be 3x3 with 3 input channels");
-      if (l.cout != 16 && l.cout != 32) return fail(c, YL_ERR_UNSUPPORTED, "stem cout must be 16 or 32");
-    } else {
-      if (l.in_slot < 0 || l.in_slot >= d->num_slots) return bad("bad in_slot");
-      L.in_h = c->slots[l.in_slot].h; L.in_w = c->slots[l.in_slot].w;
-      if (l.in_shift != 0) {
-        if (l.op != YL_OP_CONV || l.k < 2 || l.dw_k != 0 || l.in_shift < 0 || l.in_shift > 3)
-          return bad("in_shift needs a kxk (k>1) conv without depthwise prologue");
-        L.in_h <<= l.in_shift; L.in_w <<= l.in_shift;          // dims of the virtually upsampled input
-      }
-      const bool uib = (l.op == YL_OP_CONV && l.c2 > 0);
-      if (c->slots[l.in_slot].c != (uib ? l.c2 : l.cin)) return bad("cin does not match the input slot");
-      if (uib) {
-        if (!l.w2 || l.dw_k == 0 || l.dw_stride < 1 || l.k != 1 || l.head_level >= 0)
-          return bad("fused expand->depthwise->project block: needs w2, a depthwise prologue, 1x1 projection");
-        // workgroup-level halo kernel (yl_ir_kernel: stride 1 / 2, TF-SAME pads) or the per-wave one (yl_uib_kernel)
-        const bool ir = l.out_slot >= 0 && l.out_slot < d->num_slots &&
-                        yl_ir_supported(l.c2, l.cin, l.cout, l.dw_k, l.dw_stride, c->slots[l.out_slot].h, c->slots[l.out_slot].w);
-        if (!ir) {
-          if (l.up_slot >= 0) return fail(c, YL_ERR_UNSUPPORTED, "fused block with an upsample-add: shape not instantiated");
-          if (l.dw_stride != 1) return fail(c, YL_ERR_UNSUPPORTED, "fused inverted-residual block: stride-2 shape not instantiated");
-          if (!yl_uib_supported(l.c2, l.cin, l.cout, l.dw_k))
-            return fail(c, YL_ERR_UNSUPPORTED, "fused inverted-residual block: shape not instantiated / LDS budget exceeded");
-          if ((c->slots[l.in_slot].h & 3) || (c->slots[l.in_slot].w & 3))
-            return fail(c, YL_ERR_UNSUPPORTED, "fused inverted-residual block needs H,W multiples of 4");
-        }
-      }
-    }
-    // output geometry.  Sizes are declared by the host (slot / level dims); pad_t/pad_l are explicit
-    // and the bottom/right padding is implied, so only reachability is checked here.
-    if (l.op == YL_OP_CONV && l.dw_k > 0) {
-      if (l.k != 1 || l.stride != 1) return fail(c, YL_ERR_UNSUPPORTED, "dw prologue needs a 1x1 stride-1 main conv");
-      if (!l.dw_w) return bad("dw prologue weights are NULL");
-      if (l.dw_stride < 1) return bad("bad dw_stride");
-      if ((size_t)(l.dw_k * l.dw_k + 1) * l.cin * sizeof(float) > YL_DW_LDS_MAX) {
-        // beyond the tap image of the generic depthwise-prologue kernels: only the streamed-tap kernel (yl_conv_dws_kernel) runs it
-        const bool dws = l.out_slot >= 0 && l.out_slot < d->num_slots && l.c2 == 0 && l.c3 == 0 && l.scale_slot < 0 && l.head_level < 0 &&
-                         yl_dws_supported(l.cin, l.cout, l.dw_k, l.dw_stride, c->slots[l.out_slot].h, c->slots[l.out_slot].w);
-        if (!dws)
-          return fail(c, YL_ERR_UNSUPPORTED, "dw prologue: taps+bias of all input channels must fit 32 KiB of LDS (or the layer must "
-                                             "be one yl_query_dw_prologue reports as 2)");
-      }
-    }
-    if (l.head_level >= 0) {
-      if (l.op != YL_OP_CONV || l.head_level >= c->L) return bad("bad head_level");
-      L.out_h = L.out_w = c->level_S[l.head_level];
-      if (l.cout != c->E) return bad("head layers must have cout = 5+C+NM (one layer per anchor)");
-      L.head_anchor = head_seen[l.head_level]++;
-      if (L.head_anchor >= c->level_A[l.head_level]) return bad("more head layers than anchors for this level");
-      if (l.res_slot >= 0 || l.up_slot >= 0) return bad("head layers take no residual/upsample input");
-    } else {
-      if (l.out_slot < 0 || l.out_slot >= d->num_slots) return bad("bad out_slot");
-      L.out_h = c->slots[l.out_slot].h; L.out_w = c->slots[l.out_slot].w;
-      const int oc = (l.op == YL_OP_STEMBLOCK) ? (l.c3 > 0 ? l.c3 : l.c2) : ((l.op == YL_OP_CONV && l.c3 > 0) ? l.c3 : l.cout);
-      if (c->slots[l.out_slot].c != oc) return bad("cout does not match the output slot");
-    }
-    if (l.op == YL_OP_STEMBLOCK) {
-      const int sh = (L.in_h + 2 * 0 + l.pad_t + (l.k - 1 - l.pad_t) - l.k) / l.stride + 1;   // symmetric / SAME stem
-      if (L.out_h != (l.dw_k == 3 ? sh : (sh + 2 - 3) / 2 + 1) || L.out_w != L.out_h) return bad("stem block output size mismatch");
-    } else {
-      const bool pro = (l.op == YL_OP_CONV && l.dw_k > 0);
-      const int st = pro ? l.dw_stride : l.stride, pt = pro ? l.dw_pad_t : l.pad_t, pl = pro ? l.dw_pad_l : l.pad_l;
-      const int kk = pro ? l.dw_k : l.k;
-      // the last window must start inside the tensor
-      if ((L.out_h - 1) * st - pt >= L.in_h || (L.out_w - 1) * st - pl >= L.in_w || pt >= kk || pl >= kk ||
-          L.out_h < 1 || L.out_w < 1)
-        return bad("output size inconsistent with stride/padding");
-    }
-    if (l.res_slot >= 0) {
-      if (l.res_slot >= d->num_slots) return bad("bad res_slot");
-      const Slot& r = c->slots[l.res_slot];
-      if (r.h != L.out_h || r.w != L.out_w || r.c != l.cout) return bad("residual shape mismatch");
-    }
-    if (l.up_slot >= 0) {
-      if (l.up_slot >= d->num_slots || l.op != YL_OP_CONV) return bad("bad up_slot");
-      // (fused block: the addend joins the EXPANDED tensor, cin channels)
-      if (c->slots[l.up_slot].c != ((l.op == YL_OP_CONV && l.c2 > 0) ? l.cin : l.cout)) return bad("upsample source channel mismatch");
-    }
-    if (l.op == YL_OP_DW && l.cin != l.cout) return bad("depthwise needs cin == cout");
-    if (l.op != YL_OP_STEM && l.op != YL_OP_STEMBLOCK && (l.cin & 3)) return fail(c, YL_ERR_UNSUPPORTED, "cin must be a multiple of 4");
-    if ((l.res_slot >= 0 || l.up_slot >= 0 || YL_SMOOTH(l.act)) && (l.cout & 3) && l.op == YL_OP_CONV)
-      return fail(c, YL_ERR_UNSUPPORTED, "residual/upsample/SiLU epilogue needs cout % 4 == 0");
-
-    // ---- pack + upload
-    std::vector<float> wp, bias;
-    yl_status s;
-    if (l.op == YL_OP_STEM || l.op == YL_OP_STEMBLOCK) {
-      if (l.op == YL_OP_STEMBLOCK) pack_stem_rows(l.w, l.b, l.cout, wp);
-      else pack_stem(l.w, l.cout, l.cin, l.k, wp);
-      bias.assign(l.cout, 0.0f);
-      if (l.b) memcpy(bias.data(), l.b, l.cout * sizeof(float));
-      if (l.op == YL_OP_STEMBLOCK) {
-        std::vector<float> w2, b2v((size_t)cdiv(l.c2, 16) * 16, 0.0f);
-        if (l.dw_k == 3) {                                           // depthwise taps [c][1][3][3] -> tap-major [9][c]
-          w2.assign((size_t)9 * l.c2, 0.0f);
-          for (int ch = 0; ch < l.c2; ++ch)
-            for (int t = 0; t < 9; ++t) w2[(size_t)t * l.c2 + ch] = l.w2[(size_t)ch * 9 + t];
-        } else
-        pack_conv(l.w2, l.c2, l.cout, 3, w2);
-        if (l.b2) memcpy(b2v.data(), l.b2, l.c2 * sizeof(float));
-        if ((s = upload(c, w2, &L.w2p)) != YL_OK) return s;
-        if ((s = upload(c, b2v, &L.b2)) != YL_OK) return s;
-        if (l.c3 > 0) {
-          // the 1x1 conv's k-blocks are the second conv's 16-wide n-tiles: pack with cin padded to that
-          std::vector<float> w3, b3v((size_t)cdiv(l.c3, 16) * 16, 0.0f);
-          pack_conv(l.w3, l.c3, l.c2, 1, w3);
-          if (l.b3) memcpy(b3v.data(), l.b3, l.c3 * sizeof(float));
-          if ((s = upload(c, w3, &L.w3p)) != YL_OK) return s;
-          if ((s = upload(c, b3v, &L.b3)) != YL_OK) return s;
-        }
-      }
-    } else if (l.op == YL_OP_CONV) {
-      pack_conv(l.w, l.cout, l.cin, l.k, wp);
-      bias.assign((size_t)cdiv(l.cout, 16) * 16 + 128, 0.0f);
-      if (l.b) memcpy(bias.data(), l.b, l.cout * sizeof(float));
-      if (l.k == 3 && l.stride == 1 && l.dw_k == 0 && l.c2 == 0 && l.c3 == 0 && l.pad_t == 1 && l.pad_l == 1 && l.in_shift <= 1 &&
-          l.cin >= 16 && l.cout >= 16 && (l.cout & 3) == 0 && l.head_level < 0 && l.up_slot < 0) {
-        std::vector<float> wn;
-        pack_wino(l.w, l.cout, l.cin, wn);
-        if ((s = upload(c, wn, &L.wino)) != YL_OK) return s;
-        if (l.cin >= 64 && l.cout >= 64 && L.out_h * L.out_w > c->wino_max_hw) c->wino_max_hw = L.out_h * L.out_w;
-      }
-      if (l.head_level >= 0 && c->NM > 0 && (c->NM & 3) == 0 && l.k == 1 && l.dw_k == 0 && l.c2 == 0 && l.c3 == 0 &&
-          5 + c->C <= 96 && l.cout == c->E && c->level_A[l.head_level] == 1) {
-        const int nd = 5 + c->C;
-        std::vector<float> wd, wm, bd((size_t)cdiv(nd, 16) * 16 + 128, 0.0f), bm((size_t)cdiv(c->NM, 16) * 16 + 128, 0.0f);
-        pack_conv(l.w, nd, l.cin, 1, wd);
-        pack_conv(l.w + (size_t)nd * l.cin, c->NM, l.cin, 1, wm);
-        if (l.b) { memcpy(bd.data(), l.b, nd * sizeof(float)); memcpy(bm.data(), l.b + nd, c->NM * sizeof(float)); }
-        if ((s = upload(c, wd, &L.wp_det)) != YL_OK || (s = upload(c, bd, &L.b_det)) != YL_OK ||
-            (s = upload(c, wm, &L.wp_mc)) != YL_OK || (s = upload(c, bm, &L.b_mc)) != YL_OK)
-          return s;
-      }
-      if (l.c3 > 0) {       // chained 1x1 conv [c3][cout][1][1]: its k-blocks are this conv's 16-wide n-tiles
-        if (!l.w3 || l.k < 2 || l.dw_k > 0 || l.c2 > 0 || l.head_level >= 0 || l.res_slot >= 0 || l.up_slot >= 0 || l.in_shift ||
-            (l.cout & 3) || (l.c3 & 3) || l.c3 > 32 || l.cout > 96 || YL_SMOOTH(l.act) || YL_SMOOTH(l.act3))
-          return fail(c, YL_ERR_UNSUPPORTED, "chained 1x1 conv: needs a plain dense k x k conv (<= 96 channels out), c3 <= 32, ReLU-family activations");
-        std::vector<float> w3, b3v((size_t)cdiv(l.c3, 16) * 16, 0.0f);
-        pack_conv(l.w3, l.c3, l.cout, 1, w3);
-        if (l.b3) memcpy(b3v.data(), l.b3, l.c3 * sizeof(float));
-        if ((s = upload(c, w3, &L.w3p)) != YL_OK) return s;
-        if ((s = upload(c, b3v, &L.b3)) != YL_OK) return s;
-      }
-      if (l.c2 > 0) {       // expansion conv of a fused inverted-residual block: [cin][c2][1][1]
-        std::vector<float> w2, b2v((size_t)cdiv(l.cin, 16) * 16, 0.0f);
-        pack_conv(l.w2, l.cin, l.c2, 1, w2);
-        if (l.b2) memcpy(b2v.data(), l.b2, l.cin * sizeof(float));
-        if ((s = upload(c, w2, &L.w2p)) != YL_OK) return s;
-        if ((s = upload(c, b2v, &L.b2)) != YL_OK) return s;
-      }
-      if (l.dw_k > 0) {
-        std::vector<float> dw, dwb;
-        pack_dw(l.dw_w, l.cin, l.dw_k, dw);
-        if ((s = upload(c, dw, &L.dw_w)) != YL_OK) return s;
-        if (l.dw_b) {
-          dwb.assign(l.dw_b, l.dw_b + l.cin);
-          if ((s = upload(c, dwb, &L.dw_b)) != YL_OK) return s;
-        }
-      }
-    } else {
-      pack_dw(l.w, l.cout, l.k, wp);
-      if (l.b) bias.assign(l.b, l.b + l.cout);
-    }
-    if ((s = upload(c, wp, &L.wp)) != YL_OK) return s;
-    if ((s = upload(c, bias, &L.bias)) != YL_OK) return s;
-    L.d.w = L.d.b = L.d.dw_w = L.d.dw_b = nullptr;
+  // the context owns the model from before its first upload: whatever fails below, destroying the context frees every image
+  const std::shared_ptr<Model> m = std::make_shared<Model>();
+  c->m = m;
+  m->device = device_id;
+  static_cast<YlGeometry&>(*m) = prog;
+  static_cast<YlTables&>(*m) = yl_program_tables(prog);
+  init_slots(c);
+  if (prog.layers.empty()) return YL_OK;
+  HIPCHK(c, hipMalloc((void**)&m->zeros, 1024));
+  HIPCHK(c, hipMemset(m->zeros, 0, 1024));
+  m->layers.reserve(prog.layers.size());
+  YlLayerImages im;
+  for (size_t i = 0; i < prog.layers.size(); ++i) {
+    yl_program_pack(prog, i, &im);
+    m->layers.emplace_back();
+    DevLayer& L = m->layers.back();
+    static_cast<YlLayerInfo&>(L) = prog.layers[i];
+    L.d.w = L.d.b = L.d.dw_w = L.d.dw_b = nullptr;      // the caller's arrays need not outlive this call
     L.d.w2 = L.d.b2 = L.d.w3 = L.d.b3 = nullptr;
-    c->layers.push_back(L);
+#define YL_X(name) if ((s = upload(c, im.name, &L.name)) != YL_OK) return s;
+    YL_LAYER_IMAGES(YL_X)
+#undef YL_X
   }
-  for (int l = 0; l < c->L; ++l)
-    if (head_seen[l] != c->level_A[l]) return fail(c, YL_ERR_INVALID, "every level needs one head layer per anchor");
-  if (c->NM > 0) {
-    if (c->proto_slot < 0 || c->proto_slot >= d->num_slots || c->slots[c->proto_slot].c != c->NM)
-      return fail(c, YL_ERR_INVALID, "num_masks > 0 needs proto_slot with num_masks channels");
-  }
-  assign_lanes(c);
-  assign_small_run(c);
-  count_readers(c);
   return YL_OK;
 }
 
@@ -1858,7 +1401,7 @@ yl_status yl_set_option(yl_ctx* c, const char* name, int32_t value) {
   if (!strcmp(name, "dev_select")) { c->opt_dev = value & (int)YL_DEV_MASK; drop_graph(c); return YL_OK; }
   if (!strcmp(name, "head_skip_count")) {   // (the counter pointer rides in the launch parameters: cached graphs are dropped)
     if (value && !c->head_skip_cnt) {
-      HIPCHK(c, hipSetDevice(c->device));
+      HIPCHK(c, hipSetDevice(c->m->device));
       HIPCHK(c, hipMalloc((void**)&c->head_skip_cnt, sizeof(unsigned)));
       HIPCHK(c, hipMemset(c->head_skip_cnt, 0, sizeof(unsigned)));
     }
@@ -1881,7 +1424,7 @@ yl_status yl_get_option(const yl_ctx* c, const char* name, int32_t* value) {
   if (!strcmp(name, "head_skipped_tiles")) {   // tiles skipped since "head_skip_count" was first set (waits for the device)
     unsigned v = 0;
     if (c->head_skip_cnt &&
-        (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
+        (hipSetDevice(c->m->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess ||
          hipMemcpy(&v, c->head_skip_cnt, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess))
       return YL_ERR_HIP;
     *value = (int32_t)(v & 0x7fffffffu);
@@ -1909,23 +1452,23 @@ int32_t yl_query_dw_prologue(int32_t c_in, int32_t c_out, int32_t dw_k, int32_t 
 static yl_status forward_impl(yl_ctx* c, const float* x, int B, float* const* level_out, hipStream_t st,
                               float* layer_ms, const yl_post_cfg* cfg, float* dets, int* counts, int* keep_idx = nullptr) {
   if (!c) return YL_ERR_INVALID;
-  if (c->layers.empty()) return fail(c, YL_ERR_STATE, "context was created without layers");
+  if (c->m->layers.empty()) return fail(c, YL_ERR_STATE, "context was created without layers");
   if (!x || B < 1) return fail(c, YL_ERR_INVALID, "bad input");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   yl_status s = ensure_act(c, B, layer_ms ? 1 : chunks_for(c, B));
   if (s != YL_OK) return s;
   if (cfg && (s = ensure_post(c, B)) != YL_OK) return s;
   if ((s = poison_act(c, st)) != YL_OK) return s;
   Job j;
   j.x = x; j.B = B; j.cfg = cfg; j.dets = dets; j.counts = counts; j.keep_idx = keep_idx;
-  for (int l = 0; l < c->L; ++l) j.outs[l] = (level_out && level_out[l]) ? level_out[l] : c->level_buf[l];
+  for (int l = 0; l < c->m->L; ++l) j.outs[l] = (level_out && level_out[l]) ? level_out[l] : c->level_buf[l];
   if (layer_ms) {        // measurement path: one stream, one chunk, an event pair around every launch
-    std::vector<hipEvent_t> ev(c->layers.size() + 1);
+    std::vector<hipEvent_t> ev(c->m->layers.size() + 1);
     for (auto& e : ev) HIPCHK(c, hipEventCreate(&e));
     s = run_layers(c, x, 0, B, j.outs, st, ev.data());
     if (s == YL_OK) {
       HIPCHK(c, hipStreamSynchronize(st));
-      for (size_t i = 0; i < c->layers.size(); ++i) hipEventElapsedTime(&layer_ms[i], ev[i], ev[i + 1]);
+      for (size_t i = 0; i < c->m->layers.size(); ++i) hipEventElapsedTime(&layer_ms[i], ev[i], ev[i + 1]);
     }
     for (auto& e : ev) hipEventDestroy(e);
     return s;
@@ -1955,7 +1498,7 @@ yl_status yl_last_timing(yl_ctx* c, float* infer_ms, float* post_ms) {
 int64_t yl_activation_bytes(const yl_ctx* c) {
   if (!c || c->plan_n < 1) return 0;
   int64_t t = 0;
-  for (int i = 0; i < c->arena_n; ++i) t += (int64_t)(c->arena_unit + c->se_unit * sizeof(float)) * c->arena_capi[i];
+  for (int i = 0; i < c->arena_n; ++i) t += (int64_t)(c->arena_unit + c->m->se_unit * sizeof(float)) * c->arena_capi[i];
   for (const auto& s : c->slots)
     if (s.pinned) t += (int64_t)s.sz * c->cap_batch;
   return t;
@@ -1965,7 +1508,7 @@ yl_status yl_read_slot(yl_ctx* c, int32_t slot, int32_t B, float* dst, void* str
   if (!c || !dst) return YL_ERR_INVALID;
   if (slot < 0 || slot >= (int)c->slots.size()) return fail(c, YL_ERR_INVALID, "bad slot");
   if (B > c->act_batch || c->plan_n < 1) return fail(c, YL_ERR_STATE, "no forward of >= B images has produced this slot");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   const Slot& s = c->slots[slot];
   if (c->opt_bf16 == 3 && !s.pinned) return fail(c, YL_ERR_UNSUPPORTED, "store_f16: activation slots are fp16 (yl_read_slot hands out fp32)");
   // (with "reuse_slots" on, a tensor that is not an output of the network may have been overwritten by later layers)
@@ -1980,18 +1523,18 @@ yl_status yl_read_slot(yl_ctx* c, int32_t slot, int32_t B, float* dst, void* str
 
 yl_status yl_preprocess(yl_ctx* c, const uint8_t* packed, const yl_pre_image* imgs, int32_t B, float* x, void* stream) {
   if (!c || !packed || !imgs || !x || B < 1) return YL_ERR_INVALID;
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   static_assert(sizeof(yl_pre_image) == 32, "yl_pre_image layout");
-  HIPCHK(c, yl_launch_preprocess(packed, imgs, B, c->img_size, x, c->opt_pre_norm, (hipStream_t)stream));
+  HIPCHK(c, yl_launch_preprocess(packed, imgs, B, c->m->img_size, x, c->opt_pre_norm, (hipStream_t)stream));
   return YL_OK;
 }
 
 yl_status yl_decode(yl_ctx* c, const float* const* levels, int32_t B, int32_t center_mode, int32_t wh_mode,
                     float* box, float* obj, float* cls, void* stream) {
   if (!c || !levels || !box || !obj || B < 1) return YL_ERR_INVALID;
-  if (c->C > 0 && !cls) return fail(c, YL_ERR_INVALID, "cls_dev is NULL");
+  if (c->m->C > 0 && !cls) return fail(c, YL_ERR_INVALID, "cls_dev is NULL");
   if (center_mode < 0 || center_mode > 1 || wh_mode < 0 || wh_mode > 2) return fail(c, YL_ERR_INVALID, "bad mode");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   YlLevels lv;
   fill_levels(c, levels, lv);
   HIPCHK(c, yl_launch_decode_only(lv, B, center_mode, wh_mode, box, obj, cls, (hipStream_t)stream));
@@ -2001,7 +1544,7 @@ yl_status yl_decode(yl_ctx* c, const float* const* levels, int32_t B, int32_t ce
 yl_status yl_forward_decoded(yl_ctx* c, const float* x, int32_t B, int32_t center_mode, int32_t wh_mode, float* box,
                              float* obj, float* cls, void* stream) {
   if (!c || !box || !obj) return YL_ERR_INVALID;
-  if (c->C > 0 && !cls) return fail(c, YL_ERR_INVALID, "cls_dev is NULL");
+  if (c->m->C > 0 && !cls) return fail(c, YL_ERR_INVALID, "cls_dev is NULL");
   if (center_mode < 0 || center_mode > 1 || wh_mode < 0 || wh_mode > 2) return fail(c, YL_ERR_INVALID, "bad mode");
   // the raw levels go to the context's own buffers (two chunk streams, hipGraph: as yl_forward), the decode follows on
   // the caller's stream behind the join
@@ -2018,11 +1561,11 @@ yl_status yl_postprocess(yl_ctx* c, const float* const* levels, int32_t B, const
   if (!c || !levels || !dets || !counts || B < 1) return YL_ERR_INVALID;
   yl_status s = check_cfg(c, cfg);
   if (s != YL_OK) return s;
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   if ((s = ensure_post(c, B)) != YL_OK) return s;
   Job j;
   j.B = B; j.cfg = cfg; j.dets = dets; j.counts = counts; j.keep_idx = keep_idx;
-  for (int l = 0; l < c->L; ++l) j.outs[l] = const_cast<float*>(levels[l]);
+  for (int l = 0; l < c->m->L; ++l) j.outs[l] = const_cast<float*>(levels[l]);
   return submit(c, j, (hipStream_t)stream, false);
 }
 
@@ -2037,16 +1580,16 @@ yl_status yl_predict(yl_ctx* c, const float* x, int32_t B, const yl_post_cfg* cf
 yl_status yl_masks(yl_ctx* c, const float* const* levels, int32_t B, const int32_t* counts, const int32_t* keep_idx,
                    int32_t max_out, float thr, uint8_t* masks, void* stream) {
   if (!c || !counts || !keep_idx || !masks || B < 1 || max_out < 1) return YL_ERR_INVALID;
-  if (c->NM <= 0 || c->proto_slot < 0) return fail(c, YL_ERR_STATE, "context has no mask branch");
-  if (B > c->act_batch || B > c->post_cap_batch || !c->slots[c->proto_slot].pin)
+  if (c->m->NM <= 0 || c->m->proto_slot < 0) return fail(c, YL_ERR_STATE, "context has no mask branch");
+  if (B > c->act_batch || B > c->post_cap_batch || !c->slots[c->m->proto_slot].pin)
     return fail(c, YL_ERR_STATE, "yl_masks needs a preceding yl_predict / yl_forward+yl_postprocess of this batch");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   const float* lp[YL_MAX_LEVELS];
-  for (int l = 0; l < c->L; ++l) lp[l] = (levels && levels[l]) ? levels[l] : c->level_buf[l];
+  for (int l = 0; l < c->m->L; ++l) lp[l] = (levels && levels[l]) ? levels[l] : c->level_buf[l];
   YlLevels lv;
   fill_levels(c, lp, lv);
-  const Slot& ps = c->slots[c->proto_slot];
-  HIPCHK(c, yl_launch_masks(lv, B, ps.pin, ps.h, ps.w, c->NM, c->img_size, c->ws_boxes, counts, keep_idx, max_out, thr,
+  const Slot& ps = c->slots[c->m->proto_slot];
+  HIPCHK(c, yl_launch_masks(lv, B, ps.pin, ps.h, ps.w, c->m->NM, c->m->img_size, c->ws_boxes, counts, keep_idx, max_out, thr,
                             masks, (hipStream_t)stream));
   return YL_OK;
 }
@@ -2057,17 +1600,17 @@ yl_status yl_masks_image(yl_ctx* c, const float* const* levels, int32_t B, const
                          uint8_t* masks, void* stream) {
   if (!c || !dets || !counts || !keep_idx || !out_hw || !mask_off || !masks || B < 1 || max_out < 1 || max_h < 1 || max_w < 1)
     return YL_ERR_INVALID;
-  if (c->NM <= 0 || c->proto_slot < 0) return fail(c, YL_ERR_STATE, "context has no mask branch");
-  if (B > c->act_batch || !c->slots[c->proto_slot].pin)
+  if (c->m->NM <= 0 || c->m->proto_slot < 0) return fail(c, YL_ERR_STATE, "context has no mask branch");
+  if (B > c->act_batch || !c->slots[c->m->proto_slot].pin)
     return fail(c, YL_ERR_STATE, "yl_masks_image needs a preceding yl_predict / yl_forward of this batch");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   const float* lp[YL_MAX_LEVELS];
-  for (int l = 0; l < c->L; ++l) lp[l] = (levels && levels[l]) ? levels[l] : c->level_buf[l];
+  for (int l = 0; l < c->m->L; ++l) lp[l] = (levels && levels[l]) ? levels[l] : c->level_buf[l];
   YlLevels lv;
   fill_levels(c, lp, lv);
-  const Slot& ps = c->slots[c->proto_slot];
+  const Slot& ps = c->slots[c->m->proto_slot];
   static_assert(sizeof(long long) == sizeof(int64_t), "offset type");
-  HIPCHK(c, yl_launch_masks_image(lv, B, ps.pin, ps.h, ps.w, c->NM, c->img_size, dets, counts, keep_idx, max_out, thr,
+  HIPCHK(c, yl_launch_masks_image(lv, B, ps.pin, ps.h, ps.w, c->m->NM, c->m->img_size, dets, counts, keep_idx, max_out, thr,
                                   backmap, out_hw, (const long long*)mask_off, max_h, max_w, packed ? 1 : 0, masks,
                                   (hipStream_t)stream));
   return YL_OK;
@@ -2082,7 +1625,7 @@ yl_status yl_allgather_dets(yl_ctx* c, void* comm, const float* local_dev, int64
   static allgather_fn fn = nullptr;
   if (!fn) fn = (allgather_fn)dlsym(RTLD_DEFAULT, "ncclAllGather");
   if (!fn) return fail(c, YL_ERR_UNSUPPORTED, "ncclAllGather not found: load RCCL (librccl.so) in this process first");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   const int rc = fn(local_dev, all_dev, (size_t)row_floats, 7 /*ncclFloat32*/, comm, (hipStream_t)stream);
   if (rc != 0) {
     char b[96];
@@ -2097,7 +1640,7 @@ yl_status yl_nms(yl_ctx* c, const float* boxes, const float* scores, int32_t n, 
   if (!c || !boxes || !scores || !keep || !count || n < 0 || max_det < 1) return YL_ERR_INVALID;
   if (impl != YL_NMS_TORCHVISION && impl != YL_NMS_GREEDY) return fail(c, YL_ERR_INVALID, "bad nms_impl");
   if (n >= (1 << 20)) return fail(c, YL_ERR_UNSUPPORTED, "n must be < 2^20");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   hipStream_t st = (hipStream_t)stream;
   if (n == 0) {
     HIPCHK(c, hipMemsetAsync(count, 0, sizeof(int), st));
@@ -2136,13 +1679,13 @@ static yl_status loss_check(yl_ctx* c, const float* const* levels, int32_t B, co
                             const int32_t* gt_off, int32_t num_gt, const yl_loss_cfg* cfg) {
   if (!c || !levels || !cfg || B < 1 || num_gt < 0) return YL_ERR_INVALID;
   if (num_gt > 0 && (!gt_xyxy || !gt_label || !gt_off)) return fail(c, YL_ERR_INVALID, "ground-truth arrays are NULL");
-  if (cfg->num_classes != c->C || cfg->img_size != c->img_size)
+  if (cfg->num_classes != c->m->C || cfg->img_size != c->m->img_size)
     return fail(c, YL_ERR_INVALID, "yl_loss_cfg num_classes / img_size differ from the context's");
-  if (c->C < 1) return fail(c, YL_ERR_INVALID, "the loss needs at least one class");
+  if (c->m->C < 1) return fail(c, YL_ERR_INVALID, "the loss needs at least one class");
   if (cfg->center_mode < 0 || cfg->center_mode > 1 || cfg->wh_mode < 0 || cfg->wh_mode > 2)
     return fail(c, YL_ERR_INVALID, "bad mode");
-  for (int l = 0; l < c->L; ++l)
-    if (c->level_A[l] != 1)
+  for (int l = 0; l < c->m->L; ++l)
+    if (c->m->level_A[l] != 1)
       return fail(c, YL_ERR_UNSUPPORTED, "LossAF is defined for one anchor per cell (the reference builds h*w anchors per level)");
   if (cfg->topk_limit < 1 || cfg->topk_limit > YL_LOSS_MAX_TOPK)
     return fail(c, YL_ERR_UNSUPPORTED, "topk_limit must be 1.." + std::to_string(YL_LOSS_MAX_TOPK));
@@ -2157,13 +1700,13 @@ static yl_status loss_forward(yl_ctx* c, const float* const* levels, int32_t B, 
   if (!out4) return YL_ERR_INVALID;
   const yl_status chk = loss_check(c, levels, B, gt_xyxy, gt_label, gt_off, num_gt, cfg);
   if (chk != YL_OK) return chk;
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   if (B > c->loss_cap_batch) {
     hipFree(c->ws_loss_keys); hipFree(c->ws_loss_neg); hipFree(c->ws_loss_pi); hipFree(c->ws_loss_pos);
     c->ws_loss_keys = nullptr; c->ws_loss_neg = nullptr; c->ws_loss_pi = nullptr; c->ws_loss_pos = nullptr;
     c->loss_cap_batch = 0;
-    HIPCHK(c, hipMalloc((void**)&c->ws_loss_keys, (size_t)B * c->N * sizeof(unsigned long long)));
-    HIPCHK(c, hipMalloc((void**)&c->ws_loss_neg, (size_t)B * c->N * sizeof(float)));
+    HIPCHK(c, hipMalloc((void**)&c->ws_loss_keys, (size_t)B * c->m->N * sizeof(unsigned long long)));
+    HIPCHK(c, hipMalloc((void**)&c->ws_loss_neg, (size_t)B * c->m->N * sizeof(float)));
     HIPCHK(c, hipMalloc((void**)&c->ws_loss_pi, (size_t)B * 3 * sizeof(float)));
     HIPCHK(c, hipMalloc((void**)&c->ws_loss_pos, (size_t)B * sizeof(int)));
     c->loss_cap_batch = B;
@@ -2205,16 +1748,16 @@ yl_status yl_loss_af_backward(yl_ctx* c, const float* const* levels, int32_t B, 
   const yl_status chk = loss_check(c, levels, B, gt_xyxy, gt_label, gt_off, num_gt, cfg);
   if (chk != YL_OK) return chk;
   if (!assign || !sel || !grad_out || !grad_levels) return fail(c, YL_ERR_INVALID, "yl_loss_af_backward: a NULL argument");
-  for (int l = 0; l < c->L; ++l)
+  for (int l = 0; l < c->m->L; ++l)
     if (!grad_levels[l]) return fail(c, YL_ERR_INVALID, "yl_loss_af_backward: a NULL gradient tensor");
-  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipSetDevice(c->m->device));
   YlLevels lv;
   fill_levels(c, levels, lv);
   YlLossGradP p;
   memset(&p, 0, sizeof(p));
   p.cfg = *cfg;
   p.gt = gt_xyxy; p.label = gt_label; p.assign = assign; p.sel = sel; p.gout = grad_out; p.B = B;
-  for (int l = 0; l < c->L; ++l) p.out[l] = grad_levels[l];
+  for (int l = 0; l < c->m->L; ++l) p.out[l] = grad_levels[l];
   HIPCHK(c, yl_launch_loss_af_grad(lv, p, (hipStream_t)stream));
   return YL_OK;
 }

@@ -2669,7 +2669,7 @@ hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st) {
 //   per k-block:  4x4 input patch of the lane's tile (16 float4 from L1/L2, zero buffer outside the image)
 //                 column transform in place (16 float4 ops), then per position xi one row-transform op -> B operand,
 //                 two A fragments of U_xi from the LDS chunk, 8 MFMAs
-// The U image ([n-group][k-block][xi][2][64][4], pack_wino in yl_api.hip) streams through LDS in 32 KiB chunks,
+// The U image ([n-group][k-block][xi][2][64][4], pack_wino in yl_program.cpp) streams through LDS in 32 KiB chunks,
 // double-buffered, one barrier per k-block, 8 waves (128 tiles = 512 output pixels) share a chunk; (n-group, m-tile)
 // items group-major in XCD bands like yl_conv_kxk_kernel.  Output transform, bias, ReLU-family clamp and the four
 // NHWC float4 stores per n-tile in the epilogue (ReLU-family clamp or SiLU).

@@ -8,13 +8,7 @@
 #include <utility>
 #include "../../include/yololite_hip.h"
 #include "yl_lp.h"
-
-// activations that are not a clamp: SiLU runs in the conv kernels' generic epilogue (the fast clamp epilogues refuse it);
-// GELU and ReLU + learnable affine (ABI v5: YL_ACT_POSTPASS) never reach a conv kernel -- the executor launches the layer with
-// no activation (and no residual) and applies them in an element-wise pass over the output (yl_ops.hip: yl_act_kernel), so the
-// hot kernels carry no code for them
-#define YL_SMOOTH(a) ((a) >= YL_ACT_SILU)
-#define YL_ACT_POSTPASS(a) ((a) >= YL_ACT_GELU)
+#include "yl_shapes.h"   // yl_stemblock_supported, yl_uib_supported, yl_ir_supported, yl_dws_supported
 
 #define YL_NUM_CU 256          // MI355X: 8 XCDs x 32 CUs
 #define YL_LDS_KEYS_MAX 16384  // 64-bit sort keys that fit the 160 KiB LDS of one CU (128 KiB)
@@ -108,7 +102,7 @@ typedef float yl_act_t;
 // ---- conv layer parameters (one struct for all conv kernels) -----------------------------------
 struct YlConvP {
   const yl_act_t* x;     // input: NHWC [B,H,W,Cin]  (STEM: the fp32 NCHW network input [B,Cin,H,W], whatever yl_act_t is)
-  const float* wp;       // packed weights (see yl_api.cpp pack_* for the layouts)
+  const float* wp;       // packed weights (see yl_program.cpp pack_* for the layouts)
   const float* bias;     // [Npad16] (zero padded) or nullptr
   const yl_act_t* res;   // residual NHWC [B,OH,OW,N] or nullptr
   const yl_act_t* up;    // NHWC [B,UH,UW,N] nearest-upsampled and added, or nullptr
@@ -371,8 +365,6 @@ hipError_t yl_launch_conv_dpq(const YlConvP& p, hipStream_t st);
 // dense 3x3 with 16 / 32 -> <= 16 channels on large grids, window in LDS (yl_dpp.hip, round 6; fp32 only)
 hipError_t yl_launch_conv_k3w(const YlConvP& p, hipStream_t st);
 bool yl_dpq_supported(int cin, int cmid, int cout, int oh, int ow);
-bool yl_stemblock_supported(int c1, int c2, int c3);
-bool yl_uib_supported(int c1, int cmid, int n, int dk);
 // block-cooperative depthwise -> 1x1 kernel (yl_convc.hip); hipErrorNotSupported = shape outside its limits
 hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st);
 // wave-autonomous 1x1 conv for small pixel counts (yl_convc.hip); hipErrorNotSupported = not a plain 1x1 layer
@@ -380,7 +372,6 @@ hipError_t yl_launch_conv_pwt(const YlConvP& p, hipStream_t st);
 hipError_t yl_launch_conv_pwt_multi(const YlConvP* ps, int n, hipStream_t st);
 // fused inverted-residual block with a workgroup-level halo (yl_convc.hip, round 3); hipErrorNotSupported = yl_uib_kernel
 hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st);
-bool yl_ir_supported(int c1, int cmid, int n, int dk, int ds, int oh, int ow);
 // plain 1x1 conv with a double-buffered weight stream for wide layers (yl_convc.hip); hipErrorNotSupported = pwt runs it
 hipError_t yl_launch_conv_pws(const YlConvP& p, hipStream_t st);
 // dense k x k conv with a double-buffered weight stream (yl_convc.hip); hipErrorNotSupported = other kernel runs it
@@ -400,6 +391,5 @@ hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st);
 // depthwise k x k -> 1x1 for >= 192 depthwise channels: streamed 1x1 weights AND tap weights, halo patch through LDS (yl_convc.hip,
 // round 5); hipErrorNotSupported = shape not instantiated
 hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st);
-bool yl_dws_supported(int cin, int n, int dk, int ds, int oh, int ow);
 // Winograd F(2x2,3x3) dense 3x3 (yl_convc.hip); hipErrorNotSupported = not this layer
 hipError_t yl_launch_conv_wino(const YlConvP& p, hipStream_t st);

@@ -112,7 +112,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void yl_stemblock_kernel(YlConvP p) {
   __syncthreads();
 
   const int plane = p.H * p.W;
-  // per-lane constants: tap decode of the lane's k slots.  K order (shared with pack_stem_rows in yl_api.hip): the 27
+  // per-lane constants: tap decode of the lane's k slots.  K order (shared with pack_stem_rows in yl_program.cpp): the 27
   // taps are 9 rows (c,ky) of 3 consecutive kx.  Lane group kq owns rows 2kq and 2kq+1 whole (slots 0-2, 3-5) and one
   // element of row 8 (slot 6, kx = kq; group 3: the bias slot), so a lane's 7 operands per patch pixel are two 12-byte
   // loads and one 4-byte load instead of seven scattered dwords.

@@ -24,6 +24,53 @@ def _stream_ptr(device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def model_desc(img_size: int, num_classes: int, level_size: Sequence[int], level_anchors: Sequence[int],
+               program: Optional[Program] = None, num_masks: int = 0):
+    """Fill a yl_model_desc from a Program (None or no layers: a post-processing-only model).  Needs no device.
+    Returns (descriptor, keep): `keep` lists the host arrays the descriptor points into -- they must outlive yl_create."""
+    d = _lib.yl_model_desc()
+    d.abi_version, d.img_size, d.in_channels = _lib.YL_ABI_VERSION, int(img_size), 3
+    d.num_classes, d.num_levels = int(num_classes), len(level_size)
+    d.num_masks = int(program.num_masks) if program is not None else int(num_masks)
+    d.proto_slot = int(program.proto_slot) if program is not None else -1
+    for i in range(len(level_size)):
+        d.level_size[i], d.level_anchors[i] = int(level_size[i]), int(level_anchors[i])
+    keep = []
+    if program is not None and program.layers:
+        sh = np.ascontiguousarray([s[0] for s in program.slots], np.int32)
+        sw = np.ascontiguousarray([s[1] for s in program.slots], np.int32)
+        sc = np.ascontiguousarray([s[2] for s in program.slots], np.int32)
+        keep += [sh, sw, sc]
+        d.num_slots = len(program.slots)
+        d.slot_h = sh.ctypes.data_as(_lib._ip)
+        d.slot_w = sw.ctypes.data_as(_lib._ip)
+        d.slot_c = sc.ctypes.data_as(_lib._ip)
+        arr = (_lib.yl_layer * len(program.layers))()
+
+        def fp(a):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, np.float32)
+            keep.append(a)
+            return a.ctypes.data_as(_lib._fp)
+
+        for i, l in enumerate(program.layers):
+            y = arr[i]
+            y.op, y.in_slot, y.out_slot, y.res_slot, y.up_slot = l.op, l.in_slot, l.out_slot, l.res_slot, l.up_slot
+            y.head_level, y.cin, y.cout = l.head_level, l.cin, l.cout
+            y.k, y.stride, y.pad_t, y.pad_l, y.act, y.in_shift = l.k, l.stride, l.pad_t, l.pad_l, l.act, l.in_shift
+            y.dw_k, y.dw_stride, y.dw_pad_t, y.dw_pad_l, y.dw_act = l.dw_k, l.dw_stride, l.dw_pad_t, l.dw_pad_l, l.dw_act
+            y.w, y.b, y.dw_w, y.dw_b = fp(l.w), fp(l.b), fp(l.dw_w), fp(l.dw_b)
+            y.c2, y.act2, y.c3, y.act3 = l.c2, l.act2, l.c3, l.act3
+            y.w2, y.b2, y.w3, y.b3 = fp(l.w2), fp(l.b2), fp(l.w3), fp(l.b3)
+            y.scale_slot, y.reserved0 = l.scale_slot, 0
+            y.lab_scale, y.lab_bias, y.eps, y.out_ch_off = l.lab_scale, l.lab_bias, l.eps, l.out_ch_off
+        d.num_layers = len(program.layers)
+        d.layers = arr
+        keep.append(arr)
+    return d, keep
+
+
 class HipContext:
     """Owns one yl_ctx.  Post-processing-only contexts are created with no layers."""
 
@@ -38,48 +85,10 @@ class HipContext:
         self.level_size, self.level_anchors = [int(s) for s in level_size], [int(a) for a in level_anchors]
         self.L = len(self.level_size)
         self.N = sum(a * s * s for a, s in zip(self.level_anchors, self.level_size))
-        d = _lib.yl_model_desc()
         self.NM = int(program.num_masks) if program is not None else int(num_masks)
         self.proto_slot = int(program.proto_slot) if program is not None else -1
         self.E = 5 + self.C + self.NM
-        d.abi_version, d.img_size, d.in_channels = _lib.YL_ABI_VERSION, self.img_size, 3
-        d.num_classes, d.num_levels = self.C, self.L
-        d.num_masks, d.proto_slot = self.NM, self.proto_slot
-        for i in range(self.L):
-            d.level_size[i], d.level_anchors[i] = self.level_size[i], self.level_anchors[i]
-        keep = []                                        # host arrays must outlive yl_create
-        if program is not None and program.layers:
-            sh = np.ascontiguousarray([s[0] for s in program.slots], np.int32)
-            sw = np.ascontiguousarray([s[1] for s in program.slots], np.int32)
-            sc = np.ascontiguousarray([s[2] for s in program.slots], np.int32)
-            keep += [sh, sw, sc]
-            d.num_slots = len(program.slots)
-            d.slot_h = sh.ctypes.data_as(_lib._ip)
-            d.slot_w = sw.ctypes.data_as(_lib._ip)
-            d.slot_c = sc.ctypes.data_as(_lib._ip)
-            arr = (_lib.yl_layer * len(program.layers))()
-
-            def fp(a):
-                if a is None:
-                    return None
-                a = np.ascontiguousarray(a, np.float32)
-                keep.append(a)
-                return a.ctypes.data_as(_lib._fp)
-
-            for i, l in enumerate(program.layers):
-                y = arr[i]
-                y.op, y.in_slot, y.out_slot, y.res_slot, y.up_slot = l.op, l.in_slot, l.out_slot, l.res_slot, l.up_slot
-                y.head_level, y.cin, y.cout = l.head_level, l.cin, l.cout
-                y.k, y.stride, y.pad_t, y.pad_l, y.act, y.in_shift = l.k, l.stride, l.pad_t, l.pad_l, l.act, l.in_shift
-                y.dw_k, y.dw_stride, y.dw_pad_t, y.dw_pad_l, y.dw_act = l.dw_k, l.dw_stride, l.dw_pad_t, l.dw_pad_l, l.dw_act
-                y.w, y.b, y.dw_w, y.dw_b = fp(l.w), fp(l.b), fp(l.dw_w), fp(l.dw_b)
-                y.c2, y.act2, y.c3, y.act3 = l.c2, l.act2, l.c3, l.act3
-                y.w2, y.b2, y.w3, y.b3 = fp(l.w2), fp(l.b2), fp(l.w3), fp(l.b3)
-                y.scale_slot, y.reserved0 = l.scale_slot, 0
-                y.lab_scale, y.lab_bias, y.eps, y.out_ch_off = l.lab_scale, l.lab_bias, l.eps, l.out_ch_off
-            d.num_layers = len(program.layers)
-            d.layers = arr
-            keep.append(arr)
+        d, keep = model_desc(self.img_size, self.C, self.level_size, self.level_anchors, program, self.NM)
         self.num_layers = int(d.num_layers)
         self.proto_shape = tuple(program.slots[self.proto_slot]) if self.proto_slot >= 0 else None
         h = C.c_void_p()

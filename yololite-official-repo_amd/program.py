@@ -309,7 +309,7 @@ def zoo_meta(name: str, num_classes: int = 80, img_size: int = 640, **kw) -> dic
 _ACT = {"none": 0, "relu": 1, "relu6": 2, "silu": 3, "gelu": 4, "relu_lab": 5}
 _OP_STEM, _OP_CONV, _OP_DW, _OP_STEMBLOCK, _OP_SE = 0, 1, 2, 3, 4
 _OP_POOL, _OP_COPY, _OP_LN, _OP_GRN, _OP_NHWC4 = 5, 6, 7, 8, 9
-DW_PROLOGUE_LDS_MAX = 32 * 1024      # bytes; mirrors YL_DW_LDS_MAX in csrc/yl_api.hip
+DW_PROLOGUE_LDS_MAX = 32 * 1024      # bytes; mirrors YL_DW_LDS_MAX in csrc/yl_program.h
 
 
 def _query_fused_block(c_in, c_mid, c_out, dk, ds, oh, ow) -> int:
