@@ -769,6 +769,83 @@ yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_h
  * whether a forward is held for yl_head_backward. */
 yl_status yl_head_held(const yl_head* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
 
+/* ---- trainable depthwise FPN neck (reference scripts/model/model_v2.py:285-294, :337-361, YOLOLiteMS_CPU) -------------
+ * Forward and backward of the whole top-down neck on the device.  Levels go finest first (p3, p4, p5; with use_p2: p2
+ * first) and are square; level L - 1 is the coarsest.  The forward runs coarsest first:
+ *     t_k = Wlat_k . c_k + blat_k   (+ up(p_{k+1}) for k < L - 1; up = nearest, torch's index rule)
+ *     p_k = block_{d-1}( ... block_0(t_k))      block = the heads' block (yl_head_block)
+ * and the backward finest first: G_k = gp_k (+ up^T(gt_{k-1}) for k > 0), the blocks back to gt_k = dL/dt_k, then
+ * dWlat_k = gt_k^T . c_k, dblat_k = colsum gt_k, dc_k = gt_k . Wlat_k.
+ * Parameters are read in PyTorch layout from the caller's tensors on every call, at any 4-byte boundary; c / p / gp / dc
+ * are NHWC fp32, 16-byte aligned.  channels % 4 != 0 or in_channels[k] % 4 != 0: YL_ERR_UNSUPPORTED.  The P6 path and
+ * the dense-3x3 + SiLU smooth blocks of YOLOLiteMS are not implemented.  YL_HEAD_TRAIN / YL_HEAD_SAVE mean what they
+ * mean for the heads; with YL_HEAD_SAVE the handle keeps, per level, t_k and every block's d, z, h and statistics
+ * (the last block's h is a copy of p_k: the caller's tensor may change before the backward), without it every level
+ * runs in one level's buffers.  Deterministic in the way of the heads: per-tile partials summed in tile order in
+ * float64, no floating-point atomics; the transposed upsample is a gather over the contiguous pre-image of each cell. */
+#define YL_NECK_MAX_DEPTH 4
+#define YL_NECK_MAX_LEVELS 4
+typedef struct yl_neck yl_neck;
+typedef struct yl_neck_cfg {
+  int32_t channels;                           /* F = fpn_channels */
+  int32_t depth;                              /* blocks per smooth, 1..YL_NECK_MAX_DEPTH */
+  int32_t num_levels;                         /* L, 1..YL_NECK_MAX_LEVELS */
+  int32_t in_channels[YL_NECK_MAX_LEVELS];    /* Cin of each level's feature map, finest first */
+  int32_t reserved0;
+} yl_neck_cfg;
+typedef struct yl_neck_level {
+  float* lat_w;                               /* lateral{k}.weight [F][Cin][1][1] */
+  float* lat_b;                               /* lateral{k}.bias [F] */
+  yl_head_block block[YL_NECK_MAX_DEPTH];     /* smooth{k}.block.{4i, 4i+1, 4i+2} */
+} yl_neck_level;
+typedef struct yl_neck_tensors {              /* the parameters, or where their gradients go (NULL = not wanted) */
+  yl_neck_level level[YL_NECK_MAX_LEVELS];
+} yl_neck_tensors;
+typedef struct yl_neck_level_plan {
+  int32_t rows;                               /* M_k = batch * S_k * S_k */
+  int32_t stat_tiles, gemm_tiles;             /* tiles of stat_rows / gemm_rows rows */
+  int32_t wgrad_rows, wgrad_splits;           /* dz^T . d of a block's 1x1 (F x F): rows per split, splits */
+  int32_t lgrad_rows, lgrad_splits;           /* gt^T . c of the lateral (Cin x F) */
+  int32_t reserved0;
+  int64_t saved_bytes;                        /* (1 + 3 depth) M_k F 4 + depth 2 F 4: t_k; d, z, h and statistics per block */
+} yl_neck_level_plan;
+typedef struct yl_neck_plan_info {
+  int32_t stat_rows, gemm_rows;
+  yl_neck_level_plan level[YL_NECK_MAX_LEVELS];
+  int64_t saved_bytes;                        /* sum of the levels' saved_bytes (YL_HEAD_SAVE) */
+  int64_t nosave_bytes;                       /* without YL_HEAD_SAVE: 4 Mmax F 4 + 2 F 4, t and ONE block of the largest level */
+  int64_t workspace_bytes;                    /* 3 Mmax F 4 (two gradients in flight and gt) + the float64 partials of the
+                                                 largest level, rounded up to 16 + 2 F 4 + the largest split partials */
+  int64_t table_bytes;                        /* the nearest maps: per k < L - 1, (S_k + 2 S_{k+1}) int32 */
+} yl_neck_plan_info;
+/* A pure host function: tile t of a cut covers the rows [t * rows_per_tile, min(M, (t + 1) * rows_per_tile)). */
+yl_status yl_neck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* sizes, yl_neck_plan_info* out);
+/* torch's nearest rule for an axis of `in` cells read at `out`: src[o] = min((int)floorf(o * ((float)in / out)), in - 1),
+ * and the pre-image of source cell i is the destination range [lo[i], hi[i]) (the map is monotone).  Host only. */
+yl_status yl_neck_nearest_map(int32_t out, int32_t in, int32_t* src, int32_t* lo, int32_t* hi);
+yl_status yl_neck_create(int32_t device, const yl_neck_cfg* cfg, yl_neck** out);
+void yl_neck_destroy(yl_neck* h);
+/* Enqueues the forward: per level 1 launch for the lateral (bias and upsample-add in its epilogue) and per block 4
+ * launches (5 with YL_HEAD_TRAIN); with YL_HEAD_SAVE one device-to-device copy per level besides (not counted).
+ * c_dev[k]: [B, S_k, S_k, Cin_k]; p_dev[k]: [B, S_k, S_k, F], written.  YL_HEAD_TRAIN with batch * S_k * S_k == 1 on any
+ * level: YL_ERR_INVALID before any launch.  The nearest maps are computed on the host and uploaded when `sizes` change
+ * (synchronising the device), as are the buffers when they must grow. */
+yl_status yl_neck_forward(yl_neck* h, const yl_neck_tensors* params, const float* const* c_dev, int32_t batch,
+                          const int32_t* sizes, uint32_t flags, float* const* p_dev, void* stream, int32_t* launches);
+/* Enqueues the backward of the held forward (YL_ERR_STATE if there is none of this batch and these sizes).  gp_dev[k]:
+ * the gradient of p_k.  Every non-NULL tensor of `grads` and every non-NULL dc_dev[k] is OVERWRITTEN.  What nobody
+ * asked for is not run.  Level k is walked only if something of a level >= k is wanted (a parameter or dc), finest
+ * first up to the coarsest such level K:
+ *   1 launch for G_k when k > 0 (the gather of gt_{k-1} plus gp_k);
+ *   the blocks, last first, as in yl_head_backward: per block [1 sums if train or gamma / beta wanted] + 1 (bn grads)
+ *     + 1 (dz) + [2 if pw wanted] + 1 (dd) + [2 if dw wanted] + [1 input gradient], stopping at the last thing wanted;
+ *     gt_k is wanted when something of the lateral k, dc_k or a level > k is;
+ *   2 launches for dWlat_k, 2 for dblat_k, 1 for dc_k, each only where wanted. */
+yl_status yl_neck_backward(yl_neck* h, const yl_neck_tensors* params, const yl_neck_tensors* grads,
+                           const float* const* c_dev, const float* const* gp_dev, float* const* dc_dev, int32_t batch,
+                           const int32_t* sizes, void* stream, int32_t* launches);
+yl_status yl_neck_held(const yl_neck* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,70 @@
+"""What the FPN-neck GPU tests and tools/neck_train_time.py share: a DetectNeck with a case's weights, one forward +
+backward of it, and the device error and bar of every fixture tensor."""
+import numpy as np
+import torch
+
+import yololite_amd as ya
+from _neck_cases import bar, case_inputs, fixture_tensors, level_names
+
+DEV = "cuda:0"
+
+
+def neck_of(case, inputs, train=True):
+    m = ya.DetectNeck(case["Cin"], case["F"], case["depth"], level_names=level_names(case))
+    sd = {}
+    for lv in inputs:
+        sd.update(lv["params"]); sd.update(lv["buffers"])
+    m.load_state_dict({k: torch.as_tensor(v) for k, v in sd.items()})
+    return m.to(DEV).train(train)
+
+
+def run(m, inputs, c_grad=True, layout="nhwc"):
+    """forward + backward with the case's gp -> per level {fixture tensor name: cpu tensor}.  c_grad: one bool, or one
+    per level"""
+    m.zero_grad(set_to_none=True)
+    want = [c_grad] * len(inputs) if isinstance(c_grad, bool) else list(c_grad)
+    cs = []
+    for lv, w in zip(inputs, want):
+        c = torch.from_numpy(lv["c"]).to(DEV)
+        if layout == "nchw":                               # contiguous NCHW memory
+            c = c.permute(0, 3, 1, 2).contiguous()
+        elif layout == "channels_last":                    # NCHW shape over NHWC memory
+            c = c.permute(0, 3, 1, 2)
+        cs.append(c.requires_grad_(w))
+    ps = m(cs, layout="nhwc" if layout == "nhwc" else "nchw")
+    if any(p.requires_grad for p in ps):
+        torch.autograd.backward(ps, [torch.from_numpy(lv["gp"]).to(DEV) for lv in inputs])
+    out = []
+    sd = m.state_dict()
+    for lv, c, p in zip(inputs, cs, ps):
+        k = lv["k"]
+        d = {"p": p.detach().cpu()}
+        if c.grad is not None:
+            g = c.grad if layout == "nhwc" else c.grad.permute(0, 2, 3, 1)
+            d["dc"] = g.contiguous().cpu()
+        for t in range(m.depth):
+            for s in ("running_mean", "running_var", "num_batches_tracked"):
+                d[f"{s}.{t}"] = sd[f"smooth{k}.block.{4 * t + 2}.{s}"].cpu().clone()
+        for n, q in m.named_parameters():
+            if n.startswith((f"lateral{k}.", f"smooth{k}.")) and q.grad is not None:
+                d["g." + n] = q.grad.cpu().clone()
+        out.append(d)
+    return out
+
+
+def parity_ratios(case, mode, z):
+    """{(level, tensor): (error, bar)} of one case and mode"""
+    inputs = case_inputs(case)
+    got = run(neck_of(case, inputs, mode == "train"), inputs)
+    out = {}
+    for li, d in enumerate(got):
+        want = fixture_tensors(z, case, mode, li)
+        assert set(d) == set(want), sorted(set(d) ^ set(want))
+        for n, (r64, idx, e32, m64) in want.items():
+            g = d[n].numpy().reshape(-1)
+            if n.startswith("num_batches_tracked"):
+                assert int(g[0]) == int(r64[0]), (case["name"], mode, li, n)
+                continue
+            g = g.astype(np.float64)
+            out[(li, n)] = (float(np.abs((g if idx is None else g[idx]) - r64).max()), bar(e32, m64))
+    return out

@@ -1,0 +1,309 @@
+"""Trainable FPN neck on the device (yololite_amd.neckops.DetectNeck, csrc/yl_neck.hip) against the reference's fixture,
+the executor, and the CPU float64 training loop.
+
+Fixture parity, per case, level and tensor: the bar is max(4 x the reference's own fp32 error, 2 fp32 ulps at the
+tensor's largest magnitude), the rule of the head tests; the worst device error / bar of each case is written to
+profiles/neck_train_parity.json."""
+import copy
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import yololite_amd as ya
+from yololite_amd.program import synth_state_dict, zoo_meta
+from _head_np import head_forward
+from _neck_cases import CASES, E2E, FIXTURE, bar, case_inputs, fixture_tensors, head_inputs, modes
+from _neck_dev import DEV, neck_of as _neck, parity_ratios, run as _run
+from _neck_np import neck_all, neck_forward
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PARITY = os.path.join(ROOT, "profiles", "neck_train_parity.json")
+BY_NAME = {c["name"]: c for c in CASES}
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_fixture_parity(case):
+    z = np.load(FIXTURE)
+    bad, worst = [], {}
+    for mode in modes(case):
+        for (li, n), (err, b) in parity_ratios(case, mode, z).items():
+            print(f"{case['name']:6s} {mode:5s} L{li} {n:32s} err {err:.3e}  bar {b:.3e}  ratio {err / b:.3f}")
+            if err / b > worst.get(mode, (0.0,))[0]:
+                worst[mode] = (err / b, f"L{li} {n}")
+            if not err <= b:
+                bad.append((mode, li, n, err, b))
+    try:                                                   # the figures of this run, beside the others' (best effort)
+        table = json.load(open(PARITY)) if os.path.exists(PARITY) else {}
+        table[case["name"]] = {m: {"worst_ratio": round(r, 4), "tensor": t} for m, (r, t) in worst.items()}
+        with open(PARITY, "w") as f:
+            json.dump(table, f, indent=1, sort_keys=True)
+            f.write("\n")
+    except OSError:
+        pass
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in CASES])
+def test_sampled_tensors_agree_with_the_restatement_everywhere(name):
+    """the fixture stores tensors above 8192 elements at a sample; here every element of those is held to the float64
+    restatement (which test_neck_train_cpu.py ties to the fixture), under the fixture's bar"""
+    case = BY_NAME[name]
+    z = np.load(FIXTURE)
+    sampled = [(li, n) for li in range(len(case["sizes"])) for n, v in fixture_tensors(z, case, "train", li).items()
+               if v[1] is not None]
+    if not sampled:
+        return                                             # nothing of this case is stored sampled
+    inputs = case_inputs(case)
+    got = _run(_neck(case, inputs), inputs)
+    ref = neck_all(inputs, case["depth"], True)
+    for li, n in sampled:
+        _, _, e32, m64 = fixture_tensors(z, case, "train", li)[n]
+        err = np.abs(got[li][n].numpy().astype(np.float64) - ref[li][n]).max()
+        assert err <= bar(e32, m64), (li, n, err, bar(e32, m64))
+
+
+def _same(a, b):
+    assert set(a) == set(b)
+    for n in a:
+        assert torch.equal(a[n], b[n]), n
+
+
+def test_two_runs_give_the_same_bits_in_both_input_layouts():
+    for case in (BY_NAME["odd"], BY_NAME["rows"]):
+        inputs = case_inputs(case)
+        first = _run(_neck(case, inputs), inputs)
+        for layout in ("nhwc", "nchw", "channels_last"):
+            again = _run(_neck(case, inputs), inputs, layout=layout)
+            for a, b in zip(first, again):
+                _same(a, b)
+
+
+def test_gradients_nobody_asked_for_are_not_computed():
+    """the launch counts are those include/yololite_hip.h documents.  depth 1, train mode: a block walked for its input
+    gradient alone is 5 launches (sums, bn grads, dz, dd, input gradient), with all its parameters 9 (8 without the
+    input gradient); a lateral is 2 + 2 + 1; the gather of a level below the finest is 1"""
+    case = BY_NAME["base"]
+    inputs = case_inputs(case)
+    m = _neck(case, inputs)
+    full = _run(m, inputs)
+    assert m.last_launches() == {"forward": 3 * (1 + 5), "backward": (9 + 5) + 2 * (1 + 9 + 5)}
+    # no feature map requires grad: three dc launches less, the same parameter gradients
+    m = _neck(case, inputs)
+    nodc = _run(m, inputs, c_grad=False)
+    assert m.last_launches()["backward"] == (9 + 4) + 2 * (1 + 9 + 4)
+    for a, b in zip(full, nodc):
+        assert "dc" not in b
+        _same({n: v for n, v in a.items() if n != "dc"}, b)
+    # only smooth5's parameters: every level's chain is walked, no lateral launch runs
+    m = _neck(case, inputs)
+    for n, p in m.named_parameters():
+        p.requires_grad_(n.startswith("smooth5."))
+    out = _run(m, inputs, c_grad=False)
+    assert m.last_launches()["backward"] == 5 + (1 + 5) + (1 + 8)
+    for n, p in m.named_parameters():
+        assert (p.grad is None) == (not n.startswith("smooth5.")), n
+    for a, b in zip(full, out):
+        _same({n: v for n, v in a.items() if n in b}, b)
+    assert sorted(n for n in out[2] if n.startswith("g.")) == sorted(n for n in full[2] if n.startswith("g.smooth5."))
+    # only lateral3: levels 4 and 5 run nothing
+    m = _neck(case, inputs)
+    for n, p in m.named_parameters():
+        p.requires_grad_(n.startswith("lateral3."))
+    out = _run(m, inputs, c_grad=False)
+    assert m.last_launches()["backward"] == 5 + 2 + 2
+    for n, p in m.named_parameters():
+        assert (p.grad is None) == (not n.startswith("lateral3.")), n
+    _same({n: v for n, v in full[0].items() if n in out[0]}, out[0])
+    assert {"g.lateral3.weight", "g.lateral3.bias"} <= set(out[0])
+    # dc only for the maps that require grad: c4 alone, all parameters frozen
+    m = _neck(case, inputs)
+    for p in m.parameters():
+        p.requires_grad_(False)
+    out = _run(m, inputs, c_grad=[False, True, False])
+    assert m.last_launches()["backward"] == 5 + (1 + 5 + 1)
+    assert ["dc" in d for d in out] == [False, True, False]
+    assert torch.equal(out[1]["dc"], full[1]["dc"])
+    # eval mode: 4 launches per block
+    m.eval()
+    with torch.no_grad():
+        ps = m([torch.from_numpy(lv["c"]).to(DEV) for lv in inputs], layout="nhwc")
+    assert all(p.grad_fn is None and not p.requires_grad for p in ps)
+    assert m.last_launches()["forward"] == 3 * (1 + 4)
+
+
+def test_no_grad_saves_nothing_and_holds_one_blocks_buffers():
+    case = BY_NAME["odd"]
+    inputs = case_inputs(case)
+    m = _neck(case, inputs)
+    assert all(p.requires_grad for p in m.parameters()) and m.training and case["depth"] == 2
+    cs = [torch.from_numpy(lv["c"]).to(DEV) for lv in inputs]
+    plan = ya.neckops.plan(case["Cin"], case["F"], case["depth"], case["B"], case["sizes"])
+    with torch.no_grad():
+        quiet = m(cs)
+    assert all(p.grad_fn is None and not p.requires_grad for p in quiet)
+    h = m.held()
+    assert h["forward_held"] == 0 and h["saved_bytes"] == plan["nosave_bytes"] < plan["saved_bytes"], (h, plan)
+    bn = m.smooth3.block[6]
+    assert int(bn.num_batches_tracked) == 4 + 1            # train mode all the same: the running statistics moved
+    ps = m(cs)
+    h = m.held()
+    assert h["forward_held"] == 1 and h["saved_bytes"] == plan["saved_bytes"], (h, plan)
+    assert h["workspace_bytes"] == plan["workspace_bytes"]
+    for a, b in zip(quiet, ps):                            # the same p either way (the statistics are the batch's)
+        assert torch.equal(a, b)
+    with torch.no_grad():                                  # a later no_grad forward drops what was held
+        m(cs)
+    assert m.held()["forward_held"] == 0
+    with pytest.raises(ya.YoloLiteHipError, match="another forward"):
+        ps[0].sum().backward()
+
+
+def test_a_second_forward_replaces_the_held_one_and_single_value_batches_raise():
+    case = BY_NAME["base"]
+    inputs = case_inputs(case)
+    m = _neck(case, inputs)
+    cs = [torch.from_numpy(lv["c"]).to(DEV) for lv in inputs]
+    p1 = m(cs, layout="nhwc")
+    m(cs, layout="nhwc")
+    with pytest.raises(ya.YoloLiteHipError, match="another forward"):
+        p1[0].sum().backward()
+    with pytest.raises(ValueError, match="more than 1 value"):
+        m([c[:1, :1, :1] for c in cs], layout="nhwc")
+    m.eval()
+    assert m([c[:1, :1, :1] for c in cs], layout="nhwc")[0].shape == (1, 1, 1, 16)
+
+
+def _edge_n():
+    meta = zoo_meta("edge_n", num_classes=3, img_size=64)
+    sd = synth_state_dict(meta)
+    model = ya.build_model_from_meta(meta)
+    model.load_state_dict(sd)
+    model.to(DEV)
+    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(5)).to(DEV)
+    return meta, sd, model, x
+
+
+def _restated(neck, heads, feats):
+    """the float64 restatement of eval-mode neck and heads on `feats`, and the bars an fp32 evaluation gets against
+    it: per p level and per head level, max(4 x the CPU fp32 restatement's error, 2 fp32 ulps at the largest value)"""
+    sd = {k: v.detach().cpu().numpy() for k, v in list(neck.state_dict().items()) + list(heads.state_dict().items())}
+    cs = [f.cpu().numpy() for f in feats]
+    ks = [int(n[1:]) for n in neck.level_names]
+    res = {}
+    with torch.no_grad():
+        for dt in (torch.float64, torch.float32):
+            ps = neck_forward(sd, sd, cs, ks, neck.depth, False, dt)[0]
+            ys = [head_forward(sd, sd, p, k, A, heads.num_classes, heads.head_depth, False, dt)[0]
+                  for p, k, A in zip(ps, ks, heads.num_anchors_per_level)]
+            res[dt] = ([p.contiguous().numpy() for p in ps], [y.numpy() for y in ys])
+    out = []
+    for which in (0, 1):
+        out.append([(r64, bar(np.abs(r32.astype(np.float64) - r64).max(), np.abs(r64).max()))
+                    for r64, r32 in zip(res[torch.float64][which], res[torch.float32][which])])
+    return out
+
+
+def _check_against_executor(model, neck, heads, x):
+    feats = model.features(x)
+    with torch.no_grad():
+        ps = neck.eval()(feats, layout="nhwc")
+        ours = heads.eval()(ps, layout="nhwc")
+    theirs, pyr = model(x), model.pyramid(x)
+    pbars, ybars = _restated(neck, heads, feats)
+    for li, (o, t, (r64, b)) in enumerate(zip(ps, pyr, pbars)):
+        eo = np.abs(o.cpu().numpy().astype(np.float64) - r64).max()
+        diff = (o - t).abs().max().item()
+        print(f"p L{li}: neck err {eo:.3e}  diff to pyramid() {diff:.3e}  bar {b:.3e}")
+        assert o.shape == t.shape and diff <= 2 * b, ("p", li, diff, b)
+    for li, (o, t, (r64, b)) in enumerate(zip(ours, theirs, ybars)):
+        eo = np.abs(o.cpu().numpy().astype(np.float64) - r64).max()
+        diff = (o - t).abs().max().item()
+        print(f"y L{li}: neck + heads err {eo:.3e}  diff to model(x) {diff:.3e}  bar {b:.3e}")
+        assert o.shape == t.shape and diff <= 2 * b, ("y", li, diff, b)
+
+
+def test_eval_neck_and_heads_agree_with_the_executor():
+    meta, sd, model, x = _edge_n()
+    before = [o.clone() for o in model(x)]
+    pbefore = [p.clone() for p in model.pyramid(x)]
+    feats = model.features(x)
+    neck = ya.DetectNeck.from_state_dict(meta, sd).to(DEV)
+    assert [tuple(f.shape) for f in feats] == [(2, s, s, c) for s, c in zip((8, 4, 2), neck.in_channels)]
+    _check_against_executor(model, neck, ya.DetectHeads.from_state_dict(meta, sd).to(DEV), x)
+    for a, b in zip(before, model(x)):                      # the executor's own contexts behave as before
+        assert torch.equal(a, b)
+    for a, b in zip(pbefore, model.pyramid(x)):
+        assert torch.equal(a, b)
+
+
+def _targets(cfg):
+    off = cfg["gt_off"]
+    return [{"boxes": torch.tensor(cfg["gt_xyxy"][off[b]:off[b + 1]], dtype=torch.float32).reshape(-1, 4),
+             "labels": torch.tensor(cfg["gt_label"][off[b]:off[b + 1]], dtype=torch.int64)} for b in range(cfg["B"])]
+
+
+def test_twenty_steps_fit_one_batch_as_the_float64_loop_does():
+    ref = np.load(FIXTURE)["e2e/losses"]
+    L0_ref, L20_ref = float(ref[0]), float(ref[-1])
+    inputs, hinputs = case_inputs(E2E), head_inputs(E2E)
+    neck = _neck(E2E, inputs)
+    heads = ya.DetectHeads(E2E["F"], E2E["C"], E2E["A"], E2E["head_depth"])
+    hsd = {}
+    for lv in hinputs:
+        hsd.update(lv["params"]); hsd.update(lv["buffers"])
+    heads.load_state_dict({k: torch.as_tensor(v) for k, v in hsd.items()})
+    heads.to(DEV).train()
+    start = {n: p.detach().clone() for n, p in neck.named_parameters()}
+    feats = [torch.from_numpy(lv["c"]).to(DEV) for lv in inputs]
+    crit = ya.LossAF(E2E["C"], E2E["img_size"], grad=True)
+    params = list(neck.parameters()) + list(heads.parameters())
+    fts = ya.FusedTrainStep(params, optimizer="sgd", amp=False, lr=E2E["lr"], momentum=E2E["momentum"], nesterov=False,
+                            weight_decay=0.0)
+    tg = _targets(E2E)
+    losses = []
+    for _ in range(E2E["steps"]):
+        fts.zero_grad()
+        loss, _ = crit(heads(neck(feats, layout="nhwc"), layout="nhwc"), tg)
+        loss.backward()
+        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in params)
+        fts.step()
+        losses.append(float(loss.detach()))
+    with torch.no_grad():
+        losses.append(float(crit(heads(neck(feats, layout="nhwc"), layout="nhwc"), tg)[0]))
+    L0, L20 = losses[0], losses[-1]
+    print(f"L0 {L0:.6f} (float64 loop {L0_ref:.6f})  L20 {L20:.6f} (float64 loop {L20_ref:.6f})")
+    assert L0_ref - L20_ref >= 0.2 * L0_ref
+    assert L20 <= L0 - 0.5 * (L0 - L20_ref)
+    same = [n for n, p in neck.named_parameters() if torch.equal(p, start[n])]
+    assert not same, same                                  # every lateral and every smooth parameter has moved
+    assert int(neck.smooth3.block[2].num_batches_tracked) == 3 + E2E["steps"] + 1
+
+
+def test_trained_neck_and_heads_round_trip_through_a_checkpoint():
+    meta, sd, model, x = _edge_n()
+    neck = ya.DetectNeck.from_state_dict(meta, sd).to(DEV).train()
+    heads = ya.DetectHeads.from_state_dict(meta, sd).to(DEV).train()
+    crit = ya.LossAF(3, 64, grad=True)
+    fts = ya.FusedTrainStep(list(neck.parameters()) + list(heads.parameters()), optimizer="sgd", amp=False, lr=0.01)
+    tg = _targets(dict(E2E, B=2))
+    feats = model.features(x)
+    for _ in range(2):
+        fts.zero_grad()
+        crit(heads(neck(feats, layout="nhwc"), layout="nhwc"), tg)[0].backward()
+        fts.step()
+    merged = dict(sd)
+    for mod in (neck, heads):
+        merged.update({k: v.detach().cpu().numpy() for k, v in mod.state_dict().items()})
+    assert set(sd) <= set(merged)
+    changed = [k for k in sd if not np.array_equal(np.asarray(sd[k]), merged[k])]
+    assert changed and all(k.startswith(("lateral", "smooth", "head")) for k in changed)
+    assert any(k.startswith("lateral") for k in changed) and any(k.startswith("smooth") for k in changed)
+    m2 = ya.build_model_from_meta(copy.deepcopy(meta))
+    m2.load_state_dict(merged)
+    m2.to(DEV)
+    _check_against_executor(m2, neck, heads, x)

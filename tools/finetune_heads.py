@@ -6,6 +6,7 @@
 
     python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
+                                   [--train-neck]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
@@ -15,6 +16,11 @@ checkpoint's the heads start freshly initialised (torch's defaults plus the refe
 they start from the checkpoint.  --synthetic NAME takes a zoo model with seeded synthetic weights and one random batch
 instead of --weights / --data.  The output is a checkpoint {"state_dict", "meta"}: the input's state_dict with the
 `head*.` entries replaced, meta.num_classes / names updated -- tools/infer.py runs it.
+
+With --train-neck (YOLOLiteMS_CPU models without P6) the FPN neck is trained as well: the executor stops being the
+pyramid's source and gives the backbone's feature maps (YOLOLiteHIP.features); DetectNeck (csrc/yl_neck.hip) starts
+from the checkpoint's `lateral*.` / `smooth*.` entries, its parameters join the heads' in the one FusedTrainStep, and
+its state_dict is merged into the output as well.
 """
 import argparse
 import copy
@@ -99,6 +105,7 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-3)
     ap.add_argument("--optimizer", default="adamw", choices=("adamw", "adam", "sgd"))
     ap.add_argument("--grad-clip", type=float, default=10.0)
+    ap.add_argument("--train-neck", action="store_true", help="train the FPN neck (laterals, smooth blocks) as well")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     if bool(a.synthetic) == bool(a.weights):
@@ -124,11 +131,14 @@ def main():
         heads = ya.DetectHeads.from_meta(meta, num_classes=nc)
         print(f"[finetune_heads] {old_nc} -> {nc} classes: heads freshly initialised")
     heads.to(a.device).train()
+    neck = ya.DetectNeck.from_state_dict(meta, sd).to(a.device).train() if a.train_neck else None
     crit = ya.LossAF(nc, img_size, grad=True)
-    fts = ya.FusedTrainStep(list(heads.parameters()), optimizer=a.optimizer, grad_clip=a.grad_clip, amp=False, lr=a.lr)
+    params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
+    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp=False, lr=a.lr)
 
     def step(x, targets):
-        feats = model.pyramid(x)                           # frozen trunk: plain tensors, nothing to backpropagate into
+        # frozen trunk: plain tensors, nothing to backpropagate into
+        feats = model.pyramid(x) if neck is None else neck(model.features(x), layout="nhwc")
         fts.zero_grad()
         loss, parts = crit(heads(feats, layout="nhwc"), targets)
         loss.backward()
@@ -156,8 +166,9 @@ def main():
             print(f"epoch {ep:3d}  mean loss {tot / max(n, 1):.4f}  ({n} batches)")
 
     out_sd = dict(sd)
-    for k, v in heads.state_dict().items():
-        out_sd[k] = v.detach().cpu()
+    for mod in ([neck] if neck is not None else []) + [heads]:
+        for k, v in mod.state_dict().items():
+            out_sd[k] = v.detach().cpu()
     out_sd = {k: (torch.as_tensor(v) if not torch.is_tensor(v) else v) for k, v in out_sd.items()}
     meta = copy.deepcopy(meta)
     meta["num_classes"] = nc

@@ -154,6 +154,33 @@ class yl_head_plan_info(C.Structure):
         ("saved_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
 
 
+YL_NECK_MAX_DEPTH, YL_NECK_MAX_LEVELS = 4, 4
+
+
+class yl_neck_cfg(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("depth", C.c_int32), ("num_levels", C.c_int32),
+                ("in_channels", C.c_int32 * YL_NECK_MAX_LEVELS), ("reserved0", C.c_int32)]
+
+
+class yl_neck_level(C.Structure):
+    _fields_ = [("lat_w", C.c_void_p), ("lat_b", C.c_void_p), ("block", yl_head_block * YL_NECK_MAX_DEPTH)]
+
+
+class yl_neck_tensors(C.Structure):
+    _fields_ = [("level", yl_neck_level * YL_NECK_MAX_LEVELS)]
+
+
+class yl_neck_level_plan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows", "stat_tiles", "gemm_tiles", "wgrad_rows", "wgrad_splits", "lgrad_rows",
+                                         "lgrad_splits", "reserved0")] + [("saved_bytes", C.c_int64)]
+
+
+class yl_neck_plan_info(C.Structure):
+    _fields_ = [("stat_rows", C.c_int32), ("gemm_rows", C.c_int32), ("level", yl_neck_level_plan * YL_NECK_MAX_LEVELS),
+                ("saved_bytes", C.c_int64), ("nosave_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+                ("table_bytes", C.c_int64)]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -221,6 +248,14 @@ SYMBOLS = [
     ("yl_head_backward", C.c_int32, [_vp, C.POINTER(yl_head_tensors), C.POINTER(yl_head_tensors), _vp, _vp, _vp,
                                      C.c_int32, C.c_int32, _vp, _ip]),
     ("yl_head_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("yl_neck_plan", C.c_int32, [C.POINTER(yl_neck_cfg), C.c_int32, _ip, C.POINTER(yl_neck_plan_info)]),
+    ("yl_neck_nearest_map", C.c_int32, [C.c_int32, C.c_int32, _ip, _ip, _ip]),
+    ("yl_neck_create", C.c_int32, [C.c_int32, C.POINTER(yl_neck_cfg), C.POINTER(_vp)]),
+    ("yl_neck_destroy", None, [_vp]),
+    ("yl_neck_forward", C.c_int32, [_vp, C.POINTER(yl_neck_tensors), _vpp, C.c_int32, _ip, C.c_uint32, _vpp, _vp, _ip]),
+    ("yl_neck_backward", C.c_int32, [_vp, C.POINTER(yl_neck_tensors), C.POINTER(yl_neck_tensors), _vpp, _vpp, _vpp,
+                                     C.c_int32, _ip, _vp, _ip]),
+    ("yl_neck_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
 ]
 
 _lib = None

@@ -1,0 +1,575 @@
+// The DWConvBlock of the reference (scripts/model/model_v2.py:23-39) on NHWC fp32 rows, shared by the detection heads
+// (yl_head.hip) and the FPN neck (yl_neck.hip): its kernels, the GEMM they share, and the launch sequences of a run of
+// blocks forward and backward.  Everything lives in an anonymous namespace: each translation unit that includes this
+// header compiles the kernels it launches into its own code object.
+//
+//   block t:  d = dw3x3(x)   z = d . W1^T   h = relu(gamma * (z - mean) * invstd + beta)     (d, z, h are kept for backward)
+#ifndef YL_BLOCK_H
+#define YL_BLOCK_H
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/yololite_hip.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int NT = 256;
+constexpr int STAT_ROWS = 256;           // rows of one tile of the row reductions
+constexpr int GEMM_ROWS = 64;            // q extent of one GEMM workgroup (four waves of 16)
+constexpr double BN_EPS = 1e-5, BN_MOMENTUM = 0.1;
+
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+
+// ---- level geometry: column n = a * E + e of the head output <-> level tensor [B, A, S, S, E], parameter rows
+struct HeadGeom { int A, E, C, SS, F; };
+__device__ __forceinline__ long head_y_off(const HeadGeom& g, int m, int n) {
+  if (g.A == 1) return (long)m * g.E + n;
+  const int a = n / g.E, e = n - a * g.E;
+  const int b = m / g.SS, ij = m - b * g.SS;
+  return (((long)b * g.A + a) * g.SS + ij) * g.E + e;
+}
+struct HeadRows {                        // the three output convolutions as one matrix [A * E][F] (+ bias [A * E])
+  float *box, *obj, *cls, *box_b, *obj_b, *cls_b;
+  HeadGeom g;
+  __device__ __forceinline__ long rowidx(int n, int& which) const {
+    const int a = n / g.E, e = n - a * g.E;
+    which = e < 4 ? 0 : (e == 4 ? 1 : 2);
+    return e < 4 ? 4 * a + e : (e == 4 ? a : g.C * a + (e - 5));
+  }
+  __device__ __forceinline__ float* row(int n) const {
+    int k; const long r = rowidx(n, k);
+    return (k == 0 ? box : (k == 1 ? obj : cls)) + r * g.F;
+  }
+  __device__ __forceinline__ float* bias(int n) const {
+    int k; const long r = rowidx(n, k);
+    return (k == 0 ? box_b : (k == 1 ? obj_b : cls_b)) + r;
+  }
+};
+
+// ---- operand accessors: load4(idx, r, NI, NR) = elements (idx, r .. r + 3), zero outside idx < NI, r + s < NR
+struct RowsVec {                         // (idx, r) = p[idx * ld + r]; 16-byte aligned rows, ld % 4 == 0, NR % 4 == 0
+  const float* p; int ld;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    if (idx < NI && r < NR) return ld4(p + (long)idx * ld + r);
+    return (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+};
+struct RowsScalar {                      // the same element, a caller's tensor at any 4-byte boundary
+  const float* p; int ld;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+      const float* q = p + (long)idx * ld;
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = q[r + s];
+    }
+    return v;
+  }
+};
+struct ColsScalar {                      // (idx, r) = p[r * ld + idx]
+  const float* p; int ld;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+        if (r + s < NR) v[s] = p[(long)(r + s) * ld + idx];
+    }
+    return v;
+  }
+};
+struct HeadWRows {                       // (n, k) = Wout[n][k]
+  HeadRows w;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+      const float* q = w.row(idx);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = q[r + s];
+    }
+    return v;
+  }
+};
+struct HeadWCols {                       // (k, n) = Wout[n][k]
+  HeadRows w;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = w.row(r + s)[idx];
+    }
+    return v;
+  }
+};
+struct HeadYRows {                       // (m, n) = level tensor element of row m, column n
+  const float* y; HeadGeom g;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = y[head_y_off(g, idx, r + s)];
+    }
+    return v;
+  }
+};
+struct HeadYCols {                       // (n, m)
+  const float* y; HeadGeom g;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = y[head_y_off(g, r + s, idx)];
+    }
+    return v;
+  }
+};
+// ---- output accessors: store(p, q, v, NP, NQ, split) writes C[p .. p + 3][q]
+struct OutRowsVec {                      // c[q * ld + p], NP % 4 == 0
+  float* c; int ld;
+  __device__ __forceinline__ void store(int p, int q, f32x4 v, int NP, int NQ, int) const {
+    if (q < NQ && p < NP) st4(c + (long)q * ld + p, v);
+  }
+};
+struct OutHeadY {                        // the level tensor, bias added
+  float* y; HeadRows w;
+  __device__ __forceinline__ void store(int p, int q, f32x4 v, int NP, int NQ, int) const {
+    if (q >= NQ) return;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (p + s < NP) y[head_y_off(w.g, q, p + s)] = v[s] + *w.bias(p + s);
+  }
+};
+struct OutPartial {                      // part[split][q][p]
+  float* part; long stride;
+  __device__ __forceinline__ void store(int p, int q, f32x4 v, int NP, int NQ, int split) const {
+    if (q >= NQ) return;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+      if (p + s < NP) part[(long)split * stride + (long)q * NP + p + s] = v[s];
+  }
+};
+
+// grid (ceil(NP / (16 PT)), ceil(NQ / 64), splits); r range of a split: [z * rsplit, min(NR, (z + 1) * rsplit))
+template <int PT, class PA, class QA, class CA>
+__global__ __launch_bounds__(NT) void yl_head_gemm_kernel(PA pa, QA qa, CA ca, int NP, int NQ, int NR, int rsplit) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4, i = lane & 15;
+  const int p0 = blockIdx.x * (16 * PT), q0 = blockIdx.y * GEMM_ROWS + wave * 16;
+  if (q0 >= NQ) return;                  // no barrier below
+  const int rbeg = blockIdx.z * rsplit;
+  const int rend = rbeg + rsplit < NR ? rbeg + rsplit : NR;
+  f32x4 acc[PT];
+#pragma unroll
+  for (int pt = 0; pt < PT; ++pt) acc[pt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (int r0 = rbeg; r0 < rend; r0 += 16) {
+    const int r = r0 + 4 * kq;
+    const f32x4 qv = qa.load4(q0 + i, r, NQ, rend);
+    f32x4 pv[PT];
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) pv[pt] = pa.load4(p0 + 16 * pt + i, r, NP, rend);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int pt = 0; pt < PT; ++pt)
+        acc[pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[pt], 0, 0, 0);
+  }
+#pragma unroll
+  for (int pt = 0; pt < PT; ++pt) ca.store(p0 + 16 * pt + 4 * kq, q0 + i, acc[pt], NP, NQ, blockIdx.z);
+}
+
+// ---- depthwise 3x3, pad 1, stride 1, weight [F][1][3][3]; FLIP: the transposed convolution (gradient of the input)
+template <bool FLIP>
+__global__ __launch_bounds__(NT) void yl_head_dw_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                       float* __restrict__ out, int M, int S, int F) {
+  const int F4 = F >> 2;
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= (long)M * F4) return;
+  const int m = (int)(idx / F4), c = (int)(idx - (long)m * F4) * 4;
+  const int SS = S * S, b = m / SS, ij = m - b * SS, i = ij / S, j = ij - i * S;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ky = 0; ky < 3; ++ky) {
+    const int yy = FLIP ? i - ky + 1 : i + ky - 1;
+    if (yy < 0 || yy >= S) continue;
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      const int xx = FLIP ? j - kx + 1 : j + kx - 1;
+      if (xx < 0 || xx >= S) continue;
+      const f32x4 v = ld4(x + ((long)(b * S + yy) * S + xx) * F + c);
+      const int t = ky * 3 + kx;
+      const f32x4 wv = {w[(c + 0) * 9 + t], w[(c + 1) * 9 + t], w[(c + 2) * 9 + t], w[(c + 3) * 9 + t]};
+      acc = acc + v * wv;
+    }
+  }
+  st4(out + (long)m * F + c, acc);
+}
+
+// ---- row reductions.  Workgroup (tile of STAT_ROWS rows, group of CQ channel quads); thread t: quad t % CQ, rows
+// m0 + t / CQ, + 256 / CQ, ...; float64 sums per thread, summed over the row lanes in lane order by the thread of lane 0.
+struct StatP {
+  const float *a, *h, *z, *stats;        // forward: a = z.  backward: a = dh, h = the block's output (ReLU mask), z, stats
+  double* part;                          // [tile][2][F]
+  int M, F, CQ, bwd;
+};
+__global__ __launch_bounds__(NT) void yl_head_colstats_kernel(StatP P) {
+  __shared__ double red[NT][8];
+  const int t = threadIdx.x, cq = t & (P.CQ - 1), rs = t / P.CQ, RS = NT / P.CQ;
+  const int c = (blockIdx.y * P.CQ + cq) * 4, F = P.F;
+  const bool on = c < F;
+  const int m0 = blockIdx.x * STAT_ROWS, m1 = m0 + STAT_ROWS < P.M ? m0 + STAT_ROWS : P.M;
+  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+  if (on) {
+    f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = mu;
+    if (P.bwd) { mu = ld4(P.stats + c); is = ld4(P.stats + F + c); }
+    for (int m = m0 + rs; m < m1; m += RS) {
+      const long o = (long)m * F + c;
+      const f32x4 a = ld4(P.a + o);
+      if (!P.bwd) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { s0[e] += (double)a[e]; s1[e] += (double)a[e] * (double)a[e]; }
+      } else {
+        const f32x4 hv = ld4(P.h + o), zv = ld4(P.z + o);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const double g = hv[e] > 0.f ? (double)a[e] : 0.0;
+          const double xh = ((double)zv[e] - (double)mu[e]) * (double)is[e];
+          s0[e] += g; s1[e] += g * xh;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { red[t][e] = s0[e]; red[t][4 + e] = s1[e]; }
+  __syncthreads();
+  if (rs == 0 && on) {
+    for (int k = 1; k < RS; ++k)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[t][e] += red[k * P.CQ + cq][e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      P.part[((long)blockIdx.x * 2 + 0) * F + c + e] = red[t][e];
+      P.part[((long)blockIdx.x * 2 + 1) * F + c + e] = red[t][4 + e];
+    }
+  }
+}
+
+// depthwise weight gradient partials: part[tile][ky * 3 + kx][F] = sum over the tile's rows of dd[m][c] * x[m + tap][c]
+__global__ __launch_bounds__(NT) void yl_head_dw_wgrad_kernel(const float* __restrict__ dd, const float* __restrict__ x,
+                                                             double* __restrict__ part, int M, int S, int F, int CQ) {
+  __shared__ double red[NT][12];
+  const int t = threadIdx.x, cq = t & (CQ - 1), rs = t / CQ, RS = NT / CQ;
+  const int c = (blockIdx.y * CQ + cq) * 4;
+  const bool on = c < F;
+  const int SS = S * S;
+  const int m0 = blockIdx.x * STAT_ROWS, m1 = m0 + STAT_ROWS < M ? m0 + STAT_ROWS : M;
+  for (int ky = 0; ky < 3; ++ky) {
+    double acc[3][4] = {};
+    if (on)
+      for (int m = m0 + rs; m < m1; m += RS) {
+        const int b = m / SS, ij = m - b * SS, i = ij / S, j = ij - i * S, yy = i + ky - 1;
+        if (yy < 0 || yy >= S) continue;
+        const f32x4 g = ld4(dd + (long)m * F + c);
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx) {
+          const int xx = j + kx - 1;
+          if (xx < 0 || xx >= S) continue;
+          const f32x4 v = ld4(x + ((long)(b * S + yy) * S + xx) * F + c);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[kx][e] += (double)g[e] * (double)v[e];
+        }
+      }
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) red[t][kx * 4 + e] = acc[kx][e];
+    __syncthreads();
+    if (rs == 0 && on) {
+      for (int k = 1; k < RS; ++k)
+#pragma unroll
+        for (int e = 0; e < 12; ++e) red[t][e] += red[k * CQ + cq][e];
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[((long)blockIdx.x * 9 + ky * 3 + kx) * F + c + e] = red[t][kx * 4 + e];
+    }
+    __syncthreads();
+  }
+}
+
+// bias gradient partials: part[tile][NE] = sum over the tile's rows of gy(m, n); thread t: column t % 64, rows t / 64, + 4, ...
+__global__ __launch_bounds__(NT) void yl_head_ysum_kernel(const float* __restrict__ gy, HeadGeom g, double* __restrict__ part,
+                                                         int M, int NE) {
+  __shared__ double red[NT];
+  const int t = threadIdx.x, n = blockIdx.y * 64 + (t & 63), rs = t >> 6;
+  const int m0 = blockIdx.x * STAT_ROWS, m1 = m0 + STAT_ROWS < M ? m0 + STAT_ROWS : M;
+  double s = 0;
+  if (n < NE)
+    for (int m = m0 + rs; m < m1; m += NT / 64) s += (double)gy[head_y_off(g, m, n)];
+  red[t] = s;
+  __syncthreads();
+  if (rs == 0 && n < NE) part[(long)blockIdx.x * NE + n] = ((red[t] + red[t + 64]) + red[t + 128]) + red[t + 192];
+}
+
+// ---- second stages: one thread per output element, the partials summed in tile order in float64
+struct BnFwdP {
+  const double* part; int tiles, M, F, train;
+  float *rm, *rv; int64_t* nbt;          // running statistics (train: updated in place)
+  float* stats;                          // [2][F]: mean, invstd of this call
+};
+__global__ __launch_bounds__(NT) void yl_head_bn_stats_kernel(BnFwdP P) {
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= P.F) return;
+  if (!P.train) {                        // eval: the running statistics
+    P.stats[c] = P.rm[c];
+    P.stats[P.F + c] = (float)(1.0 / sqrt((double)P.rv[c] + BN_EPS));
+    return;
+  }
+  double s0 = 0, s1 = 0;
+  for (int t = 0; t < P.tiles; ++t) { s0 += P.part[((long)t * 2) * P.F + c]; s1 += P.part[((long)t * 2 + 1) * P.F + c]; }
+  const double mean = s0 / P.M;
+  double var = s1 / P.M - mean * mean;
+  var = var > 0 ? var : 0;
+  P.stats[c] = (float)mean;
+  P.stats[P.F + c] = (float)(1.0 / sqrt(var + BN_EPS));
+  P.rm[c] = (float)((1.0 - BN_MOMENTUM) * (double)P.rm[c] + BN_MOMENTUM * mean);
+  P.rv[c] = (float)((1.0 - BN_MOMENTUM) * (double)P.rv[c] + BN_MOMENTUM * (var * P.M / (P.M - 1)));
+  if (c == 0) *P.nbt += 1;
+}
+struct BnBwdP {
+  const double* part; int tiles, M, F, train;
+  float *dgamma, *dbeta;                 // NULL: not wanted
+  float* coef;                           // [2][F]: dbeta / M, dgamma / M (zero in eval mode)
+};
+__global__ __launch_bounds__(NT) void yl_head_bn_grads_kernel(BnBwdP P) {
+  const int c = blockIdx.x * NT + threadIdx.x;
+  if (c >= P.F) return;
+  double s0 = 0, s1 = 0;
+  for (int t = 0; t < P.tiles; ++t) { s0 += P.part[((long)t * 2) * P.F + c]; s1 += P.part[((long)t * 2 + 1) * P.F + c]; }
+  if (P.dbeta) P.dbeta[c] = (float)s0;
+  if (P.dgamma) P.dgamma[c] = (float)s1;
+  P.coef[c] = P.train ? (float)(s0 / P.M) : 0.f;
+  P.coef[P.F + c] = P.train ? (float)(s1 / P.M) : 0.f;
+}
+__global__ __launch_bounds__(NT) void yl_head_dw_wsum_kernel(const double* __restrict__ part, int tiles, int F,
+                                                            float* __restrict__ out) {
+  const int idx = blockIdx.x * NT + threadIdx.x;          // k * F + c
+  if (idx >= 9 * F) return;
+  const int k = idx / F, c = idx - k * F;
+  double s = 0;
+  for (int t = 0; t < tiles; ++t) s += part[((long)t * 9 + k) * F + c];
+  out[c * 9 + k] = (float)s;
+}
+// weight-gradient partials [splits][NQ][NP] -> a plain matrix out[q * NP + p], or (head != 0) the weights of the three
+// output convolutions: row q = column n of the head; a NULL tensor is not written
+__global__ __launch_bounds__(NT) void yl_head_wsum_kernel(const float* __restrict__ part, int splits, int NP, int NQ,
+                                                         float* __restrict__ out, HeadRows hw, int head) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  const long n = (long)NP * NQ;
+  if (idx >= n) return;
+  double s = 0;
+  for (int z = 0; z < splits; ++z) s += (double)part[(long)z * n + idx];
+  if (!head) { out[idx] = (float)s; return; }
+  const int q = (int)(idx / NP), p = (int)(idx - (long)q * NP);
+  int k; hw.rowidx(q, k);
+  if (k == 0 ? hw.box != nullptr : (k == 1 ? hw.obj != nullptr : hw.cls != nullptr)) hw.row(q)[p] = (float)s;
+}
+__global__ __launch_bounds__(NT) void yl_head_bsum_kernel(const double* __restrict__ part, int tiles, int NE, HeadRows hw) {
+  const int n = blockIdx.x * NT + threadIdx.x;
+  if (n >= NE) return;
+  double s = 0;
+  for (int t = 0; t < tiles; ++t) s += part[(long)t * NE + n];
+  int k; hw.rowidx(n, k);
+  if (k == 0 ? hw.box_b != nullptr : (k == 1 ? hw.obj_b != nullptr : hw.cls_b != nullptr)) *hw.bias(n) = (float)s;
+}
+
+// ---- element-wise: h = relu(gamma * (z - mean) * invstd + beta);  dz = gamma * invstd * (g - c0 - xhat * c1), g = dh * [h > 0]
+__global__ __launch_bounds__(NT) void yl_head_bn_relu_kernel(const float* __restrict__ z, const float* __restrict__ stats,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ h, long n4, int F) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= n4) return;
+  const int c = (int)((idx * 4) % F);
+  const f32x4 v = ld4(z + idx * 4), mu = ld4(stats + c), is = ld4(stats + F + c);
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) o[e] = fmaxf((v[e] - mu[e]) * is[e] * gamma[c + e] + beta[c + e], 0.f);
+  st4(h + idx * 4, o);
+}
+// dh and dz may be one buffer (each thread reads its four values before it writes them): neither is __restrict__
+__global__ __launch_bounds__(NT) void yl_head_bn_bwd_kernel(const float* dh, const float* __restrict__ h,
+                                                           const float* __restrict__ z, const float* __restrict__ stats,
+                                                           const float* __restrict__ coef, const float* __restrict__ gamma,
+                                                           float* dz, long n4, int F) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= n4) return;
+  const int c = (int)((idx * 4) % F);
+  const f32x4 g = ld4(dh + idx * 4), hv = ld4(h + idx * 4), zv = ld4(z + idx * 4);
+  const f32x4 mu = ld4(stats + c), is = ld4(stats + F + c), c0 = ld4(coef + c), c1 = ld4(coef + F + c);
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float ge = hv[e] > 0.f ? g[e] : 0.f;
+    const float xh = (zv[e] - mu[e]) * is[e];
+    o[e] = gamma[c + e] * is[e] * (ge - c0[e] - xh * c1[e]);
+  }
+  st4(dz + idx * 4, o);
+}
+
+int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
+int pick_pt(int NP) {                    // p-tiles per wave: 4 (64 columns) or 6 (96), whichever pads NP less
+  const int w4 = ceil_div(NP, 64) * 64, w6 = ceil_div(NP, 96) * 96;
+  return w6 < w4 ? 6 : 4;
+}
+int pick_cq(int F) {                     // channel quads per workgroup of the row reductions: a power of two <= 64
+  int cq = 1;
+  while (cq < (F >> 2) && cq < 64) cq <<= 1;
+  return cq;
+}
+// rows per split and number of splits of a weight-gradient GEMM with NP x NQ outputs over M rows: about 1024 workgroups
+void split_plan(int M, int NP, int NQ, int* rows, int* splits) {
+  const int tiles = ceil_div(NP, 16 * pick_pt(NP)) * ceil_div(NQ, GEMM_ROWS);
+  int want = 1024 / tiles;
+  want = want < 8 ? 8 : (want > 128 ? 128 : want);
+  const int most = ceil_div(M, 64);
+  want = want < most ? want : most;
+  *rows = ceil_div(ceil_div(M, want), 16) * 16;
+  *splits = ceil_div(M, *rows);
+}
+
+template <class PA, class QA, class CA>
+void launch_gemm(hipStream_t s, PA pa, QA qa, CA ca, int NP, int NQ, int NR, int rsplit, int splits) {
+  const int pt = pick_pt(NP);
+  const dim3 grid(ceil_div(NP, 16 * pt), ceil_div(NQ, GEMM_ROWS), splits);
+  if (pt == 6)
+    hipLaunchKernelGGL((yl_head_gemm_kernel<6, PA, QA, CA>), grid, dim3(NT), 0, s, pa, qa, ca, NP, NQ, NR, rsplit);
+  else
+    hipLaunchKernelGGL((yl_head_gemm_kernel<4, PA, QA, CA>), grid, dim3(NT), 0, s, pa, qa, ca, NP, NQ, NR, rsplit);
+}
+
+// the float64 partial sums of the row reductions, rounded up so that what follows them stays 16-byte aligned
+int64_t spart_bytes(int64_t stat_tiles, int64_t F, int64_t NE) {
+  return (stat_tiles * (9 * F > NE ? 9 * F : NE) * 8 + 15) & ~(int64_t)15;
+}
+
+// ---- a run of blocks.  Buffers: where the activations of each block and the gradients in flight live
+struct Buffers {
+  float *d[YL_HEAD_MAX_DEPTH], *z[YL_HEAD_MAX_DEPTH], *h[YL_HEAD_MAX_DEPTH], *stats[YL_HEAD_MAX_DEPTH];
+  float *ga, *gb, *wpart, *coef;
+  double* spart;
+};
+struct BlockDims { int M, S, F, stat_tiles, wgrad_rows, wgrad_splits; };
+
+// Blocks 0 .. D - 1 on `in`: per block 4 launches (5 with `train`).  `save` keeps every block's d, z, h apart; without it
+// every block runs in the first block's buffers.  The last block's output goes to `last_out` if that is given.
+// -> where the last block's output is
+inline const float* blocks_forward(hipStream_t s, const yl_head_block* blocks, int D, const float* in, const Buffers& bf,
+                                   bool save, bool train, const BlockDims& dm, float* last_out, int* launches) {
+  const int M = dm.M, S = dm.S, F = dm.F;
+  const long n4 = (long)M * (F >> 2);
+  const int eg = ceil_div(n4, NT), cq = pick_cq(F);
+  int nl = 0;
+  for (int t = 0; t < D; ++t) {
+    const int k = save ? t : 0;          // nothing is kept without `save`: every block runs in the first block's buffers
+    const yl_head_block& b = blocks[t];
+    float* hout = (t == D - 1 && last_out) ? last_out : bf.h[k];
+    hipLaunchKernelGGL(yl_head_dw_kernel<false>, dim3(eg), dim3(NT), 0, s, in, (const float*)b.dw, bf.d[k], M, S, F);
+    launch_gemm(s, RowsScalar{b.pw, F}, RowsVec{bf.d[k], F}, OutRowsVec{bf.z[k], F}, F, M, F, F, 1);
+    nl += 2;
+    if (train) {
+      StatP sp;
+      sp.a = bf.z[k]; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = bf.spart;
+      sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 0;
+      hipLaunchKernelGGL(yl_head_colstats_kernel, dim3(dm.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
+      ++nl;
+    }
+    BnFwdP bp;
+    bp.part = bf.spart; bp.tiles = dm.stat_tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
+    bp.rm = b.running_mean; bp.rv = b.running_var; bp.nbt = b.num_batches_tracked; bp.stats = bf.stats[k];
+    hipLaunchKernelGGL(yl_head_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
+    hipLaunchKernelGGL(yl_head_bn_relu_kernel, dim3(eg), dim3(NT), 0, s, (const float*)bf.z[k], (const float*)bf.stats[k],
+                       (const float*)b.gamma, (const float*)b.beta, hout, n4, F);
+    nl += 2;
+    in = hout;
+  }
+  *launches += nl;
+  return in;
+}
+
+// the first block something of `grads` is wanted of (D: none)
+inline int blocks_first_wanted(const yl_head_block* grads, int D) {
+  int first = D;
+  for (int t = D - 1; t >= 0; --t) {
+    const yl_head_block& g = grads[t];
+    if (g.dw || g.pw || g.gamma || g.beta) first = t;
+  }
+  return first;
+}
+
+// The blocks D - 1 .. first backward.  `gin`: the gradient of the last block's output (bf.ga, or a tensor that is only
+// read).  x_in: the input of block 0.  dx (may be NULL): where the gradient of block 0's input goes; the caller passes
+// first = 0 with it.  The walk stops at the last thing that is wanted.
+inline void blocks_backward(hipStream_t s, const yl_head_block* params, const yl_head_block* grads, int D, int first,
+                            const float* gin, const float* x_in, float* dx, const Buffers& bf, bool train,
+                            const BlockDims& dm, int* launches) {
+  const int M = dm.M, S = dm.S, F = dm.F;
+  const long n4 = (long)M * (F >> 2);
+  const int eg = ceil_div(n4, NT), cq = pick_cq(F);
+  HeadRows none;
+  memset(&none, 0, sizeof(none));
+  int nl = 0;
+  for (int t = D - 1; t >= first; --t) {
+    const yl_head_block& b = params[t];
+    const yl_head_block& g = grads[t];
+    const float* xin = t ? bf.h[t - 1] : x_in;
+    const float* dh = t == D - 1 ? gin : bf.ga;
+    if (train || g.gamma || g.beta) {    // sum g, sum g * xhat: dbeta, dgamma, and the two means the batch statistics carry
+      StatP sp;
+      sp.a = dh; sp.h = bf.h[t]; sp.z = bf.z[t]; sp.stats = bf.stats[t]; sp.part = bf.spart;
+      sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 1;
+      hipLaunchKernelGGL(yl_head_colstats_kernel, dim3(dm.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
+      ++nl;
+    }
+    const bool below = t > first || g.dw || g.pw || (t == 0 && dx);   // anything that needs dz
+    BnBwdP bp;
+    bp.part = bf.spart; bp.tiles = (train || g.gamma || g.beta) ? dm.stat_tiles : 0; bp.M = M; bp.F = F; bp.train = train;
+    bp.dgamma = g.gamma; bp.dbeta = g.beta; bp.coef = bf.coef;
+    hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
+    ++nl;
+    if (!below) break;
+    hipLaunchKernelGGL(yl_head_bn_bwd_kernel, dim3(eg), dim3(NT), 0, s, dh, (const float*)bf.h[t],
+                       (const float*)bf.z[t], (const float*)bf.stats[t], (const float*)bf.coef, (const float*)b.gamma,
+                       bf.ga, n4, F);
+    ++nl;
+    if (g.pw) {                          // dW1 = dz^T . d
+      launch_gemm(s, ColsScalar{bf.d[t], F}, ColsScalar{bf.ga, F}, OutPartial{bf.wpart, (long)F * F}, F, F, M,
+                  dm.wgrad_rows, dm.wgrad_splits);
+      hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)F * F, NT)), dim3(NT), 0, s, (const float*)bf.wpart,
+                         dm.wgrad_splits, F, F, g.pw, none, 0);
+      nl += 2;
+    }
+    const bool need_dx = t > first || (t == 0 && dx);
+    if (!g.dw && !need_dx) break;
+    launch_gemm(s, ColsScalar{b.pw, F}, RowsVec{bf.ga, F}, OutRowsVec{bf.gb, F}, F, M, F, F, 1);   // dd = dz . W1
+    ++nl;
+    if (g.dw) {
+      hipLaunchKernelGGL(yl_head_dw_wgrad_kernel, dim3(dm.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s,
+                         (const float*)bf.gb, xin, bf.spart, M, S, F, cq);
+      hipLaunchKernelGGL(yl_head_dw_wsum_kernel, dim3(ceil_div(9 * F, NT)), dim3(NT), 0, s, (const double*)bf.spart,
+                         dm.stat_tiles, F, g.dw);
+      nl += 2;
+    }
+    if (need_dx) {                       // the gradient of the block's input: the next block's dh, or the caller's dx
+      hipLaunchKernelGGL(yl_head_dw_kernel<true>, dim3(eg), dim3(NT), 0, s, (const float*)bf.gb, (const float*)b.dw,
+                         t ? bf.ga : dx, M, S, F);
+      ++nl;
+    }
+  }
+  *launches += nl;
+}
+
+}  // namespace
+#endif  // YL_BLOCK_H

@@ -465,6 +465,7 @@ class YOLOLiteHIP:
         self.context_options: Dict[str, int] = {}
         self._ctxs: Dict[int, tuple] = {}
         self._pyramid_ctxs: Dict[int, tuple] = {}           # pyramid()'s own contexts, by input size ("reuse_slots" 0)
+        self._feature_ctxs: Dict[int, tuple] = {}           # features()'s own contexts (and the last 1x1 conv unpaired)
         self.program: Optional[Program] = None
         self.ctx: Optional[HipContext] = None
         self._sd = None
@@ -500,6 +501,7 @@ class YOLOLiteHIP:
         self._device_index = dev.index or 0
         self._ctxs = {}
         self._pyramid_ctxs = {}
+        self._feature_ctxs = {}
         self.ctx = self._ctx_for(self.program.img_size)
         return self
 
@@ -515,6 +517,10 @@ class YOLOLiteHIP:
             for k, v in opts.items():
                 if k != "reuse_slots":
                     ctx.set_option(k, int(v))
+        for _, ctx in self._feature_ctxs.values():
+            for k, v in opts.items():
+                if k != "reuse_slots":
+                    ctx.set_option(k, int(v) | _lib.DEV_PWX_OFF if k == "dev_select" else int(v))
 
     def _ctx_for(self, img_size: int) -> HipContext:
         """The reference module is input-size agnostic (tools/infer.py --img_size); the HIP program is
@@ -574,6 +580,30 @@ class YOLOLiteHIP:
         p, ctx = self._pyramid_ctxs[size]
         ctx.forward(x)
         names = sorted(n for n in p.feature_slots if n.startswith("p"))
+        return [ctx.read_slot(p.feature_slots[n], int(x.shape[0]), p.slots[p.feature_slots[n]]) for n in names]
+
+    def features(self, x: torch.Tensor) -> List[torch.Tensor]:
+        """The backbone's feature maps of a forward (program.feature_slots["c3"], "c4", "c5"; "c2" first with use_p2)
+        as NHWC tensors [B,S,S,Cin], smallest stride first: what neckops.DetectNeck takes.  The whole program runs, as
+        in pyramid(), and the maps are read afterwards.  They come from a context of their own that keeps every tensor
+        in its own memory (option "reuse_slots" 0) and does not chain lateral5 behind the backbone's last 1x1 conv
+        (dev_select DEV_PWX_OFF), so that C5 is written; the contexts of __call__ and pyramid() are not touched."""
+        if self.ctx is None:
+            raise RuntimeError("model.to('cuda') first")
+        size = int(x.shape[-1])
+        if size not in self._feature_ctxs:
+            p = self.program if size == self.program.img_size else \
+                build_program(self.meta, self._sd, img_size=size, **self._fuse_kw)
+            ctx = HipContext(p.img_size, p.num_classes, p.level_size, p.level_anchors, p, self._device_index)
+            for k, v in self.context_options.items():
+                if k not in ("reuse_slots", "dev_select"):
+                    ctx.set_option(k, v)
+            ctx.set_option("reuse_slots", 0)
+            ctx.set_option("dev_select", int(self.context_options.get("dev_select", 0)) | _lib.DEV_PWX_OFF)
+            self._feature_ctxs[size] = (p, ctx)
+        p, ctx = self._feature_ctxs[size]
+        ctx.forward(x)
+        names = sorted(n for n in p.feature_slots if n.startswith("c"))
         return [ctx.read_slot(p.feature_slots[n], int(x.shape[0]), p.slots[p.feature_slots[n]]) for n in names]
 
     def forward_decoded(self, x: torch.Tensor, center_mode="v8", wh_mode="softplus"):
