@@ -1,12 +1,11 @@
 """What the FPN-neck GPU tests and tools/neck_train_time.py share: a DetectNeck with a case's weights, one forward +
 backward of it, and the device error and bar of every fixture tensor."""
-import numpy as np
 import torch
 
 import yololite_amd as ya
-from _neck_cases import bar, case_inputs, fixture_tensors, level_names
-
-DEV = "cuda:0"
+import _train_dev
+from _neck_cases import case_inputs, fixture_tensors, level_names
+from _train_dev import DEV
 
 
 def neck_of(case, inputs, train=True):
@@ -54,17 +53,4 @@ def run(m, inputs, c_grad=True, layout="nhwc"):
 
 def parity_ratios(case, mode, z):
     """{(level, tensor): (error, bar)} of one case and mode"""
-    inputs = case_inputs(case)
-    got = run(neck_of(case, inputs, mode == "train"), inputs)
-    out = {}
-    for li, d in enumerate(got):
-        want = fixture_tensors(z, case, mode, li)
-        assert set(d) == set(want), sorted(set(d) ^ set(want))
-        for n, (r64, idx, e32, m64) in want.items():
-            g = d[n].numpy().reshape(-1)
-            if n.startswith("num_batches_tracked"):
-                assert int(g[0]) == int(r64[0]), (case["name"], mode, li, n)
-                continue
-            g = g.astype(np.float64)
-            out[(li, n)] = (float(np.abs((g if idx is None else g[idx]) - r64).max()), bar(e32, m64))
-    return out
+    return _train_dev.parity_ratios(case, mode, z, neck_of, run, case_inputs, fixture_tensors)

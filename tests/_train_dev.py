@@ -1,0 +1,52 @@
+"""What the GPU tests of the trainable modules share (detection heads, FPN neck): the device, bit equality of two
+results, the small edge_n model and targets of the end-to-end tests, and the device error and bar of every fixture
+tensor of one case."""
+import numpy as np
+import torch
+
+import yololite_amd as ya
+from yololite_amd.program import synth_state_dict, zoo_meta
+from _head_cases import bar
+
+DEV = "cuda:0"
+
+
+def same(a, b):
+    assert set(a) == set(b)
+    for n in a:
+        assert torch.equal(a[n], b[n]), n
+
+
+def edge_n():
+    meta = zoo_meta("edge_n", num_classes=3, img_size=64)
+    sd = synth_state_dict(meta)
+    model = ya.build_model_from_meta(meta)
+    model.load_state_dict(sd)
+    model.to(DEV)
+    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(5)).to(DEV)
+    return meta, sd, model, x
+
+
+def targets(cfg):
+    off = cfg["gt_off"]
+    return [{"boxes": torch.tensor(cfg["gt_xyxy"][off[b]:off[b + 1]], dtype=torch.float32).reshape(-1, 4),
+             "labels": torch.tensor(cfg["gt_label"][off[b]:off[b + 1]], dtype=torch.int64)} for b in range(cfg["B"])]
+
+
+def parity_ratios(case, mode, z, module_of, run, case_inputs, fixture_tensors):
+    """{(level, tensor): (error, bar)} of one case and mode: run(module_of(case, inputs, train), inputs) against the
+    fixture `z`, whose layout fixture_tensors knows"""
+    inputs = case_inputs(case)
+    got = run(module_of(case, inputs, mode == "train"), inputs)
+    out = {}
+    for li, d in enumerate(got):
+        want = fixture_tensors(z, case, mode, li)
+        assert set(d) == set(want), sorted(set(d) ^ set(want))
+        for n, (r64, idx, e32, m64) in want.items():
+            g = d[n].numpy().reshape(-1)
+            if n.startswith("num_batches_tracked"):
+                assert int(g[0]) == int(r64[0]), (case["name"], mode, li, n)
+                continue
+            g = g.astype(np.float64)
+            out[(li, n)] = (float(np.abs((g if idx is None else g[idx]) - r64).max()), bar(e32, m64))
+    return out

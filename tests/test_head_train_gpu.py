@@ -11,10 +11,10 @@ import pytest
 import torch
 
 import yololite_amd as ya
-from yololite_amd.program import synth_state_dict, zoo_meta
 from _head_cases import CASES, E2E, FIXTURE, bar, case_inputs, fixture_tensors, modes
-from _head_dev import DEV, heads_of as _heads, parity_ratios, run as _run
+from _head_dev import heads_of as _heads, parity_ratios, run as _run
 from _head_np import head_forward
+from _train_dev import DEV, edge_n as _edge_n, same as _same, targets as _targets
 
 pytestmark = pytest.mark.gpu
 
@@ -45,12 +45,6 @@ def test_large_tensors_agree_with_the_restatement_everywhere():
             if idx is not None:
                 err = np.abs(d[n].numpy().astype(np.float64) - ref[n]).max()
                 assert err <= bar(e32, m64), (li, n, err, bar(e32, m64))
-
-
-def _same(a, b):
-    assert set(a) == set(b)
-    for n in a:
-        assert torch.equal(a[n], b[n]), n
 
 
 def test_two_runs_give_the_same_bits_in_every_input_layout():
@@ -130,6 +124,34 @@ def test_no_grad_saves_nothing_and_holds_one_blocks_buffers():
         ys[0].sum().backward()
 
 
+def test_the_handles_memory_grows_never_shrinks_and_is_cut_the_same_inside_a_larger_buffer():
+    """the handle's memory through S = 4, 8, 4 (two blocks, so a block offset exists; two sizes, so the second S = 4
+    step is cut out of a buffer made for S = 8): what it holds is the plan's, growth drops the held forward, nothing
+    shrinks, and the step in the larger buffer gives the bits of a fresh module that ran only that step"""
+    small = dict(name="arena", F=8, C=2, A=1, depth=2, B=2, sizes=(4,), seed=909)
+    ins, inb = case_inputs(small), case_inputs(dict(small, sizes=(8,)))
+    p4, p8 = (ya.headops.plan(8, 2, 1, 2, 2, S) for S in (4, 8))
+    assert p8["saved_bytes"] > p4["saved_bytes"] and p8["workspace_bytes"] > p4["workspace_bytes"]
+    m = _heads(small, ins)
+    x4, x8 = torch.from_numpy(ins[0]["x"]).to(DEV), torch.from_numpy(inb[0]["x"]).to(DEV)
+    y1 = m([x4], layout="nhwc")
+    assert m.held() == [dict(saved_bytes=p4["saved_bytes"], workspace_bytes=p4["workspace_bytes"], forward_held=1)]
+    m([x8], layout="nhwc")
+    grown = dict(saved_bytes=p8["saved_bytes"], workspace_bytes=p8["workspace_bytes"], forward_held=1)
+    assert m.held() == [grown]
+    with pytest.raises(ya.YoloLiteHipError, match="another forward"):
+        y1[0].sum().backward()
+    m.zero_grad(set_to_none=True)
+    x = x4.clone().requires_grad_(True)
+    y = m([x], layout="nhwc")[0]
+    assert m.held() == [grown]
+    y.backward(torch.from_numpy(ins[0]["gy"]).to(DEV))
+    fresh = _run(_heads(small, ins), ins)[0]
+    assert torch.equal(y.detach().cpu(), fresh["y"]) and torch.equal(x.grad.cpu(), fresh["dx"])
+    grads = {"g." + n: p.grad.cpu() for n, p in m.named_parameters()}
+    _same(grads, {n: v for n, v in fresh.items() if n.startswith("g.")})
+
+
 def test_a_cube_shaped_map_goes_by_the_layout_it_is_given():
     """S == F: [B,8,8,8] reads as NCHW and as NHWC.  Without a layout it is refused; with one the result is that of the
     float64 restatement on the map so read, and the other reading gives another result."""
@@ -203,16 +225,6 @@ def _check_against_executor(model, heads, x):
         assert o.shape == t.shape and diff <= 2 * b, (li, diff, b)
 
 
-def _edge_n():
-    meta = zoo_meta("edge_n", num_classes=3, img_size=64)
-    sd = synth_state_dict(meta)
-    model = ya.build_model_from_meta(meta)
-    model.load_state_dict(sd)
-    model.to(DEV)
-    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(5)).to(DEV)
-    return meta, sd, model, x
-
-
 def test_eval_heads_agree_with_the_executor():
     meta, sd, model, x = _edge_n()
     before = [o.clone() for o in model(x)]
@@ -221,12 +233,6 @@ def test_eval_heads_agree_with_the_executor():
     _check_against_executor(model, ya.DetectHeads.from_state_dict(meta, sd).to(DEV), x)
     for a, b in zip(before, model(x)):                      # the executor's own contexts behave as before
         assert torch.equal(a, b)
-
-
-def _targets(cfg):
-    off = cfg["gt_off"]
-    return [{"boxes": torch.tensor(cfg["gt_xyxy"][off[b]:off[b + 1]], dtype=torch.float32).reshape(-1, 4),
-             "labels": torch.tensor(cfg["gt_label"][off[b]:off[b + 1]], dtype=torch.int64)} for b in range(cfg["B"])]
 
 
 def test_twenty_steps_fit_one_batch_as_the_float64_loop_does():

@@ -13,11 +13,11 @@ import pytest
 import torch
 
 import yololite_amd as ya
-from yololite_amd.program import synth_state_dict, zoo_meta
 from _head_np import head_forward
 from _neck_cases import CASES, E2E, FIXTURE, bar, case_inputs, fixture_tensors, head_inputs, modes
-from _neck_dev import DEV, neck_of as _neck, parity_ratios, run as _run
+from _neck_dev import neck_of as _neck, parity_ratios, run as _run
 from _neck_np import neck_all, neck_forward
+from _train_dev import DEV, edge_n as _edge_n, same as _same, targets as _targets
 
 pytestmark = pytest.mark.gpu
 
@@ -65,12 +65,6 @@ def test_sampled_tensors_agree_with_the_restatement_everywhere(name):
         _, _, e32, m64 = fixture_tensors(z, case, "train", li)[n]
         err = np.abs(got[li][n].numpy().astype(np.float64) - ref[li][n]).max()
         assert err <= bar(e32, m64), (li, n, err, bar(e32, m64))
-
-
-def _same(a, b):
-    assert set(a) == set(b)
-    for n in a:
-        assert torch.equal(a[n], b[n]), n
 
 
 def test_two_runs_give_the_same_bits_in_both_input_layouts():
@@ -163,6 +157,39 @@ def test_no_grad_saves_nothing_and_holds_one_blocks_buffers():
         ps[0].sum().backward()
 
 
+def test_the_handles_memory_grows_never_shrinks_and_is_cut_the_same_inside_a_larger_buffer():
+    """the handle's memory through the sizes (4, 2), (8, 4), (4, 2) (two blocks, so a block offset exists; two sizes, so
+    the second small step is cut out of buffers made for the larger one, and the nearest maps are made twice more): what
+    it holds is the plan's, growth drops the held forward, nothing shrinks, and the step in the larger buffers gives the
+    bits of a fresh module that ran only that step"""
+    small = dict(name="arena", B=2, F=8, Cin=(8, 8), depth=2, sizes=(4, 2), seed=919)
+    big = dict(small, sizes=(8, 4))
+    ins, inb = case_inputs(small), case_inputs(big)
+    plan, plan_big = (ya.neckops.plan((8, 8), 8, 2, 2, c["sizes"]) for c in (small, big))
+    assert plan_big["saved_bytes"] > plan["saved_bytes"] and plan_big["workspace_bytes"] > plan["workspace_bytes"]
+    m = _neck(small, ins)
+    cs, cb = ([torch.from_numpy(lv["c"]).to(DEV) for lv in i] for i in (ins, inb))
+    p1 = m(cs, layout="nhwc")
+    assert m.held() == dict(saved_bytes=plan["saved_bytes"], workspace_bytes=plan["workspace_bytes"], forward_held=1)
+    m(cb, layout="nhwc")
+    grown = dict(saved_bytes=plan_big["saved_bytes"], workspace_bytes=plan_big["workspace_bytes"], forward_held=1)
+    assert m.held() == grown
+    with pytest.raises(ya.YoloLiteHipError, match="another forward"):
+        p1[0].sum().backward()
+    m.zero_grad(set_to_none=True)
+    cs = [c.clone().requires_grad_(True) for c in cs]
+    ps = m(cs, layout="nhwc")
+    assert m.held() == grown
+    torch.autograd.backward(ps, [torch.from_numpy(lv["gp"]).to(DEV) for lv in ins])
+    fresh = _run(_neck(small, ins), ins)
+    grads = {"g." + n: q.grad.cpu() for n, q in m.named_parameters()}
+    for lv, c, p, f in zip(ins, cs, ps, fresh):
+        assert torch.equal(p.detach().cpu(), f["p"]) and torch.equal(c.grad.cpu(), f["dc"])
+        own = {n: v for n, v in grads.items() if n.startswith((f"g.lateral{lv['k']}.", f"g.smooth{lv['k']}."))}
+        _same(own, {n: v for n, v in f.items() if n.startswith("g.")})
+    assert sum(n.startswith("g.") for f in fresh for n in f) == len(grads)
+
+
 def test_a_second_forward_replaces_the_held_one_and_single_value_batches_raise():
     case = BY_NAME["base"]
     inputs = case_inputs(case)
@@ -176,16 +203,6 @@ def test_a_second_forward_replaces_the_held_one_and_single_value_batches_raise()
         m([c[:1, :1, :1] for c in cs], layout="nhwc")
     m.eval()
     assert m([c[:1, :1, :1] for c in cs], layout="nhwc")[0].shape == (1, 1, 1, 16)
-
-
-def _edge_n():
-    meta = zoo_meta("edge_n", num_classes=3, img_size=64)
-    sd = synth_state_dict(meta)
-    model = ya.build_model_from_meta(meta)
-    model.load_state_dict(sd)
-    model.to(DEV)
-    x = torch.randn(2, 3, 64, 64, generator=torch.Generator().manual_seed(5)).to(DEV)
-    return meta, sd, model, x
 
 
 def _restated(neck, heads, feats):
@@ -239,12 +256,6 @@ def test_eval_neck_and_heads_agree_with_the_executor():
         assert torch.equal(a, b)
     for a, b in zip(pbefore, model.pyramid(x)):
         assert torch.equal(a, b)
-
-
-def _targets(cfg):
-    off = cfg["gt_off"]
-    return [{"boxes": torch.tensor(cfg["gt_xyxy"][off[b]:off[b + 1]], dtype=torch.float32).reshape(-1, 4),
-             "labels": torch.tensor(cfg["gt_label"][off[b]:off[b + 1]], dtype=torch.int64)} for b in range(cfg["B"])]
 
 
 def test_twenty_steps_fit_one_batch_as_the_float64_loop_does():

@@ -16,16 +16,16 @@ to F.  With --trace only --steps steps per side are run once (for `rocprofv3 --k
 tools/head_train_time.py --trace ...`).
 
     python tools/head_train_time.py [--models edge_n,yololite_m] [--blocks 7] [--steps 20] [--out F] [--parity F] [--trace]"""
-import argparse
 import json
 import os
 import sys
-import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
+
+from tools import _train_time as tt  # noqa: E402
 
 SHAPES = {"edge_n": dict(F=96, depth=1, B=64, sizes=(80, 40, 20)), "yololite_m": dict(F=328, depth=2, B=32, sizes=(80, 40, 20))}
 NC, A = 80, 1
@@ -36,21 +36,12 @@ def torch_heads(F, depth, nlevels):
     import torch
     from torch import nn
 
-    class Block(nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.block = nn.Sequential(nn.Conv2d(F, F, 3, padding=1, groups=F, bias=False), nn.Conv2d(F, F, 1, bias=False),
-                                       nn.BatchNorm2d(F), nn.ReLU(inplace=True))
-
-        def forward(self, x):
-            return self.block(x)
-
     class Heads(nn.Module):
         def __init__(self):
             super().__init__()
             for i in range(nlevels):
                 setattr(self, f"head{3 + i}", nn.ModuleDict({
-                    "trunk": nn.Sequential(*[Block() for _ in range(depth)]),
+                    "trunk": nn.Sequential(*[tt.torch_block(F, 1) for _ in range(depth)]),
                     "out": nn.ModuleDict({"box": nn.Conv2d(F, A * 4, 1), "obj": nn.Conv2d(F, A, 1),
                                           "cls": nn.Conv2d(F, A * NC, 1)})}))
 
@@ -69,7 +60,6 @@ def torch_heads(F, depth, nlevels):
 
 
 def run_model(name, blocks, steps, trace):
-    import numpy as np
     import torch
     import yololite_amd as ya
     from yololite_amd import headops
@@ -90,14 +80,6 @@ def run_model(name, blocks, steps, trace):
             p.grad = None
         torch.autograd.backward(m(x, layout="nhwc") if m is ours else m(x), gys)
 
-    def block(m, x, n):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            step(m, x)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / n
-
     plans = [headops.plan(F, NC, A, depth, B, S) for S in sizes]
     saved = sum(p["saved_bytes"] for p in plans)
     act = sum(4 * p["rows"] * F for p in plans)
@@ -108,17 +90,9 @@ def run_model(name, blocks, steps, trace):
            # gradient 6 over its three tap rows, and the output convolutions' 2 reads of h counted once per level below),
            # the input gradient of every block but the first 2; the level tensor is written once and its gradient read twice
            "bytes_moved_estimate": act * (27 * depth + 2 * (depth - 1) + 2) + 3 * sum(4 * p["rows"] * A * (5 + NC) for p in plans)}
-    if trace:
-        block(ours, feats, steps); block(ref, feats_cl, steps)
-        res["launches_per_step"] = sum(l["forward"] + l["backward"] for l in ours.last_launches())
+    launches = lambda: sum(l["forward"] + l["backward"] for l in ours.last_launches())    # noqa: E731
+    if not tt.time_sides(res, lambda: step(ours, feats), lambda: step(ref, feats_cl), launches, blocks, steps, trace):
         return res
-    for _ in range(2):
-        block(ours, feats, 3); block(ref, feats_cl, 3)
-    to, tr = [], []
-    for _ in range(blocks):
-        to.append(block(ours, feats, steps)); tr.append(block(ref, feats_cl, steps))
-    # same weights, same inputs: both sides against the torch module in float64, one step (largest error over the
-    # parameter gradients, relative to the gradient's largest element)
     ref64 = torch_heads(F, depth, len(sizes)).to(dev).double().train()
     ref64.load_state_dict(ours.state_dict())
     # A BatchNorm output within fp32 rounding of zero gets another ReLU mask in fp32 than in float64.  One such element
@@ -137,28 +111,13 @@ def run_model(name, blocks, steps, trace):
     flips = sum(int((a != b).sum()) for a, b in zip(masks["f32"], masks["f64"]))
     elements = sum(a.numel() for a in masks["f64"])
     del masks
-    worst, worst_t, between, l2, l2_t = (0.0, ""), (0.0, ""), (0.0, ""), 0.0, 0.0
-    for (n, p), q, r in zip(ours.named_parameters(), ref.parameters(), ref64.parameters()):
-        m = r.grad.abs().max().clamp_min(1e-300)
-        worst = max(worst, (float((p.grad.double() - r.grad).abs().max() / m), n))
-        worst_t = max(worst_t, (float((q.grad.double() - r.grad).abs().max() / m), n))
-        between = max(between, (float((p.grad.double() - q.grad.double()).abs().max() / m), n))
-        l2 = max(l2, float((p.grad.double() - r.grad).norm() / r.grad.norm().clamp_min(1e-300)))
-        l2_t = max(l2_t, float((q.grad.double() - r.grad).norm() / r.grad.norm().clamp_min(1e-300)))
+    res.update(tt.grad_errors(ours, ref, ref64, between=True))
+    at = res["device_max_rel_grad_error_at"]
     # of the device's worst gradient: how many of its rows (output channels) carry an error above 1e-4 of its largest entry
-    pw, rw = dict(ours.named_parameters())[worst[1]].grad.double(), dict(ref64.named_parameters())[worst[1]].grad
+    pw, rw = dict(ours.named_parameters())[at].grad.double(), dict(ref64.named_parameters())[at].grad
     rows_off = int((((pw - rw).abs().reshape(pw.shape[0], -1).amax(1) / rw.abs().max()) > 1e-4).sum())
     del ref64
-    res.update({"blocks": blocks, "launches_per_step": sum(l["forward"] + l["backward"] for l in ours.last_launches()),
-                "device_ms": round(float(np.median(to)), 4), "device_ms_min": round(float(np.min(to)), 4),
-                "torch_ms": round(float(np.median(tr)), 4), "torch_ms_min": round(float(np.min(tr)), 4),
-                "ratio": round(float(np.median(tr)) / float(np.median(to)), 3),
-                "device_ms_blocks": [round(v, 4) for v in to], "torch_ms_blocks": [round(v, 4) for v in tr],
-                "device_max_rel_grad_error_vs_float64": worst[0], "device_max_rel_grad_error_at": worst[1],
-                "torch_max_rel_grad_error_vs_float64": worst_t[0], "torch_max_rel_grad_error_at": worst_t[1],
-                "device_vs_torch_max_rel_grad_difference": between[0], "device_vs_torch_max_rel_grad_difference_at": between[1],
-                "device_max_rel_l2_grad_error_vs_float64": l2, "torch_max_rel_l2_grad_error_vs_float64": l2_t,
-                "device_worst_gradient_rows_above_1e-4": rows_off, "device_worst_gradient_rows": int(pw.shape[0]),
+    res.update({"device_worst_gradient_rows_above_1e-4": rows_off, "device_worst_gradient_rows": int(pw.shape[0]),
                 "torch_relu_masks_differing_from_float64": flips, "batchnorm_outputs": elements})
     return res
 
@@ -180,29 +139,5 @@ def parity(path):
     return {"worst_ratio": round(worst[0], 4), "at": worst[1], "tensors": len(rows)}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--models", default="edge_n,yololite_m")
-    ap.add_argument("--blocks", type=int, default=7)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--parity", default="")
-    ap.add_argument("--trace", action="store_true")
-    args = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("head_train_time.py needs a HIP device")
-    res = {"gpu": torch.cuda.get_device_name(0), "num_classes": NC, "runs": []}
-    for name in [m for m in args.models.split(",") if m]:
-        res["runs"].append(run_model(name, args.blocks, args.steps, args.trace))
-    if args.parity:
-        res["parity"] = parity(args.parity)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    tt.main("head_train_time.py", "edge_n,yololite_m", run_model, header={"num_classes": NC}, parity=parity)

@@ -16,16 +16,15 @@ With --trace only --steps steps per side are run once (for `rocprofv3 --kernel-t
 tools/neck_train_time.py --trace ...`).
 
     python tools/neck_train_time.py [--models edge_n,edge_l] [--blocks 7] [--steps 20] [--out F] [--trace]"""
-import argparse
-import json
 import os
 import sys
-import time
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 for p in (ROOT, os.path.join(ROOT, "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
+
+from tools import _train_time as tt  # noqa: E402
 
 SHAPES = {"edge_n": dict(F=96, depth=1, Cin=(32, 48, 480), B=64, sizes=(80, 40, 20)),
           "edge_l": dict(F=320, depth=2, Cin=(64, 96, 960), B=32, sizes=(80, 40, 20))}
@@ -36,25 +35,13 @@ def torch_neck(F, depth, cins):
     import torch.nn.functional as TF
     from torch import nn
 
-    class Block(nn.Module):
-        def __init__(self):
-            super().__init__()
-            layers = []
-            for _ in range(depth):
-                layers += [nn.Conv2d(F, F, 3, padding=1, groups=F, bias=False), nn.Conv2d(F, F, 1, bias=False),
-                           nn.BatchNorm2d(F), nn.ReLU(inplace=True)]
-            self.block = nn.Sequential(*layers)
-
-        def forward(self, x):
-            return self.block(x)
-
     class Neck(nn.Module):
         def __init__(self):
             super().__init__()
             for i, ci in enumerate(cins):
                 setattr(self, f"lateral{3 + i}", nn.Conv2d(ci, F, 1))
             for i in range(len(cins)):
-                setattr(self, f"smooth{3 + i}", Block())
+                setattr(self, f"smooth{3 + i}", tt.torch_block(F, depth))
 
         def forward(self, feats):
             ps, prev = [None] * len(feats), None
@@ -69,7 +56,6 @@ def torch_neck(F, depth, cins):
 
 
 def run_model(name, blocks, steps, trace):
-    import numpy as np
     import torch
     import yololite_amd as ya
     from yololite_amd import neckops
@@ -94,14 +80,6 @@ def run_model(name, blocks, steps, trace):
         else:
             torch.autograd.backward(m(feats_cl), gps_cl)
 
-    def block(m, n):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(n):
-            step(m)
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) * 1e3 / n
-
     plan = neckops.plan(cins, F, depth, B, sizes)
     rows = [lp["rows"] for lp in plan["levels"]]
     act = sum(4 * M * F for M in rows)
@@ -115,60 +93,15 @@ def run_model(name, blocks, steps, trace):
            # coarser p read by the lateral's epilogue is a quarter and left out.  The feature maps (M x Cin) are read by
            # the lateral and by its weight gradient; no dc is asked for.
            "bytes_moved_estimate": act * (29 * depth + 8) + 2 * cact}
-    if trace:
-        block(ours, steps); block(ref, steps)
-        res["launches_per_step"] = sum(ours.last_launches().values())
+    launches = lambda: sum(ours.last_launches().values())    # noqa: E731
+    if not tt.time_sides(res, lambda: step(ours), lambda: step(ref), launches, blocks, steps, trace):
         return res
-    for _ in range(2):
-        block(ours, 3); block(ref, 3)
-    to, tr = [], []
-    for _ in range(blocks):
-        to.append(block(ours, steps)); tr.append(block(ref, steps))
-    # same weights, same inputs: both sides against the torch module in float64, one step (largest error over the
-    # parameter gradients, relative to the gradient's largest element; and the L2 error, which a flipped ReLU mask of
-    # a BatchNorm output within fp32 rounding of zero does not dominate)
     ref64 = torch_neck(F, depth, cins).to(dev).double().train()
     ref64.load_state_dict(ours.state_dict())
     torch.autograd.backward(ref64([f.double() for f in feats_cl]), [g.double() for g in gps_cl])
-    worst, worst_t, l2, l2_t = (0.0, ""), (0.0, ""), 0.0, 0.0
-    for (n, p), q, r in zip(ours.named_parameters(), ref.parameters(), ref64.parameters()):
-        m = r.grad.abs().max().clamp_min(1e-300)
-        worst = max(worst, (float((p.grad.double() - r.grad).abs().max() / m), n))
-        worst_t = max(worst_t, (float((q.grad.double() - r.grad).abs().max() / m), n))
-        l2 = max(l2, float((p.grad.double() - r.grad).norm() / r.grad.norm().clamp_min(1e-300)))
-        l2_t = max(l2_t, float((q.grad.double() - r.grad).norm() / r.grad.norm().clamp_min(1e-300)))
-    del ref64
-    res.update({"blocks": blocks, "launches_per_step": sum(ours.last_launches().values()),
-                "device_ms": round(float(np.median(to)), 4), "device_ms_min": round(float(np.min(to)), 4),
-                "torch_ms": round(float(np.median(tr)), 4), "torch_ms_min": round(float(np.min(tr)), 4),
-                "ratio": round(float(np.median(tr)) / float(np.median(to)), 3),
-                "device_ms_blocks": [round(v, 4) for v in to], "torch_ms_blocks": [round(v, 4) for v in tr],
-                "device_max_rel_grad_error_vs_float64": worst[0], "device_max_rel_grad_error_at": worst[1],
-                "torch_max_rel_grad_error_vs_float64": worst_t[0], "torch_max_rel_grad_error_at": worst_t[1],
-                "device_max_rel_l2_grad_error_vs_float64": l2, "torch_max_rel_l2_grad_error_vs_float64": l2_t})
+    res.update(tt.grad_errors(ours, ref, ref64))
     return res
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--models", default="edge_n,edge_l")
-    ap.add_argument("--blocks", type=int, default=7)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default="")
-    ap.add_argument("--trace", action="store_true")
-    args = ap.parse_args()
-    import torch
-    if not torch.cuda.is_available():
-        raise SystemExit("neck_train_time.py needs a HIP device")
-    res = {"gpu": torch.cuda.get_device_name(0), "runs": []}
-    for name in [m for m in args.models.split(",") if m]:
-        res["runs"].append(run_model(name, args.blocks, args.steps, args.trace))
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
-
-
 if __name__ == "__main__":
-    main()
+    tt.main("neck_train_time.py", "edge_n,edge_l", run_model)

@@ -1,0 +1,190 @@
+"""What the trainable modules on the device share (headops.DetectHeads, neckops.DetectNeck): the handle of one library
+object, the depthwise block's container and its entry in the library's tables, the reading of feature maps, checkpoints
+and meta, and the parts of an autograd.Function that do not depend on the module.
+
+One handle holds ONE forward for backward at a time (csrc/yl_block.h, Arena): every forward bumps the handle's
+generation, and a backward whose generation is no longer the handle's raises.  The handle's memory only grows.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, List, Optional, Sequence
+
+import torch
+from torch import nn
+
+from . import _lib
+
+
+class DeviceHandle:
+    """A `<prefix>_create`d library object (prefix "yl_head", "yl_neck") of the config `cfg(*args)`, made on first use
+    and again when the device changes.  A subclass adds table(): the order its tensors go to the library in."""
+
+    def __init__(self, prefix: str, cfg, *args):
+        self.prefix, self.cfg, self.args = prefix, cfg, args
+        self.handle, self.lib, self.device = None, None, None
+        self.generation = 0
+        self.last_launches = {"forward": 0, "backward": 0}
+
+    def __deepcopy__(self, memo):                          # a copied module (an EMA) gets a handle of its own
+        return type(self)(*self.args)
+
+    def __reduce__(self):
+        return type(self), self.args
+
+    def call(self, name: str, *args):
+        what = f"{self.prefix}_{name}"
+        _lib.check(getattr(self.lib, what)(self.handle, *args), what=what)
+
+    def held(self) -> Dict[str, int]:
+        """<prefix>_held: bytes the handle holds now and whether a forward is held for backward"""
+        if self.handle is None:
+            return {"saved_bytes": 0, "workspace_bytes": 0, "forward_held": 0}
+        sb, wb, fv = C.c_int64(), C.c_int64(), C.c_int32()
+        self.call("held", C.byref(sb), C.byref(wb), C.byref(fv))
+        return {"saved_bytes": int(sb.value), "workspace_bytes": int(wb.value), "forward_held": int(fv.value)}
+
+    def ensure(self, device: torch.device):
+        if self.handle is not None and self.device == device:
+            return
+        self.close()
+        self.lib = _lib.load()
+        h = C.c_void_p()
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        what = self.prefix + "_create"
+        _lib.check(getattr(self.lib, what)(idx, C.byref(self.cfg(*self.args)), C.byref(h)), what=what)
+        self.handle, self.device = h, device
+
+    def close(self):
+        if self.handle:
+            getattr(self.lib, self.prefix + "_destroy")(self.handle)
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def launch(self, name: str, device: torch.device, *args):
+        """<prefix>_forward / _backward(handle, *args, stream, &launches) on torch's current stream of `device`.  A
+        forward that went through is a new generation: what an earlier one held for backward is gone."""
+        n = C.c_int32()
+        self.call(name, *args, torch.cuda.current_stream(device).cuda_stream, C.byref(n))
+        if name == "forward":
+            self.generation += 1
+        self.last_launches[name] = int(n.value)
+
+    def check_generation(self, generation: int, subject: str, rule: str):
+        if generation != self.generation:
+            raise _lib.YoloLiteHipError(f"{subject} ran another forward since the one backward() belongs to "
+                                        f"({rule} is held at a time)")
+
+
+def dw_block(F: int, n: int) -> nn.Module:
+    """Container only (the reference's DWConvBlock(F, F, n)): the layers hold the parameters; their forward is never called."""
+    m = nn.Module()
+    layers = []
+    for _ in range(n):
+        layers += [nn.Conv2d(F, F, 3, padding=1, groups=F, bias=False), nn.Conv2d(F, F, 1, bias=False),
+                   nn.BatchNorm2d(F), nn.ReLU(inplace=True)]
+    m.block = nn.Sequential(*layers)
+    return m
+
+
+def ptr(t: Optional[torch.Tensor]):
+    return t.data_ptr() if t is not None else None
+
+
+def fill_block(b, params4: Sequence[Optional[torch.Tensor]], buffers3=None):
+    """one yl_head_block: dw, pw, gamma, beta (None = NULL) and, for a parameter table, the BatchNorm's three buffers"""
+    b.dw, b.pw, b.gamma, b.beta = (ptr(v) for v in params4)
+    if buffers3 is not None:
+        b.running_mean, b.running_var, b.num_batches_tracked = (ptr(v) for v in buffers3)
+
+
+def aligned(t: torch.Tensor) -> torch.Tensor:
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
+
+
+def as_nhwc(f, channels: int, layout: Optional[str], who: str, training: bool, *, name: str = "F",
+            bn_channels: Optional[int] = None) -> torch.Tensor:
+    """One feature map as an NHWC view.  `layout`: "nchw" ([B,C,S,S], any strides), "nhwc" ([B,S,S,C]) or None, which
+    reads it off the shape and refuses the one shape that is both.  Host-side facts first, the device last; then what
+    BatchNorm refuses in training (`bn_channels`: of the map the first BatchNorm sees)."""
+    c = channels
+    if not torch.is_tensor(f) or f.dim() != 4:
+        raise ValueError(f"feature maps must be 4-d tensors [B,{name},S,S] or [B,S,S,{name}]")
+    nchw = f.shape[1] == c and f.shape[2] == f.shape[3]
+    nhwc = f.shape[3] == c and f.shape[1] == f.shape[2]
+    if layout is None and nchw and nhwc:
+        raise ValueError(f"feature map {tuple(f.shape)} reads as [B,{c},S,S] and as [B,S,S,{c}]: "
+                         "pass layout='nchw' or layout='nhwc'")
+    if not (nchw if layout == "nchw" else nhwc if layout == "nhwc" else nchw or nhwc):
+        want = {None: f"neither [B,{c},S,S] nor [B,S,S,{c}]", "nchw": f"not [B,{c},S,S]", "nhwc": f"not [B,S,S,{c}]"}
+        raise ValueError(f"feature map {tuple(f.shape)} is {want[layout]}")
+    if layout == "nchw" or (layout is None and nchw):
+        f = f.permute(0, 2, 3, 1)                          # NCHW -> an NHWC view (channels-last memory: already contiguous)
+    if not f.is_cuda:
+        raise _lib.YoloLiteHipError(f"{who} needs its inputs on a HIP device (no CPU fallback)")
+    if training and f.shape[0] * f.shape[1] * f.shape[2] == 1:
+        raise ValueError("Expected more than 1 value per channel when training, got input size "
+                         f"{[int(f.shape[0]), c if bn_channels is None else bn_channels, 1, 1]}")
+    return f
+
+
+def check_layout(layout: Optional[str], feats, levels: int) -> list:
+    """the arguments of a module's forward: -> the feature maps as a list"""
+    feats = list(feats)
+    if layout not in (None, "nchw", "nhwc"):
+        raise ValueError(f"layout must be 'nchw', 'nhwc' or None, got {layout!r}")
+    if len(feats) != levels:
+        raise ValueError(f"expected {levels} feature maps, got {len(feats)}")
+    return feats
+
+
+def fill_from_state_dict(module: nn.Module, sd: dict, what: str) -> nn.Module:
+    """fills `module` with the checkpoint's entries of its own keys (tensors or numpy arrays, any shape of the right
+    size); only num_batches_tracked may be absent"""
+    own = module.state_dict()
+    missing = [k for k in own if k not in sd and not k.endswith("num_batches_tracked")]
+    if missing:
+        raise KeyError(f"checkpoint lacks {what} entries: {missing[:4]}")
+    module.load_state_dict({k: torch.as_tensor(sd[k]).reshape(v.shape).to(v.dtype) for k, v in own.items() if k in sd},
+                           strict=False)
+    return module
+
+
+def meta_fpn(meta: dict):
+    """-> (fpn channels, level names finest first, model config, training config) of the model `meta` describes
+    (program.build_program reads the same keys)"""
+    cfg = meta.get("config", {}) or {}
+    mcfg, tcfg = cfg.get("model", {}) or {}, cfg.get("training", {}) or {}
+    F = int(int(mcfg.get("fpn_channels", 128)) * float(mcfg.get("width_multiple", 1.0)))
+    names = (["p2"] if tcfg.get("use_p2") else []) + ["p3", "p4", "p5"] + (["p6"] if tcfg.get("use_p6") else [])
+    return F, names, mcfg, tcfg
+
+
+# ---- the parts of an autograd.Function's forward and backward that are the same for every module
+
+def saving(fctx, grad_mode: bool) -> bool:
+    """needs_input_grad reports requires_grad whatever the grad mode, and inside a Function's forward the mode is always
+    off: the caller says whether a graph is being recorded.  Without one nothing is saved."""
+    return grad_mode and any(fctx.needs_input_grad)
+
+
+def detached_params(who: str, params: Sequence[torch.Tensor], device: torch.device) -> List[torch.Tensor]:
+    ps = [p.detach() for p in params]
+    for p in ps:
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device != device:
+            raise _lib.YoloLiteHipError(f"{who}: parameters must be contiguous fp32 tensors on the input's device")
+    return ps
+
+
+def flags(train: bool, save: bool) -> int:
+    return (_lib.YL_HEAD_TRAIN if train else 0) | (_lib.YL_HEAD_SAVE if save else 0)
+
+
+def grads_like(tensors: Sequence[torch.Tensor], need: Sequence[bool]) -> List[Optional[torch.Tensor]]:
+    """an uninitialised contiguous gradient for every tensor whose entry of `need` (a slice of needs_input_grad) is set"""
+    return [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(tensors, need)]

@@ -1,7 +1,8 @@
 // The DWConvBlock of the reference (scripts/model/model_v2.py:23-39) on NHWC fp32 rows, shared by the detection heads
-// (yl_head.hip) and the FPN neck (yl_neck.hip): its kernels, the GEMM they share, and the launch sequences of a run of
-// blocks forward and backward.  Everything lives in an anonymous namespace: each translation unit that includes this
-// header compiles the kernels it launches into its own code object.
+// (yl_head.hip) and the FPN neck (yl_neck.hip): its kernels, the GEMM they share, the launch sequences of a run of
+// blocks forward and backward, and the host side every trainable handle has: its device memory (Arena), the cut of a run
+// of blocks out of it, and the checks of the parameter and gradient tables.  Everything lives in an anonymous namespace:
+// each translation unit that includes this header compiles the kernels it launches into its own code object.
 //
 //   block t:  d = dw3x3(x)   z = d . W1^T   h = relu(gamma * (z - mean) * invstd + beta)     (d, z, h are kept for backward)
 #ifndef YL_BLOCK_H
@@ -462,6 +463,87 @@ struct Buffers {
   double* spart;
 };
 struct BlockDims { int M, S, F, stat_tiles, wgrad_rows, wgrad_splits; };
+template <class Plan>                    // yl_head_plan_info, yl_neck_level_plan
+BlockDims dims_of(const Plan& pl, int S, int F) { return {pl.rows, S, F, pl.stat_tiles, pl.wgrad_rows, pl.wgrad_splits}; }
+
+// `blocks` blocks' d, z, h (`act` bytes each) and then their statistics, cut out of the saved buffer at `p`; the entries
+// of the blocks beyond are NULL.  -> the cursor behind them
+inline char* carve_blocks(char* p, int blocks, size_t act, size_t F, Buffers* bf) {
+  for (int t = 0; t < YL_HEAD_MAX_DEPTH; ++t) bf->d[t] = bf->z[t] = bf->h[t] = bf->stats[t] = nullptr;
+  for (int t = 0; t < blocks; ++t) {
+    bf->d[t] = (float*)p; p += act;
+    bf->z[t] = (float*)p; p += act;
+    bf->h[t] = (float*)p; p += act;
+  }
+  for (int t = 0; t < blocks; ++t) { bf->stats[t] = (float*)p; p += 2 * F * 4; }
+  return p;
+}
+
+// ---- the device memory of one handle: `saved` holds what a forward keeps for backward, `work` the gradients in flight
+// and the partial sums.  One forward is held at a time (fValid); both buffers only ever grow.
+struct Arena {
+  int device;
+  int64_t saved_cap, work_cap;           // bytes the two buffers hold
+  char *saved, *work;
+  int fValid;                            // a forward's activations are held in `saved`
+};
+
+// Both buffers hold at least the need afterwards.  Growing waits for everything enqueued, frees BOTH and drops the held
+// forward (a backward that finds fValid cleared returns YL_ERR_STATE); a smaller need keeps what is there.
+inline yl_status arena_reserve(Arena& a, int64_t need_saved, int64_t need_work) {
+  if (hipSetDevice(a.device) != hipSuccess) return YL_ERR_HIP;
+  if (need_saved <= a.saved_cap && need_work <= a.work_cap) return YL_OK;
+  if (hipDeviceSynchronize() != hipSuccess) return YL_ERR_HIP;
+  const int64_t sb = need_saved > a.saved_cap ? need_saved : a.saved_cap;
+  const int64_t wb = need_work > a.work_cap ? need_work : a.work_cap;
+  hipFree(a.saved); hipFree(a.work);
+  a.saved = a.work = nullptr; a.saved_cap = a.work_cap = 0; a.fValid = 0;
+  if (hipMalloc((void**)&a.saved, (size_t)sb) != hipSuccess || hipMalloc((void**)&a.work, (size_t)wb) != hipSuccess) {
+    hipFree(a.saved); hipFree(a.work);
+    a.saved = a.work = nullptr;
+    (void)hipGetLastError();
+    return YL_ERR_NOMEM;
+  }
+  a.saved_cap = sb; a.work_cap = wb;
+  return YL_OK;
+}
+
+// for the destroy functions: leaves the device current and idle, so the owner may free what else it holds
+inline void arena_release(Arena& a) {
+  hipSetDevice(a.device); hipDeviceSynchronize();
+  hipFree(a.saved); hipFree(a.work);
+  (void)hipGetLastError();
+}
+
+inline yl_status arena_held(const Arena* a, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
+  if (!a) return YL_ERR_INVALID;
+  if (saved_bytes) *saved_bytes = a->saved_cap;
+  if (workspace_bytes) *workspace_bytes = a->work_cap;
+  if (forward_held) *forward_held = a->fValid;
+  return YL_OK;
+}
+
+// the parameter table of blocks 0 .. D - 1: every pointer given and num_batches_tracked (an int64) 8-byte aligned.
+// The float pointers are ORed into *bits; the caller tests their 4-byte alignment together with its own.
+inline bool blocks_params_ok(const yl_head_block* blocks, int D, uintptr_t* bits) {
+  for (int t = 0; t < D; ++t) {
+    const yl_head_block& b = blocks[t];
+    if (!b.dw || !b.pw || !b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked) return false;
+    *bits |= (uintptr_t)b.dw | (uintptr_t)b.pw | (uintptr_t)b.gamma | (uintptr_t)b.beta | (uintptr_t)b.running_mean |
+             (uintptr_t)b.running_var;
+    if ((uintptr_t)b.num_batches_tracked & 7u) return false;
+  }
+  return true;
+}
+
+// the gradient table of the same blocks (NULL: not wanted): its pointers ORed into *bits.  -> is anything wanted
+inline bool blocks_grads_wanted(const yl_head_block* grads, int D, uintptr_t* bits) {
+  uintptr_t any = 0;
+  for (int t = 0; t < D; ++t)
+    any |= (uintptr_t)grads[t].dw | (uintptr_t)grads[t].pw | (uintptr_t)grads[t].gamma | (uintptr_t)grads[t].beta;
+  *bits |= any;
+  return any != 0;
+}
 
 // Blocks 0 .. D - 1 on `in`: per block 4 launches (5 with `train`).  `save` keeps every block's d, z, h apart; without it
 // every block runs in the first block's buffers.  The last block's output goes to `last_out` if that is given.

@@ -34,11 +34,9 @@ bool cfg_ok(const yl_head_cfg* c) {
 }  // namespace
 
 struct yl_head {
-  int device;
+  Arena mem;                             // yl_block.h
   yl_head_cfg cfg;
-  int64_t saved_cap, work_cap;           // bytes the two buffers hold
-  char *saved, *work;
-  int fB, fS, fTrain, fValid;            // the forward whose activations are held
+  int fB, fS, fTrain;                    // the forward whose activations are held (mem.fValid)
 };
 
 extern "C" {
@@ -67,19 +65,12 @@ yl_status yl_head_plan(const yl_head_cfg* cfg, int32_t batch, int32_t size, yl_h
 
 void yl_head_destroy(yl_head* h) {
   if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  hipFree(h->saved); hipFree(h->work);
-  (void)hipGetLastError();
+  arena_release(h->mem);
   delete h;
 }
 
 yl_status yl_head_held(const yl_head* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
-  if (!h) return YL_ERR_INVALID;
-  if (saved_bytes) *saved_bytes = h->saved_cap;
-  if (workspace_bytes) *workspace_bytes = h->work_cap;
-  if (forward_held) *forward_held = h->fValid;
-  return YL_OK;
+  return arena_held(h ? &h->mem : nullptr, saved_bytes, workspace_bytes, forward_held);
 }
 
 yl_status yl_head_create(int32_t device, const yl_head_cfg* cfg, yl_head** out) {
@@ -88,7 +79,7 @@ yl_status yl_head_create(int32_t device, const yl_head_cfg* cfg, yl_head** out) 
   if (hipSetDevice(device) != hipSuccess) return YL_ERR_HIP;
   yl_head* h = new (std::nothrow) yl_head();
   if (!h) return YL_ERR_NOMEM;
-  h->device = device; h->cfg = *cfg;
+  h->mem.device = device; h->cfg = *cfg;
   *out = h;
   return YL_OK;
 }
@@ -100,34 +91,13 @@ namespace {
 // the handle's memory for (batch, size) is cut as yl_head_plan counts it (Buffers: yl_block.h)
 // `blocks`: how many blocks' activations the call keeps apart (head_depth with YL_HEAD_SAVE and in backward, else 1)
 yl_status ensure(yl_head* h, int B, int S, int blocks, yl_head_plan_info* pl, Buffers* bf) {
-  const yl_status st = yl_head_plan(&h->cfg, B, S, pl);
+  yl_status st = yl_head_plan(&h->cfg, B, S, pl);
   if (st != YL_OK) return st;
-  if (hipSetDevice(h->device) != hipSuccess) return YL_ERR_HIP;
-  const int64_t need = pl->saved_bytes / h->cfg.head_depth * blocks;
-  if (need > h->saved_cap || pl->workspace_bytes > h->work_cap) {   // grow: what is held is dropped
-    if (hipDeviceSynchronize() != hipSuccess) return YL_ERR_HIP;
-    const int64_t sb = need > h->saved_cap ? need : h->saved_cap;
-    const int64_t wb = pl->workspace_bytes > h->work_cap ? pl->workspace_bytes : h->work_cap;
-    hipFree(h->saved); hipFree(h->work);
-    h->saved = h->work = nullptr; h->saved_cap = h->work_cap = 0; h->fValid = 0;
-    if (hipMalloc((void**)&h->saved, (size_t)sb) != hipSuccess || hipMalloc((void**)&h->work, (size_t)wb) != hipSuccess) {
-      hipFree(h->saved); hipFree(h->work);
-      h->saved = h->work = nullptr;
-      (void)hipGetLastError();
-      return YL_ERR_NOMEM;
-    }
-    h->saved_cap = sb; h->work_cap = wb;
-  }
+  st = arena_reserve(h->mem, pl->saved_bytes / h->cfg.head_depth * blocks, pl->workspace_bytes);
+  if (st != YL_OK) return st;
   const size_t act = (size_t)pl->rows * h->cfg.channels * 4, F = h->cfg.channels;
-  char* p = h->saved;
-  for (int t = 0; t < YL_HEAD_MAX_DEPTH; ++t) bf->d[t] = bf->z[t] = bf->h[t] = bf->stats[t] = nullptr;
-  for (int t = 0; t < blocks; ++t) {
-    bf->d[t] = (float*)p; p += act;
-    bf->z[t] = (float*)p; p += act;
-    bf->h[t] = (float*)p; p += act;
-  }
-  for (int t = 0; t < blocks; ++t) { bf->stats[t] = (float*)p; p += 2 * F * 4; }
-  p = h->work;
+  carve_blocks(h->mem.saved, blocks, act, F, bf);
+  char* p = h->mem.work;
   bf->ga = (float*)p; p += act;
   bf->gb = (float*)p; p += act;
   const size_t NE = (size_t)h->cfg.num_anchors * (5 + h->cfg.num_classes);
@@ -147,13 +117,7 @@ HeadRows head_rows(const yl_head_cfg& c, const yl_head_tensors* t, int SS) {
 bool params_ok(const yl_head_cfg& c, const yl_head_tensors* t) {
   if (!t) return false;
   uintptr_t any = 0;
-  for (int k = 0; k < c.head_depth; ++k) {
-    const yl_head_block& b = t->block[k];
-    if (!b.dw || !b.pw || !b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked) return false;
-    any |= (uintptr_t)b.dw | (uintptr_t)b.pw | (uintptr_t)b.gamma | (uintptr_t)b.beta | (uintptr_t)b.running_mean |
-           (uintptr_t)b.running_var;
-    if ((uintptr_t)b.num_batches_tracked & 7u) return false;
-  }
+  if (!blocks_params_ok(t->block, c.head_depth, &any)) return false;
   if (!t->box_w || !t->box_b || !t->obj_w || !t->obj_b || !t->cls_w || !t->cls_b) return false;
   any |= (uintptr_t)t->box_w | (uintptr_t)t->box_b | (uintptr_t)t->obj_w | (uintptr_t)t->obj_b | (uintptr_t)t->cls_w |
          (uintptr_t)t->cls_b;
@@ -176,16 +140,16 @@ yl_status yl_head_forward(yl_head* h, const yl_head_tensors* params, const float
   if (st != YL_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   const int M = pl.rows, F = h->cfg.channels, D = h->cfg.head_depth, S = size;
-  const BlockDims dm = {M, S, F, pl.stat_tiles, pl.wgrad_rows, pl.wgrad_splits};
+  const BlockDims dm = dims_of(pl, S, F);
   int nl = 0;
-  h->fValid = 0;
+  h->mem.fValid = 0;
   const float* in = blocks_forward(s, params->block, D, x_dev, bf, save, train, dm, nullptr, &nl);
   const HeadRows hw = head_rows(h->cfg, params, S * S);
   launch_gemm(s, HeadWRows{hw}, RowsVec{in, F}, OutHeadY{y_dev, hw}, hw.g.A * hw.g.E, M, F, F, 1);
   ++nl;
   if (launches) *launches = nl;
   if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
-  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->fValid = 1; }
+  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->mem.fValid = 1; }
   return YL_OK;
 }
 
@@ -194,22 +158,19 @@ yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_h
                            int32_t* launches) {
   if (!h || !grads || !x_dev || !gy_dev || !params_ok(h->cfg, params)) return YL_ERR_INVALID;
   if (((uintptr_t)x_dev & 15u) || ((uintptr_t)dx_dev & 15u) || ((uintptr_t)gy_dev & 3u)) return YL_ERR_UNSUPPORTED;
-  if (!h->fValid || h->fB != batch || h->fS != size) return YL_ERR_STATE;
+  if (!h->mem.fValid || h->fB != batch || h->fS != size) return YL_ERR_STATE;
   yl_head_plan_info pl;
   Buffers bf;
   uintptr_t gany = (uintptr_t)grads->box_w | (uintptr_t)grads->box_b | (uintptr_t)grads->obj_w | (uintptr_t)grads->obj_b |
                    (uintptr_t)grads->cls_w | (uintptr_t)grads->cls_b;
-  for (int t = 0; t < h->cfg.head_depth; ++t) {
-    const yl_head_block& g = grads->block[t];
-    gany |= (uintptr_t)g.dw | (uintptr_t)g.pw | (uintptr_t)g.gamma | (uintptr_t)g.beta;
-  }
+  blocks_grads_wanted(grads->block, h->cfg.head_depth, &gany);
   if (gany & 3u) return YL_ERR_UNSUPPORTED;            // before the first launch: nothing of the caller's is written
   const yl_status st = ensure(h, batch, size, h->cfg.head_depth, &pl, &bf);
   if (st != YL_OK) return st;
-  if (!h->fValid) return YL_ERR_STATE;
+  if (!h->mem.fValid) return YL_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const int M = pl.rows, F = h->cfg.channels, D = h->cfg.head_depth, S = size, train = h->fTrain;
-  const BlockDims dm = {M, S, F, pl.stat_tiles, pl.wgrad_rows, pl.wgrad_splits};
+  const BlockDims dm = dims_of(pl, S, F);
   int nl = 0;
   const HeadRows hw = head_rows(h->cfg, params, S * S);
   const int NE = hw.g.A * hw.g.E;

@@ -84,13 +84,12 @@ bool cfg_supported(const yl_neck_cfg* c) {
 }  // namespace
 
 struct yl_neck {
-  int device;
+  Arena mem;                             // yl_block.h
   yl_neck_cfg cfg;
-  int64_t saved_cap, work_cap, table_cap;
-  char *saved, *work;
+  int64_t table_cap;
   int* tables;
   int tS[YL_NECK_MAX_LEVELS];            // the sizes the tables on the device were made for (0: none)
-  int fB, fS[YL_NECK_MAX_LEVELS], fTrain, fValid;
+  int fB, fS[YL_NECK_MAX_LEVELS], fTrain;   // the forward whose activations are held (mem.fValid)
 };
 
 extern "C" {
@@ -149,19 +148,13 @@ yl_status yl_neck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* siz
 
 void yl_neck_destroy(yl_neck* h) {
   if (!h) return;
-  hipSetDevice(h->device);
-  hipDeviceSynchronize();
-  hipFree(h->saved); hipFree(h->work); hipFree(h->tables);
-  (void)hipGetLastError();
+  arena_release(h->mem);
+  hipFree(h->tables); (void)hipGetLastError();
   delete h;
 }
 
 yl_status yl_neck_held(const yl_neck* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
-  if (!h) return YL_ERR_INVALID;
-  if (saved_bytes) *saved_bytes = h->saved_cap;
-  if (workspace_bytes) *workspace_bytes = h->work_cap;
-  if (forward_held) *forward_held = h->fValid;
-  return YL_OK;
+  return arena_held(h ? &h->mem : nullptr, saved_bytes, workspace_bytes, forward_held);
 }
 
 yl_status yl_neck_create(int32_t device, const yl_neck_cfg* cfg, yl_neck** out) {
@@ -170,7 +163,7 @@ yl_status yl_neck_create(int32_t device, const yl_neck_cfg* cfg, yl_neck** out) 
   if (hipSetDevice(device) != hipSuccess) return YL_ERR_HIP;
   yl_neck* h = new (std::nothrow) yl_neck();
   if (!h) return YL_ERR_NOMEM;
-  h->device = device; h->cfg = *cfg;
+  h->mem.device = device; h->cfg = *cfg;
   *out = h;
   return YL_OK;
 }
@@ -190,26 +183,12 @@ struct NeckBuffers {
 
 // the handle's memory for (batch, sizes), cut as yl_neck_plan counts it; `save`: every level and block apart
 yl_status ensure(yl_neck* h, int B, const int32_t* sizes, bool save, yl_neck_plan_info* pl, NeckBuffers* nb) {
-  const yl_status st = yl_neck_plan(&h->cfg, B, sizes, pl);
+  yl_status st = yl_neck_plan(&h->cfg, B, sizes, pl);
   if (st != YL_OK) return st;
-  if (hipSetDevice(h->device) != hipSuccess) return YL_ERR_HIP;
+  st = arena_reserve(h->mem, save ? pl->saved_bytes : pl->nosave_bytes, pl->workspace_bytes);
+  if (st != YL_OK) return st;
   const int L = h->cfg.num_levels, D = h->cfg.depth;
   const size_t F = h->cfg.channels;
-  const int64_t need = save ? pl->saved_bytes : pl->nosave_bytes;
-  if (need > h->saved_cap || pl->workspace_bytes > h->work_cap) {   // grow: what is held is dropped
-    if (hipDeviceSynchronize() != hipSuccess) return YL_ERR_HIP;
-    const int64_t sb = need > h->saved_cap ? need : h->saved_cap;
-    const int64_t wb = pl->workspace_bytes > h->work_cap ? pl->workspace_bytes : h->work_cap;
-    hipFree(h->saved); hipFree(h->work);
-    h->saved = h->work = nullptr; h->saved_cap = h->work_cap = 0; h->fValid = 0;
-    if (hipMalloc((void**)&h->saved, (size_t)sb) != hipSuccess || hipMalloc((void**)&h->work, (size_t)wb) != hipSuccess) {
-      hipFree(h->saved); hipFree(h->work);
-      h->saved = h->work = nullptr;
-      (void)hipGetLastError();
-      return YL_ERR_NOMEM;
-    }
-    h->saved_cap = sb; h->work_cap = wb;
-  }
   bool same = true;
   for (int k = 0; k < L; ++k) same = same && h->tS[k] == sizes[k];
   if (!same && L > 1) {                  // new maps: nothing that reads the old ones may still run
@@ -245,26 +224,20 @@ yl_status ensure(yl_neck* h, int B, const int32_t* sizes, bool save, yl_neck_pla
     amax = a > amax ? a : amax;
     smax = sp > smax ? sp : smax;
   }
-  char* w = h->work;
+  char* w = h->mem.work;
   float* ga = (float*)w; w += amax;
   float* gb = (float*)w; w += amax;
   nb->gt = (float*)w; w += amax;
   double* spart = (double*)w; w += smax;
   float* coef = (float*)w; w += 2 * F * 4;
   float* wpart = (float*)w;
-  char* p = h->saved;
+  char* p = h->mem.saved;
   for (int k = 0; k < L; ++k) {
     Buffers& bf = nb->lv[k];
     const size_t act = (size_t)pl->level[k].rows * F * 4;
-    if (!save) p = h->saved;             // every level in the same memory
-    for (int t = 0; t < YL_HEAD_MAX_DEPTH; ++t) bf.d[t] = bf.z[t] = bf.h[t] = bf.stats[t] = nullptr;
+    if (!save) p = h->mem.saved;         // every level in the same memory
     nb->t[k] = (float*)p; p += act;
-    for (int t = 0; t < (save ? D : 1); ++t) {
-      bf.d[t] = (float*)p; p += act;
-      bf.z[t] = (float*)p; p += act;
-      bf.h[t] = (float*)p; p += act;
-    }
-    for (int t = 0; t < (save ? D : 1); ++t) { bf.stats[t] = (float*)p; p += 2 * F * 4; }
+    p = carve_blocks(p, save ? D : 1, act, F, &bf);
     bf.ga = ga; bf.gb = gb; bf.spart = spart; bf.coef = coef; bf.wpart = wpart;
   }
   return YL_OK;
@@ -277,19 +250,9 @@ bool params_ok(const yl_neck_cfg& c, const yl_neck_tensors* t) {
     const yl_neck_level& l = t->level[k];
     if (!l.lat_w || !l.lat_b) return false;
     any |= (uintptr_t)l.lat_w | (uintptr_t)l.lat_b;
-    for (int i = 0; i < c.depth; ++i) {
-      const yl_head_block& b = l.block[i];
-      if (!b.dw || !b.pw || !b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked) return false;
-      any |= (uintptr_t)b.dw | (uintptr_t)b.pw | (uintptr_t)b.gamma | (uintptr_t)b.beta | (uintptr_t)b.running_mean |
-             (uintptr_t)b.running_var;
-      if ((uintptr_t)b.num_batches_tracked & 7u) return false;
-    }
+    if (!blocks_params_ok(l.block, c.depth, &any)) return false;
   }
   return !(any & 3u);
-}
-
-BlockDims dims_of(const yl_neck_level_plan& lp, int S, int F) {
-  return BlockDims{lp.rows, S, F, lp.stat_tiles, lp.wgrad_rows, lp.wgrad_splits};
 }
 
 }  // namespace
@@ -312,7 +275,7 @@ yl_status yl_neck_forward(yl_neck* h, const yl_neck_tensors* params, const float
   if (st != YL_OK) return st;
   hipStream_t s = (hipStream_t)stream;
   int nl = 0;
-  h->fValid = 0;
+  h->mem.fValid = 0;
   for (int k = L - 1; k >= 0; --k) {
     const yl_neck_level& lv = params->level[k];
     const int M = pl.level[k].rows, Cin = h->cfg.in_channels[k], S = sizes[k];
@@ -329,7 +292,7 @@ yl_status yl_neck_forward(yl_neck* h, const yl_neck_tensors* params, const float
   if (launches) *launches = nl;
   if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
   if (save) {
-    h->fB = batch; h->fTrain = train ? 1 : 0; h->fValid = 1;
+    h->fB = batch; h->fTrain = train ? 1 : 0; h->mem.fValid = 1;
     for (int k = 0; k < L; ++k) h->fS[k] = sizes[k];
   }
   return YL_OK;
@@ -347,24 +310,18 @@ yl_status yl_neck_backward(yl_neck* h, const yl_neck_tensors* params, const yl_n
     float* dc = dc_dev ? dc_dev[k] : nullptr;
     if (((uintptr_t)c_dev[k] & 15u) || ((uintptr_t)gp_dev[k] & 15u) || ((uintptr_t)dc & 15u)) return YL_ERR_UNSUPPORTED;
     const yl_neck_level& g = grads->level[k];
-    bool want = g.lat_w || g.lat_b || dc;
     gany |= (uintptr_t)g.lat_w | (uintptr_t)g.lat_b;
-    for (int t = 0; t < D; ++t) {
-      const yl_head_block& b = g.block[t];
-      gany |= (uintptr_t)b.dw | (uintptr_t)b.pw | (uintptr_t)b.gamma | (uintptr_t)b.beta;
-      want = want || b.dw || b.pw || b.gamma || b.beta;
-    }
-    if (want) K = k;
+    if (blocks_grads_wanted(g.block, D, &gany) || g.lat_w || g.lat_b || dc) K = k;
   }
   if (gany & 3u) return YL_ERR_UNSUPPORTED;            // before the first launch: nothing of the caller's is written
-  if (!h->fValid || h->fB != batch) return YL_ERR_STATE;
+  if (!h->mem.fValid || h->fB != batch) return YL_ERR_STATE;
   for (int k = 0; k < L; ++k)
     if (h->fS[k] != sizes[k]) return YL_ERR_STATE;
   yl_neck_plan_info pl;
   NeckBuffers nb;
   const yl_status st = ensure(h, batch, sizes, true, &pl, &nb);
   if (st != YL_OK) return st;
-  if (!h->fValid) return YL_ERR_STATE;
+  if (!h->mem.fValid) return YL_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const bool train = h->fTrain != 0;
   int nl = 0;

@@ -24,6 +24,8 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import _trainmod as tm
+
 
 def plan(fpn_channels: int, num_classes: int, num_anchors: int, head_depth: int, batch: int, size: int,
          num_masks: int = 0) -> Dict[str, int]:
@@ -48,12 +50,7 @@ def _cfg(F, nc, A, depth):
 
 def _make_head(A: int, depth: int, nc: int, F: int) -> nn.ModuleDict:
     """Containers only: the layers hold the parameters under the reference's names; their own forward is never called."""
-    def block():
-        m = nn.Module()
-        m.block = nn.Sequential(nn.Conv2d(F, F, 3, padding=1, groups=F, bias=False), nn.Conv2d(F, F, 1, bias=False),
-                                nn.BatchNorm2d(F), nn.ReLU(inplace=True))
-        return m
-    return nn.ModuleDict({"trunk": nn.Sequential(*[block() for _ in range(depth)]),
+    return nn.ModuleDict({"trunk": nn.Sequential(*[tm.dw_block(F, 1) for _ in range(depth)]),
                           "out": nn.ModuleDict({"box": nn.Conv2d(F, A * 4, 1), "obj": nn.Conv2d(F, A, 1),
                                                 "cls": nn.Conv2d(F, A * nc, 1)})})
 
@@ -65,28 +62,12 @@ def init_detect_bias(head: nn.ModuleDict, num_classes: int, p_obj: float = 0.01)
         head["out"]["box"].bias.zero_()
 
 
-class _Level:
-    """One level's handle and the order its tensors go to the library in"""
+class _Level(tm.DeviceHandle):
+    """One level's handle (see _trainmod.DeviceHandle) and the order its tensors go to the library in"""
 
     def __init__(self, F: int, nc: int, A: int, depth: int):
-        self.F, self.nc, self.A, self.depth = F, nc, A, depth
-        self.handle, self.lib, self.device = None, None, None
-        self.generation = 0
-        self.last_launches = {"forward": 0, "backward": 0}
-
-    def held(self) -> Dict[str, int]:
-        """yl_head_held: bytes the handle holds now and whether a forward is held for backward"""
-        if self.handle is None:
-            return {"saved_bytes": 0, "workspace_bytes": 0, "forward_held": 0}
-        sb, wb, fv = C.c_int64(), C.c_int64(), C.c_int32()
-        _lib.check(self.lib.yl_head_held(self.handle, C.byref(sb), C.byref(wb), C.byref(fv)), what="yl_head_held")
-        return {"saved_bytes": int(sb.value), "workspace_bytes": int(wb.value), "forward_held": int(fv.value)}
-
-    def __deepcopy__(self, memo):                          # a copied module (an EMA) gets a handle of its own
-        return _Level(self.F, self.nc, self.A, self.depth)
-
-    def __reduce__(self):
-        return _Level, (self.F, self.nc, self.A, self.depth)
+        super().__init__("yl_head", _cfg, F, nc, A, depth)
+        self.nc, self.A, self.depth = nc, A, depth
 
     @staticmethod
     def params(head: nn.ModuleDict) -> List[torch.Tensor]:
@@ -106,41 +87,11 @@ class _Level:
     def table(self, tensors: Sequence[Optional[torch.Tensor]], buffers=None):
         """yl_head_tensors from a list in params() order (None = NULL)"""
         t = _lib.yl_head_tensors()
-        ptr = lambda v: v.data_ptr() if v is not None else None       # noqa: E731
         for k in range(self.depth):
-            b = t.block[k]
-            b.dw, b.pw, b.gamma, b.beta = (ptr(v) for v in tensors[4 * k:4 * k + 4])
-            if buffers is not None:
-                b.running_mean, b.running_var, b.num_batches_tracked = (ptr(v) for v in buffers[k])
+            tm.fill_block(t.block[k], tensors[4 * k:4 * k + 4], buffers[k] if buffers is not None else None)
         o = 4 * self.depth
-        t.box_w, t.box_b, t.obj_w, t.obj_b, t.cls_w, t.cls_b = (ptr(v) for v in tensors[o:o + 6])
+        t.box_w, t.box_b, t.obj_w, t.obj_b, t.cls_w, t.cls_b = (tm.ptr(v) for v in tensors[o:o + 6])
         return t
-
-    def ensure(self, device: torch.device):
-        if self.handle is not None and self.device == device:
-            return
-        self.close()
-        self.lib = _lib.load()
-        h = C.c_void_p()
-        cfg = _cfg(self.F, self.nc, self.A, self.depth)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(self.lib.yl_head_create(idx, C.byref(cfg), C.byref(h)), what="yl_head_create")
-        self.handle, self.device = h, device
-
-    def close(self):
-        if self.handle:
-            self.lib.yl_head_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
 class _HeadFunction(torch.autograd.Function):
@@ -149,22 +100,11 @@ class _HeadFunction(torch.autograd.Function):
     @staticmethod
     def forward(fctx, lv: _Level, bufs, train: bool, grad_mode: bool, x, *params):
         B, S = int(x.shape[0]), int(x.shape[1])
-        # needs_input_grad reports requires_grad whatever the grad mode, and inside a Function's forward the mode is
-        # always off: the caller says whether a graph is being recorded.  Without one nothing is saved.
-        save = grad_mode and any(fctx.needs_input_grad)
-        xd = _aligned(x.detach())
-        ps = [p.detach() for p in params]
-        for p in ps:
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != x.device:
-                raise _lib.YoloLiteHipError("DetectHeads: parameters must be contiguous fp32 tensors on the input's device")
+        save = tm.saving(fctx, grad_mode)
+        xd = tm.aligned(x.detach())
+        ps = tm.detached_params("DetectHeads", params, x.device)
         y = torch.empty((B, lv.A, S, S, 5 + lv.nc), device=x.device, dtype=torch.float32)
-        n = C.c_int32()
-        flags = (_lib.YL_HEAD_TRAIN if train else 0) | (_lib.YL_HEAD_SAVE if save else 0)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(lv.lib.yl_head_forward(lv.handle, C.byref(lv.table(ps, bufs)), xd.data_ptr(), B, S, flags,
-                                          y.data_ptr(), stream, C.byref(n)), what="yl_head_forward")
-        lv.generation += 1
-        lv.last_launches["forward"] = int(n.value)
+        lv.launch("forward", x.device, C.byref(lv.table(ps, bufs)), xd.data_ptr(), B, S, tm.flags(train, save), y.data_ptr())
         if save:
             fctx.save_for_backward(xd, *params)
             fctx.lv, fctx.bufs, fctx.generation, fctx.shape = lv, bufs, lv.generation, (B, S)
@@ -174,23 +114,14 @@ class _HeadFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(fctx, gy):
         lv = fctx.lv
-        if fctx.generation != lv.generation:
-            raise _lib.YoloLiteHipError("DetectHeads: this level ran another forward since the one backward() belongs to "
-                                        "(one forward per level is held at a time)")
+        lv.check_generation(fctx.generation, "DetectHeads: this level", "one forward per level")
         xd, *params = fctx.saved_tensors
         B, S = fctx.shape
-        need = fctx.needs_input_grad
         gy = gy.to(dtype=torch.float32).contiguous()
-        grads = [torch.empty_like(p, memory_format=torch.contiguous_format) if need[5 + i] else None
-                 for i, p in enumerate(params)]
-        dx = torch.empty_like(xd) if need[4] else None
-        n = C.c_int32()
-        stream = torch.cuda.current_stream(xd.device).cuda_stream
+        dx, *grads = tm.grads_like([xd, *params], fctx.needs_input_grad[4:])
         ps = [p.detach() for p in params]
-        _lib.check(lv.lib.yl_head_backward(lv.handle, C.byref(lv.table(ps, fctx.bufs)), C.byref(lv.table(grads)),
-                                           xd.data_ptr(), gy.data_ptr(), dx.data_ptr() if dx is not None else None,
-                                           B, S, stream, C.byref(n)), what="yl_head_backward")
-        lv.last_launches["backward"] = int(n.value)
+        lv.launch("backward", xd.device, C.byref(lv.table(ps, fctx.bufs)), C.byref(lv.table(grads)), xd.data_ptr(),
+                  gy.data_ptr(), tm.ptr(dx), B, S)
         return (None, None, None, None, dx) + tuple(grads)
 
 
@@ -225,13 +156,10 @@ class DetectHeads(nn.Module):
     @classmethod
     def from_meta(cls, meta: dict, num_classes: Optional[int] = None) -> "DetectHeads":
         """freshly initialised heads of the model `meta` describes (program.build_program reads the same keys)"""
-        cfg = meta.get("config", {}) or {}
-        mcfg, tcfg = cfg.get("model", {}) or {}, cfg.get("training", {}) or {}
+        F, names, mcfg, _ = tm.meta_fpn(meta)
         if mcfg.get("seg"):
             raise _lib.YoloLiteHipError("mask-coefficient heads (num_masks > 0) are not implemented")
         nc = int(num_classes or meta.get("num_classes") or mcfg.get("num_classes") or 80)
-        F = int(int(mcfg.get("fpn_channels", 128)) * float(mcfg.get("width_multiple", 1.0)))
-        names = (["p2"] if tcfg.get("use_p2") else []) + ["p3", "p4", "p5"] + (["p6"] if tcfg.get("use_p6") else [])
         apl = tuple(meta.get("num_anchors_per_level") or (1, 1, 1))
         if len(apl) >= 3:
             amap = dict(p2=apl[0], p3=apl[0], p4=apl[1], p5=apl[2], p6=apl[2])
@@ -242,14 +170,7 @@ class DetectHeads(nn.Module):
     @classmethod
     def from_state_dict(cls, meta: dict, sd: dict) -> "DetectHeads":
         """the heads of a checkpoint: built from its meta, filled with its `head*.` entries (tensors or numpy arrays)"""
-        m = cls.from_meta(meta)
-        own = m.state_dict()
-        missing = [k for k in own if k not in sd and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError(f"checkpoint lacks head entries: {missing[:4]}")
-        m.load_state_dict({k: torch.as_tensor(sd[k]).reshape(v.shape).to(v.dtype) for k, v in own.items() if k in sd},
-                          strict=False)
-        return m
+        return tm.fill_from_state_dict(cls.from_meta(meta), sd, "head")
 
     def last_launches(self) -> List[Dict[str, int]]:
         """kernels enqueued by the last forward / backward of every level"""
@@ -262,32 +183,8 @@ class DetectHeads(nn.Module):
     def forward(self, feats: Sequence[torch.Tensor], layout: Optional[str] = None) -> List[torch.Tensor]:
         """`layout`: "nchw" ([B,F,S,S], any strides) or "nhwc" ([B,S,S,F]) for every map; None reads it off each map's
         shape and refuses the one shape that is both ([B,F,F,F])."""
-        feats = list(feats)
-        if layout not in (None, "nchw", "nhwc"):
-            raise ValueError(f"layout must be 'nchw', 'nhwc' or None, got {layout!r}")
-        if len(feats) != len(self._levels):
-            raise ValueError(f"expected {len(self._levels)} feature maps, got {len(feats)}")
-        F = self.fpn_channels
-        xs = []
-        for f in feats:                                    # host-side facts first, the device last
-            if not torch.is_tensor(f) or f.dim() != 4:
-                raise ValueError("feature maps must be 4-d tensors [B,F,S,S] or [B,S,S,F]")
-            nchw = f.shape[1] == F and f.shape[2] == f.shape[3]
-            nhwc = f.shape[3] == F and f.shape[1] == f.shape[2]
-            if layout is None and nchw and nhwc:
-                raise ValueError(f"feature map {tuple(f.shape)} reads as [B,{F},S,S] and as [B,S,S,{F}]: "
-                                 "pass layout='nchw' or layout='nhwc'")
-            if not (nchw if layout == "nchw" else nhwc if layout == "nhwc" else nchw or nhwc):
-                want = {None: f"neither [B,{F},S,S] nor [B,S,S,{F}]", "nchw": f"not [B,{F},S,S]", "nhwc": f"not [B,S,S,{F}]"}
-                raise ValueError(f"feature map {tuple(f.shape)} is {want[layout]}")
-            if layout == "nchw" or (layout is None and nchw):
-                f = f.permute(0, 2, 3, 1)                  # NCHW -> an NHWC view (channels-last memory: already contiguous)
-            if not f.is_cuda:
-                raise _lib.YoloLiteHipError("DetectHeads needs its inputs on a HIP device (no CPU fallback)")
-            if self.training and f.shape[0] * f.shape[1] * f.shape[2] == 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input size "
-                                 f"{[int(f.shape[0]), F, 1, 1]}")
-            xs.append(f)
+        feats = tm.check_layout(layout, feats, len(self._levels))
+        xs = [tm.as_nhwc(f, self.fpn_channels, layout, "DetectHeads", self.training) for f in feats]
         outs = []
         for lv, n, f in zip(self._levels, self.level_names, xs):
             head = getattr(self, "head" + n[1:])

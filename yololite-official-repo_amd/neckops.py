@@ -26,6 +26,7 @@ import torch
 from torch import nn
 
 from . import _lib
+from . import _trainmod as tm
 
 
 def _check_dims(in_channels, F, depth):
@@ -86,39 +87,12 @@ def nearest_map(out_size: int, in_size: int) -> Tuple[np.ndarray, np.ndarray, np
     return np.asarray(list(src), np.int64), np.asarray(list(lo), np.int64), np.asarray(list(hi), np.int64)
 
 
-def _dw_block(F: int, n: int) -> nn.Module:
-    """Container only (the reference's DWConvBlock(F, F, n)): the layers hold the parameters; their forward is never called."""
-    m = nn.Module()
-    layers = []
-    for _ in range(n):
-        layers += [nn.Conv2d(F, F, 3, padding=1, groups=F, bias=False), nn.Conv2d(F, F, 1, bias=False),
-                   nn.BatchNorm2d(F), nn.ReLU(inplace=True)]
-    m.block = nn.Sequential(*layers)
-    return m
-
-
-class _Handle:
-    """The neck's handle and the order its tensors go to the library in"""
+class _Handle(tm.DeviceHandle):
+    """The neck's handle (see _trainmod.DeviceHandle) and the order its tensors go to the library in"""
 
     def __init__(self, in_channels, F: int, depth: int):
-        self.in_channels, self.F, self.depth = tuple(in_channels), F, depth
-        self.L = len(self.in_channels)
-        self.handle, self.lib, self.device = None, None, None
-        self.generation = 0
-        self.last_launches = {"forward": 0, "backward": 0}
-
-    def held(self) -> Dict[str, int]:
-        if self.handle is None:
-            return {"saved_bytes": 0, "workspace_bytes": 0, "forward_held": 0}
-        sb, wb, fv = C.c_int64(), C.c_int64(), C.c_int32()
-        _lib.check(self.lib.yl_neck_held(self.handle, C.byref(sb), C.byref(wb), C.byref(fv)), what="yl_neck_held")
-        return {"saved_bytes": int(sb.value), "workspace_bytes": int(wb.value), "forward_held": int(fv.value)}
-
-    def __deepcopy__(self, memo):                          # a copied module (an EMA) gets a handle of its own
-        return _Handle(self.in_channels, self.F, self.depth)
-
-    def __reduce__(self):
-        return _Handle, (self.in_channels, self.F, self.depth)
+        super().__init__("yl_neck", _cfg, tuple(in_channels), F, depth)
+        self.F, self.depth, self.L = F, depth, len(in_channels)
 
     @property
     def per_level(self) -> int:
@@ -127,47 +101,17 @@ class _Handle:
     def table(self, tensors: Sequence[Optional[torch.Tensor]], buffers=None):
         """yl_neck_tensors from a list in DetectNeck._param_list() order (None = NULL)"""
         t = _lib.yl_neck_tensors()
-        ptr = lambda v: v.data_ptr() if v is not None else None       # noqa: E731
         n = self.per_level
         for k in range(self.L):
             lv, ts = t.level[k], tensors[k * n:(k + 1) * n]
-            lv.lat_w, lv.lat_b = ptr(ts[0]), ptr(ts[1])
+            lv.lat_w, lv.lat_b = tm.ptr(ts[0]), tm.ptr(ts[1])
             for i in range(self.depth):
-                b = lv.block[i]
-                b.dw, b.pw, b.gamma, b.beta = (ptr(v) for v in ts[2 + 4 * i:6 + 4 * i])
-                if buffers is not None:
-                    b.running_mean, b.running_var, b.num_batches_tracked = (ptr(v) for v in buffers[k][i])
+                tm.fill_block(lv.block[i], ts[2 + 4 * i:6 + 4 * i], buffers[k][i] if buffers is not None else None)
         return t
-
-    def ensure(self, device: torch.device):
-        if self.handle is not None and self.device == device:
-            return
-        self.close()
-        self.lib = _lib.load()
-        h = C.c_void_p()
-        cfg = _cfg(self.in_channels, self.F, self.depth)
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        _lib.check(self.lib.yl_neck_create(idx, C.byref(cfg), C.byref(h)), what="yl_neck_create")
-        self.handle, self.device = h, device
-
-    def close(self):
-        if self.handle:
-            self.lib.yl_neck_destroy(self.handle)
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _aligned(t: torch.Tensor) -> torch.Tensor:
-    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=torch.contiguous_format)
 
 
 def _ptrs(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None else None for t in ts])
+    return (C.c_void_p * len(ts))(*[tm.ptr(t) for t in ts])
 
 
 class _NeckFunction(torch.autograd.Function):
@@ -179,24 +123,13 @@ class _NeckFunction(torch.autograd.Function):
         cs, params = args[:L], args[L:]
         B = int(cs[0].shape[0])
         sizes = [int(c.shape[1]) for c in cs]
-        # as in DetectHeads: inside a Function's forward the grad mode is always off, so the caller says whether a graph
-        # is being recorded.  Without one nothing is saved.
-        save = grad_mode and any(fctx.needs_input_grad)
-        cd = [_aligned(c.detach()) for c in cs]
-        ps = [p.detach() for p in params]
+        save = tm.saving(fctx, grad_mode)
+        cd = [tm.aligned(c.detach()) for c in cs]
         dev = cs[0].device
-        for p in ps:
-            if p.dtype != torch.float32 or not p.is_contiguous() or p.device != dev:
-                raise _lib.YoloLiteHipError("DetectNeck: parameters must be contiguous fp32 tensors on the input's device")
+        ps = tm.detached_params("DetectNeck", params, dev)
         outs = [torch.empty((B, S, S, hd.F), device=dev, dtype=torch.float32) for S in sizes]
-        n = C.c_int32()
-        flags = (_lib.YL_HEAD_TRAIN if train else 0) | (_lib.YL_HEAD_SAVE if save else 0)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        sz = (C.c_int32 * L)(*sizes)
-        _lib.check(hd.lib.yl_neck_forward(hd.handle, C.byref(hd.table(ps, bufs)), _ptrs(cd), B, sz, flags, _ptrs(outs),
-                                          stream, C.byref(n)), what="yl_neck_forward")
-        hd.generation += 1
-        hd.last_launches["forward"] = int(n.value)
+        hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), _ptrs(cd), B, (C.c_int32 * L)(*sizes), tm.flags(train, save),
+                  _ptrs(outs))
         if save:
             fctx.save_for_backward(*cd, *params)
             fctx.hd, fctx.bufs, fctx.generation, fctx.shape = hd, bufs, hd.generation, (B, sizes)
@@ -206,27 +139,17 @@ class _NeckFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(fctx, *gps):
         hd = fctx.hd
-        if fctx.generation != hd.generation:
-            raise _lib.YoloLiteHipError("DetectNeck: the neck ran another forward since the one backward() belongs to "
-                                        "(one forward is held at a time)")
+        hd.check_generation(fctx.generation, "DetectNeck: the neck", "one forward")
         L = hd.L
         saved = fctx.saved_tensors
         cd, params = saved[:L], saved[L:]
         B, sizes = fctx.shape
-        need = fctx.needs_input_grad[4:]
-        gps = [_aligned(g.to(dtype=torch.float32).contiguous()) for g in gps]
-        dcs = [torch.empty_like(c) if need[k] else None for k, c in enumerate(cd)]
-        grads = [torch.empty_like(p, memory_format=torch.contiguous_format) if need[L + i] else None
-                 for i, p in enumerate(params)]
-        n = C.c_int32()
-        stream = torch.cuda.current_stream(cd[0].device).cuda_stream
+        gps = [tm.aligned(g.to(dtype=torch.float32).contiguous()) for g in gps]
+        grads = tm.grads_like(saved, fctx.needs_input_grad[4:])
         ps = [p.detach() for p in params]
-        sz = (C.c_int32 * L)(*sizes)
-        _lib.check(hd.lib.yl_neck_backward(hd.handle, C.byref(hd.table(ps, fctx.bufs)), C.byref(hd.table(grads)),
-                                           _ptrs(cd), _ptrs(gps), _ptrs(dcs), B, sz, stream, C.byref(n)),
-                   what="yl_neck_backward")
-        hd.last_launches["backward"] = int(n.value)
-        return (None, None, None, None) + tuple(dcs) + tuple(grads)
+        hd.launch("backward", cd[0].device, C.byref(hd.table(ps, fctx.bufs)), C.byref(hd.table(grads[L:])), _ptrs(cd),
+                  _ptrs(gps), _ptrs(grads[:L]), B, (C.c_int32 * L)(*sizes))
+        return (None, None, None, None) + tuple(grads)
 
 
 class DetectNeck(nn.Module):
@@ -244,27 +167,23 @@ class DetectNeck(nn.Module):
         rest = [(n, ci) for n, ci in zip(self.level_names, in_channels) if n != "p2"]
         if "p2" in self.level_names:                       # the reference's order of registration (model_v2.py:286-294)
             self.lateral2 = nn.Conv2d(in_channels[self.level_names.index("p2")], F, 1)
-            self.smooth2 = _dw_block(F, self.depth)
+            self.smooth2 = tm.dw_block(F, self.depth)
         for n, ci in rest:
             setattr(self, "lateral" + n[1:], nn.Conv2d(ci, F, 1))
         for n, ci in rest:
-            setattr(self, "smooth" + n[1:], _dw_block(F, self.depth))
+            setattr(self, "smooth" + n[1:], tm.dw_block(F, self.depth))
         self._handle = _Handle(in_channels, F, self.depth)
 
     @staticmethod
     def _meta_dims(meta: dict):
-        cfg = meta.get("config", {}) or {}
-        mcfg, tcfg = cfg.get("model", {}) or {}, cfg.get("training", {}) or {}
+        F, names, mcfg, tcfg = tm.meta_fpn(meta)
         arch = (meta.get("arch") or mcfg.get("arch") or "YOLOLiteMS").lower()
         if arch != "yololitems_cpu":
             raise _lib.YoloLiteHipError(f"DetectNeck: the dense-3x3 + SiLU smooth blocks of arch {arch!r} are not implemented "
                                         "(only YOLOLiteMS_CPU's depthwise neck is)")
         if tcfg.get("use_p6"):
             raise _lib.YoloLiteHipError("DetectNeck: the P6 path (use_p6) is not implemented")
-        F = int(int(mcfg.get("fpn_channels", 128)) * float(mcfg.get("width_multiple", 1.0)))
-        d = max(1, round(2 * float(mcfg.get("depth_multiple", 1.0))))
-        names = (["p2"] if tcfg.get("use_p2") else []) + ["p3", "p4", "p5"]
-        return F, d, names
+        return F, max(1, round(2 * float(mcfg.get("depth_multiple", 1.0)))), names
 
     @classmethod
     def from_meta(cls, meta: dict) -> "DetectNeck":
@@ -284,14 +203,7 @@ class DetectNeck(nn.Module):
         if missing:
             raise KeyError(f"checkpoint lacks neck entries: {missing[:4]}")
         cin = [int(np.shape(sd[f"lateral{n[1:]}.weight"])[1]) for n in names]
-        m = cls(cin, F, d, level_names=names)
-        own = m.state_dict()
-        missing = [k for k in own if k not in sd and not k.endswith("num_batches_tracked")]
-        if missing:
-            raise KeyError(f"checkpoint lacks neck entries: {missing[:4]}")
-        m.load_state_dict({k: torch.as_tensor(np.asarray(sd[k]) if not torch.is_tensor(sd[k]) else sd[k])
-                           .reshape(v.shape).to(v.dtype) for k, v in own.items() if k in sd}, strict=False)
-        return m
+        return tm.fill_from_state_dict(cls(cin, F, d, level_names=names), sd, "neck")
 
     def _param_list(self) -> List[torch.Tensor]:
         """per level: lateral weight, bias, then per block dw, pw, gamma, beta"""
@@ -323,32 +235,9 @@ class DetectNeck(nn.Module):
         """`feats`: the backbone's maps, finest first, "nchw" ([B,Cin,S,S], any strides) or "nhwc" ([B,S,S,Cin]); None
         reads the layout off each map's shape and refuses a shape that is both.  -> NHWC [B,S,S,F] per level, finest
         first: what DetectHeads(..., layout="nhwc") takes."""
-        feats = list(feats)
-        if layout not in (None, "nchw", "nhwc"):
-            raise ValueError(f"layout must be 'nchw', 'nhwc' or None, got {layout!r}")
-        if len(feats) != len(self.level_names):
-            raise ValueError(f"expected {len(self.level_names)} feature maps, got {len(feats)}")
-        xs = []
-        for f, ci in zip(feats, self.in_channels):         # host-side facts first, the device last
-            if not torch.is_tensor(f) or f.dim() != 4:
-                raise ValueError("feature maps must be 4-d tensors [B,Cin,S,S] or [B,S,S,Cin]")
-            nchw = f.shape[1] == ci and f.shape[2] == f.shape[3]
-            nhwc = f.shape[3] == ci and f.shape[1] == f.shape[2]
-            if layout is None and nchw and nhwc:
-                raise ValueError(f"feature map {tuple(f.shape)} reads as [B,{ci},S,S] and as [B,S,S,{ci}]: "
-                                 "pass layout='nchw' or layout='nhwc'")
-            if not (nchw if layout == "nchw" else nhwc if layout == "nhwc" else nchw or nhwc):
-                want = {None: f"neither [B,{ci},S,S] nor [B,S,S,{ci}]", "nchw": f"not [B,{ci},S,S]",
-                        "nhwc": f"not [B,S,S,{ci}]"}
-                raise ValueError(f"feature map {tuple(f.shape)} is {want[layout]}")
-            if layout == "nchw" or (layout is None and nchw):
-                f = f.permute(0, 2, 3, 1)
-            if not f.is_cuda:
-                raise _lib.YoloLiteHipError("DetectNeck needs its inputs on a HIP device (no CPU fallback)")
-            if self.training and f.shape[0] * f.shape[1] * f.shape[2] == 1:
-                raise ValueError("Expected more than 1 value per channel when training, got input size "
-                                 f"{[int(f.shape[0]), self.fpn_channels, 1, 1]}")
-            xs.append(f)
+        feats = tm.check_layout(layout, feats, len(self.level_names))
+        xs = [tm.as_nhwc(f, ci, layout, "DetectNeck", self.training, name="Cin", bn_channels=self.fpn_channels)
+              for f, ci in zip(feats, self.in_channels)]
         if len({int(f.shape[0]) for f in xs}) != 1 or len({f.device for f in xs}) != 1:
             raise ValueError("the feature maps must share one batch size and one device")
         params = self._param_list()
