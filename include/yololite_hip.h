@@ -777,8 +777,8 @@ yl_status yl_head_held(const yl_head* h, int64_t* saved_bytes, int64_t* workspac
  * and the backward finest first: G_k = gp_k (+ up^T(gt_{k-1}) for k > 0), the blocks back to gt_k = dL/dt_k, then
  * dWlat_k = gt_k^T . c_k, dblat_k = colsum gt_k, dc_k = gt_k . Wlat_k.
  * Parameters are read in PyTorch layout from the caller's tensors on every call, at any 4-byte boundary; c / p / gp / dc
- * are NHWC fp32, 16-byte aligned.  channels % 4 != 0 or in_channels[k] % 4 != 0: YL_ERR_UNSUPPORTED.  The P6 path and
- * the dense-3x3 + SiLU smooth blocks of YOLOLiteMS are not implemented.  YL_HEAD_TRAIN / YL_HEAD_SAVE mean what they
+ * are NHWC fp32, 16-byte aligned.  channels % 4 != 0 or in_channels[k] % 4 != 0: YL_ERR_UNSUPPORTED.  The P6 path is not
+ * implemented; the dense-3x3 + SiLU smooth blocks of YOLOLiteMS are yl_dneck_* below.  YL_HEAD_TRAIN / YL_HEAD_SAVE mean what they
  * mean for the heads; with YL_HEAD_SAVE the handle keeps, per level, t_k and every block's d, z, h and statistics
  * (the last block's h is a copy of p_k: the caller's tensor may change before the backward), without it every level
  * runs in one level's buffers.  Deterministic in the way of the heads: per-tile partials summed in tile order in
@@ -845,6 +845,88 @@ yl_status yl_neck_backward(yl_neck* h, const yl_neck_tensors* params, const yl_n
                            const float* const* c_dev, const float* const* gp_dev, float* const* dc_dev, int32_t batch,
                            const int32_t* sizes, void* stream, int32_t* launches);
 yl_status yl_neck_held(const yl_neck* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+
+/* ---- trainable dense FPN neck (reference scripts/model/model_v2.py:15-22 conv_block, :115-127, :194-203, YOLOLiteMS) ----
+ * The neck above with the smooth blocks of arch YOLOLiteMS: block = dense 3x3 convolution (pad 1, stride 1, no bias,
+ * weight [F][F][3][3]) -> BatchNorm2d -> SiLU.  Laterals, top-down chain, nearest maps (yl_neck_nearest_map), the
+ * configuration (yl_neck_cfg, the same refusals), flags, layouts, alignment rules, BatchNorm numerics and the
+ * determinism argument are those of yl_neck_*; the P6 path is not implemented.
+ * The convolution is an implicit GEMM on v_mfma_f32_16x16x4_f32: a workgroup owns an 8 x 8 spatial tile of ONE image
+ * times 64 output channels, stages the tile's 10 x 10 input window (zero outside the image) in LDS once per block of 16
+ * input channels, and all nine taps read it there as shifted windows.  The weights are read from the caller's tensor on
+ * every call and copied by a pack kernel into the handle's workspace as [tap][out][in] (forward) or, for the input
+ * gradient, [8 - tap][in][out]: the input gradient is the same convolution kernel on dz.  The weight gradient cuts the
+ * level's spatial tiles into w3grad_splits runs of w3grad_tiles tiles; a workgroup (64 in x 64 out channels, one run)
+ * stages each tile's x window and dz tile once for all nine taps and writes fp32 partials [split][tap][out][in]; a
+ * second kernel sums them in split order in float64 into [F][F][3][3].
+ * With YL_HEAD_SAVE the handle keeps, per level, t_k and per block z, h and (mean, invstd): the block's input is t_k
+ * or the previous h. */
+typedef struct yl_dneck yl_dneck;
+typedef struct yl_dneck_block {     /* smooth{k}.{3i} (w), smooth{k}.{3i+1} (BatchNorm) */
+  float* w;                         /* [F][F][3][3] */
+  float* gamma;                     /* [F] BatchNorm weight */
+  float* beta;                      /* [F] BatchNorm bias */
+  float* running_mean;              /* [F] (ignored in a gradient table) */
+  float* running_var;               /* [F] (ignored in a gradient table) */
+  int64_t* num_batches_tracked;     /* one int64, 8-byte aligned (ignored in a gradient table) */
+} yl_dneck_block;
+typedef struct yl_dneck_level {
+  float* lat_w;                               /* lateral{k}.weight [F][Cin][1][1] */
+  float* lat_b;                               /* lateral{k}.bias [F] */
+  yl_dneck_block block[YL_NECK_MAX_DEPTH];
+} yl_dneck_level;
+typedef struct yl_dneck_tensors {             /* the parameters, or where their gradients go (NULL = not wanted) */
+  yl_dneck_level level[YL_NECK_MAX_LEVELS];
+} yl_dneck_tensors;
+typedef struct yl_dneck_level_plan {
+  int32_t rows;                               /* M_k = batch * S_k * S_k */
+  int32_t stat_tiles, gemm_tiles;             /* tiles of stat_rows / gemm_rows rows */
+  int32_t conv_tiles;                         /* batch * ceil(S_k / conv_tile)^2 spatial tiles, image-major then row-major */
+  int32_t lgrad_rows, lgrad_splits;           /* gt^T . c of the lateral (Cin x F): rows per split, splits */
+  int32_t w3grad_tiles, w3grad_splits;        /* the 3x3 weight gradient: spatial tiles per split, splits;
+                                                 splits = ceil(conv_tiles / w3grad_tiles), w3grad_tiles =
+                                                 ceil(conv_tiles / min(conv_tiles, 64, max(1, 512 / ceil(F / 64)^2))) */
+  int64_t saved_bytes;                        /* (1 + 2 depth) M_k F 4 + depth 2 F 4: t_k; z, h and statistics per block */
+} yl_dneck_level_plan;
+typedef struct yl_dneck_plan_info {
+  int32_t stat_rows, gemm_rows;
+  int32_t conv_tile;                          /* edge of a spatial tile (8) */
+  int32_t reserved0;
+  yl_dneck_level_plan level[YL_NECK_MAX_LEVELS];
+  int64_t saved_bytes;                        /* sum of the levels' saved_bytes (YL_HEAD_SAVE) */
+  int64_t nosave_bytes;                       /* without YL_HEAD_SAVE: 3 Mmax F 4 + 2 F 4, t and ONE block of the largest level */
+  int64_t workspace_bytes;                    /* 3 Mmax F 4 (two gradients in flight and gt)
+                                                 + round16(max_k(stat_tiles_k) 2 F 8)  the float64 column partials
+                                                 + 2 F 4                               the BatchNorm backward's coefficients
+                                                 + 9 F F 4                             one packed 3x3 weight
+                                                 + max_k round16(max(w3grad_splits_k 9 F F, lgrad_splits_k F Cin_k) 4) */
+  int64_t table_bytes;                        /* the nearest maps: per k < L - 1, (S_k + 2 S_{k+1}) int32 */
+} yl_dneck_plan_info;
+/* A pure host function.  Row tile t covers the rows [t * rows_per_tile, min(M, (t + 1) * rows_per_tile)); split z of
+ * the 3x3 weight gradient covers the spatial tiles [z * w3grad_tiles, min(conv_tiles, (z + 1) * w3grad_tiles)). */
+yl_status yl_dneck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* sizes, yl_dneck_plan_info* out);
+yl_status yl_dneck_create(int32_t device, const yl_neck_cfg* cfg, yl_dneck** out);
+void yl_dneck_destroy(yl_dneck* h);
+/* Enqueues the forward: per level 1 launch for the lateral (bias and upsample-add in its epilogue) and per block 4
+ * launches (weight pack, convolution, BatchNorm statistics, BatchNorm + SiLU; 5 with YL_HEAD_TRAIN: the column sums);
+ * with YL_HEAD_SAVE one device-to-device copy per level besides (not counted).  Arguments, refusals and the growth of
+ * the buffers as in yl_neck_forward. */
+yl_status yl_dneck_forward(yl_dneck* h, const yl_dneck_tensors* params, const float* const* c_dev, int32_t batch,
+                           const int32_t* sizes, uint32_t flags, float* const* p_dev, void* stream, int32_t* launches);
+/* Enqueues the backward of the held forward (YL_ERR_STATE if there is none of this batch and these sizes).  Every
+ * non-NULL tensor of `grads` and every non-NULL dc_dev[k] is OVERWRITTEN.  What nobody asked for is not run.  Level k
+ * is walked only if something of a level >= k is wanted (a parameter or dc), finest first up to the coarsest such
+ * level K:
+ *   1 launch for G_k when k > 0 (the gather of gt_{k-1} plus gp_k);
+ *   the blocks, last first, back to the first thing wanted: per block [1 sums if train or gamma / beta wanted]
+ *     + 1 (bn grads) + 1 (dz) + [2 if w wanted: partials, ordered sum] + [2 input gradient: weight pack, convolution];
+ *     the input gradient of block 0 runs only if gt_k is needed, which it is when something of the lateral k, dc_k or
+ *     a level > k is wanted;
+ *   2 launches for dWlat_k, 2 for dblat_k, 1 for dc_k, each only where wanted. */
+yl_status yl_dneck_backward(yl_dneck* h, const yl_dneck_tensors* params, const yl_dneck_tensors* grads,
+                            const float* const* c_dev, const float* const* gp_dev, float* const* dc_dev, int32_t batch,
+                            const int32_t* sizes, void* stream, int32_t* launches);
+yl_status yl_dneck_held(const yl_dneck* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
 
 #ifdef __cplusplus
 }

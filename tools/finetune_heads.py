@@ -17,10 +17,11 @@ they start from the checkpoint.  --synthetic NAME takes a zoo model with seeded 
 instead of --weights / --data.  The output is a checkpoint {"state_dict", "meta"}: the input's state_dict with the
 `head*.` entries replaced, meta.num_classes / names updated -- tools/infer.py runs it.
 
-With --train-neck (YOLOLiteMS_CPU models without P6) the FPN neck is trained as well: the executor stops being the
-pyramid's source and gives the backbone's feature maps (YOLOLiteHIP.features); DetectNeck (csrc/yl_neck.hip) starts
-from the checkpoint's `lateral*.` / `smooth*.` entries, its parameters join the heads' in the one FusedTrainStep, and
-its state_dict is merged into the output as well.
+With --train-neck (models without P6) the FPN neck is trained as well: the executor stops being the pyramid's source and
+gives the backbone's feature maps (YOLOLiteHIP.features); neckops.neck_for picks the neck of the model's arch --
+DetectNeck (csrc/yl_neck.hip) for YOLOLiteMS_CPU, DetectNeckMS (csrc/yl_dneck.hip, dense 3x3 + SiLU) for YOLOLiteMS,
+e.g. --synthetic yololite_n -- which starts from the checkpoint's `lateral*.` / `smooth*.` entries; its parameters join
+the heads' in the one FusedTrainStep, and its state_dict is merged into the output as well.
 """
 import argparse
 import copy
@@ -131,7 +132,7 @@ def main():
         heads = ya.DetectHeads.from_meta(meta, num_classes=nc)
         print(f"[finetune_heads] {old_nc} -> {nc} classes: heads freshly initialised")
     heads.to(a.device).train()
-    neck = ya.DetectNeck.from_state_dict(meta, sd).to(a.device).train() if a.train_neck else None
+    neck = ya.neck_for(meta, sd).to(a.device).train() if a.train_neck else None
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
     fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp=False, lr=a.lr)

@@ -181,6 +181,30 @@ class yl_neck_plan_info(C.Structure):
                 ("table_bytes", C.c_int64)]
 
 
+class yl_dneck_block(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked")]
+
+
+class yl_dneck_level(C.Structure):
+    _fields_ = [("lat_w", C.c_void_p), ("lat_b", C.c_void_p), ("block", yl_dneck_block * YL_NECK_MAX_DEPTH)]
+
+
+class yl_dneck_tensors(C.Structure):
+    _fields_ = [("level", yl_dneck_level * YL_NECK_MAX_LEVELS)]
+
+
+class yl_dneck_level_plan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("rows", "stat_tiles", "gemm_tiles", "conv_tiles", "lgrad_rows", "lgrad_splits",
+                                         "w3grad_tiles", "w3grad_splits")] + [("saved_bytes", C.c_int64)]
+
+
+class yl_dneck_plan_info(C.Structure):
+    _fields_ = [("stat_rows", C.c_int32), ("gemm_rows", C.c_int32), ("conv_tile", C.c_int32), ("reserved0", C.c_int32),
+                ("level", yl_dneck_level_plan * YL_NECK_MAX_LEVELS),
+                ("saved_bytes", C.c_int64), ("nosave_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+                ("table_bytes", C.c_int64)]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -256,6 +280,13 @@ SYMBOLS = [
     ("yl_neck_backward", C.c_int32, [_vp, C.POINTER(yl_neck_tensors), C.POINTER(yl_neck_tensors), _vpp, _vpp, _vpp,
                                      C.c_int32, _ip, _vp, _ip]),
     ("yl_neck_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("yl_dneck_plan", C.c_int32, [C.POINTER(yl_neck_cfg), C.c_int32, _ip, C.POINTER(yl_dneck_plan_info)]),
+    ("yl_dneck_create", C.c_int32, [C.c_int32, C.POINTER(yl_neck_cfg), C.POINTER(_vp)]),
+    ("yl_dneck_destroy", None, [_vp]),
+    ("yl_dneck_forward", C.c_int32, [_vp, C.POINTER(yl_dneck_tensors), _vpp, C.c_int32, _ip, C.c_uint32, _vpp, _vp, _ip]),
+    ("yl_dneck_backward", C.c_int32, [_vp, C.POINTER(yl_dneck_tensors), C.POINTER(yl_dneck_tensors), _vpp, _vpp, _vpp,
+                                      C.c_int32, _ip, _vp, _ip]),
+    ("yl_dneck_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
 ]
 
 _lib = None

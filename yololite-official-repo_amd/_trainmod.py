@@ -1,4 +1,4 @@
-"""What the trainable modules on the device share (headops.DetectHeads, neckops.DetectNeck): the handle of one library
+"""What the trainable modules on the device share (headops.DetectHeads, neckops.DetectNeck / DetectNeckMS): the handle of one library
 object, the depthwise block's container and its entry in the library's tables, the reading of feature maps, checkpoints
 and meta, and the parts of an autograd.Function that do not depend on the module.
 
@@ -17,7 +17,7 @@ from . import _lib
 
 
 class DeviceHandle:
-    """A `<prefix>_create`d library object (prefix "yl_head", "yl_neck") of the config `cfg(*args)`, made on first use
+    """A `<prefix>_create`d library object (prefix "yl_head", "yl_neck", "yl_dneck") of the config `cfg(*args)`, made on first use
     and again when the device changes.  A subclass adds table(): the order its tensors go to the library in."""
 
     def __init__(self, prefix: str, cfg, *args):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-sixteen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+seventeen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
 library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
@@ -52,8 +52,10 @@ UNITS = [   # (source, extra flags, object name)
     ("yl_head.hip", ["-ffp-contract=off"], "yl_head.o"),
     # trainable FPN neck: the heads' block (yl_block.h), the laterals and the top-down chain, forward and backward
     ("yl_neck.hip", ["-ffp-contract=off"], "yl_neck.o"),
+    # trainable dense FPN neck (YOLOLiteMS): dense 3x3 convolution with all three passes, BatchNorm + SiLU; the chain is yl_fpn.h
+    ("yl_dneck.hip", ["-ffp-contract=off"], "yl_dneck.o"),
 ]
-DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", os.path.join("..", "..", "include", "yololite_hip.h")]
+DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 
 
 def _hipcc():

@@ -1,0 +1,596 @@
+// Trainable dense FPN neck (reference scripts/model/model_v2.py:15-22 conv_block, :115-127 lateral* / smooth*, :194-203 the
+// top-down chain of YOLOLiteMS): forward and backward of all levels on NHWC fp32 rows, M_k = B * S_k * S_k rows per level.
+//
+//   block:    z = conv3x3(x, W)   h = silu(y),  y = gamma * (z - mean) * invstd + beta        (z, h are kept for backward)
+//   backward: g = dh * s(y) * (1 + y * (1 - s(y))), s = sigmoid, y recomputed from z and the statistics; then the
+//             BatchNorm backward of yl_block.h with g in place of the ReLU-masked gradient; dW = sum_m dz (x) x(m + tap);
+//             dx = conv3x3(dz, W transposed in (n, c), taps flipped)
+//
+// Everything around the blocks (laterals, upsample-add and its transpose, lateral gradients, nearest maps) is yl_fpn.h,
+// shared with yl_neck.hip.  The forward column statistics, yl_head_bn_stats_kernel and yl_head_bn_grads_kernel are those
+// of yl_block.h.  New here: the convolution (one kernel for forward and input gradient), its weight pack, its weight
+// gradient (partials + ordered float64 sum) and the three SiLU forms of the BatchNorm kernels.
+//
+// Convolution, implicit GEMM in the orientation of yl_head_gemm_kernel (weights: MFMA A operand, pixels: B operand, a lane
+// ends with four consecutive output channels of one pixel).  Workgroup (spatial tile of CT x CT pixels of ONE image, block
+// of CNB output channels); wave w owns tile rows 2w, 2w + 1.  Per k-block of CKB input channels the tile's (CT + 2)^2
+// window is staged in LDS, CXS floats per pixel (CKB + 4: a lane's float4 of pixel i and of pixel i + 2 fall in
+// different banks); a window pixel outside the image is written as zero, so no tap ever reads another image's rows or
+// the previous row's last column.  Two LDS buffers: the next k-block's window is loaded into registers before the taps
+// of this one are computed and written afterwards; one barrier per k-block.
+#include "yl_fpn.h"
+
+namespace {
+
+constexpr int CT = 8, CW = CT + 2;       // spatial tile edge; window edge
+constexpr int CKB = 16, CXS = CKB + 4;   // input channels per k-block; LDS floats per window pixel
+constexpr int CNB = 64;                  // output channels per workgroup: four 16-wide MFMA tiles
+constexpr int CWIN = CW * CW;
+constexpr int GB = 64, GXS = GB + 4;     // weight gradient: channels per block edge; LDS floats per pixel
+
+// w [F][F][3][3] (PyTorch: out, in, ky, kx) -> wp [tap][a][b]: T == 0: W[a][b][tap] (a = out, b = in);
+// T == 1: W[b][a][8 - tap] (a = in, b = out), the weight of the transposed convolution
+__global__ __launch_bounds__(NT) void yl_dneck_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int F, int T) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  const long FF = (long)F * F;
+  if (idx >= 9 * FF) return;
+  const int tap = (int)(idx / FF);
+  const long ab = idx - tap * FF;
+  const int a = (int)(ab / F), b = (int)(ab - (long)a * F);
+  wp[idx] = T ? w[((long)b * F + a) * 9 + (8 - tap)] : w[((long)a * F + b) * 9 + tap];
+}
+
+// out[b, i, j, n] = sum over taps (ky, kx) and c of wp[tap][n][c] * x[b, i + ky - 1, j + kx - 1, c], zero outside the image.
+// grid (B * TX * TX, ceil(F / CNB)); TX = ceil(S / CT)
+__global__ __launch_bounds__(NT) void yl_dneck_conv_kernel(const float* __restrict__ x, const float* __restrict__ wp,
+                                                          float* __restrict__ out, int S, int F, int TX) {
+  __shared__ float win[2][CWIN * CXS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, kq = lane >> 4, i = lane & 15;
+  const int b = blockIdx.x / (TX * TX), tr = blockIdx.x - b * TX * TX, ty0 = (tr / TX) * CT, tx0 = (tr % TX) * CT;
+  const int n0 = blockIdx.y * CNB;
+  // staging: item = window pixel * 4 + channel quad; this thread's items are t and t + NT
+  long soff[2]; bool sok[2]; int sq[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    const int item = t + r * NT, pw = item >> 2;
+    sq[r] = (item & 3) * 4;
+    const int gy = ty0 - 1 + pw / CW, gx = tx0 - 1 + pw % CW;
+    sok[r] = item < CWIN * 4 && gy >= 0 && gy < S && gx >= 0 && gx < S;
+    soff[r] = sok[r] ? (((long)b * S + gy) * S + gx) * F + sq[r] : 0;
+  }
+  const int row = 2 * wave + (i >> 3), col = i & 7;
+  const int nkb = (F + CKB - 1) / CKB;
+  f32x4 acc[4], sv[2];
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt) acc[pt] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    sv[r] = (sok[r] && sq[r] < F) ? ld4(x + soff[r] + 0) : zero;
+    if (t + r * NT < CWIN * 4) st4(&win[0][((t + r * NT) >> 2) * CXS + sq[r]], sv[r]);
+  }
+  __syncthreads();
+  for (int kb = 0; kb < nkb; ++kb) {
+    const int c0 = kb * CKB;
+    const bool more = kb + 1 < nkb;
+    if (more) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r) sv[r] = (sok[r] && c0 + CKB + sq[r] < F) ? ld4(x + soff[r] + c0 + CKB) : zero;
+    }
+    const float* wb = win[kb & 1];
+    const int c = c0 + 4 * kq;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap) {
+      const int ky = tap / 3, kx = tap - 3 * ky;
+      const f32x4 qv = ld4(wb + ((row + ky) * CW + col + kx) * CXS + 4 * kq);
+      f32x4 pv[4];
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt) {
+        const int n = n0 + 16 * pt + i;
+        pv[pt] = (n < F && c < F) ? ld4(wp + ((long)tap * F + n) * F + c) : zero;
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt) acc[pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[pt], 0, 0, 0);
+    }
+    if (more) {
+#pragma unroll
+      for (int r = 0; r < 2; ++r)
+        if (t + r * NT < CWIN * 4) st4(&win[(kb + 1) & 1][((t + r * NT) >> 2) * CXS + sq[r]], sv[r]);
+    }
+    __syncthreads();
+  }
+  const int gy = ty0 + row, gx = tx0 + col;
+  if (gy < S && gx < S) {
+    float* o = out + (((long)b * S + gy) * S + gx) * F;
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+      const int n = n0 + 16 * pt + 4 * kq;
+      if (n < F) st4(o + n, acc[pt]);
+    }
+  }
+}
+
+// Weight-gradient partials: part[split][tap][n][c] = sum over the split's spatial tiles and their pixels m of
+// dz[m][n] * x[m + tap][c].  grid (ceil(F / GB) c blocks, ceil(F / GB) n blocks, splits); wave w owns n0 + 16 w .. + 15.
+// Per tile the x window (zero outside the image) and the dz tile (zero outside the image) are staged once and all nine
+// taps read them: 9 x 4 accumulators per lane.  The MFMA's k index is the pixel: pixel 16 step + 4 kq + s of the tile.
+__global__ __launch_bounds__(NT) void yl_dneck_wgrad_kernel(const float* __restrict__ x, const float* __restrict__ dz,
+                                                           float* __restrict__ part, int S, int F, int TX, int ntiles,
+                                                           int tiles_per_split) {
+  __shared__ float xw[CWIN * GXS];
+  __shared__ float dzt[CT * CT * GXS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, kq = lane >> 4, i = lane & 15;
+  const int c0 = blockIdx.x * GB, n0 = blockIdx.y * GB;
+  const int tbeg = blockIdx.z * tiles_per_split;
+  const int tend = tbeg + tiles_per_split < ntiles ? tbeg + tiles_per_split : ntiles;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[9][4];
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) acc[tap][pt] = zero;
+  for (int tile = tbeg; tile < tend; ++tile) {
+    const int b = tile / (TX * TX), tr = tile - b * TX * TX, ty0 = (tr / TX) * CT, tx0 = (tr % TX) * CT;
+    __syncthreads();                     // the previous tile's reads are done
+    for (int item = t; item < CWIN * (GB / 4); item += NT) {
+      const int pw = item / (GB / 4), q = (item - pw * (GB / 4)) * 4;
+      const int gy = ty0 - 1 + pw / CW, gx = tx0 - 1 + pw % CW;
+      const bool ok = gy >= 0 && gy < S && gx >= 0 && gx < S && c0 + q < F;
+      st4(&xw[pw * GXS + q], ok ? ld4(x + (((long)b * S + gy) * S + gx) * F + c0 + q) : zero);
+    }
+    for (int item = t; item < CT * CT * (GB / 4); item += NT) {
+      const int pk = item / (GB / 4), q = (item - pk * (GB / 4)) * 4;
+      const int gy = ty0 + (pk >> 3), gx = tx0 + (pk & 7);
+      const bool ok = gy < S && gx < S && n0 + q < F;
+      st4(&dzt[pk * GXS + q], ok ? ld4(dz + (((long)b * S + gy) * S + gx) * F + n0 + q) : zero);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int step = 0; step < 4; ++step) {
+      const int prow = 2 * step + (kq >> 1), pcol = 4 * (kq & 1);   // pixel 16 step + 4 kq + s: (prow, pcol + s)
+      float qv[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qv[s] = dzt[(prow * CT + pcol + s) * GXS + 16 * wave + i];
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap - 3 * ky;
+        const float* xb = xw + ((prow + ky) * CW + pcol + kx) * GXS + i;
+#pragma unroll
+        for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+            acc[tap][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[s * GXS + 16 * pt], qv[s], acc[tap][pt], 0, 0, 0);
+      }
+    }
+  }
+  const int n = n0 + 16 * wave + i;
+  if (n >= F) return;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+      const int c = c0 + 16 * pt + 4 * kq;
+      if (c < F) st4(part + (((long)blockIdx.z * 9 + tap) * F + n) * F + c, acc[tap][pt]);
+    }
+}
+
+// the partials summed in split order in float64 -> dW in PyTorch layout [F][F][3][3]; one thread per element
+__global__ __launch_bounds__(NT) void yl_dneck_wsum_kernel(const float* __restrict__ part, int splits, int F, float* __restrict__ out) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  const long FF = (long)F * F;
+  if (idx >= 9 * FF) return;
+  const long nc = idx / 9;
+  const int tap = (int)(idx - nc * 9);
+  double s = 0;
+  for (int z = 0; z < splits; ++z) s += (double)part[((long)z * 9 + tap) * FF + nc];
+  out[idx] = (float)s;
+}
+
+// ---- BatchNorm + SiLU.  y and the factor of the backward are computed in fp32 by these two functions everywhere
+__device__ __forceinline__ float bn_y(float z, float mu, float is, float gamma, float beta) { return (z - mu) * is * gamma + beta; }
+__device__ __forceinline__ float silu_dfactor(float y) {        // d silu / dy = s * (1 + y * (1 - s))
+  const float sg = 1.f / (1.f + expf(-y));
+  return sg * (1.f + y * (1.f - sg));
+}
+
+__global__ __launch_bounds__(NT) void yl_dneck_bn_silu_kernel(const float* __restrict__ z, const float* __restrict__ stats,
+                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                             float* __restrict__ h, long n4, int F) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= n4) return;
+  const int c = (int)((idx * 4) % F);
+  const f32x4 v = ld4(z + idx * 4), mu = ld4(stats + c), is = ld4(stats + F + c);
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float y = bn_y(v[e], mu[e], is[e], gamma[c + e], beta[c + e]);
+    o[e] = y / (1.f + expf(-y));
+  }
+  st4(h + idx * 4, o);
+}
+
+// the backward column sums in the tiling of yl_head_colstats_kernel: part[tile][0][c] = sum g, part[tile][1][c] = sum g * xhat
+struct SiluStatP {
+  const float *dh, *z, *stats, *gamma, *beta;
+  double* part;
+  int M, F, CQ;
+};
+__global__ __launch_bounds__(NT) void yl_dneck_colstats_silu_kernel(SiluStatP P) {
+  __shared__ double red[NT][8];
+  const int t = threadIdx.x, cq = t & (P.CQ - 1), rs = t / P.CQ, RS = NT / P.CQ;
+  const int c = (blockIdx.y * P.CQ + cq) * 4, F = P.F;
+  const bool on = c < F;
+  const int m0 = blockIdx.x * STAT_ROWS, m1 = m0 + STAT_ROWS < P.M ? m0 + STAT_ROWS : P.M;
+  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
+  if (on) {
+    const f32x4 mu = ld4(P.stats + c), is = ld4(P.stats + F + c);
+    float ga[4], be[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { ga[e] = P.gamma[c + e]; be[e] = P.beta[c + e]; }
+    for (int m = m0 + rs; m < m1; m += RS) {
+      const long o = (long)m * F + c;
+      const f32x4 a = ld4(P.dh + o), zv = ld4(P.z + o);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double g = (double)(a[e] * silu_dfactor(bn_y(zv[e], mu[e], is[e], ga[e], be[e])));
+        const double xh = ((double)zv[e] - (double)mu[e]) * (double)is[e];
+        s0[e] += g; s1[e] += g * xh;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { red[t][e] = s0[e]; red[t][4 + e] = s1[e]; }
+  __syncthreads();
+  if (rs == 0 && on) {
+    for (int k = 1; k < RS; ++k)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) red[t][e] += red[k * P.CQ + cq][e];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      P.part[((long)blockIdx.x * 2 + 0) * F + c + e] = red[t][e];
+      P.part[((long)blockIdx.x * 2 + 1) * F + c + e] = red[t][4 + e];
+    }
+  }
+}
+
+// dz = gamma * invstd * (g - c0 - xhat * c1); dh and dz may be one buffer (each thread reads its four values first)
+__global__ __launch_bounds__(NT) void yl_dneck_bn_silu_bwd_kernel(const float* dh, const float* __restrict__ z,
+                                                                 const float* __restrict__ stats, const float* __restrict__ coef,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                 float* dz, long n4, int F) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= n4) return;
+  const int c = (int)((idx * 4) % F);
+  const f32x4 g = ld4(dh + idx * 4), zv = ld4(z + idx * 4);
+  const f32x4 mu = ld4(stats + c), is = ld4(stats + F + c), c0 = ld4(coef + c), c1 = ld4(coef + F + c);
+  f32x4 o;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float ge = g[e] * silu_dfactor(bn_y(zv[e], mu[e], is[e], gamma[c + e], beta[c + e]));
+    const float xh = (zv[e] - mu[e]) * is[e];
+    o[e] = gamma[c + e] * is[e] * (ge - c0[e] - xh * c1[e]);
+  }
+  st4(dz + idx * 4, o);
+}
+
+int64_t round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+}  // namespace
+
+struct yl_dneck {
+  Arena mem;                             // yl_block.h
+  yl_neck_cfg cfg;
+  MapTables maps;                        // yl_fpn.h
+  int fB, fS[YL_NECK_MAX_LEVELS], fTrain;   // the forward whose activations are held (mem.fValid)
+};
+
+extern "C" {
+
+yl_status yl_dneck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* sizes, yl_dneck_plan_info* out) {
+  if (!cfg_ok(cfg) || !out || !sizes || batch < 1) return YL_ERR_INVALID;
+  for (int k = 0; k < cfg->num_levels; ++k)
+    if (sizes[k] < 1) return YL_ERR_INVALID;
+  if (!cfg_supported(cfg)) return YL_ERR_UNSUPPORTED;
+  memset(out, 0, sizeof(*out));
+  out->stat_rows = STAT_ROWS; out->gemm_rows = GEMM_ROWS; out->conv_tile = CT;
+  const int64_t F = cfg->channels;
+  const int64_t blocks = (int64_t)ceil_div(F, GB) * ceil_div(F, GB);
+  int64_t Mmax = 0, smax = 0, wmax = 0;
+  for (int k = 0; k < cfg->num_levels; ++k) {
+    const int64_t M = (int64_t)batch * sizes[k] * sizes[k], Cin = cfg->in_channels[k];
+    if (!level_rows_ok(M, F, Cin)) return YL_ERR_UNSUPPORTED;
+    yl_dneck_level_plan& lp = out->level[k];
+    lp.rows = (int32_t)M;
+    lp.stat_tiles = ceil_div(M, STAT_ROWS); lp.gemm_tiles = ceil_div(M, GEMM_ROWS);
+    const int64_t TX = ceil_div(sizes[k], CT), tiles = (int64_t)batch * TX * TX;
+    lp.conv_tiles = (int32_t)tiles;
+    split_plan((int)M, (int)Cin, (int)F, &lp.lgrad_rows, &lp.lgrad_splits);
+    int64_t want = 512 / blocks;         // about 512 workgroups; the partials are 9 F F floats per split
+    want = want < 1 ? 1 : (want > 64 ? 64 : want);
+    want = want < tiles ? want : tiles;
+    lp.w3grad_tiles = ceil_div(tiles, want);
+    lp.w3grad_splits = ceil_div(tiles, lp.w3grad_tiles);
+    lp.saved_bytes = (1 + 2 * (int64_t)cfg->depth) * M * F * 4 + cfg->depth * 2 * F * 4;
+    out->saved_bytes += lp.saved_bytes;
+    Mmax = M > Mmax ? M : Mmax;
+    const int64_t sp = round16((int64_t)lp.stat_tiles * 2 * F * 8);
+    smax = sp > smax ? sp : smax;
+    const int64_t w3 = (int64_t)lp.w3grad_splits * 9 * F * F * 4, lpb = (int64_t)lp.lgrad_splits * F * Cin * 4;
+    const int64_t wp = round16(w3 > lpb ? w3 : lpb);
+    wmax = wp > wmax ? wp : wmax;
+  }
+  out->table_bytes = map_table_bytes(cfg->num_levels, sizes);
+  out->nosave_bytes = 3 * Mmax * F * 4 + 2 * F * 4;
+  out->workspace_bytes = 3 * Mmax * F * 4 + smax + 2 * F * 4 + 9 * F * F * 4 + wmax;
+  return YL_OK;
+}
+
+void yl_dneck_destroy(yl_dneck* h) {
+  if (!h) return;
+  arena_release(h->mem);
+  hipFree(h->maps.dev); (void)hipGetLastError();
+  delete h;
+}
+
+yl_status yl_dneck_held(const yl_dneck* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
+  return arena_held(h ? &h->mem : nullptr, saved_bytes, workspace_bytes, forward_held);
+}
+
+yl_status yl_dneck_create(int32_t device, const yl_neck_cfg* cfg, yl_dneck** out) {
+  if (!out || !cfg_ok(cfg)) return YL_ERR_INVALID;
+  if (!cfg_supported(cfg)) return YL_ERR_UNSUPPORTED;
+  if (hipSetDevice(device) != hipSuccess) return YL_ERR_HIP;
+  yl_dneck* h = new (std::nothrow) yl_dneck();
+  if (!h) return YL_ERR_NOMEM;
+  h->mem.device = device; h->cfg = *cfg;
+  *out = h;
+  return YL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+struct DBuffers {
+  float *t[YL_NECK_MAX_LEVELS];
+  float *z[YL_NECK_MAX_LEVELS][YL_NECK_MAX_DEPTH], *h[YL_NECK_MAX_LEVELS][YL_NECK_MAX_DEPTH];
+  float* stats[YL_NECK_MAX_LEVELS][YL_NECK_MAX_DEPTH];
+  float *ga, *gb, *gt, *coef, *wpack, *wpart;
+  double* spart;
+  LevelMaps maps[YL_NECK_MAX_LEVELS];
+};
+
+// the handle's memory for (batch, sizes), cut as yl_dneck_plan counts it; `save`: every level and block apart
+yl_status ensure(yl_dneck* h, int B, const int32_t* sizes, bool save, yl_dneck_plan_info* pl, DBuffers* nb) {
+  yl_status st = yl_dneck_plan(&h->cfg, B, sizes, pl);
+  if (st != YL_OK) return st;
+  st = arena_reserve(h->mem, save ? pl->saved_bytes : pl->nosave_bytes, pl->workspace_bytes);
+  if (st != YL_OK) return st;
+  const int L = h->cfg.num_levels, D = h->cfg.depth;
+  const size_t F = h->cfg.channels;
+  st = maps_ensure(h->maps, L, sizes, pl->table_bytes, nb->maps);
+  if (st != YL_OK) return st;
+  size_t amax = 0, smax = 0;
+  for (int k = 0; k < L; ++k) {
+    const size_t a = (size_t)pl->level[k].rows * F * 4, sp = (size_t)round16((int64_t)pl->level[k].stat_tiles * 2 * F * 8);
+    amax = a > amax ? a : amax;
+    smax = sp > smax ? sp : smax;
+  }
+  char* w = h->mem.work;
+  nb->ga = (float*)w; w += amax;
+  nb->gb = (float*)w; w += amax;
+  nb->gt = (float*)w; w += amax;
+  nb->spart = (double*)w; w += smax;
+  nb->coef = (float*)w; w += 2 * F * 4;
+  nb->wpack = (float*)w; w += 9 * F * F * 4;
+  nb->wpart = (float*)w;
+  char* p = h->mem.saved;
+  for (int k = 0; k < L; ++k) {
+    const size_t act = (size_t)pl->level[k].rows * F * 4;
+    if (!save) p = h->mem.saved;         // every level in the same memory
+    nb->t[k] = (float*)p; p += act;
+    const int blocks = save ? D : 1;
+    for (int i = 0; i < YL_NECK_MAX_DEPTH; ++i) nb->z[k][i] = nb->h[k][i] = nb->stats[k][i] = nullptr;
+    for (int i = 0; i < blocks; ++i) {
+      nb->z[k][i] = (float*)p; p += act;
+      nb->h[k][i] = (float*)p; p += act;
+    }
+    for (int i = 0; i < blocks; ++i) { nb->stats[k][i] = (float*)p; p += 2 * F * 4; }
+  }
+  return YL_OK;
+}
+
+bool params_ok(const yl_neck_cfg& c, const yl_dneck_tensors* t) {
+  if (!t) return false;
+  uintptr_t any = 0;
+  for (int k = 0; k < c.num_levels; ++k) {
+    const yl_dneck_level& l = t->level[k];
+    if (!l.lat_w || !l.lat_b) return false;
+    any |= (uintptr_t)l.lat_w | (uintptr_t)l.lat_b;
+    for (int i = 0; i < c.depth; ++i) {
+      const yl_dneck_block& b = l.block[i];
+      if (!b.w || !b.gamma || !b.beta || !b.running_mean || !b.running_var || !b.num_batches_tracked) return false;
+      any |= (uintptr_t)b.w | (uintptr_t)b.gamma | (uintptr_t)b.beta | (uintptr_t)b.running_mean | (uintptr_t)b.running_var;
+      if ((uintptr_t)b.num_batches_tracked & 7u) return false;
+    }
+  }
+  return !(any & 3u);
+}
+
+// pack + convolution of one level: 2 launches.  T: the transposed convolution (the gradient of the input)
+void conv3x3(hipStream_t s, const float* w, float* wpack, const float* x, float* out, int B, int S, int F, int T) {
+  const int TX = ceil_div(S, CT);
+  hipLaunchKernelGGL(yl_dneck_pack_kernel, dim3(ceil_div(9L * F * F, NT)), dim3(NT), 0, s, w, wpack, F, T);
+  hipLaunchKernelGGL(yl_dneck_conv_kernel, dim3(B * TX * TX, ceil_div(F, CNB)), dim3(NT), 0, s, x, (const float*)wpack, out, S, F, TX);
+}
+
+// the first block something of `g` is wanted of (D: none)
+int first_wanted(const yl_dneck_block* g, int D) {
+  int first = D;
+  for (int t = D - 1; t >= 0; --t)
+    if (g[t].w || g[t].gamma || g[t].beta) first = t;
+  return first;
+}
+
+}  // namespace
+
+extern "C" {
+
+yl_status yl_dneck_forward(yl_dneck* h, const yl_dneck_tensors* params, const float* const* c_dev, int32_t batch,
+                           const int32_t* sizes, uint32_t flags, float* const* p_dev, void* stream, int32_t* launches) {
+  if (!h || !c_dev || !p_dev || !sizes || !params_ok(h->cfg, params)) return YL_ERR_INVALID;
+  const int L = h->cfg.num_levels, D = h->cfg.depth, F = h->cfg.channels;
+  const bool train = flags & YL_HEAD_TRAIN, save = flags & YL_HEAD_SAVE;
+  for (int k = 0; k < L; ++k) {
+    if (!c_dev[k] || !p_dev[k] || sizes[k] < 1) return YL_ERR_INVALID;
+    if (((uintptr_t)c_dev[k] & 15u) || ((uintptr_t)p_dev[k] & 15u)) return YL_ERR_UNSUPPORTED;
+    if (train && (int64_t)batch * sizes[k] * sizes[k] < 2) return YL_ERR_INVALID;   // no variance of one value
+  }
+  yl_dneck_plan_info pl;
+  DBuffers nb;
+  const yl_status st = ensure(h, batch, sizes, save, &pl, &nb);
+  if (st != YL_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const int cq = pick_cq(F);
+  int nl = 0;
+  h->mem.fValid = 0;
+  for (int k = L - 1; k >= 0; --k) {
+    const yl_dneck_level& lv = params->level[k];
+    const yl_dneck_level_plan& lp = pl.level[k];
+    const int M = lp.rows, Cin = h->cfg.in_channels[k], S = sizes[k];
+    const long n4 = (long)M * (F >> 2);
+    lateral_forward(s, lv.lat_w, lv.lat_b, c_dev[k], nb.t[k], k + 1 < L ? p_dev[k + 1] : nullptr, nb.maps[k].src, F, M, Cin, S,
+                    k + 1 < L ? sizes[k + 1] : 0);
+    ++nl;
+    const float* in = nb.t[k];
+    for (int t = 0; t < D; ++t) {
+      const int i = save ? t : 0;        // nothing is kept without `save`: every block runs in the first block's buffers
+      const yl_dneck_block& b = lv.block[t];
+      // with `save` the last block writes the handle's h and p_k is a copy of it; without, it writes p_k
+      float* hout = (t == D - 1 && !save) ? p_dev[k] : nb.h[k][i];
+      conv3x3(s, b.w, nb.wpack, in, nb.z[k][i], batch, S, F, 0);
+      nl += 2;
+      if (train) {
+        StatP sp;
+        sp.a = nb.z[k][i]; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = nb.spart;
+        sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 0;
+        hipLaunchKernelGGL(yl_head_colstats_kernel, dim3(lp.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
+        ++nl;
+      }
+      BnFwdP bp;
+      bp.part = nb.spart; bp.tiles = lp.stat_tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
+      bp.rm = b.running_mean; bp.rv = b.running_var; bp.nbt = b.num_batches_tracked; bp.stats = nb.stats[k][i];
+      hipLaunchKernelGGL(yl_head_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
+      hipLaunchKernelGGL(yl_dneck_bn_silu_kernel, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, (const float*)nb.z[k][i],
+                         (const float*)nb.stats[k][i], (const float*)b.gamma, (const float*)b.beta, hout, n4, F);
+      nl += 2;
+      in = hout;
+    }
+    if (save && hipMemcpyAsync(p_dev[k], in, (size_t)M * F * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
+  }
+  if (launches) *launches = nl;
+  if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
+  if (save) {
+    h->fB = batch; h->fTrain = train ? 1 : 0; h->mem.fValid = 1;
+    for (int k = 0; k < L; ++k) h->fS[k] = sizes[k];
+  }
+  return YL_OK;
+}
+
+yl_status yl_dneck_backward(yl_dneck* h, const yl_dneck_tensors* params, const yl_dneck_tensors* grads,
+                            const float* const* c_dev, const float* const* gp_dev, float* const* dc_dev, int32_t batch,
+                            const int32_t* sizes, void* stream, int32_t* launches) {
+  if (!h || !grads || !c_dev || !gp_dev || !sizes || !params_ok(h->cfg, params)) return YL_ERR_INVALID;
+  const int L = h->cfg.num_levels, D = h->cfg.depth, F = h->cfg.channels;
+  uintptr_t gany = 0;
+  int K = -1;                            // the coarsest level something is wanted of
+  for (int k = 0; k < L; ++k) {
+    if (!c_dev[k] || !gp_dev[k]) return YL_ERR_INVALID;
+    float* dc = dc_dev ? dc_dev[k] : nullptr;
+    if (((uintptr_t)c_dev[k] & 15u) || ((uintptr_t)gp_dev[k] & 15u) || ((uintptr_t)dc & 15u)) return YL_ERR_UNSUPPORTED;
+    const yl_dneck_level& g = grads->level[k];
+    uintptr_t any = (uintptr_t)g.lat_w | (uintptr_t)g.lat_b;
+    for (int t = 0; t < D; ++t) any |= (uintptr_t)g.block[t].w | (uintptr_t)g.block[t].gamma | (uintptr_t)g.block[t].beta;
+    gany |= any;
+    if (any || dc) K = k;
+  }
+  if (gany & 3u) return YL_ERR_UNSUPPORTED;            // before the first launch: nothing of the caller's is written
+  if (!h->mem.fValid || h->fB != batch) return YL_ERR_STATE;
+  for (int k = 0; k < L; ++k)
+    if (h->fS[k] != sizes[k]) return YL_ERR_STATE;
+  yl_dneck_plan_info pl;
+  DBuffers nb;
+  const yl_status st = ensure(h, batch, sizes, true, &pl, &nb);
+  if (st != YL_OK) return st;
+  if (!h->mem.fValid) return YL_ERR_STATE;
+  hipStream_t s = (hipStream_t)stream;
+  const bool train = h->fTrain != 0;
+  const int cq = pick_cq(F);
+  int nl = 0;
+  for (int k = 0; k <= K; ++k) {
+    const yl_dneck_level& lv = params->level[k];
+    const yl_dneck_level& g = grads->level[k];
+    const yl_dneck_level_plan& lp = pl.level[k];
+    const int M = lp.rows, Cin = h->cfg.in_channels[k], S = sizes[k], TX = ceil_div(S, CT);
+    const long n4 = (long)M * (F >> 2);
+    const int eg = ceil_div(n4, NT);
+    float* dc = dc_dev ? dc_dev[k] : nullptr;
+    float *cur = nb.ga, *other = nb.gb;  // the two gradients in flight: dz of a block in `cur`, its input's in `other`
+    const float* dh = gp_dev[k];
+    if (k > 0) {                         // G_k = gp_k + up^T(gt_{k-1}): level k - 1 was walked down to its gt
+      hipLaunchKernelGGL(yl_neck_upadd_bwd_kernel, dim3(ceil_div((long)M * (F >> 2), NT)), dim3(NT), 0, s,
+                         (const float*)nb.gt, gp_dev[k], cur, nb.maps[k - 1].lo, nb.maps[k - 1].hi, M, S, sizes[k - 1], F);
+      ++nl;
+      dh = cur;
+    }
+    const bool lateral = g.lat_w || g.lat_b || dc;
+    const bool need_gt = lateral || k < K;
+    const int first = need_gt ? 0 : first_wanted(g.block, D);
+    for (int t = D - 1; t >= first; --t) {
+      const yl_dneck_block& b = lv.block[t];
+      const yl_dneck_block& gb = g.block[t];
+      const float* xin = t ? nb.h[k][t - 1] : nb.t[k];
+      const bool sums = train || gb.gamma || gb.beta;
+      if (sums) {                        // sum g, sum g * xhat: dbeta, dgamma, and the two means the batch statistics carry
+        SiluStatP sp;
+        sp.dh = dh; sp.z = nb.z[k][t]; sp.stats = nb.stats[k][t]; sp.gamma = b.gamma; sp.beta = b.beta; sp.part = nb.spart;
+        sp.M = M; sp.F = F; sp.CQ = cq;
+        hipLaunchKernelGGL(yl_dneck_colstats_silu_kernel, dim3(lp.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
+        ++nl;
+      }
+      const bool need_dx = t > first || (t == 0 && need_gt);
+      BnBwdP bp;
+      bp.part = nb.spart; bp.tiles = sums ? lp.stat_tiles : 0; bp.M = M; bp.F = F; bp.train = train;
+      bp.dgamma = gb.gamma; bp.dbeta = gb.beta; bp.coef = nb.coef;
+      hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
+      ++nl;
+      if (!gb.w && !need_dx) break;
+      hipLaunchKernelGGL(yl_dneck_bn_silu_bwd_kernel, dim3(eg), dim3(NT), 0, s, dh, (const float*)nb.z[k][t],
+                         (const float*)nb.stats[k][t], (const float*)nb.coef, (const float*)b.gamma, (const float*)b.beta,
+                         cur, n4, F);
+      ++nl;
+      if (gb.w) {                        // dW[n][c][tap] = sum_m dz[m][n] * x[m + tap][c]
+        const int gbk = ceil_div(F, GB);
+        hipLaunchKernelGGL(yl_dneck_wgrad_kernel, dim3(gbk, gbk, lp.w3grad_splits), dim3(NT), 0, s, xin, (const float*)cur,
+                           nb.wpart, S, F, TX, lp.conv_tiles, lp.w3grad_tiles);
+        hipLaunchKernelGGL(yl_dneck_wsum_kernel, dim3(ceil_div(9L * F * F, NT)), dim3(NT), 0, s, (const float*)nb.wpart,
+                           lp.w3grad_splits, F, gb.w);
+        nl += 2;
+      }
+      if (!need_dx) break;
+      float* dx = t ? other : nb.gt;     // the gradient of the block's input: the next block's dh, or gt_k
+      conv3x3(s, b.w, nb.wpack, cur, dx, batch, S, F, 1);
+      nl += 2;
+      if (t) { dh = dx; float* sw = cur; cur = other; other = sw; }
+    }
+    if (lateral)
+      lateral_backward(s, lv.lat_w, g.lat_w, g.lat_b, dc, c_dev[k], nb.gt, nb.wpart, nb.spart, F, Cin, M, S, lp.stat_tiles,
+                       lp.lgrad_rows, lp.lgrad_splits, &nl);
+  }
+  if (launches) *launches = nl;
+  return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;
+}
+
+}  // extern "C"

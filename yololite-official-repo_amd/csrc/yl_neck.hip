@@ -6,89 +6,16 @@
 //                                    dWlat_k = gt_k^T . c_k   dblat_k = colsum gt_k   dc_k = gt_k . Wlat_k
 //
 // The block (depthwise 3x3 -> 1x1 -> BatchNorm -> ReLU), its kernels and its launch sequences are the heads'
-// (yl_block.h).  New here:
-//   * the lateral's epilogue: an output accessor of yl_head_gemm_kernel that adds the bias and the coarser level's p read
-//     through the nearest map, and writes t_k;
-//   * the transposed upsample as a gather: the nearest map is monotone, so the pre-image of a source cell is a
-//     contiguous range of destination rows and of columns; one thread per (b, i, j, channel quad) sums its range in
-//     row-major order and adds gp_k.  No atomics;
-//   * the lateral's gradients from the GEMM forms of the heads (split GEMM + ordered sum for the weight, NP = Cin,
-//     NQ = F; float64 column sums for the bias; one GEMM for dc).
+// (yl_block.h).  The lateral's epilogue, the transposed upsample as a gather, the lateral's gradients and the nearest
+// maps on the device are shared with the dense neck (yl_fpn.h).
 // The nearest maps follow torch (scale = (float)in / out in fp32, src = min((int)floorf(dst * scale), in - 1)); they are
 // computed on the host and kept on the device as small int tables.
-#include <new>
-
-#include "yl_block.h"
-
-namespace {
-
-// ---- t = acc + bias (+ p of the coarser level at the nearest source cell); rows of F floats, F % 4 == 0
-struct OutLateral {
-  float* t; const float* bias; const float* up;     // up == NULL: the coarsest level
-  const int* src;                                   // [S]: source index of a destination index
-  int F, S, Sc;
-  __device__ __forceinline__ void store(int p, int q, f32x4 v, int NP, int NQ, int) const {
-    if (q >= NQ || p >= NP) return;
-    f32x4 o;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) o[s] = v[s] + bias[p + s];
-    if (up) {
-      const int SS = S * S, b = q / SS, ij = q - b * SS, i = ij / S, j = ij - i * S;
-      const long row = ((long)b * Sc + src[i]) * Sc + src[j];
-      o = ld4(up + row * F + p) + o;
-    }
-    st4(t + (long)q * F + p, o);
-  }
-};
-
-// G[b, i, j, :] = gp[b, i, j, :] + sum over ii in [lo[i], hi[i]), jj in [lo[j], hi[j]) of gt[b, ii, jj, :]
-__global__ __launch_bounds__(NT) void yl_neck_upadd_bwd_kernel(const float* __restrict__ gt, const float* __restrict__ gp,
-                                                              float* __restrict__ G, const int* __restrict__ lo,
-                                                              const int* __restrict__ hi, int M, int S, int Sf, int F) {
-  const int F4 = F >> 2;
-  const long idx = (long)blockIdx.x * NT + threadIdx.x;
-  if (idx >= (long)M * F4) return;
-  const int m = (int)(idx / F4), c = (int)(idx - (long)m * F4) * 4;
-  const int SS = S * S, b = m / SS, ij = m - b * SS, i = ij / S, j = ij - i * S;
-  const int i0 = lo[i], i1 = hi[i], j0 = lo[j], j1 = hi[j];
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  for (int ii = i0; ii < i1; ++ii)
-    for (int jj = j0; jj < j1; ++jj) acc = acc + ld4(gt + (((long)b * Sf + ii) * Sf + jj) * F + c);
-  st4(G + (long)m * F + c, ld4(gp + (long)m * F + c) + acc);
-}
-
-// bias gradient: the column-sum partials of yl_head_ysum_kernel summed in tile order
-__global__ __launch_bounds__(NT) void yl_neck_bsum_kernel(const double* __restrict__ part, int tiles, int n, float* __restrict__ out) {
-  const int c = blockIdx.x * NT + threadIdx.x;
-  if (c >= n) return;
-  double s = 0;
-  for (int t = 0; t < tiles; ++t) s += part[(long)t * n + c];
-  out[c] = (float)s;
-}
-
-bool cfg_ok(const yl_neck_cfg* c) {
-  if (!c || c->channels < 4 || c->depth < 1 || c->depth > YL_NECK_MAX_DEPTH || c->num_levels < 1 ||
-      c->num_levels > YL_NECK_MAX_LEVELS)
-    return false;
-  for (int k = 0; k < c->num_levels; ++k)
-    if (c->in_channels[k] < 4) return false;
-  return true;
-}
-bool cfg_supported(const yl_neck_cfg* c) {
-  if (c->channels & 3) return false;
-  for (int k = 0; k < c->num_levels; ++k)
-    if (c->in_channels[k] & 3) return false;
-  return true;
-}
-
-}  // namespace
+#include "yl_fpn.h"
 
 struct yl_neck {
   Arena mem;                             // yl_block.h
   yl_neck_cfg cfg;
-  int64_t table_cap;
-  int* tables;
-  int tS[YL_NECK_MAX_LEVELS];            // the sizes the tables on the device were made for (0: none)
+  MapTables maps;                        // yl_fpn.h
   int fB, fS[YL_NECK_MAX_LEVELS], fTrain;   // the forward whose activations are held (mem.fValid)
 };
 
@@ -123,8 +50,7 @@ yl_status yl_neck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* siz
   int64_t Mmax = 0, smax = 0, wmax = 0;
   for (int k = 0; k < cfg->num_levels; ++k) {
     const int64_t M = (int64_t)batch * sizes[k] * sizes[k], Cin = cfg->in_channels[k];
-    if (M > (int64_t)65535 * GEMM_ROWS || M * F >= ((int64_t)1 << 40) || M * Cin >= ((int64_t)1 << 40) || Cin > (1 << 20))
-      return YL_ERR_UNSUPPORTED;
+    if (!level_rows_ok(M, F, Cin)) return YL_ERR_UNSUPPORTED;
     yl_neck_level_plan& lp = out->level[k];
     lp.rows = (int32_t)M;
     lp.stat_tiles = ceil_div(M, STAT_ROWS); lp.gemm_tiles = ceil_div(M, GEMM_ROWS);
@@ -139,8 +65,8 @@ yl_status yl_neck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* siz
     const int64_t lpb = (int64_t)lp.lgrad_splits * F * Cin * 4;
     wp = ((wp > lpb ? wp : lpb) + 15) & ~(int64_t)15;
     wmax = wp > wmax ? wp : wmax;
-    if (k + 1 < cfg->num_levels) out->table_bytes += ((int64_t)sizes[k] + 2 * (int64_t)sizes[k + 1]) * 4;
   }
+  out->table_bytes = map_table_bytes(cfg->num_levels, sizes);
   out->nosave_bytes = 4 * Mmax * F * 4 + 2 * F * 4;
   out->workspace_bytes = 3 * Mmax * F * 4 + smax + 2 * F * 4 + wmax;
   return YL_OK;
@@ -149,7 +75,7 @@ yl_status yl_neck_plan(const yl_neck_cfg* cfg, int32_t batch, const int32_t* siz
 void yl_neck_destroy(yl_neck* h) {
   if (!h) return;
   arena_release(h->mem);
-  hipFree(h->tables); (void)hipGetLastError();
+  hipFree(h->maps.dev); (void)hipGetLastError();
   delete h;
 }
 
@@ -172,8 +98,6 @@ yl_status yl_neck_create(int32_t device, const yl_neck_cfg* cfg, yl_neck** out) 
 
 namespace {
 
-struct LevelMaps { const int *src, *lo, *hi; };      // of the pair (destination k, source k + 1)
-
 struct NeckBuffers {
   Buffers lv[YL_NECK_MAX_LEVELS];        // ga, gb, spart, coef, wpart are the same workspace in every level
   float* t[YL_NECK_MAX_LEVELS];
@@ -189,35 +113,8 @@ yl_status ensure(yl_neck* h, int B, const int32_t* sizes, bool save, yl_neck_pla
   if (st != YL_OK) return st;
   const int L = h->cfg.num_levels, D = h->cfg.depth;
   const size_t F = h->cfg.channels;
-  bool same = true;
-  for (int k = 0; k < L; ++k) same = same && h->tS[k] == sizes[k];
-  if (!same && L > 1) {                  // new maps: nothing that reads the old ones may still run
-    if (hipDeviceSynchronize() != hipSuccess) return YL_ERR_HIP;
-    for (int k = 0; k < L; ++k) h->tS[k] = 0;
-    if (pl->table_bytes > h->table_cap) {
-      hipFree(h->tables);
-      h->tables = nullptr; h->table_cap = 0;
-      if (hipMalloc((void**)&h->tables, (size_t)pl->table_bytes) != hipSuccess) { (void)hipGetLastError(); return YL_ERR_NOMEM; }
-      h->table_cap = pl->table_bytes;
-    }
-    int32_t* host = new (std::nothrow) int32_t[(size_t)pl->table_bytes / 4];
-    if (!host) return YL_ERR_NOMEM;
-    int32_t* q = host;
-    for (int k = 0; k + 1 < L; ++k) {
-      yl_neck_nearest_map(sizes[k], sizes[k + 1], q, q + sizes[k], q + sizes[k] + sizes[k + 1]);
-      q += sizes[k] + 2 * sizes[k + 1];
-    }
-    const hipError_t e = hipMemcpy(h->tables, host, (size_t)pl->table_bytes, hipMemcpyHostToDevice);
-    delete[] host;
-    if (e != hipSuccess) return YL_ERR_HIP;
-    for (int k = 0; k < L; ++k) h->tS[k] = sizes[k];
-  }
-  const int* q = h->tables;
-  for (int k = 0; k < YL_NECK_MAX_LEVELS; ++k) nb->maps[k] = LevelMaps{nullptr, nullptr, nullptr};
-  for (int k = 0; k + 1 < L; ++k) {
-    nb->maps[k] = LevelMaps{q, q + sizes[k], q + sizes[k] + sizes[k + 1]};
-    q += sizes[k] + 2 * sizes[k + 1];
-  }
+  st = maps_ensure(h->maps, L, sizes, pl->table_bytes, nb->maps);
+  if (st != YL_OK) return st;
   size_t amax = 0, smax = 0;
   for (int k = 0; k < L; ++k) {
     const size_t a = (size_t)pl->level[k].rows * F * 4, sp = (size_t)spart_bytes(pl->level[k].stat_tiles, F, F);
@@ -279,10 +176,8 @@ yl_status yl_neck_forward(yl_neck* h, const yl_neck_tensors* params, const float
   for (int k = L - 1; k >= 0; --k) {
     const yl_neck_level& lv = params->level[k];
     const int M = pl.level[k].rows, Cin = h->cfg.in_channels[k], S = sizes[k];
-    OutLateral ol;
-    ol.t = nb.t[k]; ol.bias = lv.lat_b; ol.up = k + 1 < L ? p_dev[k + 1] : nullptr; ol.src = nb.maps[k].src;
-    ol.F = F; ol.S = S; ol.Sc = k + 1 < L ? sizes[k + 1] : 0;
-    launch_gemm(s, RowsScalar{lv.lat_w, Cin}, RowsVec{c_dev[k], Cin}, ol, F, M, Cin, Cin, 1);
+    lateral_forward(s, lv.lat_w, lv.lat_b, c_dev[k], nb.t[k], k + 1 < L ? p_dev[k + 1] : nullptr, nb.maps[k].src, F, M, Cin, S,
+                    k + 1 < L ? sizes[k + 1] : 0);
     ++nl;
     // with `save` the last block writes the handle's h and p_k is a copy of it; without, it writes p_k
     const float* last = blocks_forward(s, lv.block, D, nb.t[k], nb.lv[k], save, train, dims_of(pl.level[k], S, F),
@@ -344,27 +239,8 @@ yl_status yl_neck_backward(yl_neck* h, const yl_neck_tensors* params, const yl_n
     const int first = need_gt ? 0 : blocks_first_wanted(g.block, D);
     blocks_backward(s, lv.block, g.block, D, first, gin, nb.t[k], need_gt ? nb.gt : nullptr, bf, train,
                     dims_of(lp, S, F), &nl);
-    if (g.lat_w) {                       // dWlat[f][cin] = sum over rows of gt[m][f] * c[m][cin]
-      launch_gemm(s, ColsScalar{c_dev[k], Cin}, ColsScalar{nb.gt, F}, OutPartial{bf.wpart, (long)F * Cin}, Cin, F, M,
-                  lp.lgrad_rows, lp.lgrad_splits);
-      HeadRows none;
-      memset(&none, 0, sizeof(none));
-      hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)F * Cin, NT)), dim3(NT), 0, s, (const float*)bf.wpart,
-                         lp.lgrad_splits, Cin, F, g.lat_w, none, 0);
-      nl += 2;
-    }
-    if (g.lat_b) {
-      const HeadGeom plain = {1, F, 0, S * S, F};   // column n of row m at m * F + n
-      hipLaunchKernelGGL(yl_head_ysum_kernel, dim3(lp.stat_tiles, ceil_div(F, 64)), dim3(NT), 0, s, (const float*)nb.gt,
-                         plain, bf.spart, M, F);
-      hipLaunchKernelGGL(yl_neck_bsum_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, (const double*)bf.spart,
-                         lp.stat_tiles, F, g.lat_b);
-      nl += 2;
-    }
-    if (dc) {                            // dc = gt . Wlat
-      launch_gemm(s, ColsScalar{lv.lat_w, Cin}, RowsVec{nb.gt, F}, OutRowsVec{dc, Cin}, Cin, M, F, F, 1);
-      ++nl;
-    }
+    lateral_backward(s, lv.lat_w, g.lat_w, g.lat_b, dc, c_dev[k], nb.gt, bf.wpart, bf.spart, F, Cin, M, S, lp.stat_tiles,
+                     lp.lgrad_rows, lp.lgrad_splits, &nl);
   }
   if (launches) *launches = nl;
   return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;

@@ -1,5 +1,9 @@
-"""Trainable depthwise FPN neck on the device: the laterals, the top-down upsample-add chain and the smooth blocks of
-the reference's YOLOLiteMS_CPU, with a backward pass.
+"""Trainable FPN necks on the device: the laterals, the top-down upsample-add chain and the smooth blocks of the
+reference's two architectures, with a backward pass.
+
+    DetectNeck      arch YOLOLiteMS_CPU: smooth block = depthwise 3x3 -> 1x1 -> BatchNorm -> ReLU   (csrc/yl_neck.hip)
+    DetectNeckMS    arch YOLOLiteMS (the default arch): dense 3x3 -> BatchNorm -> SiLU              (csrc/yl_dneck.hip)
+    neck_for(meta, sd=None)     the right class's instance for a model's meta (from_state_dict with `sd`, else from_meta)
 
     neck = DetectNeck(in_channels, fpn_channels, depth)          # or .from_meta(meta) / .from_state_dict(meta, sd)
     ps = neck(model.features(x))                                 # NHWC [B,S,S,F] per level, finest first
@@ -13,8 +17,13 @@ parameters().  The whole neck is ONE torch.autograd.Function (yl_neck_forward / 
 top-down chain is internal to it and autograd hands it the gradient of every p_k.  train() / eval() select the BatchNorm
 mode.  Gradients nobody asked for are not computed (`last_launches` says what ran).  One forward is held for backward
 at a time: a second forward before backward() replaces it, and the stale backward raises.  fp32 on one HIP device; no
-CPU fallback.  Not implemented, and refused: the P6 path (`use_p6`) and the dense-3x3 + SiLU smooth blocks of arch
-YOLOLiteMS.
+CPU fallback.  Not implemented, and refused: the P6 path (`use_p6`); DetectNeck refuses arch YOLOLiteMS and DetectNeckMS
+refuses arch YOLOLiteMS_CPU, each naming the other.
+
+DetectNeckMS is the same module around the other block (model_v2.py:15-22 conv_block, :115-127, :194-203): its entries are
+`lateral{k}.weight/bias`, `smooth{k}.{3i}.weight` [F,F,3,3] and `smooth{k}.{3i+1}.weight/bias/running_mean/running_var/
+num_batches_tracked` (conv_block is a plain nn.Sequential: no `.block.` level), one autograd.Function over
+yl_dneck_forward / yl_dneck_backward.  The 3x3 convolution runs forward, input gradient and weight gradient on fp32 MFMA.
 """
 from __future__ import annotations
 
@@ -89,6 +98,7 @@ def nearest_map(out_size: int, in_size: int) -> Tuple[np.ndarray, np.ndarray, np
 
 class _Handle(tm.DeviceHandle):
     """The neck's handle (see _trainmod.DeviceHandle) and the order its tensors go to the library in"""
+    who = "DetectNeck"
 
     def __init__(self, in_channels, F: int, depth: int):
         super().__init__("yl_neck", _cfg, tuple(in_channels), F, depth)
@@ -110,12 +120,40 @@ class _Handle(tm.DeviceHandle):
         return t
 
 
+class _HandleMS(tm.DeviceHandle):
+    """The dense neck's handle: yl_dneck_*, per level lateral weight, bias, then per block w, gamma, beta"""
+    who = "DetectNeckMS"
+
+    def __init__(self, in_channels, F: int, depth: int):
+        super().__init__("yl_dneck", _cfg, tuple(in_channels), F, depth)
+        self.F, self.depth, self.L = F, depth, len(in_channels)
+
+    @property
+    def per_level(self) -> int:
+        return 2 + 3 * self.depth
+
+    def table(self, tensors: Sequence[Optional[torch.Tensor]], buffers=None):
+        """yl_dneck_tensors from a list in DetectNeckMS._param_list() order (None = NULL)"""
+        t = _lib.yl_dneck_tensors()
+        n = self.per_level
+        for k in range(self.L):
+            lv, ts = t.level[k], tensors[k * n:(k + 1) * n]
+            lv.lat_w, lv.lat_b = tm.ptr(ts[0]), tm.ptr(ts[1])
+            for i in range(self.depth):
+                b = lv.block[i]
+                b.w, b.gamma, b.beta = (tm.ptr(v) for v in ts[2 + 3 * i:5 + 3 * i])
+                if buffers is not None:
+                    b.running_mean, b.running_var, b.num_batches_tracked = (tm.ptr(v) for v in buffers[k][i])
+        return t
+
+
 def _ptrs(ts):
     return (C.c_void_p * len(ts))(*[tm.ptr(t) for t in ts])
 
 
 class _NeckFunction(torch.autograd.Function):
-    """(p_0, ..., p_{L-1}) = neck(c_0, ..., c_{L-1} NHWC, parameters): yl_neck_forward / yl_neck_backward"""
+    """(p_0, ..., p_{L-1}) = neck(c_0, ..., c_{L-1} NHWC, parameters): <prefix>_forward / <prefix>_backward of the handle
+    (yl_neck_* or yl_dneck_*: the two share their signatures)"""
 
     @staticmethod
     def forward(fctx, hd: _Handle, bufs, train: bool, grad_mode: bool, *args):
@@ -126,7 +164,7 @@ class _NeckFunction(torch.autograd.Function):
         save = tm.saving(fctx, grad_mode)
         cd = [tm.aligned(c.detach()) for c in cs]
         dev = cs[0].device
-        ps = tm.detached_params("DetectNeck", params, dev)
+        ps = tm.detached_params(hd.who, params, dev)
         outs = [torch.empty((B, S, S, hd.F), device=dev, dtype=torch.float32) for S in sizes]
         hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), _ptrs(cd), B, (C.c_int32 * L)(*sizes), tm.flags(train, save),
                   _ptrs(outs))
@@ -139,7 +177,7 @@ class _NeckFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(fctx, *gps):
         hd = fctx.hd
-        hd.check_generation(fctx.generation, "DetectNeck: the neck", "one forward")
+        hd.check_generation(fctx.generation, hd.who + ": the neck", "one forward")
         L = hd.L
         saved = fctx.saved_tensors
         cd, params = saved[:L], saved[L:]
@@ -152,8 +190,22 @@ class _NeckFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
-class DetectNeck(nn.Module):
-    """See the module docstring.  `in_channels`: the channels of the feature maps, finest level first."""
+def conv_block(F: int, n: int) -> nn.Module:
+    """Container only (the reference's conv_block(F, F, n)): the layers hold the parameters; their forward is never called."""
+    layers = []
+    for _ in range(n):
+        layers += [nn.Conv2d(F, F, 3, padding=1, bias=False), nn.BatchNorm2d(F), nn.SiLU(inplace=True)]
+    return nn.Sequential(*layers)
+
+
+def _meta_arch(meta: dict, mcfg: dict) -> str:
+    return (meta.get("arch") or mcfg.get("arch") or "YOLOLiteMS").lower()
+
+
+class _NeckBase(nn.Module):
+    """What the two necks share: the reference constructor's order of registration, the reading of meta and checkpoint,
+    and forward().  A subclass gives _who, _handle_cls, _smooth(F, depth), _meta_dims(meta), _param_list(), _bn(level
+    name, block)."""
 
     def __init__(self, in_channels: Sequence[int], fpn_channels: int, depth: int = 1,
                  level_names: Sequence[str] = ("p3", "p4", "p5")):
@@ -167,26 +219,15 @@ class DetectNeck(nn.Module):
         rest = [(n, ci) for n, ci in zip(self.level_names, in_channels) if n != "p2"]
         if "p2" in self.level_names:                       # the reference's order of registration (model_v2.py:286-294)
             self.lateral2 = nn.Conv2d(in_channels[self.level_names.index("p2")], F, 1)
-            self.smooth2 = tm.dw_block(F, self.depth)
+            self.smooth2 = self._smooth(F, self.depth)
         for n, ci in rest:
             setattr(self, "lateral" + n[1:], nn.Conv2d(ci, F, 1))
         for n, ci in rest:
-            setattr(self, "smooth" + n[1:], tm.dw_block(F, self.depth))
-        self._handle = _Handle(in_channels, F, self.depth)
-
-    @staticmethod
-    def _meta_dims(meta: dict):
-        F, names, mcfg, tcfg = tm.meta_fpn(meta)
-        arch = (meta.get("arch") or mcfg.get("arch") or "YOLOLiteMS").lower()
-        if arch != "yololitems_cpu":
-            raise _lib.YoloLiteHipError(f"DetectNeck: the dense-3x3 + SiLU smooth blocks of arch {arch!r} are not implemented "
-                                        "(only YOLOLiteMS_CPU's depthwise neck is)")
-        if tcfg.get("use_p6"):
-            raise _lib.YoloLiteHipError("DetectNeck: the P6 path (use_p6) is not implemented")
-        return F, max(1, round(2 * float(mcfg.get("depth_multiple", 1.0)))), names
+            setattr(self, "smooth" + n[1:], self._smooth(F, self.depth))
+        self._handle = self._handle_cls(in_channels, F, self.depth)
 
     @classmethod
-    def from_meta(cls, meta: dict) -> "DetectNeck":
+    def from_meta(cls, meta: dict):
         """a freshly initialised neck of the model `meta` describes; the input channels are those of the feature maps of
         the program build_program makes for it"""
         from .program import build_program, synth_state_dict
@@ -196,7 +237,7 @@ class DetectNeck(nn.Module):
         return cls(cin, F, d, level_names=names)
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict) -> "DetectNeck":
+    def from_state_dict(cls, meta: dict, sd: dict):
         """the neck of a checkpoint: built from its meta, filled with its `lateral*.` / `smooth*.` entries"""
         F, d, names = cls._meta_dims(meta)
         missing = [f"lateral{n[1:]}.weight" for n in names if f"lateral{n[1:]}.weight" not in sd]
@@ -205,22 +246,11 @@ class DetectNeck(nn.Module):
         cin = [int(np.shape(sd[f"lateral{n[1:]}.weight"])[1]) for n in names]
         return tm.fill_from_state_dict(cls(cin, F, d, level_names=names), sd, "neck")
 
-    def _param_list(self) -> List[torch.Tensor]:
-        """per level: lateral weight, bias, then per block dw, pw, gamma, beta"""
-        out = []
-        for n in self.level_names:
-            lat, s = getattr(self, "lateral" + n[1:]), getattr(self, "smooth" + n[1:]).block
-            out += [lat.weight, lat.bias]
-            for i in range(self.depth):
-                out += [s[4 * i].weight, s[4 * i + 1].weight, s[4 * i + 2].weight, s[4 * i + 2].bias]
-        return out
-
     def _stat_buffers(self):
         out = []
         for n in self.level_names:
-            s = getattr(self, "smooth" + n[1:]).block
-            out.append([(s[4 * i + 2].running_mean, s[4 * i + 2].running_var, s[4 * i + 2].num_batches_tracked)
-                        for i in range(self.depth)])
+            bns = [self._bn(n, i) for i in range(self.depth)]
+            out.append([(bn.running_mean, bn.running_var, bn.num_batches_tracked) for bn in bns])
         return out
 
     def last_launches(self) -> Dict[str, int]:
@@ -236,13 +266,117 @@ class DetectNeck(nn.Module):
         reads the layout off each map's shape and refuses a shape that is both.  -> NHWC [B,S,S,F] per level, finest
         first: what DetectHeads(..., layout="nhwc") takes."""
         feats = tm.check_layout(layout, feats, len(self.level_names))
-        xs = [tm.as_nhwc(f, ci, layout, "DetectNeck", self.training, name="Cin", bn_channels=self.fpn_channels)
+        xs = [tm.as_nhwc(f, ci, layout, self._who, self.training, name="Cin", bn_channels=self.fpn_channels)
               for f, ci in zip(feats, self.in_channels)]
         if len({int(f.shape[0]) for f in xs}) != 1 or len({f.device for f in xs}) != 1:
             raise ValueError("the feature maps must share one batch size and one device")
         params = self._param_list()
         if any(p.device != xs[0].device for p in params):
-            raise _lib.YoloLiteHipError("DetectNeck: parameters and inputs must live on one HIP device")
+            raise _lib.YoloLiteHipError(f"{self._who}: parameters and inputs must live on one HIP device")
         self._handle.ensure(xs[0].device)
         xs = [f.float().contiguous() for f in xs]          # autograd carries the gradient back through cast and copy
         return list(_NeckFunction.apply(self._handle, self._stat_buffers(), self.training, torch.is_grad_enabled(), *xs, *params))
+
+
+class DetectNeck(_NeckBase):
+    """See the module docstring.  `in_channels`: the channels of the feature maps, finest level first."""
+    _who, _handle_cls = "DetectNeck", _Handle
+
+    @staticmethod
+    def _smooth(F: int, depth: int) -> nn.Module:
+        return tm.dw_block(F, depth)
+
+    @staticmethod
+    def _meta_dims(meta: dict):
+        F, names, mcfg, tcfg = tm.meta_fpn(meta)
+        arch = _meta_arch(meta, mcfg)
+        if arch != "yololitems_cpu":
+            raise _lib.YoloLiteHipError(f"DetectNeck: the dense-3x3 + SiLU smooth blocks of arch {arch!r} are not implemented "
+                                        "(only YOLOLiteMS_CPU's depthwise neck is)")
+        if tcfg.get("use_p6"):
+            raise _lib.YoloLiteHipError("DetectNeck: the P6 path (use_p6) is not implemented")
+        return F, max(1, round(2 * float(mcfg.get("depth_multiple", 1.0)))), names
+
+    def _param_list(self) -> List[torch.Tensor]:
+        """per level: lateral weight, bias, then per block dw, pw, gamma, beta"""
+        out = []
+        for n in self.level_names:
+            lat, s = getattr(self, "lateral" + n[1:]), getattr(self, "smooth" + n[1:]).block
+            out += [lat.weight, lat.bias]
+            for i in range(self.depth):
+                out += [s[4 * i].weight, s[4 * i + 1].weight, s[4 * i + 2].weight, s[4 * i + 2].bias]
+        return out
+
+    def _bn(self, name: str, i: int) -> nn.Module:
+        return getattr(self, "smooth" + name[1:]).block[4 * i + 2]
+
+
+class DetectNeckMS(_NeckBase):
+    """The dense 3x3 + SiLU neck of arch YOLOLiteMS; see the module docstring.  `in_channels`: the channels of the
+    feature maps, finest level first."""
+    _who, _handle_cls = "DetectNeckMS", _HandleMS
+
+    @staticmethod
+    def _smooth(F: int, depth: int) -> nn.Module:
+        return conv_block(F, depth)
+
+    @staticmethod
+    def _meta_dims(meta: dict):
+        F, names, mcfg, tcfg = tm.meta_fpn(meta)
+        arch = _meta_arch(meta, mcfg)
+        if arch == "yololitems_cpu":
+            raise _lib.YoloLiteHipError("DetectNeckMS: the depthwise smooth blocks of arch 'yololitems_cpu' are DetectNeck's "
+                                        "(this class is the dense-3x3 + SiLU neck of YOLOLiteMS)")
+        if arch != "yololitems":
+            raise _lib.YoloLiteHipError(f"DetectNeckMS: arch {arch!r} is not implemented (only YOLOLiteMS's dense neck is)")
+        if tcfg.get("use_p6"):
+            raise _lib.YoloLiteHipError("DetectNeckMS: the P6 path (use_p6) is not implemented")
+        return F, max(1, round(2 * float(mcfg.get("depth_multiple", 1.0)))), names
+
+    def _param_list(self) -> List[torch.Tensor]:
+        """per level: lateral weight, bias, then per block w, gamma, beta"""
+        out = []
+        for n in self.level_names:
+            lat, s = getattr(self, "lateral" + n[1:]), getattr(self, "smooth" + n[1:])
+            out += [lat.weight, lat.bias]
+            for i in range(self.depth):
+                out += [s[3 * i].weight, s[3 * i + 1].weight, s[3 * i + 1].bias]
+        return out
+
+    def _bn(self, name: str, i: int) -> nn.Module:
+        return getattr(self, "smooth" + name[1:])[3 * i + 1]
+
+
+def plan_ms(in_channels: Sequence[int], fpn_channels: int, depth: int, batch: int, sizes: Sequence[int]) -> Dict:
+    """yl_dneck_plan (a host function; no device): how every level of DetectNeckMS is cut and what the handle holds.
+    -> {"stat_rows", "gemm_rows", "conv_tile", "levels": [{rows, stat_tiles, gemm_tiles, conv_tiles, lgrad_rows,
+    lgrad_splits, w3grad_tiles, w3grad_splits, saved_bytes}], "saved_bytes", "nosave_bytes", "workspace_bytes",
+    "table_bytes"} with, for F channels, depth d, M_k = batch * S_k^2 rows, Mmax the largest M_k and T = conv_tile:
+        levels[k].conv_tiles    = batch * ceil(S_k / T)^2                  spatial tiles, image-major then row-major
+        levels[k].w3grad_tiles  = ceil(conv_tiles / min(conv_tiles, 64, max(1, 512 // ceil(F / 64)^2)))
+        levels[k].w3grad_splits = ceil(conv_tiles / w3grad_tiles)          split z: tiles [z w3grad_tiles, ...)
+        levels[k].saved_bytes   = (1 + 2 d) M_k F 4 + d 2 F 4              t_k; z, h and (mean, invstd) per block
+        saved_bytes             = sum of the levels'
+        nosave_bytes            = 3 Mmax F 4 + 2 F 4                        t and one block of the largest level
+        workspace_bytes         = 3 Mmax F 4 + round16(max_k(stat_tiles_k) 2 F 8) + 2 F 4 + 9 F F 4
+                                  + max_k round16(max(w3grad_splits_k 9 F F, lgrad_splits_k F Cin_k) 4)
+        table_bytes             = sum over k < L - 1 of (S_k + 2 S_{k+1}) 4"""
+    in_channels = _check_dims(in_channels, fpn_channels, depth)
+    if len(sizes) != len(in_channels):
+        raise ValueError(f"{len(in_channels)} levels but sizes {tuple(sizes)}")
+    cfg = _cfg(in_channels, fpn_channels, depth)
+    out = _lib.yl_dneck_plan_info()
+    sz = (C.c_int32 * len(sizes))(*[int(s) for s in sizes])
+    _lib.check(_lib.load().yl_dneck_plan(C.byref(cfg), int(batch), sz, C.byref(out)), what="yl_dneck_plan")
+    lv = [{n: int(getattr(out.level[k], n)) for n, _ in out.level[k]._fields_} for k in range(len(sizes))]
+    return {"stat_rows": int(out.stat_rows), "gemm_rows": int(out.gemm_rows), "conv_tile": int(out.conv_tile), "levels": lv,
+            "saved_bytes": int(out.saved_bytes), "nosave_bytes": int(out.nosave_bytes),
+            "workspace_bytes": int(out.workspace_bytes), "table_bytes": int(out.table_bytes)}
+
+
+def neck_for(meta: dict, sd: Optional[dict] = None):
+    """the trainable neck of the model `meta` describes: DetectNeck for arch YOLOLiteMS_CPU, DetectNeckMS for YOLOLiteMS
+    (and a meta without `arch`); filled from the checkpoint `sd` if that is given, freshly initialised otherwise"""
+    mcfg = (meta.get("config", {}) or {}).get("model", {}) or {}
+    cls = DetectNeck if _meta_arch(meta, mcfg) == "yololitems_cpu" else DetectNeckMS
+    return cls.from_state_dict(meta, sd) if sd is not None else cls.from_meta(meta)
