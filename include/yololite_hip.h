@@ -860,7 +860,22 @@ yl_status yl_neck_held(const yl_neck* h, int64_t* saved_bytes, int64_t* workspac
  * stages each tile's x window and dz tile once for all nine taps and writes fp32 partials [split][tap][out][in]; a
  * second kernel sums them in split order in float64 into [F][F][3][3].
  * With YL_HEAD_SAVE the handle keeps, per level, t_k and per block z, h and (mean, invstd): the block's input is t_k
- * or the previous h. */
+ * or the previous h.
+ *
+ * Mixed precision.  YL_DNECK_F16 / YL_DNECK_BF16 in the forward's flags (exclusive: both set is YL_ERR_INVALID, checked
+ * before the device is touched) run the three 3x3 GEMMs -- forward (x, W), input gradient (dz, W), weight gradient
+ * (x, dz) -- with BOTH operands rounded to that type, round to nearest even, on v_mfma_f32_16x16x16_{f16,bf16}: products
+ * exact, accumulation in fp32.  The pack kernel writes the 16-bit weight, the convolution converts the window and the
+ * weight gradient the x window and the dz tile where they are written to LDS.  Nothing is clamped: a finite fp32 value
+ * beyond fp16's range becomes +-inf and the gradients it reaches are not finite.  Everything else (laterals, the chain,
+ * BatchNorm statistics, SiLU, the saved z / h / t, the partials and their ordered float64 sum, parameters, gradients)
+ * is fp32 as without the bits, the launch counts and yl_dneck_plan's figures are the same, and equal inputs give equal
+ * bits.  The backward runs in the mode of the forward it belongs to. */
+#define YL_DNECK_F16 0x100u
+#define YL_DNECK_BF16 0x200u
+#define YL_DNECK_PASS_FORWARD 0     /* a = x  [B][S][S][F], b = W  [F][F][3][3] -> out = z  [B][S][S][F] */
+#define YL_DNECK_PASS_DGRAD 1       /* a = dz [B][S][S][F], b = W  [F][F][3][3] -> out = dx [B][S][S][F] */
+#define YL_DNECK_PASS_WGRAD 2       /* a = x  [B][S][S][F], b = dz [B][S][S][F] -> out = dW [F][F][3][3] */
 typedef struct yl_dneck yl_dneck;
 typedef struct yl_dneck_block {     /* smooth{k}.{3i} (w), smooth{k}.{3i+1} (BatchNorm) */
   float* w;                         /* [F][F][3][3] */
@@ -927,6 +942,14 @@ yl_status yl_dneck_backward(yl_dneck* h, const yl_dneck_tensors* params, const y
                             const float* const* c_dev, const float* const* gp_dev, float* const* dc_dev, int32_t batch,
                             const int32_t* sizes, void* stream, int32_t* launches);
 yl_status yl_dneck_held(const yl_dneck* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+/* One 3x3 GEMM of the neck on its own, launched exactly as the module launches it: `pass` is a YL_DNECK_PASS_*, `mode`
+ * is 0 (fp32), YL_DNECK_F16 or YL_DNECK_BF16 (anything else: YL_ERR_INVALID); F is the handle's cfg.channels, `size` the
+ * level's S.  FORWARD and DGRAD: 2 launches (weight pack, convolution); WGRAD: 2 launches (partials, cut as
+ * yl_dneck_plan cuts a level of this batch and size, and their ordered float64 sum).  The three pointers are 16-byte
+ * aligned (else YL_ERR_UNSUPPORTED).  Uses the handle's workspace (9 F F 4 + w3grad_splits 9 F F 4 bytes at most); if
+ * that has to grow, a held forward is dropped as any growth drops it. */
+yl_status yl_dneck_conv3x3(yl_dneck* h, int32_t pass, uint32_t mode, const float* a_dev, const float* b_dev,
+                           float* out_dev, int32_t batch, int32_t size, void* stream, int32_t* launches);
 
 #ifdef __cplusplus
 }

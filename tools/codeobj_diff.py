@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Compare the device code of two builds kernel by kernel.
 
-    python tools/codeobj_diff.py A_DIR B_DIR
+    python tools/codeobj_diff.py A_DIR B_DIR [--alias B_TEXT=A_TEXT ...]
 
 A_DIR and B_DIR hold gfx950 assembly files of the same names (one per object: the compile line of csrc/build.py with
 `--offload-device-only -S -o NAME.s`).  Each file is split at its kernel symbols; a kernel is its instruction text
 and the resource lines of its `.amdhsa_kernel` block (`<symbol>:` up to `.end_amdhsa_kernel`).  Compiler-local label numbers
 (`.LBB<n>_<m>`, `.Lfunc_end<n>`, ... -- they follow the order of emission, which host code can change) are normalised.
 Prints one line per object and a total; the exit status is 0 only when every object has the same kernel symbols with
-identical text.  Device functions that are not kernels (none in this project: everything is inlined) are not compared."""
+identical text.  --alias replaces B_TEXT by A_TEXT in B's files first: for a kernel that became one instantiation of a
+template, whose mangled name changed and nothing else should have (the other instantiations then count as kernels of B only).
+Device functions that are not kernels (none in this project: everything is inlined) are not compared."""
 import os
 import re
 import sys
@@ -16,8 +18,14 @@ import sys
 LABEL = re.compile(r"\.L(BB|func_begin|func_end|tmp|JTI)(\d+)(_\d+)?")
 
 
-def kernels(path):
-    lines = open(path).read().split("\n")
+ALIASES = []
+
+
+def kernels(path, aliases=()):
+    text = open(path).read()
+    for new, old in aliases:
+        text = text.replace(new, old)
+    lines = text.split("\n")
     names = [m.group(1) for m in (re.match(r"\s*\.amdhsa_kernel\s+(\S+)", ln) for ln in lines) if m]
     out = {n: [] for n in names}
     cur = None
@@ -49,7 +57,7 @@ def main(a_dir, b_dir):
     for f in files:
         if f in missing:
             continue
-        a, b = kernels(os.path.join(a_dir, f)), kernels(os.path.join(b_dir, f))
+        a, b = kernels(os.path.join(a_dir, f)), kernels(os.path.join(b_dir, f), ALIASES)
         bad = sorted(set(a) ^ set(b)) + sorted(n for n in set(a) & set(b) if a[n] != b[n] or len(a[n]) < 2)
         for n in bad:
             print("  %s: %s %s" % (f, "only in one build:" if (n in a) != (n in b) else "differs:", n))
@@ -61,6 +69,10 @@ def main(a_dir, b_dir):
 
 
 if __name__ == "__main__":
+    while "--alias" in sys.argv:
+        i = sys.argv.index("--alias")
+        ALIASES.append(tuple(sys.argv[i + 1].split("=", 1)))
+        del sys.argv[i:i + 2]
     if len(sys.argv) != 3:
         sys.exit(__doc__)
     sys.exit(main(sys.argv[1], sys.argv[2]))

@@ -14,10 +14,16 @@ clock around it.  Per side: median and minimum over the blocks of the time per s
 launches per step of the device side, what yl_dneck_plan says the handle holds, the convolution work per step, and the
 gradient error of both sides against a float64 run of the torch module.
 
+--precision fp16 | bf16: the device side runs DetectNeckMS(precision=...) (the three 3x3 GEMMs on 16-bit MFMA, operands
+rounded to nearest even, fp32 accumulation) and the torch side runs the SAME module under torch.autocast("cuda",
+dtype=...) -- the reference's AMP, tools/train.py:284-357 -- channels-last, in the same process.  The JSON line names the
+mode on both sides ("device_precision", "torch_autocast").
+
 With --trace only --steps steps per side are run once (for `rocprofv3 --kernel-trace --stats -- python
 tools/dense_neck_train_time.py --trace ...`).
 
-    python tools/dense_neck_train_time.py [--models yololite_n,yololite_m] [--blocks 7] [--steps 20] [--out F] [--trace]"""
+    python tools/dense_neck_train_time.py [--models yololite_n,yololite_m] [--precision fp32|fp16|bf16] [--blocks 7]
+                                          [--steps 20] [--out F] [--trace]"""
 import os
 import sys
 
@@ -27,6 +33,8 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 from tools import _train_time as tt  # noqa: E402
+
+PRECISION = "fp32"                       # --precision, read off the command line before tools/_train_time.py's own arguments
 
 SHAPES = {"yololite_n": dict(F=196, depth=2, Cin=(40, 112, 320), B=32, sizes=(80, 40, 20)),
           "yololite_m": dict(F=328, depth=2, Cin=(48, 120, 352), B=16, sizes=(80, 40, 20))}
@@ -71,7 +79,8 @@ def run_model(name, blocks, steps, trace):
     F, depth, cins, B, sizes = sh["F"], sh["depth"], sh["Cin"], sh["B"], sh["sizes"]
     dev = "cuda:0"
     torch.manual_seed(3)
-    ours = ya.DetectNeckMS(cins, F, depth).to(dev).train()
+    ours = ya.DetectNeckMS(cins, F, depth, precision=PRECISION).to(dev).train()
+    cast = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(PRECISION)
     ref = torch_neck(F, depth, cins).to(dev).to(memory_format=torch.channels_last).train()
     ref.load_state_dict(ours.state_dict())
     gen = torch.Generator().manual_seed(5)
@@ -85,12 +94,16 @@ def run_model(name, blocks, steps, trace):
             p.grad = None
         if m is ours:
             torch.autograd.backward(m(feats, layout="nhwc"), gps)
-        else:
+        elif cast is None:
             torch.autograd.backward(m(feats_cl), gps_cl)
+        else:
+            with torch.autocast("cuda", dtype=cast):
+                ps = m(feats_cl)
+            torch.autograd.backward(ps, [g.to(p.dtype) for g, p in zip(gps_cl, ps)])
 
     plan = neckops.plan_ms(cins, F, depth, B, sizes)
     rows = [lp["rows"] for lp in plan["levels"]]
-    res = {"model": name, "F": F, "depth": depth, "in_channels": list(cins), "batch": B, "sizes": list(sizes),
+    res = {"model": name, "device_precision": PRECISION, "torch_autocast": PRECISION if cast is not None else "off", "F": F, "depth": depth, "in_channels": list(cins), "batch": B, "sizes": list(sizes),
            "steps_per_block": steps, "saved_bytes": plan["saved_bytes"], "nosave_bytes": plan["nosave_bytes"],
            "workspace_bytes": plan["workspace_bytes"], "table_bytes": plan["table_bytes"],
            "w3grad_splits": [lp["w3grad_splits"] for lp in plan["levels"]],
@@ -107,4 +120,10 @@ def run_model(name, blocks, steps, trace):
 
 
 if __name__ == "__main__":
-    tt.main("dense_neck_train_time.py", "yololite_n,yololite_m", run_model)
+    import argparse
+    ap = argparse.ArgumentParser(add_help=False)
+    ap.add_argument("--precision", choices=("fp32", "fp16", "bf16"), default="fp32")
+    known, rest = ap.parse_known_args()
+    PRECISION = known.precision
+    sys.argv = sys.argv[:1] + rest
+    tt.main("dense_neck_train_time.py", "yololite_n,yololite_m", run_model, header={"precision": PRECISION})

@@ -6,7 +6,7 @@
 
     python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
-                                   [--train-neck]
+                                   [--train-neck [--amp fp16|bf16]]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
@@ -22,6 +22,12 @@ gives the backbone's feature maps (YOLOLiteHIP.features); neckops.neck_for picks
 DetectNeck (csrc/yl_neck.hip) for YOLOLiteMS_CPU, DetectNeckMS (csrc/yl_dneck.hip, dense 3x3 + SiLU) for YOLOLiteMS,
 e.g. --synthetic yololite_n -- which starts from the checkpoint's `lateral*.` / `smooth*.` entries; its parameters join
 the heads' in the one FusedTrainStep, and its state_dict is merged into the output as well.
+
+--amp fp16 | bf16 (with --train-neck and a YOLOLiteMS model; the reference's AMP, tools/train.py:284-357): DetectNeckMS runs
+its three 3x3 GEMMs in that precision (operands rounded, fp32 accumulation; parameters and gradients stay fp32).  With
+fp16 the loss is multiplied by FusedTrainStep's loss scale before backward() and the step unscales, skips a step whose
+gradients are not finite and updates the scale, all on the device; with bf16 the scale is fixed at 1.  The heads, the
+laterals and the loss stay fp32.
 """
 import argparse
 import copy
@@ -107,10 +113,14 @@ def main():
     ap.add_argument("--optimizer", default="adamw", choices=("adamw", "adam", "sgd"))
     ap.add_argument("--grad-clip", type=float, default=10.0)
     ap.add_argument("--train-neck", action="store_true", help="train the FPN neck (laterals, smooth blocks) as well")
+    ap.add_argument("--amp", default="", choices=("", "fp16", "bf16"),
+                    help="with --train-neck, YOLOLiteMS models: the dense neck's 3x3 GEMMs in this precision")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     if bool(a.synthetic) == bool(a.weights):
         raise SystemExit("give either --weights (with --data) or --synthetic NAME")
+    if a.amp and not a.train_neck:
+        raise SystemExit("--amp sets the precision of the trainable dense neck: it needs --train-neck")
     if a.synthetic:
         meta = zoo_meta(a.synthetic, num_classes=a.num_classes or 3, img_size=a.img_size or 128)
         sd = synth_state_dict(meta, seed=1)
@@ -132,17 +142,19 @@ def main():
         heads = ya.DetectHeads.from_meta(meta, num_classes=nc)
         print(f"[finetune_heads] {old_nc} -> {nc} classes: heads freshly initialised")
     heads.to(a.device).train()
-    neck = ya.neck_for(meta, sd).to(a.device).train() if a.train_neck else None
+    # DetectNeck (arch YOLOLiteMS_CPU) refuses a reduced precision and says why
+    neck = ya.neck_for(meta, sd, precision=a.amp or "fp32").to(a.device).train() if a.train_neck else None
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
-    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp=False, lr=a.lr)
+    # fp16: dynamic loss scale (unscale, found-inf skip, growth / backoff in the step); bf16 has fp32's range: scale 1
+    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp=a.amp == "fp16", lr=a.lr)
 
     def step(x, targets):
         # frozen trunk: plain tensors, nothing to backpropagate into
         feats = model.pyramid(x) if neck is None else neck(model.features(x), layout="nhwc")
         fts.zero_grad()
         loss, parts = crit(heads(feats, layout="nhwc"), targets)
-        loss.backward()
+        fts.scale(loss).backward()                         # the identity unless --amp fp16
         norm = fts.step()
         return float(loss), parts, float(norm)
 

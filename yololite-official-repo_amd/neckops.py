@@ -3,7 +3,9 @@ reference's two architectures, with a backward pass.
 
     DetectNeck      arch YOLOLiteMS_CPU: smooth block = depthwise 3x3 -> 1x1 -> BatchNorm -> ReLU   (csrc/yl_neck.hip)
     DetectNeckMS    arch YOLOLiteMS (the default arch): dense 3x3 -> BatchNorm -> SiLU              (csrc/yl_dneck.hip)
-    neck_for(meta, sd=None)     the right class's instance for a model's meta (from_state_dict with `sd`, else from_meta)
+    neck_for(meta, sd=None, precision="fp32")   the right class's instance for a model's meta (from_state_dict with `sd`,
+                                                else from_meta)
+    conv3x3(x, w_or_dz, pass_, precision)       one 3x3 GEMM of DetectNeckMS on its own (yl_dneck_conv3x3)
 
     neck = DetectNeck(in_channels, fpn_channels, depth)          # or .from_meta(meta) / .from_state_dict(meta, sd)
     ps = neck(model.features(x))                                 # NHWC [B,S,S,F] per level, finest first
@@ -24,6 +26,13 @@ DetectNeckMS is the same module around the other block (model_v2.py:15-22 conv_b
 `lateral{k}.weight/bias`, `smooth{k}.{3i}.weight` [F,F,3,3] and `smooth{k}.{3i+1}.weight/bias/running_mean/running_var/
 num_batches_tracked` (conv_block is a plain nn.Sequential: no `.block.` level), one autograd.Function over
 yl_dneck_forward / yl_dneck_backward.  The 3x3 convolution runs forward, input gradient and weight gradient on fp32 MFMA.
+
+Mixed precision (the reference's AMP, tools/train.py:284-357): DetectNeckMS(..., precision="fp16" | "bf16"), or
+`neck.precision = ...` at any time, runs the three 3x3 GEMMs with both operands rounded to that type (nearest even) and fp32
+accumulation on 16-bit MFMA; everything else, the parameters and every returned gradient stay fp32.  Nothing is clamped:
+an operand beyond fp16's range becomes inf and the gradients are not finite, which is what FusedTrainStep's found-inf /
+loss-scale logic looks for.  A backward runs in the precision of the forward it belongs to.  DetectNeck refuses it: the
+depthwise neck has no dense 3x3 GEMM, and its 1x1 is the heads' fp32 GEMM.
 """
 from __future__ import annotations
 
@@ -36,6 +45,15 @@ from torch import nn
 
 from . import _lib
 from . import _trainmod as tm
+
+
+PRECISIONS = {"fp32": 0, "fp16": _lib.YL_DNECK_F16, "bf16": _lib.YL_DNECK_BF16}    # -> yl_dneck_forward's flag bits
+
+
+def _check_precision(precision) -> str:
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
+    return precision
 
 
 def _check_dims(in_channels, F, depth):
@@ -103,6 +121,7 @@ class _Handle(tm.DeviceHandle):
     def __init__(self, in_channels, F: int, depth: int):
         super().__init__("yl_neck", _cfg, tuple(in_channels), F, depth)
         self.F, self.depth, self.L = F, depth, len(in_channels)
+        self.mode_bits = 0
 
     @property
     def per_level(self) -> int:
@@ -127,6 +146,7 @@ class _HandleMS(tm.DeviceHandle):
     def __init__(self, in_channels, F: int, depth: int):
         super().__init__("yl_dneck", _cfg, tuple(in_channels), F, depth)
         self.F, self.depth, self.L = F, depth, len(in_channels)
+        self.mode_bits = 0                                 # YL_DNECK_F16 / YL_DNECK_BF16 of the next forward
 
     @property
     def per_level(self) -> int:
@@ -166,8 +186,8 @@ class _NeckFunction(torch.autograd.Function):
         dev = cs[0].device
         ps = tm.detached_params(hd.who, params, dev)
         outs = [torch.empty((B, S, S, hd.F), device=dev, dtype=torch.float32) for S in sizes]
-        hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), _ptrs(cd), B, (C.c_int32 * L)(*sizes), tm.flags(train, save),
-                  _ptrs(outs))
+        hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), _ptrs(cd), B, (C.c_int32 * L)(*sizes),
+                  tm.flags(train, save) | hd.mode_bits, _ptrs(outs))
         if save:
             fctx.save_for_backward(*cd, *params)
             fctx.hd, fctx.bufs, fctx.generation, fctx.shape = hd, bufs, hd.generation, (B, sizes)
@@ -208,9 +228,10 @@ class _NeckBase(nn.Module):
     name, block)."""
 
     def __init__(self, in_channels: Sequence[int], fpn_channels: int, depth: int = 1,
-                 level_names: Sequence[str] = ("p3", "p4", "p5")):
+                 level_names: Sequence[str] = ("p3", "p4", "p5"), precision: str = "fp32"):
         super().__init__()
         in_channels = _check_dims(in_channels, fpn_channels, depth)
+        self._check_precision(precision)
         self.level_names = tuple(level_names)
         if len(self.level_names) != len(in_channels):
             raise ValueError(f"{len(self.level_names)} levels but in_channels {in_channels}")
@@ -225,26 +246,41 @@ class _NeckBase(nn.Module):
         for n, ci in rest:
             setattr(self, "smooth" + n[1:], self._smooth(F, self.depth))
         self._handle = self._handle_cls(in_channels, F, self.depth)
+        self.precision = precision
 
     @classmethod
-    def from_meta(cls, meta: dict):
+    def _check_precision(cls, precision) -> str:
+        """the operand types this neck's GEMMs run in: a subclass without a reduced mode refuses the others"""
+        return _check_precision(precision)
+
+    @property
+    def precision(self) -> str:
+        """"fp32", "fp16" or "bf16": the operand type of the 3x3 GEMMs of the next forward (and of its backward)"""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str):
+        self._precision = self._check_precision(value)
+
+    @classmethod
+    def from_meta(cls, meta: dict, precision: str = "fp32"):
         """a freshly initialised neck of the model `meta` describes; the input channels are those of the feature maps of
         the program build_program makes for it"""
         from .program import build_program, synth_state_dict
         F, d, names = cls._meta_dims(meta)
         prog = build_program(meta, synth_state_dict(meta))
         cin = [int(prog.slots[prog.feature_slots["c" + n[1:]]][2]) for n in names]
-        return cls(cin, F, d, level_names=names)
+        return cls(cin, F, d, level_names=names, precision=precision)
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict):
+    def from_state_dict(cls, meta: dict, sd: dict, precision: str = "fp32"):
         """the neck of a checkpoint: built from its meta, filled with its `lateral*.` / `smooth*.` entries"""
         F, d, names = cls._meta_dims(meta)
         missing = [f"lateral{n[1:]}.weight" for n in names if f"lateral{n[1:]}.weight" not in sd]
         if missing:
             raise KeyError(f"checkpoint lacks neck entries: {missing[:4]}")
         cin = [int(np.shape(sd[f"lateral{n[1:]}.weight"])[1]) for n in names]
-        return tm.fill_from_state_dict(cls(cin, F, d, level_names=names), sd, "neck")
+        return tm.fill_from_state_dict(cls(cin, F, d, level_names=names, precision=precision), sd, "neck")
 
     def _stat_buffers(self):
         out = []
@@ -274,6 +310,7 @@ class _NeckBase(nn.Module):
         if any(p.device != xs[0].device for p in params):
             raise _lib.YoloLiteHipError(f"{self._who}: parameters and inputs must live on one HIP device")
         self._handle.ensure(xs[0].device)
+        self._handle.mode_bits = PRECISIONS[self._precision]
         xs = [f.float().contiguous() for f in xs]          # autograd carries the gradient back through cast and copy
         return list(_NeckFunction.apply(self._handle, self._stat_buffers(), self.training, torch.is_grad_enabled(), *xs, *params))
 
@@ -281,6 +318,14 @@ class _NeckBase(nn.Module):
 class DetectNeck(_NeckBase):
     """See the module docstring.  `in_channels`: the channels of the feature maps, finest level first."""
     _who, _handle_cls = "DetectNeck", _Handle
+
+    @classmethod
+    def _check_precision(cls, precision) -> str:
+        if _check_precision(precision) != "fp32":
+            raise _lib.YoloLiteHipError(f"DetectNeck: precision {precision!r} is not implemented: the depthwise neck has no dense "
+                                        "3x3 GEMM to run on 16-bit MFMA (its 3x3 is depthwise, its 1x1 is the heads' fp32 "
+                                        "GEMM); only DetectNeckMS has the reduced modes")
+        return precision
 
     @staticmethod
     def _smooth(F: int, depth: int) -> nn.Module:
@@ -374,9 +419,47 @@ def plan_ms(in_channels: Sequence[int], fpn_channels: int, depth: int, batch: in
             "workspace_bytes": int(out.workspace_bytes), "table_bytes": int(out.table_bytes)}
 
 
-def neck_for(meta: dict, sd: Optional[dict] = None):
+def neck_for(meta: dict, sd: Optional[dict] = None, precision: str = "fp32"):
     """the trainable neck of the model `meta` describes: DetectNeck for arch YOLOLiteMS_CPU, DetectNeckMS for YOLOLiteMS
-    (and a meta without `arch`); filled from the checkpoint `sd` if that is given, freshly initialised otherwise"""
+    (and a meta without `arch`); filled from the checkpoint `sd` if that is given, freshly initialised otherwise.
+    `precision`: DetectNeckMS's operand type; DetectNeck refuses anything but "fp32"."""
     mcfg = (meta.get("config", {}) or {}).get("model", {}) or {}
     cls = DetectNeck if _meta_arch(meta, mcfg) == "yololitems_cpu" else DetectNeckMS
-    return cls.from_state_dict(meta, sd) if sd is not None else cls.from_meta(meta)
+    return cls.from_state_dict(meta, sd, precision) if sd is not None else cls.from_meta(meta, precision)
+
+
+PASSES = {"forward": _lib.YL_DNECK_PASS_FORWARD, "dgrad": _lib.YL_DNECK_PASS_DGRAD, "wgrad": _lib.YL_DNECK_PASS_WGRAD}
+
+
+def conv3x3(x_nhwc: torch.Tensor, w_or_dz: torch.Tensor, pass_: str, precision: str = "fp32",
+            neck: Optional[DetectNeckMS] = None) -> torch.Tensor:
+    """One 3x3 GEMM of DetectNeckMS on its own (yl_dneck_conv3x3: pack + convolution, or partials + ordered sum, launched as
+    the module launches them), fp32 tensors on one HIP device:
+        "forward":  x  [B,S,S,F], W  [F,F,3,3] -> z  [B,S,S,F]      (pad 1, stride 1, no bias)
+        "dgrad":    dz [B,S,S,F], W  [F,F,3,3] -> dx [B,S,S,F]      the gradient of forward's x
+        "wgrad":    x  [B,S,S,F], dz [B,S,S,F] -> dW [F,F,3,3]      the gradient of forward's W
+    `precision`: both operands are rounded to it (nearest even), fp32 accumulation.  `neck`: a DetectNeckMS of F channels
+    whose handle (and workspace) is used (if the workspace has to grow for it, a forward that neck holds for backward is
+    dropped and that backward raises); without one a handle is made for the call."""
+    if pass_ not in PASSES:
+        raise ValueError(f"pass_ must be one of {sorted(PASSES)}, got {pass_!r}")
+    _check_precision(precision)
+    if not (torch.is_tensor(x_nhwc) and x_nhwc.dim() == 4 and x_nhwc.shape[1] == x_nhwc.shape[2]):
+        raise ValueError("the first operand must be [B,S,S,F]")
+    B, S, _, F = (int(v) for v in x_nhwc.shape)
+    want = (B, S, S, F) if pass_ == "wgrad" else (F, F, 3, 3)
+    if not torch.is_tensor(w_or_dz) or tuple(w_or_dz.shape) != want:
+        raise ValueError(f"the second operand of {pass_!r} must be {want}")
+    if not x_nhwc.is_cuda or w_or_dz.device != x_nhwc.device:
+        raise _lib.YoloLiteHipError("conv3x3 needs both operands on one HIP device (no CPU fallback)")
+    if neck is not None and (not isinstance(neck, DetectNeckMS) or neck.fpn_channels != F):
+        raise ValueError(f"`neck` must be a DetectNeckMS of {F} channels")
+    hd = neck._handle if neck is not None else _HandleMS(_check_dims((F,), F, 1), F, 1)
+    hd.ensure(x_nhwc.device)
+    a = tm.aligned(x_nhwc.detach().float().contiguous())
+    b = tm.aligned(w_or_dz.detach().float().contiguous())
+    out = torch.empty((F, F, 3, 3) if pass_ == "wgrad" else (B, S, S, F), device=a.device, dtype=torch.float32)
+    n = C.c_int32()
+    hd.call("conv3x3", PASSES[pass_], PRECISIONS[precision], a.data_ptr(), b.data_ptr(), out.data_ptr(), B, S,
+            torch.cuda.current_stream(a.device).cuda_stream, C.byref(n))
+    return out
