@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define YL_ABI_VERSION 5
+#define YL_ABI_VERSION 6
 #define YL_MAX_LEVELS 8
 
 typedef struct yl_ctx yl_ctx;
@@ -703,17 +703,36 @@ yl_status yl_train_write_state(yl_train* t, float scale, int32_t growth_tracker,
  * [B, A, S, S, 5 + C] (anchor-major channels).  A yl_head handle needs no yl_ctx and holds no parameter: every call
  * reads the caller's tensors in PyTorch layout (fp32, contiguous, any 4-byte boundary), so an optimizer may update them
  * in place between two calls.  The input x is NHWC [B, S, S, F], 16-byte aligned; F a multiple of 4 (anything else,
- * and num_masks != 0: YL_ERR_UNSUPPORTED).  fp32 storage and arithmetic; the GEMMs run on v_mfma_f32_16x16x4_f32.
+ * and num_masks != 0: YL_ERR_UNSUPPORTED).  fp32 storage and arithmetic; the GEMMs run on v_mfma_f32_16x16x4_f32
+ * (or, see "Mixed precision" below, on the 16-bit MFMA).
  * BatchNorm: YL_HEAD_TRAIN normalises with the batch statistics (biased variance, eps 1e-5), updates running_mean /
  * running_var in place (momentum 0.1, unbiased variance) and adds 1 to num_batches_tracked; without it the running
  * statistics are used and nothing is updated.  YL_HEAD_SAVE keeps d, z, h of every block and the statistics in the
  * handle for ONE later yl_head_backward of the same (batch, size); a forward without it drops what is held, runs
  * every block in one block's buffers and allocates no more than those (saved_bytes / head_depth).
  * Deterministic: every sum over rows is written as per-tile partials and summed in tile order in float64 by a second
- * kernel; no floating-point atomics; equal inputs give equal bits. */
+ * kernel; no floating-point atomics; equal inputs give equal bits.
+ *
+ * Mixed precision.  YL_HEAD_F16 / YL_HEAD_BF16 in the forward's flags (exclusive: both set is YL_ERR_INVALID, checked
+ * before anything is enqueued or a held forward is dropped) run every 1x1 GEMM of the head -- per block z = d . W1^T,
+ * dd = dz . W1, dW1 = dz^T . d; for the outputs y = h . Wout^T, dh = gy . Wout, dWout = gy^T . h -- with BOTH operands
+ * rounded to that type, round to nearest even, on v_mfma_f32_16x16x16_{f16,bf16}: products exact, accumulation in fp32.
+ * The rounding happens in registers, on the four values a lane has loaded; a value outside the matrices stays the zero
+ * it was filled with.  Nothing is clamped: a finite fp32 value beyond fp16's range becomes +-inf and the gradients it
+ * reaches are not finite.  Everything else (depthwise 3x3 and its gradients, BatchNorm statistics, BN + ReLU and their
+ * backward, the bias added to y, the float64 column sum of the unrounded gy, the partials and their ordered float64 sum,
+ * the saved d / z / h, parameters, gradients) is fp32 as without the bits; the launch counts and yl_head_plan's figures
+ * are the same, and equal inputs give equal bits.  The handle records the mode with the held forward: yl_head_backward
+ * runs in the mode of the forward it belongs to. */
 #define YL_HEAD_MAX_DEPTH 4
 #define YL_HEAD_TRAIN 1u
 #define YL_HEAD_SAVE 2u
+#define YL_HEAD_F16 0x100u
+#define YL_HEAD_BF16 0x200u
+#define YL_HEAD_SITE_OUT (-1)       /* yl_head_gemm's site: the output convolutions; 0 .. head_depth - 1: that trunk block's 1x1 */
+#define YL_HEAD_PASS_FORWARD 0      /* block t: a = d  [B][S][S][F] -> out = z  [B][S][S][F];  outputs: a = h -> out = y (level tensor) */
+#define YL_HEAD_PASS_DGRAD 1        /* block t: a = dz [B][S][S][F] -> out = dd [B][S][S][F];  outputs: a = gy (level tensor) -> out = dh */
+#define YL_HEAD_PASS_WGRAD 2        /* block t: a = d, b = dz -> out = dW1 [F][F];  outputs: a = h, b = gy -> out = [4A + A + A C][F] */
 typedef struct yl_head yl_head;
 typedef struct yl_head_cfg {
   int32_t channels;       /* F = fpn_channels */
@@ -768,6 +787,17 @@ yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_h
 /* What the handle holds now (a host function; any out pointer may be NULL): the bytes of its two device buffers and
  * whether a forward is held for yl_head_backward. */
 yl_status yl_head_held(const yl_head* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+/* One 1x1 GEMM of the head on its own, launched exactly as the module launches it: `site` is a trunk block or
+ * YL_HEAD_SITE_OUT, `pass` a YL_HEAD_PASS_*, `mode` 0 (fp32), YL_HEAD_F16 or YL_HEAD_BF16 (anything else:
+ * YL_ERR_INVALID, checked first).  The weights (and, for the outputs' forward, the biases) are read from `params`, a
+ * whole parameter table, through the accessors the module uses; b_dev is read by WGRAD only.  FORWARD and DGRAD: 1
+ * launch; WGRAD: 2 launches (partials, cut as yl_head_plan cuts this batch and size, and their ordered float64 sum).  The
+ * outputs' WGRAD writes the rows of box_w, obj_w and cls_w one after the other.  [B][S][S][F] operands and results of
+ * FORWARD and DGRAD are 16-byte aligned (else YL_ERR_UNSUPPORTED); the level tensor and WGRAD's operands and result
+ * need 4 bytes.  Uses the handle's workspace; if that has to grow, a held forward is dropped as any growth drops it. */
+yl_status yl_head_gemm(yl_head* h, int32_t site, int32_t pass, uint32_t mode, const yl_head_tensors* params,
+                       const float* a_dev, const float* b_dev, float* out_dev, int32_t batch, int32_t size, void* stream,
+                       int32_t* launches);
 
 /* ---- trainable depthwise FPN neck (reference scripts/model/model_v2.py:285-294, :337-361, YOLOLiteMS_CPU) -------------
  * Forward and backward of the whole top-down neck on the device.  Levels go finest first (p3, p4, p5; with use_p2: p2

@@ -1,0 +1,253 @@
+"""The six 1x1 GEMMs of DetectHeads in precision "fp16" / "bf16" (yololite_amd.headops.head_gemm over yl_head_gemm,
+yl_head_gemm_kernel of csrc/yl_block.h) on given operands, against the float64 product of the RNE-rounded operands.
+
+The operands are given, so no rounding can flip: the bar is the project's rule, max(4 x e32, 2 fp32 ulps at the tensor's
+maximum), e32 = the error of torch's fp32 CPU product of the same rounded operands.  Every case also holds the UNROUNDED
+float64 result outside that bar: a kernel that forgets a rounding cannot pass.  The worst error / bar of every (case,
+precision) is written to profiles/head_amp_parity.json under "op"."""
+import ctypes as C
+import functools
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import yololite_amd as ya
+from yololite_amd import _lib, headops
+from _head_amp_cases import (BY_NAME, PASSES, PRECISIONS, SITES, cat_rows, gemm_pass, level_weights, op_reference, reference,
+                             rounded, split_rows, tie_operands)
+from _head_cases import CASES, case_inputs
+from _head_dev import heads_of
+from _train_dev import DEV
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PARITY = os.path.join(ROOT, "profiles", "head_amp_parity.json")
+YL_ERR_INVALID = -1                                        # include/yololite_hip.h, yl_status
+
+
+@functools.lru_cache(maxsize=None)
+def _heads(name):
+    """one module per case with the case's weights, shared; the tests that write weights make their own"""
+    case = BY_NAME[name]
+    return heads_of(case, case_inputs(case))
+
+
+def _one(case, got, site, pass_):
+    """head_gemm's result in the reference's form (the outputs' weight gradient as ONE matrix, level channel order)"""
+    if site == "out" and pass_ == "wgrad":
+        return cat_rows(*[g.cpu() for g in got], case["A"], case["C"]).reshape(-1, case["F"])
+    return got.cpu()
+
+
+def _dev(heads, case, li, site, pass_, a, b, precision):
+    got = headops.head_gemm(heads, li, site, pass_, a.to(DEV), None if b is None else b.to(DEV), precision=precision)
+    return _one(case, got, site, pass_)
+
+
+def _record(section, key, value):
+    try:                                                   # the figures of this run, beside the others' (best effort)
+        table = json.load(open(PARITY)) if os.path.exists(PARITY) else {}
+        table.setdefault(section, {})[key] = value
+        with open(PARITY, "w") as f:
+            json.dump(table, f, indent=1, sort_keys=True)
+            f.write("\n")
+    except OSError:
+        pass
+
+
+def _cells(case):
+    return [(li, site, pass_) for li in range(len(case["sizes"])) for site in SITES for pass_ in PASSES]
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_op_parity_with_the_rounded_operand_reference(case, precision):
+    heads = _heads(case["name"])
+    bad, worst = [], (0.0, "")
+    for li, site, pass_ in _cells(case):
+        ref = op_reference(case["name"], li, site, pass_, precision)
+        got = _dev(heads, case, li, site, pass_, ref["a"], ref["b"], precision)
+        assert got.shape == ref["r64"].shape and got.dtype == torch.float32, (li, site, pass_, got.shape)
+        err = float((got.double() - ref["r64"]).abs().max())
+        miss = float((ref["unrounded"] - ref["r64"]).abs().max())
+        print(f"{case['name']:5s} {precision} L{li} {site!s:3s} {pass_:8s} err {err:.3e}  bar {ref['bar']:.3e}  "
+              f"ratio {err / ref['bar']:.3f}  unrounded {miss / ref['bar']:.1f} bars away")
+        worst = max(worst, (round(err / ref["bar"], 4), f"L{li}/{site}/{pass_}"))
+        assert miss > ref["bar"], (li, site, pass_, "the case cannot see a missing rounding: take the next seed")
+        if not err <= ref["bar"]:
+            bad.append((li, site, pass_, err, ref["bar"]))
+        again = _dev(heads, case, li, site, pass_, ref["a"], ref["b"], precision)
+        assert torch.equal(got, again), (li, site, pass_, "two calls differ")
+    _record("op", f"{case['name']}/{precision}", {"worst_ratio": worst[0], "at": worst[1]})
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_fp32_precision_is_the_unrounded_product(precision):
+    """the same entry in "fp32" sums the operands as they are: inside the bar of the UNROUNDED reference, and outside the
+    rounded one's (the modes are told apart from both sides)"""
+    case = BY_NAME["a2c1"]
+    heads = _heads("a2c1")
+    for li, site, pass_ in _cells(case):
+        ref = op_reference("a2c1", li, site, pass_, precision)
+        got = _dev(heads, case, li, site, pass_, ref["a"], ref["b"], "fp32").double()
+        w = level_weights(case, li)
+        r32 = gemm_pass(site, pass_, ref["a"], ref["b"], w["Wout"] if site == "out" else w["W1"], w["bout"], case["A"]).double()
+        b = max(4.0 * float((r32 - ref["unrounded"]).abs().max()),
+                2.0 * float(np.spacing(np.float32(ref["unrounded"].abs().max()))))
+        assert float((got - ref["unrounded"]).abs().max()) <= b, (li, site, pass_)
+        assert float((got - ref["r64"]).abs().max()) > ref["bar"], (li, site, pass_)
+
+
+def _with_weights(case, li, W, bias, site):
+    """a module of its own whose level `li` has the 1x1 weight of block 0 (site 0) or the outputs' weights and biases
+    (site "out") replaced"""
+    heads = heads_of(case, case_inputs(case))
+    head = getattr(heads, "head%d" % (3 + li))
+    F = case["F"]
+    with torch.no_grad():
+        if site == "out":
+            for n, w, b in zip(("box", "obj", "cls"), split_rows(W, case["A"], case["C"]), split_rows(bias, case["A"], case["C"])):
+                head["out"][n].weight.copy_(w.reshape(-1, F, 1, 1))
+                head["out"][n].bias.copy_(b)
+        else:
+            head["trunk"][0].block[1].weight.copy_(W.reshape(F, F, 1, 1))
+    return heads
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_ties_round_to_even_bit_for_bit(precision):
+    """1 + 2^-11 and 1 + 3 2^-11 (fp16; 2^-8 for bf16) against small integers: RNE gives 1 and 1 + 4 eps, every product
+    and sum is exact in fp32, so the device must give the exact value"""
+    case, li = BY_NAME["a2c1"], 0
+    for site in SITES:
+        for pass_ in PASSES:
+            a, b, W, bias = tie_operands(case, li, site, pass_, precision)
+            heads = _with_weights(case, li, W, bias, site)
+            d = lambda t: None if t is None else t.double()     # noqa: E731
+            exact = gemm_pass(site, pass_, rounded(a, precision).double(), d(b), W.double(), bias.double(), case["A"])
+            assert torch.equal(exact.float().double(), exact)   # representable: the sums are exact in fp32
+            got = _dev(heads, case, li, site, pass_, a, b, precision)
+            assert torch.equal(got, exact.float()), (site, pass_, float((got.double() - exact).abs().max()))
+            away = gemm_pass(site, pass_, a.double(), d(b), W.double(), bias.double(), case["A"])
+            assert not torch.equal(away, exact)                 # what no rounding at all would give
+
+
+def test_an_operand_beyond_fp16_overflows_to_inf_and_bf16_holds_it():
+    """the outputs' weight-gradient pass, gy with one entry 1e5: RNE to fp16 is +inf, nothing is clamped, and that output
+    row of dWout is not finite (what FusedTrainStep's found-inf looks for) while every other row is; bf16 has fp32's range
+    and stays inside its bar"""
+    case, li = BY_NAME["a2c1"], 0
+    heads = _heads("a2c1")
+    ref = op_reference("a2c1", li, "out", "wgrad", "bf16")
+    h, gy = ref["a"], ref["b"].clone()
+    anchor, e = 1, 3
+    gy[1, anchor, 2, 3, e] = 1e5
+    n = anchor * (5 + case["C"]) + e
+    got = _dev(heads, case, li, "out", "wgrad", h, gy, "fp16")
+    assert not torch.isfinite(got[n]).any(), "the overflowing row must not be finite anywhere"
+    assert torch.isfinite(torch.cat([got[:n], got[n + 1:]])).all()
+    r = reference(case, li, "out", "wgrad", h, gy, "bf16")
+    got = _dev(heads, case, li, "out", "wgrad", h, gy, "bf16")
+    assert torch.isfinite(got).all()
+    err = float((got.double() - r["r64"]).abs().max())
+    print(f"bf16 with 1e5: err {err:.3e} bar {r['bar']:.3e}")
+    assert err <= r["bar"], (err, r["bar"])
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_image_0_does_not_change_by_a_bit_when_image_1_does(precision):
+    """1152 rows in eighteen 64-row workgroups, image 1 from row 576 on: its rows are other q indices of the same launch"""
+    case = BY_NAME["rows"]
+    heads = _heads("rows")
+    for site in SITES:
+        for pass_ in ("forward", "dgrad"):
+            ref = op_reference("rows", 0, site, pass_, precision)
+            a2 = ref["a"].clone()
+            a2[1] = 100.0 * torch.randn(a2[1].shape, generator=torch.Generator().manual_seed(5))
+            one = _dev(heads, case, 0, site, pass_, ref["a"], None, precision)
+            two = _dev(heads, case, 0, site, pass_, a2, None, precision)
+            assert torch.equal(one[0], two[0]), (site, pass_)
+            assert not torch.equal(one[1], two[1]), (site, pass_)
+
+
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_unaligned_parameter_storage_gives_the_bits_of_the_aligned_one(precision):
+    """every weight of the level as a view that starts 4 bytes into a 16-byte aligned buffer"""
+    case, li = BY_NAME["a2c1"], 1
+    aligned = _heads("a2c1")
+    shifted = heads_of(case, case_inputs(case))
+    for p in getattr(shifted, "head%d" % (3 + li)).parameters():
+        buf = torch.empty(p.numel() + 5, device=p.device, dtype=torch.float32)
+        o = 1 + (-(buf.data_ptr() // 4) % 4)               # the first element 4 bytes past a 16-byte boundary
+        view = buf[o:o + p.numel()].view(p.shape)
+        view.copy_(p.data)
+        p.data = view
+        assert p.data_ptr() % 16 == 4
+    for site in SITES:
+        for pass_ in PASSES:
+            ref = op_reference("a2c1", li, site, pass_, precision)
+            one = _dev(aligned, case, li, site, pass_, ref["a"], ref["b"], precision)
+            two = _dev(shifted, case, li, site, pass_, ref["a"], ref["b"], precision)
+            assert torch.equal(one, two), (site, pass_)
+
+
+def test_both_precision_bits_are_refused_and_a_held_forward_stays_held():
+    case = BY_NAME["base"]
+    inputs = case_inputs(case)
+    heads = heads_of(case, inputs)
+    xs = [torch.from_numpy(lv["x"]).to(DEV).requires_grad_(True) for lv in inputs]
+    ys = heads(xs, layout="nhwc")                          # a forward with a graph: every level holds it
+    assert all(h["forward_held"] == 1 for h in heads.held())
+    lv, head = heads._levels[0], heads.head3
+    ps = [p.detach() for p in lv.params(head)]
+    table = lv.table(ps, lv.buffers(head))
+    B, S = case["B"], case["sizes"][0]
+    both = _lib.YL_HEAD_F16 | _lib.YL_HEAD_BF16
+    x = xs[0].detach()
+    y = torch.empty_like(ys[0])
+    n = C.c_int32()
+    st = lv.lib.yl_head_forward(lv.handle, C.byref(table), x.data_ptr(), B, S, _lib.YL_HEAD_TRAIN | _lib.YL_HEAD_SAVE | both,
+                                y.data_ptr(), None, C.byref(n))
+    assert st == YL_ERR_INVALID
+    z = torch.empty_like(x)
+    for mode in (both, 0x400, 1):
+        st = lv.lib.yl_head_gemm(lv.handle, 0, _lib.YL_HEAD_PASS_FORWARD, mode, C.byref(table), x.data_ptr(), None,
+                                 z.data_ptr(), B, S, None, C.byref(n))
+        assert st == YL_ERR_INVALID, mode
+    assert heads.held()[0]["forward_held"] == 1
+    torch.autograd.backward(ys, [torch.from_numpy(v["gy"]).to(DEV) for v in inputs])     # and its backward still runs
+    assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in heads.parameters())
+
+
+def test_head_gemm_refuses_what_it_cannot_run():
+    case = BY_NAME["base"]
+    heads = _heads("base")
+    B, S, F, E = case["B"], case["sizes"][0], case["F"], 5 + case["C"]
+    x = torch.zeros((B, S, S, F), device=DEV)
+    gy = torch.zeros((B, case["A"], S, S, E), device=DEV)
+    with pytest.raises(ValueError, match="precision"):
+        headops.head_gemm(heads, 0, 0, "forward", x, precision="fp8")
+    with pytest.raises(ValueError, match="pass_"):
+        headops.head_gemm(heads, 0, 0, "backward", x)
+    with pytest.raises(ValueError, match="site"):
+        headops.head_gemm(heads, 0, case["depth"], "forward", x)
+    with pytest.raises(ValueError, match="site"):
+        headops.head_gemm(heads, 0, "box", "forward", x)
+    with pytest.raises(ValueError, match="level"):
+        headops.head_gemm(heads, 3, 0, "forward", x)
+    with pytest.raises(ValueError, match="first operand"):
+        headops.head_gemm(heads, 0, "out", "dgrad", x)
+    with pytest.raises(ValueError, match="second operand"):
+        headops.head_gemm(heads, 0, "out", "wgrad", x, x)
+    with pytest.raises(ValueError, match="second operand"):
+        headops.head_gemm(heads, 0, 0, "wgrad", x)
+    with pytest.raises(ValueError, match="one operand"):
+        headops.head_gemm(heads, 0, 0, "forward", x, x)
+    with pytest.raises(ya.YoloLiteHipError):
+        headops.head_gemm(heads, 0, 0, "forward", x.cpu())
+    assert headops.head_gemm(heads, 0, "out", "dgrad", gy).shape == x.shape       # precision=None: the heads' own (fp32)

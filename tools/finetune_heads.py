@@ -6,7 +6,7 @@
 
     python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
-                                   [--train-neck [--amp fp16|bf16]]
+                                   [--train-neck [--amp fp16|bf16]] [--amp-heads fp16|bf16]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
@@ -26,8 +26,11 @@ the heads' in the one FusedTrainStep, and its state_dict is merged into the outp
 --amp fp16 | bf16 (with --train-neck and a YOLOLiteMS model; the reference's AMP, tools/train.py:284-357): DetectNeckMS runs
 its three 3x3 GEMMs in that precision (operands rounded, fp32 accumulation; parameters and gradients stay fp32).  With
 fp16 the loss is multiplied by FusedTrainStep's loss scale before backward() and the step unscales, skips a step whose
-gradients are not finite and updates the scale, all on the device; with bf16 the scale is fixed at 1.  The heads, the
-laterals and the loss stay fp32.
+gradients are not finite and updates the scale, all on the device; with bf16 the scale is fixed at 1.  The laterals
+and the loss stay fp32.
+
+--amp-heads fp16 | bf16 (with or without --train-neck): DetectHeads runs every 1x1 GEMM of the heads in that precision, on
+the same terms.  The loss scale is on when either of --amp and --amp-heads is fp16.
 """
 import argparse
 import copy
@@ -115,6 +118,8 @@ def main():
     ap.add_argument("--train-neck", action="store_true", help="train the FPN neck (laterals, smooth blocks) as well")
     ap.add_argument("--amp", default="", choices=("", "fp16", "bf16"),
                     help="with --train-neck, YOLOLiteMS models: the dense neck's 3x3 GEMMs in this precision")
+    ap.add_argument("--amp-heads", default="", choices=("", "fp16", "bf16"),
+                    help="the heads' 1x1 GEMMs in this precision (independent of --train-neck)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     if bool(a.synthetic) == bool(a.weights):
@@ -137,9 +142,9 @@ def main():
     model.load_state_dict(sd)
     model.to(a.device)
     if nc == old_nc:
-        heads = ya.DetectHeads.from_state_dict(meta, sd)
+        heads = ya.DetectHeads.from_state_dict(meta, sd, precision=a.amp_heads or "fp32")
     else:
-        heads = ya.DetectHeads.from_meta(meta, num_classes=nc)
+        heads = ya.DetectHeads.from_meta(meta, num_classes=nc, precision=a.amp_heads or "fp32")
         print(f"[finetune_heads] {old_nc} -> {nc} classes: heads freshly initialised")
     heads.to(a.device).train()
     # DetectNeck (arch YOLOLiteMS_CPU) refuses a reduced precision and says why
@@ -147,14 +152,14 @@ def main():
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
     # fp16: dynamic loss scale (unscale, found-inf skip, growth / backoff in the step); bf16 has fp32's range: scale 1
-    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp=a.amp == "fp16", lr=a.lr)
+    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp="fp16" in (a.amp, a.amp_heads), lr=a.lr)
 
     def step(x, targets):
         # frozen trunk: plain tensors, nothing to backpropagate into
         feats = model.pyramid(x) if neck is None else neck(model.features(x), layout="nhwc")
         fts.zero_grad()
         loss, parts = crit(heads(feats, layout="nhwc"), targets)
-        fts.scale(loss).backward()                         # the identity unless --amp fp16
+        fts.scale(loss).backward()                         # the identity unless --amp or --amp-heads is fp16
         norm = fts.step()
         return float(loss), parts, float(norm)
 

@@ -15,7 +15,13 @@ With --parity F the cases of tests/_head_cases.py are run and device error, bar 
 to F.  With --trace only --steps steps per side are run once (for `rocprofv3 --kernel-trace --stats -- python
 tools/head_train_time.py --trace ...`).
 
-    python tools/head_train_time.py [--models edge_n,yololite_m] [--blocks 7] [--steps 20] [--out F] [--parity F] [--trace]"""
+--precision fp16 | bf16: the device side is DetectHeads(precision=...), the torch side the same module under
+torch.autocast of that dtype (its parameters stay fp32, as the reference trains); the line names the mode on both sides.
+The gradient errors are against the unrounded float64 module in every mode: in a reduced one they show the rounding.
+
+    python tools/head_train_time.py [--models edge_n,yololite_m] [--blocks 7] [--steps 20] [--out F] [--parity F] [--trace]
+                                    [--precision fp32|fp16|bf16]"""
+import contextlib
 import json
 import os
 import sys
@@ -29,6 +35,27 @@ from tools import _train_time as tt  # noqa: E402
 
 SHAPES = {"edge_n": dict(F=96, depth=1, B=64, sizes=(80, 40, 20)), "yololite_m": dict(F=328, depth=2, B=32, sizes=(80, 40, 20))}
 NC, A = 80, 1
+PRECISIONS = ("fp32", "fp16", "bf16")
+
+
+def take_precision(argv):
+    """--precision P (or --precision=P) out of argv -> P; the rest of the command line is tools/_train_time.py's"""
+    p = "fp32"
+    for i, v in enumerate(argv):
+        if v == "--precision" and i + 1 < len(argv):
+            p = argv[i + 1]
+            del argv[i:i + 2]
+            break
+        if v.startswith("--precision="):
+            p = v.split("=", 1)[1]
+            del argv[i]
+            break
+    if p not in PRECISIONS:
+        raise SystemExit(f"--precision must be one of {PRECISIONS}, got {p!r}")
+    return p
+
+
+PRECISION = "fp32"
 
 
 def torch_heads(F, depth, nlevels):
@@ -67,7 +94,7 @@ def run_model(name, blocks, steps, trace):
     F, depth, B, sizes = sh["F"], sh["depth"], sh["B"], sh["sizes"]
     dev = "cuda:0"
     torch.manual_seed(3)
-    ours = ya.DetectHeads(F, NC, A, depth).to(dev).train()
+    ours = ya.DetectHeads(F, NC, A, depth, precision=PRECISION).to(dev).train()
     ref = torch_heads(F, depth, len(sizes)).to(dev).to(memory_format=torch.channels_last).train()
     ref.load_state_dict(ours.state_dict())
     gen = torch.Generator().manual_seed(5)
@@ -75,15 +102,22 @@ def run_model(name, blocks, steps, trace):
     feats_cl = [f.permute(0, 3, 1, 2) for f in feats]                                        # the same memory, NCHW shape
     gys = [(1e-3 * torch.randn(B, A, S, S, 5 + NC, generator=gen)).to(dev) for S in sizes]
 
+    cast = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(PRECISION)
+
     def step(m, x):
         for p in m.parameters():
             p.grad = None
-        torch.autograd.backward(m(x, layout="nhwc") if m is ours else m(x), gys)
+        if m is ours:
+            ys = m(x, layout="nhwc")
+        else:                                              # the level tensors come out in the autocast dtype: gys follow
+            with torch.autocast("cuda", dtype=cast) if cast else contextlib.nullcontext():
+                ys = m(x)
+        torch.autograd.backward(ys, gys if m is ours or not cast else [g.to(y.dtype) for g, y in zip(gys, ys)])
 
     plans = [headops.plan(F, NC, A, depth, B, S) for S in sizes]
     saved = sum(p["saved_bytes"] for p in plans)
     act = sum(4 * p["rows"] * F for p in plans)
-    res = {"model": name, "F": F, "head_depth": depth, "batch": B, "sizes": list(sizes), "steps_per_block": steps,
+    res = {"model": name, "device_precision": PRECISION, "torch_autocast": PRECISION if cast else "off", "F": F, "head_depth": depth, "batch": B, "sizes": list(sizes), "steps_per_block": steps,
            "saved_bytes": saved, "workspace_bytes": sum(p["workspace_bytes"] for p in plans),
            # activation-sized tensors (M x F fp32) read or written per block: forward 7 (depthwise 2, 1x1 2, statistics 1,
            # normalisation 2), backward 20 (dh 1, its two sums 3, dz 4, 1x1 weight gradient 2, dd 2, depthwise weight
@@ -140,4 +174,6 @@ def parity(path):
 
 
 if __name__ == "__main__":
-    tt.main("head_train_time.py", "edge_n,yololite_m", run_model, header={"num_classes": NC}, parity=parity)
+    PRECISION = take_precision(sys.argv)
+    tt.main("head_train_time.py", "edge_n,yololite_m", run_model, header={"num_classes": NC, "precision": PRECISION},
+            parity=parity)

@@ -38,7 +38,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # YOLOLITE_HIP_LIB selects another build of the same ABI (kernel A/B runs); default: the in-tree library
 LIB_PATH = os.environ.get("YOLOLITE_HIP_LIB") or os.path.join(_HERE, "libyololite_hip.so")
 
-YL_ABI_VERSION = 5
+YL_ABI_VERSION = 6
 YL_MAX_LEVELS = 8
 YL_OK = 0
 ACT = {"none": 0, "relu": 1, "relu6": 2, "silu": 3, "gelu": 4, "relu_lab": 5}
@@ -132,6 +132,9 @@ class yl_train_hyper(C.Structure):
 
 YL_HEAD_MAX_DEPTH = 4
 YL_HEAD_TRAIN, YL_HEAD_SAVE = 1, 2
+YL_HEAD_F16, YL_HEAD_BF16 = 0x100, 0x200                   # yl_head_forward's flags: the 1x1 GEMMs' operand type
+YL_HEAD_SITE_OUT = -1                                      # yl_head_gemm's site: the output convolutions (else a trunk block)
+YL_HEAD_PASS_FORWARD, YL_HEAD_PASS_DGRAD, YL_HEAD_PASS_WGRAD = 0, 1, 2
 YL_DNECK_F16, YL_DNECK_BF16 = 0x100, 0x200                 # yl_dneck_forward's flags: the 3x3 GEMMs' operand type
 YL_DNECK_PASS_FORWARD, YL_DNECK_PASS_DGRAD, YL_DNECK_PASS_WGRAD = 0, 1, 2
 
@@ -274,6 +277,8 @@ SYMBOLS = [
     ("yl_head_backward", C.c_int32, [_vp, C.POINTER(yl_head_tensors), C.POINTER(yl_head_tensors), _vp, _vp, _vp,
                                      C.c_int32, C.c_int32, _vp, _ip]),
     ("yl_head_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("yl_head_gemm", C.c_int32, [_vp, C.c_int32, C.c_int32, C.c_uint32, C.POINTER(yl_head_tensors), _vp, _vp, _vp,
+                                 C.c_int32, C.c_int32, _vp, _ip]),
     ("yl_neck_plan", C.c_int32, [C.POINTER(yl_neck_cfg), C.c_int32, _ip, C.POINTER(yl_neck_plan_info)]),
     ("yl_neck_nearest_map", C.c_int32, [C.c_int32, C.c_int32, _ip, _ip, _ip]),
     ("yl_neck_create", C.c_int32, [C.c_int32, C.POINTER(yl_neck_cfg), C.POINTER(_vp)]),

@@ -81,6 +81,17 @@ class DeviceHandle:
                                         f"({rule} is held at a time)")
 
 
+# the operand type of a module's GEMMs -> the precision bits of its forward's flags (YL_HEAD_F16 / _BF16 and
+# YL_DNECK_F16 / _BF16 are the same bits)
+PRECISIONS = {"fp32": 0, "fp16": _lib.YL_HEAD_F16, "bf16": _lib.YL_HEAD_BF16}
+
+
+def check_precision(precision) -> str:
+    if not isinstance(precision, str) or precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
+    return precision
+
+
 def dw_block(F: int, n: int) -> nn.Module:
     """Container only (the reference's DWConvBlock(F, F, n)): the layers hold the parameters; their forward is never called."""
     m = nn.Module()

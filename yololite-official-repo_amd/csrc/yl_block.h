@@ -26,6 +26,20 @@ constexpr double BN_EPS = 1e-5, BN_MOMENTUM = 0.1;
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
+// ---- the 16-bit MFMA operands: a lane's four k values as one 8-byte fragment (v_mfma_f32_16x16x16_f16 / _bf16, fp32
+// accumulation).  __builtin_convertvector from f32x4 rounds to nearest even; nothing is clamped.
+typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 b16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ f32x4 mfma16(h16x4 a, h16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma16(b16x4 a, b16x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
+}
+// the operand type of a GEMM, P: 0 fp32, 1 fp16, 2 bf16 (the handles' fMode; mode_of() reads it off a call's flags)
+template <int P> struct Frag16;
+template <> struct Frag16<1> { typedef h16x4 T; };
+template <> struct Frag16<2> { typedef b16x4 T; };
+
 // ---- level geometry: column n = a * E + e of the head output <-> level tensor [B, A, S, S, E], parameter rows
 struct HeadGeom { int A, E, C, SS, F; };
 __device__ __forceinline__ long head_y_off(const HeadGeom& g, int m, int n) {
@@ -156,7 +170,9 @@ struct OutPartial {                      // part[split][q][p]
 };
 
 // grid (ceil(NP / (16 PT)), ceil(NQ / 64), splits); r range of a split: [z * rsplit, min(NR, (z + 1) * rsplit))
-template <int PT, class PA, class QA, class CA>
+// P != 0: both fragments are rounded to the 16-bit type as load4 returns them (the zero fill stays zero) and the lane's
+// four r values, the k layout of v_mfma_f32_16x16x16_*, go through ONE MFMA per p-tile in the place of four; C/D is the same.
+template <int PT, class PA, class QA, class CA, int P>
 __global__ __launch_bounds__(NT) void yl_head_gemm_kernel(PA pa, QA qa, CA ca, int NP, int NQ, int NR, int rsplit) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, kq = lane >> 4, i = lane & 15;
   const int p0 = blockIdx.x * (16 * PT), q0 = blockIdx.y * GEMM_ROWS + wave * 16;
@@ -172,11 +188,18 @@ __global__ __launch_bounds__(NT) void yl_head_gemm_kernel(PA pa, QA qa, CA ca, i
     f32x4 pv[PT];
 #pragma unroll
     for (int pt = 0; pt < PT; ++pt) pv[pt] = pa.load4(p0 + 16 * pt + i, r, NP, rend);
+    if constexpr (P == 0) {
 #pragma unroll
-    for (int s = 0; s < 4; ++s)
+      for (int s = 0; s < 4; ++s)
 #pragma unroll
-      for (int pt = 0; pt < PT; ++pt)
-        acc[pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[pt], 0, 0, 0);
+        for (int pt = 0; pt < PT; ++pt)
+          acc[pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[pt], 0, 0, 0);
+    } else {
+      typedef typename Frag16<P>::T H;
+      const H qh = __builtin_convertvector(qv, H);
+#pragma unroll
+      for (int pt = 0; pt < PT; ++pt) acc[pt] = mfma16(__builtin_convertvector(pv[pt], H), qh, acc[pt]);
+    }
   }
 #pragma unroll
   for (int pt = 0; pt < PT; ++pt) ca.store(p0 + 16 * pt + 4 * kq, q0 + i, acc[pt], NP, NQ, blockIdx.z);
@@ -441,14 +464,30 @@ void split_plan(int M, int NP, int NQ, int* rows, int* splits) {
   *splits = ceil_div(M, *rows);
 }
 
-template <class PA, class QA, class CA>
+template <int P, class PA, class QA, class CA>
 void launch_gemm(hipStream_t s, PA pa, QA qa, CA ca, int NP, int NQ, int NR, int rsplit, int splits) {
   const int pt = pick_pt(NP);
   const dim3 grid(ceil_div(NP, 16 * pt), ceil_div(NQ, GEMM_ROWS), splits);
   if (pt == 6)
-    hipLaunchKernelGGL((yl_head_gemm_kernel<6, PA, QA, CA>), grid, dim3(NT), 0, s, pa, qa, ca, NP, NQ, NR, rsplit);
+    hipLaunchKernelGGL((yl_head_gemm_kernel<6, PA, QA, CA, P>), grid, dim3(NT), 0, s, pa, qa, ca, NP, NQ, NR, rsplit);
   else
-    hipLaunchKernelGGL((yl_head_gemm_kernel<4, PA, QA, CA>), grid, dim3(NT), 0, s, pa, qa, ca, NP, NQ, NR, rsplit);
+    hipLaunchKernelGGL((yl_head_gemm_kernel<4, PA, QA, CA, P>), grid, dim3(NT), 0, s, pa, qa, ca, NP, NQ, NR, rsplit);
+}
+// the same launch in a mode known at run time.  AMP = false (the necks, whose 1x1 GEMMs are fp32 only) instantiates
+// nothing but P = 0, so their code objects hold no 16-bit kernel
+template <bool AMP, class PA, class QA, class CA>
+void launch_gemm_in(int mode, hipStream_t s, PA pa, QA qa, CA ca, int NP, int NQ, int NR, int rsplit, int splits) {
+  if constexpr (AMP) {
+    if (mode == 1) return launch_gemm<1>(s, pa, qa, ca, NP, NQ, NR, rsplit, splits);
+    if (mode == 2) return launch_gemm<2>(s, pa, qa, ca, NP, NQ, NR, rsplit, splits);
+  }
+  launch_gemm<0>(s, pa, qa, ca, NP, NQ, NR, rsplit, splits);
+}
+// the precision bits of a forward's flags -> P; both: -1
+static_assert(YL_HEAD_F16 == YL_DNECK_F16 && YL_HEAD_BF16 == YL_DNECK_BF16, "one mode_of for the heads and the dense neck");
+inline int mode_of(uint32_t flags) {
+  const bool f = flags & YL_HEAD_F16, b = flags & YL_HEAD_BF16;
+  return f && b ? -1 : (f ? 1 : (b ? 2 : 0));
 }
 
 // the float64 partial sums of the row reductions, rounded up so that what follows them stays 16-byte aligned
@@ -547,9 +586,10 @@ inline bool blocks_grads_wanted(const yl_head_block* grads, int D, uintptr_t* bi
 
 // Blocks 0 .. D - 1 on `in`: per block 4 launches (5 with `train`).  `save` keeps every block's d, z, h apart; without it
 // every block runs in the first block's buffers.  The last block's output goes to `last_out` if that is given.
-// -> where the last block's output is
-inline const float* blocks_forward(hipStream_t s, const yl_head_block* blocks, int D, const float* in, const Buffers& bf,
-                                   bool save, bool train, const BlockDims& dm, float* last_out, int* launches) {
+// `mode`: the operand type of the 1x1 GEMM (0 with AMP = false).  -> where the last block's output is
+template <bool AMP>
+const float* blocks_forward(hipStream_t s, const yl_head_block* blocks, int D, const float* in, const Buffers& bf,
+                            bool save, bool train, int mode, const BlockDims& dm, float* last_out, int* launches) {
   const int M = dm.M, S = dm.S, F = dm.F;
   const long n4 = (long)M * (F >> 2);
   const int eg = ceil_div(n4, NT), cq = pick_cq(F);
@@ -559,7 +599,7 @@ inline const float* blocks_forward(hipStream_t s, const yl_head_block* blocks, i
     const yl_head_block& b = blocks[t];
     float* hout = (t == D - 1 && last_out) ? last_out : bf.h[k];
     hipLaunchKernelGGL(yl_head_dw_kernel<false>, dim3(eg), dim3(NT), 0, s, in, (const float*)b.dw, bf.d[k], M, S, F);
-    launch_gemm(s, RowsScalar{b.pw, F}, RowsVec{bf.d[k], F}, OutRowsVec{bf.z[k], F}, F, M, F, F, 1);
+    launch_gemm_in<AMP>(mode, s, RowsScalar{b.pw, F}, RowsVec{bf.d[k], F}, OutRowsVec{bf.z[k], F}, F, M, F, F, 1);
     nl += 2;
     if (train) {
       StatP sp;
@@ -593,10 +633,11 @@ inline int blocks_first_wanted(const yl_head_block* grads, int D) {
 
 // The blocks D - 1 .. first backward.  `gin`: the gradient of the last block's output (bf.ga, or a tensor that is only
 // read).  x_in: the input of block 0.  dx (may be NULL): where the gradient of block 0's input goes; the caller passes
-// first = 0 with it.  The walk stops at the last thing that is wanted.
-inline void blocks_backward(hipStream_t s, const yl_head_block* params, const yl_head_block* grads, int D, int first,
-                            const float* gin, const float* x_in, float* dx, const Buffers& bf, bool train,
-                            const BlockDims& dm, int* launches) {
+// first = 0 with it.  The walk stops at the last thing that is wanted.  `mode`: as in blocks_forward, of both 1x1 GEMMs.
+template <bool AMP>
+void blocks_backward(hipStream_t s, const yl_head_block* params, const yl_head_block* grads, int D, int first,
+                     const float* gin, const float* x_in, float* dx, const Buffers& bf, bool train, int mode,
+                     const BlockDims& dm, int* launches) {
   const int M = dm.M, S = dm.S, F = dm.F;
   const long n4 = (long)M * (F >> 2);
   const int eg = ceil_div(n4, NT), cq = pick_cq(F);
@@ -627,15 +668,15 @@ inline void blocks_backward(hipStream_t s, const yl_head_block* params, const yl
                        bf.ga, n4, F);
     ++nl;
     if (g.pw) {                          // dW1 = dz^T . d
-      launch_gemm(s, ColsScalar{bf.d[t], F}, ColsScalar{bf.ga, F}, OutPartial{bf.wpart, (long)F * F}, F, F, M,
-                  dm.wgrad_rows, dm.wgrad_splits);
+      launch_gemm_in<AMP>(mode, s, ColsScalar{bf.d[t], F}, ColsScalar{bf.ga, F}, OutPartial{bf.wpart, (long)F * F}, F, F, M,
+                          dm.wgrad_rows, dm.wgrad_splits);
       hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)F * F, NT)), dim3(NT), 0, s, (const float*)bf.wpart,
                          dm.wgrad_splits, F, F, g.pw, none, 0);
       nl += 2;
     }
     const bool need_dx = t > first || (t == 0 && dx);
     if (!g.dw && !need_dx) break;
-    launch_gemm(s, ColsScalar{b.pw, F}, RowsVec{bf.ga, F}, OutRowsVec{bf.gb, F}, F, M, F, F, 1);   // dd = dz . W1
+    launch_gemm_in<AMP>(mode, s, ColsScalar{b.pw, F}, RowsVec{bf.ga, F}, OutRowsVec{bf.gb, F}, F, M, F, F, 1);   // dd = dz . W1
     ++nl;
     if (g.dw) {
       hipLaunchKernelGGL(yl_head_dw_wgrad_kernel, dim3(dm.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s,

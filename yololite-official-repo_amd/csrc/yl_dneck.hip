@@ -47,15 +47,9 @@ constexpr int GB = 64, GXS = GB + 4;     // weight gradient: channels per block 
 //   their 16 lanes over (channel quad parity, column half, row & 3): 16 q' + 2 h + 4 r mod 32, sixteen 2-dword slots.
 constexpr int CHP = 24, CHR = 320;
 constexpr int GXP = 88, GDP = 72;
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ f32x4 mfma16(h16x4 a, h16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma16(b16x4 a, b16x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(__builtin_bit_cast(s16x4, a), __builtin_bit_cast(s16x4, b), c, 0, 0, 0);
-}
+// h16x4 / b16x4 / mfma16 and mode_of (flags -> Opnd<P>'s P; -1: both bits) are yl_block.h's, shared with the heads' GEMM
 
-template <int P> struct Opnd;            // E: element in the packed weight and in LDS; Frag: a lane's four k values
+template <int P> struct Opnd;          // E: element in the packed weight and in LDS; Frag: a lane's four k values
 template <> struct Opnd<0> {
   typedef float E; typedef f32x4 Frag;
   static constexpr int WIN = CWIN * CXS, XW = CWIN * GXS, DZ = CT * CT * GXS;
@@ -390,12 +384,6 @@ void w3_split(int64_t F, int64_t tiles, int32_t* tiles_per_split, int32_t* split
   want = want < tiles ? want : tiles;
   *tiles_per_split = ceil_div(tiles, want);
   *splits = ceil_div(tiles, *tiles_per_split);
-}
-
-// flags -> Opnd<P>'s P; -1: both bits
-int mode_of(uint32_t flags) {
-  const bool f = flags & YL_DNECK_F16, b = flags & YL_DNECK_BF16;
-  return f && b ? -1 : (f ? 1 : (b ? 2 : 0));
 }
 
 }  // namespace

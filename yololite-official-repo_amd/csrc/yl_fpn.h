@@ -135,7 +135,7 @@ inline void lateral_forward(hipStream_t s, const float* lat_w, const float* lat_
   OutLateral ol;
   ol.t = t; ol.bias = lat_b; ol.up = up; ol.src = src;
   ol.F = F; ol.S = S; ol.Sc = Sc;
-  launch_gemm(s, RowsScalar{lat_w, Cin}, RowsVec{c, Cin}, ol, F, M, Cin, Cin, 1);
+  launch_gemm<0>(s, RowsScalar{lat_w, Cin}, RowsVec{c, Cin}, ol, F, M, Cin, Cin, 1);
 }
 
 // the lateral's three gradients from gt, each only where wanted: 2 launches for dWlat, 2 for dblat, 1 for dc
@@ -144,7 +144,7 @@ inline void lateral_backward(hipStream_t s, const float* lat_w, float* g_lat_w, 
                              int lgrad_rows, int lgrad_splits, int* launches) {
   int nl = 0;
   if (g_lat_w) {                         // dWlat[f][cin] = sum over rows of gt[m][f] * c[m][cin]
-    launch_gemm(s, ColsScalar{c, Cin}, ColsScalar{gt, F}, OutPartial{wpart, (long)F * Cin}, Cin, F, M, lgrad_rows, lgrad_splits);
+    launch_gemm<0>(s, ColsScalar{c, Cin}, ColsScalar{gt, F}, OutPartial{wpart, (long)F * Cin}, Cin, F, M, lgrad_rows, lgrad_splits);
     HeadRows none;
     memset(&none, 0, sizeof(none));
     hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)F * Cin, NT)), dim3(NT), 0, s, (const float*)wpart,
@@ -159,7 +159,7 @@ inline void lateral_backward(hipStream_t s, const float* lat_w, float* g_lat_w, 
     nl += 2;
   }
   if (dc) {                              // dc = gt . Wlat
-    launch_gemm(s, ColsScalar{lat_w, Cin}, RowsVec{gt, F}, OutRowsVec{dc, Cin}, Cin, M, F, F, 1);
+    launch_gemm<0>(s, ColsScalar{lat_w, Cin}, RowsVec{gt, F}, OutRowsVec{dc, Cin}, Cin, M, F, F, 1);
     ++nl;
   }
   *launches += nl;

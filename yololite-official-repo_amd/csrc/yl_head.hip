@@ -20,6 +20,11 @@
 // No floating-point atomics.  Every sum over rows (BN statistics, dgamma / dbeta, depthwise weight gradient, weight and
 // bias gradients) is written as per-tile (per-split) partials and summed in tile order in float64 by a second kernel.
 // Equal inputs give equal bits.
+//
+// Mixed precision.  YL_HEAD_F16 / YL_HEAD_BF16 in the forward's flags run the six 1x1 GEMMs (z, dd, dW1 per block; y, dh,
+// dWout) with both operands rounded to that type as load4 returns them and one v_mfma_f32_16x16x16_* per p-tile and
+// 16-wide k step (yl_head_gemm_kernel<.., P>, yl_block.h); the handle keeps the mode with the held forward (fMode) and the
+// backward runs in it.  Everything else here is the fp32 code, whatever the mode.
 #include <new>
 
 #include "yl_block.h"
@@ -37,6 +42,7 @@ struct yl_head {
   Arena mem;                             // yl_block.h
   yl_head_cfg cfg;
   int fB, fS, fTrain;                    // the forward whose activations are held (mem.fValid)
+  int fMode;                             // and the operand type of its 1x1 GEMMs (yl_head_gemm_kernel's P): the backward's too
 };
 
 extern "C" {
@@ -124,13 +130,34 @@ bool params_ok(const yl_head_cfg& c, const yl_head_tensors* t) {
   return !(any & 3u);
 }
 
+// ---- the three GEMMs of the output convolutions in the mode `mode`, as yl_head_forward / _backward / _gemm launch them
+// y = h . Wout^T + bias: 1 launch
+void out_forward(int mode, hipStream_t s, const HeadRows& hw, const float* h_in, float* y, int M) {
+  const int F = hw.g.F;
+  launch_gemm_in<true>(mode, s, HeadWRows{hw}, RowsVec{h_in, F}, OutHeadY{y, hw}, hw.g.A * hw.g.E, M, F, F, 1);
+}
+// dh = gy . Wout: 1 launch
+void out_dgrad(int mode, hipStream_t s, const HeadRows& hw, const float* gy, float* dh, int M) {
+  const int F = hw.g.F, NE = hw.g.A * hw.g.E;
+  launch_gemm_in<true>(mode, s, HeadWCols{hw}, HeadYRows{gy, hw.g}, OutRowsVec{dh, F}, F, M, NE, NE, 1);
+}
+// dWout = gy^T . h into the non-NULL weights of `gw`: the partials of the row splits and their ordered sum, 2 launches
+void out_wgrad(int mode, hipStream_t s, const HeadGeom& g, const float* h_in, const float* gy, float* wpart, const HeadRows& gw,
+               int M, int rows, int splits) {
+  const int F = g.F, NE = g.A * g.E;
+  launch_gemm_in<true>(mode, s, ColsScalar{h_in, F}, HeadYCols{gy, g}, OutPartial{wpart, (long)NE * F}, F, NE, M, rows, splits);
+  hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)NE * F, NT)), dim3(NT), 0, s, (const float*)wpart, splits, F,
+                     NE, (float*)nullptr, gw, 1);
+}
+
 }  // namespace
 
 extern "C" {
 
 yl_status yl_head_forward(yl_head* h, const yl_head_tensors* params, const float* x_dev, int32_t batch, int32_t size,
                           uint32_t flags, float* y_dev, void* stream, int32_t* launches) {
-  if (!h || !x_dev || !y_dev || !params_ok(h->cfg, params)) return YL_ERR_INVALID;
+  const int mode = mode_of(flags);       // both precision bits: refused here, before a held forward is touched
+  if (!h || !x_dev || !y_dev || mode < 0 || !params_ok(h->cfg, params)) return YL_ERR_INVALID;
   if (((uintptr_t)x_dev & 15u) || ((uintptr_t)y_dev & 3u)) return YL_ERR_UNSUPPORTED;
   const bool train = flags & YL_HEAD_TRAIN, save = flags & YL_HEAD_SAVE;
   if (train && (int64_t)batch * size * size < 2) return YL_ERR_INVALID;   // no variance of one value
@@ -143,13 +170,13 @@ yl_status yl_head_forward(yl_head* h, const yl_head_tensors* params, const float
   const BlockDims dm = dims_of(pl, S, F);
   int nl = 0;
   h->mem.fValid = 0;
-  const float* in = blocks_forward(s, params->block, D, x_dev, bf, save, train, dm, nullptr, &nl);
+  const float* in = blocks_forward<true>(s, params->block, D, x_dev, bf, save, train, mode, dm, nullptr, &nl);
   const HeadRows hw = head_rows(h->cfg, params, S * S);
-  launch_gemm(s, HeadWRows{hw}, RowsVec{in, F}, OutHeadY{y_dev, hw}, hw.g.A * hw.g.E, M, F, F, 1);
+  out_forward(mode, s, hw, in, y_dev, M);
   ++nl;
   if (launches) *launches = nl;
   if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
-  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->mem.fValid = 1; }
+  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->fMode = mode; h->mem.fValid = 1; }
   return YL_OK;
 }
 
@@ -169,7 +196,7 @@ yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_h
   if (st != YL_OK) return st;
   if (!h->mem.fValid) return YL_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
-  const int M = pl.rows, F = h->cfg.channels, D = h->cfg.head_depth, S = size, train = h->fTrain;
+  const int M = pl.rows, F = h->cfg.channels, D = h->cfg.head_depth, S = size, train = h->fTrain, mode = h->fMode;
   const BlockDims dm = dims_of(pl, S, F);
   int nl = 0;
   const HeadRows hw = head_rows(h->cfg, params, S * S);
@@ -177,10 +204,7 @@ yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_h
   // 1. the output convolutions: weights by one GEMM over the rows and one sum, biases by column sums of gy
   const HeadRows gw = head_rows(h->cfg, grads, S * S);
   if (grads->box_w || grads->obj_w || grads->cls_w) {
-    launch_gemm(s, ColsScalar{bf.h[D - 1], F}, HeadYCols{gy_dev, hw.g}, OutPartial{bf.wpart, (long)NE * F}, F, NE, M,
-                pl.ograd_rows, pl.ograd_splits);
-    hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)NE * F, NT)), dim3(NT), 0, s, (const float*)bf.wpart,
-                       pl.ograd_splits, F, NE, (float*)nullptr, gw, 1);
+    out_wgrad(mode, s, hw.g, bf.h[D - 1], gy_dev, bf.wpart, gw, M, pl.ograd_rows, pl.ograd_splits);
     nl += 2;
   }
   if (grads->box_b || grads->obj_b || grads->cls_b) {
@@ -194,10 +218,61 @@ yl_status yl_head_backward(yl_head* h, const yl_head_tensors* params, const yl_h
   int first = blocks_first_wanted(grads->block, D);
   if (dx_dev) first = 0;
   if (first < D) {
-    launch_gemm(s, HeadWCols{hw}, HeadYRows{gy_dev, hw.g}, OutRowsVec{bf.ga, F}, F, M, NE, NE, 1);   // dh = gy . Wout
+    out_dgrad(mode, s, hw, gy_dev, bf.ga, M);
     ++nl;
   }
-  blocks_backward(s, params->block, grads->block, D, first, bf.ga, x_dev, dx_dev, bf, train != 0, dm, &nl);
+  blocks_backward<true>(s, params->block, grads->block, D, first, bf.ga, x_dev, dx_dev, bf, train != 0, mode, dm, &nl);
+  if (launches) *launches = nl;
+  return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;
+}
+
+yl_status yl_head_gemm(yl_head* h, int32_t site, int32_t pass, uint32_t mode, const yl_head_tensors* params,
+                       const float* a_dev, const float* b_dev, float* out_dev, int32_t batch, int32_t size, void* stream,
+                       int32_t* launches) {
+  if (mode != 0 && mode != YL_HEAD_F16 && mode != YL_HEAD_BF16) return YL_ERR_INVALID;
+  if (!h || !a_dev || !out_dev || !params_ok(h->cfg, params)) return YL_ERR_INVALID;
+  const bool out = site == YL_HEAD_SITE_OUT, wgrad = pass == YL_HEAD_PASS_WGRAD;
+  if ((!out && (site < 0 || site >= h->cfg.head_depth)) || pass < YL_HEAD_PASS_FORWARD || pass > YL_HEAD_PASS_WGRAD ||
+      (wgrad && !b_dev))
+    return YL_ERR_INVALID;
+  // what the kernels read and write as float4 (RowsVec, OutRowsVec); the level tensor and the weights are read by element
+  const bool a_rows = !wgrad && !(out && pass == YL_HEAD_PASS_DGRAD), out_rows = !wgrad && !(out && pass == YL_HEAD_PASS_FORWARD);
+  if (((uintptr_t)a_dev & (a_rows ? 15u : 3u)) || ((uintptr_t)b_dev & 3u) || ((uintptr_t)out_dev & (out_rows ? 15u : 3u)))
+    return YL_ERR_UNSUPPORTED;
+  yl_head_plan_info pl;
+  Buffers bf;
+  const yl_status st = ensure(h, batch, size, 0, &pl, &bf);   // the workspace only: nothing of a held forward is written
+  if (st != YL_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  const int M = pl.rows, F = h->cfg.channels, P = mode_of(mode);
+  const HeadRows hw = head_rows(h->cfg, params, size * size);
+  int nl = 1;
+  if (!out) {
+    const float* pw = params->block[site].pw;
+    if (pass == YL_HEAD_PASS_FORWARD) {
+      launch_gemm_in<true>(P, s, RowsScalar{pw, F}, RowsVec{a_dev, F}, OutRowsVec{out_dev, F}, F, M, F, F, 1);
+    } else if (pass == YL_HEAD_PASS_DGRAD) {
+      launch_gemm_in<true>(P, s, ColsScalar{pw, F}, RowsVec{a_dev, F}, OutRowsVec{out_dev, F}, F, M, F, F, 1);
+    } else {
+      HeadRows none;
+      memset(&none, 0, sizeof(none));
+      launch_gemm_in<true>(P, s, ColsScalar{a_dev, F}, ColsScalar{b_dev, F}, OutPartial{bf.wpart, (long)F * F}, F, F, M,
+                           pl.wgrad_rows, pl.wgrad_splits);
+      hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)F * F, NT)), dim3(NT), 0, s, (const float*)bf.wpart,
+                         pl.wgrad_splits, F, F, out_dev, none, 0);
+      nl = 2;
+    }
+  } else if (pass == YL_HEAD_PASS_FORWARD) {
+    out_forward(P, s, hw, a_dev, out_dev, M);
+  } else if (pass == YL_HEAD_PASS_DGRAD) {
+    out_dgrad(P, s, hw, a_dev, out_dev, M);
+  } else {
+    HeadRows gw = hw;                    // out_dev: the rows of box_w, obj_w, cls_w one after the other
+    gw.box = out_dev; gw.obj = gw.box + (long)4 * hw.g.A * F; gw.cls = gw.obj + (long)hw.g.A * F;
+    gw.box_b = gw.obj_b = gw.cls_b = nullptr;
+    out_wgrad(P, s, hw.g, a_dev, b_dev, bf.wpart, gw, M, pl.ograd_rows, pl.ograd_splits);
+    nl = 2;
+  }
   if (launches) *launches = nl;
   return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;
 }

@@ -180,8 +180,8 @@ yl_status yl_neck_forward(yl_neck* h, const yl_neck_tensors* params, const float
                     k + 1 < L ? sizes[k + 1] : 0);
     ++nl;
     // with `save` the last block writes the handle's h and p_k is a copy of it; without, it writes p_k
-    const float* last = blocks_forward(s, lv.block, D, nb.t[k], nb.lv[k], save, train, dims_of(pl.level[k], S, F),
-                                       save ? nullptr : p_dev[k], &nl);
+    const float* last = blocks_forward<false>(s, lv.block, D, nb.t[k], nb.lv[k], save, train, 0, dims_of(pl.level[k], S, F),
+                                              save ? nullptr : p_dev[k], &nl);
     if (save && hipMemcpyAsync(p_dev[k], last, (size_t)M * F * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
   }
   if (launches) *launches = nl;
@@ -237,8 +237,8 @@ yl_status yl_neck_backward(yl_neck* h, const yl_neck_tensors* params, const yl_n
     const bool lateral = g.lat_w || g.lat_b || dc;
     const bool need_gt = lateral || k < K;
     const int first = need_gt ? 0 : blocks_first_wanted(g.block, D);
-    blocks_backward(s, lv.block, g.block, D, first, gin, nb.t[k], need_gt ? nb.gt : nullptr, bf, train,
-                    dims_of(lp, S, F), &nl);
+    blocks_backward<false>(s, lv.block, g.block, D, first, gin, nb.t[k], need_gt ? nb.gt : nullptr, bf, train, 0,
+                           dims_of(lp, S, F), &nl);
     lateral_backward(s, lv.lat_w, g.lat_w, g.lat_b, dc, c_dev[k], nb.gt, bf.wpart, bf.spart, F, Cin, M, S, lp.stat_tiles,
                      lp.lgrad_rows, lp.lgrad_splits, &nl);
   }

@@ -12,7 +12,16 @@ FusedTrainStep takes parameters().  Every level runs through one torch.autograd.
 are yl_head_forward / yl_head_backward (csrc/yl_head.hip); the kernels read the parameters where torch keeps them.
 train() / eval() select the BatchNorm mode.  Gradients nobody asked for are not computed (`last_launches` says what
 ran).  One forward per level is held for backward at a time: a second forward before backward() replaces it, and the
-stale backward raises.  fp32 on one HIP device; no CPU fallback.
+stale backward raises.  One HIP device; no CPU fallback.
+
+Mixed precision (the reference's AMP, tools/train.py:284-357): DetectHeads(..., precision="fp16" | "bf16"), or
+`heads.precision = ...` at any time, runs every 1x1 GEMM of the heads -- the trunk blocks' z = d . W1^T, dd = dz . W1,
+dW1 = dz^T . d and the outputs' y = h . Wout^T, dh = gy . Wout, dWout = gy^T . h -- with both operands rounded to that
+type (nearest even) and fp32 accumulation on the 16-bit MFMA.  Parameters, gradients, the saved activations, the
+depthwise 3x3, BatchNorm, the bias and every ordered float64 sum stay fp32; the launch counts are the same.  Nothing is
+clamped: a value beyond fp16's range becomes inf and the gradients it reaches are not finite, which is what
+FusedTrainStep's loss-scale logic looks for.  A backward runs in the precision of the forward it belongs to.
+head_gemm() runs one of those GEMMs on its own (yl_head_gemm).
 """
 from __future__ import annotations
 
@@ -67,7 +76,8 @@ class _Level(tm.DeviceHandle):
 
     def __init__(self, F: int, nc: int, A: int, depth: int):
         super().__init__("yl_head", _cfg, F, nc, A, depth)
-        self.nc, self.A, self.depth = nc, A, depth
+        self.F, self.nc, self.A, self.depth = F, nc, A, depth
+        self.mode_bits = 0                                 # yl_head_forward's precision bits: the module sets them per call
 
     @staticmethod
     def params(head: nn.ModuleDict) -> List[torch.Tensor]:
@@ -104,7 +114,8 @@ class _HeadFunction(torch.autograd.Function):
         xd = tm.aligned(x.detach())
         ps = tm.detached_params("DetectHeads", params, x.device)
         y = torch.empty((B, lv.A, S, S, 5 + lv.nc), device=x.device, dtype=torch.float32)
-        lv.launch("forward", x.device, C.byref(lv.table(ps, bufs)), xd.data_ptr(), B, S, tm.flags(train, save), y.data_ptr())
+        lv.launch("forward", x.device, C.byref(lv.table(ps, bufs)), xd.data_ptr(), B, S,
+                  tm.flags(train, save) | lv.mode_bits, y.data_ptr())
         if save:
             fctx.save_for_backward(xd, *params)
             fctx.lv, fctx.bufs, fctx.generation, fctx.shape = lv, bufs, lv.generation, (B, S)
@@ -129,8 +140,9 @@ class DetectHeads(nn.Module):
     """See the module docstring.  `num_anchors_per_level`: one int per level (or one int for all)."""
 
     def __init__(self, fpn_channels: int, num_classes: int, num_anchors_per_level=1, head_depth: int = 1,
-                 level_names: Sequence[str] = ("p3", "p4", "p5"), num_masks: int = 0):
+                 level_names: Sequence[str] = ("p3", "p4", "p5"), num_masks: int = 0, precision: str = "fp32"):
         super().__init__()
+        tm.check_precision(precision)
         F, nc, depth = int(fpn_channels), int(num_classes), int(head_depth)
         if int(num_masks):
             raise _lib.YoloLiteHipError("mask-coefficient heads (num_masks > 0) are not implemented")
@@ -152,9 +164,19 @@ class DetectHeads(nn.Module):
             init_detect_bias(head, nc)
             setattr(self, "head" + n[1:], head)
             self._levels.append(_Level(F, nc, A, depth))
+        self.precision = precision
+
+    @property
+    def precision(self) -> str:
+        """"fp32", "fp16" or "bf16": the operand type of the 1x1 GEMMs of the forwards to come (and of their backwards)"""
+        return self._precision
+
+    @precision.setter
+    def precision(self, value: str):
+        self._precision = tm.check_precision(value)
 
     @classmethod
-    def from_meta(cls, meta: dict, num_classes: Optional[int] = None) -> "DetectHeads":
+    def from_meta(cls, meta: dict, num_classes: Optional[int] = None, precision: str = "fp32") -> "DetectHeads":
         """freshly initialised heads of the model `meta` describes (program.build_program reads the same keys)"""
         F, names, mcfg, _ = tm.meta_fpn(meta)
         if mcfg.get("seg"):
@@ -165,12 +187,13 @@ class DetectHeads(nn.Module):
             amap = dict(p2=apl[0], p3=apl[0], p4=apl[1], p5=apl[2], p6=apl[2])
         else:
             amap = dict.fromkeys(("p2", "p3", "p4", "p5", "p6"), apl[0] if apl else 1)
-        return cls(F, nc, tuple(int(amap[n]) for n in names), int(mcfg.get("head_depth", 1)), level_names=names)
+        return cls(F, nc, tuple(int(amap[n]) for n in names), int(mcfg.get("head_depth", 1)), level_names=names,
+                   precision=precision)
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict) -> "DetectHeads":
+    def from_state_dict(cls, meta: dict, sd: dict, precision: str = "fp32") -> "DetectHeads":
         """the heads of a checkpoint: built from its meta, filled with its `head*.` entries (tensors or numpy arrays)"""
-        return tm.fill_from_state_dict(cls.from_meta(meta), sd, "head")
+        return tm.fill_from_state_dict(cls.from_meta(meta, precision=precision), sd, "head")
 
     def last_launches(self) -> List[Dict[str, int]]:
         """kernels enqueued by the last forward / backward of every level"""
@@ -192,6 +215,72 @@ class DetectHeads(nn.Module):
             if any(p.device != f.device for p in params):
                 raise _lib.YoloLiteHipError("DetectHeads: parameters and inputs must live on one HIP device")
             lv.ensure(f.device)
+            lv.mode_bits = tm.PRECISIONS[self._precision]
             x = f.float().contiguous()                     # autograd carries the gradient back through cast and copy
             outs.append(_HeadFunction.apply(lv, lv.buffers(head), self.training, torch.is_grad_enabled(), x, *params))
         return outs
+
+
+PASSES = {"forward": _lib.YL_HEAD_PASS_FORWARD, "dgrad": _lib.YL_HEAD_PASS_DGRAD, "wgrad": _lib.YL_HEAD_PASS_WGRAD}
+
+
+def head_gemm(heads: DetectHeads, level: int, site, pass_: str, a: torch.Tensor, b: Optional[torch.Tensor] = None,
+              precision: Optional[str] = None):
+    """One 1x1 GEMM of level `level` (an index into heads.level_names) on its own, launched as the module launches it
+    (yl_head_gemm), with that level's weights read where torch keeps them.  `site`: a trunk block's index or "out", the
+    three output convolutions.  fp32 tensors on the heads' HIP device:
+        site t, "forward":  a = d  [B,S,S,F]                 -> z  [B,S,S,F]          = d . W1^T
+        site t, "dgrad":    a = dz [B,S,S,F]                 -> dd [B,S,S,F]          = dz . W1
+        site t, "wgrad":    a = d  [B,S,S,F], b = dz [B,S,S,F] -> dW1 [F,F,1,1]        = dz^T . d
+        "out",  "forward":  a = h  [B,S,S,F]                 -> y  [B,A,S,S,5+C]      = h . Wout^T + bias
+        "out",  "dgrad":    a = gy [B,A,S,S,5+C]             -> dh [B,S,S,F]          = gy . Wout
+        "out",  "wgrad":    a = h  [B,S,S,F], b = gy [B,A,S,S,5+C] -> (dbox_w, dobj_w, dcls_w)
+    `precision`: both operands are rounded to it (nearest even), fp32 accumulation; None: the heads' own.  Uses the
+    level's handle: if its workspace has to grow for the call, a forward it holds for backward is dropped and that
+    backward raises."""
+    if not isinstance(heads, DetectHeads):
+        raise ValueError("`heads` must be a DetectHeads")
+    if isinstance(level, bool) or not isinstance(level, int) or not 0 <= level < len(heads._levels):
+        raise ValueError(f"level must be an index 0..{len(heads._levels) - 1}, got {level!r}")
+    out_site = isinstance(site, str) and site == "out"
+    if not out_site and (isinstance(site, bool) or not isinstance(site, int) or not 0 <= site < heads.head_depth):
+        raise ValueError(f"site must be a block index 0..{heads.head_depth - 1} or 'out', got {site!r}")
+    if not isinstance(pass_, str) or pass_ not in PASSES:
+        raise ValueError(f"pass_ must be one of {sorted(PASSES)}, got {pass_!r}")
+    precision = tm.check_precision(heads.precision if precision is None else precision)
+    lv, F = heads._levels[level], heads.fpn_channels
+    E = 5 + lv.nc
+    level_in = out_site and pass_ == "dgrad"               # `a` is the level tensor
+    if not torch.is_tensor(a) or a.dim() != (5 if level_in else 4):
+        raise ValueError("the first operand must be " + ("[B,A,S,S,5+C]" if level_in else "[B,S,S,F]"))
+    B, S = int(a.shape[0]), int(a.shape[2])
+    rows, lvl = (B, S, S, F), (B, lv.A, S, S, E)
+    if tuple(a.shape) != (lvl if level_in else rows) or B < 1 or S < 1:
+        raise ValueError(f"the first operand of {pass_!r} must be {lvl if level_in else rows}, got {tuple(a.shape)}")
+    if pass_ == "wgrad":
+        want = lvl if out_site else rows
+        if not torch.is_tensor(b) or tuple(b.shape) != want:
+            raise ValueError(f"the second operand of 'wgrad' must be {want}")
+    elif b is not None:
+        raise ValueError(f"{pass_!r} takes one operand")
+    if not a.is_cuda or (b is not None and b.device != a.device):
+        raise _lib.YoloLiteHipError("head_gemm needs its operands on one HIP device (no CPU fallback)")
+    head = getattr(heads, "head" + heads.level_names[level][1:])
+    ps = tm.detached_params("DetectHeads", lv.params(head), a.device)
+    lv.ensure(a.device)
+    ad = tm.aligned(a.detach().float().contiguous())
+    bd = tm.aligned(b.detach().float().contiguous()) if b is not None else None
+    NE = lv.A * E
+    if pass_ == "wgrad":
+        out = torch.empty((NE, F) if out_site else (F, F, 1, 1), device=a.device, dtype=torch.float32)
+    else:
+        out = torch.empty(lvl if out_site and pass_ == "forward" else rows, device=a.device, dtype=torch.float32)
+    n = C.c_int32()
+    lv.call("gemm", _lib.YL_HEAD_SITE_OUT if out_site else site, PASSES[pass_], tm.PRECISIONS[precision],
+            C.byref(lv.table(ps, lv.buffers(head))), ad.data_ptr(), tm.ptr(bd), out.data_ptr(), B, S,
+            torch.cuda.current_stream(a.device).cuda_stream, C.byref(n))
+    if out_site and pass_ == "wgrad":                      # the rows of box_w, obj_w, cls_w one after the other
+        A, nc = lv.A, lv.nc
+        return (out[:4 * A].reshape(4 * A, F, 1, 1), out[4 * A:5 * A].reshape(A, F, 1, 1),
+                out[5 * A:].reshape(A * nc, F, 1, 1))
+    return out

@@ -47,13 +47,8 @@ from . import _lib
 from . import _trainmod as tm
 
 
-PRECISIONS = {"fp32": 0, "fp16": _lib.YL_DNECK_F16, "bf16": _lib.YL_DNECK_BF16}    # -> yl_dneck_forward's flag bits
-
-
-def _check_precision(precision) -> str:
-    if not isinstance(precision, str) or precision not in PRECISIONS:
-        raise ValueError(f"precision must be one of {sorted(PRECISIONS)}, got {precision!r}")
-    return precision
+PRECISIONS = tm.PRECISIONS                                 # -> yl_dneck_forward's flag bits (YL_DNECK_F16 / _BF16)
+_check_precision = tm.check_precision
 
 
 def _check_dims(in_channels, F, depth):
