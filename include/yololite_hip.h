@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define YL_ABI_VERSION 6
+#define YL_ABI_VERSION 7
 #define YL_MAX_LEVELS 8
 
 typedef struct yl_ctx yl_ctx;
@@ -980,6 +980,110 @@ yl_status yl_dneck_held(const yl_dneck* h, int64_t* saved_bytes, int64_t* worksp
  * that has to grow, a held forward is dropped as any growth drops it. */
 yl_status yl_dneck_conv3x3(yl_dneck* h, int32_t pass, uint32_t mode, const float* a_dev, const float* b_dev,
                            float* out_dev, int32_t batch, int32_t size, void* stream, int32_t* launches);
+
+/* ---- trainable backbone stage: a stack of MobileNetV4 UIB blocks (timm UniversalInvertedResidual) and 1x1 ConvBnAct ----
+ * Forward and backward of up to YL_STAGE_MAX_BLOCKS blocks over square NHWC fp32 maps [B][S][S][C], fp32 throughout.
+ * A block is a run of UNITS, each a bias-free convolution followed by BatchNorm2d:
+ *     uir:  [dw_start: depthwise a x a, stride (k ? 1 : s), BN]   pw_exp: 1x1 cin -> mid, BN, ReLU
+ *           [dw_mid:   depthwise k x k, stride s, BN, ReLU]        pw_proj: 1x1 mid -> cout, BN
+ *           a, k in {0, 3, 5} (0: the unit is absent), s in {1, 2}; the block adds its input when cin == cout and s == 1
+ *     cn:   1x1 cin -> cout, BN, ReLU   (held in the pw_exp entry of the tables; mid is ignored)
+ * A depthwise k x k pads (k - 1) / 2 on every side: S_out = (S + 2 p - k) / s + 1, odd S under stride 2 included.  Every
+ * channel count is a multiple of 4, block i's cin is block i - 1's cout, s == 2 needs a depthwise unit to carry it and
+ * eps > 0: anything else is YL_ERR_INVALID from a host-side check before any device call.  ReLU is the only activation;
+ * TF-SAME padding, squeeze-excite and layer-scale do not exist here.
+ * Parameters are read in PyTorch layout from the caller's tensors on every call, at any 4-byte boundary (depthwise
+ * [C][1][k][k], 1x1 [out][in][1][1]); x / out / gy / dx are 16-byte aligned (else YL_ERR_UNSUPPORTED).
+ * The depthwise passes: forward, one thread per output pixel x 4 channels, taps in (ky, kx) order, fp32 sum from zero;
+ * input gradient as a gather, one thread per INPUT pixel x 4 channels summing, in (ky, kx) order, the taps whose
+ * (i + p - ky) is a multiple of the stride; weight gradient as float64 partials per tile of stat_rows OUTPUT rows and
+ * their sum in tile order.  The 1x1 convolutions are the heads' GEMM (v_mfma_f32_16x16x4_f32) in all three passes.
+ * BatchNorm numerics are the heads' with eps from the configuration: statistics in float64 partials per tile of
+ * stat_rows rows summed in tile order, biased variance to normalise, unbiased for running_var, momentum 0.1,
+ * num_batches_tracked += 1; without YL_HEAD_TRAIN the running statistics are used and nothing is updated.
+ * Equal inputs give equal bits: no floating-point atomics. */
+#define YL_STAGE_MAX_BLOCKS 16
+#define YL_STAGE_UIR 0
+#define YL_STAGE_CN 1
+#define YL_STAGE_PASS_FORWARD 0     /* a = x  [B][S][S][C],    b = W  [C][1][k][k]   -> out = y  [B][So][So][C] */
+#define YL_STAGE_PASS_DGRAD 1       /* a = dy [B][So][So][C],  b = W  [C][1][k][k]   -> out = dx [B][S][S][C]  */
+#define YL_STAGE_PASS_WGRAD 2       /* a = x  [B][S][S][C],    b = dy [B][So][So][C] -> out = dW [C][1][k][k]  */
+typedef struct yl_stage yl_stage;
+typedef struct yl_stage_block_cfg {
+  int32_t type;                     /* YL_STAGE_UIR / YL_STAGE_CN */
+  int32_t a, k, s;                  /* uir: dw_start kernel, dw_mid kernel, stride; cn: 0, 1, 1 */
+  int32_t mid;                      /* uir: the expanded width */
+  int32_t cout;
+  int32_t reserved0, reserved1;
+} yl_stage_block_cfg;
+typedef struct yl_stage_cfg {
+  int32_t in_channels;              /* cin of block 0 */
+  int32_t num_blocks;               /* 1..YL_STAGE_MAX_BLOCKS */
+  double eps;                       /* of every BatchNorm */
+  yl_stage_block_cfg block[YL_STAGE_MAX_BLOCKS];
+} yl_stage_cfg;
+typedef struct yl_stage_unit {      /* one convolution and its BatchNorm; an absent unit's entries are ignored */
+  float* w;                         /* conv.weight */
+  float* gamma;                     /* bn.weight */
+  float* beta;                      /* bn.bias */
+  float* running_mean;              /* (ignored in a gradient table) */
+  float* running_var;               /* (ignored in a gradient table) */
+  int64_t* num_batches_tracked;     /* one int64, 8-byte aligned (ignored in a gradient table) */
+} yl_stage_unit;
+typedef struct yl_stage_block {     /* cn: pw_exp holds conv / bn1 */
+  yl_stage_unit dw_start, pw_exp, dw_mid, pw_proj;
+} yl_stage_block;
+typedef struct yl_stage_tensors {   /* the parameters, or where their gradients go (NULL = not wanted) */
+  yl_stage_block block[YL_STAGE_MAX_BLOCKS];
+} yl_stage_tensors;
+typedef struct yl_stage_block_plan {
+  int32_t size_in, size_mid, size_out;        /* S entering the block, behind dw_start (where pw_exp runs), leaving it */
+  int32_t rows_mid, rows_out;                 /* batch * size_mid^2 (dw_start, pw_exp; cn), batch * size_out^2 (dw_mid, pw_proj) */
+  int32_t stat_tiles_mid, stat_tiles_out;     /* tiles of stat_rows rows */
+  int32_t exp_rows, exp_splits;               /* weight gradient of pw_exp / cn (cin x mid over rows_mid): rows per split, splits */
+  int32_t proj_rows, proj_splits;             /* of pw_proj (mid x cout over rows_out); 0 for cn */
+  int32_t units;                              /* 1..4 */
+  int64_t saved_bytes;                        /* sum over the block's units of 2 M_u C_u 4 + 2 C_u 4: z, h and (mean, invstd);
+                                                 M_u, C_u: rows and channels of the unit's OUTPUT */
+} yl_stage_block_plan;
+typedef struct yl_stage_plan_info {
+  int32_t stat_rows, gemm_rows;
+  yl_stage_block_plan block[YL_STAGE_MAX_BLOCKS];
+  int64_t saved_bytes;              /* YL_HEAD_SAVE: M_0 C_0 4 (a copy of x) + the blocks' saved_bytes */
+  int64_t nosave_bytes;             /* without: 4 Amax + 2 Cmax 4; Amax = max_u M_u C_u 4 (one z, three rotating h), Cmax = max_u C_u */
+  int64_t workspace_bytes;          /* 3 max(Amax, M_0 C_0 4)                        three rotating gradients
+                                       + max_u round16(tiles_u T_u C_u 8)           float64 partials; T_u = k^2 for a depthwise unit, 2 for a 1x1
+                                       + 2 Cmax 4                                    the BatchNorm backward's coefficients
+                                       + max over 1x1 units of round16(splits_u cin_u cout_u 4) */
+} yl_stage_plan_info;
+/* A pure host function: tile t of a cut covers the rows [t * rows_per_tile, min(M, (t + 1) * rows_per_tile)); the
+ * splits are those the heads' weight gradient makes of an NP x NQ GEMM over M rows. */
+yl_status yl_stage_plan(const yl_stage_cfg* cfg, int32_t batch, int32_t size, yl_stage_plan_info* out);
+yl_status yl_stage_create(int32_t device, const yl_stage_cfg* cfg, yl_stage** out);
+void yl_stage_destroy(yl_stage* h);
+yl_status yl_stage_held(const yl_stage* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+/* Enqueues the forward: per unit 3 launches (convolution, BatchNorm statistics, BatchNorm [+ ReLU] [+ the block's
+ * input]), 4 with YL_HEAD_TRAIN (the column sums); with YL_HEAD_SAVE two device-to-device copies besides (x in, the
+ * last h out; not counted).  x_dev: [B][size][size][in_channels]; out_dev: [B][S_out][S_out][cout of the last block],
+ * written.  `flags`: YL_HEAD_TRAIN, YL_HEAD_SAVE; any other bit (the precision bits among them) is YL_ERR_INVALID.
+ * YL_HEAD_TRAIN with a unit of ONE output row: YL_ERR_INVALID before any launch.  One forward is held per handle. */
+yl_status yl_stage_forward(yl_stage* h, const yl_stage_tensors* params, const float* x_dev, int32_t batch, int32_t size,
+                           uint32_t flags, float* out_dev, void* stream, int32_t* launches);
+/* Enqueues the backward of the held forward (YL_ERR_STATE if there is none).  gy_dev: the gradient of out.  Every
+ * non-NULL tensor of `grads` and dx_dev (may be NULL) is OVERWRITTEN.  The units are walked last first down to the
+ * first one something is wanted of (unit 0 with dx_dev); nothing upstream of it runs.  Per unit: [1 sums if train or
+ * gamma / beta wanted] + 1 (bn grads) + 1 (dz) + [2 if w wanted: partials, ordered sum] + [1 input gradient, if the
+ * walk goes on]; + 1 per residual block whose input gradient is computed (the add of the block output's gradient). */
+yl_status yl_stage_backward(yl_stage* h, const yl_stage_tensors* params, const yl_stage_tensors* grads,
+                            const float* gy_dev, float* dx_dev, void* stream, int32_t* launches);
+/* ONE depthwise pass on its own, launched exactly as the module launches it, on the current device: `pass` is a
+ * YL_STAGE_PASS_*, k in {3, 5}, stride in {1, 2}, `size` the FORWARD's input size S (So follows).  FORWARD and DGRAD: 1
+ * launch; WGRAD: 2 (partials, ordered sum), with a temporary buffer for the partials that is freed before the call
+ * returns, which waits for `stream`.  a_dev and out_dev of FORWARD / DGRAD and both operands of WGRAD are 16-byte
+ * aligned (else YL_ERR_UNSUPPORTED); a weight may start at any 4-byte boundary. */
+yl_status yl_stage_depthwise(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k,
+                             int32_t stride, int32_t batch, int32_t size, int32_t channels, void* stream,
+                             int32_t* launches);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Generate tests/golden/stage_train.npz from the oracle/backbones.py modules (UniversalInvertedResidual, ConvBnAct; pure
+torch, CPU, torch autograd), forward and backward, in fp32 and in float64 on the SAME fp32-valued inputs.
+
+    python tests/golden/make_stage_fixtures.py [--search]
+
+Inputs come from the seeds of tests/_stage_cases.py; the archive's layout is described there.
+
+Admission rule, asserted for every case, mode and unit with a ReLU (none is dropped; change the seed in _stage_cases.py
+and say so there): the ReLU masks of the fp32 and the float64 run are identical, and the smallest |BatchNorm output| in
+front of the ReLU in the float64 run is at least 64 x the fp32 run's error in that tensor -- otherwise a case pins a ReLU
+tie.  --search prints, per case, the first seed of 101, 202, 303, ... that is admitted, and writes nothing."""
+import argparse
+import os
+import sys
+
+os.environ["PYTHONDONTWRITEBYTECODE"] = "1"
+sys.dont_write_bytecode = True
+import numpy as np
+import torch
+from torch import nn
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+from _stage_cases import CASES, EPS, case_inputs, modes, stored_indices, tensor_shapes, units  # noqa: E402
+from oracle.backbones import ConvBnAct, UniversalInvertedResidual  # noqa: E402
+
+OUT = os.environ.get("YL_FIXTURE_OUT") or HERE
+
+
+def oracle_stack(case):
+    """the case's blocks as oracle modules under the case's key names"""
+    root, cin = nn.Module(), case["cin"]
+    for b in case["blocks"]:
+        if b["type"] == "cn":
+            m = ConvBnAct(cin, b["c"], b["k"], b["s"], "relu", EPS, False)
+        else:
+            m = UniversalInvertedResidual(cin, b["c"], b["a"], b["k"], b["s"], b["mid"] / cin, "relu", EPS, False)
+            assert m.pw_exp.conv.out_channels == b["mid"], (b, m.pw_exp.conv.out_channels)
+        node = root
+        parts = (case.get("prefix", "") + "blocks." + b["name"]).split(".")
+        for p in parts[:-1]:
+            if not hasattr(node, p):
+                node.add_module(p, nn.Module())
+            node = getattr(node, p)
+        node.add_module(parts[-1], m)
+        cin = b["c"]
+    return root
+
+
+def run_oracle(case, inputs, train, dtype):
+    """-> {tensor name: array}, [(BatchNorm output in front of a ReLU)] in running order"""
+    root = oracle_stack(case).to(dtype)
+    sd = {n: torch.from_numpy(np.asarray(v)) for n, v in {**inputs["params"], **inputs["buffers"]}.items()}
+    root.load_state_dict({n: v.to(dtype) if v.dtype.is_floating_point else v for n, v in sd.items()}, strict=True)
+    root.train(train)
+    mods = dict(root.named_modules())
+    pre_relu, hooks = [], []
+    for u in units(case):
+        if u["relu"]:
+            bn = mods[u["key"] + u["bn"]]
+            assert isinstance(bn.act, nn.ReLU)
+            hooks.append(bn.act.register_forward_hook(lambda m, i, o: pre_relu.append(i[0].detach().clone())))
+            bn.act.inplace = False
+    x = torch.from_numpy(inputs["x"]).to(dtype).permute(0, 3, 1, 2).contiguous().requires_grad_(True)
+    h = x
+    for b in case["blocks"]:
+        h = mods[case.get("prefix", "") + "blocks." + b["name"]](h)
+    h.backward(torch.from_numpy(inputs["gy"]).to(dtype).permute(0, 3, 1, 2))
+    for hk in hooks:
+        hk.remove()
+    out = {"y": h.detach().permute(0, 2, 3, 1).contiguous().numpy(), "dx": x.grad.permute(0, 2, 3, 1).contiguous().numpy()}
+    for n, v in root.state_dict().items():
+        if "running_" in n or "num_batches" in n:
+            out["b." + n] = v.numpy().copy()
+    for n, p in root.named_parameters():
+        out["g." + n] = p.grad.numpy()
+    return out, [b.numpy() for b in pre_relu]
+
+
+def admitted(case, inputs, mode):
+    r32, bn32 = run_oracle(case, inputs, mode == "train", torch.float32)
+    r64, bn64 = run_oracle(case, inputs, mode == "train", torch.float64)
+    why = None
+    for t, (b32, b64) in enumerate(zip(bn32, bn64)):
+        margin, err = np.abs(b64).min(), np.abs(b32.astype(np.float64) - b64).max()
+        if not np.array_equal(b32 > 0, b64 > 0):
+            why = (case["name"], mode, t, "ReLU masks differ")
+        elif not margin >= 64 * err:
+            why = (case["name"], mode, t, float(margin), float(err))
+    return r32, r64, bn64, why
+
+
+def search():
+    for case in CASES:
+        for k in range(1, 40):
+            seed = 101 * k
+            inputs = case_inputs(case, seed)
+            if all(admitted(case, inputs, mode)[3] is None for mode in modes(case)):
+                print(f"{case['name']:10s} first admitted seed {seed}" + ("" if seed == case["seed"] else f"   (the case says {case['seed']})"))
+                break
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--search", action="store_true")
+    if ap.parse_args().search:
+        return search()
+    arrays = {}
+    for case in CASES:
+        inputs = case_inputs(case)
+        for mode in modes(case):
+            r32, r64, bn64, why = admitted(case, inputs, mode)
+            assert why is None, why                        # admission rule: change the seed in _stage_cases.py
+            key = f"{case['name']}/{mode}"
+            vals, e32s, m64s = [], [], []
+            shapes = tensor_shapes(case)
+            assert set(shapes) == set(r64), sorted(set(shapes) ^ set(r64))
+            for n, shape in shapes.items():
+                v32, v64 = r32[n], r64[n]
+                assert v32.shape == v64.shape == tuple(shape), (n, v64.shape, shape)
+                e32s.append(np.abs(v32.astype(np.float64) - v64).max())
+                m64s.append(np.abs(v64).max())
+                flat = v64.reshape(-1).astype(np.float64)
+                idx = stored_indices(key, n, shape)
+                vals.append(flat if idx is None else flat[idx])
+            arrays[key + "/r64"] = np.concatenate(vals)
+            arrays[key + "/e32"] = np.asarray(e32s, np.float64)
+            arrays[key + "/max64"] = np.asarray(m64s, np.float64)
+            worst = max(e / max(m, 1e-300) for e, m in zip(e32s, m64s))
+            print(f"{case['name']:10s} {mode:5s} min|bn|={min(np.abs(b).min() for b in bn64):.1e}  worst e32/max64={worst:.1e}")
+    path = os.path.join(OUT, "stage_train.npz")
+    np.savez_compressed(path, **arrays)
+    print(path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < (1 << 20)
+
+
+if __name__ == "__main__":
+    main()

@@ -6,7 +6,7 @@
 
     python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
-                                   [--train-neck [--amp fp16|bf16]] [--amp-heads fp16|bf16]
+                                   [--train-neck [--amp fp16|bf16] [--train-tail [--lr-tail 1e-4]]] [--amp-heads fp16|bf16]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
@@ -28,6 +28,14 @@ its three 3x3 GEMMs in that precision (operands rounded, fp32 accumulation; para
 fp16 the loss is multiplied by FusedTrainStep's loss scale before backward() and the step unscales, skips a step whose
 gradients are not finite and updates the scale, all on the device; with bf16 the scale is fixed at 1.  The laterals
 and the loss stay fp32.
+
+With --train-tail (needs --train-neck; the mobilenetv4_conv_small backbones, i.e. edge_n / edge_s / edge_m / edge_l) the
+backbone's last stage is trained as well: stageops.BackboneTail (csrc/yl_stage.hip) holds the UIB blocks and the 1x1
+ConvBnAct between the C4 and the C5 tap, starts from the checkpoint's `backbone.blocks.*` entries, and runs
+`c3, c4, _ = model.features(x); c5 = tail(c4); neck([c3, c4, c5])`; stages 0..3 stay frozen in the executor.  The tail's
+parameters are a FusedTrainStep group of their own with the rate --lr-tail (default: --lr), and its state_dict is merged
+into the output.  The tail is fp32; --amp / --amp-heads go with it: nothing in the code ties the precision of the
+neck's or the heads' GEMMs to the tail's, and the loss scale reaches its gradients through the chain like any others.
 
 --amp-heads fp16 | bf16 (with or without --train-neck): DetectHeads runs every 1x1 GEMM of the heads in that precision, on
 the same terms.  The loss scale is on when either of --amp and --amp-heads is fp16.
@@ -116,6 +124,9 @@ def main():
     ap.add_argument("--optimizer", default="adamw", choices=("adamw", "adam", "sgd"))
     ap.add_argument("--grad-clip", type=float, default=10.0)
     ap.add_argument("--train-neck", action="store_true", help="train the FPN neck (laterals, smooth blocks) as well")
+    ap.add_argument("--train-tail", action="store_true",
+                    help="with --train-neck: train the backbone's last stage (C4 tap -> C5 tap) as well")
+    ap.add_argument("--lr-tail", type=float, default=0.0, help="learning rate of the tail's parameters (default: --lr)")
     ap.add_argument("--amp", default="", choices=("", "fp16", "bf16"),
                     help="with --train-neck, YOLOLiteMS models: the dense neck's 3x3 GEMMs in this precision")
     ap.add_argument("--amp-heads", default="", choices=("", "fp16", "bf16"),
@@ -126,6 +137,8 @@ def main():
         raise SystemExit("give either --weights (with --data) or --synthetic NAME")
     if a.amp and not a.train_neck:
         raise SystemExit("--amp sets the precision of the trainable dense neck: it needs --train-neck")
+    if a.train_tail and not a.train_neck:
+        raise SystemExit("--train-tail feeds the tail's C5 to the trainable neck: it needs --train-neck")
     if a.synthetic:
         meta = zoo_meta(a.synthetic, num_classes=a.num_classes or 3, img_size=a.img_size or 128)
         sd = synth_state_dict(meta, seed=1)
@@ -149,14 +162,24 @@ def main():
     heads.to(a.device).train()
     # DetectNeck (arch YOLOLiteMS_CPU) refuses a reduced precision and says why
     neck = ya.neck_for(meta, sd, precision=a.amp or "fp32").to(a.device).train() if a.train_neck else None
+    # BackboneTail refuses, by name, a backbone whose last stage is not made of UIB / 1x1 ConvBnAct blocks
+    tail = ya.BackboneTail.from_state_dict(meta, sd).to(a.device).train() if a.train_tail else None
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
+    if tail is not None:                                   # a group of its own: its rate is --lr-tail
+        params = [{"params": params}, {"params": list(tail.parameters()), "lr": a.lr_tail or a.lr}]
     # fp16: dynamic loss scale (unscale, found-inf skip, growth / backoff in the step); bf16 has fp32's range: scale 1
     fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp="fp16" in (a.amp, a.amp_heads), lr=a.lr)
 
     def step(x, targets):
         # frozen trunk: plain tensors, nothing to backpropagate into
-        feats = model.pyramid(x) if neck is None else neck(model.features(x), layout="nhwc")
+        if neck is None:
+            feats = model.pyramid(x)
+        else:
+            cs = model.features(x)
+            if tail is not None:                           # the executor's C5 is replaced by the trainable tail's
+                cs = cs[:-2] + [cs[-2], tail(cs[-2], layout="nhwc")]
+            feats = neck(cs, layout="nhwc")
         fts.zero_grad()
         loss, parts = crit(heads(feats, layout="nhwc"), targets)
         fts.scale(loss).backward()                         # the identity unless --amp or --amp-heads is fp16
@@ -184,7 +207,7 @@ def main():
             print(f"epoch {ep:3d}  mean loss {tot / max(n, 1):.4f}  ({n} batches)")
 
     out_sd = dict(sd)
-    for mod in ([neck] if neck is not None else []) + [heads]:
+    for mod in [m for m in (tail, neck) if m is not None] + [heads]:
         for k, v in mod.state_dict().items():
             out_sd[k] = v.detach().cpu()
     out_sd = {k: (torch.as_tensor(v) if not torch.is_tensor(v) else v) for k, v in out_sd.items()}

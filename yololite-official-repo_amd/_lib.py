@@ -38,7 +38,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # YOLOLITE_HIP_LIB selects another build of the same ABI (kernel A/B runs); default: the in-tree library
 LIB_PATH = os.environ.get("YOLOLITE_HIP_LIB") or os.path.join(_HERE, "libyololite_hip.so")
 
-YL_ABI_VERSION = 6
+YL_ABI_VERSION = 7
 YL_MAX_LEVELS = 8
 YL_OK = 0
 ACT = {"none": 0, "relu": 1, "relu6": 2, "silu": 3, "gelu": 4, "relu_lab": 5}
@@ -210,6 +210,43 @@ class yl_dneck_plan_info(C.Structure):
                 ("table_bytes", C.c_int64)]
 
 
+YL_STAGE_MAX_BLOCKS = 16
+YL_STAGE_UIR, YL_STAGE_CN = 0, 1
+YL_STAGE_PASS_FORWARD, YL_STAGE_PASS_DGRAD, YL_STAGE_PASS_WGRAD = 0, 1, 2
+
+
+class yl_stage_block_cfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("type", "a", "k", "s", "mid", "cout", "reserved0", "reserved1")]
+
+
+class yl_stage_cfg(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("num_blocks", C.c_int32), ("eps", C.c_double),
+                ("block", yl_stage_block_cfg * YL_STAGE_MAX_BLOCKS)]
+
+
+class yl_stage_unit(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w", "gamma", "beta", "running_mean", "running_var", "num_batches_tracked")]
+
+
+class yl_stage_block(C.Structure):
+    _fields_ = [(n, yl_stage_unit) for n in ("dw_start", "pw_exp", "dw_mid", "pw_proj")]
+
+
+class yl_stage_tensors(C.Structure):
+    _fields_ = [("block", yl_stage_block * YL_STAGE_MAX_BLOCKS)]
+
+
+class yl_stage_block_plan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("size_in", "size_mid", "size_out", "rows_mid", "rows_out", "stat_tiles_mid",
+                                         "stat_tiles_out", "exp_rows", "exp_splits", "proj_rows", "proj_splits",
+                                         "units")] + [("saved_bytes", C.c_int64)]
+
+
+class yl_stage_plan_info(C.Structure):
+    _fields_ = [("stat_rows", C.c_int32), ("gemm_rows", C.c_int32), ("block", yl_stage_block_plan * YL_STAGE_MAX_BLOCKS),
+                ("saved_bytes", C.c_int64), ("nosave_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -294,6 +331,14 @@ SYMBOLS = [
     ("yl_dneck_backward", C.c_int32, [_vp, C.POINTER(yl_dneck_tensors), C.POINTER(yl_dneck_tensors), _vpp, _vpp, _vpp,
                                       C.c_int32, _ip, _vp, _ip]),
     ("yl_dneck_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("yl_stage_plan", C.c_int32, [C.POINTER(yl_stage_cfg), C.c_int32, C.c_int32, C.POINTER(yl_stage_plan_info)]),
+    ("yl_stage_create", C.c_int32, [C.c_int32, C.POINTER(yl_stage_cfg), C.POINTER(_vp)]),
+    ("yl_stage_destroy", None, [_vp]),
+    ("yl_stage_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("yl_stage_forward", C.c_int32, [_vp, C.POINTER(yl_stage_tensors), _vp, C.c_int32, C.c_int32, C.c_uint32, _vp, _vp, _ip]),
+    ("yl_stage_backward", C.c_int32, [_vp, C.POINTER(yl_stage_tensors), C.POINTER(yl_stage_tensors), _vp, _vp, _vp, _ip]),
+    ("yl_stage_depthwise", C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                       _ip]),
 ]
 # entries whose names carry a digit, bound like the others.  Listed apart: SYMBOLS is held, name for name, to what a
 # letters-only pattern finds declared in the header (tests/test_host_cpu.py), and that pattern does not see these

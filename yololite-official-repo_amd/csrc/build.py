@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-seventeen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+eighteen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
 library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
@@ -54,6 +54,9 @@ UNITS = [   # (source, extra flags, object name)
     ("yl_neck.hip", ["-ffp-contract=off"], "yl_neck.o"),
     # trainable dense FPN neck (YOLOLiteMS): dense 3x3 convolution with all three passes, BatchNorm + SiLU; the chain is yl_fpn.h
     ("yl_dneck.hip", ["-ffp-contract=off"], "yl_dneck.o"),
+    # trainable backbone stage (MobileNetV4 UIB blocks): depthwise k x k with stride in three passes, BatchNorm with and
+    # without ReLU, the residual; the 1x1 convolutions are the heads' GEMM (yl_block.h)
+    ("yl_stage.hip", ["-ffp-contract=off"], "yl_stage.o"),
 ]
 DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 
