@@ -1085,6 +1085,97 @@ yl_status yl_stage_depthwise(const float* a_dev, const float* b_dev, float* out_
                              int32_t stride, int32_t batch, int32_t size, int32_t channels, void* stream,
                              int32_t* launches);
 
+/* ---- trainable dense stem: a stack of dense convolutions, each followed by BatchNorm2d and ReLU --------------------------
+ * Forward and backward of up to YL_STEM_MAX_UNITS units, fp32 throughout.  A unit is a bias-free dense k x k convolution,
+ * k in {1, 3}, stride s in {1, 2}, padding (k - 1) / 2 on every side (S_out = (S + 2 p - k) / s + 1, odd S included), its
+ * BatchNorm2d and a ReLU.  Activations are square NHWC maps [B][S][S][C] with C a multiple of 4; with input_nchw = 1 the
+ * stack's input alone is planar [B][cin][S][S], cin in 1..4 (the image): forward and weight gradient read it, its own
+ * gradient does not exist (dx_dev with input_nchw: YL_ERR_INVALID).  Every cout is a multiple of 4.  Residuals, other
+ * activations and TF-SAME padding do not exist here.  Anything else is YL_ERR_INVALID from a host-side check before any
+ * device call.  Parameters are read in PyTorch layout ([cout][cin][k][k]) from the caller's tensors on every call, at any
+ * 4-byte boundary; x (NHWC) / out / gy / dx are 16-byte aligned (else YL_ERR_UNSUPPORTED), a planar x 4-byte aligned.
+ * The 3x3 passes are implicit GEMMs on v_mfma_f32_16x16x4_f32 over spatial tiles of conv_tile x conv_tile pixels; the
+ * GEMM's k index runs (tap, c) with c fastest and every tap's c padded to a multiple of 4; a weight pack kernel writes
+ * that order once per call.  Input gradient under stride 2: four parity classes of input pixels, each a GEMM of its own
+ * over 1, 2, 2, 4 taps (no zero insertion, no atomics).  Weight gradient: fp32 partials part[split][tap][n][c] over whole
+ * spatial tiles, summed in split order in float64.  The 1x1 units are the heads' GEMM in all three passes (stride 2:
+ * the rows read / write every second pixel; its input gradient zeroes dx first).  BatchNorm numerics are the stage's
+ * (yl_stage_*), with one difference: a unit's statistics tiles hold stat_rows_u = stat_rows * ceil(ceil(M_u / stat_rows)
+ * / stat_tiles_max) rows, so that no unit has more than stat_tiles_max tiles; partials are float64, summed in tile order.
+ * Equal inputs give equal bits: no floating-point atomics. */
+#define YL_STEM_MAX_UNITS 8
+typedef struct yl_stem yl_stem;
+typedef struct yl_stem_unit_cfg {
+  int32_t k, s, cout, reserved0;
+} yl_stem_unit_cfg;
+typedef struct yl_stem_cfg {
+  int32_t in_channels;              /* cin of unit 0 */
+  int32_t num_units;                /* 1..YL_STEM_MAX_UNITS */
+  int32_t input_nchw;               /* 1: x is planar [B][cin][S][S], cin in 1..4 */
+  int32_t reserved0;
+  double eps;                       /* of every BatchNorm */
+  yl_stem_unit_cfg unit[YL_STEM_MAX_UNITS];
+} yl_stem_cfg;
+typedef struct yl_stem_tensors {    /* the parameters, or where their gradients go (NULL = not wanted) */
+  yl_stage_unit unit[YL_STEM_MAX_UNITS];
+} yl_stem_tensors;
+typedef struct yl_stem_unit_plan {
+  int32_t size_in, size_out;        /* S entering and leaving the unit */
+  int32_t rows_out;                 /* M_u = batch * size_out^2 */
+  int32_t stat_rows, stat_tiles;    /* stat_rows_u (above); ceil(M_u / stat_rows_u) <= stat_tiles_max */
+  int32_t wgrad_rows, wgrad_splits; /* 1x1: rows per split and splits as the heads cut a cin x cout weight gradient over M_u
+                                       rows.  3x3: spatial tiles per split and splits: with tiles = batch * ceil(size_out /
+                                       conv_tile)^2, blocks = ceil(round4(cin) / 32) * ceil(cout / 64) and want =
+                                       clamp(1024 / blocks, 1, tiles): wgrad_rows = ceil(tiles / want), splits = ceil(tiles / wgrad_rows) */
+  int32_t conv_block;               /* 3x3: output channels per workgroup, 16 PT with the PT of {4, 3, 2} that minimises
+                                       ceil(cout / (16 PT)) PT (ties: the larger PT); 1x1: 0 */
+  int64_t saved_bytes;              /* 2 M_u C_u 4 + 2 C_u 4: z, h and (mean, invstd); C_u = cout */
+} yl_stem_unit_plan;
+typedef struct yl_stem_plan_info {
+  int32_t stat_rows, gemm_rows, conv_tile, stat_tiles_max;
+  yl_stem_unit_plan unit[YL_STEM_MAX_UNITS];
+  int64_t saved_bytes;              /* YL_HEAD_SAVE: round16(M_0 C_0 4) (a copy of x) + the units' saved_bytes.  The edge_n
+                                       stem at batch 64, 640 px keeps 2.67 GB: 2.36 GB of z and h, 0.84 GB each for unit 0's,
+                                       and the 0.31 GB copy of x */
+  int64_t nosave_bytes;             /* without: 3 Amax + 2 Cmax 4; Amax = max_u M_u C_u 4 (one z, two alternating h), Cmax = max_u C_u */
+  int64_t workspace_bytes;          /* 2 Amax                                         two alternating gradients
+                                       + max_u round16(stat_tiles_u 2 C_u 8)         float64 partials
+                                       + 2 Cmax 4                                    the BatchNorm backward's coefficients
+                                       + max over 3x3 units of round16(9 cout round4(cin) 4)      the packed weight
+                                       + max_u round16(splits_u W_u 4), W_u = cin cout (1x1), 9 cout round4(cin) (3x3) */
+} yl_stem_plan_info;
+/* A pure host function.  YL_ERR_UNSUPPORTED: a shape beyond the kernels' index arithmetic (a 1x1 unit of more than
+ * 65535 * gemm_rows rows among them). */
+yl_status yl_stem_plan(const yl_stem_cfg* cfg, int32_t batch, int32_t size, yl_stem_plan_info* out);
+yl_status yl_stem_create(int32_t device, const yl_stem_cfg* cfg, yl_stem** out);
+void yl_stem_destroy(yl_stem* h);
+yl_status yl_stem_held(const yl_stem* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held);
+/* Enqueues the forward.  Launches per unit: convolution (3x3: 2, pack and convolution; 1x1: 1) + [1 column sums with
+ * YL_HEAD_TRAIN] + 2 (BatchNorm statistics, BatchNorm + ReLU); with YL_HEAD_SAVE two device-to-device copies besides (x
+ * in, the last h out; not counted).  x_dev: [B][size][size][in_channels], or planar with input_nchw; out_dev:
+ * [B][S_out][S_out][cout of the last unit], written.  `flags`: YL_HEAD_TRAIN, YL_HEAD_SAVE; any other bit (the precision
+ * bits among them) is YL_ERR_INVALID.  YL_HEAD_TRAIN with a unit of ONE output row: YL_ERR_INVALID before any launch.
+ * One forward is held per handle. */
+yl_status yl_stem_forward(yl_stem* h, const yl_stem_tensors* params, const float* x_dev, int32_t batch, int32_t size,
+                          uint32_t flags, float* out_dev, void* stream, int32_t* launches);
+/* Enqueues the backward of the held forward (YL_ERR_STATE if there is none).  Every non-NULL tensor of `grads` and
+ * dx_dev (may be NULL; must be NULL with input_nchw) is OVERWRITTEN.  The units are walked last first down to the first
+ * one something is wanted of (unit 0 with dx_dev); nothing upstream of it runs.  Per unit: [1 sums if train or gamma /
+ * beta wanted] + 1 (bn grads) + 1 (dz) + [2 if w wanted: partials, ordered sum] + [the input gradient, if the walk goes
+ * on: 1x1: 1 (stride 2: and a memset, not counted); 3x3 stride 1: 2 (pack, convolution); 3x3 stride 2: 1 + C (pack, one
+ * convolution per parity class that has pixels: C = 4 if size_in >= 2, else 1)]. */
+yl_status yl_stem_backward(yl_stem* h, const yl_stem_tensors* params, const yl_stem_tensors* grads, const float* gy_dev,
+                           float* dx_dev, void* stream, int32_t* launches);
+/* ONE convolution pass on its own, launched exactly as the module launches it, on the current device: `pass` is a
+ * YL_STAGE_PASS_* (FORWARD: a = x, b = W -> y; DGRAD: a = dy, b = W -> dx; WGRAD: a = x, b = dy -> dW), W is
+ * [cout][cin][k][k], `size` the FORWARD's input size S.  input_nchw: x is planar, cin in 1..4; DGRAD is then
+ * YL_ERR_INVALID.  Launch counts as in yl_stem_forward / yl_stem_backward.  Packed weight and partials live in a temporary
+ * buffer that is freed before the call returns, which waits for `stream`.  A weight and a planar x may start at any
+ * 4-byte boundary, every other tensor is 16-byte aligned (else YL_ERR_UNSUPPORTED). */
+yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,
+                       int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, void* stream,
+                       int32_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

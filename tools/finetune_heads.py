@@ -7,6 +7,7 @@
     python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
                                    [--train-neck [--amp fp16|bf16] [--train-tail [--lr-tail 1e-4]]] [--amp-heads fp16|bf16]
+                                   [--train-neck --train-backbone [--lr-backbone 1e-4]]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
@@ -36,6 +37,12 @@ ConvBnAct between the C4 and the C5 tap, starts from the checkpoint's `backbone.
 parameters are a FusedTrainStep group of their own with the rate --lr-tail (default: --lr), and its state_dict is merged
 into the output.  The tail is fp32; --amp / --amp-heads go with it: nothing in the code ties the precision of the
 neck's or the heads' GEMMs to the tail's, and the loss scale reaches its gradients through the chain like any others.
+
+With --train-backbone (needs --train-neck, implies --train-tail; the same backbones) the WHOLE backbone is trained:
+stageops.MobileNetV4Backbone holds the stem (stemops.BackboneStem, csrc/yl_stem.hip: image -> C3), the C3 -> C4 stage
+(stageops.BackboneMid) and the tail, starts from the checkpoint's `backbone.*` entries, and the step runs
+`neck(backbone(x))`: the executor is out of the loop.  The backbone's parameters are a FusedTrainStep group of their own
+with the rate --lr-backbone (default: --lr), and its state_dict is merged into the output.  The backbone is fp32.
 
 --amp-heads fp16 | bf16 (with or without --train-neck): DetectHeads runs every 1x1 GEMM of the heads in that precision, on
 the same terms.  The loss scale is on when either of --amp and --amp-heads is fp16.
@@ -127,6 +134,9 @@ def main():
     ap.add_argument("--train-tail", action="store_true",
                     help="with --train-neck: train the backbone's last stage (C4 tap -> C5 tap) as well")
     ap.add_argument("--lr-tail", type=float, default=0.0, help="learning rate of the tail's parameters (default: --lr)")
+    ap.add_argument("--train-backbone", action="store_true",
+                    help="with --train-neck: train the whole backbone (image -> C3, C4, C5); implies --train-tail")
+    ap.add_argument("--lr-backbone", type=float, default=0.0, help="learning rate of the backbone's parameters (default: --lr)")
     ap.add_argument("--amp", default="", choices=("", "fp16", "bf16"),
                     help="with --train-neck, YOLOLiteMS models: the dense neck's 3x3 GEMMs in this precision")
     ap.add_argument("--amp-heads", default="", choices=("", "fp16", "bf16"),
@@ -139,6 +149,8 @@ def main():
         raise SystemExit("--amp sets the precision of the trainable dense neck: it needs --train-neck")
     if a.train_tail and not a.train_neck:
         raise SystemExit("--train-tail feeds the tail's C5 to the trainable neck: it needs --train-neck")
+    if a.train_backbone and not a.train_neck:
+        raise SystemExit("--train-backbone feeds the backbone's maps to the trainable neck: it needs --train-neck")
     if a.synthetic:
         meta = zoo_meta(a.synthetic, num_classes=a.num_classes or 3, img_size=a.img_size or 128)
         sd = synth_state_dict(meta, seed=1)
@@ -163,11 +175,15 @@ def main():
     # DetectNeck (arch YOLOLiteMS_CPU) refuses a reduced precision and says why
     neck = ya.neck_for(meta, sd, precision=a.amp or "fp32").to(a.device).train() if a.train_neck else None
     # BackboneTail refuses, by name, a backbone whose last stage is not made of UIB / 1x1 ConvBnAct blocks
-    tail = ya.BackboneTail.from_state_dict(meta, sd).to(a.device).train() if a.train_tail else None
+    tail = ya.BackboneTail.from_state_dict(meta, sd).to(a.device).train() if a.train_tail and not a.train_backbone else None
+    # MobileNetV4Backbone (stem, C3 -> C4 stage and the tail in one) refuses the other backbone families by name as well
+    backbone = ya.MobileNetV4Backbone.from_state_dict(meta, sd).to(a.device).train() if a.train_backbone else None
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
     if tail is not None:                                   # a group of its own: its rate is --lr-tail
         params = [{"params": params}, {"params": list(tail.parameters()), "lr": a.lr_tail or a.lr}]
+    if backbone is not None:                               # likewise: --lr-backbone
+        params = [{"params": params}, {"params": list(backbone.parameters()), "lr": a.lr_backbone or a.lr}]
     # fp16: dynamic loss scale (unscale, found-inf skip, growth / backoff in the step); bf16 has fp32's range: scale 1
     fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp="fp16" in (a.amp, a.amp_heads), lr=a.lr)
 
@@ -175,6 +191,8 @@ def main():
         # frozen trunk: plain tensors, nothing to backpropagate into
         if neck is None:
             feats = model.pyramid(x)
+        elif backbone is not None:                         # image -> [c3, c4, c5], every stage trainable: no executor
+            feats = neck(backbone(x), layout="nhwc")
         else:
             cs = model.features(x)
             if tail is not None:                           # the executor's C5 is replaced by the trainable tail's
@@ -207,7 +225,7 @@ def main():
             print(f"epoch {ep:3d}  mean loss {tot / max(n, 1):.4f}  ({n} batches)")
 
     out_sd = dict(sd)
-    for mod in [m for m in (tail, neck) if m is not None] + [heads]:
+    for mod in [m for m in (backbone, tail, neck) if m is not None] + [heads]:
         for k, v in mod.state_dict().items():
             out_sd[k] = v.detach().cpu()
     out_sd = {k: (torch.as_tensor(v) if not torch.is_tensor(v) else v) for k, v in out_sd.items()}

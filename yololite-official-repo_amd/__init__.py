@@ -18,7 +18,8 @@ from .lossops import LossAF, targets_to_xyxy_px  # noqa: F401
 from .trainops import FusedTrainStep  # noqa: F401
 from .headops import DetectHeads  # noqa: F401
 from .neckops import DetectNeck, DetectNeckMS, neck_for  # noqa: F401
-from .stageops import BackboneTail, UIBStack  # noqa: F401
+from .stageops import BackboneMid, BackboneTail, MobileNetV4Backbone, UIBStack  # noqa: F401
+from .stemops import BackboneStem, ConvStack  # noqa: F401
 from .tracker import KalmanSortTracker, TrackerBank  # noqa: F401
 from .serving import ServingPipeline  # noqa: F401
 
@@ -26,5 +27,5 @@ __all__ = ["YoloLiteHipError", "load_library", "HipContext", "YOLOLiteHIP", "bui
            "load_model_names_imgsize_from_ckpt", "decode_preds_anchorfree", "_decode_batch_to_coco_dets",
            "decode_anchorfree_like_train", "infer_main_postprocess", "nms", "predict_main", "predict_coco_dets", "build_program", "Program", "BACKBONES",
            "preprocess_batch", "letterbox_geometry", "build_curves_from_coco", "create_confusion_matrix",
-           "coco_eval", "_coco_eval_from_lists", "coco_summary_lines", "LossAF", "targets_to_xyxy_px", "FusedTrainStep", "DetectHeads", "DetectNeck", "DetectNeckMS", "neck_for", "UIBStack", "BackboneTail",
+           "coco_eval", "_coco_eval_from_lists", "coco_summary_lines", "LossAF", "targets_to_xyxy_px", "FusedTrainStep", "DetectHeads", "DetectNeck", "DetectNeckMS", "neck_for", "UIBStack", "BackboneTail", "BackboneMid", "MobileNetV4Backbone", "ConvStack", "BackboneStem",
            "KalmanSortTracker", "TrackerBank", "ServingPipeline"]

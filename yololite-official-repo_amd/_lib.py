@@ -247,6 +247,33 @@ class yl_stage_plan_info(C.Structure):
                 ("saved_bytes", C.c_int64), ("nosave_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
 
 
+YL_STEM_MAX_UNITS = 8
+
+
+class yl_stem_unit_cfg(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("k", "s", "cout", "reserved0")]
+
+
+class yl_stem_cfg(C.Structure):
+    _fields_ = [("in_channels", C.c_int32), ("num_units", C.c_int32), ("input_nchw", C.c_int32), ("reserved0", C.c_int32),
+                ("eps", C.c_double), ("unit", yl_stem_unit_cfg * YL_STEM_MAX_UNITS)]
+
+
+class yl_stem_tensors(C.Structure):
+    _fields_ = [("unit", yl_stage_unit * YL_STEM_MAX_UNITS)]
+
+
+class yl_stem_unit_plan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("size_in", "size_out", "rows_out", "stat_rows", "stat_tiles", "wgrad_rows",
+                                         "wgrad_splits", "conv_block")] + [("saved_bytes", C.c_int64)]
+
+
+class yl_stem_plan_info(C.Structure):
+    _fields_ = [("stat_rows", C.c_int32), ("gemm_rows", C.c_int32), ("conv_tile", C.c_int32), ("stat_tiles_max", C.c_int32),
+                ("unit", yl_stem_unit_plan * YL_STEM_MAX_UNITS),
+                ("saved_bytes", C.c_int64), ("nosave_bytes", C.c_int64), ("workspace_bytes", C.c_int64)]
+
+
 # every symbol include/yololite_hip.h declares: (name, restype, argtypes)
 _vp = C.c_void_p
 _vpp = C.POINTER(C.c_void_p)
@@ -339,6 +366,13 @@ SYMBOLS = [
     ("yl_stage_backward", C.c_int32, [_vp, C.POINTER(yl_stage_tensors), C.POINTER(yl_stage_tensors), _vp, _vp, _vp, _ip]),
     ("yl_stage_depthwise", C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
                                        _ip]),
+    ("yl_stem_plan", C.c_int32, [C.POINTER(yl_stem_cfg), C.c_int32, C.c_int32, C.POINTER(yl_stem_plan_info)]),
+    ("yl_stem_create", C.c_int32, [C.c_int32, C.POINTER(yl_stem_cfg), C.POINTER(_vp)]),
+    ("yl_stem_destroy", None, [_vp]),
+    ("yl_stem_held", C.c_int32, [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip]),
+    ("yl_stem_forward", C.c_int32, [_vp, C.POINTER(yl_stem_tensors), _vp, C.c_int32, C.c_int32, C.c_uint32, _vp, _vp, _ip]),
+    ("yl_stem_backward", C.c_int32, [_vp, C.POINTER(yl_stem_tensors), C.POINTER(yl_stem_tensors), _vp, _vp, _vp, _ip]),
+    ("yl_stem_conv", C.c_int32, [_vp, _vp, _vp] + [C.c_int32] * 8 + [_vp, _ip]),
 ]
 # entries whose names carry a digit, bound like the others.  Listed apart: SYMBOLS is held, name for name, to what a
 # letters-only pattern finds declared in the header (tests/test_host_cpu.py), and that pattern does not see these

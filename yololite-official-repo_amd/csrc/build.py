@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-eighteen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+nineteen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
 library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
@@ -57,8 +57,11 @@ UNITS = [   # (source, extra flags, object name)
     # trainable backbone stage (MobileNetV4 UIB blocks): depthwise k x k with stride in three passes, BatchNorm with and
     # without ReLU, the residual; the 1x1 convolutions are the heads' GEMM (yl_block.h)
     ("yl_stage.hip", ["-ffp-contract=off"], "yl_stage.o"),
+    # trainable dense stem (image -> C3): dense 3x3 convolution with stride in three passes on fp32 MFMA, strided 1x1 units on
+    # the heads' GEMM; BatchNorm + ReLU are yl_bn.h, shared with yl_stage.hip
+    ("yl_stem.hip", ["-ffp-contract=off"], "yl_stem.o"),
 ]
-DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]
+DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_bn.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 
 
 def _hipcc():

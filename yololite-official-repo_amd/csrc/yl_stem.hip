@@ -1,0 +1,831 @@
+// Trainable dense stem: a stack of bias-free dense k x k convolutions (k in {1, 3}, stride in {1, 2}), each followed by
+// BatchNorm2d and ReLU, forward and backward on NHWC fp32 rows (include/yololite_hip.h, yl_stem_*).  The stack's input
+// may be the planar image [B][cin][S][S], cin in 1..4, which forward and weight gradient read and no gradient exists of.
+//
+//   unit u:  z = conv(x_u)   h = relu(bn(z))          x_u: the previous unit's h (the caller's x for unit 0)
+//
+// BatchNorm, ReLU, the column sums and the BatchNorm backward are yl_bn.h's (shared with yl_stage.hip), the 1x1 units the
+// heads' GEMM (yl_block.h: launch_gemm<0>) with accessors of their own where the unit strides or reads the planar image.
+// New here: the 3x3 convolution in three passes.
+//
+// ---- 3x3 forward and input gradient: ONE kernel, an implicit GEMM on v_mfma_f32_16x16x4_f32 in the orientation of
+// yl_dneck_conv_kernel (weights: A operand, pixels: B operand; a lane ends with four consecutive output channels of one
+// pixel: one 16-byte NHWC store).  The kernel gathers: output pixel (a, b) of a CLASS of destination pixels sums, over a
+// tap table (ty, tx) in 0..nty-1 x 0..ntx-1, wp[tap][n][c] * src[ST a + o0 + ty][ST b + o0 + tx][c], zero outside src,
+// and lands at dst[os a + poy][os b + pox]:
+//   forward, stride s:        ST = s, o0 = -1, 3 x 3 taps (ky, kx) = (ty, tx), every output pixel (os = 1)
+//   input gradient, stride 1: ST = 1, o0 = -1, 3 x 3 taps (ky, kx) = (2 - ty, 2 - tx), pack transposed (cin <-> cout)
+//   input gradient, stride 2: no zero insertion and no atomics.  Input pixel (i, j) receives tap ky from output row
+//     (i + 1 - ky) / 2 when that is even-numerator, so the pixels fall into four parity classes (pi, pj) = (i & 1, j & 1)
+//     of (1 + pi) (1 + pj) = 1, 2, 2, 4 taps.  Class pixel a is input row 2 a + pi (os = 2, poy = pi); along y it reads
+//     dz row a + ty with ky = 1 (pi = 0; one tap) or ky = 2 - 2 ty (pi = 1; ty = 0, 1): a stride-1 gather (ST = 1,
+//     o0 = 0) over dz.  A row a + ty >= S_out lies outside src and is read as zero: the dropped taps of an odd S.
+// The k index of the GEMM runs (tap, c), c fastest; each tap's c is padded to a multiple of 4 (cp), so the planar image of
+// 3 channels has K = 9 x 4 = 36 of which 27 are not zero.  yl_stem_pack_kernel writes wp[tap][n][cp] once per call from the
+// caller's PyTorch-layout tensor, which may start at any 4-byte boundary.
+// Workgroup: a tile of T x T = 8 x 8 class pixels of ONE image x a block of 16 PT output channels, PT in {2, 3, 4} (the
+// one that pads cout least; cout is 16..96 here: 32 -> one block of 32, 64 -> one of 64, 96 -> two of 48); wave w owns
+// tile rows 2 w, 2 w + 1, lane (kq, i): pixel (2 w + (i >> 3), i & 7), k quad kq.
+// LDS window: (ST (T - 1) + 3)^2 source pixels, 10 x 10 or 17 x 17, zeros for pixels outside the image.
+//   NHWC source: per k-block of 16 channels, FOUR planes win[kq][pixel][4 floats], a plane PL pixels (PL % 16 == 0), a
+//   window row RP stored pixels; under ST = 2 a row holds its even columns first and then its odd ones (column wx at
+//   (wx & 1) 9 + (wx >> 1)), so the eight pixels of a lane row, two window columns apart, are consecutive for every tap.
+//   Bank arithmetic of the tap read (ds_read_b128: four groups of 16 lanes, bank = dword % 64, i.e. 16 slots of 16 bytes;
+//   group 0 is lanes 0-3, 12-15, 20-27 = (kq 0: i 0-3, 12-15) and (kq 1: i 4-11), the others alike): a lane's slot is
+//   kq PL + q(i) + tap offset mod 16 with q(i) = ST RP (i >> 3) + (i & 7).  ST RP = 24 (ST = 1, RP = 24) or 40 (ST = 2,
+//   RP = 20), both 8 mod 16, so q(i) takes all sixteen residues over i = 0..15 and a group's sixteen lanes hit sixteen
+//   slots: no conflict, for every tap, at both strides.  (The stride-1 pitch without the parity split gives q = 2 (i & 7)
+//   under stride 2: eight residues, 2-way.)
+//   Planar source: one plane win[pixel][4] (channel c of the pixel, zero for c >= cin), staged plane by plane with
+//   consecutive threads along x; a k step is FOUR TAPS (lane kq: tap 4 step + kq), 3 steps for 9 taps.  The lanes of a
+//   group then read q(i) + their own tap's offset: by the code at most 2-way, not measured.
+//
+// ---- 3x3 weight gradient: dW[n][c][ky][kx] = sum_m dz[m][n] x[s m + tap - 1][c].  The pixel is the MFMA's k index.
+// Workgroup (block of GC = 32 input channels, block of GN = 64 output channels, split); wave w owns n0 + 16 w .. + 15; per
+// spatial tile of 8 x 8 OUTPUT pixels the x window [pixel][GXS = 36] and the dz tile [pixel][GDS = 68] are staged once
+// and all nine taps read them (ds_read_b32, banks per 32-lane half: lanes i are consecutive channels, kq 0 and kq 1 are
+// four stored pixels apart, 4 x 36 = 144 and 4 x 68 = 272, both 16 mod 32: no conflict; the parity split keeps "four class
+// pixels" at four stored pixels under stride 2).  part[split][tap][n][cp] in fp32 over whole tiles, then an ordered float64
+// sum in split order: equal inputs give equal bits.  The split count fills the chip (about 1024 workgroups).
+#include <new>
+
+#include "yl_bn.h"
+
+namespace {
+
+constexpr int ST_T = 8;                  // spatial tile edge
+constexpr int SKB = 16;                  // channels per k-block
+constexpr int STAT_TILES_MAX = 1024;     // tiles of a unit's row reductions
+constexpr int GC = 32, GXS = GC + 4, GN = 64, GDS = GN + 4;
+
+template <int ST> struct Win {
+  static constexpr int WE = ST * (ST_T - 1) + 3;           // window edge: 10 / 17
+  static constexpr int WH = (WE + 1) / 2;                  // ST == 2: stored column of the first odd window column
+  static constexpr int RP = ST == 1 ? 24 : 20;             // stored pixels per window row: ST * RP == 8 mod 16
+  static constexpr int PL = (WE * RP + 15) / 16 * 16;      // pixels per plane
+  static __device__ __forceinline__ int col(int wx) { return ST == 1 ? wx : (wx & 1) * WH + (wx >> 1); }
+  static __device__ __forceinline__ int at(int wy, int wx) { return wy * RP + col(wx); }      // convolution window
+  static __device__ __forceinline__ int gat(int wy, int wx) { return wy * WE + col(wx); }     // weight-gradient window
+};
+static_assert((1 * Win<1>::RP) % 16 == 8 && (2 * Win<2>::RP) % 16 == 8, "the lane rows are 8 slots apart");
+static_assert(Win<1>::RP >= Win<1>::WE && Win<2>::RP >= Win<2>::WE, "a window row fits its pitch");
+
+struct PackP { int ntap; int ky[9], kx[9]; };
+// w [O][I][3][3] (PyTorch) -> wp[tap][a][b], b padded with zeros from Bn to Bp.  T == 0: W[a][b][tap] (a = out, b = in);
+// T == 1: W[b][a][tap] (a = in, b = out); the tap table says which (ky, kx) a packed tap is
+__global__ __launch_bounds__(NT) void yl_stem_pack_kernel(const float* __restrict__ w, float* __restrict__ wp, int A, int Bn,
+                                                         int Bp, int T, PackP tp) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  const long AB = (long)A * Bp;
+  if (idx >= tp.ntap * AB) return;
+  const int tap = (int)(idx / AB);
+  const long ab = idx - tap * AB;
+  const int a = (int)(ab / Bp), b = (int)(ab - (long)a * Bp);
+  float v = 0.f;
+  if (b < Bn) {
+    const long oi = T ? (long)b * A + a : (long)a * Bn + b;
+    v = w[oi * 9 + tp.ky[tap] * 3 + tp.kx[tap]];
+  }
+  wp[idx] = v;
+}
+
+struct ConvP {
+  const float* src; const float* wp; float* dst;
+  int Ss, Cs, Cp, N, Sd;                 // source edge, channels (planes), channels per packed tap; output channels, edge
+  int TY, TXn;                           // tiles along y and x
+  int ey, ex;                            // class pixels along y and x
+  int os, poy, pox;                      // class pixel (a, b) -> destination pixel (os a + poy, os b + pox)
+  int o0;                                // class pixel a, tap ty -> source row ST a + o0 + ty
+  int nty, ntx;
+};
+// grid (B * TY * TXn, ceil(N / (16 PT)))
+template <int ST, int PT, bool PLANAR>
+__global__ __launch_bounds__(NT) void yl_stem_conv_kernel(ConvP P) {
+  typedef Win<ST> W;
+  constexpr int WE = W::WE;
+  __shared__ __attribute__((aligned(16))) float win[(PLANAR ? 1 : 4) * W::PL * 4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, kq = lane >> 4, i = lane & 15;
+  const int tiles = P.TY * P.TXn;
+  const int b = blockIdx.x / tiles, tr = blockIdx.x - b * tiles;
+  const int ty0 = (tr / P.TXn) * ST_T, tx0 = (tr % P.TXn) * ST_T;
+  const int n0 = blockIdx.y * (16 * PT);
+  const int row = 2 * wave + (i >> 3), col = i & 7;
+  const int sy0 = ty0 * ST + P.o0, sx0 = tx0 * ST + P.o0;  // the window's first source pixel
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  // NHWC: one accumulator per tap, summed pairwise at the end: a chain is the 4 ceil(Cs / 16) MFMAs of ONE tap, not of nine
+  constexpr int NA = PLANAR ? 1 : 9;
+  f32x4 acc[NA][PT];
+#pragma unroll
+  for (int a = 0; a < NA; ++a)
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) acc[a][pt] = zero;
+  if constexpr (PLANAR) {
+    for (int item = t; item < 4 * WE * WE; item += NT) {   // plane by plane, consecutive threads along x
+      const int c = item / (WE * WE), pw = item - c * (WE * WE), wy = pw / WE, wx = pw - wy * WE;
+      const int gy = sy0 + wy, gx = sx0 + wx;
+      float v = 0.f;
+      if (c < P.Cs && gy >= 0 && gy < P.Ss && gx >= 0 && gx < P.Ss) v = P.src[(((long)b * P.Cs + c) * P.Ss + gy) * P.Ss + gx];
+      win[W::at(wy, wx) * 4 + c] = v;
+    }
+    __syncthreads();
+    const int ntap = P.nty * P.ntx;
+    for (int t0 = 0; t0 < ntap; t0 += 4) {
+      const int tap = t0 + kq;
+      const bool on = tap < ntap;
+      const int ty = on ? tap / P.ntx : 0, tx = on ? tap - ty * P.ntx : 0;
+      const f32x4 qv = on ? ld4(&win[W::at(row * ST + ty, col * ST + tx) * 4]) : zero;
+      f32x4 pv[PT];
+#pragma unroll
+      for (int pt = 0; pt < PT; ++pt) {
+        const int n = n0 + 16 * pt + i;
+        pv[pt] = (on && n < P.N) ? ld4(P.wp + ((long)tap * P.N + n) * 4) : zero;
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) acc[0][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[0][pt], 0, 0, 0);
+    }
+  } else {
+    const int nkb = (P.Cs + SKB - 1) / SKB;
+    for (int kb = 0; kb < nkb; ++kb) {
+      const int c0 = kb * SKB;
+      if (kb) __syncthreads();           // the previous k-block's reads are done
+      for (int item = t; item < 4 * WE * WE; item += NT) {
+        const int pw = item >> 2, q = item & 3, wy = pw / WE, wx = pw - wy * WE;
+        const int gy = sy0 + wy, gx = sx0 + wx;
+        const bool ok = gy >= 0 && gy < P.Ss && gx >= 0 && gx < P.Ss && c0 + 4 * q < P.Cs;
+        st4(&win[(q * W::PL + W::at(wy, wx)) * 4], ok ? ld4(P.src + (((long)b * P.Ss + gy) * P.Ss + gx) * P.Cs + c0 + 4 * q) : zero);
+      }
+      __syncthreads();
+      const int c = c0 + 4 * kq;
+#pragma unroll
+      for (int ty = 0; ty < 3; ++ty)
+#pragma unroll
+        for (int tx = 0; tx < 3; ++tx) {
+          if (ty >= P.nty || tx >= P.ntx) continue;        // uniform: the accumulators are indexed by constants
+          const int tap = ty * P.ntx + tx;
+          const f32x4 qv = ld4(&win[(kq * W::PL + W::at(row * ST + ty, col * ST + tx)) * 4]);
+          f32x4 pv[PT];
+#pragma unroll
+          for (int pt = 0; pt < PT; ++pt) {
+            const int n = n0 + 16 * pt + i;
+            pv[pt] = (n < P.N && c < P.Cp) ? ld4(P.wp + ((long)tap * P.N + n) * P.Cp + c) : zero;
+          }
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int pt = 0; pt < PT; ++pt)
+              acc[ty * 3 + tx][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[ty * 3 + tx][pt], 0, 0, 0);
+        }
+    }
+    if constexpr (!PLANAR) {             // ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) + 8; a tap that does not exist is zero
+#pragma unroll
+      for (int pt = 0; pt < PT; ++pt)
+        acc[0][pt] = (((acc[0][pt] + acc[1][pt]) + (acc[2][pt] + acc[3][pt])) + ((acc[4][pt] + acc[5][pt]) + (acc[6][pt] + acc[7][pt]))) +
+                     acc[8 % NA][pt];
+    }
+  }
+  const int ay = ty0 + row, ax = tx0 + col;
+  if (ay < P.ey && ax < P.ex) {
+    float* o = P.dst + (((long)b * P.Sd + ay * P.os + P.poy) * P.Sd + ax * P.os + P.pox) * P.N;
+#pragma unroll
+    for (int pt = 0; pt < PT; ++pt) {
+      const int n = n0 + 16 * pt + 4 * kq;
+      if (n < P.N) st4(o + n, acc[0][pt]);
+    }
+  }
+}
+
+struct WgP {
+  const float* x; const float* dz; float* part;
+  int S, So, Cs, Cp, N, TX, ntiles, tps; // x edge, dz edge, x channels (planes), padded; dz channels; tiles per edge, in all, per split
+};
+// grid (ceil(Cp / GC), ceil(N / GN), splits); PTC c-tiles of 16 per lane (planar: 1, the image has at most 4 channels)
+template <int ST, bool PLANAR>
+__global__ __launch_bounds__(NT) void yl_stem_wgrad_kernel(WgP P) {
+  typedef Win<ST> W;
+  constexpr int WE = W::WE, PTC = PLANAR ? 1 : GC / 16;
+  __shared__ __attribute__((aligned(16))) float xw[WE * WE * GXS];
+  __shared__ __attribute__((aligned(16))) float dzt[ST_T * ST_T * GDS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, kq = lane >> 4, i = lane & 15;
+  const int c0 = blockIdx.x * GC, n0 = blockIdx.y * GN;
+  const int tbeg = blockIdx.z * P.tps;
+  const int tend = tbeg + P.tps < P.ntiles ? tbeg + P.tps : P.ntiles;
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[9][PTC];
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int pt = 0; pt < PTC; ++pt) acc[tap][pt] = zero;
+  if constexpr (PLANAR) {                // channels 4 .. 15 of the window stay zero
+    for (int item = t; item < WE * WE * (GXS / 4); item += NT) st4(&xw[item * 4], zero);
+  }
+  for (int tile = tbeg; tile < tend; ++tile) {
+    const int b = tile / (P.TX * P.TX), tr = tile - b * P.TX * P.TX, ty0 = (tr / P.TX) * ST_T, tx0 = (tr % P.TX) * ST_T;
+    const int sy0 = ty0 * ST - 1, sx0 = tx0 * ST - 1;
+    __syncthreads();                     // the previous tile's reads (the zero fill) are done
+    if constexpr (PLANAR) {
+      for (int item = t; item < 4 * WE * WE; item += NT) {
+        const int c = item / (WE * WE), pw = item - c * (WE * WE), wy = pw / WE, wx = pw - wy * WE;
+        const int gy = sy0 + wy, gx = sx0 + wx;
+        float v = 0.f;
+        if (c < P.Cs && gy >= 0 && gy < P.S && gx >= 0 && gx < P.S) v = P.x[(((long)b * P.Cs + c) * P.S + gy) * P.S + gx];
+        xw[W::gat(wy, wx) * GXS + c] = v;
+      }
+    } else {
+      for (int item = t; item < WE * WE * (GC / 4); item += NT) {
+        const int pw = item / (GC / 4), q = (item - pw * (GC / 4)) * 4, wy = pw / WE, wx = pw - wy * WE;
+        const int gy = sy0 + wy, gx = sx0 + wx;
+        const bool ok = gy >= 0 && gy < P.S && gx >= 0 && gx < P.S && c0 + q < P.Cs;
+        st4(&xw[W::gat(wy, wx) * GXS + q], ok ? ld4(P.x + (((long)b * P.S + gy) * P.S + gx) * P.Cs + c0 + q) : zero);
+      }
+    }
+    for (int item = t; item < ST_T * ST_T * (GN / 4); item += NT) {
+      const int pk = item / (GN / 4), q = (item - pk * (GN / 4)) * 4;
+      const int gy = ty0 + (pk >> 3), gx = tx0 + (pk & 7);
+      const bool ok = gy < P.So && gx < P.So && n0 + q < P.N;
+      st4(&dzt[pk * GDS + q], ok ? ld4(P.dz + (((long)b * P.So + gy) * P.So + gx) * P.N + n0 + q) : zero);
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int step = 0; step < 4; ++step) {
+      const int prow = 2 * step + (kq >> 1), pcol = 4 * (kq & 1);     // pixel 16 step + 4 kq + s: (prow, pcol + s)
+      float qv[4];
+#pragma unroll
+      for (int s = 0; s < 4; ++s) qv[s] = dzt[(prow * ST_T + pcol + s) * GDS + 16 * wave + i];
+#pragma unroll
+      for (int tap = 0; tap < 9; ++tap) {
+        const int ky = tap / 3, kx = tap - 3 * ky;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const float* xb = xw + W::gat(ST * prow + ky, ST * (pcol + s) + kx) * GXS + i;
+#pragma unroll
+          for (int pt = 0; pt < PTC; ++pt)
+            acc[tap][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[16 * pt], qv[s], acc[tap][pt], 0, 0, 0);
+        }
+      }
+    }
+  }
+  const int n = n0 + 16 * wave + i;
+  if (n >= P.N) return;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap)
+#pragma unroll
+    for (int pt = 0; pt < PTC; ++pt) {
+      const int c = c0 + 16 * pt + 4 * kq;
+      if (c < P.Cp) st4(P.part + (((long)blockIdx.z * 9 + tap) * P.N + n) * P.Cp + c, acc[tap][pt]);
+    }
+}
+// the partials summed in split order in float64 -> dW in PyTorch layout [N][Cs][3][3]; one thread per element
+__global__ __launch_bounds__(NT) void yl_stem_wsum_kernel(const float* __restrict__ part, int splits, int N, int Cs, int Cp,
+                                                         float* __restrict__ out) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  if (idx >= 9L * N * Cs) return;
+  const long nc = idx / 9;
+  const int tap = (int)(idx - nc * 9), n = (int)(nc / Cs), c = (int)(nc - (long)n * Cs);
+  double s = 0;
+  for (int z = 0; z < splits; ++z) s += (double)part[(((long)z * 9 + tap) * N + n) * Cp + c];
+  out[idx] = (float)s;
+}
+
+// ---- the 1x1 units that stride or read the planar image: accessors of the heads' GEMM.  Row m of the unit's OUTPUT
+// (b, i, j) reads / writes source pixel (b, st i, st j)
+struct SrcGeom { int C, Sin, Sout, st, planar; };
+__device__ __forceinline__ long src_off(const SrcGeom& g, int m, int c) {
+  const int SS = g.Sout * g.Sout, b = m / SS, ij = m - b * SS, i = ij / g.Sout, j = ij - i * g.Sout;
+  const int y = i * g.st, x = j * g.st;
+  return g.planar ? (((long)b * g.C + c) * g.Sin + y) * g.Sin + x : (((long)b * g.Sin + y) * g.Sin + x) * g.C + c;
+}
+struct SrcRows {                         // (m, c)
+  const float* p; SrcGeom g;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = p[src_off(g, idx, r + s)];
+    }
+    return v;
+  }
+};
+struct SrcCols {                         // (c, m)
+  const float* p; SrcGeom g;
+  __device__ __forceinline__ f32x4 load4(int idx, int r, int NI, int NR) const {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (idx < NI) {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) if (r + s < NR) v[s] = p[src_off(g, r + s, idx)];
+    }
+    return v;
+  }
+};
+struct OutPix {                          // the input gradient of a strided 1x1: NHWC, the other pixels were zeroed
+  float* c; SrcGeom g;
+  __device__ __forceinline__ void store(int p, int q, f32x4 v, int NP, int NQ, int) const {
+    if (q < NQ && p < NP) st4(c + src_off(g, q, p), v);
+  }
+};
+
+inline int round4(int v) { return (v + 3) & ~3; }
+int pick_conv_pt(int N) {                // 16 PT output channels per workgroup: the PT of {4, 3, 2} that pads N least
+  int best = 4;
+  for (int pt = 3; pt >= 2; --pt)
+    if (ceil_div(N, 16 * pt) * pt < ceil_div(N, 16 * best) * best) best = pt;
+  return best;
+}
+
+template <int ST, bool PLANAR>
+void launch_conv_st(hipStream_t s, const ConvP& P, int B) {
+  const int pt = pick_conv_pt(P.N);
+  const dim3 grid(B * P.TY * P.TXn, ceil_div(P.N, 16 * pt)), blk(NT);
+  if (pt == 2) hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 2, PLANAR>), grid, blk, 0, s, P);
+  else if (pt == 3) hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 3, PLANAR>), grid, blk, 0, s, P);
+  else hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 4, PLANAR>), grid, blk, 0, s, P);
+}
+void launch_conv(hipStream_t s, const ConvP& P, int B, int st, bool planar) {
+  if (st == 1 && !planar) launch_conv_st<1, false>(s, P, B);
+  else if (st == 1) launch_conv_st<1, true>(s, P, B);
+  else if (!planar) launch_conv_st<2, false>(s, P, B);
+  else launch_conv_st<2, true>(s, P, B);
+}
+void launch_pack(hipStream_t s, const float* w, float* wp, int A, int Bn, int Bp, int T, const PackP& tp) {
+  hipLaunchKernelGGL(yl_stem_pack_kernel, dim3(ceil_div((long)tp.ntap * A * Bp, NT)), dim3(NT), 0, s, w, wp, A, Bn, Bp, T, tp);
+}
+
+// 3x3 forward: 2 launches (pack, convolution).  wpack: 9 cout round4(cin) floats
+int conv3_forward(hipStream_t s, const float* x, const float* w, float* wpack, float* z, int st, int B, int Sin, int Sout,
+                  int cin, int cout, bool planar) {
+  const int cp = round4(cin);
+  PackP tp;
+  tp.ntap = 9;
+  for (int t = 0; t < 9; ++t) { tp.ky[t] = t / 3; tp.kx[t] = t % 3; }
+  launch_pack(s, w, wpack, cout, cin, cp, 0, tp);
+  ConvP P;
+  P.src = x; P.wp = wpack; P.dst = z;
+  P.Ss = Sin; P.Cs = cin; P.Cp = cp; P.N = cout; P.Sd = Sout;
+  P.TY = P.TXn = ceil_div(Sout, ST_T); P.ey = P.ex = Sout;
+  P.os = 1; P.poy = P.pox = 0; P.o0 = -1; P.nty = P.ntx = 3;
+  launch_conv(s, P, B, st, planar);
+  return 2;
+}
+// the parity classes of a stride-2 input gradient that have pixels: 4 if S >= 2, else 1
+inline int dgrad_classes(int S) { return S >= 2 ? 4 : 1; }
+// 3x3 input gradient: stride 1: 2 launches; stride 2: 1 + dgrad_classes(Sin).  wpack: 9 cin cout floats
+int conv3_dgrad(hipStream_t s, const float* dz, const float* w, float* wpack, float* dx, int st, int B, int Sin, int Sout,
+                int cin, int cout) {
+  ConvP P;
+  P.src = dz; P.dst = dx;
+  P.Ss = Sout; P.Cs = cout; P.Cp = cout; P.N = cin; P.Sd = Sin;
+  PackP tp;
+  tp.ntap = 9;
+  if (st == 1) {
+    for (int t = 0; t < 9; ++t) { tp.ky[t] = 2 - t / 3; tp.kx[t] = 2 - t % 3; }
+    launch_pack(s, w, wpack, cin, cout, cout, 1, tp);
+    P.wp = wpack;
+    P.TY = P.TXn = ceil_div(Sin, ST_T); P.ey = P.ex = Sin;
+    P.os = 1; P.poy = P.pox = 0; P.o0 = -1; P.nty = P.ntx = 3;
+    launch_conv(s, P, B, 1, false);
+    return 2;
+  }
+  int o = 0, first[4];                   // the classes' taps, one after the other: 1 + 2 + 2 + 4 = 9
+  for (int pi = 0; pi < 2; ++pi)
+    for (int pj = 0; pj < 2; ++pj) {
+      first[pi * 2 + pj] = o;
+      for (int ty = 0; ty <= pi; ++ty)
+        for (int tx = 0; tx <= pj; ++tx) { tp.ky[o] = pi ? 2 - 2 * ty : 1; tp.kx[o] = pj ? 2 - 2 * tx : 1; ++o; }
+    }
+  launch_pack(s, w, wpack, cin, cout, cout, 1, tp);
+  int nl = 1;
+  for (int pi = 0; pi < 2; ++pi)
+    for (int pj = 0; pj < 2; ++pj) {
+      P.ey = (Sin - pi + 1) / 2; P.ex = (Sin - pj + 1) / 2;
+      if (P.ey < 1 || P.ex < 1) continue;
+      P.wp = wpack + (long)first[pi * 2 + pj] * cin * cout;
+      P.TY = ceil_div(P.ey, ST_T); P.TXn = ceil_div(P.ex, ST_T);
+      P.os = 2; P.poy = pi; P.pox = pj; P.o0 = 0; P.nty = 1 + pi; P.ntx = 1 + pj;
+      launch_conv(s, P, B, 1, false);
+      ++nl;
+    }
+  return nl;
+}
+// the cut of a 3x3 weight gradient: whole spatial tiles per split, about 1024 workgroups in all
+void wgrad3_plan(int B, int Sout, int cin, int cout, int* tps, int* splits) {
+  const int ntiles = B * ceil_div(Sout, ST_T) * ceil_div(Sout, ST_T);
+  const int blocks = ceil_div(round4(cin), GC) * ceil_div(cout, GN);
+  int want = 1024 / blocks;
+  want = want < 1 ? 1 : (want > ntiles ? ntiles : want);
+  *tps = ceil_div(ntiles, want);
+  *splits = ceil_div(ntiles, *tps);
+}
+// 3x3 weight gradient: 2 launches (partials, ordered sum).  part: splits 9 cout round4(cin) floats
+int conv3_wgrad(hipStream_t s, const float* x, const float* dz, float* part, float* dw, int st, int B, int Sin, int Sout,
+                int cin, int cout, bool planar, int tps, int splits) {
+  WgP P;
+  P.x = x; P.dz = dz; P.part = part;
+  P.S = Sin; P.So = Sout; P.Cs = cin; P.Cp = round4(cin); P.N = cout;
+  P.TX = ceil_div(Sout, ST_T); P.ntiles = B * P.TX * P.TX; P.tps = tps;
+  const dim3 grid(ceil_div(P.Cp, GC), ceil_div(cout, GN), splits), blk(NT);
+  if (st == 1 && !planar) hipLaunchKernelGGL((yl_stem_wgrad_kernel<1, false>), grid, blk, 0, s, P);
+  else if (st == 1) hipLaunchKernelGGL((yl_stem_wgrad_kernel<1, true>), grid, blk, 0, s, P);
+  else if (!planar) hipLaunchKernelGGL((yl_stem_wgrad_kernel<2, false>), grid, blk, 0, s, P);
+  else hipLaunchKernelGGL((yl_stem_wgrad_kernel<2, true>), grid, blk, 0, s, P);
+  hipLaunchKernelGGL(yl_stem_wsum_kernel, dim3(ceil_div(9L * cout * cin, NT)), blk, 0, s, (const float*)part, splits, cout, cin,
+                     P.Cp, dw);
+  return 2;
+}
+
+// ---- 1x1: the heads' GEMM.  Stride 1 on NHWC rows launches what yl_stage.hip launches
+int conv1_forward(hipStream_t s, const float* x, const float* w, float* z, int st, int B, int Sin, int Sout, int cin, int cout,
+                  bool planar) {
+  const int M = B * Sout * Sout;
+  if (st == 1 && !planar) launch_gemm<0>(s, RowsScalar{w, cin}, RowsVec{x, cin}, OutRowsVec{z, cout}, cout, M, cin, cin, 1);
+  else launch_gemm<0>(s, RowsScalar{w, cin}, SrcRows{x, SrcGeom{cin, Sin, Sout, st, planar ? 1 : 0}}, OutRowsVec{z, cout}, cout, M, cin, cin, 1);
+  return 1;
+}
+// stride 2: dx is zeroed (a memset, not counted) and the rows land on its even pixels
+int conv1_dgrad(hipStream_t s, const float* dz, const float* w, float* dx, int st, int B, int Sin, int Sout, int cin, int cout) {
+  const int M = B * Sout * Sout;
+  if (st == 1) {
+    launch_gemm<0>(s, ColsScalar{w, cin}, RowsVec{dz, cout}, OutRowsVec{dx, cin}, cin, M, cout, cout, 1);
+  } else {
+    hipMemsetAsync(dx, 0, (size_t)B * Sin * Sin * cin * 4, s);
+    launch_gemm<0>(s, ColsScalar{w, cin}, RowsVec{dz, cout}, OutPix{dx, SrcGeom{cin, Sin, Sout, st, 0}}, cin, M, cout, cout, 1);
+  }
+  return 1;
+}
+int conv1_wgrad(hipStream_t s, const float* x, const float* dz, float* part, float* dw, int st, int B, int Sin, int Sout, int cin,
+                int cout, bool planar, int rows, int splits) {
+  const int M = B * Sout * Sout;
+  if (st == 1 && !planar)
+    launch_gemm<0>(s, ColsScalar{x, cin}, ColsScalar{dz, cout}, OutPartial{part, (long)cin * cout}, cin, cout, M, rows, splits);
+  else
+    launch_gemm<0>(s, SrcCols{x, SrcGeom{cin, Sin, Sout, st, planar ? 1 : 0}}, ColsScalar{dz, cout}, OutPartial{part, (long)cin * cout},
+                   cin, cout, M, rows, splits);
+  HeadRows none;
+  memset(&none, 0, sizeof(none));
+  hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)cin * cout, NT)), dim3(NT), 0, s, (const float*)part, splits, cin,
+                     cout, dw, none, 0);
+  return 2;
+}
+
+// ---- the stack as units
+struct SUnit {
+  int k, st, cin, cout, Sin, Sout, planar;
+  int64_t Min, Mout;
+  int stat_rows, tiles;                  // the row reductions: at most STAT_TILES_MAX tiles of stat_rows rows
+  int wrows, wsplits;                    // the weight gradient's cut: 1x1 rows per split, 3x3 spatial tiles per split
+};
+
+bool cfg_ok(const yl_stem_cfg* c) {
+  if (!c || c->num_units < 1 || c->num_units > YL_STEM_MAX_UNITS || !(c->eps > 0)) return false;
+  if (c->input_nchw != 0 && c->input_nchw != 1) return false;
+  if (c->input_nchw) {
+    if (c->in_channels < 1 || c->in_channels > 4) return false;
+  } else if (c->in_channels < 4 || (c->in_channels & 3)) {
+    return false;
+  }
+  for (int i = 0; i < c->num_units; ++i) {
+    const yl_stem_unit_cfg& u = c->unit[i];
+    if ((u.k != 1 && u.k != 3) || (u.s != 1 && u.s != 2) || u.cout < 4 || (u.cout & 3)) return false;
+  }
+  return true;
+}
+
+// the rows of one statistics tile: multiples of STAT_ROWS until at most STAT_TILES_MAX tiles cover M rows
+inline int stat_rows_of(int64_t M) { return STAT_ROWS * ceil_div(ceil_div(M, STAT_ROWS), STAT_TILES_MAX); }
+
+int make_units(const yl_stem_cfg& cfg, int B, int S, SUnit* us) {
+  int cin = cfg.in_channels;
+  for (int i = 0; i < cfg.num_units; ++i) {
+    const yl_stem_unit_cfg& c = cfg.unit[i];
+    SUnit& u = us[i];
+    u.k = c.k; u.st = c.s; u.cin = cin; u.cout = c.cout; u.Sin = S; u.Sout = out_size(S, c.k, c.s);
+    u.planar = i == 0 && cfg.input_nchw;
+    u.Min = (int64_t)B * S * S; u.Mout = (int64_t)B * u.Sout * u.Sout;
+    u.stat_rows = stat_rows_of(u.Mout); u.tiles = ceil_div(u.Mout, u.stat_rows);
+    u.wrows = u.wsplits = 0;
+    if (u.Mout < ((int64_t)1 << 31)) {
+      if (u.k == 1) split_plan((int)u.Mout, cin, c.cout, &u.wrows, &u.wsplits);
+      else wgrad3_plan(B, u.Sout, cin, c.cout, &u.wrows, &u.wsplits);
+    }
+    S = u.Sout; cin = c.cout;
+  }
+  return cfg.num_units;
+}
+
+struct Sizes { int64_t x0, amax, gmax, cmax, smax, pmax, wmax; };
+// false: a shape the kernels' index arithmetic does not cover
+bool sizes_of(const yl_stem_cfg& cfg, const SUnit* us, int n, int B, int S, Sizes* z) {
+  memset(z, 0, sizeof(*z));
+  const int64_t M0 = (int64_t)B * S * S;
+  z->x0 = M0 * cfg.in_channels * 4;
+  if (M0 >= ((int64_t)1 << 31) || z->x0 >= ((int64_t)1 << 42)) return false;
+  for (int i = 0; i < n; ++i) {
+    const SUnit& u = us[i];
+    if (u.Mout * u.cout >= ((int64_t)1 << 40) || u.cin > (1 << 16) || u.cout > (1 << 16)) return false;
+    if (u.k == 1 && u.Mout > (int64_t)65535 * GEMM_ROWS) return false;              // the GEMM's grid.y
+    const int64_t a = u.Mout * u.cout * 4;
+    z->amax = a > z->amax ? a : z->amax;
+    z->cmax = u.cout > z->cmax ? u.cout : z->cmax;
+    const int64_t sp = round16((int64_t)u.tiles * 2 * u.cout * 8);
+    z->smax = sp > z->smax ? sp : z->smax;
+    const int64_t wp = u.k == 1 ? round16((int64_t)u.wsplits * u.cin * u.cout * 4)
+                                : round16((int64_t)u.wsplits * 9 * u.cout * round4(u.cin) * 4);
+    z->wmax = wp > z->wmax ? wp : z->wmax;
+    if (u.k == 3) {
+      const int64_t pk = round16((int64_t)9 * u.cout * round4(u.cin) * 4);
+      z->pmax = pk > z->pmax ? pk : z->pmax;
+    }
+  }
+  z->gmax = z->amax;
+  return true;
+}
+
+}  // namespace
+
+struct yl_stem {
+  Arena mem;                             // yl_block.h
+  yl_stem_cfg cfg;
+  int fB, fS, fTrain;                    // the forward whose activations are held (mem.fValid)
+};
+
+extern "C" {
+
+yl_status yl_stem_plan(const yl_stem_cfg* cfg, int32_t batch, int32_t size, yl_stem_plan_info* out) {
+  if (!cfg_ok(cfg) || !out || batch < 1 || size < 1) return YL_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  out->stat_rows = STAT_ROWS; out->gemm_rows = GEMM_ROWS; out->conv_tile = ST_T; out->stat_tiles_max = STAT_TILES_MAX;
+  SUnit us[YL_STEM_MAX_UNITS];
+  const int n = make_units(*cfg, batch, size, us);
+  Sizes z;
+  if (!sizes_of(*cfg, us, n, batch, size, &z)) return YL_ERR_UNSUPPORTED;
+  out->saved_bytes = round16(z.x0);
+  for (int i = 0; i < n; ++i) {
+    const SUnit& u = us[i];
+    yl_stem_unit_plan& p = out->unit[i];
+    p.size_in = u.Sin; p.size_out = u.Sout; p.rows_out = (int32_t)u.Mout;
+    p.stat_rows = u.stat_rows; p.stat_tiles = u.tiles; p.wgrad_rows = u.wrows; p.wgrad_splits = u.wsplits;
+    p.conv_block = u.k == 3 ? 16 * pick_conv_pt(u.cout) : 0;
+    p.saved_bytes = 2 * u.Mout * u.cout * 4 + 2 * (int64_t)u.cout * 4;
+    out->saved_bytes += p.saved_bytes;
+  }
+  out->nosave_bytes = 3 * z.amax + 2 * z.cmax * 4;
+  out->workspace_bytes = 2 * z.gmax + z.smax + 2 * z.cmax * 4 + z.pmax + z.wmax;
+  return YL_OK;
+}
+
+yl_status yl_stem_create(int32_t device, const yl_stem_cfg* cfg, yl_stem** out) {
+  if (!out || !cfg_ok(cfg)) return YL_ERR_INVALID;
+  if (hipSetDevice(device) != hipSuccess) return YL_ERR_HIP;
+  yl_stem* h = new (std::nothrow) yl_stem();
+  if (!h) return YL_ERR_NOMEM;
+  h->mem.device = device; h->cfg = *cfg;
+  *out = h;
+  return YL_OK;
+}
+
+void yl_stem_destroy(yl_stem* h) {
+  if (!h) return;
+  arena_release(h->mem);
+  delete h;
+}
+
+yl_status yl_stem_held(const yl_stem* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
+  return arena_held(h ? &h->mem : nullptr, saved_bytes, workspace_bytes, forward_held);
+}
+
+}  // extern "C"
+
+namespace {
+
+struct StemBuffers {
+  SUnit us[YL_STEM_MAX_UNITS];
+  int n;
+  float* x;                              // save: the copy of the caller's x
+  float *z[YL_STEM_MAX_UNITS], *h[YL_STEM_MAX_UNITS], *stats[YL_STEM_MAX_UNITS];    // save: per unit
+  float *nz, *nh[2], *nstats;            // no save: one z, two alternating h, one (mean, invstd)
+  float *g[2], *coef, *wpack, *wpart;
+  double* spart;
+};
+
+// the handle's memory for (B, S), cut as yl_stem_plan counts it
+yl_status ensure(yl_stem* h, int B, int S, bool save, StemBuffers* sb) {
+  yl_stem_plan_info pl;
+  yl_status st = yl_stem_plan(&h->cfg, B, S, &pl);
+  if (st != YL_OK) return st;
+  st = arena_reserve(h->mem, save ? pl.saved_bytes : pl.nosave_bytes, pl.workspace_bytes);
+  if (st != YL_OK) return st;
+  sb->n = make_units(h->cfg, B, S, sb->us);
+  Sizes z;
+  sizes_of(h->cfg, sb->us, sb->n, B, S, &z);
+  char* w = h->mem.work;
+  for (int i = 0; i < 2; ++i) { sb->g[i] = (float*)w; w += z.gmax; }
+  sb->spart = (double*)w; w += z.smax;
+  sb->coef = (float*)w; w += 2 * z.cmax * 4;
+  sb->wpack = (float*)w; w += z.pmax;
+  sb->wpart = (float*)w;
+  char* p = h->mem.saved;
+  if (save) {
+    sb->x = (float*)p; p += round16(z.x0);
+    for (int i = 0; i < sb->n; ++i) {
+      const SUnit& u = sb->us[i];
+      const size_t a = (size_t)u.Mout * u.cout * 4;
+      sb->z[i] = (float*)p; p += a;
+      sb->h[i] = (float*)p; p += a;
+      sb->stats[i] = (float*)p; p += 2 * (size_t)u.cout * 4;
+    }
+  } else {
+    sb->nz = (float*)p; p += z.amax;
+    for (int i = 0; i < 2; ++i) { sb->nh[i] = (float*)p; p += z.amax; }
+    sb->nstats = (float*)p;
+  }
+  return YL_OK;
+}
+
+bool params_ok(const yl_stem* h, const yl_stem_tensors* t) {
+  if (!t) return false;
+  uintptr_t any = 0;
+  for (int i = 0; i < h->cfg.num_units; ++i) {
+    const yl_stage_unit& e = t->unit[i];
+    if (!e.w || !e.gamma || !e.beta || !e.running_mean || !e.running_var || !e.num_batches_tracked) return false;
+    any |= (uintptr_t)e.w | (uintptr_t)e.gamma | (uintptr_t)e.beta | (uintptr_t)e.running_mean | (uintptr_t)e.running_var;
+    if ((uintptr_t)e.num_batches_tracked & 7u) return false;
+  }
+  return !(any & 3u);
+}
+
+}  // namespace
+
+extern "C" {
+
+yl_status yl_stem_forward(yl_stem* h, const yl_stem_tensors* params, const float* x_dev, int32_t batch, int32_t size,
+                          uint32_t flags, float* out_dev, void* stream, int32_t* launches) {
+  if (!h || !x_dev || !out_dev || batch < 1 || size < 1 || !params_ok(h, params)) return YL_ERR_INVALID;
+  if (flags & ~(uint32_t)(YL_HEAD_TRAIN | YL_HEAD_SAVE)) return YL_ERR_INVALID;       // fp32 only: no precision bits
+  if (((uintptr_t)x_dev & (h->cfg.input_nchw ? 3u : 15u)) || ((uintptr_t)out_dev & 15u)) return YL_ERR_UNSUPPORTED;
+  const bool train = flags & YL_HEAD_TRAIN, save = flags & YL_HEAD_SAVE;
+  {
+    SUnit us[YL_STEM_MAX_UNITS];
+    const int n = make_units(h->cfg, batch, size, us);
+    for (int i = 0; i < n; ++i)
+      if (us[i].Mout < 1 || (train && us[i].Mout < 2)) return YL_ERR_INVALID;          // no variance of one value
+  }
+  StemBuffers sb;
+  const yl_status st = ensure(h, batch, size, save, &sb);
+  if (st != YL_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  h->mem.fValid = 0;
+  const size_t x0 = (size_t)batch * size * size * h->cfg.in_channels * 4;
+  if (save && hipMemcpyAsync(sb.x, x_dev, x0, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
+  int nl = 0;
+  const float* in = save ? sb.x : x_dev;
+  for (int i = 0; i < sb.n; ++i) {
+    const SUnit& u = sb.us[i];
+    const yl_stage_unit& e = params->unit[i];
+    float* z = save ? sb.z[i] : sb.nz;
+    float* stats = save ? sb.stats[i] : sb.nstats;
+    float* hout = save ? sb.h[i] : (i == sb.n - 1 ? out_dev : sb.nh[i & 1]);
+    const int M = (int)u.Mout, F = u.cout;
+    if (u.k == 3) nl += conv3_forward(s, in, e.w, sb.wpack, z, u.st, batch, u.Sin, u.Sout, u.cin, F, u.planar);
+    else nl += conv1_forward(s, in, e.w, z, u.st, batch, u.Sin, u.Sout, u.cin, F, u.planar);
+    if (train) {
+      StatP sp;
+      sp.a = z; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = sb.spart;
+      sp.M = M; sp.F = F; sp.CQ = pick_cq(F); sp.bwd = 0;
+      hipLaunchKernelGGL(yl_stem_colstats_kernel<false>, dim3(u.tiles, ceil_div(F >> 2, sp.CQ)), dim3(NT), 0, s, sp, u.stat_rows);
+      ++nl;
+    }
+    BnFwdP bp;
+    bp.part = sb.spart; bp.tiles = u.tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
+    bp.rm = e.running_mean; bp.rv = e.running_var; bp.nbt = e.num_batches_tracked; bp.stats = stats;
+    hipLaunchKernelGGL(yl_stage_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp, h->cfg.eps);
+    const long n4 = (long)M * (F >> 2);
+    hipLaunchKernelGGL(yl_stage_bn_kernel<true>, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, (const float*)z, (const float*)stats,
+                       (const float*)e.gamma, (const float*)e.beta, (const float*)nullptr, hout, n4, F);
+    nl += 2;
+    in = hout;
+  }
+  if (save) {
+    const SUnit& u = sb.us[sb.n - 1];
+    if (hipMemcpyAsync(out_dev, in, (size_t)u.Mout * u.cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
+  }
+  if (launches) *launches = nl;
+  if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
+  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->mem.fValid = 1; }
+  return YL_OK;
+}
+
+yl_status yl_stem_backward(yl_stem* h, const yl_stem_tensors* params, const yl_stem_tensors* grads, const float* gy_dev,
+                           float* dx_dev, void* stream, int32_t* launches) {
+  if (!h || !grads || !gy_dev || !params_ok(h, params)) return YL_ERR_INVALID;
+  if (dx_dev && h->cfg.input_nchw) return YL_ERR_INVALID;  // the planar image has no gradient
+  if (((uintptr_t)gy_dev & 15u) || ((uintptr_t)dx_dev & 15u)) return YL_ERR_UNSUPPORTED;
+  if (!h->mem.fValid) return YL_ERR_STATE;
+  StemBuffers sb;
+  const yl_status st = ensure(h, h->fB, h->fS, true, &sb);
+  if (st != YL_OK) return st;
+  if (!h->mem.fValid) return YL_ERR_STATE;
+  uintptr_t gany = 0;
+  int first = dx_dev ? 0 : sb.n;         // the first unit something is wanted of
+  for (int i = sb.n - 1; i >= 0; --i) {
+    const yl_stage_unit& g = grads->unit[i];
+    const uintptr_t any = (uintptr_t)g.w | (uintptr_t)g.gamma | (uintptr_t)g.beta;
+    gany |= any;
+    if (any && i < first) first = i;
+  }
+  if (gany & 3u) return YL_ERR_UNSUPPORTED;                // before the first launch: nothing of the caller's is written
+  hipStream_t s = (hipStream_t)stream;
+  const bool train = h->fTrain != 0;
+  const int B = h->fB;
+  int nl = 0;
+  const float* dh = gy_dev;
+  int cur = -1;                          // the buffer dh is in (-1: the caller's gy)
+  for (int i = sb.n - 1; i >= first; --i) {
+    const SUnit& u = sb.us[i];
+    const yl_stage_unit& e = params->unit[i];
+    const yl_stage_unit& g = grads->unit[i];
+    const float* xin = i ? sb.h[i - 1] : sb.x;
+    const int M = (int)u.Mout, F = u.cout, cq = pick_cq(F);
+    const long n4 = (long)M * (F >> 2);
+    const bool sums = train || g.gamma || g.beta;          // sum g, sum g * xhat: dbeta, dgamma and the batch statistics' two means
+    if (sums) {
+      StatP sp;
+      sp.a = dh; sp.h = sb.h[i]; sp.z = sb.z[i]; sp.stats = sb.stats[i]; sp.part = sb.spart;
+      sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 1;
+      hipLaunchKernelGGL(yl_stem_colstats_kernel<true>, dim3(u.tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp, u.stat_rows);
+      ++nl;
+    }
+    BnBwdP bp;
+    bp.part = sb.spart; bp.tiles = sums ? u.tiles : 0; bp.M = M; bp.F = F; bp.train = train;
+    bp.dgamma = g.gamma; bp.dbeta = g.beta; bp.coef = sb.coef;
+    hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
+    ++nl;
+    const bool need_dx = i > first || (i == 0 && dx_dev);
+    if (!need_dx && !g.w) break;
+    const int t = cur >= 0 ? cur : 0;    // dz: in place, or (the caller's gy is only read) in the first buffer
+    float* dz = sb.g[t];
+    hipLaunchKernelGGL(yl_stage_bn_bwd_kernel<true>, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, dh, (const float*)sb.h[i],
+                       (const float*)sb.z[i], (const float*)sb.stats[i], (const float*)sb.coef, (const float*)e.gamma, dz, n4, F);
+    ++nl;
+    if (g.w) {
+      if (u.k == 3) nl += conv3_wgrad(s, xin, dz, sb.wpart, g.w, u.st, B, u.Sin, u.Sout, u.cin, F, u.planar, u.wrows, u.wsplits);
+      else nl += conv1_wgrad(s, xin, dz, sb.wpart, g.w, u.st, B, u.Sin, u.Sout, u.cin, F, u.planar, u.wrows, u.wsplits);
+    }
+    if (!need_dx) break;
+    float* dst = i ? sb.g[1 - t] : dx_dev;
+    if (u.k == 3) nl += conv3_dgrad(s, dz, e.w, sb.wpack, dst, u.st, B, u.Sin, u.Sout, u.cin, F);
+    else nl += conv1_dgrad(s, dz, e.w, dst, u.st, B, u.Sin, u.Sout, u.cin, F);
+    dh = dst; cur = 1 - t;
+  }
+  if (launches) *launches = nl;
+  return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;
+}
+
+yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,
+                       int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, void* stream,
+                       int32_t* launches) {
+  if (!a_dev || !b_dev || !out_dev || batch < 1 || size < 1 || cout < 4 || (cout & 3)) return YL_ERR_INVALID;
+  if ((k != 1 && k != 3) || (stride != 1 && stride != 2)) return YL_ERR_INVALID;
+  if (pass != YL_STAGE_PASS_FORWARD && pass != YL_STAGE_PASS_DGRAD && pass != YL_STAGE_PASS_WGRAD) return YL_ERR_INVALID;
+  if (input_nchw != 0 && input_nchw != 1) return YL_ERR_INVALID;
+  if (input_nchw ? (cin < 1 || cin > 4 || pass == YL_STAGE_PASS_DGRAD) : (cin < 4 || (cin & 3))) return YL_ERR_INVALID;
+  const bool wg = pass == YL_STAGE_PASS_WGRAD, planar = input_nchw != 0;
+  // the weight (b of FORWARD / DGRAD, out of WGRAD) and the planar image at any 4-byte boundary, every other tensor at 16
+  if (((uintptr_t)a_dev & ((planar && pass != YL_STAGE_PASS_DGRAD) ? 3u : 15u)) || ((uintptr_t)b_dev & (wg ? 15u : 3u)) ||
+      ((uintptr_t)out_dev & (wg ? 3u : 15u)))
+    return YL_ERR_UNSUPPORTED;
+  const int So = out_size(size, k, stride);
+  const int64_t M = (int64_t)batch * size * size, Mo = (int64_t)batch * So * So;
+  const int big = cin > cout ? cin : cout;
+  if (M * big >= ((int64_t)1 << 40) || M >= ((int64_t)1 << 31) || big > (1 << 16)) return YL_ERR_UNSUPPORTED;
+  if (k == 1 && Mo > (int64_t)65535 * GEMM_ROWS) return YL_ERR_UNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  int rows = 0, splits = 0;
+  int64_t bytes = 16;
+  if (wg) {
+    if (k == 1) { split_plan((int)Mo, cin, cout, &rows, &splits); bytes = round16((int64_t)splits * cin * cout * 4); }
+    else { wgrad3_plan(batch, So, cin, cout, &rows, &splits); bytes = round16((int64_t)splits * 9 * cout * round4(cin) * 4); }
+  } else if (k == 3) {
+    bytes = round16((int64_t)9 * cout * round4(cin) * 4);
+  }
+  float* tmp = nullptr;
+  if (hipMalloc((void**)&tmp, (size_t)bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return YL_ERR_NOMEM;
+  }
+  int nl = 0;
+  if (pass == YL_STAGE_PASS_FORWARD)
+    nl = k == 3 ? conv3_forward(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar)
+                : conv1_forward(s, a_dev, b_dev, out_dev, stride, batch, size, So, cin, cout, planar);
+  else if (pass == YL_STAGE_PASS_DGRAD)
+    nl = k == 3 ? conv3_dgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout)
+                : conv1_dgrad(s, a_dev, b_dev, out_dev, stride, batch, size, So, cin, cout);
+  else
+    nl = k == 3 ? conv3_wgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, rows, splits)
+                : conv1_wgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, rows, splits);
+  const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+  hipFree(tmp);
+  if (launches) *launches = nl;
+  return ok ? YL_OK : YL_ERR_HIP;
+}
+
+}  // extern "C"

@@ -3,6 +3,8 @@
 
     UIBStack(in_channels, blocks, eps=1e-5, prefix="")     any such stack
     BackboneTail.from_meta(meta) / .from_state_dict(meta, sd)   the backbone's last stage: its C4 tap -> its C5 tap
+    BackboneMid.from_meta(meta) / .from_state_dict(meta, sd)    the stage between its C3 and its C4 tap
+    MobileNetV4Backbone.from_meta(meta) / .from_state_dict(meta, sd)   image -> [c3, c4, c5]: stemops.BackboneStem, mid, tail
     depthwise(x, w_or_dy, pass_, k, stride)                one depthwise pass on its own (yl_stage_depthwise)
     plan(in_channels, blocks, batch, size)                 yl_stage_plan: what the handle holds
 
@@ -371,6 +373,109 @@ class BackboneTail(UIBStack):
     def from_state_dict(cls, meta: dict, sd: dict, start: str = "c4"):
         """the tail of a checkpoint: built from its meta, filled with its `backbone.blocks.{si}.{bi}.` entries"""
         return tm.fill_from_state_dict(cls.from_meta(meta, start), sd, "backbone tail")
+
+
+def _mid_blocks(meta: dict):
+    """-> (cin at the C3 tap, blocks with their names "si.bi", eps) of the stages between the C3 and the C4 tap of the
+    backbone `meta` names (mobilenetv4_conv_small[_050]: stage 2, six uir blocks).  Host-side facts only; refuses by name."""
+    import math
+    from .program import BACKBONES, CONVNEXT, HGNET, _make_divisible, _parse
+    who = "BackboneMid"
+    mcfg = (meta.get("config", {}) or {}).get("model", {}) or {}
+    name = meta.get("backbone") or mcfg.get("backbone") or "resnet18"
+    if name in HGNET or name in CONVNEXT or name not in BACKBONES:
+        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented (its C3 -> C4 stage is not made of uir / 1x1 cn "
+                                    "blocks; only the mobilenetv4_conv_small family's is)")
+    spec = BACKBONES[name]
+    arch, rlim = spec["arch"], spec.get("round_limit", 0.9)
+    if spec["act"] != "relu":
+        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: activation {spec['act']!r} (ReLU only)")
+    if spec["same"]:
+        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: TF-SAME padding")
+    ns = len(arch)
+    taps = [si for si in range(ns) if si + 1 == ns or _parse(arch[si + 1][0])["s"] > 1]
+    if len(taps) < 3:
+        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} has no C3 tap")
+    cin, c3, blocks = spec["stem"], None, []
+    for si, stage in enumerate(arch[:taps[-2] + 1]):
+        bi = 0
+        for bstr in stage:
+            d = _parse(bstr)
+            rep = d["r"]
+            if spec["dmult"] != 1.0 and not (spec["fix_first_last"] and si in (0, ns - 1)):
+                rep = int(math.ceil(rep * spec["dmult"]))
+            cout = _make_divisible(d["c"] * spec["cmult"], 8, rlim)
+            for r in range(rep):
+                if si > taps[-3]:
+                    if d["type"] not in ("uir", "cn") or d.get("se") or d.get("skip"):
+                        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: block {bstr!r} of its C3 -> C4 "
+                                                    "stage is not a uir or 1x1 cn block")
+                    blocks.append(dict(type=d["type"], a=d.get("a", 0), k=d["k"], s=d["s"] if r == 0 else 1, c=cout,
+                                       name=f"{si}.{bi}", mid=_make_divisible(cin * d["e"], 8) if d["type"] == "uir" else 0))
+                cin = cout
+                bi += 1
+        if si == taps[-3]:
+            c3 = cin
+    return c3, blocks, float(spec["eps"])
+
+
+class _MidHandle(_Handle):
+    who = "BackboneMid"
+
+
+class BackboneMid(UIBStack):
+    """The stack from the backbone's C3 tap to its C4 tap (mobilenetv4_conv_small[_050]: `backbone.blocks.2.*`, six UIB
+    blocks of which the first strides) under the checkpoint's key names.  mid(c3) -> c4, both NHWC."""
+    _who, _handle_cls = "BackboneMid", _MidHandle
+
+    @classmethod
+    def from_meta(cls, meta: dict):
+        cin, blocks, eps = _mid_blocks(meta)
+        return cls(cin, blocks, eps=eps, prefix="backbone.")
+
+    @classmethod
+    def from_state_dict(cls, meta: dict, sd: dict):
+        return tm.fill_from_state_dict(cls.from_meta(meta), sd, "backbone C3 -> C4 stage")
+
+
+class MobileNetV4Backbone(nn.Module):
+    """The whole mobilenetv4_conv_small[_050] backbone with every parameter trainable: .stem (stemops.BackboneStem, image ->
+    C3), .mid (BackboneMid, C3 -> C4), .tail (BackboneTail, C4 -> C5).  backbone(x [B,3,S,S]) -> [c3, c4, c5] NHWC,
+    smallest stride first: what neck(cs, layout="nhwc") takes.  torch sums the two gradients that arrive at C3 and at C4.
+    Freezing is torch's own: backbone.stem.requires_grad_(False).eval(); nothing upstream of the first wanted gradient
+    runs.  state_dict() / load_state_dict() speak the checkpoint's key names (`backbone.conv_stem.weight`, ...)."""
+
+    def __init__(self, stem: nn.Module, mid: nn.Module, tail: nn.Module):
+        super().__init__()
+        self.stem, self.mid, self.tail = stem, mid, tail
+
+    @classmethod
+    def from_meta(cls, meta: dict):
+        from .stemops import BackboneStem
+        return cls(BackboneStem.from_meta(meta), BackboneMid.from_meta(meta), BackboneTail.from_meta(meta))
+
+    @classmethod
+    def from_state_dict(cls, meta: dict, sd: dict):
+        m = cls.from_meta(meta)
+        m.load_state_dict(sd)
+        return m
+
+    def state_dict(self, *args, **kwargs):                 # the three parts' own keys, which are the checkpoint's
+        out = self.stem.state_dict()
+        out.update(self.mid.state_dict())
+        out.update(self.tail.state_dict())
+        return out
+
+    def load_state_dict(self, sd, strict: bool = True):
+        for part, what in ((self.stem, "backbone stem"), (self.mid, "backbone C3 -> C4 stage"), (self.tail, "backbone tail")):
+            tm.fill_from_state_dict(part, sd, what)
+        return self
+
+    def forward(self, x: torch.Tensor) -> List[torch.Tensor]:
+        c3 = self.stem(x)
+        c4 = self.mid(c3, layout="nhwc")
+        c5 = self.tail(c4, layout="nhwc")
+        return [c3, c4, c5]
 
 
 PASSES = {"forward": _lib.YL_STAGE_PASS_FORWARD, "dgrad": _lib.YL_STAGE_PASS_DGRAD, "wgrad": _lib.YL_STAGE_PASS_WGRAD}
