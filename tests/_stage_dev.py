@@ -5,7 +5,7 @@ import torch
 
 import yololite_amd as ya
 from _stage_cases import bar, case_inputs, fixture_tensors
-from _train_dev import DEV
+from _train_dev import DEV, collect
 
 
 def stack_of(case, inputs, train=True):
@@ -27,13 +27,7 @@ def run(m, inputs, x_grad=True, layout="nhwc"):
     d = {"y": y.detach().cpu()}
     if x.grad is not None:
         d["dx"] = (x.grad if layout == "nhwc" else x.grad.permute(0, 2, 3, 1)).contiguous().cpu()
-    for n, v in m.state_dict().items():
-        if "running_" in n or "num_batches_tracked" in n:
-            d["b." + n] = v.cpu().clone()
-    for n, q in m.named_parameters():
-        if q.grad is not None:
-            d["g." + n] = q.grad.cpu().clone()
-    return d
+    return collect(m, d)
 
 
 def parity_ratios(case, mode, z):

@@ -6,23 +6,13 @@ import torch
 import yololite_amd as ya
 import _stage_cases as sc
 from _stem_cases import bar, case_inputs, fixture_tensors, sizes, stack_all
-from _train_dev import DEV
+from _train_dev import DEV, collect
 
 
 def stack_of(case, inputs, train=True):
     m = ya.ConvStack(case["cin"], case["units"], prefix=case.get("prefix", ""), input_layout="nchw" if case["planar"] else "nhwc")
     m.load_state_dict({k: torch.as_tensor(v) for k, v in {**inputs["params"], **inputs["buffers"]}.items()})
     return m.to(DEV).train(train)
-
-
-def collect(m, d):
-    for n, v in m.state_dict().items():
-        if "running_" in n or "num_batches_tracked" in n:
-            d["b." + n] = v.cpu().clone()
-    for n, q in m.named_parameters():
-        if q.grad is not None:
-            d["g." + n] = q.grad.cpu().clone()
-    return d
 
 
 def run(m, case, inputs, x_grad=True):

@@ -1,6 +1,6 @@
 """What the GPU tests of the trainable modules share (detection heads, FPN neck): the device, bit equality of two
-results, the small edge_n model and targets of the end-to-end tests, and the device error and bar of every fixture
-tensor of one case."""
+results, what a unit stack (backbone stage, dense stem) leaves behind after a step, the small edge_n model and targets
+of the end-to-end tests, and the device error and bar of every fixture tensor of one case."""
 import numpy as np
 import torch
 
@@ -15,6 +15,17 @@ def same(a, b):
     assert set(a) == set(b)
     for n in a:
         assert torch.equal(a[n], b[n]), n
+
+
+def collect(m, d):
+    """adds a unit stack's BatchNorm buffers ("b." + name) and the gradients its parameters have ("g." + name) to d"""
+    for n, v in m.state_dict().items():
+        if "running_" in n or "num_batches_tracked" in n:
+            d["b." + n] = v.cpu().clone()
+    for n, q in m.named_parameters():
+        if q.grad is not None:
+            d["g." + n] = q.grad.cpu().clone()
+    return d
 
 
 def edge_n():

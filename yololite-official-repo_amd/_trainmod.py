@@ -1,6 +1,8 @@
-"""What the trainable modules on the device share (headops.DetectHeads, neckops.DetectNeck / DetectNeckMS): the handle of one library
+"""What the trainable modules on the device share (headops.DetectHeads, neckops.DetectNeck / DetectNeckMS,
+stageops.UIBStack, stemops.ConvStack): the handle of one library
 object, the depthwise block's container and its entry in the library's tables, the reading of feature maps, checkpoints
-and meta, and the parts of an autograd.Function that do not depend on the module.
+and meta, the parts of an autograd.Function that do not depend on the module, and the Function and module base of the
+conv + BatchNorm unit stacks (backbone stage and dense stem).
 
 One handle holds ONE forward for backward at a time (csrc/yl_block.h, Arena): every forward bumps the handle's
 generation, and a backward whose generation is no longer the handle's raises.  The handle's memory only grows.
@@ -199,3 +201,86 @@ def flags(train: bool, save: bool) -> int:
 def grads_like(tensors: Sequence[torch.Tensor], need: Sequence[bool]) -> List[Optional[torch.Tensor]]:
     """an uninitialised contiguous gradient for every tensor whose entry of `need` (a slice of needs_input_grad) is set"""
     return [torch.empty_like(t, memory_format=torch.contiguous_format) if n else None for t, n in zip(tensors, need)]
+
+
+# ---- a stack of conv + BatchNorm units (csrc/yl_units.h): stageops.UIBStack and stemops.ConvStack
+
+class UnitStackFunction(torch.autograd.Function):
+    """y = stack(x, parameters): <prefix>_forward / <prefix>_backward of the handle `hd`.  x: NHWC [B,S,S,C], or with
+    `nchw` the planar image [B,C,S,S], which has no gradient"""
+    ARGS = 6                                               # what stands in front of x
+
+    @staticmethod
+    def forward(fctx, hd: DeviceHandle, bufs, train: bool, grad_mode: bool, out_shape, nchw: bool, x, *params):
+        save = saving(fctx, grad_mode)
+        xd = x.detach() if nchw else aligned(x.detach())
+        dev = x.device
+        ps = detached_params(hd.who, params, dev)
+        B, S = int(x.shape[0]), int(x.shape[2])            # S stands third in either layout
+        out = torch.empty(out_shape, device=dev, dtype=torch.float32)
+        hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), xd.data_ptr(), B, S, flags(train, save), out.data_ptr())
+        if save:
+            fctx.save_for_backward(xd, *params)
+            fctx.hd, fctx.bufs, fctx.generation, fctx.nchw = hd, bufs, hd.generation, nchw
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(fctx, gy):
+        hd = fctx.hd
+        hd.check_generation(fctx.generation, hd.who + ": the stack", "one forward")
+        saved = fctx.saved_tensors
+        gy = aligned(gy.to(dtype=torch.float32).contiguous())
+        need = list(fctx.needs_input_grad[UnitStackFunction.ARGS:])
+        if fctx.nchw:
+            need[0] = False
+        grads = grads_like(saved, need)
+        ps = [p.detach() for p in saved[1:]]
+        hd.launch("backward", saved[0].device, C.byref(hd.table(ps, fctx.bufs)), C.byref(hd.table(grads[1:])), gy.data_ptr(),
+                  ptr(grads[0]))
+        return (None,) * UnitStackFunction.ARGS + tuple(grads)
+
+
+class UnitStack(nn.Module):
+    """What the unit stacks share.  A subclass fills _convs, _bns (one layer each per unit, in running order) and _handle,
+    and gives _unit_sizes(S): the size of the map every unit writes."""
+
+    def _param_list(self) -> List[torch.Tensor]:
+        """per unit in running order: conv weight, BatchNorm weight, BatchNorm bias"""
+        out = []
+        for cv, bn in zip(self._convs, self._bns):
+            out += [cv.weight, bn.weight, bn.bias]
+        return out
+
+    def _stat_buffers(self):
+        return [(bn.running_mean, bn.running_var, bn.num_batches_tracked) for bn in self._bns]
+
+    @property
+    def last_launches(self) -> Dict[str, int]:
+        """kernels enqueued by the last forward / backward"""
+        return dict(self._handle.last_launches)
+
+    def held(self) -> Dict[str, int]:
+        """the bytes the handle holds on the device and whether a forward is held for backward"""
+        return self._handle.held()
+
+    def _check_rows(self, B: int, S: int) -> List[int]:
+        """-> the size of every unit's output; in training no BatchNorm may see ONE value per channel"""
+        sizes = self._unit_sizes(S)
+        if self.training:
+            for So, bn in zip(sizes, self._bns):
+                if B * So * So == 1:
+                    raise ValueError("Expected more than 1 value per channel when training, got input size "
+                                     f"{[B, bn.num_features, So, So]}")
+        return sizes
+
+    def _run_stack(self, x: torch.Tensor, B: int, sizes: List[int], nchw: bool) -> torch.Tensor:
+        """forward()'s tail, once x's shape is checked and it is on a device: -> NHWC [B,S_out,S_out,C_out]"""
+        params = self._param_list()
+        if any(p.device != x.device for p in params):
+            raise _lib.YoloLiteHipError(f"{self._who}: parameters and inputs must live on one HIP device")
+        self._handle.ensure(x.device)
+        x = x.float().contiguous()                         # autograd carries the gradient back through cast and copy
+        shape = (B, sizes[-1], sizes[-1], self.out_channels)
+        return UnitStackFunction.apply(self._handle, self._stat_buffers(), self.training, torch.is_grad_enabled(), shape, nchw,
+                                       x, *params)

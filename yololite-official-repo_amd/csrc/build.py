@@ -54,14 +54,15 @@ UNITS = [   # (source, extra flags, object name)
     ("yl_neck.hip", ["-ffp-contract=off"], "yl_neck.o"),
     # trainable dense FPN neck (YOLOLiteMS): dense 3x3 convolution with all three passes, BatchNorm + SiLU; the chain is yl_fpn.h
     ("yl_dneck.hip", ["-ffp-contract=off"], "yl_dneck.o"),
-    # trainable backbone stage (MobileNetV4 UIB blocks): depthwise k x k with stride in three passes, BatchNorm with and
-    # without ReLU, the residual; the 1x1 convolutions are the heads' GEMM (yl_block.h)
+    # trainable backbone stage (MobileNetV4 UIB blocks): depthwise k x k with stride in three passes and the residual's add;
+    # the 1x1 convolutions are the heads' GEMM (yl_block.h).  The walk over its conv + BatchNorm units, forward and backward,
+    # is yl_units.h and the BatchNorm kernels are yl_bn.h, both shared with yl_stem.hip
     ("yl_stage.hip", ["-ffp-contract=off"], "yl_stage.o"),
     # trainable dense stem (image -> C3): dense 3x3 convolution with stride in three passes on fp32 MFMA, strided 1x1 units on
-    # the heads' GEMM; BatchNorm + ReLU are yl_bn.h, shared with yl_stage.hip
+    # the heads' GEMM; the unit walk (yl_units.h) and BatchNorm + ReLU (yl_bn.h) are the ones yl_stage.hip runs
     ("yl_stem.hip", ["-ffp-contract=off"], "yl_stem.o"),
 ]
-DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_bn.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]
+DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_bn.h", "yl_units.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]
 
 
 def _hipcc():

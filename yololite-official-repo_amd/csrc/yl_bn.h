@@ -1,6 +1,7 @@
 // BatchNorm2d with and without ReLU on NHWC fp32 rows, eps from the configuration: what the trainable backbone stage
 // (yl_stage.hip) and the trainable dense stem (yl_stem.hip) share.  Like yl_block.h, everything lives in an anonymous
 // namespace: each translation unit that includes this header compiles the kernels it launches into its own code object.
+// The kernels only: the walk over a stack's units that launches them, forward and backward, is yl_units.h.
 #ifndef YL_BN_H
 #define YL_BN_H
 #include "yl_block.h"

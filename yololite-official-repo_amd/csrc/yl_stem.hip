@@ -4,9 +4,12 @@
 //
 //   unit u:  z = conv(x_u)   h = relu(bn(z))          x_u: the previous unit's h (the caller's x for unit 0)
 //
-// BatchNorm, ReLU, the column sums and the BatchNorm backward are yl_bn.h's (shared with yl_stage.hip), the 1x1 units the
-// heads' GEMM (yl_block.h: launch_gemm<0>) with accessors of their own where the unit strides or reads the planar image.
-// New here: the 3x3 convolution in three passes.
+// The walk over the units, forward and backward, with the handle, its memory and the table checks, is yl_units.h, shared
+// with yl_stage.hip: a unit here is a block of its own without a residual, so two rotating buffers do.  BatchNorm, ReLU,
+// the column sums and the BatchNorm backward are yl_bn.h's, the 1x1 units the heads' GEMM (yl_block.h: launch_gemm<0>)
+// with accessors of their own where the unit strides or reads the planar image.  Here are the stack's configuration and
+// units (cfg_ok, make_units, wgrad3_plan), the policy that tells the walk what a unit's convolution launches, and what is
+// new: the 3x3 convolution in three passes.
 //
 // ---- 3x3 forward and input gradient: ONE kernel, an implicit GEMM on v_mfma_f32_16x16x4_f32 in the orientation of
 // yl_dneck_conv_kernel (weights: A operand, pixels: B operand; a lane ends with four consecutive output channels of one
@@ -47,9 +50,7 @@
 // four stored pixels apart, 4 x 36 = 144 and 4 x 68 = 272, both 16 mod 32: no conflict; the parity split keeps "four class
 // pixels" at four stored pixels under stride 2).  part[split][tap][n][cp] in fp32 over whole tiles, then an ordered float64
 // sum in split order: equal inputs give equal bits.  The split count fills the chip (about 1024 workgroups).
-#include <new>
-
-#include "yl_bn.h"
+#include "yl_units.h"
 
 namespace {
 
@@ -325,7 +326,6 @@ struct OutPix {                          // the input gradient of a strided 1x1:
   }
 };
 
-inline int round4(int v) { return (v + 3) & ~3; }
 int pick_conv_pt(int N) {                // 16 PT output channels per workgroup: the PT of {4, 3, 2} that pads N least
   int best = 4;
   for (int pt = 3; pt >= 2; --pt)
@@ -467,14 +467,7 @@ int conv1_wgrad(hipStream_t s, const float* x, const float* dz, float* part, flo
   return 2;
 }
 
-// ---- the stack as units
-struct SUnit {
-  int k, st, cin, cout, Sin, Sout, planar;
-  int64_t Min, Mout;
-  int stat_rows, tiles;                  // the row reductions: at most STAT_TILES_MAX tiles of stat_rows rows
-  int wrows, wsplits;                    // the weight gradient's cut: 1x1 rows per split, 3x3 spatial tiles per split
-};
-
+// ---- the stack as units (yl_units.h: Unit).  The row reductions run over at most STAT_TILES_MAX tiles of stat_rows rows
 bool cfg_ok(const yl_stem_cfg* c) {
   if (!c || c->num_units < 1 || c->num_units > YL_STEM_MAX_UNITS || !(c->eps > 0)) return false;
   if (c->input_nchw != 0 && c->input_nchw != 1) return false;
@@ -493,11 +486,13 @@ bool cfg_ok(const yl_stem_cfg* c) {
 // the rows of one statistics tile: multiples of STAT_ROWS until at most STAT_TILES_MAX tiles cover M rows
 inline int stat_rows_of(int64_t M) { return STAT_ROWS * ceil_div(ceil_div(M, STAT_ROWS), STAT_TILES_MAX); }
 
-int make_units(const yl_stem_cfg& cfg, int B, int S, SUnit* us) {
+// every unit is a block of its own: ReLU, no residual
+int make_units(const yl_stem_cfg& cfg, int B, int S, Unit* us) {
   int cin = cfg.in_channels;
   for (int i = 0; i < cfg.num_units; ++i) {
     const yl_stem_unit_cfg& c = cfg.unit[i];
-    SUnit& u = us[i];
+    Unit& u = us[i];
+    u.block = i; u.slot = 0; u.dw = 0; u.relu = 1; u.first = u.last = 1; u.res = 0;
     u.k = c.k; u.st = c.s; u.cin = cin; u.cout = c.cout; u.Sin = S; u.Sout = out_size(S, c.k, c.s);
     u.planar = i == 0 && cfg.input_nchw;
     u.Min = (int64_t)B * S * S; u.Mout = (int64_t)B * u.Sout * u.Sout;
@@ -512,41 +507,48 @@ int make_units(const yl_stem_cfg& cfg, int B, int S, SUnit* us) {
   return cfg.num_units;
 }
 
-struct Sizes { int64_t x0, amax, gmax, cmax, smax, pmax, wmax; };
-// false: a shape the kernels' index arithmetic does not cover
-bool sizes_of(const yl_stem_cfg& cfg, const SUnit* us, int n, int B, int S, Sizes* z) {
-  memset(z, 0, sizeof(*z));
-  const int64_t M0 = (int64_t)B * S * S;
-  z->x0 = M0 * cfg.in_channels * 4;
-  if (M0 >= ((int64_t)1 << 31) || z->x0 >= ((int64_t)1 << 42)) return false;
-  for (int i = 0; i < n; ++i) {
-    const SUnit& u = us[i];
-    if (u.Mout * u.cout >= ((int64_t)1 << 40) || u.cin > (1 << 16) || u.cout > (1 << 16)) return false;
-    if (u.k == 1 && u.Mout > (int64_t)65535 * GEMM_ROWS) return false;              // the GEMM's grid.y
-    const int64_t a = u.Mout * u.cout * 4;
-    z->amax = a > z->amax ? a : z->amax;
-    z->cmax = u.cout > z->cmax ? u.cout : z->cmax;
-    const int64_t sp = round16((int64_t)u.tiles * 2 * u.cout * 8);
-    z->smax = sp > z->smax ? sp : z->smax;
-    const int64_t wp = u.k == 1 ? round16((int64_t)u.wsplits * u.cin * u.cout * 4)
-                                : round16((int64_t)u.wsplits * 9 * u.cout * round4(u.cin) * 4);
-    z->wmax = wp > z->wmax ? wp : z->wmax;
-    if (u.k == 3) {
-      const int64_t pk = round16((int64_t)9 * u.cout * round4(u.cin) * 4);
-      z->pmax = pk > z->pmax ? pk : z->pmax;
-    }
-  }
-  z->gmax = z->amax;
-  return true;
+// units and sizes of cfg at (B, S): what yl_stem_plan reports and the walk runs on
+yl_status layout(const yl_stem_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z) {
+  *n = make_units(cfg, B, S, us);
+  const int64_t M0 = (int64_t)B * S * S, x0 = M0 * cfg.in_channels * 4;
+  if (M0 >= ((int64_t)1 << 31) || x0 >= ((int64_t)1 << 42)) return YL_ERR_UNSUPPORTED;
+  if (!unit_sizes(us, *n, 1 << 16, z)) return YL_ERR_UNSUPPORTED;
+  for (int i = 0; i < *n; ++i)
+    if (us[i].k == 1 && us[i].Mout > (int64_t)65535 * GEMM_ROWS) return YL_ERR_UNSUPPORTED;   // the GEMM's grid.y
+  z->x0 = x0; z->xsave = round16(x0); z->gmax = z->amax;
+  return YL_OK;
 }
+
+int resolve(const yl_stem_cfg& cfg, const yl_stem_tensors* t, const yl_stage_unit** tab) {
+  for (int i = 0; i < cfg.num_units; ++i) tab[i] = &t->unit[i];
+  return cfg.num_units;
+}
+
+// what yl_units.h's walk launches for this stack: the 3x3 convolution, or the heads' GEMM for a 1x1 unit
+struct StemPolicy {
+  static constexpr int ROT = 2;
+  static constexpr bool MIXED = false;   // every unit has its ReLU and no block a residual
+  static yl_status layout(const yl_stem_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z) { return ::layout(cfg, B, S, us, n, z); }
+  static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers& sb) {
+    return u.k == 3 ? conv3_forward(s, x, w, sb.wpack, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar)
+                    : conv1_forward(s, x, w, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar);
+  }
+  static int conv_wgrad(hipStream_t s, const Unit& u, int B, const float* x, const float* dz, float* dw, const UnitBuffers& sb) {
+    return u.k == 3 ? conv3_wgrad(s, x, dz, sb.wpart, dw, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, u.wrows, u.wsplits)
+                    : conv1_wgrad(s, x, dz, sb.wpart, dw, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, u.wrows, u.wsplits);
+  }
+  static int conv_dgrad(hipStream_t s, const Unit& u, int B, const float* dz, const float* w, float* dx, const UnitBuffers& sb) {
+    return u.k == 3 ? conv3_dgrad(s, dz, w, sb.wpack, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout)
+                    : conv1_dgrad(s, dz, w, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout);
+  }
+  template <bool RELU> static void colstats(hipStream_t s, const Unit& u, const StatP& sp) {
+    hipLaunchKernelGGL(yl_stem_colstats_kernel<RELU>, dim3(u.tiles, ceil_div(sp.F >> 2, sp.CQ)), dim3(NT), 0, s, sp, u.stat_rows);
+  }
+};
 
 }  // namespace
 
-struct yl_stem {
-  Arena mem;                             // yl_block.h
-  yl_stem_cfg cfg;
-  int fB, fS, fTrain;                    // the forward whose activations are held (mem.fValid)
-};
+struct yl_stem : UnitStack<yl_stem_cfg> {};
 
 extern "C" {
 
@@ -554,230 +556,50 @@ yl_status yl_stem_plan(const yl_stem_cfg* cfg, int32_t batch, int32_t size, yl_s
   if (!cfg_ok(cfg) || !out || batch < 1 || size < 1) return YL_ERR_INVALID;
   memset(out, 0, sizeof(*out));
   out->stat_rows = STAT_ROWS; out->gemm_rows = GEMM_ROWS; out->conv_tile = ST_T; out->stat_tiles_max = STAT_TILES_MAX;
-  SUnit us[YL_STEM_MAX_UNITS];
-  const int n = make_units(*cfg, batch, size, us);
+  Unit us[MAX_UNITS];
   Sizes z;
-  if (!sizes_of(*cfg, us, n, batch, size, &z)) return YL_ERR_UNSUPPORTED;
-  out->saved_bytes = round16(z.x0);
+  int n;
+  const yl_status st = layout(*cfg, batch, size, us, &n, &z);
+  if (st != YL_OK) return st;
   for (int i = 0; i < n; ++i) {
-    const SUnit& u = us[i];
+    const Unit& u = us[i];
     yl_stem_unit_plan& p = out->unit[i];
     p.size_in = u.Sin; p.size_out = u.Sout; p.rows_out = (int32_t)u.Mout;
     p.stat_rows = u.stat_rows; p.stat_tiles = u.tiles; p.wgrad_rows = u.wrows; p.wgrad_splits = u.wsplits;
     p.conv_block = u.k == 3 ? 16 * pick_conv_pt(u.cout) : 0;
-    p.saved_bytes = 2 * u.Mout * u.cout * 4 + 2 * (int64_t)u.cout * 4;
-    out->saved_bytes += p.saved_bytes;
+    p.saved_bytes = unit_saved_bytes(u);
   }
-  out->nosave_bytes = 3 * z.amax + 2 * z.cmax * 4;
-  out->workspace_bytes = 2 * z.gmax + z.smax + 2 * z.cmax * 4 + z.pmax + z.wmax;
+  const ArenaBytes b = arena_bytes(us, n, z, StemPolicy::ROT);
+  out->saved_bytes = b.saved; out->nosave_bytes = b.nosave; out->workspace_bytes = b.work;
   return YL_OK;
 }
 
 yl_status yl_stem_create(int32_t device, const yl_stem_cfg* cfg, yl_stem** out) {
-  if (!out || !cfg_ok(cfg)) return YL_ERR_INVALID;
-  if (hipSetDevice(device) != hipSuccess) return YL_ERR_HIP;
-  yl_stem* h = new (std::nothrow) yl_stem();
-  if (!h) return YL_ERR_NOMEM;
-  h->mem.device = device; h->cfg = *cfg;
-  *out = h;
-  return YL_OK;
+  return units_create(device, cfg, cfg_ok(cfg), out);
 }
 
-void yl_stem_destroy(yl_stem* h) {
-  if (!h) return;
-  arena_release(h->mem);
-  delete h;
-}
+void yl_stem_destroy(yl_stem* h) { units_destroy(h); }
 
 yl_status yl_stem_held(const yl_stem* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
-  return arena_held(h ? &h->mem : nullptr, saved_bytes, workspace_bytes, forward_held);
+  return units_held(h, saved_bytes, workspace_bytes, forward_held);
 }
-
-}  // extern "C"
-
-namespace {
-
-struct StemBuffers {
-  SUnit us[YL_STEM_MAX_UNITS];
-  int n;
-  float* x;                              // save: the copy of the caller's x
-  float *z[YL_STEM_MAX_UNITS], *h[YL_STEM_MAX_UNITS], *stats[YL_STEM_MAX_UNITS];    // save: per unit
-  float *nz, *nh[2], *nstats;            // no save: one z, two alternating h, one (mean, invstd)
-  float *g[2], *coef, *wpack, *wpart;
-  double* spart;
-};
-
-// the handle's memory for (B, S), cut as yl_stem_plan counts it
-yl_status ensure(yl_stem* h, int B, int S, bool save, StemBuffers* sb) {
-  yl_stem_plan_info pl;
-  yl_status st = yl_stem_plan(&h->cfg, B, S, &pl);
-  if (st != YL_OK) return st;
-  st = arena_reserve(h->mem, save ? pl.saved_bytes : pl.nosave_bytes, pl.workspace_bytes);
-  if (st != YL_OK) return st;
-  sb->n = make_units(h->cfg, B, S, sb->us);
-  Sizes z;
-  sizes_of(h->cfg, sb->us, sb->n, B, S, &z);
-  char* w = h->mem.work;
-  for (int i = 0; i < 2; ++i) { sb->g[i] = (float*)w; w += z.gmax; }
-  sb->spart = (double*)w; w += z.smax;
-  sb->coef = (float*)w; w += 2 * z.cmax * 4;
-  sb->wpack = (float*)w; w += z.pmax;
-  sb->wpart = (float*)w;
-  char* p = h->mem.saved;
-  if (save) {
-    sb->x = (float*)p; p += round16(z.x0);
-    for (int i = 0; i < sb->n; ++i) {
-      const SUnit& u = sb->us[i];
-      const size_t a = (size_t)u.Mout * u.cout * 4;
-      sb->z[i] = (float*)p; p += a;
-      sb->h[i] = (float*)p; p += a;
-      sb->stats[i] = (float*)p; p += 2 * (size_t)u.cout * 4;
-    }
-  } else {
-    sb->nz = (float*)p; p += z.amax;
-    for (int i = 0; i < 2; ++i) { sb->nh[i] = (float*)p; p += z.amax; }
-    sb->nstats = (float*)p;
-  }
-  return YL_OK;
-}
-
-bool params_ok(const yl_stem* h, const yl_stem_tensors* t) {
-  if (!t) return false;
-  uintptr_t any = 0;
-  for (int i = 0; i < h->cfg.num_units; ++i) {
-    const yl_stage_unit& e = t->unit[i];
-    if (!e.w || !e.gamma || !e.beta || !e.running_mean || !e.running_var || !e.num_batches_tracked) return false;
-    any |= (uintptr_t)e.w | (uintptr_t)e.gamma | (uintptr_t)e.beta | (uintptr_t)e.running_mean | (uintptr_t)e.running_var;
-    if ((uintptr_t)e.num_batches_tracked & 7u) return false;
-  }
-  return !(any & 3u);
-}
-
-}  // namespace
-
-extern "C" {
 
 yl_status yl_stem_forward(yl_stem* h, const yl_stem_tensors* params, const float* x_dev, int32_t batch, int32_t size,
                           uint32_t flags, float* out_dev, void* stream, int32_t* launches) {
-  if (!h || !x_dev || !out_dev || batch < 1 || size < 1 || !params_ok(h, params)) return YL_ERR_INVALID;
-  if (flags & ~(uint32_t)(YL_HEAD_TRAIN | YL_HEAD_SAVE)) return YL_ERR_INVALID;       // fp32 only: no precision bits
-  if (((uintptr_t)x_dev & (h->cfg.input_nchw ? 3u : 15u)) || ((uintptr_t)out_dev & 15u)) return YL_ERR_UNSUPPORTED;
-  const bool train = flags & YL_HEAD_TRAIN, save = flags & YL_HEAD_SAVE;
-  {
-    SUnit us[YL_STEM_MAX_UNITS];
-    const int n = make_units(h->cfg, batch, size, us);
-    for (int i = 0; i < n; ++i)
-      if (us[i].Mout < 1 || (train && us[i].Mout < 2)) return YL_ERR_INVALID;          // no variance of one value
-  }
-  StemBuffers sb;
-  const yl_status st = ensure(h, batch, size, save, &sb);
-  if (st != YL_OK) return st;
-  hipStream_t s = (hipStream_t)stream;
-  h->mem.fValid = 0;
-  const size_t x0 = (size_t)batch * size * size * h->cfg.in_channels * 4;
-  if (save && hipMemcpyAsync(sb.x, x_dev, x0, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
-  int nl = 0;
-  const float* in = save ? sb.x : x_dev;
-  for (int i = 0; i < sb.n; ++i) {
-    const SUnit& u = sb.us[i];
-    const yl_stage_unit& e = params->unit[i];
-    float* z = save ? sb.z[i] : sb.nz;
-    float* stats = save ? sb.stats[i] : sb.nstats;
-    float* hout = save ? sb.h[i] : (i == sb.n - 1 ? out_dev : sb.nh[i & 1]);
-    const int M = (int)u.Mout, F = u.cout;
-    if (u.k == 3) nl += conv3_forward(s, in, e.w, sb.wpack, z, u.st, batch, u.Sin, u.Sout, u.cin, F, u.planar);
-    else nl += conv1_forward(s, in, e.w, z, u.st, batch, u.Sin, u.Sout, u.cin, F, u.planar);
-    if (train) {
-      StatP sp;
-      sp.a = z; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = sb.spart;
-      sp.M = M; sp.F = F; sp.CQ = pick_cq(F); sp.bwd = 0;
-      hipLaunchKernelGGL(yl_stem_colstats_kernel<false>, dim3(u.tiles, ceil_div(F >> 2, sp.CQ)), dim3(NT), 0, s, sp, u.stat_rows);
-      ++nl;
-    }
-    BnFwdP bp;
-    bp.part = sb.spart; bp.tiles = u.tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
-    bp.rm = e.running_mean; bp.rv = e.running_var; bp.nbt = e.num_batches_tracked; bp.stats = stats;
-    hipLaunchKernelGGL(yl_stage_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp, h->cfg.eps);
-    const long n4 = (long)M * (F >> 2);
-    hipLaunchKernelGGL(yl_stage_bn_kernel<true>, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, (const float*)z, (const float*)stats,
-                       (const float*)e.gamma, (const float*)e.beta, (const float*)nullptr, hout, n4, F);
-    nl += 2;
-    in = hout;
-  }
-  if (save) {
-    const SUnit& u = sb.us[sb.n - 1];
-    if (hipMemcpyAsync(out_dev, in, (size_t)u.Mout * u.cout * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
-  }
-  if (launches) *launches = nl;
-  if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
-  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->mem.fValid = 1; }
-  return YL_OK;
+  if (!h || !x_dev || !out_dev || batch < 1 || size < 1 || !params) return YL_ERR_INVALID;
+  const yl_stage_unit* par[MAX_UNITS];
+  const int n = resolve(h->cfg, params, par);
+  return units_forward<StemPolicy>(h, par, n, x_dev, h->cfg.input_nchw ? 3u : 15u, batch, size, flags, out_dev, stream, launches);
 }
 
 yl_status yl_stem_backward(yl_stem* h, const yl_stem_tensors* params, const yl_stem_tensors* grads, const float* gy_dev,
                            float* dx_dev, void* stream, int32_t* launches) {
-  if (!h || !grads || !gy_dev || !params_ok(h, params)) return YL_ERR_INVALID;
+  if (!h || !grads || !gy_dev || !params) return YL_ERR_INVALID;
   if (dx_dev && h->cfg.input_nchw) return YL_ERR_INVALID;  // the planar image has no gradient
-  if (((uintptr_t)gy_dev & 15u) || ((uintptr_t)dx_dev & 15u)) return YL_ERR_UNSUPPORTED;
-  if (!h->mem.fValid) return YL_ERR_STATE;
-  StemBuffers sb;
-  const yl_status st = ensure(h, h->fB, h->fS, true, &sb);
-  if (st != YL_OK) return st;
-  if (!h->mem.fValid) return YL_ERR_STATE;
-  uintptr_t gany = 0;
-  int first = dx_dev ? 0 : sb.n;         // the first unit something is wanted of
-  for (int i = sb.n - 1; i >= 0; --i) {
-    const yl_stage_unit& g = grads->unit[i];
-    const uintptr_t any = (uintptr_t)g.w | (uintptr_t)g.gamma | (uintptr_t)g.beta;
-    gany |= any;
-    if (any && i < first) first = i;
-  }
-  if (gany & 3u) return YL_ERR_UNSUPPORTED;                // before the first launch: nothing of the caller's is written
-  hipStream_t s = (hipStream_t)stream;
-  const bool train = h->fTrain != 0;
-  const int B = h->fB;
-  int nl = 0;
-  const float* dh = gy_dev;
-  int cur = -1;                          // the buffer dh is in (-1: the caller's gy)
-  for (int i = sb.n - 1; i >= first; --i) {
-    const SUnit& u = sb.us[i];
-    const yl_stage_unit& e = params->unit[i];
-    const yl_stage_unit& g = grads->unit[i];
-    const float* xin = i ? sb.h[i - 1] : sb.x;
-    const int M = (int)u.Mout, F = u.cout, cq = pick_cq(F);
-    const long n4 = (long)M * (F >> 2);
-    const bool sums = train || g.gamma || g.beta;          // sum g, sum g * xhat: dbeta, dgamma and the batch statistics' two means
-    if (sums) {
-      StatP sp;
-      sp.a = dh; sp.h = sb.h[i]; sp.z = sb.z[i]; sp.stats = sb.stats[i]; sp.part = sb.spart;
-      sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 1;
-      hipLaunchKernelGGL(yl_stem_colstats_kernel<true>, dim3(u.tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp, u.stat_rows);
-      ++nl;
-    }
-    BnBwdP bp;
-    bp.part = sb.spart; bp.tiles = sums ? u.tiles : 0; bp.M = M; bp.F = F; bp.train = train;
-    bp.dgamma = g.gamma; bp.dbeta = g.beta; bp.coef = sb.coef;
-    hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
-    ++nl;
-    const bool need_dx = i > first || (i == 0 && dx_dev);
-    if (!need_dx && !g.w) break;
-    const int t = cur >= 0 ? cur : 0;    // dz: in place, or (the caller's gy is only read) in the first buffer
-    float* dz = sb.g[t];
-    hipLaunchKernelGGL(yl_stage_bn_bwd_kernel<true>, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, dh, (const float*)sb.h[i],
-                       (const float*)sb.z[i], (const float*)sb.stats[i], (const float*)sb.coef, (const float*)e.gamma, dz, n4, F);
-    ++nl;
-    if (g.w) {
-      if (u.k == 3) nl += conv3_wgrad(s, xin, dz, sb.wpart, g.w, u.st, B, u.Sin, u.Sout, u.cin, F, u.planar, u.wrows, u.wsplits);
-      else nl += conv1_wgrad(s, xin, dz, sb.wpart, g.w, u.st, B, u.Sin, u.Sout, u.cin, F, u.planar, u.wrows, u.wsplits);
-    }
-    if (!need_dx) break;
-    float* dst = i ? sb.g[1 - t] : dx_dev;
-    if (u.k == 3) nl += conv3_dgrad(s, dz, e.w, sb.wpack, dst, u.st, B, u.Sin, u.Sout, u.cin, F);
-    else nl += conv1_dgrad(s, dz, e.w, dst, u.st, B, u.Sin, u.Sout, u.cin, F);
-    dh = dst; cur = 1 - t;
-  }
-  if (launches) *launches = nl;
-  return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;
+  const yl_stage_unit *par[MAX_UNITS], *grd[MAX_UNITS];
+  const int n = resolve(h->cfg, params, par);
+  resolve(h->cfg, grads, grd);
+  return units_backward<StemPolicy>(h, par, grd, n, gy_dev, dx_dev, stream, launches);
 }
 
 yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,

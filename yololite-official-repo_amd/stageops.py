@@ -22,7 +22,8 @@ k == 0.  Parameters and buffers carry timm's names and shapes under `prefix`
 num_batches_tracked`, `pw_exp.*`, `dw_mid.*`, `pw_proj.*`; `conv.weight`, `bn1.*` for cn blocks), so state_dict() merges
 into a checkpoint and FusedTrainStep takes parameters().
 
-The whole stack is ONE torch.autograd.Function over yl_stage_forward / yl_stage_backward.  train() / eval() select the
+The whole stack is ONE torch.autograd.Function (_trainmod.UnitStackFunction, which the dense stem shares) over
+yl_stage_forward / yl_stage_backward.  train() / eval() select the
 BatchNorm mode.  Gradients nobody asked for are not computed, and nothing upstream of the first one wanted runs
 (`last_launches` says what ran).  One forward is held for backward at a time: a second forward before backward()
 replaces it, and the stale backward raises.  fp32 on one HIP device; no CPU fallback.  ReLU only: relu6, silu, TF-SAME
@@ -177,37 +178,6 @@ class _TailHandle(_Handle):
     who = "BackboneTail"
 
 
-class _StageFunction(torch.autograd.Function):
-    """y = stack(x NHWC, parameters): yl_stage_forward / yl_stage_backward"""
-
-    @staticmethod
-    def forward(fctx, hd: _Handle, bufs, train: bool, grad_mode: bool, out_shape, x, *params):
-        save = tm.saving(fctx, grad_mode)
-        xd = tm.aligned(x.detach())
-        dev = x.device
-        ps = tm.detached_params(hd.who, params, dev)
-        B, S = int(x.shape[0]), int(x.shape[1])
-        out = torch.empty(out_shape, device=dev, dtype=torch.float32)
-        hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), xd.data_ptr(), B, S, tm.flags(train, save), out.data_ptr())
-        if save:
-            fctx.save_for_backward(xd, *params)
-            fctx.hd, fctx.bufs, fctx.generation = hd, bufs, hd.generation
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(fctx, gy):
-        hd = fctx.hd
-        hd.check_generation(fctx.generation, hd.who + ": the stack", "one forward")
-        saved = fctx.saved_tensors
-        gy = tm.aligned(gy.to(dtype=torch.float32).contiguous())
-        grads = tm.grads_like(saved, fctx.needs_input_grad[5:])
-        ps = [p.detach() for p in saved[1:]]
-        hd.launch("backward", saved[0].device, C.byref(hd.table(ps, fctx.bufs)), C.byref(hd.table(grads[1:])), gy.data_ptr(),
-                  tm.ptr(grads[0]))
-        return (None, None, None, None, None) + tuple(grads)
-
-
 def _conv_bn(cin: int, cout: int, k: int, s: int, groups: int, eps: float, names=("conv", "bn")) -> nn.Module:
     """Container only (timm's ConvNormAct / ConvBnAct): the layers hold the parameters; their forward is never called."""
     m = nn.Module()
@@ -226,7 +196,7 @@ def _nest(root: nn.Module, path: str, module: nn.Module):
     root.add_module(parts[-1], module)
 
 
-class UIBStack(nn.Module):
+class UIBStack(tm.UnitStack):
     """See the module docstring."""
     _who, _handle_cls = "UIBStack", _Handle
 
@@ -257,37 +227,11 @@ class UIBStack(nn.Module):
             _nest(self, f"{self.prefix}blocks.{d['name']}", blk)
         self._handle = self._handle_cls(self.in_channels, self.blocks_cfg, self.eps)
 
-    def _param_list(self) -> List[torch.Tensor]:
-        """per unit in running order: conv weight, BatchNorm weight, BatchNorm bias"""
-        out = []
-        for cv, bn in zip(self._convs, self._bns):
-            out += [cv.weight, bn.weight, bn.bias]
-        return out
-
-    def _stat_buffers(self):
-        return [(bn.running_mean, bn.running_var, bn.num_batches_tracked) for bn in self._bns]
-
-    @property
-    def last_launches(self) -> Dict[str, int]:
-        """kernels enqueued by the last forward / backward"""
-        return dict(self._handle.last_launches)
-
-    def held(self) -> Dict[str, int]:
-        """the bytes the handle holds on the device and whether a forward is held for backward"""
-        return self._handle.held()
-
     def out_size(self, size: int) -> int:
         return _sizes(self.blocks_cfg, int(size))[-1]
 
-    def _check_rows(self, B: int, S: int) -> List[int]:
-        """-> the size of every unit's output; in training no BatchNorm may see ONE value per channel"""
-        sizes = _sizes(self.blocks_cfg, S)
-        if self.training:
-            for So, bn in zip(sizes, self._bns):
-                if B * So * So == 1:
-                    raise ValueError("Expected more than 1 value per channel when training, got input size "
-                                     f"{[B, bn.num_features, So, So]}")
-        return sizes
+    def _unit_sizes(self, S: int) -> List[int]:
+        return _sizes(self.blocks_cfg, S)
 
     def forward(self, x: torch.Tensor, layout: Optional[str] = None) -> torch.Tensor:
         """`x`: "nchw" ([B,Cin,S,S], any strides) or "nhwc" ([B,S,S,Cin]); None reads the layout off the shape and
@@ -300,14 +244,7 @@ class UIBStack(nn.Module):
             self._check_rows(int(x.shape[0]), int(x.shape[2]))   # is not: what BatchNorm refuses comes first all the same
             raise
         B, S = int(x.shape[0]), int(x.shape[1])
-        sizes = self._check_rows(B, S)
-        params = self._param_list()
-        if any(p.device != x.device for p in params):
-            raise _lib.YoloLiteHipError(f"{self._who}: parameters and inputs must live on one HIP device")
-        self._handle.ensure(x.device)
-        x = x.float().contiguous()                         # autograd carries the gradient back through cast and copy
-        shape = (B, sizes[-1], sizes[-1], self.out_channels)
-        return _StageFunction.apply(self._handle, self._stat_buffers(), self.training, torch.is_grad_enabled(), shape, x, *params)
+        return self._run_stack(x, B, self._check_rows(B, S), False)
 
 
 def _tail_blocks(meta: dict, start: str = "c4"):

@@ -16,7 +16,8 @@ input_layout="nchw": the stack's input is the planar image [B,cin,S,S] with cin 
 gradient here, and a tensor that requires one is refused.  With "nhwc" x is [B,S,S,cin] (cin a multiple of 4) and its
 gradient is computed when asked for.  The output is NHWC.
 
-The whole stack is ONE torch.autograd.Function over yl_stem_forward / yl_stem_backward.  train() / eval() select the
+The whole stack is ONE torch.autograd.Function (_trainmod.UnitStackFunction, which the backbone stage shares) over
+yl_stem_forward / yl_stem_backward.  train() / eval() select the
 BatchNorm mode.  Gradients nobody asked for are not computed, and nothing upstream of the first one wanted runs
 (`last_launches` says what ran).  One forward is held for backward at a time.  fp32 on one HIP device; no CPU fallback.
 ReLU only: the `_skip` residual, other activations and TF-SAME padding are refused by name, as are the backbone
@@ -130,41 +131,7 @@ class _StemHandle(_Handle):
     who = "BackboneStem"
 
 
-class _StemFunction(torch.autograd.Function):
-    """y = stack(x, parameters): yl_stem_forward / yl_stem_backward.  x: NHWC, or the planar image (no gradient)"""
-
-    @staticmethod
-    def forward(fctx, hd: _Handle, bufs, train: bool, grad_mode: bool, out_shape, nchw: bool, x, *params):
-        save = tm.saving(fctx, grad_mode)
-        xd = x.detach() if nchw else tm.aligned(x.detach())
-        dev = x.device
-        ps = tm.detached_params(hd.who, params, dev)
-        B, S = int(x.shape[0]), int(x.shape[2])
-        out = torch.empty(out_shape, device=dev, dtype=torch.float32)
-        hd.launch("forward", dev, C.byref(hd.table(ps, bufs)), xd.data_ptr(), B, S, tm.flags(train, save), out.data_ptr())
-        if save:
-            fctx.save_for_backward(xd, *params)
-            fctx.hd, fctx.bufs, fctx.generation, fctx.nchw = hd, bufs, hd.generation, nchw
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(fctx, gy):
-        hd = fctx.hd
-        hd.check_generation(fctx.generation, hd.who + ": the stack", "one forward")
-        saved = fctx.saved_tensors
-        gy = tm.aligned(gy.to(dtype=torch.float32).contiguous())
-        need = list(fctx.needs_input_grad[6:])
-        if fctx.nchw:
-            need[0] = False
-        grads = tm.grads_like(saved, need)
-        ps = [p.detach() for p in saved[1:]]
-        hd.launch("backward", saved[0].device, C.byref(hd.table(ps, fctx.bufs)), C.byref(hd.table(grads[1:])), gy.data_ptr(),
-                  tm.ptr(grads[0]))
-        return (None, None, None, None, None, None) + tuple(grads)
-
-
-class ConvStack(nn.Module):
+class ConvStack(tm.UnitStack):
     """See the module docstring."""
     _who, _handle_cls = "ConvStack", _Handle
 
@@ -183,34 +150,11 @@ class ConvStack(nn.Module):
             self._convs.append(cv); self._bns.append(bn)
         self._handle = self._handle_cls(self.in_channels, self.units_cfg, self.eps, input_layout == "nchw")
 
-    def _param_list(self) -> List[torch.Tensor]:
-        out = []
-        for cv, bn in zip(self._convs, self._bns):
-            out += [cv.weight, bn.weight, bn.bias]
-        return out
-
-    def _stat_buffers(self):
-        return [(bn.running_mean, bn.running_var, bn.num_batches_tracked) for bn in self._bns]
-
-    @property
-    def last_launches(self) -> Dict[str, int]:
-        """kernels enqueued by the last forward / backward"""
-        return dict(self._handle.last_launches)
-
-    def held(self) -> Dict[str, int]:
-        return self._handle.held()
-
     def out_size(self, size: int) -> int:
         return _sizes(self.units_cfg, int(size))[-1]
 
-    def _check_rows(self, B: int, S: int) -> List[int]:
-        sizes = _sizes(self.units_cfg, S)
-        if self.training:
-            for So, bn in zip(sizes, self._bns):
-                if B * So * So == 1:
-                    raise ValueError("Expected more than 1 value per channel when training, got input size "
-                                     f"{[B, bn.num_features, So, So]}")
-        return sizes
+    def _unit_sizes(self, S: int) -> List[int]:
+        return _sizes(self.units_cfg, S)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """`x`: [B,cin,S,S] with input_layout "nchw", [B,S,S,cin] with "nhwc".  -> NHWC [B,S_out,S_out,C_out]."""
@@ -228,14 +172,7 @@ class ConvStack(nn.Module):
         sizes = self._check_rows(B, S)
         if not x.is_cuda:
             raise _lib.YoloLiteHipError(f"{self._who} needs its inputs on a HIP device (no CPU fallback)")
-        params = self._param_list()
-        if any(p.device != x.device for p in params):
-            raise _lib.YoloLiteHipError(f"{self._who}: parameters and inputs must live on one HIP device")
-        self._handle.ensure(x.device)
-        x = x.float().contiguous()
-        shape = (B, sizes[-1], sizes[-1], self.out_channels)
-        return _StemFunction.apply(self._handle, self._stat_buffers(), self.training, torch.is_grad_enabled(), shape, nchw, x,
-                                   *params)
+        return self._run_stack(x, B, sizes, nchw)
 
 
 def _stem_units(meta: dict):
