@@ -29,7 +29,13 @@ OP_CASES = [
     dict(name="centre", F=8, S=1, B=4, seed=1204),      # centre tap only
     dict(name="k32", F=40, S=3, B=1, seed=1205),        # one full 32-block plus a ragged one
 ]
-OP_BY_NAME = {c["name"]: c for c in OP_CASES}
+# the first level of the wide cases of _dense_neck_cases.py: six channel blocks and 21 k-blocks of 16 with a ragged last
+# (F 328), eight full channel blocks (F 512)
+OP_WIDE = [
+    dict(name="f328", F=328, S=4, B=1, seed=1206),
+    dict(name="f512", F=512, S=3, B=1, seed=1207),
+]
+OP_BY_NAME = {c["name"]: c for c in OP_CASES + OP_WIDE}
 
 
 def rounded(t: torch.Tensor, precision: str) -> torch.Tensor:

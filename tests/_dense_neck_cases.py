@@ -39,6 +39,19 @@ CASES = [
 ]
 EVAL_CASE = "base"
 
+# the widths the zoo's dense necks run (F = 196 .. 512), in tests/golden/dense_neck_train_wide.npz.  Seeds: the series goes on
+# (717 is E2E's)
+WIDE = [
+    dict(name="f328", B=1, F=328, Cin=(48, 320), depth=1, sizes=(4, 2), seed=818),     # six channel blocks and 21 k-blocks, the last ragged; two groups
+    dict(name="f512", B=1, F=512, Cin=(64, 64), depth=1, sizes=(3, 2), seed=919),      # eight full channel blocks, two full groups
+]
+FIXTURE_WIDE = os.path.join(GOLDEN, "dense_neck_train_wide.npz")
+
+
+def fixture_path(case):
+    return FIXTURE_WIDE if any(case["name"] == w["name"] for w in WIDE) else FIXTURE
+
+
 # the configuration whose reference key list DetectNeckMS is held to
 KEYS = dict(B=1, F=16, Cin=(8, 12, 20), depth=2, sizes=(8, 4, 2))
 

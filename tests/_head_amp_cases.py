@@ -29,13 +29,13 @@ import torch
 import torch.nn.functional as TF
 
 from _dense_neck_amp_np import DTYPES, round_to
-from _head_cases import CASES, bar, case_inputs, stored_indices, tensor_shapes  # noqa: F401  (bar is re-exported)
+from _head_cases import CASES, WIDE, bar, case_inputs, stored_indices, tensor_shapes  # noqa: F401  (bar is re-exported)
 from _head_np import EPS, MOMENTUM
 
 PRECISIONS = ("fp16", "bf16")
 PASSES = ("forward", "dgrad", "wgrad")
 SITES = (0, "out")
-BY_NAME = {c["name"]: c for c in CASES}
+BY_NAME = {c["name"]: c for c in CASES + WIDE}          # the op level runs over the wide cases as well
 
 
 def rounded(t: torch.Tensor, precision: str) -> torch.Tensor:

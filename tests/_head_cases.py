@@ -32,6 +32,29 @@ EVAL_CASE = "base"
 # seeds: the first of 101, 202, 303.., counting up, whose case passes the generator's admission rule (f244: 303-305 put
 # a BatchNorm output within 64 fp32 errors of zero)
 
+# the widths the zoo's heads run (F = 160 .. 512), in tests/golden/head_train_wide.npz.  Above 256 channels the row
+# reductions and the depthwise weight gradient run a second channel group and the per-channel kernels a second workgroup;
+# few rows, because every value in front of a ReLU has to pass the admission rule.  Seeds: the rule of CASES (101 is
+# admitted for all of them)
+WIDE = [
+    dict(name="f328", F=328, C=2, A=1, depth=1, B=2, sizes=(3,), seed=101),    # 82 quads: a ragged second group; six p-tiles, the last ragged
+    dict(name="f512", F=512, C=2, A=1, depth=2, B=2, sizes=(2,), seed=101),    # two full groups, two blocks
+]
+FIXTURE_WIDE = os.path.join(GOLDEN, "head_train_wide.npz")
+
+
+def fixture_path(case):
+    return FIXTURE_WIDE if any(case["name"] == w["name"] for w in WIDE) else FIXTURE
+
+
+# the shapes of test_head_gemm_fp32_gpu.py: where split_plan's other bounds decide.  cap128: 10 368 rows, want 128 against
+# most 162: 108 splits of 96 rows.  free: 4 608 rows, 16 tiles, want 64 against most 72: 58 splits of 80 rows; three
+# anchors of 85 columns are 255 columns, four q groups, so the outputs' weight gradient has 16 tiles and is cut the same way
+GEMM_OP_SHAPES = [
+    dict(name="cap128", F=16, C=3, A=1, depth=1, B=2, sizes=(72,), seed=1501, wgrad=(96, 108, "cap128")),
+    dict(name="free", F=256, C=80, A=3, depth=1, B=2, sizes=(48,), seed=1502, wgrad=(80, 58, "free")),
+]
+
 # the 20-step fit of the end-to-end test: one fixed batch, SGD with momentum (no nesterov, no weight decay), amp off
 E2E = dict(F=16, C=3, A=1, depth=1, B=2, sizes=(8, 4, 2), seed=707, img_size=64, lr=0.02, momentum=0.9, steps=20,
            gt_xyxy=[[6.0, 8.0, 30.0, 34.0], [36.0, 30.0, 60.0, 58.0], [10.0, 12.0, 50.0, 44.0]], gt_label=[0, 2, 1],

@@ -36,6 +36,20 @@ EVAL_CASE = "base"
 # seeds: the first of 101, 202, 303.., counting up, whose case passes the generator's admission rule (base: 101 puts an
 # eval-mode BatchNorm output of p4 within 64 fp32 errors of zero; rows: 505 fails the rule likewise)
 
+# the widths the zoo's depthwise necks run (F = 160 .. 320, Cin up to 960), in tests/golden/neck_train_wide.npz; few rows,
+# because every value in front of a ReLU has to pass the admission rule.  Seeds: the rule of CASES (f288: 101, 202 and 303
+# fail it; f320: 101 .. 707 do)
+WIDE = [
+    dict(name="f288", B=1, F=288, Cin=(96, 960), depth=1, sizes=(4, 2), seed=404),     # 72 quads: a ragged second group; pt 6, three p-tiles; K = 960
+    dict(name="f320", B=2, F=320, Cin=(64, 128), depth=1, sizes=(4, 2), seed=808),     # 80 quads; pt 4, five full p-tiles
+]
+FIXTURE_WIDE = os.path.join(GOLDEN, "neck_train_wide.npz")
+
+
+def fixture_path(case):
+    return FIXTURE_WIDE if any(case["name"] == w["name"] for w in WIDE) else FIXTURE
+
+
 # the configuration whose reference key list DetectNeck is held to
 KEYS = dict(B=1, F=16, Cin=(8, 12, 20), depth=2, sizes=(8, 4, 2))
 

@@ -20,6 +20,7 @@ import os
 import numpy as np
 
 from _head_cases import SAMPLE_ABOVE, bar, sample_indices  # noqa: F401  (re-exported)
+from _launch_classes import cdiv, r16, split_plan
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIXTURE = os.path.join(GOLDEN, "stage_train.npz")
@@ -48,6 +49,29 @@ EVAL_CASE = "a5k5s2"
 EPS = 1e-5
 # seeds: the first of 101, 202, 303.., counting up, whose case passes the generator's admission rule
 # (make_stage_fixtures.py --search prints them; a5k5s2: 101, 202 and 303 fail it in one of the two modes)
+
+# the widths the zoo's backbones run (edge_n: mid 288 / 256, C5 480; edge_s / m / l: mid 576 / 512, C5 960), in
+# tests/golden/stage_train_wide.npz.  Above 256 channels the row reductions and the depthwise weight gradient run a second
+# channel group and the per-channel kernels a second workgroup; few rows, because every value in front of a ReLU has to
+# pass the admission rule (the row-count classes are test_stage_depthwise_gpu.py's and test_head_gemm_fp32_gpu.py's)
+WIDE = [
+    # 72 quads: two groups, the last ragged; 5x5 stride 2 over two groups; pt 6 with three (NP 288) and five (NP 480) p-tiles
+    dict(name="wide288", B=2, S=4, cin=48, blocks=[_uir(0, 5, 2, 288, 64), dict(type="cn", k=1, s=1, c=480, name="1.0")], seed=303),
+    # two full groups; 3x3 stride 1 over two full groups; pt 4 with eight full p-tiles; a weight gradient with 8 q groups
+    dict(name="wide512", B=2, S=3, cin=64, blocks=[_uir(3, 3, 1, 512, 64)], seed=1616),
+]
+FIXTURE_WIDE = os.path.join(GOLDEN, "stage_train_wide.npz")
+
+
+def fixture_path(case):
+    return FIXTURE_WIDE if any(case["name"] == w["name"] for w in WIDE) else FIXTURE
+
+# the shapes of test_stage_depthwise_gpu.py, (B, S, C), each run for every (k, stride) of DW_OP_KS and every pass.  C 260 is
+# 65 quads: a second channel group with one quad switched on; C 512 is two full groups; (2, 32, 4) gives 2048 / 512 output
+# rows under stride 1 / 2: full row tiles; (3, 20, 4) gives 1200 / 300: a ragged last tile
+DW_OP_KS = [(k, s) for k in (3, 5) for s in (1, 2)]
+DW_OP_SHAPES = [(B, S, C) for S in (1, 2, 5, 8, 9) for C in (4, 20) for B in (1, 3)] + [(3, 10, 4), (3, 10, 20)]
+DW_OP_WIDE = [(1, 5, 260), (1, 5, 512), (2, 32, 4), (3, 20, 4)]
 
 
 def modes(case):
@@ -282,21 +306,8 @@ def stack_all(case, inputs, train, dtype=np.float64):
 
 def plan_restated(case, B=None, S=None, stat_rows=256, gemm_rows=64):
     """the byte formulas of include/yololite_hip.h (yl_stage_plan_info) written again"""
-    def cdiv(a, b):
-        return -(-a // b)
-
-    def r16(v):
-        return (v + 15) // 16 * 16
-
-    def pick_pt(NP):
-        return 6 if cdiv(NP, 96) * 96 < cdiv(NP, 64) * 64 else 4
-
     def splits(M, NP, NQ):
-        tiles = cdiv(NP, 16 * pick_pt(NP)) * cdiv(NQ, gemm_rows)
-        want = min(max(1024 // tiles, 8), 128)
-        want = min(want, cdiv(M, 64))
-        rows = cdiv(cdiv(M, want), 16) * 16
-        return rows, cdiv(M, rows)
+        return split_plan(M, NP, NQ, gemm_rows)[:2]
 
     B = case["B"] if B is None else B
     c = dict(case, S=case["S"] if S is None else S)

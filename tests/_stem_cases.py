@@ -49,6 +49,19 @@ CASES = [
                 _u(3, 2, 16, "blocks.1.0.conv", "blocks.1.0.bn1"), _u(1, 1, 8, "blocks.1.1.conv", "blocks.1.1.bn1")]),
 ]
 EVAL_CASE = "stem_to_c3"
+# the widths the zoo's stems run (stage 1 of mobilenetv4_conv_small: 32 -> 96 channels, 3x3 stride 2), in
+# tests/golden/stem_train_wide.npz: the convolution with 48 output channels per workgroup (PT 3) and two channel blocks,
+# and its weight gradient with two 64-wide blocks of dz channels
+WIDE = [
+    dict(name="wide96", B=2, S=4, cin=32, planar=False, units=[_u(3, 2, 96)], seed=101),
+]
+FIXTURE_WIDE = os.path.join(GOLDEN, "stem_train_wide.npz")
+
+
+def fixture_path(case):
+    return FIXTURE_WIDE if any(case["name"] == w["name"] for w in WIDE) else FIXTURE
+
+
 # the whole oracle_tiny backbone: the stem_to_c3 units, then stage 2 (C3 -> C4) and stages 3 + 4 (C4 -> C5) as _stage_cases cases
 TINY = dict(name="tiny_backbone", B=2, S=64, seed=34037,
             stem=dict(CASES[-1], name="tiny_backbone.stem", S=64),

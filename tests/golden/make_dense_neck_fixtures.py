@@ -3,7 +3,10 @@
 of the reference checkout, imported unmodified; pure torch, CPU), forward and backward, in fp32 and in fp64 on the SAME
 fp32-valued inputs.
 
-    python tests/golden/make_dense_neck_fixtures.py --reference /path/to/YoloLite-Official-Repo
+    python tests/golden/make_dense_neck_fixtures.py --reference /path/to/YoloLite-Official-Repo [--wide]
+
+--wide writes dense_neck_train_wide.npz (the WIDE cases: their tensors only, no `keys`, no `e2e/losses`) and leaves
+dense_neck_train.npz alone.
 
 As make_neck_fixtures.py: an empty module named timm is placed in sys.modules first (model_v2.py imports timm at module
 level and uses it only in the constructors), and the model is made without its constructor (__new__ +
@@ -26,8 +29,8 @@ from torch import nn
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-from _dense_neck_cases import (CASES, E2E, KEYS, case_inputs, head_inputs, modes, stored_indices,  # noqa: E402
-                               tensor_shapes)
+from _dense_neck_cases import (CASES, E2E, FIXTURE, FIXTURE_WIDE, KEYS, WIDE, case_inputs, head_inputs, modes,  # noqa: E402
+                               stored_indices, tensor_shapes)
 from _dense_neck_np import fit_reference  # noqa: E402
 from make_neck_fixtures import _Feats, load_reference  # noqa: E402
 
@@ -104,10 +107,11 @@ def run_reference(mod, case, inputs, train, dtype):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="checkout of the reference repository")
+    ap.add_argument("--wide", action="store_true", help="write the WIDE cases' file instead")
     a = ap.parse_args()
     mod = load_reference(a.reference)
     arrays = {}
-    for case in CASES:
+    for case in (WIDE if a.wide else CASES):
         inputs = case_inputs(case)
         for mode in modes(case):
             r32s = run_reference(mod, case, inputs, mode == "train", torch.float32)
@@ -131,16 +135,17 @@ def main():
                 arrays[key + "/max64"] = np.asarray(m64s, np.float64)
                 worst = max(e / max(m, 1e-300) for e, m in zip(e32s, m64s))
                 print(f"{case['name']:6s} {mode:5s} L{li} S={lv['S']:2d}  worst e32/max64={worst:.1e}")
-    # the key list DetectNeckMS is held to: the reference's names, shapes and dtypes of laterals and smooth blocks
-    m = build_reference(mod, KEYS["F"], KEYS["depth"], KEYS["Cin"], [3, 4, 5], torch.float32)
-    keys = [[n, list(v.shape), str(v.dtype)] for n, v in m.state_dict().items() if n.startswith(("lateral", "smooth"))]
-    arrays["keys"] = np.asarray(json.dumps(keys))
-    losses = fit_reference(E2E, case_inputs(E2E), head_inputs(E2E))
-    drop = (losses[0] - losses[-1]) / losses[0]
-    print("e2e losses", losses[0], "->", losses[-1], f"drop {100 * drop:.1f} %")
-    assert drop >= 0.2, "the CPU loop's own drop must be at least 20 % of L0: choose another lr / batch"
-    arrays["e2e/losses"] = losses
-    path = os.path.join(OUT, "dense_neck_train.npz")
+    if not a.wide:
+        # the key list DetectNeckMS is held to: the reference's names, shapes and dtypes of laterals and smooth blocks
+        m = build_reference(mod, KEYS["F"], KEYS["depth"], KEYS["Cin"], [3, 4, 5], torch.float32)
+        keys = [[n, list(v.shape), str(v.dtype)] for n, v in m.state_dict().items() if n.startswith(("lateral", "smooth"))]
+        arrays["keys"] = np.asarray(json.dumps(keys))
+        losses = fit_reference(E2E, case_inputs(E2E), head_inputs(E2E))
+        drop = (losses[0] - losses[-1]) / losses[0]
+        print("e2e losses", losses[0], "->", losses[-1], f"drop {100 * drop:.1f} %")
+        assert drop >= 0.2, "the CPU loop's own drop must be at least 20 % of L0: choose another lr / batch"
+        arrays["e2e/losses"] = losses
+    path = os.path.join(OUT, os.path.basename(FIXTURE_WIDE if a.wide else FIXTURE))
     np.savez_compressed(path, **arrays)
     print(path, os.path.getsize(path), "bytes")
     assert os.path.getsize(path) < (1 << 20)

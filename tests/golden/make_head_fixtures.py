@@ -3,7 +3,10 @@
 YOLOLiteMS._forward_head (scripts/model/model_v2.py of the reference checkout, imported unmodified; pure torch, CPU),
 forward and backward, in fp32 and in fp64 on the SAME fp32-valued inputs.
 
-    python tests/golden/make_head_fixtures.py --reference /path/to/YoloLite-Official-Repo
+    python tests/golden/make_head_fixtures.py --reference /path/to/YoloLite-Official-Repo [--wide]
+
+--wide writes head_train_wide.npz (the WIDE cases: their tensors only, no `keys`, no `e2e/losses`) and leaves
+head_train.npz alone.
 
 model_v2.py imports timm at module level and uses it only in the model constructors; an empty module named timm is
 placed in sys.modules first.  Inputs come from the seeds of tests/_head_cases.py; the archive's layout is described
@@ -27,7 +30,8 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from _head_cases import CASES, E2E, case_inputs, modes, stored_indices, tensor_shapes  # noqa: E402
+from _head_cases import (CASES, E2E, FIXTURE, FIXTURE_WIDE, WIDE, case_inputs, modes, stored_indices,  # noqa: E402
+                         tensor_shapes)
 from _head_np import fit_reference  # noqa: E402
 
 OUT = os.environ.get("YL_FIXTURE_OUT") or HERE
@@ -73,10 +77,11 @@ def run_reference(mod, case, lv, train, dtype):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="checkout of the reference repository")
+    ap.add_argument("--wide", action="store_true", help="write the WIDE cases' file instead")
     a = ap.parse_args()
     mod = load_reference(a.reference)
     arrays = {}
-    for case in CASES:
+    for case in (WIDE if a.wide else CASES):
         inputs = case_inputs(case)
         for mode in modes(case):
             for li, lv in enumerate(inputs):
@@ -104,18 +109,19 @@ def main():
                 worst = max(e / max(m, 1e-300) for e, m in zip(e32s, m64s))
                 print(f"{case['name']:6s} {mode:5s} L{li} S={lv['S']:2d}  min|bn|={min(np.abs(b).min() for b in bn64):.1e}  "
                       f"worst e32/max64={worst:.1e}")
-    # the key list DetectHeads is held to: three reference heads as YOLOLiteMS names them
-    keys = []
-    for k in (3, 4, 5):
-        head = mod.make_head(1, 2, 3, 16)
-        keys += [[f"head{k}.{n}", list(v.shape), str(v.dtype)] for n, v in head.state_dict().items()]
-    arrays["keys"] = np.asarray(json.dumps(keys))
-    losses = fit_reference(E2E, case_inputs(E2E))
-    drop = (losses[0] - losses[-1]) / losses[0]
-    print("e2e losses", losses[0], "->", losses[-1], f"drop {100 * drop:.1f} %")
-    assert drop >= 0.2, "the CPU loop's own drop must be at least 20 % of L0: choose another lr / batch"
-    arrays["e2e/losses"] = losses
-    path = os.path.join(OUT, "head_train.npz")
+    if not a.wide:
+        # the key list DetectHeads is held to: three reference heads as YOLOLiteMS names them
+        keys = []
+        for k in (3, 4, 5):
+            head = mod.make_head(1, 2, 3, 16)
+            keys += [[f"head{k}.{n}", list(v.shape), str(v.dtype)] for n, v in head.state_dict().items()]
+        arrays["keys"] = np.asarray(json.dumps(keys))
+        losses = fit_reference(E2E, case_inputs(E2E))
+        drop = (losses[0] - losses[-1]) / losses[0]
+        print("e2e losses", losses[0], "->", losses[-1], f"drop {100 * drop:.1f} %")
+        assert drop >= 0.2, "the CPU loop's own drop must be at least 20 % of L0: choose another lr / batch"
+        arrays["e2e/losses"] = losses
+    path = os.path.join(OUT, os.path.basename(FIXTURE_WIDE if a.wide else FIXTURE))
     np.savez_compressed(path, **arrays)
     print(path, os.path.getsize(path), "bytes")
     assert os.path.getsize(path) < (1 << 20)

@@ -2,14 +2,17 @@
 """Generate tests/golden/stage_train.npz from the oracle/backbones.py modules (UniversalInvertedResidual, ConvBnAct; pure
 torch, CPU, torch autograd), forward and backward, in fp32 and in float64 on the SAME fp32-valued inputs.
 
-    python tests/golden/make_stage_fixtures.py [--search]
+    python tests/golden/make_stage_fixtures.py [--wide] [--search]
+
+--wide writes stage_train_wide.npz from the WIDE cases and leaves stage_train.npz alone; without it only the CASES file is
+written.
 
 Inputs come from the seeds of tests/_stage_cases.py; the archive's layout is described there.
 
 Admission rule, asserted for every case, mode and unit with a ReLU (none is dropped; change the seed in _stage_cases.py
 and say so there): the ReLU masks of the fp32 and the float64 run are identical, and the smallest |BatchNorm output| in
 front of the ReLU in the float64 run is at least 64 x the fp32 run's error in that tensor -- otherwise a case pins a ReLU
-tie.  --search prints, per case, the first seed of 101, 202, 303, ... that is admitted, and writes nothing."""
+tie.  --search prints, per case of CASES and WIDE, the first seed of 101, 202, 303, ... that is admitted, and writes nothing."""
 import argparse
 import os
 import sys
@@ -23,7 +26,7 @@ from torch import nn
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-from _stage_cases import CASES, EPS, case_inputs, modes, stored_indices, tensor_shapes, units  # noqa: E402
+from _stage_cases import CASES, EPS, FIXTURE, FIXTURE_WIDE, WIDE, case_inputs, modes, stored_indices, tensor_shapes, units  # noqa: E402
 from oracle.backbones import ConvBnAct, UniversalInvertedResidual  # noqa: E402
 
 OUT = os.environ.get("YL_FIXTURE_OUT") or HERE
@@ -93,8 +96,8 @@ def admitted(case, inputs, mode):
 
 
 def search():
-    for case in CASES:
-        for k in range(1, 40):
+    for case in CASES + WIDE:
+        for k in range(1, 100):
             seed = 101 * k
             inputs = case_inputs(case, seed)
             if all(admitted(case, inputs, mode)[3] is None for mode in modes(case)):
@@ -105,10 +108,12 @@ def search():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--search", action="store_true")
-    if ap.parse_args().search:
+    ap.add_argument("--wide", action="store_true", help="write stage_train_wide.npz (the WIDE cases) instead")
+    a = ap.parse_args()
+    if a.search:
         return search()
     arrays = {}
-    for case in CASES:
+    for case in (WIDE if a.wide else CASES):
         inputs = case_inputs(case)
         for mode in modes(case):
             r32, r64, bn64, why = admitted(case, inputs, mode)
@@ -130,7 +135,7 @@ def main():
             arrays[key + "/max64"] = np.asarray(m64s, np.float64)
             worst = max(e / max(m, 1e-300) for e, m in zip(e32s, m64s))
             print(f"{case['name']:10s} {mode:5s} min|bn|={min(np.abs(b).min() for b in bn64):.1e}  worst e32/max64={worst:.1e}")
-    path = os.path.join(OUT, "stage_train.npz")
+    path = os.path.join(OUT, os.path.basename(FIXTURE_WIDE if a.wide else FIXTURE))
     np.savez_compressed(path, **arrays)
     print(path, os.path.getsize(path), "bytes")
     assert os.path.getsize(path) < (1 << 20)

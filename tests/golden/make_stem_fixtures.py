@@ -2,14 +2,16 @@
 """Generate tests/golden/stem_train.npz from the oracle/backbones.py modules (ConvBnAct, FeatureBackbone; pure torch, CPU,
 torch autograd), forward and backward, in fp32 and in float64 on the SAME fp32-valued inputs.
 
-    python tests/golden/make_stem_fixtures.py [--search]
+    python tests/golden/make_stem_fixtures.py [--wide] [--search]
+
+--wide writes stem_train_wide.npz from the WIDE cases and leaves stem_train.npz alone.
 
 Inputs come from the seeds of tests/_stem_cases.py; the archive's layout is described there.
 
 Admission rule, asserted for every case, mode and ReLU (none is dropped; change the seed in _stem_cases.py and say so
 there): the ReLU masks of the fp32 and the float64 run are identical, and the smallest |BatchNorm output| in front of the
 ReLU in the float64 run is at least 64 x the fp32 run's error in that tensor -- otherwise a case pins a ReLU tie.
---search prints, per case, the first seed of 101, 202, 303, ... that is admitted, and writes nothing."""
+--search prints, per case of CASES and WIDE, the first seed of 101, 202, 303, ... that is admitted, and writes nothing."""
 import argparse
 import os
 import sys
@@ -23,7 +25,7 @@ from torch import nn
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
-from _stem_cases import (CASES, EPS, TINY, case_inputs, modes, stored_indices, tensor_shapes, tiny_inputs,  # noqa: E402
+from _stem_cases import (CASES, EPS, FIXTURE, FIXTURE_WIDE, TINY, WIDE, case_inputs, modes, stored_indices, tensor_shapes, tiny_inputs,  # noqa: E402
                          tiny_tensor_shapes, units)
 from oracle.backbones import BatchNormAct2d, ConvBnAct, FeatureBackbone  # noqa: E402
 
@@ -139,14 +141,15 @@ def admitted(runner):
     return r32, r64, bn64, why
 
 
-def runners():
+def runners(which=("cases", "wide")):
     """(case name, modes, seed -> {mode: runner(dtype)}, shapes, the case's own seed)"""
-    for case in CASES:
+    for case in (CASES if "cases" in which else []) + (WIDE if "wide" in which else []):
         def make(seed, case=case):
             inputs = case_inputs(case, seed)
             return {mode: (lambda dt, mode=mode: run_oracle(case, inputs, mode == "train", dt)) for mode in modes(case)}
         yield case["name"], make, tensor_shapes(case), case["seed"]
-    yield TINY["name"], (lambda seed: {"train": lambda dt: run_tiny(tiny_inputs(seed), dt)}), tiny_tensor_shapes(), TINY["seed"]
+    if "cases" in which:
+        yield TINY["name"], (lambda seed: {"train": lambda dt: run_tiny(tiny_inputs(seed), dt)}), tiny_tensor_shapes(), TINY["seed"]
 
 
 def search():
@@ -161,10 +164,12 @@ def search():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--search", action="store_true")
-    if ap.parse_args().search:
+    ap.add_argument("--wide", action="store_true", help="write stem_train_wide.npz (the WIDE cases) instead")
+    a = ap.parse_args()
+    if a.search:
         return search()
     arrays = {}
-    for name, make, shapes, seed in runners():
+    for name, make, shapes, seed in runners(("wide",) if a.wide else ("cases",)):
         for mode, runner in make(seed).items():
             r32, r64, bn64, why = admitted(runner)
             assert why is None, (name, mode, why)          # admission rule: change the seed in _stem_cases.py
@@ -184,7 +189,7 @@ def main():
             arrays[key + "/max64"] = np.asarray(m64s, np.float64)
             worst = max(e / max(m, 1e-300) for e, m in zip(e32s, m64s))
             print(f"{name:14s} {mode:5s} min|bn|={min(np.abs(b).min() for b in bn64):.1e}  worst e32/max64={worst:.1e}")
-    path = os.path.join(OUT, "stem_train.npz")
+    path = os.path.join(OUT, os.path.basename(FIXTURE_WIDE if a.wide else FIXTURE))
     np.savez_compressed(path, **arrays)
     print(path, os.path.getsize(path), "bytes")
     assert os.path.getsize(path) < (1 << 20)

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 from yololite_amd import neckops
-from _dense_neck_amp_cases import (OP_BY_NAME, OP_CASES, PASSES, conv_pass, op_reference, reference, rounded, tie_operands)
+from _dense_neck_amp_cases import (OP_BY_NAME, OP_CASES, OP_WIDE, PASSES, conv_pass, op_reference, reference, rounded, tie_operands)
 from _train_dev import DEV
 
 pytestmark = pytest.mark.gpu
@@ -39,7 +39,7 @@ def _record(section, key, value):
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
-@pytest.mark.parametrize("case", OP_CASES, ids=[c["name"] for c in OP_CASES])
+@pytest.mark.parametrize("case", OP_CASES + OP_WIDE, ids=[c["name"] for c in OP_CASES + OP_WIDE])
 def test_op_parity_with_the_rounded_operand_reference(case, precision):
     bad, worst = [], {}
     for pass_ in PASSES:

@@ -12,7 +12,7 @@ import torch
 
 import yololite_amd as ya
 from yololite_amd import neckops
-from _dense_neck_cases import CASES, E2E, FIXTURE, KEYS, case_inputs, fixture_tensors, level_names, modes
+from _dense_neck_cases import CASES, E2E, FIXTURE, FIXTURE_WIDE, KEYS, WIDE, case_inputs, fixture_tensors, level_names, modes
 from _dense_neck_np import neck_all
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,12 +23,17 @@ def fixture():
     return np.load(FIXTURE)
 
 
+@pytest.fixture(scope="module")
+def wide():
+    return np.load(FIXTURE_WIDE)
+
+
 def test_the_fixture_is_a_committable_file():
-    assert os.path.getsize(FIXTURE) < (1 << 20)
+    assert os.path.getsize(FIXTURE) < (1 << 20) and os.path.getsize(FIXTURE_WIDE) < (1 << 20)
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
-def test_float64_restatement_reproduces_the_reference(case, fixture):
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
+def test_float64_restatement_reproduces_the_reference(case, fixture, wide):
     """tests/_dense_neck_np.py in float64 against the reference's own float64 run: every tensor to 1e-12 of its largest
     value.  One tensor's true value is zero (case tiny, g.lateral5.bias: at S = 1 the bias is a constant per channel in
     front of a train-mode BatchNorm; the fixture holds 5e-15): two float64 evaluations of a sum of O(10) terms that
@@ -37,7 +42,7 @@ def test_float64_restatement_reproduces_the_reference(case, fixture):
     for mode in modes(case):
         got = neck_all(inputs, case["depth"], mode == "train")
         for li in range(len(inputs)):
-            want = fixture_tensors(fixture, case, mode, li)
+            want = fixture_tensors(wide if case in WIDE else fixture, case, mode, li)
             assert set(got[li]) == set(want)
             for n, (r64, idx, _, m64) in want.items():
                 g = np.asarray(got[li][n], np.float64).reshape(-1)

@@ -15,7 +15,7 @@ import torch
 import yololite_amd as ya
 from yololite_amd.program import synth_state_dict, zoo_meta
 from _head_np import head_forward
-from _dense_neck_cases import CASES, E2E, FIXTURE, bar, case_inputs, fixture_tensors, head_inputs, modes
+from _dense_neck_cases import CASES, E2E, FIXTURE, WIDE, bar, case_inputs, fixture_path, fixture_tensors, head_inputs, modes
 from _dense_neck_dev import neck_of as _neck, parity_ratios, run as _run
 from _dense_neck_np import neck_all, neck_forward
 from _train_dev import DEV, same as _same, targets as _targets
@@ -24,12 +24,12 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARITY = os.path.join(ROOT, "profiles", "dense_neck_train_parity.json")
-BY_NAME = {c["name"]: c for c in CASES}
+BY_NAME = {c["name"]: c for c in CASES + WIDE}
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
 def test_fixture_parity(case):
-    z = np.load(FIXTURE)
+    z = np.load(fixture_path(case))
     bad, worst = [], {}
     for mode in modes(case):
         for (li, n), (err, b) in parity_ratios(case, mode, z).items():
@@ -49,12 +49,12 @@ def test_fixture_parity(case):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("name", [c["name"] for c in CASES])
+@pytest.mark.parametrize("name", [c["name"] for c in CASES + WIDE])
 def test_sampled_tensors_agree_with_the_restatement_everywhere(name):
     """the fixture stores tensors above 8192 elements at a sample; here every element of those is held to the float64
     restatement (which test_dense_neck_train_cpu.py ties to the fixture), under the fixture's bar"""
     case = BY_NAME[name]
-    z = np.load(FIXTURE)
+    z = np.load(fixture_path(case))
     sampled = [(li, n) for li in range(len(case["sizes"])) for n, v in fixture_tensors(z, case, "train", li).items()
                if v[1] is not None]
     if not sampled:

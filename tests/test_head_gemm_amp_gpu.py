@@ -18,7 +18,7 @@ import yololite_amd as ya
 from yololite_amd import _lib, headops
 from _head_amp_cases import (BY_NAME, PASSES, PRECISIONS, SITES, cat_rows, gemm_pass, level_weights, op_reference, reference,
                              rounded, split_rows, tie_operands)
-from _head_cases import CASES, case_inputs
+from _head_cases import CASES, WIDE, case_inputs
 from _head_dev import heads_of
 from _train_dev import DEV
 
@@ -64,7 +64,7 @@ def _cells(case):
 
 
 @pytest.mark.parametrize("precision", PRECISIONS)
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
 def test_op_parity_with_the_rounded_operand_reference(case, precision):
     heads = _heads(case["name"])
     bad, worst = [], (0.0, "")

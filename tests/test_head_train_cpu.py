@@ -9,7 +9,7 @@ import torch
 
 import yololite_amd as ya
 from yololite_amd import headops
-from _head_cases import CASES, E2E, FIXTURE, case_inputs, fixture_tensors, level_names, modes
+from _head_cases import CASES, E2E, FIXTURE, FIXTURE_WIDE, WIDE, case_inputs, fixture_tensors, level_names, modes
 from _head_np import head_all
 
 
@@ -18,14 +18,19 @@ def fixture():
     return np.load(FIXTURE)
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
-def test_float64_restatement_reproduces_the_reference(case, fixture):
+@pytest.fixture(scope="module")
+def wide():
+    return np.load(FIXTURE_WIDE)
+
+
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
+def test_float64_restatement_reproduces_the_reference(case, fixture, wide):
     """tests/_head_np.py in float64 against the reference's own float64 run: every tensor to 1e-12 of its largest value"""
     for mode in modes(case):
         for li, lv in enumerate(case_inputs(case)):
             got = head_all(lv["params"], lv["buffers"], lv["x"], lv["gy"], lv["k"], case["A"], case["C"], case["depth"],
                            mode == "train")
-            want = fixture_tensors(fixture, case, mode, li)
+            want = fixture_tensors(wide if case in WIDE else fixture, case, mode, li)
             assert set(got) == set(want)
             for n, (r64, idx, _, m64) in want.items():
                 g = np.asarray(got[n], np.float64).reshape(-1)

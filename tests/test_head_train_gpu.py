@@ -5,38 +5,63 @@ Fixture parity, per case, level and tensor (figures of one run on an MI355X, dev
 each case): see profiles/head_train_parity.json.  The bar is max(4 x the reference's own fp32 error, 2 fp32 ulps at
 the tensor's largest magnitude), the rule of the loss and train-step tests."""
 import copy
+import json
+import os
 
 import numpy as np
 import pytest
 import torch
 
 import yololite_amd as ya
-from _head_cases import CASES, E2E, FIXTURE, bar, case_inputs, fixture_tensors, modes
+from _head_cases import CASES, E2E, FIXTURE, WIDE, bar, case_inputs, fixture_path, fixture_tensors, modes
 from _head_dev import heads_of as _heads, parity_ratios, run as _run
 from _head_np import head_forward
 from _train_dev import DEV, edge_n as _edge_n, same as _same, targets as _targets
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PARITY = os.path.join(ROOT, "profiles", "head_train_parity.json")
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
 def test_fixture_parity(case):
-    z = np.load(FIXTURE)
-    bad = []
+    z = np.load(fixture_path(case))
+    bad, rows = [], []
     for mode in modes(case):
         for (li, n), (err, b) in parity_ratios(case, mode, z).items():
             print(f"{case['name']:5s} {mode:5s} L{li} {n:40s} err {err:.3e}  bar {b:.3e}  ratio {err / b:.3f}")
+            rows.append(dict(case=case["name"], mode=mode, level=li, tensor=n, error=err, bar=b, ratio=round(err / b, 4)))
             if not err <= b:
                 bad.append((mode, li, n, err, b))
+    if case in WIDE:                                       # the figures of this run, beside the others' rows (best effort)
+        try:
+            table = [r for r in json.load(open(PARITY)) if r["case"] != case["name"]] if os.path.exists(PARITY) else []
+            with open(PARITY, "w") as f:
+                json.dump(table + rows, f, indent=1)
+                f.write("\n")
+        except OSError:
+            pass
     assert not bad, bad
 
 
 def test_large_tensors_agree_with_the_restatement_everywhere():
     """the fixture stores the 1x1 weight gradients of the F = 244 case at a sample of their elements; here every element
     is held to the float64 restatement (which test_head_train_cpu.py ties to the fixture), under the fixture's bar"""
+    _everywhere("f244")
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in WIDE])
+def test_large_tensors_of_the_wide_cases_agree_with_the_restatement_everywhere(name):
+    """and so do the wide cases': every tensor their fixture stores sampled (the 1x1 weight gradients)"""
+    _everywhere(name)
+
+
+def _everywhere(name):
     from _head_np import head_all
-    case = [c for c in CASES if c["name"] == "f244"][0]
-    z = np.load(FIXTURE)
+    case = [c for c in CASES + WIDE if c["name"] == name][0]
+    z = np.load(fixture_path(case))
+    assert any(v[1] is not None for li in range(len(case["sizes"])) for v in fixture_tensors(z, case, "train", li).values())
     inputs = case_inputs(case)
     got = _run(_heads(case, inputs), inputs)
     for li, (lv, d) in enumerate(zip(inputs, got)):

@@ -13,7 +13,7 @@ import torch.nn.functional as TF
 
 import yololite_amd as ya
 from yololite_amd import neckops
-from _neck_cases import CASES, E2E, FIXTURE, KEYS, case_inputs, fixture_tensors, level_names, modes
+from _neck_cases import CASES, E2E, FIXTURE, FIXTURE_WIDE, KEYS, WIDE, case_inputs, fixture_tensors, level_names, modes
 from _neck_np import nearest_src, neck_all
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,14 +24,19 @@ def fixture():
     return np.load(FIXTURE)
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
-def test_float64_restatement_reproduces_the_reference(case, fixture):
+@pytest.fixture(scope="module")
+def wide():
+    return np.load(FIXTURE_WIDE)
+
+
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
+def test_float64_restatement_reproduces_the_reference(case, fixture, wide):
     """tests/_neck_np.py in float64 against the reference's own float64 run: every tensor to 1e-12 of its largest value"""
     inputs = case_inputs(case)
     for mode in modes(case):
         got = neck_all(inputs, case["depth"], mode == "train")
         for li in range(len(inputs)):
-            want = fixture_tensors(fixture, case, mode, li)
+            want = fixture_tensors(wide if case in WIDE else fixture, case, mode, li)
             assert set(got[li]) == set(want)
             for n, (r64, idx, _, m64) in want.items():
                 g = np.asarray(got[li][n], np.float64).reshape(-1)

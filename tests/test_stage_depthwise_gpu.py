@@ -2,7 +2,9 @@
 csrc/yl_stage.hip) against torch's CPU convolution in float64.
 
 Every cell of k in {3, 5} x stride in {1, 2} x {forward, dgrad, wgrad} x S in {1, 2, 5, 8, 9} x C in {4, 20} x B in {1, 3},
-plus B 3 / S 10 (300 rows under stride 1: two tiles of the weight gradient's partials), is held to
+plus B 3 / S 10 (300 rows under stride 1: two tiles of the weight gradient's partials) and the shapes of
+_stage_cases.DW_OP_WIDE (C 260 and 512: a second channel group of the weight gradient, one quad of it and all of it
+switched on; B 2 / S 32 and B 3 / S 20: several row tiles under either stride, the last full and ragged), is held to
 max(4 x e32, 2 fp32 ulps of the tensor's largest magnitude), e32 the error of torch's own fp32 CPU convolution on the
 same fp32-valued inputs."""
 import functools
@@ -14,12 +16,13 @@ import torch.nn.functional as TF
 
 from yololite_amd import stageops
 from _head_cases import bar
+from _stage_cases import DW_OP_KS, DW_OP_SHAPES, DW_OP_WIDE
 from _train_dev import DEV
 
 pytestmark = pytest.mark.gpu
 
-KS = [(k, s) for k in (3, 5) for s in (1, 2)]
-SHAPES = [(B, S, C) for S in (1, 2, 5, 8, 9) for C in (4, 20) for B in (1, 3)] + [(3, 10, 4), (3, 10, 20)]
+KS = DW_OP_KS
+SHAPES = DW_OP_SHAPES + DW_OP_WIDE                         # data of _stage_cases.py: the launch census reads them too
 PASSES = ("forward", "dgrad", "wgrad")
 
 
@@ -61,7 +64,7 @@ def test_every_cell_against_the_float64_convolution(k, s, pass_):
         assert got.shape == r64[pass_].shape
         err = np.abs(got.astype(np.float64) - r64[pass_]).max()
         b = bar(np.abs(r32[pass_].astype(np.float64) - r64[pass_]).max(), np.abs(r64[pass_]).max())
-        print(f"k{k} s{s} {pass_:7s} B{B} S{S:2d} C{C:2d}  err {err:.3e}  bar {b:.3e}")
+        print(f"k{k} s{s} {pass_:7s} B{B} S{S:2d} C{C:3d}  err {err:.3e}  bar {b:.3e}")
         if not err <= b:
             bad.append((B, S, C, err, b))
     assert not bad, bad

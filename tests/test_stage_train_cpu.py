@@ -12,11 +12,13 @@ import torch
 import yololite_amd as ya
 from yololite_amd import stageops
 from yololite_amd.program import zoo_meta, make_meta
-from _stage_cases import (CASES, FIXTURE, bar, case_inputs, dw_dgrad, dw_forward, dw_wgrad, fixture_tensors, modes,
+from _stage_cases import (CASES, FIXTURE, FIXTURE_WIDE, WIDE, bar, case_inputs, dw_dgrad, dw_forward, dw_wgrad, fixture_tensors, modes,
                           plan_restated, stack_all, units)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = [c["name"] for c in CASES]
+ALL = CASES + WIDE
+ALL_IDS = [c["name"] for c in ALL]
 
 
 @pytest.fixture(scope="module")
@@ -24,14 +26,19 @@ def fixture():
     return np.load(FIXTURE)
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_float64_restatement_reproduces_the_fixture(case, fixture):
+@pytest.fixture(scope="module")
+def wide():
+    return np.load(FIXTURE_WIDE)
+
+
+@pytest.mark.parametrize("case", ALL, ids=ALL_IDS)
+def test_float64_restatement_reproduces_the_fixture(case, fixture, wide):
     """tests/_stage_cases.py stack_all in float64 against the oracle's float64 run: every tensor to 1e-12 of its
     largest value"""
     inputs = case_inputs(case)
     for mode in modes(case):
         got = stack_all(case, inputs, mode == "train")
-        want = fixture_tensors(fixture, case, mode)
+        want = fixture_tensors(wide if case in WIDE else fixture, case, mode)
         assert set(got) == set(want)
         for n, (r64, idx, _, m64) in want.items():
             g = np.asarray(got[n], np.float64).reshape(-1)
@@ -39,13 +46,13 @@ def test_float64_restatement_reproduces_the_fixture(case, fixture):
             assert np.abs(g - r64).max() <= 1e-12 * max(m64, 1.0), (case["name"], mode, n)
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_a_plain_fp32_run_of_the_restatement_passes_every_bar(case, fixture):
+@pytest.mark.parametrize("case", ALL, ids=ALL_IDS)
+def test_a_plain_fp32_run_of_the_restatement_passes_every_bar(case, fixture, wide):
     """the bars are not out of an fp32 implementation's reach: numpy's own fp32 arithmetic stays inside them"""
     inputs = case_inputs(case)
     for mode in modes(case):
         got = stack_all(case, inputs, mode == "train", np.float32)
-        for n, (r64, idx, e32, m64) in fixture_tensors(fixture, case, mode).items():
+        for n, (r64, idx, e32, m64) in fixture_tensors(wide if case in WIDE else fixture, case, mode).items():
             g = np.asarray(got[n]).reshape(-1)
             if "num_batches_tracked" in n:
                 assert int(g[0]) == int(r64[0])
@@ -71,7 +78,7 @@ def test_the_restated_depthwise_passes_are_torchs(k, s, S):
     assert np.abs(dw_wgrad(x, dy, k, s) - wt.grad.numpy()).max() <= 1e-12
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", ALL, ids=ALL_IDS)
 def test_plan_counts_the_bytes_the_header_gives(case):
     for B, S in ((case["B"], case["S"]), (64, 40), (1, 7)):
         p = stageops.plan(case["cin"], case["blocks"], B, S)

@@ -14,7 +14,7 @@ import torch
 
 import yololite_amd as ya
 from _neck_cases import E2E
-from _stage_cases import CASES, FIXTURE, bar, case_inputs, modes, stack_all
+from _stage_cases import CASES, WIDE, bar, case_inputs, fixture_path, fixture_tensors, modes, stack_all
 from _stage_dev import parity_ratios, run as _run, stack_of as _stack
 from _train_dev import DEV, edge_n as _edge_n, same as _same, targets as _targets
 
@@ -22,12 +22,12 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARITY = os.path.join(ROOT, "profiles", "stage_train_parity.json")
-BY_NAME = {c["name"]: c for c in CASES}
+BY_NAME = {c["name"]: c for c in CASES + WIDE}
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
 def test_fixture_parity(case):
-    z = np.load(FIXTURE)
+    z = np.load(fixture_path(case))
     bad, worst = [], {}
     for mode in modes(case):
         for n, (err, b) in parity_ratios(case, mode, z).items():
@@ -45,6 +45,24 @@ def test_fixture_parity(case):
     except OSError:
         pass
     assert not bad, bad
+
+
+@pytest.mark.parametrize("name", [c["name"] for c in WIDE])
+def test_sampled_tensors_agree_with_the_restatement_everywhere(name):
+    """the fixture stores tensors above 8192 elements at a sample (only the wide cases have any); here every element of
+    those is held to the float64 restatement (which test_stage_train_cpu.py ties to the fixture), under the fixture's bar"""
+    case = BY_NAME[name]
+    want = fixture_tensors(np.load(fixture_path(case)), case, "train")
+    sampled = [n for n, v in want.items() if v[1] is not None]
+    if not sampled:
+        return                                             # nothing of this case is stored sampled
+    inputs = case_inputs(case)
+    got = _run(_stack(case, inputs), inputs)
+    ref = stack_all(case, inputs, True)
+    for n in sampled:
+        _, _, e32, m64 = want[n]
+        err = np.abs(got[n].numpy().astype(np.float64) - ref[n]).max()
+        assert err <= bar(e32, m64), (n, err, bar(e32, m64))
 
 
 def test_two_runs_give_the_same_bits_in_both_input_layouts():

@@ -14,16 +14,23 @@ import torch
 import yololite_amd as ya
 from yololite_amd import stageops, stemops
 from yololite_amd.program import zoo_meta, make_meta
-from _stem_cases import (CASES, FIXTURE, TINY, bar, case_inputs, conv_dgrad, conv_forward, conv_wgrad, fixture_tensors, modes,
+from _stem_cases import (CASES, FIXTURE, FIXTURE_WIDE, TINY, WIDE, bar, case_inputs, conv_dgrad, conv_forward, conv_wgrad, fixture_tensors, modes,
                          plan_restated, stack_all, tiny_all, tiny_inputs, tiny_tensor_shapes, units)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDS = [c["name"] for c in CASES]
+ALL = CASES + WIDE
+ALL_IDS = [c["name"] for c in ALL]
 
 
 @pytest.fixture(scope="module")
 def fixture():
     return np.load(FIXTURE)
+
+
+@pytest.fixture(scope="module")
+def wide():
+    return np.load(FIXTURE_WIDE)
 
 
 def _held(got, want, tol):
@@ -38,12 +45,13 @@ def _held(got, want, tol):
         assert err <= tol(e32, m64), (n, err, tol(e32, m64))
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
-def test_float64_restatement_reproduces_the_fixture(case, fixture):
+@pytest.mark.parametrize("case", ALL, ids=ALL_IDS)
+def test_float64_restatement_reproduces_the_fixture(case, fixture, wide):
     """tests/_stem_cases.py stack_all in float64 against the oracle's float64 run: every tensor to 1e-12 of its largest value"""
     inputs = case_inputs(case)
     for mode in modes(case):
-        _held(stack_all(case, inputs, mode == "train"), fixture_tensors(fixture, case, mode), lambda e, m: 1e-12 * max(m, 1.0))
+        _held(stack_all(case, inputs, mode == "train"), fixture_tensors(wide if case in WIDE else fixture, case, mode),
+              lambda e, m: 1e-12 * max(m, 1.0))
 
 
 def test_the_whole_backbone_restated_reproduces_the_fixture(fixture):
@@ -68,11 +76,11 @@ def test_the_restated_convolution_passes_are_torchs(k, s, S):
     assert np.abs(conv_wgrad(x, dy, k, s) - wt.grad.numpy()).max() <= 1e-12
 
 
-def test_the_recipe_regenerates_the_committed_fixture(tmp_path):
+def _regenerates(tmp_path, committed, flags):
     env = dict(os.environ, YL_FIXTURE_OUT=str(tmp_path))
-    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "make_stem_fixtures.py")], check=True, env=env,
+    subprocess.run([sys.executable, os.path.join(ROOT, "tests", "golden", "make_stem_fixtures.py")] + flags, check=True, env=env,
                    stdout=subprocess.DEVNULL)
-    new, old = np.load(tmp_path / "stem_train.npz"), np.load(FIXTURE)
+    new, old = np.load(tmp_path / os.path.basename(committed)), np.load(committed)
     assert sorted(new.files) == sorted(old.files)
     for n in old.files:
         a, b = new[n], old[n]
@@ -82,14 +90,22 @@ def test_the_recipe_regenerates_the_committed_fixture(tmp_path):
             assert np.all(a[big] <= 4 * b[big] + 1e-30) and np.all(b[big] <= 4 * a[big] + 1e-30), n
         else:
             assert np.abs(a - b).max() <= 1e-9 * max(np.abs(b).max(), 1.0), n
-    assert os.path.getsize(FIXTURE) < 600 * 1024
+    assert os.path.getsize(committed) < 600 * 1024
+
+
+def test_the_recipe_regenerates_the_committed_fixture(tmp_path):
+    _regenerates(tmp_path, FIXTURE, [])
+
+
+def test_the_recipe_regenerates_the_committed_wide_fixture(tmp_path):
+    _regenerates(tmp_path, FIXTURE_WIDE, ["--wide"])
 
 
 def _layout(case):
     return "nchw" if case["planar"] else "nhwc"
 
 
-@pytest.mark.parametrize("case", CASES, ids=IDS)
+@pytest.mark.parametrize("case", ALL, ids=ALL_IDS)
 def test_plan_counts_what_the_header_gives(case):
     for B, S in ((case["B"], case["S"]), (64, 40), (1, 7)):
         p = stemops.plan(case["cin"], case["units"], B, S, input_layout=_layout(case))

@@ -16,8 +16,8 @@ import torch
 
 import yololite_amd as ya
 from _neck_cases import E2E
-from _stem_cases import (CASES, FIXTURE, TINY, backward_launches, case_inputs, fixture_tensors, forward_launches, modes, tiny_inputs,
-                         tiny_tensor_shapes)
+from _stem_cases import (CASES, FIXTURE, TINY, WIDE, backward_launches, bar, case_inputs, fixture_path, fixture_tensors, forward_launches,
+                         modes, stack_all, tiny_inputs, tiny_tensor_shapes)
 from _stem_dev import parity_ratios, ratios, restated_features, run as _run, run_tiny, stack_of as _stack, tiny_backbone
 from _train_dev import DEV, edge_n as _edge_n, same as _same, targets as _targets
 
@@ -48,10 +48,26 @@ def _judge(name, per_mode):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+@pytest.mark.parametrize("case", CASES + WIDE, ids=[c["name"] for c in CASES + WIDE])
 def test_fixture_parity(case):
-    z = np.load(FIXTURE)
+    z = np.load(fixture_path(case))
     _judge(case["name"], {mode: parity_ratios(case, mode, z) for mode in modes(case)})
+
+
+@pytest.mark.parametrize("case", WIDE, ids=[c["name"] for c in WIDE])
+def test_sampled_tensors_agree_with_the_restatement_everywhere(case):
+    """the fixture stores tensors above 8192 elements at a sample (only the wide cases have any); here every element of
+    those is held to the float64 restatement (which test_stem_train_cpu.py ties to the fixture), under the fixture's bar"""
+    want = fixture_tensors(np.load(fixture_path(case)), case, "train")
+    sampled = [n for n, v in want.items() if v[1] is not None]
+    assert sampled
+    inputs = case_inputs(case)
+    got = _run(_stack(case, inputs), case, inputs)
+    ref = stack_all(case, inputs, True)
+    for n in sampled:
+        _, _, e32, m64 = want[n]
+        err = np.abs(got[n].numpy().astype(np.float64) - np.asarray(ref[n])).max()
+        assert err <= bar(e32, m64), (n, err, bar(e32, m64))
 
 
 def test_the_whole_tiny_backbone_against_the_fixture():
