@@ -1176,6 +1176,26 @@ yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, i
                        int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, void* stream,
                        int32_t* launches);
 
+/* ---- Mixed precision of the trainable backbone (stage and stem): the operand type of every DENSE GEMM, i.e. the stem's
+ * 3x3 convolution and every 1x1 of stage and stem, in all three passes.  `mode` is 0 (fp32), YL_HEAD_F16 or YL_HEAD_BF16;
+ * anything else, both bits among it, is YL_ERR_INVALID and changes nothing.  In a 16-bit mode both operands of each such
+ * GEMM are rounded to nearest even inside the launch that consumes them (the 3x3 weight in its pack launch), products are
+ * exact and accumulation is fp32 (v_mfma_f32_16x16x16_f16 / _bf16_1k); nothing is clamped, so an fp16 overflow is inf.
+ * Parameters, saved activations, partial sums and every returned gradient stay fp32; the depthwise convolutions,
+ * BatchNorm, ReLU, the residual add and every float64 sum are the same in all three modes, and so are the launch counts.
+ * The setter changes the mode of the NEXT forward: a held forward keeps its own, and its backward runs in it.  _get reports
+ * the handle's mode and the held forward's (0 when none is held); either pointer may be NULL.  The forward's `flags` go on
+ * refusing the precision bits. */
+yl_status yl_amp_stage_set(yl_stage* h, uint32_t mode);
+yl_status yl_amp_stem_set(yl_stem* h, uint32_t mode);
+yl_status yl_amp_stage_get(const yl_stage* h, uint32_t* mode, uint32_t* held_mode);
+yl_status yl_amp_stem_get(const yl_stem* h, uint32_t* mode, uint32_t* held_mode);
+/* yl_stem_conv in the operand type `mode` (yl_stem_conv itself is mode 0): same arguments, launches and alignment rules;
+ * the packed weight of a 16-bit 3x3 pass takes half the temporary buffer. */
+yl_status yl_amp_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,
+                           int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, uint32_t mode,
+                           void* stream, int32_t* launches);
+
 #ifdef __cplusplus
 }
 #endif

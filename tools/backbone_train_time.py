@@ -15,7 +15,14 @@ launches per step of the device side and what yl_stem_plan / yl_stage_plan say t
 With --trace only --steps steps per side are run once (for `rocprofv3 --kernel-trace --stats -- python
 tools/backbone_train_time.py --trace ...`).
 
-    python tools/backbone_train_time.py [--models edge_n,edge_m] [--blocks 7] [--steps 20] [--out F] [--trace]"""
+--precision fp16 | bf16: the device side is MobileNetV4Backbone(precision=...), i.e. every dense GEMM (the stem's 3x3, every
+1x1) on 16-bit MFMA with depthwise convolutions and BatchNorm in fp32; the torch side is the same module under
+torch.autocast of that dtype (its parameters stay fp32), which also runs the depthwise convolutions in 16 bits.  The line
+names the mode on both sides.
+
+    python tools/backbone_train_time.py [--models edge_n,edge_m] [--blocks 7] [--steps 20] [--out F] [--trace]
+                                        [--precision fp32|fp16|bf16]"""
+import contextlib
 import os
 import sys
 
@@ -26,6 +33,25 @@ if ROOT not in sys.path:
 from tools import _train_time as tt  # noqa: E402
 
 SHAPES = {"edge_n": dict(B=64, S=640), "edge_m": dict(B=32, S=640)}
+PRECISIONS = ("fp32", "fp16", "bf16")
+PRECISION = "fp32"
+
+
+def take_precision(argv):
+    """--precision P (or --precision=P) out of argv -> P; the rest of the command line is tools/_train_time.py's"""
+    p = "fp32"
+    for i, v in enumerate(argv):
+        if v == "--precision" and i + 1 < len(argv):
+            p = argv[i + 1]
+            del argv[i:i + 2]
+            break
+        if v.startswith("--precision="):
+            p = v.split("=", 1)[1]
+            del argv[i]
+            break
+    if p not in PRECISIONS:
+        raise SystemExit(f"--precision must be one of {PRECISIONS}, got {p!r}")
+    return p
 
 
 def torch_backbone(backbone, upto=None):
@@ -63,7 +89,9 @@ def run_model(name, blocks, steps, trace):
     dev = "cuda:0"
     torch.manual_seed(3)
     meta = zoo_meta(name, num_classes=3, img_size=S)
-    ours = ya.MobileNetV4Backbone.from_meta(meta).to(dev).train()
+    ours = ya.MobileNetV4Backbone.from_meta(meta, precision=PRECISION).to(dev).train()
+    cast = {"fp16": torch.float16, "bf16": torch.bfloat16}.get(PRECISION)
+    autocast = (lambda: torch.autocast("cuda", dtype=cast)) if cast else contextlib.nullcontext
     sd = {k[len("backbone."):]: v for k, v in ours.state_dict().items()}
     gen = torch.Generator().manual_seed(5)
     x = torch.randn(B, 3, S, S, generator=gen).to(dev)
@@ -76,7 +104,7 @@ def run_model(name, blocks, steps, trace):
     splan = stemops.plan(3, stem.units_cfg, B, S, stem.eps, input_layout="nchw")
     mplan = stageops.plan(ours.mid.in_channels, ours.mid.blocks_cfg, B, shapes[0][1], ours.mid.eps)
     tplan = stageops.plan(ours.tail.in_channels, ours.tail.blocks_cfg, B, shapes[1][1], ours.tail.eps)
-    res = {"model": name, "backbone": meta["backbone"], "batch": B, "image": [B, 3, S, S], "c3": list(shapes[0]),
+    res = {"model": name, "device_precision": PRECISION, "torch_autocast": PRECISION if cast else "off", "backbone": meta["backbone"], "batch": B, "image": [B, 3, S, S], "c3": list(shapes[0]),
            "c4": list(shapes[1]), "c5": list(shapes[2]), "steps_per_block": steps,
            "stem_saved_bytes": splan["saved_bytes"], "stem_workspace_bytes": splan["workspace_bytes"],
            "stem_stat_rows": [u["stat_rows"] for u in splan["units"]], "stem_stat_tiles": [u["stat_tiles"] for u in splan["units"]],
@@ -100,10 +128,12 @@ def run_model(name, blocks, steps, trace):
 
         def ref_step():
             grads_off(ref)
-            if what == "stem":
-                ref(x_cl)[0].backward(gs_cl[0])
+            with autocast():
+                feats = ref(x_cl)
+            if what == "stem":                             # the maps come out in the autocast dtype: the gradients follow
+                feats[0].backward(gs_cl[0].to(feats[0].dtype))
             else:
-                torch.autograd.backward(ref(x_cl), gs_cl)
+                torch.autograd.backward(feats, [g.to(f.dtype) for g, f in zip(gs_cl, feats)])
 
         parts = (stem,) if what == "stem" else (stem, ours.mid, ours.tail)
         launches = lambda: sum(sum(p.last_launches.values()) for p in parts)   # noqa: E731
@@ -116,4 +146,5 @@ def run_model(name, blocks, steps, trace):
 
 
 if __name__ == "__main__":
-    tt.main("backbone_train_time.py", "edge_n,edge_m", run_model)
+    PRECISION = take_precision(sys.argv)
+    tt.main("backbone_train_time.py", "edge_n,edge_m", run_model, header={"precision": PRECISION})

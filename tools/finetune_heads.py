@@ -8,6 +8,7 @@
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
                                    [--train-neck [--amp fp16|bf16] [--train-tail [--lr-tail 1e-4]]] [--amp-heads fp16|bf16]
                                    [--train-neck --train-backbone [--lr-backbone 1e-4]]
+                                   [--amp-backbone fp16|bf16]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
@@ -45,7 +46,10 @@ stageops.MobileNetV4Backbone holds the stem (stemops.BackboneStem, csrc/yl_stem.
 with the rate --lr-backbone (default: --lr), and its state_dict is merged into the output.  The backbone is fp32.
 
 --amp-heads fp16 | bf16 (with or without --train-neck): DetectHeads runs every 1x1 GEMM of the heads in that precision, on
-the same terms.  The loss scale is on when either of --amp and --amp-heads is fp16.
+the same terms.  --amp-backbone fp16 | bf16 (needs --train-backbone or --train-tail) does the same for the trainable
+backbone: every dense GEMM of MobileNetV4Backbone (the stem's 3x3 and every 1x1 convolution) or of BackboneTail, on the
+same terms; its depthwise convolutions and BatchNorm stay fp32.  The loss scale is on when any of --amp, --amp-heads and
+--amp-backbone is fp16.
 """
 import argparse
 import copy
@@ -141,10 +145,14 @@ def main():
                     help="with --train-neck, YOLOLiteMS models: the dense neck's 3x3 GEMMs in this precision")
     ap.add_argument("--amp-heads", default="", choices=("", "fp16", "bf16"),
                     help="the heads' 1x1 GEMMs in this precision (independent of --train-neck)")
+    ap.add_argument("--amp-backbone", default="", choices=("", "fp16", "bf16"),
+                    help="with --train-backbone or --train-tail: the backbone's dense GEMMs (3x3 stem, every 1x1) in this precision")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     if bool(a.synthetic) == bool(a.weights):
         raise SystemExit("give either --weights (with --data) or --synthetic NAME")
+    if a.amp_backbone and not (a.train_backbone or a.train_tail):
+        raise SystemExit("--amp-backbone sets the precision of the trainable backbone: it needs --train-backbone or --train-tail")
     if a.amp and not a.train_neck:
         raise SystemExit("--amp sets the precision of the trainable dense neck: it needs --train-neck")
     if a.train_tail and not a.train_neck:
@@ -175,9 +183,10 @@ def main():
     # DetectNeck (arch YOLOLiteMS_CPU) refuses a reduced precision and says why
     neck = ya.neck_for(meta, sd, precision=a.amp or "fp32").to(a.device).train() if a.train_neck else None
     # BackboneTail refuses, by name, a backbone whose last stage is not made of UIB / 1x1 ConvBnAct blocks
-    tail = ya.BackboneTail.from_state_dict(meta, sd).to(a.device).train() if a.train_tail and not a.train_backbone else None
+    bprec = a.amp_backbone or "fp32"
+    tail = ya.BackboneTail.from_state_dict(meta, sd, precision=bprec).to(a.device).train() if a.train_tail and not a.train_backbone else None
     # MobileNetV4Backbone (stem, C3 -> C4 stage and the tail in one) refuses the other backbone families by name as well
-    backbone = ya.MobileNetV4Backbone.from_state_dict(meta, sd).to(a.device).train() if a.train_backbone else None
+    backbone = ya.MobileNetV4Backbone.from_state_dict(meta, sd, precision=bprec).to(a.device).train() if a.train_backbone else None
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
     if tail is not None:                                   # a group of its own: its rate is --lr-tail
@@ -185,7 +194,7 @@ def main():
     if backbone is not None:                               # likewise: --lr-backbone
         params = [{"params": params}, {"params": list(backbone.parameters()), "lr": a.lr_backbone or a.lr}]
     # fp16: dynamic loss scale (unscale, found-inf skip, growth / backoff in the step); bf16 has fp32's range: scale 1
-    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp="fp16" in (a.amp, a.amp_heads), lr=a.lr)
+    fts = ya.FusedTrainStep(params, optimizer=a.optimizer, grad_clip=a.grad_clip, amp="fp16" in (a.amp, a.amp_heads, a.amp_backbone), lr=a.lr)
 
     def step(x, targets):
         # frozen trunk: plain tensors, nothing to backpropagate into
@@ -200,7 +209,7 @@ def main():
             feats = neck(cs, layout="nhwc")
         fts.zero_grad()
         loss, parts = crit(heads(feats, layout="nhwc"), targets)
-        fts.scale(loss).backward()                         # the identity unless --amp or --amp-heads is fp16
+        fts.scale(loss).backward()                         # the identity unless one of the --amp options is fp16
         norm = fts.step()
         return float(loss), parts, float(norm)
 

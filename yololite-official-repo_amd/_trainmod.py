@@ -94,6 +94,9 @@ def check_precision(precision) -> str:
     return precision
 
 
+PRECISION_OF = {v: k for k, v in PRECISIONS.items()}
+
+
 def dw_block(F: int, n: int) -> nn.Module:
     """Container only (the reference's DWConvBlock(F, F, n)): the layers hold the parameters; their forward is never called."""
     m = nn.Module()
@@ -205,6 +208,27 @@ def grads_like(tensors: Sequence[torch.Tensor], need: Sequence[bool]) -> List[Op
 
 # ---- a stack of conv + BatchNorm units (csrc/yl_units.h): stageops.UIBStack and stemops.ConvStack
 
+class UnitStackHandle(DeviceHandle):
+    """The handle of a unit stack (prefix "yl_stage", "yl_stem"): its dense GEMMs' operand type goes through
+    yl_amp_<stage|stem>_set / _get, not through the forward's flags"""
+
+    def _amp(self, name: str, *args):
+        what = f"yl_amp_{self.prefix[3:]}_{name}"
+        _lib.check(getattr(self.lib, what)(self.handle, *args), what=what)
+
+    def amp_set(self, precision: str):
+        """the mode of the NEXT forward; a held forward keeps its own"""
+        self._amp("set", PRECISIONS[precision])
+
+    def amp_get(self) -> Dict[str, Optional[str]]:
+        """{"precision": the handle's mode, "held": the held forward's, None without one}"""
+        if self.handle is None:
+            return {"precision": "fp32", "held": None}
+        m, hm = C.c_uint32(), C.c_uint32()
+        self._amp("get", C.byref(m), C.byref(hm))
+        return {"precision": PRECISION_OF[int(m.value)], "held": PRECISION_OF[int(hm.value)] if self.held()["forward_held"] else None}
+
+
 class UnitStackFunction(torch.autograd.Function):
     """y = stack(x, parameters): <prefix>_forward / <prefix>_backward of the handle `hd`.  x: NHWC [B,S,S,C], or with
     `nchw` the planar image [B,C,S,S], which has no gradient"""
@@ -243,7 +267,21 @@ class UnitStackFunction(torch.autograd.Function):
 
 class UnitStack(nn.Module):
     """What the unit stacks share.  A subclass fills _convs, _bns (one layer each per unit, in running order) and _handle,
-    and gives _unit_sizes(S): the size of the map every unit writes."""
+    and gives _unit_sizes(S): the size of the map every unit writes.  `.precision` ("fp32", "fp16", "bf16") is the operand
+    type of the stack's dense GEMMs from the next forward on; a backward runs in the precision of its forward."""
+    _precision = "fp32"
+
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, value):
+        self._precision = check_precision(value)           # host side only: the handle learns it in front of a forward
+
+    def amp_state(self) -> Dict[str, Optional[str]]:
+        """yl_amp_*_get: {"precision": the mode the handle was last given, "held": that of the forward held for backward}"""
+        return self._handle.amp_get()
 
     def _param_list(self) -> List[torch.Tensor]:
         """per unit in running order: conv weight, BatchNorm weight, BatchNorm bias"""
@@ -280,6 +318,7 @@ class UnitStack(nn.Module):
         if any(p.device != x.device for p in params):
             raise _lib.YoloLiteHipError(f"{self._who}: parameters and inputs must live on one HIP device")
         self._handle.ensure(x.device)
+        self._handle.amp_set(self._precision)
         x = x.float().contiguous()                         # autograd carries the gradient back through cast and copy
         shape = (B, sizes[-1], sizes[-1], self.out_channels)
         return UnitStackFunction.apply(self._handle, self._stat_buffers(), self.training, torch.is_grad_enabled(), shape, nchw,

@@ -58,7 +58,7 @@ UNITS = [   # (source, extra flags, object name)
     # the 1x1 convolutions are the heads' GEMM (yl_block.h).  The walk over its conv + BatchNorm units, forward and backward,
     # is yl_units.h and the BatchNorm kernels are yl_bn.h, both shared with yl_stem.hip
     ("yl_stage.hip", ["-ffp-contract=off"], "yl_stage.o"),
-    # trainable dense stem (image -> C3): dense 3x3 convolution with stride in three passes on fp32 MFMA, strided 1x1 units on
+    # trainable dense stem (image -> C3): dense 3x3 convolution with stride in three passes on fp32 (or fp16 / bf16) MFMA, strided 1x1 units on
     # the heads' GEMM; the unit walk (yl_units.h) and BatchNorm + ReLU (yl_bn.h) are the ones yl_stage.hip runs
     ("yl_stem.hip", ["-ffp-contract=off"], "yl_stem.o"),
 ]

@@ -4,7 +4,9 @@
 // The stack is flattened into UNITS, each a bias-free convolution and its BatchNorm:
 //   unit u:  z = conv(x_u)   h = bn(z) [relu] [+ the block's input, behind the last unit of a residual block]
 // x_u is the previous unit's h (the caller's x for unit 0).  A depthwise unit is k x k with stride 1 or 2; a 1x1 unit is
-// the heads' GEMM (yl_block.h: launch_gemm<0> with its accessors) in all three passes.
+// the heads' GEMM (yl_block.h: launch_gemm_in with its accessors) in all three passes, in the handle's operand type
+// (yl_amp_stage_set: fp32, or fp16 / bf16 operands rounded to nearest even inside the GEMM, fp32 accumulation).  The
+// depthwise units, BatchNorm, ReLU and the residual are fp32 in every mode.
 // The walk over the units, forward and backward, with the handle, its memory and the table checks, is yl_units.h, shared
 // with yl_stem.hip; here are what is this stack's own: its configuration and units (cfg_ok, make_units, the per-block
 // plan), the policy that tells the walk what a unit's convolution launches (three rotating buffers; units without ReLU and
@@ -247,18 +249,18 @@ struct StagePolicy {
   static yl_status layout(const yl_stage_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z) {
     return ::layout(cfg, B, S, us, n, z, nullptr);
   }
-  static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers&) {
+  static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers&, int mode) {
     if (u.dw) launch_dw<false>(s, x, w, z, u.k, u.st, B, u.Sin, u.Sout, u.cout);
-    else launch_gemm<0>(s, RowsScalar{w, u.cin}, RowsVec{x, u.cin}, OutRowsVec{z, u.cout}, u.cout, (int)u.Mout, u.cin, u.cin, 1);
+    else launch_gemm_in<true>(mode, s, RowsScalar{w, u.cin}, RowsVec{x, u.cin}, OutRowsVec{z, u.cout}, u.cout, (int)u.Mout, u.cin, u.cin, 1);
     return 1;
   }
-  static int conv_wgrad(hipStream_t s, const Unit& u, int B, const float* x, const float* dz, float* dw, const UnitBuffers& sb) {
+  static int conv_wgrad(hipStream_t s, const Unit& u, int B, const float* x, const float* dz, float* dw, const UnitBuffers& sb, int mode) {
     const int F = u.cout;
     if (u.dw) {
       launch_dw_wgrad(s, dz, x, sb.spart, dw, u.k, u.st, B, u.Sin, u.Sout, F, u.tiles);
     } else {                             // dW = dz^T . x
-      launch_gemm<0>(s, ColsScalar{x, u.cin}, ColsScalar{dz, F}, OutPartial{sb.wpart, (long)u.cin * F}, u.cin, F, (int)u.Mout,
-                     u.wrows, u.wsplits);
+      launch_gemm_in<true>(mode, s, ColsScalar{x, u.cin}, ColsScalar{dz, F}, OutPartial{sb.wpart, (long)u.cin * F}, u.cin, F,
+                           (int)u.Mout, u.wrows, u.wsplits);
       HeadRows none;
       memset(&none, 0, sizeof(none));
       hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)u.cin * F, NT)), dim3(NT), 0, s, (const float*)sb.wpart,
@@ -266,10 +268,10 @@ struct StagePolicy {
     }
     return 2;
   }
-  static int conv_dgrad(hipStream_t s, const Unit& u, int B, const float* dz, const float* w, float* dx, const UnitBuffers&) {
+  static int conv_dgrad(hipStream_t s, const Unit& u, int B, const float* dz, const float* w, float* dx, const UnitBuffers&, int mode) {
     const int F = u.cout;
     if (u.dw) launch_dw<true>(s, dz, w, dx, u.k, u.st, B, u.Sin, u.Sout, F);
-    else launch_gemm<0>(s, ColsScalar{w, u.cin}, RowsVec{dz, F}, OutRowsVec{dx, u.cin}, u.cin, (int)u.Mout, F, F, 1);   // dx = dz . W
+    else launch_gemm_in<true>(mode, s, ColsScalar{w, u.cin}, RowsVec{dz, F}, OutRowsVec{dx, u.cin}, u.cin, (int)u.Mout, F, F, 1);   // dx = dz . W
     return 1;
   }
   template <bool RELU> static void colstats(hipStream_t s, const Unit& u, const StatP& sp) {
@@ -309,6 +311,10 @@ void yl_stage_destroy(yl_stage* h) { units_destroy(h); }
 yl_status yl_stage_held(const yl_stage* h, int64_t* saved_bytes, int64_t* workspace_bytes, int32_t* forward_held) {
   return units_held(h, saved_bytes, workspace_bytes, forward_held);
 }
+
+yl_status yl_amp_stage_set(yl_stage* h, uint32_t mode) { return units_amp_set(h, mode); }
+
+yl_status yl_amp_stage_get(const yl_stage* h, uint32_t* mode, uint32_t* held_mode) { return units_amp_get(h, mode, held_mode); }
 
 yl_status yl_stage_forward(yl_stage* h, const yl_stage_tensors* params, const float* x_dev, int32_t batch, int32_t size,
                            uint32_t flags, float* out_dev, void* stream, int32_t* launches) {

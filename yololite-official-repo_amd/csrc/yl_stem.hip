@@ -6,8 +6,10 @@
 //
 // The walk over the units, forward and backward, with the handle, its memory and the table checks, is yl_units.h, shared
 // with yl_stage.hip: a unit here is a block of its own without a residual, so two rotating buffers do.  BatchNorm, ReLU,
-// the column sums and the BatchNorm backward are yl_bn.h's, the 1x1 units the heads' GEMM (yl_block.h: launch_gemm<0>)
-// with accessors of their own where the unit strides or reads the planar image.  Here are the stack's configuration and
+// the column sums and the BatchNorm backward are yl_bn.h's, the 1x1 units the heads' GEMM (yl_block.h: launch_gemm_in)
+// with accessors of their own where the unit strides or reads the planar image.  Every dense GEMM, 3x3 and 1x1 in all three
+// passes, runs in the handle's operand type (yl_amp_stem_set): fp32, or fp16 / bf16 operands rounded to nearest even with
+// fp32 accumulation on v_mfma_f32_16x16x16_*; BatchNorm, ReLU and every float64 sum are the same in every mode.  Here are the stack's configuration and
 // units (cfg_ok, make_units, wgrad3_plan), the policy that tells the walk what a unit's convolution launches, and what is
 // new: the 3x3 convolution in three passes.
 //
@@ -89,6 +91,36 @@ __global__ __launch_bounds__(NT) void yl_stem_pack_kernel(const float* __restric
   }
   wp[idx] = v;
 }
+// ---- 16-bit modes (PR: 1 fp16, 2 bf16; yl_block.h: Frag16, mfma16).  Every staged value is rounded ONCE, to nearest even
+// and without a clamp: the weight here, into a pack of 16-bit elements in the same [tap][a][b] order (half the bytes of the
+// fp32 pack, in the same buffer), the window when it goes into LDS, where it stays a float that lies on the 16-bit grid, so
+// the pitches and the bank arithmetic above hold as they are and the conversion in front of each MFMA is exact.
+template <int PR> struct Elem16;
+template <> struct Elem16<1> { typedef _Float16 T; };
+template <> struct Elem16<2> { typedef __bf16 T; };
+template <int PR> __device__ __forceinline__ f32x4 rne4(f32x4 v) {
+  return __builtin_convertvector(__builtin_convertvector(v, typename Frag16<PR>::T), f32x4);
+}
+template <int PR> __device__ __forceinline__ float rne1(float v) { return (float)(typename Elem16<PR>::T)v; }
+template <int PR> __device__ __forceinline__ typename Frag16<PR>::T ldh4(const void* base, long elem) {   // elem % 4 == 0
+  return *reinterpret_cast<const typename Frag16<PR>::T*>(reinterpret_cast<const char*>(base) + elem * 2);
+}
+template <int PR>
+__global__ __launch_bounds__(NT) void yl_stem_pack16_kernel(const float* __restrict__ w, typename Elem16<PR>::T* __restrict__ wp,
+                                                           int A, int Bn, int Bp, int T, PackP tp) {
+  const long idx = (long)blockIdx.x * NT + threadIdx.x;
+  const long AB = (long)A * Bp;
+  if (idx >= tp.ntap * AB) return;
+  const int tap = (int)(idx / AB);
+  const long ab = idx - tap * AB;
+  const int a = (int)(ab / Bp), b = (int)(ab - (long)a * Bp);
+  float v = 0.f;
+  if (b < Bn) {
+    const long oi = T ? (long)b * A + a : (long)a * Bn + b;
+    v = w[oi * 9 + tp.ky[tap] * 3 + tp.kx[tap]];
+  }
+  wp[idx] = (typename Elem16<PR>::T)v;
+}
 
 struct ConvP {
   const float* src; const float* wp; float* dst;
@@ -99,8 +131,10 @@ struct ConvP {
   int o0;                                // class pixel a, tap ty -> source row ST a + o0 + ty
   int nty, ntx;
 };
-// grid (B * TY * TXn, ceil(N / (16 PT)))
-template <int ST, int PT, bool PLANAR>
+// grid (B * TY * TXn, ceil(N / (16 PT))).  PR != 0: P.wp is the 16-bit pack, and the four 16x16x4 steps over a lane's four k
+// values are ONE v_mfma_f32_16x16x16_* on the same four values (NHWC: 9 MFMAs per k-block and p-tile for 36; planar: one per
+// k step of four taps); the accumulators, one per tap, and their pairwise sum are those of fp32
+template <int ST, int PT, bool PLANAR, int PR = 0>
 __global__ __launch_bounds__(NT) void yl_stem_conv_kernel(ConvP P) {
   typedef Win<ST> W;
   constexpr int WE = W::WE;
@@ -126,6 +160,7 @@ __global__ __launch_bounds__(NT) void yl_stem_conv_kernel(ConvP P) {
       const int gy = sy0 + wy, gx = sx0 + wx;
       float v = 0.f;
       if (c < P.Cs && gy >= 0 && gy < P.Ss && gx >= 0 && gx < P.Ss) v = P.src[(((long)b * P.Cs + c) * P.Ss + gy) * P.Ss + gx];
+      if constexpr (PR != 0) v = rne1<PR>(v);
       win[W::at(wy, wx) * 4 + c] = v;
     }
     __syncthreads();
@@ -135,16 +170,26 @@ __global__ __launch_bounds__(NT) void yl_stem_conv_kernel(ConvP P) {
       const bool on = tap < ntap;
       const int ty = on ? tap / P.ntx : 0, tx = on ? tap - ty * P.ntx : 0;
       const f32x4 qv = on ? ld4(&win[W::at(row * ST + ty, col * ST + tx) * 4]) : zero;
-      f32x4 pv[PT];
+      if constexpr (PR == 0) {
+        f32x4 pv[PT];
 #pragma unroll
-      for (int pt = 0; pt < PT; ++pt) {
-        const int n = n0 + 16 * pt + i;
-        pv[pt] = (on && n < P.N) ? ld4(P.wp + ((long)tap * P.N + n) * 4) : zero;
+        for (int pt = 0; pt < PT; ++pt) {
+          const int n = n0 + 16 * pt + i;
+          pv[pt] = (on && n < P.N) ? ld4(P.wp + ((long)tap * P.N + n) * 4) : zero;
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int pt = 0; pt < PT; ++pt) acc[0][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[0][pt], 0, 0, 0);
+      } else {
+        typedef typename Frag16<PR>::T H;
+        const H zh = __builtin_convertvector(zero, H), qh = __builtin_convertvector(qv, H);
+#pragma unroll
+        for (int pt = 0; pt < PT; ++pt) {
+          const int n = n0 + 16 * pt + i;
+          acc[0][pt] = mfma16((on && n < P.N) ? ldh4<PR>(P.wp, ((long)tap * P.N + n) * 4) : zh, qh, acc[0][pt]);
+        }
       }
-#pragma unroll
-      for (int s = 0; s < 4; ++s)
-#pragma unroll
-        for (int pt = 0; pt < PT; ++pt) acc[0][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[0][pt], 0, 0, 0);
     }
   } else {
     const int nkb = (P.Cs + SKB - 1) / SKB;
@@ -155,7 +200,11 @@ __global__ __launch_bounds__(NT) void yl_stem_conv_kernel(ConvP P) {
         const int pw = item >> 2, q = item & 3, wy = pw / WE, wx = pw - wy * WE;
         const int gy = sy0 + wy, gx = sx0 + wx;
         const bool ok = gy >= 0 && gy < P.Ss && gx >= 0 && gx < P.Ss && c0 + 4 * q < P.Cs;
-        st4(&win[(q * W::PL + W::at(wy, wx)) * 4], ok ? ld4(P.src + (((long)b * P.Ss + gy) * P.Ss + gx) * P.Cs + c0 + 4 * q) : zero);
+        if constexpr (PR == 0)
+          st4(&win[(q * W::PL + W::at(wy, wx)) * 4], ok ? ld4(P.src + (((long)b * P.Ss + gy) * P.Ss + gx) * P.Cs + c0 + 4 * q) : zero);
+        else
+          st4(&win[(q * W::PL + W::at(wy, wx)) * 4],
+              ok ? rne4<PR>(ld4(P.src + (((long)b * P.Ss + gy) * P.Ss + gx) * P.Cs + c0 + 4 * q)) : zero);
       }
       __syncthreads();
       const int c = c0 + 4 * kq;
@@ -166,17 +215,28 @@ __global__ __launch_bounds__(NT) void yl_stem_conv_kernel(ConvP P) {
           if (ty >= P.nty || tx >= P.ntx) continue;        // uniform: the accumulators are indexed by constants
           const int tap = ty * P.ntx + tx;
           const f32x4 qv = ld4(&win[(kq * W::PL + W::at(row * ST + ty, col * ST + tx)) * 4]);
-          f32x4 pv[PT];
+          if constexpr (PR == 0) {
+            f32x4 pv[PT];
 #pragma unroll
-          for (int pt = 0; pt < PT; ++pt) {
-            const int n = n0 + 16 * pt + i;
-            pv[pt] = (n < P.N && c < P.Cp) ? ld4(P.wp + ((long)tap * P.N + n) * P.Cp + c) : zero;
+            for (int pt = 0; pt < PT; ++pt) {
+              const int n = n0 + 16 * pt + i;
+              pv[pt] = (n < P.N && c < P.Cp) ? ld4(P.wp + ((long)tap * P.N + n) * P.Cp + c) : zero;
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+              for (int pt = 0; pt < PT; ++pt)
+                acc[ty * 3 + tx][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[ty * 3 + tx][pt], 0, 0, 0);
+          } else {
+            typedef typename Frag16<PR>::T H;
+            const H zh = __builtin_convertvector(zero, H), qh = __builtin_convertvector(qv, H);
+#pragma unroll
+            for (int pt = 0; pt < PT; ++pt) {
+              const int n = n0 + 16 * pt + i;
+              acc[ty * 3 + tx][pt] = mfma16((n < P.N && c < P.Cp) ? ldh4<PR>(P.wp, ((long)tap * P.N + n) * P.Cp + c) : zh, qh,
+                                            acc[ty * 3 + tx][pt]);
+            }
           }
-#pragma unroll
-          for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int pt = 0; pt < PT; ++pt)
-              acc[ty * 3 + tx][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pv[pt][s], qv[s], acc[ty * 3 + tx][pt], 0, 0, 0);
         }
     }
     if constexpr (!PLANAR) {             // ((0 + 1) + (2 + 3)) + ((4 + 5) + (6 + 7)) + 8; a tap that does not exist is zero
@@ -201,8 +261,10 @@ struct WgP {
   const float* x; const float* dz; float* part;
   int S, So, Cs, Cp, N, TX, ntiles, tps; // x edge, dz edge, x channels (planes), padded; dz channels; tiles per edge, in all, per split
 };
-// grid (ceil(Cp / GC), ceil(N / GN), splits); PTC c-tiles of 16 per lane (planar: 1, the image has at most 4 channels)
-template <int ST, bool PLANAR>
+// grid (ceil(Cp / GC), ceil(N / GN), splits); PTC c-tiles of 16 per lane (planar: 1, the image has at most 4 channels).
+// PR != 0: x and dz are rounded as they are staged; kq selects four stored pixels, so the four K = 4 steps over them are ONE
+// K = 16 MFMA per tap and c-tile.  The partials stay fp32
+template <int ST, bool PLANAR, int PR = 0>
 __global__ __launch_bounds__(NT) void yl_stem_wgrad_kernel(WgP P) {
   typedef Win<ST> W;
   constexpr int WE = W::WE, PTC = PLANAR ? 1 : GC / 16;
@@ -231,6 +293,7 @@ __global__ __launch_bounds__(NT) void yl_stem_wgrad_kernel(WgP P) {
         const int gy = sy0 + wy, gx = sx0 + wx;
         float v = 0.f;
         if (c < P.Cs && gy >= 0 && gy < P.S && gx >= 0 && gx < P.S) v = P.x[(((long)b * P.Cs + c) * P.S + gy) * P.S + gx];
+        if constexpr (PR != 0) v = rne1<PR>(v);
         xw[W::gat(wy, wx) * GXS + c] = v;
       }
     } else {
@@ -238,14 +301,20 @@ __global__ __launch_bounds__(NT) void yl_stem_wgrad_kernel(WgP P) {
         const int pw = item / (GC / 4), q = (item - pw * (GC / 4)) * 4, wy = pw / WE, wx = pw - wy * WE;
         const int gy = sy0 + wy, gx = sx0 + wx;
         const bool ok = gy >= 0 && gy < P.S && gx >= 0 && gx < P.S && c0 + q < P.Cs;
-        st4(&xw[W::gat(wy, wx) * GXS + q], ok ? ld4(P.x + (((long)b * P.S + gy) * P.S + gx) * P.Cs + c0 + q) : zero);
+        if constexpr (PR == 0)
+          st4(&xw[W::gat(wy, wx) * GXS + q], ok ? ld4(P.x + (((long)b * P.S + gy) * P.S + gx) * P.Cs + c0 + q) : zero);
+        else
+          st4(&xw[W::gat(wy, wx) * GXS + q], ok ? rne4<PR>(ld4(P.x + (((long)b * P.S + gy) * P.S + gx) * P.Cs + c0 + q)) : zero);
       }
     }
     for (int item = t; item < ST_T * ST_T * (GN / 4); item += NT) {
       const int pk = item / (GN / 4), q = (item - pk * (GN / 4)) * 4;
       const int gy = ty0 + (pk >> 3), gx = tx0 + (pk & 7);
       const bool ok = gy < P.So && gx < P.So && n0 + q < P.N;
-      st4(&dzt[pk * GDS + q], ok ? ld4(P.dz + (((long)b * P.So + gy) * P.So + gx) * P.N + n0 + q) : zero);
+      if constexpr (PR == 0)
+        st4(&dzt[pk * GDS + q], ok ? ld4(P.dz + (((long)b * P.So + gy) * P.So + gx) * P.N + n0 + q) : zero);
+      else
+        st4(&dzt[pk * GDS + q], ok ? rne4<PR>(ld4(P.dz + (((long)b * P.So + gy) * P.So + gx) * P.N + n0 + q)) : zero);
     }
     __syncthreads();
 #pragma unroll 1
@@ -254,15 +323,32 @@ __global__ __launch_bounds__(NT) void yl_stem_wgrad_kernel(WgP P) {
       float qv[4];
 #pragma unroll
       for (int s = 0; s < 4; ++s) qv[s] = dzt[(prow * ST_T + pcol + s) * GDS + 16 * wave + i];
+      if constexpr (PR == 0) {
 #pragma unroll
-      for (int tap = 0; tap < 9; ++tap) {
-        const int ky = tap / 3, kx = tap - 3 * ky;
+        for (int tap = 0; tap < 9; ++tap) {
+          const int ky = tap / 3, kx = tap - 3 * ky;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-          const float* xb = xw + W::gat(ST * prow + ky, ST * (pcol + s) + kx) * GXS + i;
+          for (int s = 0; s < 4; ++s) {
+            const float* xb = xw + W::gat(ST * prow + ky, ST * (pcol + s) + kx) * GXS + i;
 #pragma unroll
-          for (int pt = 0; pt < PTC; ++pt)
-            acc[tap][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[16 * pt], qv[s], acc[tap][pt], 0, 0, 0);
+            for (int pt = 0; pt < PTC; ++pt)
+              acc[tap][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(xb[16 * pt], qv[s], acc[tap][pt], 0, 0, 0);
+          }
+        }
+      } else {
+        typedef typename Frag16<PR>::T H;
+        const f32x4 qf = {qv[0], qv[1], qv[2], qv[3]};
+        const H qh = __builtin_convertvector(qf, H);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+          const int ky = tap / 3, kx = tap - 3 * ky;
+#pragma unroll
+          for (int pt = 0; pt < PTC; ++pt) {
+            f32x4 xf;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) xf[s] = xw[W::gat(ST * prow + ky, ST * (pcol + s) + kx) * GXS + i + 16 * pt];
+            acc[tap][pt] = mfma16(__builtin_convertvector(xf, H), qh, acc[tap][pt]);
+          }
         }
       }
     }
@@ -333,45 +419,59 @@ int pick_conv_pt(int N) {                // 16 PT output channels per workgroup:
   return best;
 }
 
-template <int ST, bool PLANAR>
+template <int ST, bool PLANAR, int PR>
 void launch_conv_st(hipStream_t s, const ConvP& P, int B) {
   const int pt = pick_conv_pt(P.N);
   const dim3 grid(B * P.TY * P.TXn, ceil_div(P.N, 16 * pt)), blk(NT);
-  if (pt == 2) hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 2, PLANAR>), grid, blk, 0, s, P);
-  else if (pt == 3) hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 3, PLANAR>), grid, blk, 0, s, P);
-  else hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 4, PLANAR>), grid, blk, 0, s, P);
+  if (pt == 2) hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 2, PLANAR, PR>), grid, blk, 0, s, P);
+  else if (pt == 3) hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 3, PLANAR, PR>), grid, blk, 0, s, P);
+  else hipLaunchKernelGGL((yl_stem_conv_kernel<ST, 4, PLANAR, PR>), grid, blk, 0, s, P);
 }
-void launch_conv(hipStream_t s, const ConvP& P, int B, int st, bool planar) {
-  if (st == 1 && !planar) launch_conv_st<1, false>(s, P, B);
-  else if (st == 1) launch_conv_st<1, true>(s, P, B);
-  else if (!planar) launch_conv_st<2, false>(s, P, B);
-  else launch_conv_st<2, true>(s, P, B);
+template <int PR>
+void launch_conv_in(hipStream_t s, const ConvP& P, int B, int st, bool planar) {
+  if (st == 1 && !planar) launch_conv_st<1, false, PR>(s, P, B);
+  else if (st == 1) launch_conv_st<1, true, PR>(s, P, B);
+  else if (!planar) launch_conv_st<2, false, PR>(s, P, B);
+  else launch_conv_st<2, true, PR>(s, P, B);
 }
-void launch_pack(hipStream_t s, const float* w, float* wp, int A, int Bn, int Bp, int T, const PackP& tp) {
-  hipLaunchKernelGGL(yl_stem_pack_kernel, dim3(ceil_div((long)tp.ntap * A * Bp, NT)), dim3(NT), 0, s, w, wp, A, Bn, Bp, T, tp);
+// `mode`: the operand type (0 fp32, 1 fp16, 2 bf16); P.wp is a pack launch_pack wrote in the same mode
+void launch_conv(hipStream_t s, const ConvP& P, int B, int st, bool planar, int mode) {
+  if (mode == 1) launch_conv_in<1>(s, P, B, st, planar);
+  else if (mode == 2) launch_conv_in<2>(s, P, B, st, planar);
+  else launch_conv_in<0>(s, P, B, st, planar);
+}
+void launch_pack(hipStream_t s, const float* w, float* wp, int A, int Bn, int Bp, int T, const PackP& tp, int mode) {
+  const dim3 grid(ceil_div((long)tp.ntap * A * Bp, NT)), blk(NT);
+  if (mode == 1) hipLaunchKernelGGL(yl_stem_pack16_kernel<1>, grid, blk, 0, s, w, (_Float16*)wp, A, Bn, Bp, T, tp);
+  else if (mode == 2) hipLaunchKernelGGL(yl_stem_pack16_kernel<2>, grid, blk, 0, s, w, (__bf16*)wp, A, Bn, Bp, T, tp);
+  else hipLaunchKernelGGL(yl_stem_pack_kernel, grid, blk, 0, s, w, wp, A, Bn, Bp, T, tp);
+}
+// packed tap `tap` of a pack of `per` elements a tap: 4 bytes an element in fp32, 2 in the 16-bit modes
+inline const float* pack_tap(const float* wp, long tap, long per, int mode) {
+  return (const float*)((const char*)wp + tap * per * (mode ? 2 : 4));
 }
 
 // 3x3 forward: 2 launches (pack, convolution).  wpack: 9 cout round4(cin) floats
 int conv3_forward(hipStream_t s, const float* x, const float* w, float* wpack, float* z, int st, int B, int Sin, int Sout,
-                  int cin, int cout, bool planar) {
+                  int cin, int cout, bool planar, int mode) {
   const int cp = round4(cin);
   PackP tp;
   tp.ntap = 9;
   for (int t = 0; t < 9; ++t) { tp.ky[t] = t / 3; tp.kx[t] = t % 3; }
-  launch_pack(s, w, wpack, cout, cin, cp, 0, tp);
+  launch_pack(s, w, wpack, cout, cin, cp, 0, tp, mode);
   ConvP P;
   P.src = x; P.wp = wpack; P.dst = z;
   P.Ss = Sin; P.Cs = cin; P.Cp = cp; P.N = cout; P.Sd = Sout;
   P.TY = P.TXn = ceil_div(Sout, ST_T); P.ey = P.ex = Sout;
   P.os = 1; P.poy = P.pox = 0; P.o0 = -1; P.nty = P.ntx = 3;
-  launch_conv(s, P, B, st, planar);
+  launch_conv(s, P, B, st, planar, mode);
   return 2;
 }
 // the parity classes of a stride-2 input gradient that have pixels: 4 if S >= 2, else 1
 inline int dgrad_classes(int S) { return S >= 2 ? 4 : 1; }
 // 3x3 input gradient: stride 1: 2 launches; stride 2: 1 + dgrad_classes(Sin).  wpack: 9 cin cout floats
 int conv3_dgrad(hipStream_t s, const float* dz, const float* w, float* wpack, float* dx, int st, int B, int Sin, int Sout,
-                int cin, int cout) {
+                int cin, int cout, int mode) {
   ConvP P;
   P.src = dz; P.dst = dx;
   P.Ss = Sout; P.Cs = cout; P.Cp = cout; P.N = cin; P.Sd = Sin;
@@ -379,11 +479,11 @@ int conv3_dgrad(hipStream_t s, const float* dz, const float* w, float* wpack, fl
   tp.ntap = 9;
   if (st == 1) {
     for (int t = 0; t < 9; ++t) { tp.ky[t] = 2 - t / 3; tp.kx[t] = 2 - t % 3; }
-    launch_pack(s, w, wpack, cin, cout, cout, 1, tp);
+    launch_pack(s, w, wpack, cin, cout, cout, 1, tp, mode);
     P.wp = wpack;
     P.TY = P.TXn = ceil_div(Sin, ST_T); P.ey = P.ex = Sin;
     P.os = 1; P.poy = P.pox = 0; P.o0 = -1; P.nty = P.ntx = 3;
-    launch_conv(s, P, B, 1, false);
+    launch_conv(s, P, B, 1, false, mode);
     return 2;
   }
   int o = 0, first[4];                   // the classes' taps, one after the other: 1 + 2 + 2 + 4 = 9
@@ -393,16 +493,16 @@ int conv3_dgrad(hipStream_t s, const float* dz, const float* w, float* wpack, fl
       for (int ty = 0; ty <= pi; ++ty)
         for (int tx = 0; tx <= pj; ++tx) { tp.ky[o] = pi ? 2 - 2 * ty : 1; tp.kx[o] = pj ? 2 - 2 * tx : 1; ++o; }
     }
-  launch_pack(s, w, wpack, cin, cout, cout, 1, tp);
+  launch_pack(s, w, wpack, cin, cout, cout, 1, tp, mode);
   int nl = 1;
   for (int pi = 0; pi < 2; ++pi)
     for (int pj = 0; pj < 2; ++pj) {
       P.ey = (Sin - pi + 1) / 2; P.ex = (Sin - pj + 1) / 2;
       if (P.ey < 1 || P.ex < 1) continue;
-      P.wp = wpack + (long)first[pi * 2 + pj] * cin * cout;
+      P.wp = pack_tap(wpack, first[pi * 2 + pj], (long)cin * cout, mode);
       P.TY = ceil_div(P.ey, ST_T); P.TXn = ceil_div(P.ex, ST_T);
       P.os = 2; P.poy = pi; P.pox = pj; P.o0 = 0; P.nty = 1 + pi; P.ntx = 1 + pj;
-      launch_conv(s, P, B, 1, false);
+      launch_conv(s, P, B, 1, false, mode);
       ++nl;
     }
   return nl;
@@ -416,18 +516,25 @@ void wgrad3_plan(int B, int Sout, int cin, int cout, int* tps, int* splits) {
   *tps = ceil_div(ntiles, want);
   *splits = ceil_div(ntiles, *tps);
 }
+template <int PR>
+void launch_wgrad(hipStream_t s, dim3 grid, const WgP& P, int st, bool planar) {
+  const dim3 blk(NT);
+  if (st == 1 && !planar) hipLaunchKernelGGL((yl_stem_wgrad_kernel<1, false, PR>), grid, blk, 0, s, P);
+  else if (st == 1) hipLaunchKernelGGL((yl_stem_wgrad_kernel<1, true, PR>), grid, blk, 0, s, P);
+  else if (!planar) hipLaunchKernelGGL((yl_stem_wgrad_kernel<2, false, PR>), grid, blk, 0, s, P);
+  else hipLaunchKernelGGL((yl_stem_wgrad_kernel<2, true, PR>), grid, blk, 0, s, P);
+}
 // 3x3 weight gradient: 2 launches (partials, ordered sum).  part: splits 9 cout round4(cin) floats
 int conv3_wgrad(hipStream_t s, const float* x, const float* dz, float* part, float* dw, int st, int B, int Sin, int Sout,
-                int cin, int cout, bool planar, int tps, int splits) {
+                int cin, int cout, bool planar, int tps, int splits, int mode) {
   WgP P;
   P.x = x; P.dz = dz; P.part = part;
   P.S = Sin; P.So = Sout; P.Cs = cin; P.Cp = round4(cin); P.N = cout;
   P.TX = ceil_div(Sout, ST_T); P.ntiles = B * P.TX * P.TX; P.tps = tps;
   const dim3 grid(ceil_div(P.Cp, GC), ceil_div(cout, GN), splits), blk(NT);
-  if (st == 1 && !planar) hipLaunchKernelGGL((yl_stem_wgrad_kernel<1, false>), grid, blk, 0, s, P);
-  else if (st == 1) hipLaunchKernelGGL((yl_stem_wgrad_kernel<1, true>), grid, blk, 0, s, P);
-  else if (!planar) hipLaunchKernelGGL((yl_stem_wgrad_kernel<2, false>), grid, blk, 0, s, P);
-  else hipLaunchKernelGGL((yl_stem_wgrad_kernel<2, true>), grid, blk, 0, s, P);
+  if (mode == 1) launch_wgrad<1>(s, grid, P, st, planar);
+  else if (mode == 2) launch_wgrad<2>(s, grid, P, st, planar);
+  else launch_wgrad<0>(s, grid, P, st, planar);
   hipLaunchKernelGGL(yl_stem_wsum_kernel, dim3(ceil_div(9L * cout * cin, NT)), blk, 0, s, (const float*)part, splits, cout, cin,
                      P.Cp, dw);
   return 2;
@@ -435,31 +542,33 @@ int conv3_wgrad(hipStream_t s, const float* x, const float* dz, float* part, flo
 
 // ---- 1x1: the heads' GEMM.  Stride 1 on NHWC rows launches what yl_stage.hip launches
 int conv1_forward(hipStream_t s, const float* x, const float* w, float* z, int st, int B, int Sin, int Sout, int cin, int cout,
-                  bool planar) {
+                  bool planar, int mode) {
   const int M = B * Sout * Sout;
-  if (st == 1 && !planar) launch_gemm<0>(s, RowsScalar{w, cin}, RowsVec{x, cin}, OutRowsVec{z, cout}, cout, M, cin, cin, 1);
-  else launch_gemm<0>(s, RowsScalar{w, cin}, SrcRows{x, SrcGeom{cin, Sin, Sout, st, planar ? 1 : 0}}, OutRowsVec{z, cout}, cout, M, cin, cin, 1);
+  if (st == 1 && !planar) launch_gemm_in<true>(mode, s, RowsScalar{w, cin}, RowsVec{x, cin}, OutRowsVec{z, cout}, cout, M, cin, cin, 1);
+  else launch_gemm_in<true>(mode, s, RowsScalar{w, cin}, SrcRows{x, SrcGeom{cin, Sin, Sout, st, planar ? 1 : 0}}, OutRowsVec{z, cout}, cout, M,
+                            cin, cin, 1);
   return 1;
 }
 // stride 2: dx is zeroed (a memset, not counted) and the rows land on its even pixels
-int conv1_dgrad(hipStream_t s, const float* dz, const float* w, float* dx, int st, int B, int Sin, int Sout, int cin, int cout) {
+int conv1_dgrad(hipStream_t s, const float* dz, const float* w, float* dx, int st, int B, int Sin, int Sout, int cin, int cout,
+                int mode) {
   const int M = B * Sout * Sout;
   if (st == 1) {
-    launch_gemm<0>(s, ColsScalar{w, cin}, RowsVec{dz, cout}, OutRowsVec{dx, cin}, cin, M, cout, cout, 1);
+    launch_gemm_in<true>(mode, s, ColsScalar{w, cin}, RowsVec{dz, cout}, OutRowsVec{dx, cin}, cin, M, cout, cout, 1);
   } else {
     hipMemsetAsync(dx, 0, (size_t)B * Sin * Sin * cin * 4, s);
-    launch_gemm<0>(s, ColsScalar{w, cin}, RowsVec{dz, cout}, OutPix{dx, SrcGeom{cin, Sin, Sout, st, 0}}, cin, M, cout, cout, 1);
+    launch_gemm_in<true>(mode, s, ColsScalar{w, cin}, RowsVec{dz, cout}, OutPix{dx, SrcGeom{cin, Sin, Sout, st, 0}}, cin, M, cout, cout, 1);
   }
   return 1;
 }
 int conv1_wgrad(hipStream_t s, const float* x, const float* dz, float* part, float* dw, int st, int B, int Sin, int Sout, int cin,
-                int cout, bool planar, int rows, int splits) {
+                int cout, bool planar, int rows, int splits, int mode) {
   const int M = B * Sout * Sout;
   if (st == 1 && !planar)
-    launch_gemm<0>(s, ColsScalar{x, cin}, ColsScalar{dz, cout}, OutPartial{part, (long)cin * cout}, cin, cout, M, rows, splits);
+    launch_gemm_in<true>(mode, s, ColsScalar{x, cin}, ColsScalar{dz, cout}, OutPartial{part, (long)cin * cout}, cin, cout, M, rows, splits);
   else
-    launch_gemm<0>(s, SrcCols{x, SrcGeom{cin, Sin, Sout, st, planar ? 1 : 0}}, ColsScalar{dz, cout}, OutPartial{part, (long)cin * cout},
-                   cin, cout, M, rows, splits);
+    launch_gemm_in<true>(mode, s, SrcCols{x, SrcGeom{cin, Sin, Sout, st, planar ? 1 : 0}}, ColsScalar{dz, cout},
+                         OutPartial{part, (long)cin * cout}, cin, cout, M, rows, splits);
   HeadRows none;
   memset(&none, 0, sizeof(none));
   hipLaunchKernelGGL(yl_head_wsum_kernel, dim3(ceil_div((long)cin * cout, NT)), dim3(NT), 0, s, (const float*)part, splits, cin,
@@ -529,17 +638,20 @@ struct StemPolicy {
   static constexpr int ROT = 2;
   static constexpr bool MIXED = false;   // every unit has its ReLU and no block a residual
   static yl_status layout(const yl_stem_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z) { return ::layout(cfg, B, S, us, n, z); }
-  static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers& sb) {
-    return u.k == 3 ? conv3_forward(s, x, w, sb.wpack, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar)
-                    : conv1_forward(s, x, w, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar);
+  static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers& sb,
+                          int mode) {
+    return u.k == 3 ? conv3_forward(s, x, w, sb.wpack, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, mode)
+                    : conv1_forward(s, x, w, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, mode);
   }
-  static int conv_wgrad(hipStream_t s, const Unit& u, int B, const float* x, const float* dz, float* dw, const UnitBuffers& sb) {
-    return u.k == 3 ? conv3_wgrad(s, x, dz, sb.wpart, dw, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, u.wrows, u.wsplits)
-                    : conv1_wgrad(s, x, dz, sb.wpart, dw, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, u.wrows, u.wsplits);
+  static int conv_wgrad(hipStream_t s, const Unit& u, int B, const float* x, const float* dz, float* dw, const UnitBuffers& sb,
+                        int mode) {
+    return u.k == 3 ? conv3_wgrad(s, x, dz, sb.wpart, dw, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, u.wrows, u.wsplits, mode)
+                    : conv1_wgrad(s, x, dz, sb.wpart, dw, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, u.wrows, u.wsplits, mode);
   }
-  static int conv_dgrad(hipStream_t s, const Unit& u, int B, const float* dz, const float* w, float* dx, const UnitBuffers& sb) {
-    return u.k == 3 ? conv3_dgrad(s, dz, w, sb.wpack, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout)
-                    : conv1_dgrad(s, dz, w, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout);
+  static int conv_dgrad(hipStream_t s, const Unit& u, int B, const float* dz, const float* w, float* dx, const UnitBuffers& sb,
+                        int mode) {
+    return u.k == 3 ? conv3_dgrad(s, dz, w, sb.wpack, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout, mode)
+                    : conv1_dgrad(s, dz, w, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout, mode);
   }
   template <bool RELU> static void colstats(hipStream_t s, const Unit& u, const StatP& sp) {
     hipLaunchKernelGGL(yl_stem_colstats_kernel<RELU>, dim3(u.tiles, ceil_div(sp.F >> 2, sp.CQ)), dim3(NT), 0, s, sp, u.stat_rows);
@@ -584,6 +696,10 @@ yl_status yl_stem_held(const yl_stem* h, int64_t* saved_bytes, int64_t* workspac
   return units_held(h, saved_bytes, workspace_bytes, forward_held);
 }
 
+yl_status yl_amp_stem_set(yl_stem* h, uint32_t mode) { return units_amp_set(h, mode); }
+
+yl_status yl_amp_stem_get(const yl_stem* h, uint32_t* mode, uint32_t* held_mode) { return units_amp_get(h, mode, held_mode); }
+
 yl_status yl_stem_forward(yl_stem* h, const yl_stem_tensors* params, const float* x_dev, int32_t batch, int32_t size,
                           uint32_t flags, float* out_dev, void* stream, int32_t* launches) {
   if (!h || !x_dev || !out_dev || batch < 1 || size < 1 || !params) return YL_ERR_INVALID;
@@ -602,9 +718,11 @@ yl_status yl_stem_backward(yl_stem* h, const yl_stem_tensors* params, const yl_s
   return units_backward<StemPolicy>(h, par, grd, n, gy_dev, dx_dev, stream, launches);
 }
 
-yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,
-                       int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, void* stream,
-                       int32_t* launches) {
+yl_status yl_amp_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,
+                           int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, uint32_t mode_flag,
+                           void* stream, int32_t* launches) {
+  const int mode = mode_of_bits(mode_flag);
+  if (mode < 0) return YL_ERR_INVALID;
   if (!a_dev || !b_dev || !out_dev || batch < 1 || size < 1 || cout < 4 || (cout & 3)) return YL_ERR_INVALID;
   if ((k != 1 && k != 3) || (stride != 1 && stride != 2)) return YL_ERR_INVALID;
   if (pass != YL_STAGE_PASS_FORWARD && pass != YL_STAGE_PASS_DGRAD && pass != YL_STAGE_PASS_WGRAD) return YL_ERR_INVALID;
@@ -636,18 +754,24 @@ yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, i
   }
   int nl = 0;
   if (pass == YL_STAGE_PASS_FORWARD)
-    nl = k == 3 ? conv3_forward(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar)
-                : conv1_forward(s, a_dev, b_dev, out_dev, stride, batch, size, So, cin, cout, planar);
+    nl = k == 3 ? conv3_forward(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, mode)
+                : conv1_forward(s, a_dev, b_dev, out_dev, stride, batch, size, So, cin, cout, planar, mode);
   else if (pass == YL_STAGE_PASS_DGRAD)
-    nl = k == 3 ? conv3_dgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout)
-                : conv1_dgrad(s, a_dev, b_dev, out_dev, stride, batch, size, So, cin, cout);
+    nl = k == 3 ? conv3_dgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, mode)
+                : conv1_dgrad(s, a_dev, b_dev, out_dev, stride, batch, size, So, cin, cout, mode);
   else
-    nl = k == 3 ? conv3_wgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, rows, splits)
-                : conv1_wgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, rows, splits);
+    nl = k == 3 ? conv3_wgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, rows, splits, mode)
+                : conv1_wgrad(s, a_dev, b_dev, tmp, out_dev, stride, batch, size, So, cin, cout, planar, rows, splits, mode);
   const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   hipFree(tmp);
   if (launches) *launches = nl;
   return ok ? YL_OK : YL_ERR_HIP;
+}
+
+yl_status yl_stem_conv(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k, int32_t stride,
+                       int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, void* stream,
+                       int32_t* launches) {
+  return yl_amp_stem_conv(a_dev, b_dev, out_dev, pass, k, stride, batch, size, cin, cout, input_nchw, 0u, stream, launches);
 }
 
 }  // extern "C"

@@ -18,7 +18,8 @@
 //   P::MIXED                     units without ReLU and residual blocks can occur.  false keeps yl_stage_bn_kernel<false>,
 //                                yl_stage_bn_bwd_kernel<false> and the add out of the object
 //   P::layout(cfg, B, S, us, &n, &z)   the units and sizes of cfg at (B, S); a status.  us and n are filled either way
-//   P::conv_forward / conv_wgrad / conv_dgrad(s, u, B, ..., sb)   the unit's convolution passes -> launches enqueued
+//   P::conv_forward / conv_wgrad / conv_dgrad(s, u, B, ..., sb, mode)   the unit's convolution passes in the dense GEMMs'
+//                                operand type `mode` (a depthwise unit has none) -> launches enqueued
 //   P::colstats<RELU>(s, u, sp)  the column sums over the unit's statistics tiles
 //   P::add(s, io, g, n4)         io += g (MIXED only)
 #ifndef YL_UNITS_H
@@ -153,7 +154,26 @@ template <class Cfg> struct UnitStack {
   Arena mem;                             // yl_block.h
   Cfg cfg;
   int fB, fS, fTrain;                    // the forward whose activations are held (mem.fValid)
+  int mode, fMode;                       // the dense GEMMs' operand type (yl_block.h: 0 fp32, 1 fp16, 2 bf16): of the next
+                                         // forward (yl_amp_*_set) and of the held one, which its backward runs in
 };
+// yl_amp_*_set / _get: the mode as the bits of the heads' flags (0, YL_HEAD_F16, YL_HEAD_BF16)
+inline uint32_t mode_bits(int mode) { return mode == 1 ? YL_HEAD_F16 : (mode == 2 ? YL_HEAD_BF16 : 0u); }
+inline int mode_of_bits(uint32_t bits) {                   // anything but the three values: -1
+  return bits == 0 ? 0 : (bits == YL_HEAD_F16 ? 1 : (bits == YL_HEAD_BF16 ? 2 : -1));
+}
+template <class H> yl_status units_amp_set(H* h, uint32_t bits) {
+  const int m = mode_of_bits(bits);
+  if (!h || m < 0) return YL_ERR_INVALID;
+  h->mode = m;                           // a held forward keeps fMode
+  return YL_OK;
+}
+template <class H> yl_status units_amp_get(const H* h, uint32_t* mode, uint32_t* held_mode) {
+  if (!h) return YL_ERR_INVALID;
+  if (mode) *mode = mode_bits(h->mode);
+  if (held_mode) *held_mode = h->mem.fValid ? mode_bits(h->fMode) : 0u;
+  return YL_OK;
+}
 template <class H, class Cfg> yl_status units_create(int device, const Cfg* cfg, bool cfg_ok, H** out) {
   if (!out || !cfg_ok) return YL_ERR_INVALID;
   if (hipSetDevice(device) != hipSuccess) return YL_ERR_HIP;
@@ -190,7 +210,7 @@ template <class P, class H>
 yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const float* x_dev, unsigned xmask, int batch, int size,
                         uint32_t flags, float* out_dev, void* stream, int32_t* launches) {
   if (!params_ok(par, npar)) return YL_ERR_INVALID;
-  if (flags & ~(uint32_t)(YL_HEAD_TRAIN | YL_HEAD_SAVE)) return YL_ERR_INVALID;       // fp32 only: no precision bits
+  if (flags & ~(uint32_t)(YL_HEAD_TRAIN | YL_HEAD_SAVE)) return YL_ERR_INVALID;       // no precision bits: yl_amp_*_set
   if (((uintptr_t)x_dev & xmask) || ((uintptr_t)out_dev & 15u)) return YL_ERR_UNSUPPORTED;
   const bool train = flags & YL_HEAD_TRAIN, save = flags & YL_HEAD_SAVE;
   Unit us[MAX_UNITS];
@@ -204,6 +224,7 @@ yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const f
   const yl_status st = units_reserve(h->mem, us, n, sz, P::ROT, save, &sb);
   if (st != YL_OK) return st;
   hipStream_t s = (hipStream_t)stream;
+  const int mode = h->mode;
   h->mem.fValid = 0;
   if (save && hipMemcpyAsync(sb.x, x_dev, (size_t)sz.x0, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
   int nl = 0;
@@ -222,7 +243,7 @@ yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const f
     else if (i == n - 1) hout = out_dev;
     else { out_i = pick(in_i, bin_i); hout = sb.nh[out_i]; }
     const int M = (int)u.Mout, F = u.cout;
-    nl += P::conv_forward(s, u, batch, in, e.w, z, sb);
+    nl += P::conv_forward(s, u, batch, in, e.w, z, sb, mode);
     if (train) {
       StatP sp;
       sp.a = z; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = sb.spart;
@@ -247,7 +268,7 @@ yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const f
   }
   if (launches) *launches = nl;
   if (hipGetLastError() != hipSuccess) return YL_ERR_HIP;
-  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->mem.fValid = 1; }
+  if (save) { h->fB = batch; h->fS = size; h->fTrain = train ? 1 : 0; h->fMode = mode; h->mem.fValid = 1; }
   return YL_OK;
 }
 
@@ -273,7 +294,7 @@ yl_status units_backward(H* h, const yl_stage_unit* const* par, const yl_stage_u
   if (gany & 3u) return YL_ERR_UNSUPPORTED;                // before the first launch: nothing of the caller's is written
   hipStream_t s = (hipStream_t)stream;
   const bool train = h->fTrain != 0;
-  const int B = h->fB;
+  const int B = h->fB, mode = h->fMode;  // the backward runs in the precision of its forward
   int nl = 0;
   const float* dh = gy_dev;
   int cur = -1;                          // the buffer dh is in (-1: the caller's gy)
@@ -308,11 +329,11 @@ yl_status units_backward(H* h, const yl_stage_unit* const* par, const yl_stage_u
     if (u.relu) launch_bn_bwd<true>(s, dh, sb.h[i], sb.z[i], sb.stats[i], sb.coef, e, dz, n4, F);
     else if constexpr (P::MIXED) launch_bn_bwd<false>(s, dh, sb.h[i], sb.z[i], sb.stats[i], sb.coef, e, dz, n4, F);
     ++nl;
-    if (g.w) nl += P::conv_wgrad(s, u, B, xin, dz, g.w, sb);
+    if (g.w) nl += P::conv_wgrad(s, u, B, xin, dz, g.w, sb, mode);
     if (!need_dx) break;
     const int d = pick(keep, t);
     float* dst = i ? sb.g[d] : dx_dev;
-    nl += P::conv_dgrad(s, u, B, dz, e.w, dst, sb);
+    nl += P::conv_dgrad(s, u, B, dz, e.w, dst, sb, mode);
     if constexpr (P::MIXED) {
       if (u.first && u.res) {            // the block's input also went straight to its output
         const long m4 = (long)u.Min * (u.cin >> 2);

@@ -1,7 +1,7 @@
 """A trainable backbone stage on the device: a stack of MobileNetV4 UIB blocks (timm's UniversalInvertedResidual) and
 1x1 ConvBnAct blocks, with a backward pass (csrc/yl_stage.hip).
 
-    UIBStack(in_channels, blocks, eps=1e-5, prefix="")     any such stack
+    UIBStack(in_channels, blocks, eps=1e-5, prefix="", precision="fp32")     any such stack
     BackboneTail.from_meta(meta) / .from_state_dict(meta, sd)   the backbone's last stage: its C4 tap -> its C5 tap
     BackboneMid.from_meta(meta) / .from_state_dict(meta, sd)    the stage between its C3 and its C4 tap
     MobileNetV4Backbone.from_meta(meta) / .from_state_dict(meta, sd)   image -> [c3, c4, c5]: stemops.BackboneStem, mid, tail
@@ -26,7 +26,12 @@ The whole stack is ONE torch.autograd.Function (_trainmod.UnitStackFunction, whi
 yl_stage_forward / yl_stage_backward.  train() / eval() select the
 BatchNorm mode.  Gradients nobody asked for are not computed, and nothing upstream of the first one wanted runs
 (`last_launches` says what ran).  One forward is held for backward at a time: a second forward before backward()
-replaces it, and the stale backward raises.  fp32 on one HIP device; no CPU fallback.  ReLU only: relu6, silu, TF-SAME
+replaces it, and the stale backward raises.  fp32 tensors on one HIP device; no CPU fallback.  precision="fp16" / "bf16"
+(constructor, from_meta / from_state_dict, or the settable `.precision`; MobileNetV4Backbone sets all three parts) runs the
+1x1 GEMMs (pw_exp, pw_proj, cn) of all three passes on 16-bit MFMA: operands rounded to nearest even inside the GEMM, fp32
+accumulation, nothing clamped.  Parameters, saved activations and gradients stay fp32, and so do the depthwise
+convolutions, BatchNorm, ReLU and the residual: unlike torch.autocast, which also runs the depthwise convolutions in 16
+bits.  A backward runs in the precision of its forward.  ReLU only: relu6, silu, TF-SAME
 padding, squeeze-excite and layer-scale are refused by name, as are the backbone families built from other blocks.
 """
 from __future__ import annotations
@@ -152,8 +157,8 @@ def plan(in_channels: int, blocks: Sequence[dict], batch: int, size: int, eps: f
             "workspace_bytes": int(out.workspace_bytes)}
 
 
-class _Handle(tm.DeviceHandle):
-    """The stack's handle (see _trainmod.DeviceHandle) and the order its tensors go to the library in"""
+class _Handle(tm.UnitStackHandle):
+    """The stack's handle (see _trainmod.UnitStackHandle) and the order its tensors go to the library in"""
     who = "UIBStack"
 
     def __init__(self, in_channels: int, blocks: List[dict], eps: float):
@@ -200,8 +205,9 @@ class UIBStack(tm.UnitStack):
     """See the module docstring."""
     _who, _handle_cls = "UIBStack", _Handle
 
-    def __init__(self, in_channels: int, blocks: Sequence[dict], eps: float = 1e-5, prefix: str = ""):
+    def __init__(self, in_channels: int, blocks: Sequence[dict], eps: float = 1e-5, prefix: str = "", precision: str = "fp32"):
         super().__init__()
+        self.precision = precision
         self.blocks_cfg = _check_blocks(in_channels, blocks, eps)
         self.in_channels, self.eps, self.prefix = int(in_channels), float(eps), str(prefix)
         self.out_channels = self.blocks_cfg[-1]["c"]
@@ -301,15 +307,16 @@ class BackboneTail(UIBStack):
     _who, _handle_cls = "BackboneTail", _TailHandle
 
     @classmethod
-    def from_meta(cls, meta: dict, start: str = "c4"):
+    def from_meta(cls, meta: dict, start: str = "c4", precision: str = "fp32"):
         """a freshly initialised tail of the model `meta` describes"""
+        tm.check_precision(precision)
         cin, blocks, eps = _tail_blocks(meta, start)
-        return cls(cin, blocks, eps=eps, prefix="backbone.")
+        return cls(cin, blocks, eps=eps, prefix="backbone.", precision=precision)
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict, start: str = "c4"):
+    def from_state_dict(cls, meta: dict, sd: dict, start: str = "c4", precision: str = "fp32"):
         """the tail of a checkpoint: built from its meta, filled with its `backbone.blocks.{si}.{bi}.` entries"""
-        return tm.fill_from_state_dict(cls.from_meta(meta, start), sd, "backbone tail")
+        return tm.fill_from_state_dict(cls.from_meta(meta, start, precision), sd, "backbone tail")
 
 
 def _mid_blocks(meta: dict):
@@ -366,13 +373,14 @@ class BackboneMid(UIBStack):
     _who, _handle_cls = "BackboneMid", _MidHandle
 
     @classmethod
-    def from_meta(cls, meta: dict):
+    def from_meta(cls, meta: dict, precision: str = "fp32"):
+        tm.check_precision(precision)
         cin, blocks, eps = _mid_blocks(meta)
-        return cls(cin, blocks, eps=eps, prefix="backbone.")
+        return cls(cin, blocks, eps=eps, prefix="backbone.", precision=precision)
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict):
-        return tm.fill_from_state_dict(cls.from_meta(meta), sd, "backbone C3 -> C4 stage")
+    def from_state_dict(cls, meta: dict, sd: dict, precision: str = "fp32"):
+        return tm.fill_from_state_dict(cls.from_meta(meta, precision), sd, "backbone C3 -> C4 stage")
 
 
 class MobileNetV4Backbone(nn.Module):
@@ -380,20 +388,41 @@ class MobileNetV4Backbone(nn.Module):
     C3), .mid (BackboneMid, C3 -> C4), .tail (BackboneTail, C4 -> C5).  backbone(x [B,3,S,S]) -> [c3, c4, c5] NHWC,
     smallest stride first: what neck(cs, layout="nhwc") takes.  torch sums the two gradients that arrive at C3 and at C4.
     Freezing is torch's own: backbone.stem.requires_grad_(False).eval(); nothing upstream of the first wanted gradient
-    runs.  state_dict() / load_state_dict() speak the checkpoint's key names (`backbone.conv_stem.weight`, ...)."""
+    runs.  state_dict() / load_state_dict() speak the checkpoint's key names (`backbone.conv_stem.weight`, ...).
+    `precision` (None: the parts keep theirs) and the settable `.precision` set the operand type of every dense GEMM of all
+    three parts; reading `.precision` while the parts differ raises."""
 
-    def __init__(self, stem: nn.Module, mid: nn.Module, tail: nn.Module):
+    def __init__(self, stem: nn.Module, mid: nn.Module, tail: nn.Module, precision: Optional[str] = None):
         super().__init__()
+        if precision is not None:
+            tm.check_precision(precision)
         self.stem, self.mid, self.tail = stem, mid, tail
+        if precision is not None:
+            self.precision = precision
+
+    @property
+    def precision(self) -> str:
+        ps = [p.precision for p in (self.stem, self.mid, self.tail)]
+        if len(set(ps)) != 1:
+            raise ValueError(f"the backbone's parts differ in precision: stem {ps[0]!r}, mid {ps[1]!r}, tail {ps[2]!r}")
+        return ps[0]
+
+    @precision.setter
+    def precision(self, value):
+        tm.check_precision(value)
+        for p in (self.stem, self.mid, self.tail):
+            p.precision = value
 
     @classmethod
-    def from_meta(cls, meta: dict):
+    def from_meta(cls, meta: dict, precision: str = "fp32"):
         from .stemops import BackboneStem
-        return cls(BackboneStem.from_meta(meta), BackboneMid.from_meta(meta), BackboneTail.from_meta(meta))
+        tm.check_precision(precision)
+        return cls(BackboneStem.from_meta(meta, precision), BackboneMid.from_meta(meta, precision),
+                   BackboneTail.from_meta(meta, precision=precision))
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict):
-        m = cls.from_meta(meta)
+    def from_state_dict(cls, meta: dict, sd: dict, precision: str = "fp32"):
+        m = cls.from_meta(meta, precision)
         m.load_state_dict(sd)
         return m
 

@@ -1,9 +1,10 @@
 """A trainable dense stem on the device: a stack of dense `conv -> BatchNorm -> ReLU` units with a backward pass
 (csrc/yl_stem.hip), the part of a MobileNetV4 backbone between the image and its C3 tap.
 
-    ConvStack(in_channels, units, eps=1e-5, prefix="", input_layout="nhwc")    any such stack
+    ConvStack(in_channels, units, eps=1e-5, prefix="", input_layout="nhwc", precision="fp32")    any such stack
     BackboneStem.from_meta(meta) / .from_state_dict(meta, sd)    conv_stem, stage 0 and stage 1: image -> C3
-    conv(a, b, pass_, k, stride, size=None, layout="nhwc")       one convolution pass on its own (yl_stem_conv)
+    conv(a, b, pass_, k, stride, size=None, layout="nhwc", precision=None)   one convolution pass on its own (yl_stem_conv,
+                                                                 with a precision yl_amp_stem_conv)
     plan(in_channels, units, batch, size, input_layout="nhwc")   yl_stem_plan: what the handle holds
 
     c3 = stem(x)                                           # x: the image [B,3,S,S]; c3: NHWC [B,S/8,S/8,C3]
@@ -19,7 +20,12 @@ gradient is computed when asked for.  The output is NHWC.
 The whole stack is ONE torch.autograd.Function (_trainmod.UnitStackFunction, which the backbone stage shares) over
 yl_stem_forward / yl_stem_backward.  train() / eval() select the
 BatchNorm mode.  Gradients nobody asked for are not computed, and nothing upstream of the first one wanted runs
-(`last_launches` says what ran).  One forward is held for backward at a time.  fp32 on one HIP device; no CPU fallback.
+(`last_launches` says what ran).  One forward is held for backward at a time.  fp32 tensors on one HIP device; no CPU
+fallback.  precision="fp16" / "bf16" (constructor, from_meta / from_state_dict, or the settable `.precision`) runs every
+dense GEMM, the 3x3 and the 1x1 convolutions of all three passes, on 16-bit MFMA: operands rounded to nearest even inside
+the launch that reads them, fp32 accumulation, nothing clamped (an fp16 overflow is inf).  Parameters, saved activations
+and gradients stay fp32, BatchNorm and ReLU too, and the launch counts are those of fp32.  A backward runs in the
+precision of its forward.
 ReLU only: the `_skip` residual, other activations and TF-SAME padding are refused by name, as are the backbone
 families whose first stages are built from other blocks.
 """
@@ -108,8 +114,8 @@ def plan(in_channels: int, units: Sequence[dict], batch: int, size: int, eps: fl
             "nosave_bytes": int(out.nosave_bytes), "workspace_bytes": int(out.workspace_bytes)}
 
 
-class _Handle(tm.DeviceHandle):
-    """The stack's handle (see _trainmod.DeviceHandle) and the order its tensors go to the library in"""
+class _Handle(tm.UnitStackHandle):
+    """The stack's handle (see _trainmod.UnitStackHandle) and the order its tensors go to the library in"""
     who = "ConvStack"
 
     def __init__(self, in_channels: int, units: List[dict], eps: float, nchw: bool):
@@ -135,8 +141,10 @@ class ConvStack(tm.UnitStack):
     """See the module docstring."""
     _who, _handle_cls = "ConvStack", _Handle
 
-    def __init__(self, in_channels: int, units: Sequence[dict], eps: float = 1e-5, prefix: str = "", input_layout: str = "nhwc"):
+    def __init__(self, in_channels: int, units: Sequence[dict], eps: float = 1e-5, prefix: str = "", input_layout: str = "nhwc",
+                 precision: str = "fp32"):
         super().__init__()
+        self.precision = precision
         self.units_cfg = _check_units(in_channels, units, eps, input_layout)
         self.in_channels, self.eps, self.prefix = int(in_channels), float(eps), str(prefix)
         self.input_layout = input_layout
@@ -227,24 +235,29 @@ class BackboneStem(ConvStack):
     _who, _handle_cls = "BackboneStem", _StemHandle
 
     @classmethod
-    def from_meta(cls, meta: dict):
+    def from_meta(cls, meta: dict, precision: str = "fp32"):
+        tm.check_precision(precision)
         units, eps = _stem_units(meta)
-        return cls(3, units, eps=eps, prefix="backbone.", input_layout="nchw")
+        return cls(3, units, eps=eps, prefix="backbone.", input_layout="nchw", precision=precision)
 
     @classmethod
-    def from_state_dict(cls, meta: dict, sd: dict):
-        return tm.fill_from_state_dict(cls.from_meta(meta), sd, "backbone stem")
+    def from_state_dict(cls, meta: dict, sd: dict, precision: str = "fp32"):
+        return tm.fill_from_state_dict(cls.from_meta(meta, precision), sd, "backbone stem")
 
 
 def conv(a: torch.Tensor, b: torch.Tensor, pass_: str, k: int, stride: int, size: Optional[int] = None,
-         layout: str = "nhwc") -> torch.Tensor:
+         layout: str = "nhwc", precision: Optional[str] = None) -> torch.Tensor:
     """One convolution pass of the stack on its own (yl_stem_conv, launched as the module launches it), fp32 tensors on
     one HIP device, pad (k - 1) / 2, So = (S + 2 pad - k) / stride + 1:
         "forward":  x  [B,S,S,cin],     W  [cout,cin,k,k]    -> y  [B,So,So,cout]
         "dgrad":    dy [B,So,So,cout],  W  [cout,cin,k,k]    -> dx [B,S,S,cin]       the gradient of forward's x
         "wgrad":    x  [B,S,S,cin],     dy [B,So,So,cout]    -> dW [cout,cin,k,k]    the gradient of forward's W
     layout="nchw": x is the planar image [B,cin,S,S], cin in 1..4 ("forward" and "wgrad" only).  `size`: S of "dgrad",
-    which So does not determine under stride 2 (stride 1: S = So).  The weight may start at any 4-byte boundary."""
+    which So does not determine under stride 2 (stride 1: S = So).  The weight may start at any 4-byte boundary.
+    `precision`: None is yl_stem_conv (fp32); "fp32", "fp16", "bf16" go through yl_amp_stem_conv: both operands rounded to
+    nearest even inside the launches, fp32 accumulation, an fp32 result."""
+    if precision is not None:
+        tm.check_precision(precision)
     if pass_ not in PASSES:
         raise ValueError(f"pass_ must be one of {sorted(PASSES)}, got {pass_!r}")
     if layout not in ("nhwc", "nchw"):
@@ -298,9 +311,14 @@ def conv(a: torch.Tensor, b: torch.Tensor, pass_: str, k: int, stride: int, size
     out = torch.empty(shape, device=a.device, dtype=torch.float32)
     n = C.c_int32()
     with torch.cuda.device(a.device):
-        _lib.check(lib.yl_stem_conv(a.data_ptr(), b.data_ptr(), out.data_ptr(), PASSES[pass_], k, stride, B, S, cin, cout,
-                                    int(nchw), torch.cuda.current_stream(a.device).cuda_stream, C.byref(n)),
-                   what="yl_stem_conv")
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        if precision is None:
+            _lib.check(lib.yl_stem_conv(a.data_ptr(), b.data_ptr(), out.data_ptr(), PASSES[pass_], k, stride, B, S, cin, cout,
+                                        int(nchw), stream, C.byref(n)), what="yl_stem_conv")
+        else:
+            _lib.check(lib.yl_amp_stem_conv(a.data_ptr(), b.data_ptr(), out.data_ptr(), PASSES[pass_], k, stride, B, S, cin,
+                                            cout, int(nchw), tm.PRECISIONS[precision], stream, C.byref(n)),
+                       what="yl_amp_stem_conv")
     conv.last_launches = int(n.value)
     return out
 
