@@ -327,6 +327,16 @@ int32_t yl_query_fused_block(int32_t c_in, int32_t c_mid, int32_t c_out, int32_t
  * 4x4-tileable output -- tf_efficientnet_lite stages 4-6), 1: the generic depthwise-prologue kernels do (taps + bias of all
  * channels within 32 KiB of LDS), 0: no -- emit the depthwise conv as its own YL_OP_DW layer.                          */
 int32_t yl_query_dw_prologue(int32_t c_in, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t out_h, int32_t out_w);
+/* Host-side query (additive to ABI v7), no device needed: which Winograd F(2x2,3x3) kernel form runs a dense 3x3 stride-1 pad-1 conv c_in -> c_out
+ * with an out_h x out_w output on `batch` images per launch (in_shift 1: the input is read nearest-upsampled by 2) under
+ * option "winograd" 1 and the given "dev_select" value (bit 11, bits 12-13)?  0: none (the direct kernels run it), 1: the
+ * first form (yl_conv_wino_kernel: every transform position in one wave), 2: the position-split form
+ * (yl_conv_wino2_kernel) with *mt m-tiles x *nt n-tiles per item (mt / nt may be NULL; they are 0 unless 2 is returned).
+ * Only layers whose output grid equals their (virtual) input grid carry a Winograd image, so out_h x out_w is also the size
+ * of the tensor the kernels read.  The launcher takes the same decision from the same function; the tests ask which
+ * instantiation a case ran.                                                                                              */
+int32_t yl_query_wino_form(int32_t c_in, int32_t c_out, int32_t out_h, int32_t out_w, int32_t batch, int32_t in_shift,
+                           int32_t dev_select, int32_t* mt, int32_t* nt);
 
 /* ---- pre-processing ----------------------------------------------------------------------------
  * Replaces letterbox() + cv2.cvtColor + /255 + (x-mean)/std + transpose of tools/infer.py:121-131,446-453

@@ -1449,6 +1449,21 @@ int32_t yl_query_dw_prologue(int32_t c_in, int32_t c_out, int32_t dw_k, int32_t 
   return 0;
 }
 
+int32_t yl_query_wino_form(int32_t c_in, int32_t c_out, int32_t out_h, int32_t out_w, int32_t batch, int32_t in_shift,
+                           int32_t dev_select, int32_t* mt, int32_t* nt) {
+  if (mt) *mt = 0;
+  if (nt) *nt = 0;
+  // the channel conditions under which a layer carries a Winograd image (yl_program.cpp), then the launcher's own decision
+  if (c_in < 16 || c_out < 16 || (c_in & 3) || (c_out & 3)) return 0;
+  const unsigned dev = (unsigned)dev_select;
+  const YlWinoForm f = yl_wino_form(c_in, c_out, out_h, out_w, batch, in_shift, sizeof(float), (dev & YL_DEV_WINO_V1) != 0, YL_DEV_WINO_SHAPE(dev));
+  if (f.form == 2) {
+    if (mt) *mt = f.mt;
+    if (nt) *nt = f.nt;
+  }
+  return f.form;
+}
+
 static yl_status forward_impl(yl_ctx* c, const float* x, int B, float* const* level_out, hipStream_t st,
                               float* layer_ms, const yl_post_cfg* cfg, float* dets, int* counts, int* keep_idx = nullptr) {
   if (!c) return YL_ERR_INVALID;

@@ -3179,8 +3179,7 @@ __global__ __launch_bounds__(512, 2) void yl_conv_wino2_kernel(YlConvP p) {
   }
 }
 
-// instantiated: (m-tiles, n-tiles per item), each for a plain and a 2x upsampled input (in_shift)
-#define YL_WINO2_SHAPES(X) X(4, 3) X(4, 4) X(2, 3) X(2, 4) X(2, 7)
+// instantiated: YL_WINO2_SHAPES (yl_shapes.h: (m-tiles, n-tiles per item)), each for a plain and a 2x upsampled input (in_shift)
 static YlConvKernel wino2_kernel_of(int MT, int NT, int in_shift) {
 #define YL_WINO2_PICK(A, B) if (MT == A && NT == B) return in_shift ? yl_conv_wino2_kernel<A, B, 1> : yl_conv_wino2_kernel<A, B, 0>;
   YL_WINO2_SHAPES(YL_WINO2_PICK)
@@ -3202,30 +3201,12 @@ static hipError_t wino2_go(const YlConvP& p0, hipStream_t st, int MT, int NT) {
 // dense 3x3 stride-1 pad-1 layers that carry a Winograd image (yl_api.hip builds it for >= 64 channels, plain
 // ReLU-family epilogue; layer_params hands it over only under option "winograd").
 hipError_t yl_launch_conv_wino(const YlConvP& p, hipStream_t st) {
-  if (!p.wino || p.k != 3 || p.stride != 1 || p.dw_k > 0 || p.up || p.dec_boxes || p.C1 > 0 || (p.N & 3) || p.w3p || p.scale ||
-      p.in_shift > 1 || ((size_t)p.B * (p.H >> p.in_shift) * (p.W >> p.in_shift) * p.Cin + (size_t)(p.W + 1) * p.Cin) * sizeof(yl_act_t) >= ((size_t)1 << 31))
-    return hipErrorNotSupported;                            // (32-bit byte offsets: both forms read through buffer descriptors)
-  // second form (positions across the waves): K loops long enough to amortise the accumulator exchange, grids that fill
-  // the 4 x 4-tile m-tiles; "dev_select" bit 11 keeps the first form (bitwise A/B), bits 12-13 pick a shape (A/B runs)
-  // (second form: 32-bit byte offsets into the input tensor and the U image)
-  const bool small = (size_t)p.B * (p.H >> p.in_shift) * (p.W >> p.in_shift) * p.Cin * sizeof(yl_act_t) < ((size_t)1 << 31) &&
-                     (size_t)((p.NTtot + 1) / 2) * p.KB * 32768 < ((size_t)1 << 31);
-  if (!(p.dev & YL_DEV_WINO_V1) && p.KB >= 2 && p.NTtot >= 3 && small) {   // (KB >= 2: the peeled last two blocks)
-    const int TW = (p.OW + 1) >> 1, TH = (p.OH + 1) >> 1;
-    const int MX = (TW + 3) >> 2, MY = (TH + 3) >> 2;
-    const long MTOT = (long)p.B * MX * MY;
-    if ((long)TW * TH * 100 >= (long)MX * MY * 16 * 65) {         // >= 65 % of the m-tiles' Winograd tiles exist (20 x 20: 69 %, 0.232 -> 0.205 ms)
-      const int pad3 = (p.NTtot + 2) / 3 * 3, pad4 = (p.NTtot + 3) / 4 * 4;
-      int nt = pad3 <= pad4 ? 3 : 4;
-      // 4 m-tiles halve the U bytes per MFMA (80 x 80: 1.79 against 1.95 ms) when there are >= 3 items per CU; with 4
-      // n-tiles that shape spills (2 x 4 x 4 accumulator quads + two U register sets)
-      int mt = nt == 3 && (MTOT / 4) * ((p.NTtot + nt - 1) / nt) >= 3 * YL_NUM_CU ? 4 : 2;
-      const unsigned v = YL_DEV_WINO_SHAPE(p.dev);
-      if (v == 1) { mt = 4; nt = 4; } else if (v == 2) { mt = 2; nt = 7; } else if (v == 3) { mt = 2; }
-      if (wino2_kernel_of(mt, nt, 0)) return wino2_go(p, st, mt, nt);
-    }
-  }
-  return wino_go(p, st);
+  if (!p.wino || p.k != 3 || p.stride != 1 || p.dw_k > 0 || p.up || p.dec_boxes || p.C1 > 0 || p.w3p || p.scale) return hipErrorNotSupported;
+  // first form or second form with (m-tiles, n-tiles) per item: yl_wino_form (yl_shapes.h), which yl_query_wino_form reports
+  const YlWinoForm f = yl_wino_form(p.Cin, p.N, p.OH, p.OW, p.B,   // (p.OH x p.OW is also the virtual input grid p.H x p.W: a layer carries p.wino only then, yl_program.cpp)
+                                    p.in_shift, sizeof(yl_act_t), (p.dev & YL_DEV_WINO_V1) != 0, YL_DEV_WINO_SHAPE(p.dev));
+  if (f.form == 0) return hipErrorNotSupported;
+  return f.form == 2 ? wino2_go(p, st, f.mt, f.nt) : wino_go(p, st);
 }
 
 // ------------------------------------------------------------------------------------------------

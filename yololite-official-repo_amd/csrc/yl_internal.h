@@ -8,9 +8,8 @@
 #include <utility>
 #include "../../include/yololite_hip.h"
 #include "yl_lp.h"
-#include "yl_shapes.h"   // yl_stemblock_supported, yl_uib_supported, yl_ir_supported, yl_dws_supported
+#include "yl_shapes.h"   // YL_NUM_CU, yl_stemblock_supported, yl_uib_supported, yl_ir_supported, yl_dws_supported, yl_wino_form
 
-#define YL_NUM_CU 256          // MI355X: 8 XCDs x 32 CUs
 #define YL_LDS_KEYS_MAX 16384  // 64-bit sort keys that fit the 160 KiB LDS of one CU (128 KiB)
 
 // ---- detection-level geometry handed to the post-processing kernels by value -------------------

@@ -278,7 +278,8 @@ yl_status check_layer(const yl_model_desc* d, YlProgram& p, int i, std::vector<i
   if (l.op != YL_OP_CONV) return YL_OK;
   // the optional images of a conv layer, and the chained 1x1 [c3][cout][1][1] (its k-blocks are this conv's 16-wide n-tiles)
   L.wino = l.k == 3 && l.stride == 1 && l.dw_k == 0 && l.c2 == 0 && l.c3 == 0 && l.pad_t == 1 && l.pad_l == 1 && l.in_shift <= 1 &&
-           l.cin >= 16 && l.cout >= 16 && (l.cout & 3) == 0 && l.head_level < 0 && l.up_slot < 0;
+           l.cin >= 16 && l.cout >= 16 && (l.cout & 3) == 0 && l.head_level < 0 && l.up_slot < 0 &&
+           L.out_h == L.in_h && L.out_w == L.in_w;   // the output grid IS the (virtual) input grid: yl_wino_form sizes its 32-bit offsets by it
   if (L.wino && l.cin >= 64 && l.cout >= 64 && L.out_h * L.out_w > p.wino_max_hw) p.wino_max_hw = L.out_h * L.out_w;
   L.split_head = l.head_level >= 0 && p.NM > 0 && (p.NM & 3) == 0 && l.k == 1 && l.dw_k == 0 && l.c2 == 0 && l.c3 == 0 &&
                  5 + p.C <= 96 && l.cout == p.E && p.level_A[l.head_level] == 1;
