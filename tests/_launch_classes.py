@@ -7,14 +7,15 @@ census: every label a MODEL_ZOO model reaches in training must be reached by a p
 _*_cases.py files) or, for the GEMM and the depthwise kernels, by an op-level test shape.
 
 Restated (re-derive when the C++ changes):
-    csrc/yl_block.h    pick_pt, pick_cq, split_plan, STAT_ROWS = 256, GEMM_ROWS = 64, NT = 256; the launches of
-                       blocks_forward / blocks_backward
+    csrc/yl_bn.h       pick_cq, STAT_ROWS = 256, NT = 256; the launches of bn_forward / bn_backward_sums, which every walk
+                       below goes through with its activation
+    csrc/yl_block.h    pick_pt, split_plan, GEMM_ROWS = 64; the launches of blocks_forward / blocks_backward
     csrc/yl_head.hip   the three output GEMMs, column sums over 64 columns per workgroup
     csrc/yl_fpn.h      the lateral's three GEMMs and its bias sums
     csrc/yl_dneck.hip  CT = 8, CNB = 64, GB = 64, CKB = 16 (32 in the 16x16x32 forms), w3_split
     csrc/yl_stage.hip  make_units, the depthwise weight gradient per (k, stride)
     csrc/yl_stem.hip   pick_conv_pt, ST_T = 8, GC = 32, GN = 64, wgrad3_plan, stat_rows_of
-    csrc/yl_units.h    the walk: forward statistics, backward sums with or without the ReLU mask
+    csrc/yl_units.h    the walk: which activation a unit's BatchNorm runs with
 The axes are independent: a label says one thing about one launch, never a combination."""
 NT = 256
 STAT_ROWS = 256
@@ -32,12 +33,7 @@ def r16(v):
     return (v + 15) // 16 * 16
 
 
-# ---- csrc/yl_block.h
-
-def pick_pt(NP):
-    """p-tiles per wave: 4 (64 columns) or 6 (96), whichever pads NP less"""
-    return 6 if cdiv(NP, 96) * 96 < cdiv(NP, 64) * 64 else 4
-
+# ---- csrc/yl_bn.h
 
 def pick_cq(F):
     """channel quads per workgroup of the row reductions: a power of two <= 64"""
@@ -45,6 +41,13 @@ def pick_cq(F):
     while cq < (F >> 2) and cq < 64:
         cq <<= 1
     return cq
+
+
+# ---- csrc/yl_block.h
+
+def pick_pt(NP):
+    """p-tiles per wave: 4 (64 columns) or 6 (96), whichever pads NP less"""
+    return 6 if cdiv(NP, 96) * 96 < cdiv(NP, 64) * 64 else 4
 
 
 def split_plan(M, NP, NQ, gemm_rows=GEMM_ROWS):
@@ -134,11 +137,19 @@ def per_channel(src, n):
     return {(src, "-", "workgroups", "1" if cdiv(n, NT) == 1 else ">=2")}
 
 
+def batchnorm(act, M, F, stat_rows=STAT_ROWS):
+    """bn_forward + bn_backward_sums of csrc/yl_bn.h over M rows of F channels: the column sums of both passes and the two
+    second stages.  The activation is a template argument that the cut into tiles and groups does not depend on: an axis
+    of its own"""
+    out = rows("bn_colstats", "fwd", M, F, stat_rows) | rows("bn_colstats", "bwd", M, F, stat_rows)
+    out.add(("bn_colstats", "bwd", "act", act))
+    return out | per_channel("bn_stats", F) | per_channel("bn_grads", F)
+
+
 def _blocks(M, F):
     """a run of DWConvBlocks of yl_block.h at M rows: blocks_forward + blocks_backward with every gradient wanted"""
     out = gemm("gemm", "forward", F, M, F) | gemm("gemm", "dgrad", F, M, F) | wgrad_gemm("gemm", F, F, M)
-    out |= rows("head_colstats", "fwd", M, F) | rows("head_colstats", "bwd", M, F) | rows("head_dw_wgrad", "bwd", M, F)
-    out |= per_channel("head_bn_stats", F) | per_channel("head_bn_grads", F) | per_channel("head_dw_wsum", 9 * F)
+    out |= batchnorm("relu", M, F) | rows("head_dw_wgrad", "bwd", M, F) | per_channel("head_dw_wsum", 9 * F)
     out |= per_channel("head_wsum", F * F)
     return out
 
@@ -221,8 +232,7 @@ def dense_neck_labels(Cin, F, depth, B, sizes):
         M = B * S * S
         out |= _lateral(M, ci, F)
         out |= dense_conv("forward", F) | dense_conv("dgrad", F) | dense_wgrad(F, S, B)
-        out |= rows("head_colstats", "fwd", M, F) | rows("dneck_colstats_silu", "bwd", M, F)
-        out |= per_channel("head_bn_stats", F) | per_channel("head_bn_grads", F)
+        out |= batchnorm("silu", M, F)
         out |= per_channel("dneck_pack", 9 * F * F) | per_channel("dneck_wsum", 9 * F * F)
     return out
 
@@ -270,13 +280,8 @@ def dw_labels(k, s, Mo, C):
 
 
 def _unit_tail(u, stat_rows=STAT_ROWS):
-    """what yl_units.h's walk launches around a unit's convolution.  The row reductions of the stage and of the stem are one
-    body (YL_COLSTATS_BODY of csrc/yl_bn.h; the stem's takes its rows per tile as an argument); the ReLU mask of its
-    backward form is a template argument that the cut into tiles and groups does not depend on: an axis of its own"""
-    M, F = u["M"], u["cout"]
-    out = rows("bn_colstats", "fwd", M, F, stat_rows) | rows("bn_colstats", "bwd", M, F, stat_rows)
-    out.add(("bn_colstats", "bwd", "mask", "relu" if u["relu"] else "none"))
-    return out | per_channel("stage_bn_stats", F) | per_channel("head_bn_grads", F)
+    """what yl_units.h's walk launches around a unit's convolution (the stem's row reductions take more rows per tile)"""
+    return batchnorm("relu" if u["relu"] else "none", u["M"], u["cout"], stat_rows)
 
 
 def stage_labels(cin, blocks, B, S):

@@ -56,10 +56,10 @@ UNITS = [   # (source, extra flags, object name)
     ("yl_dneck.hip", ["-ffp-contract=off"], "yl_dneck.o"),
     # trainable backbone stage (MobileNetV4 UIB blocks): depthwise k x k with stride in three passes and the residual's add;
     # the 1x1 convolutions are the heads' GEMM (yl_block.h).  The walk over its conv + BatchNorm units, forward and backward,
-    # is yl_units.h and the BatchNorm kernels are yl_bn.h, both shared with yl_stem.hip
+    # is yl_units.h, shared with yl_stem.hip; BatchNorm is yl_bn.h, the bottom header of all five training units
     ("yl_stage.hip", ["-ffp-contract=off"], "yl_stage.o"),
     # trainable dense stem (image -> C3): dense 3x3 convolution with stride in three passes on fp32 (or fp16 / bf16) MFMA, strided 1x1 units on
-    # the heads' GEMM; the unit walk (yl_units.h) and BatchNorm + ReLU (yl_bn.h) are the ones yl_stage.hip runs
+    # the heads' GEMM; the unit walk is yl_units.h (the one yl_stage.hip runs) and BatchNorm + ReLU is yl_bn.h
     ("yl_stem.hip", ["-ffp-contract=off"], "yl_stem.o"),
 ]
 DEPS = ["yl_internal.h", "yl_shapes.h", "yl_program.h", "yl_dev.h", "yl_lp.h", "yl_epi.h", "yl_decode.h", "yl_block.h", "yl_bn.h", "yl_units.h", "yl_fpn.h", os.path.join("..", "..", "include", "yololite_hip.h")]

@@ -3,28 +3,19 @@
 // blocks forward and backward, and the host side every trainable handle has: its device memory (Arena), the cut of a run
 // of blocks out of it, and the checks of the parameter and gradient tables.  Everything lives in an anonymous namespace:
 // each translation unit that includes this header compiles the kernels it launches into its own code object.
+// BatchNorm + ReLU, kernels and launch sequences, is yl_bn.h's, and so are the primitives (f32x4, ld4 / st4, NT, ceil_div).
 //
 //   block t:  d = dw3x3(x)   z = d . W1^T   h = relu(gamma * (z - mean) * invstd + beta)     (d, z, h are kept for backward)
 #ifndef YL_BLOCK_H
 #define YL_BLOCK_H
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
 #include <string.h>
 
 #include "../../include/yololite_hip.h"
+#include "yl_bn.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int NT = 256;
-constexpr int STAT_ROWS = 256;           // rows of one tile of the row reductions
 constexpr int GEMM_ROWS = 64;            // q extent of one GEMM workgroup (four waves of 16)
-constexpr double BN_EPS = 1e-5, BN_MOMENTUM = 0.1;
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
 // ---- the 16-bit MFMA operands: a lane's four k values as one 8-byte fragment (v_mfma_f32_16x16x16_f16 / _bf16, fp32
 // accumulation).  __builtin_convertvector from f32x4 rounds to nearest even; nothing is clamped.
@@ -232,56 +223,9 @@ __global__ __launch_bounds__(NT) void yl_head_dw_kernel(const float* __restrict_
   st4(out + (long)m * F + c, acc);
 }
 
-// ---- row reductions.  Workgroup (tile of STAT_ROWS rows, group of CQ channel quads); thread t: quad t % CQ, rows
-// m0 + t / CQ, + 256 / CQ, ...; float64 sums per thread, summed over the row lanes in lane order by the thread of lane 0.
-struct StatP {
-  const float *a, *h, *z, *stats;        // forward: a = z.  backward: a = dh, h = the block's output (ReLU mask), z, stats
-  double* part;                          // [tile][2][F]
-  int M, F, CQ, bwd;
-};
-__global__ __launch_bounds__(NT) void yl_head_colstats_kernel(StatP P) {
-  __shared__ double red[NT][8];
-  const int t = threadIdx.x, cq = t & (P.CQ - 1), rs = t / P.CQ, RS = NT / P.CQ;
-  const int c = (blockIdx.y * P.CQ + cq) * 4, F = P.F;
-  const bool on = c < F;
-  const int m0 = blockIdx.x * STAT_ROWS, m1 = m0 + STAT_ROWS < P.M ? m0 + STAT_ROWS : P.M;
-  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
-  if (on) {
-    f32x4 mu = {0.f, 0.f, 0.f, 0.f}, is = mu;
-    if (P.bwd) { mu = ld4(P.stats + c); is = ld4(P.stats + F + c); }
-    for (int m = m0 + rs; m < m1; m += RS) {
-      const long o = (long)m * F + c;
-      const f32x4 a = ld4(P.a + o);
-      if (!P.bwd) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { s0[e] += (double)a[e]; s1[e] += (double)a[e] * (double)a[e]; }
-      } else {
-        const f32x4 hv = ld4(P.h + o), zv = ld4(P.z + o);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const double g = hv[e] > 0.f ? (double)a[e] : 0.0;
-          const double xh = ((double)zv[e] - (double)mu[e]) * (double)is[e];
-          s0[e] += g; s1[e] += g * xh;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { red[t][e] = s0[e]; red[t][4 + e] = s1[e]; }
-  __syncthreads();
-  if (rs == 0 && on) {
-    for (int k = 1; k < RS; ++k)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[t][e] += red[k * P.CQ + cq][e];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      P.part[((long)blockIdx.x * 2 + 0) * F + c + e] = red[t][e];
-      P.part[((long)blockIdx.x * 2 + 1) * F + c + e] = red[t][4 + e];
-    }
-  }
-}
-
-// depthwise weight gradient partials: part[tile][ky * 3 + kx][F] = sum over the tile's rows of dd[m][c] * x[m + tap][c]
+// ---- depthwise weight gradient partials: part[tile][ky * 3 + kx][F] = sum over the tile's rows of dd[m][c] * x[m + tap][c].
+// A row reduction in the tiling of yl_bn_colstats_kernel (yl_bn.h): workgroup (tile of STAT_ROWS rows, group of CQ channel
+// quads); float64 sums per thread, summed over the row lanes in lane order by the thread of lane 0.
 __global__ __launch_bounds__(NT) void yl_head_dw_wgrad_kernel(const float* __restrict__ dd, const float* __restrict__ x,
                                                              double* __restrict__ part, int M, int S, int F, int CQ) {
   __shared__ double red[NT][12];
@@ -339,45 +283,6 @@ __global__ __launch_bounds__(NT) void yl_head_ysum_kernel(const float* __restric
 }
 
 // ---- second stages: one thread per output element, the partials summed in tile order in float64
-struct BnFwdP {
-  const double* part; int tiles, M, F, train;
-  float *rm, *rv; int64_t* nbt;          // running statistics (train: updated in place)
-  float* stats;                          // [2][F]: mean, invstd of this call
-};
-__global__ __launch_bounds__(NT) void yl_head_bn_stats_kernel(BnFwdP P) {
-  const int c = blockIdx.x * NT + threadIdx.x;
-  if (c >= P.F) return;
-  if (!P.train) {                        // eval: the running statistics
-    P.stats[c] = P.rm[c];
-    P.stats[P.F + c] = (float)(1.0 / sqrt((double)P.rv[c] + BN_EPS));
-    return;
-  }
-  double s0 = 0, s1 = 0;
-  for (int t = 0; t < P.tiles; ++t) { s0 += P.part[((long)t * 2) * P.F + c]; s1 += P.part[((long)t * 2 + 1) * P.F + c]; }
-  const double mean = s0 / P.M;
-  double var = s1 / P.M - mean * mean;
-  var = var > 0 ? var : 0;
-  P.stats[c] = (float)mean;
-  P.stats[P.F + c] = (float)(1.0 / sqrt(var + BN_EPS));
-  P.rm[c] = (float)((1.0 - BN_MOMENTUM) * (double)P.rm[c] + BN_MOMENTUM * mean);
-  P.rv[c] = (float)((1.0 - BN_MOMENTUM) * (double)P.rv[c] + BN_MOMENTUM * (var * P.M / (P.M - 1)));
-  if (c == 0) *P.nbt += 1;
-}
-struct BnBwdP {
-  const double* part; int tiles, M, F, train;
-  float *dgamma, *dbeta;                 // NULL: not wanted
-  float* coef;                           // [2][F]: dbeta / M, dgamma / M (zero in eval mode)
-};
-__global__ __launch_bounds__(NT) void yl_head_bn_grads_kernel(BnBwdP P) {
-  const int c = blockIdx.x * NT + threadIdx.x;
-  if (c >= P.F) return;
-  double s0 = 0, s1 = 0;
-  for (int t = 0; t < P.tiles; ++t) { s0 += P.part[((long)t * 2) * P.F + c]; s1 += P.part[((long)t * 2 + 1) * P.F + c]; }
-  if (P.dbeta) P.dbeta[c] = (float)s0;
-  if (P.dgamma) P.dgamma[c] = (float)s1;
-  P.coef[c] = P.train ? (float)(s0 / P.M) : 0.f;
-  P.coef[P.F + c] = P.train ? (float)(s1 / P.M) : 0.f;
-}
 __global__ __launch_bounds__(NT) void yl_head_dw_wsum_kernel(const double* __restrict__ part, int tiles, int F,
                                                             float* __restrict__ out) {
   const int idx = blockIdx.x * NT + threadIdx.x;          // k * F + c
@@ -410,48 +315,9 @@ __global__ __launch_bounds__(NT) void yl_head_bsum_kernel(const double* __restri
   if (k == 0 ? hw.box_b != nullptr : (k == 1 ? hw.obj_b != nullptr : hw.cls_b != nullptr)) *hw.bias(n) = (float)s;
 }
 
-// ---- element-wise: h = relu(gamma * (z - mean) * invstd + beta);  dz = gamma * invstd * (g - c0 - xhat * c1), g = dh * [h > 0]
-__global__ __launch_bounds__(NT) void yl_head_bn_relu_kernel(const float* __restrict__ z, const float* __restrict__ stats,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            float* __restrict__ h, long n4, int F) {
-  const long idx = (long)blockIdx.x * NT + threadIdx.x;
-  if (idx >= n4) return;
-  const int c = (int)((idx * 4) % F);
-  const f32x4 v = ld4(z + idx * 4), mu = ld4(stats + c), is = ld4(stats + F + c);
-  f32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) o[e] = fmaxf((v[e] - mu[e]) * is[e] * gamma[c + e] + beta[c + e], 0.f);
-  st4(h + idx * 4, o);
-}
-// dh and dz may be one buffer (each thread reads its four values before it writes them): neither is __restrict__
-__global__ __launch_bounds__(NT) void yl_head_bn_bwd_kernel(const float* dh, const float* __restrict__ h,
-                                                           const float* __restrict__ z, const float* __restrict__ stats,
-                                                           const float* __restrict__ coef, const float* __restrict__ gamma,
-                                                           float* dz, long n4, int F) {
-  const long idx = (long)blockIdx.x * NT + threadIdx.x;
-  if (idx >= n4) return;
-  const int c = (int)((idx * 4) % F);
-  const f32x4 g = ld4(dh + idx * 4), hv = ld4(h + idx * 4), zv = ld4(z + idx * 4);
-  const f32x4 mu = ld4(stats + c), is = ld4(stats + F + c), c0 = ld4(coef + c), c1 = ld4(coef + F + c);
-  f32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float ge = hv[e] > 0.f ? g[e] : 0.f;
-    const float xh = (zv[e] - mu[e]) * is[e];
-    o[e] = gamma[c + e] * is[e] * (ge - c0[e] - xh * c1[e]);
-  }
-  st4(dz + idx * 4, o);
-}
-
-int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 int pick_pt(int NP) {                    // p-tiles per wave: 4 (64 columns) or 6 (96), whichever pads NP less
   const int w4 = ceil_div(NP, 64) * 64, w6 = ceil_div(NP, 96) * 96;
   return w6 < w4 ? 6 : 4;
-}
-int pick_cq(int F) {                     // channel quads per workgroup of the row reductions: a power of two <= 64
-  int cq = 1;
-  while (cq < (F >> 2) && cq < 64) cq <<= 1;
-  return cq;
 }
 // rows per split and number of splits of a weight-gradient GEMM with NP x NQ outputs over M rows: about 1024 workgroups
 void split_plan(int M, int NP, int NQ, int* rows, int* splits) {
@@ -584,6 +450,12 @@ inline bool blocks_grads_wanted(const yl_head_block* grads, int D, uintptr_t* bi
   return any != 0;
 }
 
+// block t's BatchNorm over the run's rows; its statistics are those of slot k of the buffers
+inline BnLayer bn_of(const yl_head_block& b, const BlockDims& dm, const Buffers& bf, int k) {
+  return {dm.M, dm.F, STAT_ROWS, dm.stat_tiles, b.gamma, b.beta, b.running_mean, b.running_var, b.num_batches_tracked, BN_EPS,
+          bf.stats[k], bf.spart};
+}
+
 // Blocks 0 .. D - 1 on `in`: per block 4 launches (5 with `train`).  `save` keeps every block's d, z, h apart; without it
 // every block runs in the first block's buffers.  The last block's output goes to `last_out` if that is given.
 // `mode`: the operand type of the 1x1 GEMM (0 with AMP = false).  -> where the last block's output is
@@ -591,8 +463,7 @@ template <bool AMP>
 const float* blocks_forward(hipStream_t s, const yl_head_block* blocks, int D, const float* in, const Buffers& bf,
                             bool save, bool train, int mode, const BlockDims& dm, float* last_out, int* launches) {
   const int M = dm.M, S = dm.S, F = dm.F;
-  const long n4 = (long)M * (F >> 2);
-  const int eg = ceil_div(n4, NT), cq = pick_cq(F);
+  const int eg = ceil_div((long)M * (F >> 2), NT);
   int nl = 0;
   for (int t = 0; t < D; ++t) {
     const int k = save ? t : 0;          // nothing is kept without `save`: every block runs in the first block's buffers
@@ -600,21 +471,7 @@ const float* blocks_forward(hipStream_t s, const yl_head_block* blocks, int D, c
     float* hout = (t == D - 1 && last_out) ? last_out : bf.h[k];
     hipLaunchKernelGGL(yl_head_dw_kernel<false>, dim3(eg), dim3(NT), 0, s, in, (const float*)b.dw, bf.d[k], M, S, F);
     launch_gemm_in<AMP>(mode, s, RowsScalar{b.pw, F}, RowsVec{bf.d[k], F}, OutRowsVec{bf.z[k], F}, F, M, F, F, 1);
-    nl += 2;
-    if (train) {
-      StatP sp;
-      sp.a = bf.z[k]; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = bf.spart;
-      sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 0;
-      hipLaunchKernelGGL(yl_head_colstats_kernel, dim3(dm.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
-      ++nl;
-    }
-    BnFwdP bp;
-    bp.part = bf.spart; bp.tiles = dm.stat_tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
-    bp.rm = b.running_mean; bp.rv = b.running_var; bp.nbt = b.num_batches_tracked; bp.stats = bf.stats[k];
-    hipLaunchKernelGGL(yl_head_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
-    hipLaunchKernelGGL(yl_head_bn_relu_kernel, dim3(eg), dim3(NT), 0, s, (const float*)bf.z[k], (const float*)bf.stats[k],
-                       (const float*)b.gamma, (const float*)b.beta, hout, n4, F);
-    nl += 2;
+    nl += 2 + bn_forward<ACT_RELU>(s, bn_of(b, dm, bf, k), train, bf.z[k], nullptr, hout);
     in = hout;
   }
   *launches += nl;
@@ -639,8 +496,7 @@ void blocks_backward(hipStream_t s, const yl_head_block* params, const yl_head_b
                      const float* gin, const float* x_in, float* dx, const Buffers& bf, bool train, int mode,
                      const BlockDims& dm, int* launches) {
   const int M = dm.M, S = dm.S, F = dm.F;
-  const long n4 = (long)M * (F >> 2);
-  const int eg = ceil_div(n4, NT), cq = pick_cq(F);
+  const int eg = ceil_div((long)M * (F >> 2), NT), cq = pick_cq(F);
   HeadRows none;
   memset(&none, 0, sizeof(none));
   int nl = 0;
@@ -649,24 +505,12 @@ void blocks_backward(hipStream_t s, const yl_head_block* params, const yl_head_b
     const yl_head_block& g = grads[t];
     const float* xin = t ? bf.h[t - 1] : x_in;
     const float* dh = t == D - 1 ? gin : bf.ga;
-    if (train || g.gamma || g.beta) {    // sum g, sum g * xhat: dbeta, dgamma, and the two means the batch statistics carry
-      StatP sp;
-      sp.a = dh; sp.h = bf.h[t]; sp.z = bf.z[t]; sp.stats = bf.stats[t]; sp.part = bf.spart;
-      sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 1;
-      hipLaunchKernelGGL(yl_head_colstats_kernel, dim3(dm.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
-      ++nl;
-    }
+    const BnLayer bn = bn_of(b, dm, bf, t);
+    // sum g, sum g * xhat: dbeta, dgamma, and the two means the batch statistics carry
+    nl += bn_backward_sums<ACT_RELU>(s, bn, train, dh, bf.h[t], bf.z[t], g.gamma, g.beta, bf.coef);
     const bool below = t > first || g.dw || g.pw || (t == 0 && dx);   // anything that needs dz
-    BnBwdP bp;
-    bp.part = bf.spart; bp.tiles = (train || g.gamma || g.beta) ? dm.stat_tiles : 0; bp.M = M; bp.F = F; bp.train = train;
-    bp.dgamma = g.gamma; bp.dbeta = g.beta; bp.coef = bf.coef;
-    hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
-    ++nl;
     if (!below) break;
-    hipLaunchKernelGGL(yl_head_bn_bwd_kernel, dim3(eg), dim3(NT), 0, s, dh, (const float*)bf.h[t],
-                       (const float*)bf.z[t], (const float*)bf.stats[t], (const float*)bf.coef, (const float*)b.gamma,
-                       bf.ga, n4, F);
-    ++nl;
+    nl += bn_backward_dz<ACT_RELU>(s, bn, dh, bf.h[t], bf.z[t], bf.coef, bf.ga);
     if (g.pw) {                          // dW1 = dz^T . d
       launch_gemm_in<AMP>(mode, s, ColsScalar{bf.d[t], F}, ColsScalar{bf.ga, F}, OutPartial{bf.wpart, (long)F * F}, F, F, M,
                           dm.wgrad_rows, dm.wgrad_splits);

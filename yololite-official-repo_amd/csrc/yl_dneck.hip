@@ -3,13 +3,13 @@
 //
 //   block:    z = conv3x3(x, W)   h = silu(y),  y = gamma * (z - mean) * invstd + beta        (z, h are kept for backward)
 //   backward: g = dh * s(y) * (1 + y * (1 - s(y))), s = sigmoid, y recomputed from z and the statistics; then the
-//             BatchNorm backward of yl_block.h with g in place of the ReLU-masked gradient; dW = sum_m dz (x) x(m + tap);
+//             BatchNorm backward of yl_bn.h with g in place of the ReLU-masked gradient; dW = sum_m dz (x) x(m + tap);
 //             dx = conv3x3(dz, W transposed in (n, c), taps flipped)
 //
 // Everything around the blocks (laterals, upsample-add and its transpose, lateral gradients, nearest maps) is yl_fpn.h,
-// shared with yl_neck.hip.  The forward column statistics, yl_head_bn_stats_kernel and yl_head_bn_grads_kernel are those
-// of yl_block.h.  New here: the convolution (one kernel for forward and input gradient), its weight pack, its weight
-// gradient (partials + ordered float64 sum) and the three SiLU forms of the BatchNorm kernels.
+// shared with yl_neck.hip.  BatchNorm + SiLU is the ACT_SILU instantiation of yl_bn.h's kernels and launch sequences.
+// New here: the convolution (one kernel for forward and input gradient), its weight pack and its weight gradient
+// (partials + ordered float64 sum).
 //
 // Convolution, implicit GEMM in the orientation of yl_head_gemm_kernel (weights: MFMA A operand, pixels: B operand, a lane
 // ends with four consecutive output channels of one pixel).  Workgroup (spatial tile of CT x CT pixels of ONE image, block
@@ -291,95 +291,6 @@ __global__ __launch_bounds__(NT) void yl_dneck_wsum_kernel(const float* __restri
   out[idx] = (float)s;
 }
 
-// ---- BatchNorm + SiLU.  y and the factor of the backward are computed in fp32 by these two functions everywhere
-__device__ __forceinline__ float bn_y(float z, float mu, float is, float gamma, float beta) { return (z - mu) * is * gamma + beta; }
-__device__ __forceinline__ float silu_dfactor(float y) {        // d silu / dy = s * (1 + y * (1 - s))
-  const float sg = 1.f / (1.f + expf(-y));
-  return sg * (1.f + y * (1.f - sg));
-}
-
-__global__ __launch_bounds__(NT) void yl_dneck_bn_silu_kernel(const float* __restrict__ z, const float* __restrict__ stats,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             float* __restrict__ h, long n4, int F) {
-  const long idx = (long)blockIdx.x * NT + threadIdx.x;
-  if (idx >= n4) return;
-  const int c = (int)((idx * 4) % F);
-  const f32x4 v = ld4(z + idx * 4), mu = ld4(stats + c), is = ld4(stats + F + c);
-  f32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float y = bn_y(v[e], mu[e], is[e], gamma[c + e], beta[c + e]);
-    o[e] = y / (1.f + expf(-y));
-  }
-  st4(h + idx * 4, o);
-}
-
-// the backward column sums in the tiling of yl_head_colstats_kernel: part[tile][0][c] = sum g, part[tile][1][c] = sum g * xhat
-struct SiluStatP {
-  const float *dh, *z, *stats, *gamma, *beta;
-  double* part;
-  int M, F, CQ;
-};
-__global__ __launch_bounds__(NT) void yl_dneck_colstats_silu_kernel(SiluStatP P) {
-  __shared__ double red[NT][8];
-  const int t = threadIdx.x, cq = t & (P.CQ - 1), rs = t / P.CQ, RS = NT / P.CQ;
-  const int c = (blockIdx.y * P.CQ + cq) * 4, F = P.F;
-  const bool on = c < F;
-  const int m0 = blockIdx.x * STAT_ROWS, m1 = m0 + STAT_ROWS < P.M ? m0 + STAT_ROWS : P.M;
-  double s0[4] = {0, 0, 0, 0}, s1[4] = {0, 0, 0, 0};
-  if (on) {
-    const f32x4 mu = ld4(P.stats + c), is = ld4(P.stats + F + c);
-    float ga[4], be[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { ga[e] = P.gamma[c + e]; be[e] = P.beta[c + e]; }
-    for (int m = m0 + rs; m < m1; m += RS) {
-      const long o = (long)m * F + c;
-      const f32x4 a = ld4(P.dh + o), zv = ld4(P.z + o);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double g = (double)(a[e] * silu_dfactor(bn_y(zv[e], mu[e], is[e], ga[e], be[e])));
-        const double xh = ((double)zv[e] - (double)mu[e]) * (double)is[e];
-        s0[e] += g; s1[e] += g * xh;
-      }
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { red[t][e] = s0[e]; red[t][4 + e] = s1[e]; }
-  __syncthreads();
-  if (rs == 0 && on) {
-    for (int k = 1; k < RS; ++k)
-#pragma unroll
-      for (int e = 0; e < 8; ++e) red[t][e] += red[k * P.CQ + cq][e];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      P.part[((long)blockIdx.x * 2 + 0) * F + c + e] = red[t][e];
-      P.part[((long)blockIdx.x * 2 + 1) * F + c + e] = red[t][4 + e];
-    }
-  }
-}
-
-// dz = gamma * invstd * (g - c0 - xhat * c1); dh and dz may be one buffer (each thread reads its four values first)
-__global__ __launch_bounds__(NT) void yl_dneck_bn_silu_bwd_kernel(const float* dh, const float* __restrict__ z,
-                                                                 const float* __restrict__ stats, const float* __restrict__ coef,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                 float* dz, long n4, int F) {
-  const long idx = (long)blockIdx.x * NT + threadIdx.x;
-  if (idx >= n4) return;
-  const int c = (int)((idx * 4) % F);
-  const f32x4 g = ld4(dh + idx * 4), zv = ld4(z + idx * 4);
-  const f32x4 mu = ld4(stats + c), is = ld4(stats + F + c), c0 = ld4(coef + c), c1 = ld4(coef + F + c);
-  f32x4 o;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const float ge = g[e] * silu_dfactor(bn_y(zv[e], mu[e], is[e], gamma[c + e], beta[c + e]));
-    const float xh = (zv[e] - mu[e]) * is[e];
-    o[e] = gamma[c + e] * is[e] * (ge - c0[e] - xh * c1[e]);
-  }
-  st4(dz + idx * 4, o);
-}
-
-int64_t round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 // the 3x3 weight gradient's cut of `tiles` spatial tiles into runs: about 512 workgroups; the partials are 9 F F floats per split
 void w3_split(int64_t F, int64_t tiles, int32_t* tiles_per_split, int32_t* splits) {
   const int64_t blocks = (int64_t)ceil_div(F, GB) * ceil_div(F, GB);
@@ -558,6 +469,12 @@ void wgrad3x3(int mode, hipStream_t s, const float* x, const float* dz, float* w
   else wgrad3x3_as<0>(s, x, dz, wpart, dw, S, F, tiles, tiles_per_split, splits);
 }
 
+// a block's BatchNorm over the level's rows
+BnLayer bn_of(const yl_dneck_block& b, const yl_dneck_level_plan& lp, int F, float* stats, double* spart) {
+  return {lp.rows, F, STAT_ROWS, lp.stat_tiles, b.gamma, b.beta, b.running_mean, b.running_var, b.num_batches_tracked, BN_EPS, stats,
+          spart};
+}
+
 // the first block something of `g` is wanted of (D: none)
 int first_wanted(const yl_dneck_block* g, int D) {
   int first = D;
@@ -586,14 +503,12 @@ yl_status yl_dneck_forward(yl_dneck* h, const yl_dneck_tensors* params, const fl
   const yl_status st = ensure(h, batch, sizes, save, &pl, &nb);
   if (st != YL_OK) return st;
   hipStream_t s = (hipStream_t)stream;
-  const int cq = pick_cq(F);
   int nl = 0;
   h->mem.fValid = 0;
   for (int k = L - 1; k >= 0; --k) {
     const yl_dneck_level& lv = params->level[k];
     const yl_dneck_level_plan& lp = pl.level[k];
     const int M = lp.rows, Cin = h->cfg.in_channels[k], S = sizes[k];
-    const long n4 = (long)M * (F >> 2);
     lateral_forward(s, lv.lat_w, lv.lat_b, c_dev[k], nb.t[k], k + 1 < L ? p_dev[k + 1] : nullptr, nb.maps[k].src, F, M, Cin, S,
                     k + 1 < L ? sizes[k + 1] : 0);
     ++nl;
@@ -604,21 +519,7 @@ yl_status yl_dneck_forward(yl_dneck* h, const yl_dneck_tensors* params, const fl
       // with `save` the last block writes the handle's h and p_k is a copy of it; without, it writes p_k
       float* hout = (t == D - 1 && !save) ? p_dev[k] : nb.h[k][i];
       conv3x3(mode, s, b.w, nb.wpack, in, nb.z[k][i], batch, S, F, 0);
-      nl += 2;
-      if (train) {
-        StatP sp;
-        sp.a = nb.z[k][i]; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = nb.spart;
-        sp.M = M; sp.F = F; sp.CQ = cq; sp.bwd = 0;
-        hipLaunchKernelGGL(yl_head_colstats_kernel, dim3(lp.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
-        ++nl;
-      }
-      BnFwdP bp;
-      bp.part = nb.spart; bp.tiles = lp.stat_tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
-      bp.rm = b.running_mean; bp.rv = b.running_var; bp.nbt = b.num_batches_tracked; bp.stats = nb.stats[k][i];
-      hipLaunchKernelGGL(yl_head_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
-      hipLaunchKernelGGL(yl_dneck_bn_silu_kernel, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, (const float*)nb.z[k][i],
-                         (const float*)nb.stats[k][i], (const float*)b.gamma, (const float*)b.beta, hout, n4, F);
-      nl += 2;
+      nl += 2 + bn_forward<ACT_SILU>(s, bn_of(b, lp, F, nb.stats[k][i], nb.spart), train, nb.z[k][i], nullptr, hout);
       in = hout;
     }
     if (save && hipMemcpyAsync(p_dev[k], in, (size_t)M * F * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) return YL_ERR_HIP;
@@ -660,15 +561,12 @@ yl_status yl_dneck_backward(yl_dneck* h, const yl_dneck_tensors* params, const y
   if (!h->mem.fValid) return YL_ERR_STATE;
   hipStream_t s = (hipStream_t)stream;
   const bool train = h->fTrain != 0;
-  const int cq = pick_cq(F);
   int nl = 0;
   for (int k = 0; k <= K; ++k) {
     const yl_dneck_level& lv = params->level[k];
     const yl_dneck_level& g = grads->level[k];
     const yl_dneck_level_plan& lp = pl.level[k];
     const int M = lp.rows, Cin = h->cfg.in_channels[k], S = sizes[k];
-    const long n4 = (long)M * (F >> 2);
-    const int eg = ceil_div(n4, NT);
     float* dc = dc_dev ? dc_dev[k] : nullptr;
     float *cur = nb.ga, *other = nb.gb;  // the two gradients in flight: dz of a block in `cur`, its input's in `other`
     const float* dh = gp_dev[k];
@@ -685,25 +583,12 @@ yl_status yl_dneck_backward(yl_dneck* h, const yl_dneck_tensors* params, const y
       const yl_dneck_block& b = lv.block[t];
       const yl_dneck_block& gb = g.block[t];
       const float* xin = t ? nb.h[k][t - 1] : nb.t[k];
-      const bool sums = train || gb.gamma || gb.beta;
-      if (sums) {                        // sum g, sum g * xhat: dbeta, dgamma, and the two means the batch statistics carry
-        SiluStatP sp;
-        sp.dh = dh; sp.z = nb.z[k][t]; sp.stats = nb.stats[k][t]; sp.gamma = b.gamma; sp.beta = b.beta; sp.part = nb.spart;
-        sp.M = M; sp.F = F; sp.CQ = cq;
-        hipLaunchKernelGGL(yl_dneck_colstats_silu_kernel, dim3(lp.stat_tiles, ceil_div(F >> 2, cq)), dim3(NT), 0, s, sp);
-        ++nl;
-      }
+      const BnLayer bn = bn_of(b, lp, F, nb.stats[k][t], nb.spart);
+      // sum g, sum g * xhat: dbeta, dgamma, and the two means the batch statistics carry
+      nl += bn_backward_sums<ACT_SILU>(s, bn, train, dh, nb.h[k][t], nb.z[k][t], gb.gamma, gb.beta, nb.coef);
       const bool need_dx = t > first || (t == 0 && need_gt);
-      BnBwdP bp;
-      bp.part = nb.spart; bp.tiles = sums ? lp.stat_tiles : 0; bp.M = M; bp.F = F; bp.train = train;
-      bp.dgamma = gb.gamma; bp.dbeta = gb.beta; bp.coef = nb.coef;
-      hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
-      ++nl;
       if (!gb.w && !need_dx) break;
-      hipLaunchKernelGGL(yl_dneck_bn_silu_bwd_kernel, dim3(eg), dim3(NT), 0, s, dh, (const float*)nb.z[k][t],
-                         (const float*)nb.stats[k][t], (const float*)nb.coef, (const float*)b.gamma, (const float*)b.beta,
-                         cur, n4, F);
-      ++nl;
+      nl += bn_backward_dz<ACT_SILU>(s, bn, dh, nb.h[k][t], nb.z[k][t], nb.coef, cur);
       if (gb.w) {                        // dW[n][c][tap] = sum_m dz[m][n] * x[m + tap][c]
         wgrad3x3(h->fMode, s, xin, cur, nb.wpart, gb.w, S, F, lp.conv_tiles, lp.w3grad_tiles, lp.w3grad_splits);
         nl += 2;

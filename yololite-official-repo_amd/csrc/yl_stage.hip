@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NT) void yl_stage_dw_wsum_kernel(const double* __re
   out[c * KK + k] = (float)s;
 }
 
-// ---- BatchNorm: the column sums, the statistics, the normalisation and its backward are yl_bn.h, shared with yl_stem.hip
+// ---- BatchNorm: the column sums, the statistics, the normalisation and its backward are yl_bn.h, which every training unit runs
 // the residual's backward: io += g
 __global__ __launch_bounds__(NT) void yl_stage_add_kernel(float* io, const float* __restrict__ g, long n4) {
   const long idx = (long)blockIdx.x * NT + threadIdx.x;
@@ -273,9 +273,6 @@ struct StagePolicy {
     if (u.dw) launch_dw<true>(s, dz, w, dx, u.k, u.st, B, u.Sin, u.Sout, F);
     else launch_gemm_in<true>(mode, s, ColsScalar{w, u.cin}, RowsVec{dz, F}, OutRowsVec{dx, u.cin}, u.cin, (int)u.Mout, F, F, 1);   // dx = dz . W
     return 1;
-  }
-  template <bool RELU> static void colstats(hipStream_t s, const Unit& u, const StatP& sp) {
-    hipLaunchKernelGGL(yl_stage_colstats_kernel<RELU>, dim3(u.tiles, ceil_div(sp.F >> 2, sp.CQ)), dim3(NT), 0, s, sp);
   }
   static void add(hipStream_t s, float* io, const float* g, long n4) {
     hipLaunchKernelGGL(yl_stage_add_kernel, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, io, g, n4);

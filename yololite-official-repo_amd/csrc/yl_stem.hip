@@ -653,9 +653,6 @@ struct StemPolicy {
     return u.k == 3 ? conv3_dgrad(s, dz, w, sb.wpack, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout, mode)
                     : conv1_dgrad(s, dz, w, dx, u.st, B, u.Sin, u.Sout, u.cin, u.cout, mode);
   }
-  template <bool RELU> static void colstats(hipStream_t s, const Unit& u, const StatP& sp) {
-    hipLaunchKernelGGL(yl_stem_colstats_kernel<RELU>, dim3(u.tiles, ceil_div(sp.F >> 2, sp.CQ)), dim3(NT), 0, s, sp, u.stat_rows);
-  }
 };
 
 }  // namespace

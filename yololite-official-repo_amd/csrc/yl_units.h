@@ -15,18 +15,17 @@
 // third is never touched.
 // What a translation unit supplies is a POLICY P:
 //   P::ROT                       rotating buffers: 3 with residual blocks, 2 without
-//   P::MIXED                     units without ReLU and residual blocks can occur.  false keeps yl_stage_bn_kernel<false>,
-//                                yl_stage_bn_bwd_kernel<false> and the add out of the object
+//   P::MIXED                     units without ReLU and residual blocks can occur.  false keeps the ACT_NONE instantiations
+//                                of yl_bn.h's kernels and the add out of the object
 //   P::layout(cfg, B, S, us, &n, &z)   the units and sizes of cfg at (B, S); a status.  us and n are filled either way
 //   P::conv_forward / conv_wgrad / conv_dgrad(s, u, B, ..., sb, mode)   the unit's convolution passes in the dense GEMMs'
 //                                operand type `mode` (a depthwise unit has none) -> launches enqueued
-//   P::colstats<RELU>(s, u, sp)  the column sums over the unit's statistics tiles
 //   P::add(s, io, g, n4)         io += g (MIXED only)
 #ifndef YL_UNITS_H
 #define YL_UNITS_H
 #include <new>
 
-#include "yl_bn.h"
+#include "yl_block.h"
 
 namespace {
 
@@ -45,6 +44,7 @@ struct Unit {
 };
 
 inline int round4(int v) { return (v + 3) & ~3; }
+inline int out_size(int S, int k, int st) { return (S + 2 * ((k - 1) / 2) - k) / st + 1; }
 
 // bytes, but cmax: channels.  x0 (the caller's x), xsave (its saved copy) and gmax (one gradient buffer) are the
 // translation unit's to set; the rest is unit_sizes'
@@ -192,16 +192,10 @@ template <class H> yl_status units_held(const H* h, int64_t* saved_bytes, int64_
   return arena_held(h ? &h->mem : nullptr, saved_bytes, workspace_bytes, forward_held);
 }
 
-template <bool RELU>
-void launch_bn(hipStream_t s, const float* z, const float* stats, const yl_stage_unit& e, const float* res, float* h, long n4, int F) {
-  hipLaunchKernelGGL(yl_stage_bn_kernel<RELU>, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, z, stats, (const float*)e.gamma,
-                     (const float*)e.beta, res, h, n4, F);
-}
-template <bool RELU>
-void launch_bn_bwd(hipStream_t s, const float* dh, const float* h, const float* z, const float* stats, const float* coef,
-                   const yl_stage_unit& e, float* dz, long n4, int F) {
-  hipLaunchKernelGGL(yl_stage_bn_bwd_kernel<RELU>, dim3(ceil_div(n4, NT)), dim3(NT), 0, s, dh, RELU ? h : (const float*)nullptr, z,
-                     stats, coef, (const float*)e.gamma, dz, n4, F);
+// unit u's BatchNorm: its statistics in `stats`, the partial sums of its row reductions in the stack's spart
+inline BnLayer bn_of(const Unit& u, const yl_stage_unit& e, double eps, float* stats, const UnitBuffers& sb) {
+  return {(int)u.Mout, u.cout, u.stat_rows, u.tiles, e.gamma, e.beta, e.running_mean, e.running_var, e.num_batches_tracked, eps,
+          stats, sb.spart};
 }
 
 // ---- forward.  par: the parameters, one entry per unit (npar of them: which units exist does not depend on the shape);
@@ -242,24 +236,11 @@ yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const f
     if (save) hout = sb.h[i];
     else if (i == n - 1) hout = out_dev;
     else { out_i = pick(in_i, bin_i); hout = sb.nh[out_i]; }
-    const int M = (int)u.Mout, F = u.cout;
     nl += P::conv_forward(s, u, batch, in, e.w, z, sb, mode);
-    if (train) {
-      StatP sp;
-      sp.a = z; sp.h = nullptr; sp.z = nullptr; sp.stats = nullptr; sp.part = sb.spart;
-      sp.M = M; sp.F = F; sp.CQ = pick_cq(F); sp.bwd = 0;
-      P::template colstats<false>(s, u, sp);
-      ++nl;
-    }
-    BnFwdP bp;
-    bp.part = sb.spart; bp.tiles = u.tiles; bp.M = M; bp.F = F; bp.train = train ? 1 : 0;
-    bp.rm = e.running_mean; bp.rv = e.running_var; bp.nbt = e.num_batches_tracked; bp.stats = stats;
-    hipLaunchKernelGGL(yl_stage_bn_stats_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp, h->cfg.eps);
-    const long n4 = (long)M * (F >> 2);
+    const BnLayer bn = bn_of(u, e, h->cfg.eps, stats, sb);
     const float* res = (u.last && u.res) ? bin : nullptr;
-    if (u.relu) launch_bn<true>(s, z, stats, e, res, hout, n4, F);
-    else if constexpr (P::MIXED) launch_bn<false>(s, z, stats, e, res, hout, n4, F);
-    nl += 2;
+    if (u.relu) nl += bn_forward<ACT_RELU>(s, bn, train, z, res, hout);
+    else if constexpr (P::MIXED) nl += bn_forward<ACT_NONE>(s, bn, train, z, res, hout);
     in = hout; in_i = out_i;
   }
   if (save) {
@@ -305,30 +286,17 @@ yl_status units_backward(H* h, const yl_stage_unit* const* par, const yl_stage_u
     const yl_stage_unit& e = *par[i];
     const yl_stage_unit& g = *grd[i];
     const float* xin = i ? sb.h[i - 1] : sb.x;
-    const int M = (int)u.Mout, F = u.cout;
-    const long n4 = (long)M * (F >> 2);
     if (u.last && u.res) { G = dh; keep = cur; }
-    const bool sums = train || g.gamma || g.beta;          // sum g, sum g * xhat: dbeta, dgamma and the batch statistics' two means
-    if (sums) {
-      StatP sp;
-      sp.a = dh; sp.h = sb.h[i]; sp.z = sb.z[i]; sp.stats = sb.stats[i]; sp.part = sb.spart;
-      sp.M = M; sp.F = F; sp.CQ = pick_cq(F); sp.bwd = 1;
-      if (u.relu) P::template colstats<true>(s, u, sp);
-      else if constexpr (P::MIXED) P::template colstats<false>(s, u, sp);
-      ++nl;
-    }
-    BnBwdP bp;
-    bp.part = sb.spart; bp.tiles = sums ? u.tiles : 0; bp.M = M; bp.F = F; bp.train = train;
-    bp.dgamma = g.gamma; bp.dbeta = g.beta; bp.coef = sb.coef;
-    hipLaunchKernelGGL(yl_head_bn_grads_kernel, dim3(ceil_div(F, NT)), dim3(NT), 0, s, bp);
-    ++nl;
+    const BnLayer bn = bn_of(u, e, h->cfg.eps, sb.stats[i], sb);
+    // sum g, sum g * xhat: dbeta, dgamma and the batch statistics' two means
+    if (u.relu) nl += bn_backward_sums<ACT_RELU>(s, bn, train, dh, sb.h[i], sb.z[i], g.gamma, g.beta, sb.coef);
+    else if constexpr (P::MIXED) nl += bn_backward_sums<ACT_NONE>(s, bn, train, dh, sb.h[i], sb.z[i], g.gamma, g.beta, sb.coef);
     const bool need_dx = i > first || (i == 0 && dx_dev);
     if (!need_dx && !g.w) break;
     const int t = (cur >= 0 && cur != keep) ? cur : pick(keep, -1);      // dz: in place unless dh must survive
     float* dz = sb.g[t];
-    if (u.relu) launch_bn_bwd<true>(s, dh, sb.h[i], sb.z[i], sb.stats[i], sb.coef, e, dz, n4, F);
-    else if constexpr (P::MIXED) launch_bn_bwd<false>(s, dh, sb.h[i], sb.z[i], sb.stats[i], sb.coef, e, dz, n4, F);
-    ++nl;
+    if (u.relu) nl += bn_backward_dz<ACT_RELU>(s, bn, dh, sb.h[i], sb.z[i], sb.coef, dz);
+    else if constexpr (P::MIXED) nl += bn_backward_dz<ACT_NONE>(s, bn, dh, sb.h[i], sb.z[i], sb.coef, dz);
     if (g.w) nl += P::conv_wgrad(s, u, B, xin, dz, g.w, sb, mode);
     if (!need_dx) break;
     const int d = pick(keep, t);
