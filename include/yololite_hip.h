@@ -1206,6 +1206,53 @@ yl_status yl_amp_stem_conv(const float* a_dev, const float* b_dev, float* out_de
                            int32_t batch, int32_t size, int32_t cin, int32_t cout, int32_t input_nchw, uint32_t mode,
                            void* stream, int32_t* launches);
 
+/* ---- training-time augmentation (csrc/yl_aug.hip) ------------------------------------------------------------------
+ * The training sibling of yl_preprocess: replaces the dataset's 4-image mosaic (scripts/data/dataset.py:124-175) and
+ * get_base_transform (scripts/data/augment.py:54-101) for a batch, in one launch with one bilinear gather per output
+ * pixel.  `packed_u8_dev` holds BGR uint8 HWC images back to back (the packing of yl_preprocess); x_dev receives
+ * [B,3,S,S] fp32 planar RGB.  Output image b shows a FRAME of frame_w x frame_h pixels made of num_tiles tiles
+ * (tiles_dev[first_tile ...]); a tile is one source image stretched over the rectangle [x0,x1) x [y0,y1) of the frame
+ * (1 tile: the frame is the image; 4 tiles: the quadrants of the mosaic canvas).  Per output pixel (x, y), in this order:
+ *   1. y - top outside [0,nh) or x - left outside [0,nw): raw 114 in every channel, straight to step 8 (letterbox pad);
+ *   2. (u, v) = ((m0 x + m1 y) + m2, (m3 x + m4 y) + m5): frame coordinates with pixel centres at +0.5; the host composes
+ *      letterbox^-1, affine^-1 and the un-flip in float64 and rounds to fp32 once;
+ *   3. (u, v) outside [0,frame_w) x [0,frame_h): 114 (the affine's constant border), which does go through 6 and 7;
+ *   4. the first tile whose rectangle holds (u, v): fx = (u - x0) * (w0 / (x1 - x0)) - 0.5 (fy alike), fp32 bilinear
+ *      a + (b - a) * frac along x, then along y, of the four neighbours, indices clamped to the source's edge;
+ *   5. BGR -> RGB, then channel c takes RGB channel perm[c];
+ *   6. color_mode (one per image; every result clipped to [0,255]): YL_AUG_BRIGHTNESS_CONTRAST v = color[0] v + color[1] 255;
+ *      YL_AUG_HSV_SHIFT RGB -> HSV in fp32, hue + color[0] OpenCV hue units (2 degrees each, wrapped), saturation +
+ *      color[1] / 255, value + color[2] (0..255 scale), clipped, back to RGB; YL_AUG_RGB_SHIFT v_c += color[c];
+ *      YL_AUG_NONE and YL_AUG_CHANNEL_SHUFFLE (whose work is perm) change nothing;
+ *   7. noise_sigma > 0: v += noise_sigma * (sum of twelve uniforms in [0,1) - 6), the uniforms 24-bit words of an
+ *      integer-only uint32 counter hash of (noise_seed, channel, y, x, k); clipped to [0,255].  The result depends on
+ *      the descriptor alone: not on the batch, the image's slot in it, or the launch geometry;
+ *   8. (v - mean 255) * (1 / (std 255)) in fp32, the evaluate path's arithmetic ("pre_norm" 1 of yl_preprocess).
+ * Only IEEE-exact fp32 operations, each rounded where written.  Takes no context, like yl_stem_conv; enqueues one kernel on
+ * `stream` and returns.  NULL pointers, batch <= 0, batch > 65535, size <= 0 or size > 262140: YL_ERR_INVALID before any
+ * device call.  The descriptors live on the device and are not validated: a tile's offset / h0 / w0 must lie inside
+ * packed_u8_dev, h0, w0 >= 1 and first_tile + num_tiles inside tiles_dev.                                             */
+enum { YL_AUG_NONE = 0, YL_AUG_BRIGHTNESS_CONTRAST = 1, YL_AUG_HSV_SHIFT = 2, YL_AUG_RGB_SHIFT = 3,
+       YL_AUG_CHANNEL_SHUFFLE = 4 };
+typedef struct yl_aug_tile {
+  int64_t offset;             /* byte offset of the source image in packed_u8_dev ([h0][w0][3] BGR)                    */
+  int32_t h0, w0;             /* source size                                                                          */
+  float x0, y0, x1, y1;       /* the tile's rectangle in frame pixels                                                 */
+} yl_aug_tile;
+typedef struct yl_aug_image {
+  int32_t first_tile, num_tiles;
+  int32_t frame_w, frame_h;
+  int32_t nh, nw, top, left;  /* letterbox of the frame in the S x S output                                           */
+  float m[6];                 /* output pixel index -> frame coordinates, row-major 2x3                               */
+  int32_t perm[3];            /* channel permutation over RGB (identity 0,1,2)                                        */
+  int32_t color_mode;         /* YL_AUG_*                                                                             */
+  float color[4];
+  float noise_sigma;          /* 0: no noise                                                                          */
+  uint32_t noise_seed;
+} yl_aug_image;
+yl_status yl_augment(const uint8_t* packed_u8_dev, const yl_aug_tile* tiles_dev, const yl_aug_image* imgs_dev,
+                     int32_t batch, int32_t size, float* x_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,11 +9,13 @@
                                    [--train-neck [--amp fp16|bf16] [--train-tail [--lr-tail 1e-4]]] [--amp-heads fp16|bf16]
                                    [--train-neck --train-backbone [--lr-backbone 1e-4]]
                                    [--amp-backbone fp16|bf16]
+                                   [--augment [--mosaic-p 0.2] [--aug-seed 0]]
     python tools/finetune_heads.py --synthetic edge_n --out out.pt [--num-classes 3] [--img-size 128] [--steps 20]
+                                   [--augment [--mosaic-p 0.2] [--aug-seed 0]]
 
 DIR is a YOLO-txt dataset: DIR/images/*.{jpg,jpeg,png,bmp} and DIR/labels/<stem>.txt with lines
 `class cx cy w h` (normalised to the image).  Images are read with PIL, letterboxed by the library's preprocess path
-(yl_preprocess), the boxes follow the same geometry.  No augmentation.  With --num-classes other than the
+(yl_preprocess), the boxes follow the same geometry.  No augmentation unless --augment is given (below).  With --num-classes other than the
 checkpoint's the heads start freshly initialised (torch's defaults plus the reference's init_detect_bias); otherwise
 they start from the checkpoint.  --synthetic NAME takes a zoo model with seeded synthetic weights and one random batch
 instead of --weights / --data.  The output is a checkpoint {"state_dict", "meta"}: the input's state_dict with the
@@ -50,6 +52,16 @@ the same terms.  --amp-backbone fp16 | bf16 (needs --train-backbone or --train-t
 backbone: every dense GEMM of MobileNetV4Backbone (the stem's 3x3 and every 1x1 convolution) or of BackboneTail, on the
 same terms; its depthwise convolutions and BatchNorm stay fp32.  The loss scale is on when any of --amp, --amp-heads and
 --amp-backbone is fp16.
+
+--augment: batches go through augment.TrainAugmenter (csrc/yl_aug.hip) instead of yl_preprocess: the reference's
+training-time transforms (scripts/data/augment.py:54-101: flips, affine, one colour operation, noise, letterbox, normalise)
+and its 4-image mosaic (scripts/data/dataset.py:124-175) with their probabilities and ranges, one kernel launch per batch,
+the boxes transformed and filtered on the host; augment.py's docstring lists what differs from Albumentations / cv2.  With
+--data the three extra images of a mosaic are drawn from the dataset, and the schedule of tools/train.py:326-331 holds
+(mosaic off from 70 % of the epochs, everything off after 90 %).  With --synthetic the one batch is seeded random uint8
+images of mixed sizes, augmented anew at every step.  --mosaic-p sets the mosaic's probability (default: the reference's
+0.2), --aug-seed the generator's seed.  The images are normalised with the evaluate path's arithmetic (A.Normalize), which
+is what the reference trains on.
 """
 import argparse
 import copy
@@ -106,6 +118,31 @@ def load_batch(ctx, items, img_size):
     return x, targets
 
 
+def load_item(item):
+    """-> (BGR uint8 image, {"boxes": xyxy in the image's pixels, "labels"}): what TrainAugmenter takes"""
+    from PIL import Image
+    path, labels, boxes = item
+    rgb = np.asarray(Image.open(path).convert("RGB"))
+    h, w = rgb.shape[:2]
+    cx, cy, bw, bh = (boxes[:, i] for i in range(4))
+    xyxy = np.stack([(cx - bw / 2) * w, (cy - bh / 2) * h, (cx + bw / 2) * w, (cy + bh / 2) * h], 1).reshape(-1, 4)
+    return np.ascontiguousarray(rgb[:, :, ::-1]), {"boxes": xyxy, "labels": labels}
+
+
+def synthetic_images(img_size, batch, num_classes, seed=0):
+    """--synthetic --augment: seeded random uint8 images of mixed sizes with 1..3 boxes each, in source pixels"""
+    rs = np.random.RandomState(seed)
+    images, targets = [], []
+    for _ in range(batch):
+        h, w = (int(v) for v in rs.randint(img_size // 2, 2 * img_size + 1, 2))
+        images.append(rs.randint(0, 256, (h, w, 3)).astype(np.uint8))
+        n = int(rs.randint(1, 4))
+        c = rs.uniform(0.25, 0.75, (n, 2)) * (w, h)
+        wh = rs.uniform(0.15, 0.45, (n, 2)) * (w, h)
+        targets.append({"boxes": np.concatenate([c - wh / 2, c + wh / 2], 1), "labels": rs.randint(0, num_classes, n).astype(np.int64)})
+    return images, targets
+
+
 def synthetic_batch(img_size, batch, num_classes, device, seed=0):
     rs = np.random.RandomState(seed)
     x = torch.from_numpy(rs.standard_normal((batch, 3, img_size, img_size)).astype(np.float32)).to(device)
@@ -147,8 +184,14 @@ def main():
                     help="the heads' 1x1 GEMMs in this precision (independent of --train-neck)")
     ap.add_argument("--amp-backbone", default="", choices=("", "fp16", "bf16"),
                     help="with --train-backbone or --train-tail: the backbone's dense GEMMs (3x3 stem, every 1x1) in this precision")
+    ap.add_argument("--augment", action="store_true",
+                    help="training-time augmentation on the device (flips, affine, colour, noise, mosaic) instead of the plain letterbox")
+    ap.add_argument("--mosaic-p", type=float, default=-1.0, help="with --augment: probability of the 4-image mosaic (default 0.2)")
+    ap.add_argument("--aug-seed", type=int, default=0, help="with --augment: seed of the augmentation's generator")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
+    if (a.mosaic_p >= 0 or a.aug_seed) and not a.augment:
+        raise SystemExit("--mosaic-p / --aug-seed set the augmentation: they need --augment")
     if bool(a.synthetic) == bool(a.weights):
         raise SystemExit("give either --weights (with --data) or --synthetic NAME")
     if a.amp_backbone and not (a.train_backbone or a.train_tail):
@@ -213,9 +256,19 @@ def main():
         norm = fts.step()
         return float(loss), parts, float(norm)
 
+    augmenter = None
+    if a.augment:
+        cfg = ya.AugmentConfig() if a.mosaic_p < 0 else ya.AugmentConfig(mosaic_p=a.mosaic_p)
+        augmenter = ya.TrainAugmenter(cfg, img_size, seed=a.aug_seed, device=a.device)
+
     if a.synthetic:
-        x, targets = synthetic_batch(img_size, min(a.batch, 8), nc, a.device)
+        if augmenter is not None:
+            images, src_targets = synthetic_images(img_size, min(a.batch, 8), nc)
+        else:
+            x, targets = synthetic_batch(img_size, min(a.batch, 8), nc, a.device)
         for i in range(a.steps):
+            if augmenter is not None:                      # the same sources, drawn anew: mosaics take their extras from the batch
+                x, targets = augmenter(images, src_targets, dataset_len=len(images), fetch=lambda j: (images[j], src_targets[j]))
             loss, parts, norm = step(x, targets)
             print(f"step {i:3d}  loss {loss:.4f}  box {parts['box']:.4f} obj {parts['obj']:.4f} cls {parts['cls']:.4f}  "
                   f"|g| {norm:.3f}")
@@ -225,8 +278,15 @@ def main():
         for ep in range(a.epochs):
             order = np.random.RandomState(ep).permutation(len(items))
             tot, n = 0.0, 0
+            if augmenter is not None:
+                augmenter.epoch_schedule(ep, a.epochs)
             for i in range(0, len(order), a.batch):
-                x, targets = load_batch(ctx, [items[j] for j in order[i:i + a.batch]], img_size)
+                if augmenter is not None:
+                    loaded = [load_item(items[j]) for j in order[i:i + a.batch]]
+                    x, targets = augmenter([im for im, _ in loaded], [t for _, t in loaded], dataset_len=len(items),
+                                           fetch=lambda j: load_item(items[j]))
+                else:
+                    x, targets = load_batch(ctx, [items[j] for j in order[i:i + a.batch]], img_size)
                 if x.shape[0] * (img_size // 32) ** 2 < 2:
                     continue                               # BatchNorm needs more than one value per channel
                 loss, _, _ = step(x, targets)

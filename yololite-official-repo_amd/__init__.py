@@ -11,6 +11,8 @@ from .model import (HipContext, YOLOLiteHIP, build_model_from_meta,  # noqa: F40
 from .postprocess import (_decode_batch_to_coco_dets, decode_anchorfree_like_train,  # noqa: F401
                           decode_preds_anchorfree, infer_main_postprocess, nms, predict_coco_dets, predict_main)
 from .preprocess import letterbox_geometry, preprocess_batch  # noqa: F401
+from .augment import (AugmentConfig, ImageParams, TrainAugmenter, augment_batch, compose,  # noqa: F401
+                      sample_params, transform_boxes)
 from .program import BACKBONES, Program, build_program  # noqa: F401
 from .evalops import (_coco_eval_from_lists, build_curves_from_coco, coco_eval,  # noqa: F401
                       coco_summary_lines, create_confusion_matrix)
@@ -28,4 +30,5 @@ __all__ = ["YoloLiteHipError", "load_library", "HipContext", "YOLOLiteHIP", "bui
            "decode_anchorfree_like_train", "infer_main_postprocess", "nms", "predict_main", "predict_coco_dets", "build_program", "Program", "BACKBONES",
            "preprocess_batch", "letterbox_geometry", "build_curves_from_coco", "create_confusion_matrix",
            "coco_eval", "_coco_eval_from_lists", "coco_summary_lines", "LossAF", "targets_to_xyxy_px", "FusedTrainStep", "DetectHeads", "DetectNeck", "DetectNeckMS", "neck_for", "UIBStack", "BackboneTail", "BackboneMid", "MobileNetV4Backbone", "ConvStack", "BackboneStem",
-           "KalmanSortTracker", "TrackerBank", "ServingPipeline"]
+           "KalmanSortTracker", "TrackerBank", "ServingPipeline",
+           "AugmentConfig", "ImageParams", "TrainAugmenter", "augment_batch", "compose", "sample_params", "transform_boxes"]

@@ -379,6 +379,7 @@ SYMBOLS = [
     ("yl_amp_stage_get", C.c_int32, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("yl_amp_stem_get", C.c_int32, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("yl_amp_stem_conv", C.c_int32, [_vp, _vp, _vp] + [C.c_int32] * 8 + [C.c_uint32, _vp, _ip]),
+    ("yl_augment", C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
 ]
 # entries whose names carry a digit, bound like the others.  Listed apart: SYMBOLS is held, name for name, to what a
 # letters-only pattern finds declared in the header (tests/test_host_cpu.py), and that pattern does not see these

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Build libyololite_hip.so (gfx950) in-tree with hipcc.  No cmake, no torch extension machinery:
-nineteen translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
+twenty translation units (one of them, yl_program.cpp, plain host C++; three of them compiled four times: fp32, bf16-MFMA, fp16-MFMA and fp16-storage builds), one shared
 library with a plain C ABI (include/yololite_hip.h).
 
     python yololite-official-repo_amd/csrc/build.py [--force | --asan]
@@ -40,6 +40,8 @@ UNITS = [   # (source, extra flags, object name)
     # reference-exact fp32 arithmetic in decode/NMS: no fused multiply-add contraction
     ("yl_post.hip", ["-ffp-contract=off"], "yl_post.o"),
     ("yl_pre.hip", ["-ffp-contract=off"], "yl_pre.o"),
+    # training-time augmentation (warp, colour, noise, mosaic): IEEE-exact fp32 held bit for bit to a numpy restatement
+    ("yl_aug.hip", ["-ffp-contract=off"], "yl_aug.o"),
     # evaluation consumers: python-float / numpy-float32 exact IoU arithmetic
     ("yl_eval.hip", ["-ffp-contract=off"], "yl_eval.o"),
     # tracker: float32 scalar arithmetic of the reference's bbox conversions / IoU, op by op
