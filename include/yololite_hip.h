@@ -321,6 +321,16 @@ yl_status yl_get_option(const yl_ctx* ctx, const char* name, int32_t* value);
  * "compiler" (program.py) asks this instead of mirroring the kernels' shape tables.                                */
 int32_t yl_query_fused_block(int32_t c_in, int32_t c_mid, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t out_h,
                              int32_t out_w);
+/* Host-side query (additive), no device needed: which form of yl_ir_kernel runs a fused block that yl_query_fused_block
+ * reports as 1, on `batch` fp32 images per launch with an in_h x in_w block input, an up_h x up_w FPN addend of c_mid channels
+ * (0 x 0: none) and the activation ids of the projection (act), the depthwise conv (dw_act) and the expansion (act2)?
+ * 0: the kernel has no instantiation for the shape, 1: its first form (any activation, 64-bit addresses), 2: its second form
+ * (all three activations none / ReLU / ReLU6 and every tensor within 32-bit byte offsets; same results bit for bit).
+ * shape, if not NULL, receives the seven template arguments of the instantiation: input k-blocks, n-tile bucket, dw k,
+ * dw stride, m-tiles per wave, wave rows, wave columns.  The launcher takes the same decision from the same function.     */
+int32_t yl_query_ir_form(int32_t c_in, int32_t c_mid, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t out_h, int32_t out_w,
+                         int32_t batch, int32_t in_h, int32_t in_w, int32_t up_h, int32_t up_w, int32_t act, int32_t dw_act,
+                         int32_t act2, int32_t* shape);
 /* Host-side query (ABI v5): can a depthwise dw_k x dw_k (stride dw_stride) conv on c_in channels be the PROLOGUE of the 1x1
  * conv c_in -> c_out that follows it (yl_layer.dw_k > 0; timm `conv_dw` -> `conv_pwl`, DWConvBlock model_v2.py:23-39), output
  * out_h x out_w?  2: the streamed-tap kernel takes it (yl_conv_dws_kernel: >= 192 depthwise channels, 7..22 output n-tiles,

@@ -1442,6 +1442,13 @@ int32_t yl_query_fused_block(int32_t c_in, int32_t c_mid, int32_t c_out, int32_t
   return 0;
 }
 
+int32_t yl_query_ir_form(int32_t c_in, int32_t c_mid, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t out_h, int32_t out_w,
+                         int32_t batch, int32_t in_h, int32_t in_w, int32_t up_h, int32_t up_w, int32_t act, int32_t dw_act,
+                         int32_t act2, int32_t* shape) {
+  if (c_in < 1 || c_mid < 1 || c_out < 1 || out_h < 1 || out_w < 1 || batch < 1 || in_h < 1 || in_w < 1 || up_h < 0 || up_w < 0) return 0;
+  return yl_ir_form(c_in, c_mid, c_out, dw_k, dw_stride, out_h, out_w, batch, in_h, in_w, up_h, up_w, act, dw_act, act2, shape);
+}
+
 int32_t yl_query_dw_prologue(int32_t c_in, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t out_h, int32_t out_w) {
   if (c_in < 1 || c_out < 1 || dw_k < 1 || dw_stride < 1 || out_h < 1 || out_w < 1) return 0;
   if (yl_dws_supported(c_in, c_out, dw_k, dw_stride, out_h, out_w)) return 2;

@@ -48,6 +48,7 @@
 #define yl_ir_kernel YL_LP_NAME(yl_ir_kernel)
 #define yl_launch_conv_ir YL_LP_NAME(yl_launch_conv_ir)
 #define yl_ir_supported YL_LP_NAME(yl_ir_supported)
+#define yl_ir_form YL_LP_NAME(yl_ir_form)
 #endif
 #include <stdlib.h>
 #include <type_traits>
@@ -1654,8 +1655,36 @@ struct YlIrLds {
         bytes((b2l + (size_t)KB * 16) * 4) {}
 };
 
-template <int KBI /*ceil(C1/16)*/, int NT, int DK, int DS, int MT, int RBN /*wave rows*/, int CBN /*wave columns*/>
-__global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 3 && NT <= 3) ? 3 : 2) void yl_ir_kernel(YlConvP p) {
+// Two forms of one text.  CLAMP = false is the kernel as it was first written and takes every case.  CLAMP = true (the launcher
+// picks it when act, act2 and dw_act are all clamp-type -- none / ReLU / ReLU6, !YL_SMOOTH -- and the block input, the FPN
+// addend and the expansion weights lie within 32-bit byte offsets) is the same arithmetic with less beside the MFMAs:
+//   - the activation is yl_clamp4 alone: exactly what yl_actc evaluates for a clamp-type id (yl_ir_act below), so no SiLU code
+//     and no activation branch is compiled into the slab loop;
+//   - the block input, the expansion weights and the FPN addend are read through raw buffer descriptors: a 32-bit byte offset per
+//     lane, fixed per workgroup (weights) or per tile (halo pixels), + a scalar offset per slab -- no 64-bit vector address
+//     arithmetic and no pointer select against p.zeros per slab.  A halo pixel outside the image carries an out-of-range offset
+//     and reads zeros from the range check, as it read p.zeros; the channel tails carry one where a tail can be: the last input
+//     k-block (once per tile), the last slab of the addend.  The projection weights' LDS-DMA requests stay global loads (32-bit
+//     index arithmetic), waited for at the slab barrier as before.
+// Same k order, tap order, fma chains and epilogues: the two forms are bit-identical (tests/test_ir_forms_gpu.py).
+// Measured and NOT in the second form (one-stream medians at edge_n 640^2, B = 64, us: UIB 40x40 / lateral3 / lateral4; parent
+// 47.1 / 170.4 / 60.3, the form above 43.4 / 163.4 / 57.2): the 3 x 3 tap loop unrolled to immediates, a row at a time where
+// registers are tight, 54.4 / 171.1 / 125.4, with the taps as v_pk_fma_f32 by name 45.1 / 173.7 / 59.6; packed taps in the rolled
+// loop with empty halo slots skipped and full m-tiles stored unmasked 46.0 / 182.6 / 61.1; the skip and the unmasked store alone
+// 44.8 / 171.9 / 58.3; `up` decided once per slab instead of per m-tile: no difference.  The static vector-instruction count of
+// the slab loop fell to a third in all of them -- it is not what these kernels wait for (profiles/README.md, ir_mix_*).
+template <bool CLAMP>
+__device__ __forceinline__ f32x4 yl_ir_act(f32x4 v, int act, float lo, float hi) {
+  if constexpr (CLAMP) return yl_clamp4(v, lo, hi);      // == yl_actc(v, act, lo, hi) for !YL_SMOOTH(act): its second return
+  else return yl_actc(v, act, lo, hi);
+}
+// waves per SIMD the kernel is compiled for.  The second form promises what the first form reaches: <3,6,3,1,1> asks for 2 and
+// fits 3 (163 VGPRs)
+constexpr int yl_ir_waves(int kbi, int nt, int dk, int ds, int mt, bool clamp) {
+  return (dk == 3 && ds * mt <= 2 && kbi <= 3 && (nt <= 3 || (clamp && ds * mt == 1))) ? 3 : 2;
+}
+template <int KBI /*ceil(C1/16)*/, int NT, int DK, int DS, int MT, int RBN /*wave rows*/, int CBN /*wave columns*/, bool CLAMP>
+__global__ __launch_bounds__(RBN * CBN * 64, yl_ir_waves(KBI, NT, DK, DS, MT, CLAMP)) void yl_ir_kernel(YlConvP p) {
   constexpr int NWV = RBN * CBN, NTH = NWV * 64;                   // waves / threads per workgroup
   constexpr int TH = 4 * RBN, TW = 4 * MT * CBN;                   // workgroup tile: every wave a 4 x 4 MT block
   constexpr int HH = (TH - 1) * DS + DK, HW = (TW - 1) * DS + DK, HN = HH * HW;
@@ -1716,8 +1745,28 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
     tile = blockIdx.x; tend = ntiles; tstride = gridDim.x;
   }
   auto load_proj = [&](int kb, int buf) {                           // projection weights of slab kb -> LDS (asynchronous)
-    for (int nt = wave; nt < NT; nt += NWV)
-      yl_glds16(wg + ((size_t)kb * NTtot + (nt < NTtot ? nt : NTtot - 1)) * 64 + lane, wpl + ((size_t)buf * NT + nt) * 64);
+    for (int nt = wave; nt < NT; nt += NWV) {
+      if constexpr (CLAMP) yl_glds16(wg + (unsigned)((kb * NTtot + (nt < NTtot ? nt : NTtot - 1)) * 64) + (unsigned)lane, wpl + (buf * NT + nt) * 64);
+      else yl_glds16(wg + ((size_t)kb * NTtot + (nt < NTtot ? nt : NTtot - 1)) * 64 + lane, wpl + ((size_t)buf * NT + nt) * 64);
+    }
+  };
+  // second form: the block input, the FPN addend and the expansion weights through raw buffer descriptors (see yl_conv_dwk_kernel):
+  // a 32-bit byte offset per lane + a scalar offset per slab; an offset of 2^31 is out of range and reads zeros
+  constexpr int ESZ = (int)sizeof(yl_act_t);
+  constexpr unsigned OOR = 0x80000000u;
+  const int lane16 = lane * 16;
+  __amdgpu_buffer_rsrc_t xrs, urs, wrs;
+  if constexpr (CLAMP) {
+    xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<yl_act_t*>(xin), 0, p.B * H * W * C1 * ESZ, 0x00020000);
+    urs = __builtin_amdgcn_make_buffer_rsrc(const_cast<yl_act_t*>(up ? up : xin), 0, up ? p.B * p.UH * p.UW * Cmid * ESZ : 0, 0x00020000);
+    wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<f32x4*>(w2g), 0, KBI * KB * 1024, 0x00020000);
+  }
+  auto bld4 = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, int soff) {   // four channels of an activation tensor
+#if YL_F16S
+    return __builtin_convertvector(__builtin_bit_cast(yl_h16x4, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, soff, 0)), f32x4);
+#else
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, soff, 0));
+#endif
   };
   unsigned gs = 0;                                                  // slabs started by this workgroup (buffer = gs & 1)
   if (tile < tend) load_proj(0, 0);
@@ -1725,7 +1774,8 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
 
   // (wi is never read.  Without this second induction variable the compiler emits the loop differently; it stays until the
   // kernel's code is next allowed to change.)
-  for (int wi = 0; tile < tend; tile += tstride, ++wi) {
+  // (the first form only; the second has no such variable)
+  for (int wi = 0; tile < tend; tile += tstride, wi += CLAMP ? 0 : 1) {
     const int b = tile / tiles_img;
     const int trem = tile - b * tiles_img;
     const int tyi = trem / twn, txi = trem - tyi * twn;
@@ -1743,10 +1793,20 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
     f32x4 xh[HMW][KBI];
     bool h_in[HMW];
     long uoff[HMW];
+    unsigned uo[HMW];                                                // second form: byte offset of the addend, out of range outside the image
 #pragma unroll
     for (int j = 0; j < HMW; ++j) {
       const int iy = iy0 + h_r[j], ix = ix0 + h_c[j];
       h_in[j] = h_ok[j] && iy >= 0 && iy < H && ix >= 0 && ix < W;
+      if constexpr (CLAMP) {
+        uo[j] = OOR;
+        if (up && h_in[j]) uo[j] = (unsigned)(((((b * p.UH + (iy * p.UH) / H) * p.UW + (ix * p.UW) / W) * Cmid) + 4 * kq) * ESZ);
+        const unsigned xo = h_in[j] ? (unsigned)((((b * H + iy) * W + ix) * C1 + 4 * kq) * ESZ) : OOR;
+#pragma unroll
+        for (int kbi = 0; kbi < KBI; ++kbi)                          // only the last k-block can hold a channel tail
+          xh[j][kbi] = bld4(xrs, ((kbi + 1 < KBI || (kbi * 16 + 4 * kq) < C1) ? xo : OOR) + kbi * 16 * ESZ, 0);
+        continue;
+      }
       uoff[j] = 0;
       if (up && h_in[j]) uoff[j] = ((((long)b * p.UH + (iy * p.UH) / H) * p.UW + (ix * p.UW) / W) * Cmid) + 4 * kq;
       const yl_act_t* src = xin + (((size_t)b * H + iy) * W + ix) * C1 + 4 * kq;
@@ -1767,14 +1827,22 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
       }
     f32x4 we[KBI], wn[KBI];
 #pragma unroll
-    for (int kbi = 0; kbi < KBI; ++kbi) wn[kbi] = w2g[((size_t)kbi * KB + 0) * 64 + lane];
+    for (int kbi = 0; kbi < KBI; ++kbi) {
+      if constexpr (CLAMP) wn[kbi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, kbi * KB * 1024, 0));
+      else wn[kbi] = w2g[((size_t)kbi * KB + 0) * 64 + lane];
+    }
     // FPN lateral: the addend of slab kb + 1 (the nearest-upsampled coarser level at the lane's halo pixels) is requested
     // one slab ahead like the expansion weights -- requested where it is used, every slab began with a wait for a
     // fragment-shaped load from L2 in front of its first MFMA (it initialises the accumulator)
     // (one register set: m-tile j's addend of slab kb + 1 is requested right behind the MFMAs that consumed slab kb's)
     f32x4 un[HMW];
     auto load_up = [&](int kb, int j) {
-      return yl_ld4((h_in[j] && kb * 16 + 4 * kq < Cmid) ? up + uoff[j] + kb * 16 : p.zeros);
+      if constexpr (CLAMP) {
+        // only the last slab can hold a channel tail
+        return bld4(urs, (kb + 1 < KB || kb * 16 + 4 * kq < Cmid) ? uo[j] : OOR, kb * 16 * ESZ);
+      } else {
+        return yl_ld4((h_in[j] && kb * 16 + 4 * kq < Cmid) ? up + uoff[j] + kb * 16 : p.zeros);
+      }
     };
     if (up) {
 #pragma unroll
@@ -1786,7 +1854,10 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
       for (int kbi = 0; kbi < KBI; ++kbi) we[kbi] = wn[kbi];
       if (kb + 1 < KB) {
 #pragma unroll
-        for (int kbi = 0; kbi < KBI; ++kbi) wn[kbi] = w2g[((size_t)kbi * KB + kb + 1) * 64 + lane];
+        for (int kbi = 0; kbi < KBI; ++kbi) {
+          if constexpr (CLAMP) wn[kbi] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane16, (kbi * KB + kb + 1) * 1024, 0));
+          else wn[kbi] = w2g[((size_t)kbi * KB + kb + 1) * 64 + lane];
+        }
       }
       // ---- E: expansion slab on the wave's halo m-tiles -> LDS
       const f32x4 eb = yl_ld4(b2l + kb * 16 + 4 * kq);
@@ -1803,7 +1874,7 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
           yl_mma_step<1, 1>(wq1, xq1, e);
         }
         if (up && kb + 1 < KB) un[j] = load_up(kb + 1, j);
-        const f32x4 v = yl_sel4(h_in[j], yl_actc(e[0][0] + eb, act2, elo, ehi));   // zero padding of the EXPANDED tensor
+        const f32x4 v = yl_sel4(h_in[j], yl_ir_act<CLAMP>(e[0][0] + eb, act2, elo, ehi));   // zero padding of the EXPANDED tensor
         if (h_ok[j]) *reinterpret_cast<f32x4*>(sb + h_lo[j]) = v;
       }
       __syncthreads();                 // slab `buf` complete; the projection weights of this slab have landed
@@ -1829,7 +1900,7 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
 #pragma unroll 1
       for (int dy = 0; dy < DK; ++dy) tap_row(dy);                   // one tap row at a time bounds the register footprint
 #pragma unroll
-      for (int mt = 0; mt < MT; ++mt) xq[mt] = yl_actc(xq[mt], dw_act, dlo, dhi);
+      for (int mt = 0; mt < MT; ++mt) xq[mt] = yl_ir_act<CLAMP>(xq[mt], dw_act, dlo, dhi);
       // channel tail (c >= Cmid): the packed projection weights of those k slots are zero, no select needed.  The slab channels
       // there are computed from the block input with zero expansion weights and bias; that input is masked at C1 and the halo
       // stays inside the tile's image (h_in), so they can only carry this image's own non-finite values, never a neighbour's
@@ -1840,19 +1911,20 @@ __global__ __launch_bounds__(RBN * CBN * 64, (DK == 3 && DS * MT <= 2 && KBI <= 
       for (int nt = 0; nt < NT; ++nt) wq[nt] = wrow[nt * 64];
       yl_mma_step<NT, MT>(wq, xq, acc);
     }
-    if (!pre_add && (p.res || YL_SMOOTH(p.act))) yl_epi_generic<NT, MT>(p, acc, px, 0, kq);
+    if (!pre_add && (p.res || (!CLAMP && YL_SMOOTH(p.act)))) yl_epi_generic<NT, MT>(p, acc, px, 0, kq);
     else yl_epi_fast<NT, MT>(p, acc, px, 0, kq, lo, hi, true);
   }
 }
 
-template <int KBI, int NT, int DK, int DS, int MT, int RBN, int CBN>
-static hipError_t ir_go(const YlConvP& p, hipStream_t st) {
+template <int KBI, int NT, int DK, int DS, int MT, int RBN, int CBN, bool CLAMP>
+static hipError_t ir_go(const YlConvP& p, hipStream_t st, bool second) {
+  if (CLAMP && !second) return hipErrorNotSupported;                 // SiLU somewhere, or past 32-bit offsets: the first form runs
   const size_t lds = YlIrLds(DK, DS, MT, RBN, CBN, NT, p.KB).bytes;
   const long ntiles = (long)p.B * (p.OH / (4 * RBN)) * (p.OW / (4 * MT * CBN));
-  int gx = yl_resident_blocks((const void*)yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>, RBN * CBN * 64, lds, 8);
+  int gx = yl_resident_blocks((const void*)yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN, CLAMP>, RBN * CBN * 64, lds, 8);
   if (gx > ntiles) gx = (int)ntiles;
   if (gx >= 8) gx &= ~7;
-  hipLaunchKernelGGL((yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN>), dim3(gx), dim3(RBN * CBN * 64), lds, st, p);
+  hipLaunchKernelGGL((yl_ir_kernel<KBI, NT, DK, DS, MT, RBN, CBN, CLAMP>), dim3(gx), dim3(RBN * CBN * 64), lds, st, p);
   return hipGetLastError();
 }
 
@@ -1878,13 +1950,40 @@ bool yl_ir_supported(int c1, int cmid, int n, int dk, int ds, int oh, int ow) {
   return false;
 }
 
+// The one decision of yl_launch_conv_ir and yl_query_ir_form: 0 = no instantiation, 1 = the first form of the instantiation
+// written to shape[7] (if given), 2 = its second form (CLAMP): all three activations clamp-type and the block input, the FPN
+// addend (uh x uw x cmid per image; uh = 0: none) and both weight images within 32-bit byte offsets -- the kernel adds a
+// lane's float4 and one k-block to an offset, hence the margin.  Anything else keeps the first form.
+int yl_ir_form(int c1, int cmid, int n, int dk, int ds, int oh, int ow, int batch, int h, int w, int uh, int uw, int act,
+               int dw_act, int act2, int* shape) {
+  const int kbi = (c1 + 15) / 16, nt = (n + 15) / 16, KB = (cmid + 15) / 16;
+  const size_t lim = ((size_t)1 << 31) - 4096, e = sizeof(yl_act_t);
+  const bool second = !YL_SMOOTH(act) && !YL_SMOOTH(dw_act) && !YL_SMOOTH(act2) && batch > 0 && h > 0 && w > 0 && uh >= 0 && uw >= 0 &&
+                      (size_t)batch * h * w * c1 * e < lim && (size_t)batch * uh * uw * cmid * e < lim &&
+                      (size_t)kbi * KB * 1024 < lim && (size_t)KB * nt * 1024 < lim;
+#define YL_IR_FORM(A, B, C, D, E, R, S)                                                                              \
+  if (kbi == A && nt <= B && nt > YL_IR_BUCKET_LO(B) && dk == C && ds == D && (oh % (4 * R)) == 0 &&                    \
+      (ow % (4 * E * S)) == 0 && YlIrLds(C, D, E, R, S, B, KB).bytes <= YlIrLds::LIMIT) {                                \
+    const int sh[7] = {A, B, C, D, E, R, S};                                                                         \
+    for (int i = 0; shape && i < 7; ++i) shape[i] = sh[i];                                                           \
+    return second ? 2 : 1;                                                                                           \
+  }
+  YL_IR_SHAPES(YL_IR_FORM)
+#undef YL_IR_FORM
+  return 0;
+}
+
 hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st) {
   if (p.C1 <= 0 || p.k != 1 || p.dw_k == 0 || (p.N & 3)) return hipErrorNotSupported;
   const int kbi = (p.C1 + 15) / 16, nt = p.NTtot;
+  const bool second = yl_ir_form(p.C1, p.Cin, p.N, p.dw_k, p.dw_stride, p.OH, p.OW, p.B, p.H, p.W, p.up ? p.UH : 0, p.up ? p.UW : 0,
+                                 p.act, p.dw_act, p.act2, nullptr) == 2;
 #define YL_IR_RUN(A, B, C, D, E, R, S)                                                                               \
   if (kbi == A && nt <= B && nt > YL_IR_BUCKET_LO(B) && p.dw_k == C && p.dw_stride == D && (p.OH % (4 * R)) == 0 &&     \
-      (p.OW % (4 * E * S)) == 0 && YlIrLds(C, D, E, R, S, B, p.KB).bytes <= YlIrLds::LIMIT)                                 \
-    return ir_go<A, B, C, D, E, R, S>(p, st);
+      (p.OW % (4 * E * S)) == 0 && YlIrLds(C, D, E, R, S, B, p.KB).bytes <= YlIrLds::LIMIT) {                               \
+    const hipError_t e2 = ir_go<A, B, C, D, E, R, S, true>(p, st, second);                                           \
+    return e2 != hipErrorNotSupported ? e2 : ir_go<A, B, C, D, E, R, S, false>(p, st, second);                        \
+  }
   YL_IR_SHAPES(YL_IR_RUN)
 #undef YL_IR_RUN
   return hipErrorNotSupported;
@@ -3227,7 +3326,7 @@ hipError_t yl_convc_init() {
   const auto cap = [&e](const auto& kernels, size_t bytes) { if (e == hipSuccess) e = yl_set_lds_cap(kernels, bytes); };
 #define YL_KXK_CAP(A, B, C) cap(yl_conv_kxk_kernel<A, B, C>, YlKxkLds::LIMIT);
   YL_KXK_SHAPES(YL_KXK_CAP)
-#define YL_IR_CAP(A, B, C, D, E, R, S) cap(yl_ir_kernel<A, B, C, D, E, R, S>, YlIrLds::LIMIT);
+#define YL_IR_CAP(A, B, C, D, E, R, S) cap(yl_ir_kernel<A, B, C, D, E, R, S, false>, YlIrLds::LIMIT); cap(yl_ir_kernel<A, B, C, D, E, R, S, true>, YlIrLds::LIMIT);
   YL_IR_SHAPES(YL_IR_CAP)
   cap(pws_kernels, YlPwsLds::LIMIT);
   cap(pws_dec_kernels, YlPwsLds::LIMIT);

@@ -19,6 +19,10 @@
 bool yl_stemblock_supported(int c1, int c2, int c3);
 bool yl_uib_supported(int c1, int cmid, int n, int dk);
 bool yl_ir_supported(int c1, int cmid, int n, int dk, int ds, int oh, int ow);
+// which form of yl_ir_kernel runs a block yl_ir_supported accepts (0: none, 1: first, 2: second -- clamp-type activations, 32-bit
+// offsets) and, in shape[7] if given, the instantiation; h x w input, uh x uw FPN addend (0: none).  fp32 tensors.
+int yl_ir_form(int c1, int cmid, int n, int dk, int ds, int oh, int ow, int batch, int h, int w, int uh, int uw, int act,
+               int dw_act, int act2, int* shape);
 bool yl_dws_supported(int cin, int n, int dk, int ds, int oh, int ow);
 
 // ---- Winograd F(2x2,3x3): which kernel form runs a dense 3x3 stride-1 pad-1 layer (yl_convc.hip) ----
