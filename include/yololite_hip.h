@@ -1010,14 +1010,17 @@ yl_status yl_dneck_conv3x3(yl_dneck* h, int32_t pass, uint32_t mode, const float
  *     cn:   1x1 cin -> cout, BN, ReLU   (held in the pw_exp entry of the tables; mid is ignored)
  * A depthwise k x k pads (k - 1) / 2 on every side: S_out = (S + 2 p - k) / s + 1, odd S under stride 2 included.  Every
  * channel count is a multiple of 4, block i's cin is block i - 1's cout, s == 2 needs a depthwise unit to carry it and
- * eps > 0: anything else is YL_ERR_INVALID from a host-side check before any device call.  ReLU is the only activation;
- * TF-SAME padding, squeeze-excite and layer-scale do not exist here.
+ * eps > 0: anything else is YL_ERR_INVALID from a host-side check before any device call.
+ * A handle's VARIANT (yl_variant_stage_set, below) replaces ReLU by ReLU6 and the symmetric padding by TF-SAME's; a uir
+ * block with a = 0 is then timm's InvertedResidual without squeeze-excite (conv_pw, conv_dw, conv_pwl), which is what
+ * the EfficientNet-Lite stages are made of.  Squeeze-excite, SiLU and layer-scale do not exist here.
  * Parameters are read in PyTorch layout from the caller's tensors on every call, at any 4-byte boundary (depthwise
  * [C][1][k][k], 1x1 [out][in][1][1]); x / out / gy / dx are 16-byte aligned (else YL_ERR_UNSUPPORTED).
  * The depthwise passes: forward, one thread per output pixel x 4 channels, taps in (ky, kx) order, fp32 sum from zero;
  * input gradient as a gather, one thread per INPUT pixel x 4 channels summing, in (ky, kx) order, the taps whose
  * (i + p - ky) is a multiple of the stride; weight gradient as float64 partials per tile of stat_rows OUTPUT rows and
- * their sum in tile order.  The 1x1 convolutions are the heads' GEMM (v_mfma_f32_16x16x4_f32) in all three passes.
+ * their sum in tile order (under TF-SAME p is the leading pad, see yl_variant_stage_set; tap order and sums are the same).
+ * The 1x1 convolutions are the heads' GEMM (v_mfma_f32_16x16x4_f32) in all three passes.
  * BatchNorm numerics are the heads' with eps from the configuration: statistics in float64 partials per tile of
  * stat_rows rows summed in tile order, biased variance to normalise, unbiased for running_var, momentum 0.1,
  * num_batches_tracked += 1; without YL_HEAD_TRAIN the running statistics are used and nothing is updated.
@@ -1104,6 +1107,30 @@ yl_status yl_stage_backward(yl_stage* h, const yl_stage_tensors* params, const y
 yl_status yl_stage_depthwise(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k,
                              int32_t stride, int32_t batch, int32_t size, int32_t channels, void* stream,
                              int32_t* launches);
+/* ---- The variant of a stage: what the EfficientNet-Lite family (tf_efficientnet_lite0..4) needs of it.
+ * `act` is YL_STAGE_ACT_RELU (a new handle's) or YL_STAGE_ACT_RELU6: what every activated unit (pw_exp, dw_mid, cn) runs
+ * behind its BatchNorm.  ReLU6 is h = min(max(y, 0), 6); its backward passes dh where 0 < h < 6, both strict (torch's
+ * hardtanh_backward), read off the saved output as ReLU's mask is.
+ * `same` is 0 (a new handle's: (k - 1) / 2 zeros on every side) or 1: TensorFlow's SAME padding of every depthwise unit.  For
+ * odd k its output size is ceil(S / s), which is S_out above, so yl_stage_plan, the arenas and every tile count hold for both.
+ * What differs is the pad in front of the first row and column: total = max((S_out - 1) s + k - S, 0), of which the leading
+ * side gets total / 2 rounded down: (k - 1) / 2 - 1 when s == 2 and S is even, (k - 1) / 2 otherwise, so only strided
+ * depthwise units over an even S change.  Forward: tap ky of output row i reads input row i s + ky - p; input gradient: input
+ * row i gathers the taps whose (i + p - ky) is a multiple of s; the weight gradient reads the forward's rows.  Tap order,
+ * fp32 sums from zero and float64 partials are those of the symmetric form, which runs the same kernels with p = (k - 1) / 2
+ * and gives the bits it gave before the variant existed.
+ * Any other value of either argument is YL_ERR_INVALID from a host-side check and changes nothing; with a forward held for
+ * backward the setter is YL_ERR_STATE (the backward runs in the variant of its forward, and a forward stays held until
+ * the next one): set the variant before the first forward, or behind a forward without YL_HEAD_SAVE.  _get: either
+ * pointer may be NULL. */
+#define YL_STAGE_ACT_RELU 0
+#define YL_STAGE_ACT_RELU6 1
+yl_status yl_variant_stage_set(yl_stage* h, int32_t act, int32_t same);
+yl_status yl_variant_stage_get(const yl_stage* h, int32_t* act, int32_t* same);
+/* yl_stage_depthwise (which is same = 0) with the padding chosen: same arguments, launches and alignment rules. */
+yl_status yl_variant_stage_depthwise(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k,
+                                     int32_t stride, int32_t batch, int32_t size, int32_t channels, int32_t same,
+                                     void* stream, int32_t* launches);
 
 /* ---- trainable dense stem: a stack of dense convolutions, each followed by BatchNorm2d and ReLU --------------------------
  * Forward and backward of up to YL_STEM_MAX_UNITS units, fp32 throughout.  A unit is a bias-free dense k x k convolution,

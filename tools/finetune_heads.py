@@ -6,7 +6,7 @@
 
     python tools/finetune_heads.py --weights in.pt --data DIR --out out.pt [--num-classes N] [--names a,b,c]
                                    [--epochs 10] [--batch 16] [--lr 1e-3] [--optimizer adamw] [--grad-clip 10]
-                                   [--train-neck [--amp fp16|bf16] [--train-tail [--lr-tail 1e-4]]] [--amp-heads fp16|bf16]
+                                   [--train-neck [--amp fp16|bf16] [--train-tail [--lr-tail 1e-4] [--train-mid]]] [--amp-heads fp16|bf16]
                                    [--train-neck --train-backbone [--lr-backbone 1e-4]]
                                    [--amp-backbone fp16|bf16]
                                    [--augment [--mosaic-p 0.2] [--aug-seed 0]]
@@ -41,7 +41,15 @@ parameters are a FusedTrainStep group of their own with the rate --lr-tail (defa
 into the output.  The tail is fp32; --amp / --amp-heads go with it: nothing in the code ties the precision of the
 neck's or the heads' GEMMs to the tail's, and the loss scale reaches its gradients through the chain like any others.
 
-With --train-backbone (needs --train-neck, implies --train-tail; the same backbones) the WHOLE backbone is trained:
+For the EfficientNet-Lite backbones (tf_efficientnet_lite0..4: yololite_n / s / m / l / xl) --train-tail picks
+irops.EfficientNetLiteTail through irops.tail_for (timm's `ir` blocks under ReLU6 and TF-SAME padding, arch stages 5 and 6),
+e.g. --synthetic yololite_n --train-neck --train-tail.  --train-mid (needs --train-tail; this family only) trains the
+C3 -> C4 stage as well (irops.EfficientNetLiteMid, arch stages 3 and 4): `c3 = model.features(x)[0]; c4 = mid(c3);
+c5 = tail(c4)`, torch sums the two gradients that meet at C4; its parameters are a group of their own with --lr-tail.
+--train-backbone is refused for this family: its stem is a dense 3x3 under TF-SAME and its stage 0 a `ds` block whose
+1x1 has no activation, neither of which the trainable modules have; stages 0..2 stay frozen in the executor.
+
+With --train-backbone (needs --train-neck, implies --train-tail; the mobilenetv4_conv_small backbones) the WHOLE backbone is trained:
 stageops.MobileNetV4Backbone holds the stem (stemops.BackboneStem, csrc/yl_stem.hip: image -> C3), the C3 -> C4 stage
 (stageops.BackboneMid) and the tail, starts from the checkpoint's `backbone.*` entries, and the step runs
 `neck(backbone(x))`: the executor is out of the loop.  The backbone's parameters are a FusedTrainStep group of their own
@@ -174,7 +182,9 @@ def main():
     ap.add_argument("--train-neck", action="store_true", help="train the FPN neck (laterals, smooth blocks) as well")
     ap.add_argument("--train-tail", action="store_true",
                     help="with --train-neck: train the backbone's last stage (C4 tap -> C5 tap) as well")
-    ap.add_argument("--lr-tail", type=float, default=0.0, help="learning rate of the tail's parameters (default: --lr)")
+    ap.add_argument("--lr-tail", type=float, default=0.0, help="learning rate of the tail's (and the mid's) parameters (default: --lr)")
+    ap.add_argument("--train-mid", action="store_true",
+                    help="with --train-tail, EfficientNet-Lite backbones: train the C3 tap -> C4 tap stage as well")
     ap.add_argument("--train-backbone", action="store_true",
                     help="with --train-neck: train the whole backbone (image -> C3, C4, C5); implies --train-tail")
     ap.add_argument("--lr-backbone", type=float, default=0.0, help="learning rate of the backbone's parameters (default: --lr)")
@@ -200,6 +210,8 @@ def main():
         raise SystemExit("--amp sets the precision of the trainable dense neck: it needs --train-neck")
     if a.train_tail and not a.train_neck:
         raise SystemExit("--train-tail feeds the tail's C5 to the trainable neck: it needs --train-neck")
+    if a.train_mid and not a.train_tail:
+        raise SystemExit("--train-mid feeds the stage's C4 to the trainable tail: it needs --train-tail")
     if a.train_backbone and not a.train_neck:
         raise SystemExit("--train-backbone feeds the backbone's maps to the trainable neck: it needs --train-neck")
     if a.synthetic:
@@ -225,15 +237,26 @@ def main():
     heads.to(a.device).train()
     # DetectNeck (arch YOLOLiteMS_CPU) refuses a reduced precision and says why
     neck = ya.neck_for(meta, sd, precision=a.amp or "fp32").to(a.device).train() if a.train_neck else None
-    # BackboneTail refuses, by name, a backbone whose last stage is not made of UIB / 1x1 ConvBnAct blocks
+    lite = ya.irops.is_lite(meta)
+    if lite and a.train_backbone:
+        raise SystemExit("--train-backbone is not implemented for the EfficientNet-Lite backbones: the stem is a dense 3x3 under "
+                         "TF-SAME padding and stage 0 a `ds` block whose 1x1 has no activation; --train-tail [--train-mid] "
+                         "trains stages 3..6")
+    if a.train_mid and not lite:
+        raise SystemExit("--train-mid is the EfficientNet-Lite backbones' (yololite_n .. xl); the mobilenetv4_conv_small "
+                         "backbones train their C3 -> C4 stage with --train-backbone")
+    # tail_for picks the tail of the backbone's family and refuses, by name, a backbone whose last stage neither has
     bprec = a.amp_backbone or "fp32"
-    tail = ya.BackboneTail.from_state_dict(meta, sd, precision=bprec).to(a.device).train() if a.train_tail and not a.train_backbone else None
+    tail = ya.tail_for(meta, sd, precision=bprec).to(a.device).train() if a.train_tail and not a.train_backbone else None
+    mid = ya.EfficientNetLiteMid.from_state_dict(meta, sd, precision=bprec).to(a.device).train() if a.train_mid else None
     # MobileNetV4Backbone (stem, C3 -> C4 stage and the tail in one) refuses the other backbone families by name as well
     backbone = ya.MobileNetV4Backbone.from_state_dict(meta, sd, precision=bprec).to(a.device).train() if a.train_backbone else None
     crit = ya.LossAF(nc, img_size, grad=True)
     params = (list(neck.parameters()) if neck is not None else []) + list(heads.parameters())
     if tail is not None:                                   # a group of its own: its rate is --lr-tail
         params = [{"params": params}, {"params": list(tail.parameters()), "lr": a.lr_tail or a.lr}]
+    if mid is not None:                                    # likewise, at the tail's rate
+        params.append({"params": list(mid.parameters()), "lr": a.lr_tail or a.lr})
     if backbone is not None:                               # likewise: --lr-backbone
         params = [{"params": params}, {"params": list(backbone.parameters()), "lr": a.lr_backbone or a.lr}]
     # fp16: dynamic loss scale (unscale, found-inf skip, growth / backoff in the step); bf16 has fp32's range: scale 1
@@ -247,7 +270,10 @@ def main():
             feats = neck(backbone(x), layout="nhwc")
         else:
             cs = model.features(x)
-            if tail is not None:                           # the executor's C5 is replaced by the trainable tail's
+            if mid is not None:                            # the executor's C4 and C5 are replaced: C4 feeds the neck and the tail
+                c4 = mid(cs[-3], layout="nhwc")
+                cs = cs[:-2] + [c4, tail(c4, layout="nhwc")]
+            elif tail is not None:                         # the executor's C5 is replaced by the trainable tail's
                 cs = cs[:-2] + [cs[-2], tail(cs[-2], layout="nhwc")]
             feats = neck(cs, layout="nhwc")
         fts.zero_grad()
@@ -294,7 +320,7 @@ def main():
             print(f"epoch {ep:3d}  mean loss {tot / max(n, 1):.4f}  ({n} batches)")
 
     out_sd = dict(sd)
-    for mod in [m for m in (backbone, tail, neck) if m is not None] + [heads]:
+    for mod in [m for m in (backbone, mid, tail, neck) if m is not None] + [heads]:
         for k, v in mod.state_dict().items():
             out_sd[k] = v.detach().cpu()
     out_sd = {k: (torch.as_tensor(v) if not torch.is_tensor(v) else v) for k, v in out_sd.items()}

@@ -4,7 +4,10 @@ torch -- the stages behind the C4 tap of oracle/backbones.py's FeatureBackbone (
 channels-last fp32 input, same weights -- in one process on one device.
 
 Shapes: edge_n (mobilenetv4_conv_small_050: C4 [64,40,40,48] -> C5 [64,20,20,480]) and edge_m (mobilenetv4_conv_small:
-C4 [32,40,40,96] -> C5 [32,20,20,960]).  One step = train-mode forward of the tail on a fixed C4 that does not require
+C4 [32,40,40,96] -> C5 [32,20,20,960]).  --model yololite_n | yololite_m times the EfficientNet-Lite tail instead
+(yololite_amd.EfficientNetLiteTail: InvertedResidual blocks under ReLU6 and TF-SAME; tf_efficientnet_lite0: C4
+[64,40,40,112] -> C5 [64,20,20,320], tf_efficientnet_lite2: C4 [32,40,40,120] -> C5 [32,20,20,352]) against the oracle's
+blocks of the same stages.  One step = train-mode forward of the tail on a fixed C4 that does not require
 grad, backward from a fixed gradient of C5 into every parameter.
 
 Block protocol: --blocks times, alternating the two sides, each block = synchronise, --steps steps, synchronise, host
@@ -18,7 +21,7 @@ error relative to rounding noise says nothing.
 With --trace only --steps steps per side are run once (for `rocprofv3 --kernel-trace --stats -- python
 tools/tail_train_time.py --trace ...`).
 
-    python tools/tail_train_time.py [--models edge_n,edge_m] [--blocks 7] [--steps 20] [--out F] [--trace]"""
+    python tools/tail_train_time.py [--models edge_n,edge_m | --model yololite_n] [--blocks 7] [--steps 20] [--out F] [--trace]"""
 import os
 import sys
 
@@ -28,7 +31,7 @@ if ROOT not in sys.path:
 
 from tools import _train_time as tt  # noqa: E402
 
-SHAPES = {"edge_n": dict(B=64, S=40), "edge_m": dict(B=32, S=40)}
+SHAPES = {"edge_n": dict(B=64, S=40), "edge_m": dict(B=32, S=40), "yololite_n": dict(B=64, S=40), "yololite_m": dict(B=32, S=40)}
 
 
 def torch_tail(backbone):
@@ -67,13 +70,14 @@ class _Only:
 def run_model(name, blocks, steps, trace):
     import torch
     import yololite_amd as ya
-    from yololite_amd import stageops
+    from yololite_amd import irops, stageops
     from yololite_amd.program import zoo_meta
     B, S = SHAPES[name]["B"], SHAPES[name]["S"]
     dev = "cuda:0"
     torch.manual_seed(3)
     meta = zoo_meta(name, num_classes=3, img_size=16 * S)
-    ours = ya.BackboneTail.from_meta(meta).to(dev).train()
+    lite = irops.is_lite(meta)
+    ours = (ya.EfficientNetLiteTail if lite else ya.BackboneTail).from_meta(meta).to(dev).train()
     sd = {k[len("backbone."):]: v for k, v in ours.state_dict().items()}
     ref = torch_tail(meta["backbone"])
     ref.load_state_dict(sd)
@@ -93,7 +97,7 @@ def run_model(name, blocks, steps, trace):
         else:
             m(x_cl).backward(gy_cl)
 
-    plan = stageops.plan(ours.in_channels, ours.blocks_cfg, B, S, ours.eps)
+    plan = (irops if lite else stageops).plan(ours.in_channels, ours.blocks_cfg, B, S, ours.eps)
     res = {"model": name, "backbone": meta["backbone"], "batch": B, "c4": [B, S, S, ours.in_channels],
            "c5": [B, So, So, ours.out_channels], "blocks_in_tail": len(ours.blocks_cfg), "steps_per_block": steps,
            "saved_bytes": plan["saved_bytes"], "workspace_bytes": plan["workspace_bytes"]}
@@ -112,4 +116,5 @@ def run_model(name, blocks, steps, trace):
 
 
 if __name__ == "__main__":
+    sys.argv = ["--models" if v == "--model" else v.replace("--model=", "--models=", 1) for v in sys.argv]    # one model: the same list
     tt.main("tail_train_time.py", "edge_n,edge_m", run_model)

@@ -22,6 +22,7 @@ from .headops import DetectHeads  # noqa: F401
 from .neckops import DetectNeck, DetectNeckMS, neck_for  # noqa: F401
 from .stageops import BackboneMid, BackboneTail, MobileNetV4Backbone, UIBStack  # noqa: F401
 from .stemops import BackboneStem, ConvStack  # noqa: F401
+from .irops import EfficientNetLiteMid, EfficientNetLiteTail, IRStack, tail_for  # noqa: F401
 from .tracker import KalmanSortTracker, TrackerBank  # noqa: F401
 from .serving import ServingPipeline  # noqa: F401
 
@@ -30,5 +31,6 @@ __all__ = ["YoloLiteHipError", "load_library", "HipContext", "YOLOLiteHIP", "bui
            "decode_anchorfree_like_train", "infer_main_postprocess", "nms", "predict_main", "predict_coco_dets", "build_program", "Program", "BACKBONES",
            "preprocess_batch", "letterbox_geometry", "build_curves_from_coco", "create_confusion_matrix",
            "coco_eval", "_coco_eval_from_lists", "coco_summary_lines", "LossAF", "targets_to_xyxy_px", "FusedTrainStep", "DetectHeads", "DetectNeck", "DetectNeckMS", "neck_for", "UIBStack", "BackboneTail", "BackboneMid", "MobileNetV4Backbone", "ConvStack", "BackboneStem",
+           "IRStack", "EfficientNetLiteTail", "EfficientNetLiteMid", "tail_for",
            "KalmanSortTracker", "TrackerBank", "ServingPipeline",
            "AugmentConfig", "ImageParams", "TrainAugmenter", "augment_batch", "compose", "sample_params", "transform_boxes"]

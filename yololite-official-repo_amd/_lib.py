@@ -213,6 +213,7 @@ class yl_dneck_plan_info(C.Structure):
 YL_STAGE_MAX_BLOCKS = 16
 YL_STAGE_UIR, YL_STAGE_CN = 0, 1
 YL_STAGE_PASS_FORWARD, YL_STAGE_PASS_DGRAD, YL_STAGE_PASS_WGRAD = 0, 1, 2
+YL_STAGE_ACT_RELU, YL_STAGE_ACT_RELU6 = 0, 1
 
 
 class yl_stage_block_cfg(C.Structure):
@@ -380,6 +381,10 @@ SYMBOLS = [
     ("yl_amp_stage_get", C.c_int32, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("yl_amp_stem_get", C.c_int32, [_vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("yl_amp_stem_conv", C.c_int32, [_vp, _vp, _vp] + [C.c_int32] * 8 + [C.c_uint32, _vp, _ip]),
+    ("yl_variant_stage_set", C.c_int32, [_vp, C.c_int32, C.c_int32]),
+    ("yl_variant_stage_get", C.c_int32, [_vp, _ip, _ip]),
+    ("yl_variant_stage_depthwise", C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.c_int32, _vp, _ip]),
     ("yl_augment", C.c_int32, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp]),
 ]
 # entries whose names carry a digit, bound like the others.  Listed apart: SYMBOLS is held, name for name, to what a

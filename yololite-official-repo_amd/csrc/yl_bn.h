@@ -1,4 +1,4 @@
-// BatchNorm2d followed by nothing, ReLU or SiLU on NHWC fp32 rows, forward and backward: the five kernels and the three
+// BatchNorm2d followed by nothing, ReLU, ReLU6 or SiLU on NHWC fp32 rows, forward and backward: the five kernels and the three
 // launch sequences that every trainable module runs -- the heads' and the depthwise neck's blocks (yl_block.h), the dense
 // neck (yl_dneck.hip), the backbone stage and the stem (yl_units.h) -- with the few primitives they are written in.  This
 // is the bottom header of the training units.  Everything lives in an anonymous namespace: each translation unit that
@@ -34,17 +34,21 @@ inline int pick_cq(int F) {              // channel quads per workgroup of the r
 inline int64_t round16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 // ---- the activation's part.  y is computed in fp32 by bn_y everywhere; the SiLU factor is recomputed from it
-constexpr int ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2;
+constexpr int ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_RELU6 = 3;
+constexpr bool act_reads_h(int act) { return act == ACT_RELU || act == ACT_RELU6; }
 __device__ __forceinline__ float bn_y(float z, float mu, float is, float gamma, float beta) { return (z - mu) * is * gamma + beta; }
 template <int ACT> __device__ __forceinline__ float act_apply(float y) {
   if constexpr (ACT == ACT_RELU) return fmaxf(y, 0.f);
+  if constexpr (ACT == ACT_RELU6) return fminf(fmaxf(y, 0.f), 6.f);
   if constexpr (ACT == ACT_SILU) return y / (1.f + expf(-y));
   return y;
 }
-// g = dh * act'(y) in T (float, or double for the column sums): ReLU reads its mask off the output h and widens dh itself;
-// SiLU forms the product with d silu / dy = s * (1 + y * (1 - s)) in float and widens that.  h is read by ReLU only, y by SiLU only
+// g = dh * act'(y) in T (float, or double for the column sums): ReLU and ReLU6 read their mask off the output h and widen dh
+// themselves (ReLU6: 0 < h < 6, both strict, torch's hardtanh_backward; h = 6 exactly where y >= 6);
+// SiLU forms the product with d silu / dy = s * (1 + y * (1 - s)) in float and widens that.  h is read by ReLU / ReLU6 only, y by SiLU only
 template <int ACT, class T> __device__ __forceinline__ T act_grad(float dh, float h, float y) {
   if constexpr (ACT == ACT_RELU) return h > 0.f ? (T)dh : (T)0;
+  if constexpr (ACT == ACT_RELU6) return (h > 0.f && h < 6.f) ? (T)dh : (T)0;
   if constexpr (ACT == ACT_SILU) {
     const float sg = 1.f / (1.f + expf(-y));
     return (T)(dh * (sg * (1.f + y * (1.f - sg))));
@@ -56,7 +60,7 @@ template <int ACT, class T> __device__ __forceinline__ T act_grad(float dh, floa
 // + 256 / CQ, ...; float64 sums per thread, summed over the row lanes in lane order by the thread of lane 0.
 // Forward (bwd = 0, the same for every ACT): sum z, sum z^2.  Backward: sum g, sum g * xhat.
 struct StatP {
-  const float *a, *h, *z, *stats;        // forward: a = z.  backward: a = dh, h = the output (read by ReLU only), z, stats
+  const float *a, *h, *z, *stats;        // forward: a = z.  backward: a = dh, h = the output (read by ReLU / ReLU6 only), z, stats
   double* part;                          // [tile][2][F]
   int M, F, CQ, bwd;
   int rows;                              // of one tile: a multiple of STAT_ROWS
@@ -89,7 +93,7 @@ __global__ __launch_bounds__(NT) void yl_bn_colstats_kernel(StatP P) {
       } else {
         const f32x4 zv = ld4(P.z + o);
         f32x4 hv = {1.f, 1.f, 1.f, 1.f};
-        if constexpr (ACT == ACT_RELU) hv = ld4(P.h + o);
+        if constexpr (act_reads_h(ACT)) hv = ld4(P.h + o);
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           float y = 0.f;
@@ -174,7 +178,7 @@ __global__ __launch_bounds__(NT) void yl_bn_apply_kernel(const float* __restrict
   st4(h + idx * 4, o);
 }
 // dz = gamma * invstd * (g - c0 - xhat * c1).  dh and dz may be one buffer (each thread reads its four values before it
-// writes them): neither is __restrict__.  h is read by ReLU only, beta by SiLU only
+// writes them): neither is __restrict__.  h is read by ReLU / ReLU6 only, beta by SiLU only
 template <int ACT>
 __global__ __launch_bounds__(NT) void yl_bn_bwd_kernel(const float* dh, const float* __restrict__ h, const float* __restrict__ z,
                                                       const float* __restrict__ stats, const float* __restrict__ coef,
@@ -185,7 +189,7 @@ __global__ __launch_bounds__(NT) void yl_bn_bwd_kernel(const float* dh, const fl
   const int c = (int)((idx * 4) % F);
   const f32x4 g = ld4(dh + idx * 4), zv = ld4(z + idx * 4);
   f32x4 hv = {1.f, 1.f, 1.f, 1.f};
-  if constexpr (ACT == ACT_RELU) hv = ld4(h + idx * 4);
+  if constexpr (act_reads_h(ACT)) hv = ld4(h + idx * 4);
   const f32x4 mu = ld4(stats + c), is = ld4(stats + F + c), c0 = ld4(coef + c), c1 = ld4(coef + F + c);
   f32x4 o;
 #pragma unroll

@@ -1,5 +1,7 @@
 // Trainable backbone stage: a stack of MobileNetV4 UIB blocks (timm UniversalInvertedResidual) and 1x1 ConvBnAct blocks,
-// forward and backward on NHWC fp32 rows (include/yololite_hip.h, yl_stage_*).
+// forward and backward on NHWC fp32 rows (include/yololite_hip.h, yl_stage_*).  A uir block with a = 0 is, unit for unit,
+// timm's InvertedResidual without squeeze-excite (conv_pw, conv_dw, conv_pwl): with the handle's variant
+// (yl_variant_stage_set: ReLU6 for ReLU, TF-SAME padding) the same walk trains the EfficientNet-Lite stages.
 //
 // The stack is flattened into UNITS, each a bias-free convolution and its BatchNorm:
 //   unit u:  z = conv(x_u)   h = bn(z) [relu] [+ the block's input, behind the last unit of a residual block]
@@ -16,14 +18,15 @@
 
 namespace {
 
-// ---- depthwise K x K, pad (K - 1) / 2, stride ST, weight [C][1][K][K].  x: [B][Sx][Sx][C], y: [B][So][So][C].
+// ---- depthwise K x K, stride ST, weight [C][1][K][K].  x: [B][Sx][Sx][C], y: [B][So][So][C].  `pb` pixels of zeros stand
+// in front of the first row and column (yl_units.h pad_begin: (K - 1) / 2, or TF-SAME's leading pad); behind the last ones as
+// many as the taps reach.
 // GRAD = false: y = conv(x); a thread owns one OUTPUT pixel x 4 channels.  GRAD = true: `src` is dy, `dst` is dx; a thread
-// owns one INPUT pixel (i, j) x 4 channels and sums, ky then kx ascending, the taps whose (i + p - ky) is a multiple of ST
-// (output row (i + p - ky) / ST): the transposed convolution as a gather.  fp32 sum from zero in tap order either way.
+// owns one INPUT pixel (i, j) x 4 channels and sums, ky then kx ascending, the taps whose (i + pb - ky) is a multiple of ST
+// (output row (i + pb - ky) / ST): the transposed convolution as a gather.  fp32 sum from zero in tap order either way.
 template <int K, int ST, bool GRAD>
 __global__ __launch_bounds__(NT) void yl_stage_dw_kernel(const float* __restrict__ src, const float* __restrict__ w,
-                                                        float* __restrict__ dst, int B, int Sx, int So, int C) {
-  constexpr int P = (K - 1) / 2;
+                                                        float* __restrict__ dst, int B, int Sx, int So, int C, int pb) {
   const int C4 = C >> 2;
   const int T = GRAD ? Sx : So, R = GRAD ? So : Sx;         // extent of the pixels the threads own / of the map read
   const long idx = (long)blockIdx.x * NT + threadIdx.x;
@@ -35,9 +38,9 @@ __global__ __launch_bounds__(NT) void yl_stage_dw_kernel(const float* __restrict
   for (int ky = 0; ky < K; ++ky) {
     int yy;
     if (!GRAD) {
-      yy = i * ST + ky - P;
+      yy = i * ST + ky - pb;
     } else {
-      const int t = i + P - ky;
+      const int t = i + pb - ky;
       if (t < 0 || (ST == 2 && (t & 1))) continue;
       yy = t / ST;
     }
@@ -46,9 +49,9 @@ __global__ __launch_bounds__(NT) void yl_stage_dw_kernel(const float* __restrict
     for (int kx = 0; kx < K; ++kx) {
       int xx;
       if (!GRAD) {
-        xx = j * ST + kx - P;
+        xx = j * ST + kx - pb;
       } else {
-        const int t = j + P - kx;
+        const int t = j + pb - kx;
         if (t < 0 || (ST == 2 && (t & 1))) continue;
         xx = t / ST;
       }
@@ -66,8 +69,8 @@ __global__ __launch_bounds__(NT) void yl_stage_dw_kernel(const float* __restrict
 // The workgroup and thread layout of the row reductions (yl_block.h); one ky row at a time, so K * 4 float64 sums per thread.
 template <int K, int ST>
 __global__ __launch_bounds__(NT) void yl_stage_dw_wgrad_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                              double* __restrict__ part, int Mo, int Sx, int So, int C, int CQ) {
-  constexpr int P = (K - 1) / 2;
+                                                              double* __restrict__ part, int Mo, int Sx, int So, int C, int CQ,
+                                                              int pb) {
   __shared__ double red[NT][K * 4];
   const int t = threadIdx.x, cq = t & (CQ - 1), rs = t / CQ, RS = NT / CQ;
   const int c = (blockIdx.y * CQ + cq) * 4;
@@ -78,12 +81,12 @@ __global__ __launch_bounds__(NT) void yl_stage_dw_wgrad_kernel(const float* __re
     double acc[K][4] = {};
     if (on)
       for (int m = m0 + rs; m < m1; m += RS) {
-        const int b = m / SS, ij = m - b * SS, i = ij / So, j = ij - i * So, yy = i * ST + ky - P;
+        const int b = m / SS, ij = m - b * SS, i = ij / So, j = ij - i * So, yy = i * ST + ky - pb;
         if (yy < 0 || yy >= Sx) continue;
         const f32x4 g = ld4(dy + (long)m * C + c);
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
-          const int xx = j * ST + kx - P;
+          const int xx = j * ST + kx - pb;
           if (xx < 0 || xx >= Sx) continue;
           const f32x4 v = ld4(x + ((long)(b * Sx + yy) * Sx + xx) * C + c);
 #pragma unroll
@@ -125,27 +128,27 @@ __global__ __launch_bounds__(NT) void yl_stage_add_kernel(float* io, const float
   st4(io + idx * 4, ld4(io + idx * 4) + ld4(g + idx * 4));
 }
 
-// ---- launches of one depthwise pass.  false: (k, stride) is not one of {3, 5} x {1, 2}
+// ---- launches of one depthwise pass with the leading pad pb.  false: (k, stride) is not one of {3, 5} x {1, 2}
 template <bool GRAD>
-bool launch_dw(hipStream_t s, const float* src, const float* w, float* dst, int k, int st, int B, int Sx, int So, int C) {
+bool launch_dw(hipStream_t s, const float* src, const float* w, float* dst, int k, int st, int pb, int B, int Sx, int So, int C) {
   const long n = (long)B * (GRAD ? Sx : So) * (GRAD ? Sx : So) * (C >> 2);
   const dim3 grid(ceil_div(n, NT)), blk(NT);
-  if (k == 3 && st == 1) hipLaunchKernelGGL((yl_stage_dw_kernel<3, 1, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C);
-  else if (k == 3 && st == 2) hipLaunchKernelGGL((yl_stage_dw_kernel<3, 2, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C);
-  else if (k == 5 && st == 1) hipLaunchKernelGGL((yl_stage_dw_kernel<5, 1, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C);
-  else if (k == 5 && st == 2) hipLaunchKernelGGL((yl_stage_dw_kernel<5, 2, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C);
+  if (k == 3 && st == 1) hipLaunchKernelGGL((yl_stage_dw_kernel<3, 1, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C, pb);
+  else if (k == 3 && st == 2) hipLaunchKernelGGL((yl_stage_dw_kernel<3, 2, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C, pb);
+  else if (k == 5 && st == 1) hipLaunchKernelGGL((yl_stage_dw_kernel<5, 1, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C, pb);
+  else if (k == 5 && st == 2) hipLaunchKernelGGL((yl_stage_dw_kernel<5, 2, GRAD>), grid, blk, 0, s, src, w, dst, B, Sx, So, C, pb);
   else return false;
   return true;
 }
 // partials over `tiles` tiles of the B * So * So output rows, then their ordered sum into dw [C][1][k][k]: 2 launches
-bool launch_dw_wgrad(hipStream_t s, const float* dy, const float* x, double* part, float* dw, int k, int st, int B, int Sx,
+bool launch_dw_wgrad(hipStream_t s, const float* dy, const float* x, double* part, float* dw, int k, int st, int pb, int B, int Sx,
                      int So, int C, int tiles) {
   const int Mo = B * So * So, cq = pick_cq(C);
   const dim3 grid(tiles, ceil_div(C >> 2, cq)), blk(NT);
-  if (k == 3 && st == 1) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<3, 1>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq);
-  else if (k == 3 && st == 2) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<3, 2>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq);
-  else if (k == 5 && st == 1) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<5, 1>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq);
-  else if (k == 5 && st == 2) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<5, 2>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq);
+  if (k == 3 && st == 1) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<3, 1>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq, pb);
+  else if (k == 3 && st == 2) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<3, 2>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq, pb);
+  else if (k == 5 && st == 1) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<5, 1>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq, pb);
+  else if (k == 5 && st == 2) hipLaunchKernelGGL((yl_stage_dw_wgrad_kernel<5, 2>), grid, blk, 0, s, dy, x, part, Mo, Sx, So, C, cq, pb);
   else return false;
   hipLaunchKernelGGL(yl_stage_dw_wsum_kernel, dim3(ceil_div((long)k * k * C, NT)), blk, 0, s, (const double*)part, tiles, C,
                      k * k, dw);
@@ -172,8 +175,13 @@ bool cfg_ok(const yl_stage_cfg* c) {
   return true;
 }
 
-// the units of cfg at (B, S) -> their number; fills the per-block plan if `bp` is given.  cfg_ok(cfg) holds
-int make_units(const yl_stage_cfg& cfg, int B, int S, Unit* us, yl_stage_block_plan* bp) {
+// the handle's variant: what an activated unit runs behind its BatchNorm, and whether the depthwise units pad as TF-SAME.
+// TF-SAME's output size is ceil(S / s), which for odd k is out_size's: sizes, arenas and tile counts do not depend on it
+struct Variant { int act, same; };
+constexpr Variant PLAIN = {ACT_RELU, 0};
+
+// the units of cfg at (B, S) under the variant v -> their number; fills the per-block plan if `bp` is given.  cfg_ok(cfg) holds
+int make_units(const yl_stage_cfg& cfg, Variant v, int B, int S, Unit* us, yl_stage_block_plan* bp) {
   int n = 0, cin = cfg.in_channels;
   for (int i = 0; i < cfg.num_blocks; ++i) {
     const yl_stage_block_cfg& b = cfg.block[i];
@@ -186,7 +194,8 @@ int make_units(const yl_stage_cfg& cfg, int B, int S, Unit* us, yl_stage_block_p
     const int n0 = n;
     auto add = [&](int slot, int dw, int relu, int k, int st, int ci, int co, int Si, int So) {
       Unit& u = us[n++];
-      u.block = i; u.slot = slot; u.dw = dw; u.planar = 0; u.relu = relu; u.k = k; u.st = st;
+      u.block = i; u.slot = slot; u.dw = dw; u.planar = 0; u.act = relu ? v.act : ACT_NONE; u.k = k; u.st = st;
+      u.pb = pad_begin(k, st, Si, v.same);
       u.cin = ci; u.cout = co; u.Sin = Si; u.Sout = So;
       u.Min = (int64_t)B * Si * Si; u.Mout = (int64_t)B * So * So;
       u.stat_rows = STAT_ROWS; u.tiles = ceil_div(u.Mout, STAT_ROWS);
@@ -218,10 +227,10 @@ int make_units(const yl_stage_cfg& cfg, int B, int S, Unit* us, yl_stage_block_p
 }
 
 // units, per-block plan (if `bp` is given) and sizes of cfg at (B, S): what yl_stage_plan reports and the walk runs on
-yl_status layout(const yl_stage_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z, yl_stage_block_plan* bp) {
+yl_status layout(const yl_stage_cfg& cfg, Variant v, int B, int S, Unit* us, int* n, Sizes* z, yl_stage_block_plan* bp) {
   const int64_t M0 = (int64_t)B * S * S;
   const bool rows_ok = M0 <= (int64_t)65535 * GEMM_ROWS;   // the GEMM's grid.y; no unit has more rows than x
-  *n = make_units(cfg, B, S, us, rows_ok ? bp : nullptr);
+  *n = make_units(cfg, v, B, S, us, rows_ok ? bp : nullptr);
   if (!rows_ok) return YL_ERR_UNSUPPORTED;
   if (!unit_sizes(us, *n, 1 << 20, z)) return YL_ERR_UNSUPPORTED;
   z->x0 = z->xsave = M0 * cfg.in_channels * 4;
@@ -233,7 +242,7 @@ yl_status layout(const yl_stage_cfg& cfg, int B, int S, Unit* us, int* n, Sizes*
 // the entries of a table in unit order -> their number (which units exist does not depend on the shape)
 int resolve(const yl_stage_cfg& cfg, const yl_stage_tensors* t, const yl_stage_unit** tab) {
   Unit us[MAX_UNITS];
-  const int n = make_units(cfg, 1, 1, us, nullptr);
+  const int n = make_units(cfg, PLAIN, 1, 1, us, nullptr);
   for (int i = 0; i < n; ++i) {
     const yl_stage_block& b = t->block[us[i].block];
     const int slot = us[i].slot;
@@ -246,18 +255,19 @@ int resolve(const yl_stage_cfg& cfg, const yl_stage_tensors* t, const yl_stage_u
 struct StagePolicy {
   static constexpr int ROT = 3;
   static constexpr bool MIXED = true;
-  static yl_status layout(const yl_stage_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z) {
-    return ::layout(cfg, B, S, us, n, z, nullptr);
+  static constexpr bool RELU6 = true;
+  template <class H> static yl_status layout(const H& h, int B, int S, Unit* us, int* n, Sizes* z) {
+    return ::layout(h.cfg, Variant{h.act, h.same}, B, S, us, n, z, nullptr);
   }
   static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers&, int mode) {
-    if (u.dw) launch_dw<false>(s, x, w, z, u.k, u.st, B, u.Sin, u.Sout, u.cout);
+    if (u.dw) launch_dw<false>(s, x, w, z, u.k, u.st, u.pb, B, u.Sin, u.Sout, u.cout);
     else launch_gemm_in<true>(mode, s, RowsScalar{w, u.cin}, RowsVec{x, u.cin}, OutRowsVec{z, u.cout}, u.cout, (int)u.Mout, u.cin, u.cin, 1);
     return 1;
   }
   static int conv_wgrad(hipStream_t s, const Unit& u, int B, const float* x, const float* dz, float* dw, const UnitBuffers& sb, int mode) {
     const int F = u.cout;
     if (u.dw) {
-      launch_dw_wgrad(s, dz, x, sb.spart, dw, u.k, u.st, B, u.Sin, u.Sout, F, u.tiles);
+      launch_dw_wgrad(s, dz, x, sb.spart, dw, u.k, u.st, u.pb, B, u.Sin, u.Sout, F, u.tiles);
     } else {                             // dW = dz^T . x
       launch_gemm_in<true>(mode, s, ColsScalar{x, u.cin}, ColsScalar{dz, F}, OutPartial{sb.wpart, (long)u.cin * F}, u.cin, F,
                            (int)u.Mout, u.wrows, u.wsplits);
@@ -270,7 +280,7 @@ struct StagePolicy {
   }
   static int conv_dgrad(hipStream_t s, const Unit& u, int B, const float* dz, const float* w, float* dx, const UnitBuffers&, int mode) {
     const int F = u.cout;
-    if (u.dw) launch_dw<true>(s, dz, w, dx, u.k, u.st, B, u.Sin, u.Sout, F);
+    if (u.dw) launch_dw<true>(s, dz, w, dx, u.k, u.st, u.pb, B, u.Sin, u.Sout, F);
     else launch_gemm_in<true>(mode, s, ColsScalar{w, u.cin}, RowsVec{dz, F}, OutRowsVec{dx, u.cin}, u.cin, (int)u.Mout, F, F, 1);   // dx = dz . W
     return 1;
   }
@@ -292,7 +302,7 @@ yl_status yl_stage_plan(const yl_stage_cfg* cfg, int32_t batch, int32_t size, yl
   Unit us[MAX_UNITS];
   Sizes z;
   int n;
-  const yl_status st = layout(*cfg, batch, size, us, &n, &z, out->block);
+  const yl_status st = layout(*cfg, PLAIN, batch, size, us, &n, &z, out->block);
   if (st != YL_OK) return st;
   const ArenaBytes b = arena_bytes(us, n, z, StagePolicy::ROT);
   out->saved_bytes = b.saved; out->nosave_bytes = b.nosave; out->workspace_bytes = b.work;
@@ -330,22 +340,44 @@ yl_status yl_stage_backward(yl_stage* h, const yl_stage_tensors* params, const y
   return units_backward<StagePolicy>(h, par, grd, n, gy_dev, dx_dev, stream, launches);
 }
 
+yl_status yl_variant_stage_set(yl_stage* h, int32_t act, int32_t same) {
+  if (!h || (act != YL_STAGE_ACT_RELU && act != YL_STAGE_ACT_RELU6) || (same != 0 && same != 1)) return YL_ERR_INVALID;
+  if (h->mem.fValid) return YL_ERR_STATE;                  // the held forward's backward runs in the variant of its forward
+  h->act = act == YL_STAGE_ACT_RELU6 ? ACT_RELU6 : ACT_RELU;
+  h->same = same;
+  return YL_OK;
+}
+
+yl_status yl_variant_stage_get(const yl_stage* h, int32_t* act, int32_t* same) {
+  if (!h) return YL_ERR_INVALID;
+  if (act) *act = h->act == ACT_RELU6 ? YL_STAGE_ACT_RELU6 : YL_STAGE_ACT_RELU;
+  if (same) *same = h->same;
+  return YL_OK;
+}
+
 yl_status yl_stage_depthwise(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k,
                              int32_t stride, int32_t batch, int32_t size, int32_t channels, void* stream,
                              int32_t* launches) {
+  return yl_variant_stage_depthwise(a_dev, b_dev, out_dev, pass, k, stride, batch, size, channels, 0, stream, launches);
+}
+
+yl_status yl_variant_stage_depthwise(const float* a_dev, const float* b_dev, float* out_dev, int32_t pass, int32_t k,
+                                     int32_t stride, int32_t batch, int32_t size, int32_t channels, int32_t same, void* stream,
+                                     int32_t* launches) {
+  if (same != 0 && same != 1) return YL_ERR_INVALID;
   if (!a_dev || !b_dev || !out_dev || batch < 1 || size < 1 || channels < 4 || (channels & 3)) return YL_ERR_INVALID;
   if ((k != 3 && k != 5) || (stride != 1 && stride != 2)) return YL_ERR_INVALID;
   if (pass != YL_STAGE_PASS_FORWARD && pass != YL_STAGE_PASS_DGRAD && pass != YL_STAGE_PASS_WGRAD) return YL_ERR_INVALID;
   const bool wg = pass == YL_STAGE_PASS_WGRAD;
   if (((uintptr_t)a_dev & 15u) || ((uintptr_t)(wg ? (const void*)b_dev : (const void*)out_dev) & 15u)) return YL_ERR_UNSUPPORTED;
   if (((uintptr_t)b_dev & 3u) || ((uintptr_t)out_dev & 3u)) return YL_ERR_UNSUPPORTED;
-  const int So = out_size(size, k, stride);
+  const int So = out_size(size, k, stride), pb = pad_begin(k, stride, size, same);
   const int64_t M = (int64_t)batch * size * size, Mo = (int64_t)batch * So * So;
   if (M * channels >= ((int64_t)1 << 40) || M >= ((int64_t)1 << 31)) return YL_ERR_UNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
   if (!wg) {
-    if (pass == YL_STAGE_PASS_FORWARD) launch_dw<false>(s, a_dev, b_dev, out_dev, k, stride, batch, size, So, channels);
-    else launch_dw<true>(s, a_dev, b_dev, out_dev, k, stride, batch, size, So, channels);
+    if (pass == YL_STAGE_PASS_FORWARD) launch_dw<false>(s, a_dev, b_dev, out_dev, k, stride, pb, batch, size, So, channels);
+    else launch_dw<true>(s, a_dev, b_dev, out_dev, k, stride, pb, batch, size, So, channels);
     if (launches) *launches = 1;
     return hipGetLastError() == hipSuccess ? YL_OK : YL_ERR_HIP;
   }
@@ -355,7 +387,7 @@ yl_status yl_stage_depthwise(const float* a_dev, const float* b_dev, float* out_
     (void)hipGetLastError();
     return YL_ERR_NOMEM;
   }
-  launch_dw_wgrad(s, b_dev, a_dev, part, out_dev, k, stride, batch, size, So, channels, tiles);
+  launch_dw_wgrad(s, b_dev, a_dev, part, out_dev, k, stride, pb, batch, size, So, channels, tiles);
   const bool ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
   hipFree(part);
   if (launches) *launches = 2;

@@ -601,8 +601,9 @@ int make_units(const yl_stem_cfg& cfg, int B, int S, Unit* us) {
   for (int i = 0; i < cfg.num_units; ++i) {
     const yl_stem_unit_cfg& c = cfg.unit[i];
     Unit& u = us[i];
-    u.block = i; u.slot = 0; u.dw = 0; u.relu = 1; u.first = u.last = 1; u.res = 0;
+    u.block = i; u.slot = 0; u.dw = 0; u.act = ACT_RELU; u.first = u.last = 1; u.res = 0;
     u.k = c.k; u.st = c.s; u.cin = cin; u.cout = c.cout; u.Sin = S; u.Sout = out_size(S, c.k, c.s);
+    u.pb = pad_begin(c.k, c.s, S, 0);
     u.planar = i == 0 && cfg.input_nchw;
     u.Min = (int64_t)B * S * S; u.Mout = (int64_t)B * u.Sout * u.Sout;
     u.stat_rows = stat_rows_of(u.Mout); u.tiles = ceil_div(u.Mout, u.stat_rows);
@@ -637,7 +638,8 @@ int resolve(const yl_stem_cfg& cfg, const yl_stem_tensors* t, const yl_stage_uni
 struct StemPolicy {
   static constexpr int ROT = 2;
   static constexpr bool MIXED = false;   // every unit has its ReLU and no block a residual
-  static yl_status layout(const yl_stem_cfg& cfg, int B, int S, Unit* us, int* n, Sizes* z) { return ::layout(cfg, B, S, us, n, z); }
+  static constexpr bool RELU6 = false;
+  template <class H> static yl_status layout(const H& h, int B, int S, Unit* us, int* n, Sizes* z) { return ::layout(h.cfg, B, S, us, n, z); }
   static int conv_forward(hipStream_t s, const Unit& u, int B, const float* x, const float* w, float* z, const UnitBuffers& sb,
                           int mode) {
     return u.k == 3 ? conv3_forward(s, x, w, sb.wpack, z, u.st, B, u.Sin, u.Sout, u.cin, u.cout, u.planar, mode)

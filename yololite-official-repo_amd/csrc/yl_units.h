@@ -17,13 +17,17 @@
 //   P::ROT                       rotating buffers: 3 with residual blocks, 2 without
 //   P::MIXED                     units without ReLU and residual blocks can occur.  false keeps the ACT_NONE instantiations
 //                                of yl_bn.h's kernels and the add out of the object
-//   P::layout(cfg, B, S, us, &n, &z)   the units and sizes of cfg at (B, S); a status.  us and n are filled either way
+//   P::RELU6                     units with ReLU6 can occur (the stage's variant, yl_variant_stage_set).  false keeps the
+//                                ACT_RELU6 instantiations out of the object
+//   P::layout(h, B, S, us, &n, &z)     the units and sizes of the handle's cfg (and variant) at (B, S); a status.  us and n
+//                                are filled either way
 //   P::conv_forward / conv_wgrad / conv_dgrad(s, u, B, ..., sb, mode)   the unit's convolution passes in the dense GEMMs'
 //                                operand type `mode` (a depthwise unit has none) -> launches enqueued
 //   P::add(s, io, g, n4)         io += g (MIXED only)
 #ifndef YL_UNITS_H
 #define YL_UNITS_H
 #include <new>
+#include <type_traits>
 
 #include "yl_block.h"
 
@@ -35,7 +39,8 @@ static_assert(YL_STEM_MAX_UNITS <= MAX_UNITS, "one unit array serves both stacks
 struct Unit {
   int block, slot;                       // the stage's: slot 0 dw_start, 1 pw_exp (cn), 2 dw_mid, 3 pw_proj of yl_stage_block
   int dw, planar;                        // depthwise / dense; the input is the planar image (the stem's unit 0)
-  int relu, k, st;                       // k x k of stride st
+  int act, k, st;                        // the activation behind the BatchNorm (yl_bn.h: ACT_NONE, ACT_RELU, ACT_RELU6); k x k of stride st
+  int pb;                                // the leading pad of the k x k window (pad_begin), rows and columns alike
   int cin, cout, Sin, Sout;
   int64_t Min, Mout;                     // rows of the unit's input and output
   int stat_rows, tiles;                  // the row reductions: `tiles` tiles of stat_rows rows
@@ -45,6 +50,14 @@ struct Unit {
 
 inline int round4(int v) { return (v + 3) & ~3; }
 inline int out_size(int S, int k, int st) { return (S + 2 * ((k - 1) / 2) - k) / st + 1; }
+// the pad in front of the first row and column of an odd k x k convolution of stride st over S pixels: (k - 1) / 2 on every
+// side, or with `same` TF-SAME's: total = max((So - 1) st + k - S, 0) with So = ceil(S / st) = out_size(S, k, st), of which
+// the leading side gets total / 2 rounded down: (k - 1) / 2 - 1 when st == 2 and S is even, (k - 1) / 2 otherwise
+inline int pad_begin(int k, int st, int S, int same) {
+  if (!same) return (k - 1) / 2;
+  const int total = (out_size(S, k, st) - 1) * st + k - S;
+  return total > 0 ? total / 2 : 0;
+}
 
 // bytes, but cmax: channels.  x0 (the caller's x), xsave (its saved copy) and gmax (one gradient buffer) are the
 // translation unit's to set; the rest is unit_sizes'
@@ -156,6 +169,8 @@ template <class Cfg> struct UnitStack {
   int fB, fS, fTrain;                    // the forward whose activations are held (mem.fValid)
   int mode, fMode;                       // the dense GEMMs' operand type (yl_block.h: 0 fp32, 1 fp16, 2 bf16): of the next
                                          // forward (yl_amp_*_set) and of the held one, which its backward runs in
+  int act = ACT_RELU, same = 0;          // the stage's variant (yl_variant_stage_set): the activation of every activated
+                                         // unit, TF-SAME padding.  Not changed while a forward is held
 };
 // yl_amp_*_set / _get: the mode as the bits of the heads' flags (0, YL_HEAD_F16, YL_HEAD_BF16)
 inline uint32_t mode_bits(int mode) { return mode == 1 ? YL_HEAD_F16 : (mode == 2 ? YL_HEAD_BF16 : 0u); }
@@ -198,6 +213,17 @@ inline BnLayer bn_of(const Unit& u, const yl_stage_unit& e, double eps, float* s
           stats, sb.spart};
 }
 
+// f(the unit's activation as a constant) -> what it returns: ACT_RELU, ACT_RELU6 where the policy has it, ACT_NONE where the
+// policy has it; anything else runs nothing.  The BatchNorm instantiations a translation unit gets are the ones named here
+template <class P, class F> inline int by_act(int act, F f) {
+  if (act == ACT_RELU) return f(std::integral_constant<int, ACT_RELU>());
+  if constexpr (P::RELU6) {
+    if (act == ACT_RELU6) return f(std::integral_constant<int, ACT_RELU6>());
+  }
+  if constexpr (P::MIXED) return f(std::integral_constant<int, ACT_NONE>());
+  return 0;
+}
+
 // ---- forward.  par: the parameters, one entry per unit (npar of them: which units exist does not depend on the shape);
 // xmask: the alignment of x_dev.  The caller has checked its pointers and batch, size >= 1
 template <class P, class H>
@@ -210,7 +236,7 @@ yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const f
   Unit us[MAX_UNITS];
   Sizes sz;
   int n;
-  const yl_status lst = P::layout(h->cfg, batch, size, us, &n, &sz);
+  const yl_status lst = P::layout(*h, batch, size, us, &n, &sz);
   for (int i = 0; i < n; ++i)
     if (us[i].Mout < 1 || (train && us[i].Mout < 2)) return YL_ERR_INVALID;            // no variance of one value
   if (lst != YL_OK) return lst;
@@ -239,8 +265,7 @@ yl_status units_forward(H* h, const yl_stage_unit* const* par, int npar, const f
     nl += P::conv_forward(s, u, batch, in, e.w, z, sb, mode);
     const BnLayer bn = bn_of(u, e, h->cfg.eps, stats, sb);
     const float* res = (u.last && u.res) ? bin : nullptr;
-    if (u.relu) nl += bn_forward<ACT_RELU>(s, bn, train, z, res, hout);
-    else if constexpr (P::MIXED) nl += bn_forward<ACT_NONE>(s, bn, train, z, res, hout);
+    nl += by_act<P>(u.act, [&](auto A) { return bn_forward<decltype(A)::value>(s, bn, train, z, res, hout); });
     in = hout; in_i = out_i;
   }
   if (save) {
@@ -264,7 +289,7 @@ yl_status units_backward(H* h, const yl_stage_unit* const* par, const yl_stage_u
   Unit us[MAX_UNITS];
   Sizes sz;
   int n;
-  yl_status st = P::layout(h->cfg, h->fB, h->fS, us, &n, &sz);
+  yl_status st = P::layout(*h, h->fB, h->fS, us, &n, &sz);
   if (st != YL_OK) return st;
   UnitBuffers sb;
   st = units_reserve(h->mem, us, n, sz, P::ROT, true, &sb);
@@ -289,14 +314,14 @@ yl_status units_backward(H* h, const yl_stage_unit* const* par, const yl_stage_u
     if (u.last && u.res) { G = dh; keep = cur; }
     const BnLayer bn = bn_of(u, e, h->cfg.eps, sb.stats[i], sb);
     // sum g, sum g * xhat: dbeta, dgamma and the batch statistics' two means
-    if (u.relu) nl += bn_backward_sums<ACT_RELU>(s, bn, train, dh, sb.h[i], sb.z[i], g.gamma, g.beta, sb.coef);
-    else if constexpr (P::MIXED) nl += bn_backward_sums<ACT_NONE>(s, bn, train, dh, sb.h[i], sb.z[i], g.gamma, g.beta, sb.coef);
+    nl += by_act<P>(u.act, [&](auto A) {
+      return bn_backward_sums<decltype(A)::value>(s, bn, train, dh, sb.h[i], sb.z[i], g.gamma, g.beta, sb.coef);
+    });
     const bool need_dx = i > first || (i == 0 && dx_dev);
     if (!need_dx && !g.w) break;
     const int t = (cur >= 0 && cur != keep) ? cur : pick(keep, -1);      // dz: in place unless dh must survive
     float* dz = sb.g[t];
-    if (u.relu) nl += bn_backward_dz<ACT_RELU>(s, bn, dh, sb.h[i], sb.z[i], sb.coef, dz);
-    else if constexpr (P::MIXED) nl += bn_backward_dz<ACT_NONE>(s, bn, dh, sb.h[i], sb.z[i], sb.coef, dz);
+    nl += by_act<P>(u.act, [&](auto A) { return bn_backward_dz<decltype(A)::value>(s, bn, dh, sb.h[i], sb.z[i], sb.coef, dz); });
     if (g.w) nl += P::conv_wgrad(s, u, B, xin, dz, g.w, sb, mode);
     if (!need_dx) break;
     const int d = pick(keep, t);

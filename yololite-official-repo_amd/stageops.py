@@ -5,7 +5,7 @@
     BackboneTail.from_meta(meta) / .from_state_dict(meta, sd)   the backbone's last stage: its C4 tap -> its C5 tap
     BackboneMid.from_meta(meta) / .from_state_dict(meta, sd)    the stage between its C3 and its C4 tap
     MobileNetV4Backbone.from_meta(meta) / .from_state_dict(meta, sd)   image -> [c3, c4, c5]: stemops.BackboneStem, mid, tail
-    depthwise(x, w_or_dy, pass_, k, stride)                one depthwise pass on its own (yl_stage_depthwise)
+    depthwise(x, w_or_dy, pass_, k, stride, same=False)    one depthwise pass on its own (yl_stage_depthwise)
     plan(in_channels, blocks, batch, size)                 yl_stage_plan: what the handle holds
 
     c3, c4, _ = model.features(x)                          # NHWC; the executor's frozen stages 0..3
@@ -32,7 +32,8 @@ replaces it, and the stale backward raises.  fp32 tensors on one HIP device; no 
 accumulation, nothing clamped.  Parameters, saved activations and gradients stay fp32, and so do the depthwise
 convolutions, BatchNorm, ReLU and the residual: unlike torch.autocast, which also runs the depthwise convolutions in 16
 bits.  A backward runs in the precision of its forward.  ReLU only: relu6, silu, TF-SAME
-padding, squeeze-excite and layer-scale are refused by name, as are the backbone families built from other blocks.
+padding, squeeze-excite and layer-scale are refused by name, as are the backbone families built from other blocks
+(ReLU6, TF-SAME and timm's `ir` block, i.e. the EfficientNet-Lite stages, are irops.IRStack's).
 """
 from __future__ import annotations
 
@@ -207,31 +208,43 @@ class UIBStack(tm.UnitStack):
 
     def __init__(self, in_channels: int, blocks: Sequence[dict], eps: float = 1e-5, prefix: str = "", precision: str = "fp32"):
         super().__init__()
+        self._setup(in_channels, _check_blocks(in_channels, blocks, eps), eps, prefix, precision)
+
+    def _setup(self, in_channels: int, blocks_cfg: List[dict], eps: float, prefix: str, precision: str):
+        """the constructor behind the checks (irops.IRStack shares it): the blocks' containers under their key names, the
+        units' layers in running order, the handle"""
         self.precision = precision
-        self.blocks_cfg = _check_blocks(in_channels, blocks, eps)
+        self.blocks_cfg = blocks_cfg
         self.in_channels, self.eps, self.prefix = int(in_channels), float(eps), str(prefix)
         self.out_channels = self.blocks_cfg[-1]["c"]
         self._convs, self._bns = [], []
         for d in self.blocks_cfg:
-            cin, mid, c = d["cin"], d["mid"], d["c"]
-            if d["type"] == "cn":
-                blk = _conv_bn(cin, c, 1, 1, 1, self.eps, names=("conv", "bn1"))
-                self._convs.append(blk.conv); self._bns.append(blk.bn1)
+            _nest(self, f"{self.prefix}blocks.{d['name']}", self._block_module(d))
+        self._handle = self._make_handle()
+
+    def _make_handle(self):
+        return self._handle_cls(self.in_channels, self.blocks_cfg, self.eps)
+
+    def _block_module(self, d: dict) -> nn.Module:
+        """the container of one block under timm's names; appends its units' layers to _convs / _bns in running order"""
+        cin, mid, c = d["cin"], d["mid"], d["c"]
+        if d["type"] == "cn":
+            blk = _conv_bn(cin, c, 1, 1, 1, self.eps, names=("conv", "bn1"))
+            self._convs.append(blk.conv); self._bns.append(blk.bn1)
+            return blk
+        blk = nn.Module()
+        for u in _units(d):
+            if u == "dw_start":
+                m = _conv_bn(cin, cin, d["a"], d["s"] if not d["k"] else 1, cin, self.eps)
+            elif u == "pw_exp":
+                m = _conv_bn(cin, mid, 1, 1, 1, self.eps)
+            elif u == "dw_mid":
+                m = _conv_bn(mid, mid, d["k"], d["s"], mid, self.eps)
             else:
-                blk = nn.Module()
-                for u in _units(d):
-                    if u == "dw_start":
-                        m = _conv_bn(cin, cin, d["a"], d["s"] if not d["k"] else 1, cin, self.eps)
-                    elif u == "pw_exp":
-                        m = _conv_bn(cin, mid, 1, 1, 1, self.eps)
-                    elif u == "dw_mid":
-                        m = _conv_bn(mid, mid, d["k"], d["s"], mid, self.eps)
-                    else:
-                        m = _conv_bn(mid, c, 1, 1, 1, self.eps)
-                    blk.add_module(u, m)
-                    self._convs.append(m.conv); self._bns.append(m.bn)
-            _nest(self, f"{self.prefix}blocks.{d['name']}", blk)
-        self._handle = self._handle_cls(self.in_channels, self.blocks_cfg, self.eps)
+                m = _conv_bn(mid, c, 1, 1, 1, self.eps)
+            blk.add_module(u, m)
+            self._convs.append(m.conv); self._bns.append(m.bn)
+        return blk
 
     def out_size(self, size: int) -> int:
         return _sizes(self.blocks_cfg, int(size))[-1]
@@ -253,30 +266,16 @@ class UIBStack(tm.UnitStack):
         return self._run_stack(x, B, self._check_rows(B, S), False)
 
 
-def _tail_blocks(meta: dict, start: str = "c4"):
-    """-> (cin at the C4 tap, blocks with their names "si.bi", eps) of the backbone `meta` names, read from
-    program.BACKBONES with program._backbone's channel arithmetic.  Host-side facts only; refuses by name."""
+def _arch_walk(spec: dict):
+    """-> (taps, blocks): the stages of a program.BACKBONES entry a feature is tapped behind, and every block of the
+    backbone in running order as (stage, index in the stage, arch string, its fields, stride, cin, cout), with
+    program._backbone's channel and depth arithmetic (cmult, dmult, fix_first_last, _make_divisible)"""
     import math
-    from .program import BACKBONES, CONVNEXT, HGNET, _make_divisible, _parse
-    if start != "c4":
-        raise _lib.YoloLiteHipError(f"BackboneTail: start={start!r} is not implemented (only the C4 tap -> C5 tail is; "
-                                    "stages 0..3 stay the executor's)")
-    mcfg = (meta.get("config", {}) or {}).get("model", {}) or {}
-    name = meta.get("backbone") or mcfg.get("backbone") or "resnet18"
-    if name in HGNET or name in CONVNEXT or name not in BACKBONES:
-        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented (its tail is not made of uir / 1x1 cn "
-                                    "blocks; only the mobilenetv4_conv_small family's is)")
-    spec = BACKBONES[name]
+    from .program import _make_divisible, _parse
     arch, rlim = spec["arch"], spec.get("round_limit", 0.9)
-    if spec["act"] != "relu":
-        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented: activation {spec['act']!r} (ReLU only)")
-    if spec["same"]:
-        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented: TF-SAME padding")
     ns = len(arch)
     taps = [si for si in range(ns) if si + 1 == ns or _parse(arch[si + 1][0])["s"] > 1]
-    if len(taps) < 2:
-        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} has no C4 tap")
-    cin, c4, blocks = spec["stem"], None, []
+    out, cin = [], spec["stem"]
     for si, stage in enumerate(arch):
         bi = 0
         for bstr in stage:
@@ -286,17 +285,47 @@ def _tail_blocks(meta: dict, start: str = "c4"):
                 rep = int(math.ceil(rep * spec["dmult"]))
             cout = _make_divisible(d["c"] * spec["cmult"], 8, rlim)
             for r in range(rep):
-                if si > taps[-2]:
-                    s = d["s"] if r == 0 else 1
-                    if d["type"] not in ("uir", "cn") or d.get("se") or d.get("skip"):
-                        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented: block {bstr!r} of its "
-                                                    "tail is not a uir or 1x1 cn block")
-                    blocks.append(dict(type=d["type"], a=d.get("a", 0), k=d["k"], s=s, c=cout, name=f"{si}.{bi}",
-                                       mid=_make_divisible(cin * d["e"], 8) if d["type"] == "uir" else 0))
+                out.append((si, bi, bstr, d, d["s"] if r == 0 else 1, cin, cout))
                 cin = cout
                 bi += 1
-        if si == taps[-2]:
-            c4 = cin
+    return taps, out
+
+
+def _meta_backbone(meta: dict) -> str:
+    mcfg = (meta.get("config", {}) or {}).get("model", {}) or {}
+    return meta.get("backbone") or mcfg.get("backbone") or "resnet18"
+
+
+def _tail_blocks(meta: dict, start: str = "c4"):
+    """-> (cin at the C4 tap, blocks with their names "si.bi", eps) of the backbone `meta` names, read from
+    program.BACKBONES with program._backbone's channel arithmetic.  Host-side facts only; refuses by name."""
+    from .program import BACKBONES, CONVNEXT, HGNET, _make_divisible
+    if start != "c4":
+        raise _lib.YoloLiteHipError(f"BackboneTail: start={start!r} is not implemented (only the C4 tap -> C5 tail is; "
+                                    "stages 0..3 stay the executor's)")
+    name = _meta_backbone(meta)
+    if name in HGNET or name in CONVNEXT or name not in BACKBONES:
+        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented (its tail is not made of uir / 1x1 cn "
+                                    "blocks; only the mobilenetv4_conv_small family's is)")
+    spec = BACKBONES[name]
+    if spec["act"] != "relu":
+        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented: activation {spec['act']!r} (ReLU only; "
+                                    "the EfficientNet-Lite family: see EfficientNetLiteTail)")
+    if spec["same"]:
+        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented: TF-SAME padding")
+    taps, walk = _arch_walk(spec)
+    if len(taps) < 2:
+        raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} has no C4 tap")
+    c4, blocks = None, []
+    for si, bi, bstr, d, s, cin, cout in walk:
+        if si > taps[-2]:
+            if d["type"] not in ("uir", "cn") or d.get("se") or d.get("skip"):
+                raise _lib.YoloLiteHipError(f"BackboneTail: backbone {name!r} is not implemented: block {bstr!r} of its "
+                                            "tail is not a uir or 1x1 cn block")
+            blocks.append(dict(type=d["type"], a=d.get("a", 0), k=d["k"], s=s, c=cout, name=f"{si}.{bi}",
+                               mid=_make_divisible(cin * d["e"], 8) if d["type"] == "uir" else 0))
+        elif si == taps[-2]:
+            c4 = cout
     return c4, blocks, float(spec["eps"])
 
 
@@ -322,44 +351,31 @@ class BackboneTail(UIBStack):
 def _mid_blocks(meta: dict):
     """-> (cin at the C3 tap, blocks with their names "si.bi", eps) of the stages between the C3 and the C4 tap of the
     backbone `meta` names (mobilenetv4_conv_small[_050]: stage 2, six uir blocks).  Host-side facts only; refuses by name."""
-    import math
-    from .program import BACKBONES, CONVNEXT, HGNET, _make_divisible, _parse
+    from .program import BACKBONES, CONVNEXT, HGNET, _make_divisible
     who = "BackboneMid"
-    mcfg = (meta.get("config", {}) or {}).get("model", {}) or {}
-    name = meta.get("backbone") or mcfg.get("backbone") or "resnet18"
+    name = _meta_backbone(meta)
     if name in HGNET or name in CONVNEXT or name not in BACKBONES:
         raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented (its C3 -> C4 stage is not made of uir / 1x1 cn "
                                     "blocks; only the mobilenetv4_conv_small family's is)")
     spec = BACKBONES[name]
-    arch, rlim = spec["arch"], spec.get("round_limit", 0.9)
     if spec["act"] != "relu":
-        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: activation {spec['act']!r} (ReLU only)")
+        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: activation {spec['act']!r} (ReLU only; "
+                                    "the EfficientNet-Lite family: see EfficientNetLiteMid)")
     if spec["same"]:
         raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: TF-SAME padding")
-    ns = len(arch)
-    taps = [si for si in range(ns) if si + 1 == ns or _parse(arch[si + 1][0])["s"] > 1]
+    taps, walk = _arch_walk(spec)
     if len(taps) < 3:
         raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} has no C3 tap")
-    cin, c3, blocks = spec["stem"], None, []
-    for si, stage in enumerate(arch[:taps[-2] + 1]):
-        bi = 0
-        for bstr in stage:
-            d = _parse(bstr)
-            rep = d["r"]
-            if spec["dmult"] != 1.0 and not (spec["fix_first_last"] and si in (0, ns - 1)):
-                rep = int(math.ceil(rep * spec["dmult"]))
-            cout = _make_divisible(d["c"] * spec["cmult"], 8, rlim)
-            for r in range(rep):
-                if si > taps[-3]:
-                    if d["type"] not in ("uir", "cn") or d.get("se") or d.get("skip"):
-                        raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: block {bstr!r} of its C3 -> C4 "
-                                                    "stage is not a uir or 1x1 cn block")
-                    blocks.append(dict(type=d["type"], a=d.get("a", 0), k=d["k"], s=d["s"] if r == 0 else 1, c=cout,
-                                       name=f"{si}.{bi}", mid=_make_divisible(cin * d["e"], 8) if d["type"] == "uir" else 0))
-                cin = cout
-                bi += 1
-        if si == taps[-3]:
-            c3 = cin
+    c3, blocks = None, []
+    for si, bi, bstr, d, s, cin, cout in walk:
+        if taps[-3] < si <= taps[-2]:
+            if d["type"] not in ("uir", "cn") or d.get("se") or d.get("skip"):
+                raise _lib.YoloLiteHipError(f"{who}: backbone {name!r} is not implemented: block {bstr!r} of its C3 -> C4 "
+                                            "stage is not a uir or 1x1 cn block")
+            blocks.append(dict(type=d["type"], a=d.get("a", 0), k=d["k"], s=s, c=cout, name=f"{si}.{bi}",
+                               mid=_make_divisible(cin * d["e"], 8) if d["type"] == "uir" else 0))
+        elif si == taps[-3]:
+            c3 = cout
     return c3, blocks, float(spec["eps"])
 
 
@@ -447,9 +463,11 @@ class MobileNetV4Backbone(nn.Module):
 PASSES = {"forward": _lib.YL_STAGE_PASS_FORWARD, "dgrad": _lib.YL_STAGE_PASS_DGRAD, "wgrad": _lib.YL_STAGE_PASS_WGRAD}
 
 
-def depthwise(x: torch.Tensor, w_or_dy: torch.Tensor, pass_: str, k: int, stride: int, size: Optional[int] = None) -> torch.Tensor:
+def depthwise(x: torch.Tensor, w_or_dy: torch.Tensor, pass_: str, k: int, stride: int, size: Optional[int] = None,
+              same: bool = False) -> torch.Tensor:
     """One depthwise pass of the stack on its own (yl_stage_depthwise, launched as the module launches it), fp32 NHWC
-    tensors on one HIP device, pad (k - 1) / 2, So = (S + 2 pad - k) / stride + 1:
+    tensors on one HIP device, pad (k - 1) / 2, So = (S + 2 pad - k) / stride + 1; with `same` TF-SAME padding
+    (yl_variant_stage_depthwise): the same So, the leading pad irops.pad_begin(k, stride, S):
         "forward":  x  [B,S,S,C],   W  [C,1,k,k]    -> y  [B,So,So,C]
         "dgrad":    dy [B,So,So,C], W  [C,1,k,k]    -> dx [B,S,S,C]      the gradient of forward's x
         "wgrad":    x  [B,S,S,C],   dy [B,So,So,C]  -> dW [C,1,k,k]      the gradient of forward's W
@@ -490,7 +508,11 @@ def depthwise(x: torch.Tensor, w_or_dy: torch.Tensor, pass_: str, k: int, stride
     out = torch.empty(shape, device=a.device, dtype=torch.float32)
     n = C.c_int32()
     with torch.cuda.device(a.device):
-        _lib.check(lib.yl_stage_depthwise(a.data_ptr(), b.data_ptr(), out.data_ptr(), PASSES[pass_], k, stride, B, S, Cn,
-                                          torch.cuda.current_stream(a.device).cuda_stream, C.byref(n)),
-                   what="yl_stage_depthwise")
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        if same:
+            _lib.check(lib.yl_variant_stage_depthwise(a.data_ptr(), b.data_ptr(), out.data_ptr(), PASSES[pass_], k, stride, B, S,
+                                                      Cn, 1, stream, C.byref(n)), what="yl_variant_stage_depthwise")
+        else:
+            _lib.check(lib.yl_stage_depthwise(a.data_ptr(), b.data_ptr(), out.data_ptr(), PASSES[pass_], k, stride, B, S, Cn,
+                                              stream, C.byref(n)), what="yl_stage_depthwise")
     return out
