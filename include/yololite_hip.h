@@ -347,6 +347,31 @@ int32_t yl_query_dw_prologue(int32_t c_in, int32_t c_out, int32_t dw_k, int32_t 
  * instantiation a case ran.                                                                                              */
 int32_t yl_query_wino_form(int32_t c_in, int32_t c_out, int32_t out_h, int32_t out_w, int32_t batch, int32_t in_shift,
                            int32_t dev_select, int32_t* mt, int32_t* nt);
+/* Host-side query (additive to ABI v7), no device needed: which kernel family runs ONE fp32 layer with a depthwise dw_k x dw_k
+ * (stride dw_stride, leading pads dw_pad_t / dw_pad_l) conv on c_in channels -- op YL_OP_CONV: as the prologue of the 1x1 conv
+ * c_in -> c_out (yl_layer.dw_k > 0, no c2 / c3, a launch of its own); op YL_OP_DW: stand-alone (c_out == c_in; the layer's k,
+ * stride and pads are passed as dw_k, dw_stride, dw_pad_*) -- from an in_h x in_w input to an out_h x out_w output on `batch`
+ * images per launch, with the activation id `act` of the 1x1 conv (of the depthwise conv for YL_OP_DW) and a residual or not,
+ * (GELU and ReLU + affine run in a pass behind the kernel, with the residual: the kernel is asked for neither) under the option
+ * values "tile_m", "dev_select" and "split_k"?  Returns a YL_DWF_* id, or YL_DWF_NONE where yl_create would
+ * refuse the layer or no kernel runs it.  args, if not NULL, receives the template arguments of the instantiation (unused
+ * entries 0):
+ *   DWK        yl_conv_dwk_kernel<NT, GW, NW>                DWL         yl_conv_dwl_kernel<NTT>
+ *   DWS        yl_conv_dws_kernel<NT, GW, DK, DS, NW>        DWT         yl_conv_dwt_kernel<NT, DK, DS, MT, WL, 1>
+ *   DWT_SPLITK yl_conv_dwt_kernel<4, DK, DS, 1, false, 4>    DWC         yl_conv_dwc_kernel<DK, DS, NTW>
+ *   DWH        yl_conv_dwh_kernel<NT, DK, DS>                MFMA        yl_conv_mfma_kernel<NT, MT, MODE>, then the k-steps of
+ *   DW_TILE    yl_dw_tile_kernel<K, S>                                   1x1 weights resident in LDS (fewer than c_in / 16: they stream)
+ *   DW         yl_dw_kernel
+ * The launchers (yl_launch_conv_multi, yl_launch_dw) take the same decision from the same functions; the tests ask which
+ * instantiation a case ran.  Launches that join the layer with a neighbour (the fused head and pair launches, the chained
+ * projection) are decided before these and are not reported here.                                                        */
+enum {
+  YL_DWF_NONE = 0, YL_DWF_DWK = 1, YL_DWF_DWL = 2, YL_DWF_DWS = 3, YL_DWF_DWT = 4, YL_DWF_DWT_SPLITK = 5, YL_DWF_DWC = 6,
+  YL_DWF_DWH = 7, YL_DWF_MFMA = 8, YL_DWF_DW_TILE = 9, YL_DWF_DW = 10
+};
+int32_t yl_query_dw_form(int32_t op, int32_t c_in, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t dw_pad_t, int32_t dw_pad_l,
+                         int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, int32_t batch, int32_t act, int32_t has_res,
+                         int32_t tile_m, int32_t dev_select, int32_t split_k, int32_t* args);
 
 /* ---- pre-processing ----------------------------------------------------------------------------
  * Replaces letterbox() + cv2.cvtColor + /255 + (x-mean)/std + transpose of tools/infer.py:121-131,446-453

@@ -297,6 +297,7 @@ SYMBOLS = [
     ("yl_query_dw_prologue", C.c_int32, [C.c_int32] * 6),
     ("yl_query_wino_form", C.c_int32, [C.c_int32] * 7 + [_ip, _ip]),
     ("yl_query_ir_form", C.c_int32, [C.c_int32] * 15 + [_ip]),
+    ("yl_query_dw_form", C.c_int32, [C.c_int32] * 17 + [_ip]),
     ("yl_forward_decoded", C.c_int32, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     ("yl_preprocess", C.c_int32, [_vp, _vp, _vp, C.c_int32, _vp, _vp]),
     ("yl_decode", C.c_int32, [_vp, _vpp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),

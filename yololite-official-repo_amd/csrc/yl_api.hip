@@ -1471,6 +1471,47 @@ int32_t yl_query_wino_form(int32_t c_in, int32_t c_out, int32_t out_h, int32_t o
   return f.form;
 }
 
+int32_t yl_query_dw_form(int32_t op, int32_t c_in, int32_t c_out, int32_t dw_k, int32_t dw_stride, int32_t dw_pad_t, int32_t dw_pad_l,
+                         int32_t in_h, int32_t in_w, int32_t out_h, int32_t out_w, int32_t batch, int32_t act, int32_t has_res,
+                         int32_t tile_m, int32_t dev_select, int32_t split_k, int32_t* args) {
+  if (args) memset(args, 0, 6 * sizeof(int32_t));
+  // what yl_create refuses (yl_program.cpp: validate_layer)
+  if ((op != YL_OP_CONV && op != YL_OP_DW) || c_in < 1 || c_out < 1 || dw_k < 1 || dw_stride < 1 || in_h < 1 || in_w < 1 || out_h < 1 ||
+      out_w < 1 || batch < 1 || (long)batch * out_h * out_w > 0x7fffffffL || (c_in & 3) || dw_pad_t < 0 || dw_pad_l < 0 ||
+      dw_pad_t >= dw_k || dw_pad_l >= dw_k || (out_h - 1) * dw_stride - dw_pad_t >= in_h || (out_w - 1) * dw_stride - dw_pad_l >= in_w ||
+      act < YL_ACT_NONE || act > YL_ACT_RELU_LAB)
+    return YL_DWF_NONE;
+  const bool conv_res_or_smooth = op == YL_OP_CONV && (has_res || YL_SMOOTH(act));   // (validate_layer asks the layer's own fields)
+  if (YL_ACT_POSTPASS(act)) { act = YL_ACT_NONE; has_res = 0; }   // applied by the activation pass: the kernel sees neither (layer_params)
+  static const float some = 0.0f;   // a residual the decision sees as a pointer that is set; nothing reads through it
+  YlConvP p;
+  memset(&p, 0, sizeof(p));
+  p.B = batch; p.H = in_h; p.W = in_w; p.Cin = c_in; p.OH = out_h; p.OW = out_w; p.N = c_out;
+  p.MH = out_h; p.MW = out_w; p.act = act;
+  p.KB = cdiv(c_in, 16); p.NTtot = cdiv(c_out, 16); p.M = batch * out_h * out_w;
+  p.res = has_res ? &some : nullptr;
+  p.dev = ((unsigned)dev_select & YL_DEV_MASK) | (split_k ? 0u : YL_DEV_DWT_NOSPLIT);   // (layer_params)
+  YlDwForm f;
+  if (op == YL_OP_DW) {
+    if (c_out != c_in) return YL_DWF_NONE;
+    p.k = dw_k; p.stride = dw_stride; p.pad_t = dw_pad_t; p.pad_l = dw_pad_l; p.TK = dw_k * dw_k * p.KB;
+    f = yl_dw_alone_form(p);
+  } else {
+    if (conv_res_or_smooth && (c_out & 3)) return YL_DWF_NONE;
+    if ((size_t)(dw_k * dw_k + 1) * c_in * sizeof(float) > YL_DW_LDS_MAX && !yl_dws_supported(c_in, c_out, dw_k, dw_stride, out_h, out_w))
+      return YL_DWF_NONE;
+    p.k = 1; p.stride = 1; p.TK = p.KB;
+    p.dw_k = dw_k; p.dw_stride = dw_stride; p.dw_pad_t = dw_pad_t; p.dw_pad_l = dw_pad_l;
+    YlConvMulti m = {};
+    m.n = 1;
+    m.p[0] = p;
+    f = yl_dw_form(m, 0, tile_m);
+  }
+  if (args)
+    for (int i = 0; i < 6; ++i) args[i] = f.a[i];
+  return f.family;
+}
+
 static yl_status forward_impl(yl_ctx* c, const float* x, int B, float* const* level_out, hipStream_t st,
                               float* layer_ms, const yl_post_cfg* cfg, float* dets, int* counts, int* keep_idx = nullptr) {
   if (!c) return YL_ERR_INVALID;

@@ -47,6 +47,12 @@
 #define yl_launch_conv_dwk YL_LP_NAME(yl_launch_conv_dwk)
 #define yl_launch_conv_dws YL_LP_NAME(yl_launch_conv_dws)
 #define yl_launch_conv_dwt YL_LP_NAME(yl_launch_conv_dwt)
+#define yl_dwc_form YL_LP_NAME(yl_dwc_form)
+#define yl_dwt_form YL_LP_NAME(yl_dwt_form)
+#define yl_dwk_form YL_LP_NAME(yl_dwk_form)
+#define yl_dws_form YL_LP_NAME(yl_dws_form)
+#define yl_dw_form YL_LP_NAME(yl_dw_form)
+#define yl_dw_alone_form YL_LP_NAME(yl_dw_alone_form)
 #endif
 #include <stdio.h>
 #include <stdlib.h>
@@ -1118,6 +1124,89 @@ static int yl_partition_blocks(YlConvMulti& m, const long* tiles, int gx) {
   return at;
 }
 
+// n-tiles per workgroup of the kernels that chunk N over grid.y (yl_conv_mfma_kernel, yl_conv_dwh_kernel)
+static int yl_pick_nt(int NTtot) {
+  const int nts[6] = {1, 2, 3, 4, 6, 8};
+  if (NTtot <= 8) {
+    for (int i = 0; i < 6; ++i) if (nts[i] >= NTtot) return nts[i];
+  }
+  // smallest number of chunks, then the least padding
+  int best = 8, bestc = (NTtot + 7) / 8;
+  for (int i = 5; i >= 3; --i) {
+    const int c = (NTtot + nts[i] - 1) / nts[i];
+    if (c < bestc || (c == bestc && nts[i] < best)) { best = nts[i]; bestc = c; }
+  }
+  return best;
+}
+
+// yl_conv_mfma_kernel's weight chunk for the layer p at (NT, MT): CH k-steps resident in LDS, the whole K if it fits, else
+// 48 KiB chunks stream; false: taps + store staging leave no room for one k-step
+static bool yl_mfma_chunk(const YlConvP& p, int NT, int MT, int* CH) {
+  const size_t step_bytes = YlMfmaLds::chunk(1, NT) * 4;               // one k-step of weights
+  const size_t extra = YlMfmaLds::bytes(0, NT, MT, p.dw_k, p.Cin, p.N);   // taps + store staging (head rows)
+  if (extra + step_bytes > YlMfmaLds::LIMIT) return false;
+  const size_t budget = YlMfmaLds::LIMIT - extra;
+  if ((size_t)p.TK * step_bytes <= budget) *CH = p.TK;                 // whole K resident
+  else *CH = (int)((budget < YlMfmaLds::STREAM_CHUNK ? budget : YlMfmaLds::STREAM_CHUNK) / step_bytes);   // stream K in chunks
+  return true;
+}
+
+// Which kernel runs the depthwise -> 1x1 launch m (yl_internal.h), in the order the families are asked:
+YlDwForm yl_dw_form(const YlConvMulti& m, int big, int tile_hint) {
+  const YlDwForm none = {YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
+  const int n = m.n;
+  const YlConvP& p = m.p[big];
+  if (n < 1 || n > 4 || p.dw_k <= 0 || p.C1 > 0 || p.scale) return none;
+  const int NT = yl_pick_nt(p.NTtot);
+  const int gy = (p.NTtot + NT - 1) / NT;
+  if (n > 1 && gy != 1) return none;
+  // depthwise k x k -> 1x1 with >= 192 depthwise channels and 7..22 n-tiles (EfficientNet-Lite conv_dw -> conv_pwl): streamed 1x1
+  // AND tap weights, halo patch through LDS (yl_convc.hip, round 5).  Not behind tile_hint: these layers carry more tap
+  // weights than the 32 KB image of the other depthwise-prologue kernels, nothing else can run them
+  // depthwise 3x3 -> wide 1x1 with 16 / 21 n-tiles (the 244- / 328-channel neck and head blocks): the input window through
+  // LDS where the grid fills 8 x 8-pixel windows (yl_conv_dwl_kernel), else streamed weights with the taps from L1/L2
+  // (yl_conv_dwk_kernel).  In front of yl_conv_dws_kernel, which also runs these shapes but slower (244 -> 244 @80x80 B = 32:
+  // 0.45 ms against 0.36 for yl_conv_dwk_kernel -- it took them over unnoticed when it was written for the 528 - 1248-channel
+  // 5x5 layers)
+  if (n == 1 && p.dw_k == 3 && p.dw_stride == 1 && tile_hint != 6 && tile_hint != 3) {
+    const YlDwForm f = yl_dwk_form(p);
+    if (f.family) return f;
+  }
+  if (n == 1) {
+    const YlDwForm f = yl_dws_form(p);
+    if (f.family) return f;
+  }
+  // depthwise 3x3 -> wide 1x1 whose weight image is beyond LDS: streamed weights, taps from L1/L2 (yl_convc.hip)
+  if (n == 1 && p.dw_k == 3 && tile_hint != 6 && tile_hint != 3) {
+    const YlDwForm f = yl_dwk_form(p);
+    if (f.family) return f;
+  }
+  // depthwise prologue with LDS-staged halo tiles (4x4 output pixels per wave)
+  bool halo = (p.dw_k == 3 || p.dw_k == 5) && (p.dw_stride == 1 || p.dw_stride == 2) && (p.N & 3) == 0 && tile_hint != 3;
+  for (int k = 0; k < n; ++k)
+    halo = halo && (m.p[k].OH & 3) == 0 && (m.p[k].OW & 3) == 0 &&
+           (size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * 4 < ((size_t)1 << 31);
+  if (halo && tile_hint != 6 && tile_hint != 7) {
+    // wave-autonomous kernel (yl_convc.hip): one tile per wave, A fragments from L1/L2, ~15 KB of LDS per workgroup
+    const YlDwForm f = yl_dwt_form(m);
+    if (f.family) return f;
+  }
+  if (halo && tile_hint == 7) {
+    // producer / consumer kernel (yl_convc.hip: 4 depthwise waves + 4 GEMM waves per workgroup, 1x1 weights resident
+    // in registers).  OPT-IN (tile_hint 7): faster in isolation on the K >= 192 layers (28 vs 38 us, 44 vs 50 us at
+    // 20x20, B = 64) but 0.5 % slower in the two-stream pipeline (31.10 k vs 31.27 k images/s): its workgroups
+    // hold ~100-130 KB of LDS and 8 waves per CU, which keeps the other chunk's kernels off those CUs.
+    const YlDwForm f = yl_dwc_form(m);
+    if (f.family) return f;
+  }
+  if (halo && YlDwhLds{NT, p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes() <= YlDwhLds::LIMIT)
+    return {YL_DWF_DWH, {NT, p.dw_k, p.dw_stride, 0, 0, 0}};
+  // yl_conv_mfma_kernel's depthwise-prologue modes: one m-tile per wave (register budget -> occupancy)
+  int CH = 0;
+  if (!yl_mfma_chunk(p, NT, 1, &CH)) return none;
+  return {YL_DWF_MFMA, {NT, 1, p.dw_k == 3 ? YL_CM_DW3 : p.dw_k == 5 ? YL_CM_DW5 : YL_CM_DWPRO, CH, 0, 0}};
+}
+
 // choose (NT, MT, chunking) for a layer -- or for up to 4 layers of identical configuration that run as ONE
 // launch (YlConvMulti) -- and launch.  tile_hint: 0 = auto, 1/2 = force MT.
 hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStream_t st) {
@@ -1162,19 +1251,7 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
   }
   const YlConvP& p = m.p[big];                              // decisions follow the largest problem
   if (p.scale && (p.k != 1 || p.stride != 1 || p.dw_k > 0 || p.C1 > 0 || p.in_shift || p.w3p)) return hipErrorInvalidValue;
-  const int nts[6] = {1, 2, 3, 4, 6, 8};
-  int NT = 8;
-  if (p.NTtot <= 8) {
-    for (int i = 0; i < 6; ++i) if (nts[i] >= p.NTtot) { NT = nts[i]; break; }
-  } else {
-    // smallest number of chunks, then the least padding
-    int best = 8, bestc = (p.NTtot + 7) / 8;
-    for (int i = 5; i >= 3; --i) {
-      const int c = (p.NTtot + nts[i] - 1) / nts[i];
-      if (c < bestc || (c == bestc && nts[i] < best)) { best = nts[i]; bestc = c; }
-    }
-    NT = best;
-  }
+  const int NT = yl_pick_nt(p.NTtot);
   const int gy = (p.NTtot + NT - 1) / NT;
   if (n > 1 && gy != 1) return hipErrorInvalidValue;
   if (p.C1 > 0) {          // fused inverted-residual block (expand -> depthwise -> project)
@@ -1223,63 +1300,33 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
     const hipError_t ek = yl_launch_conv_kxk(p, st);
     if (ek != hipErrorNotSupported) return ek;
   }
-  // depthwise k x k -> 1x1 with >= 192 depthwise channels and 7..22 n-tiles (EfficientNet-Lite conv_dw -> conv_pwl): streamed 1x1
-  // AND tap weights, halo patch through LDS (yl_convc.hip, round 5).  Not behind tile_hint: these layers carry more tap
-  // weights than the 32 KB image of the other depthwise-prologue kernels, nothing else can run them
-  // depthwise 3x3 -> wide 1x1 with 16 / 21 n-tiles (the 244- / 328-channel neck and head blocks): the input window through
-  // LDS where the grid fills 8 x 8-pixel windows (yl_conv_dwl_kernel), else streamed weights with the taps from L1/L2
-  // (yl_conv_dwk_kernel).  In front of yl_conv_dws_kernel, which also runs these shapes but slower (244 -> 244 @80x80 B = 32:
-  // 0.45 ms against 0.36 for yl_conv_dwk_kernel -- it took them over unnoticed when it was written for the 528 - 1248-channel
-  // 5x5 layers)
-  if (n == 1 && p.dw_k == 3 && p.dw_stride == 1 && tile_hint != 6 && tile_hint != 3) {
-    const hipError_t ed = yl_launch_conv_dwk(p, st);
-    if (ed != hipErrorNotSupported) return ed;
-  }
-  if (n == 1 && p.dw_k > 0) {
-    const hipError_t es = yl_launch_conv_dws(p, st);
-    if (es != hipErrorNotSupported) return es;
-  }
-  // depthwise 3x3 -> wide 1x1 whose weight image is beyond LDS: streamed weights, taps from L1/L2 (yl_convc.hip)
-  if (n == 1 && p.dw_k == 3 && tile_hint != 6 && tile_hint != 3) {
-    const hipError_t ed = yl_launch_conv_dwk(p, st);
-    if (ed != hipErrorNotSupported) return ed;
-  }
-  // depthwise prologue with LDS-staged halo tiles (4x4 output pixels per wave)
-  bool halo = p.dw_k > 0 && (p.dw_k == 3 || p.dw_k == 5) && (p.dw_stride == 1 || p.dw_stride == 2) && (p.N & 3) == 0 &&
-              tile_hint != 3;
-  for (int k = 0; k < n; ++k)
-    halo = halo && (m.p[k].OH & 3) == 0 && (m.p[k].OW & 3) == 0 &&
-           (size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * 4 < ((size_t)1 << 31);
-  if (halo && tile_hint != 6 && tile_hint != 7) {
-    // wave-autonomous kernel (yl_convc.hip): one tile per wave, A fragments from L1/L2, ~15 KB of LDS per workgroup
-    const hipError_t et = yl_launch_conv_dwt(m, st);
-    if (et != hipErrorNotSupported) return et;
-  }
-  if (halo && tile_hint == 7) {
-    // producer / consumer kernel (yl_convc.hip: 4 depthwise waves + 4 GEMM waves per workgroup, 1x1 weights resident
-    // in registers).  OPT-IN (tile_hint 7): faster in isolation on the K >= 192 layers (28 vs 38 us, 44 vs 50 us at
-    // 20x20, B = 64) but 0.5 % slower in the two-stream pipeline (31.10 k vs 31.27 k images/s): its workgroups
-    // hold ~100-130 KB of LDS and 8 waves per CU, which keeps the other chunk's kernels off those CUs.
-    const hipError_t ec = yl_launch_conv_dwc(m, st);
-    if (ec != hipErrorNotSupported) return ec;
-  }
-  if (halo) {
-    const size_t lds = YlDwhLds{NT, p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes();
-    if (lds <= YlDwhLds::LIMIT) {
-      const YlMultiKernel kern = yl_dwh_kernels[yl_nt_index(NT)][p.dw_k == 5][p.dw_stride == 2];   // (halo: 3 / 5, 1 / 2)
-      long tiles[4], wtotal = 0;
-      for (int k = 0; k < n; ++k) {
-        const long wt = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW >> 2);
-        tiles[k] = (wt + 3) / 4;                            // block-sized units (4 waves)
-        wtotal += tiles[k];
+  // depthwise k x k -> 1x1: the kernel yl_dw_form names (the families, their order and the tile_hint switches are there)
+  const YlDwForm dwf = p.dw_k > 0 ? yl_dw_form(m, big, tile_hint) : YlDwForm{YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
+  if (p.dw_k > 0) {
+    switch (dwf.family) {
+      case YL_DWF_DWK: case YL_DWF_DWL: return yl_launch_conv_dwk(p, dwf, st);
+      case YL_DWF_DWS: return yl_launch_conv_dws(p, dwf, st);
+      case YL_DWF_DWT: case YL_DWF_DWT_SPLITK: return yl_launch_conv_dwt(m, dwf, st);
+      case YL_DWF_DWC: return yl_launch_conv_dwc(m, dwf, st);
+      case YL_DWF_DWH: {
+        const size_t lds = YlDwhLds{NT, p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes();
+        const YlMultiKernel kern = yl_dwh_kernels[yl_nt_index(NT)][p.dw_k == 5][p.dw_stride == 2];   // (halo: 3 / 5, 1 / 2)
+        long tiles[4], wtotal = 0;
+        for (int k = 0; k < n; ++k) {
+          const long wt = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW >> 2);
+          tiles[k] = (wt + 3) / 4;                            // block-sized units (4 waves)
+          wtotal += tiles[k];
+        }
+        int gx = yl_resident_blocks((const void*)kern, 256, lds, 4) / gy;
+        if (gx < 8) gx = 8;
+        gx &= ~7;
+        if (gx > wtotal) gx = (int)wtotal;
+        gx = yl_partition_blocks(m, tiles, gx);
+        hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, st, m);
+        return hipGetLastError();
       }
-      int gx = yl_resident_blocks((const void*)kern, 256, lds, 4) / gy;
-      if (gx < 8) gx = 8;
-      gx &= ~7;
-      if (gx > wtotal) gx = (int)wtotal;
-      gx = yl_partition_blocks(m, tiles, gx);
-      hipLaunchKernelGGL(kern, dim3(gx, gy), dim3(256), lds, st, m);
-      return hipGetLastError();
+      case YL_DWF_MFMA: break;                                // below, with the other modes of yl_conv_mfma_kernel
+      default: return hipErrorInvalidValue;
     }
   }
   long Mtot = 0;
@@ -1288,17 +1335,12 @@ hipError_t yl_launch_conv_multi(const YlConvP* ps, int n, int tile_hint, hipStre
   const long tiles2 = (Mtot + 127) / 128;
   if (tile_hint == 1 || (tile_hint == 0 && tiles2 * gy < 2 * YL_NUM_CU)) MT = 1;
   if (p.dw_k > 0) MT = 1;           // depthwise prologue: one m-tile per wave (register budget -> occupancy)
-  // LDS weight chunk: whole K if it fits, else stream 48 KiB chunks
-  const size_t step_bytes = YlMfmaLds::chunk(1, NT) * 4;               // one k-step of weights
-  const size_t extra = YlMfmaLds::bytes(0, NT, MT, p.dw_k, p.Cin, p.N);   // taps + store staging (head rows)
-  if (extra + step_bytes > YlMfmaLds::LIMIT) return hipErrorInvalidValue;
-  const size_t budget = YlMfmaLds::LIMIT - extra;
+  // LDS weight chunk: whole K if it fits, else stream 48 KiB chunks (a depthwise layer: yl_dw_form's answer)
   int CH;
-  if ((size_t)p.TK * step_bytes <= budget) CH = p.TK;                  // whole K resident
-  else CH = (int)((budget < YlMfmaLds::STREAM_CHUNK ? budget : YlMfmaLds::STREAM_CHUNK) / step_bytes);   // stream K in chunks
+  if (p.dw_k > 0) CH = dwf.a[3];
+  else if (!yl_mfma_chunk(p, NT, MT, &CH)) return hipErrorInvalidValue;
   const size_t lds = YlMfmaLds::bytes(CH, NT, MT, p.dw_k, p.Cin, p.N);
-  const int mode = p.dw_k == 3 ? YL_CM_DW3 : p.dw_k == 5 ? YL_CM_DW5 : p.dw_k > 0 ? YL_CM_DWPRO
-                   : ((p.k == 1 && p.stride == 1) ? (p.scale ? YL_CM_PWSC : YL_CM_PW) : YL_CM_KXK);
+  const int mode = p.dw_k > 0 ? dwf.a[2] : ((p.k == 1 && p.stride == 1) ? (p.scale ? YL_CM_PWSC : YL_CM_PW) : YL_CM_KXK);
   long tiles[4], ttotal = 0;
   for (int k = 0; k < n; ++k) {
     m.p[k].CH = CH;
@@ -1360,14 +1402,24 @@ static hipError_t yl_launch_dw_tile(const YlConvP& p, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t yl_launch_dw(const YlConvP& p, hipStream_t st) {
+// Which kernel runs the stand-alone depthwise layer p (yl_internal.h)
+YlDwForm yl_dw_alone_form(const YlConvP& p) {
   const bool tile_off = (p.dev & YL_DEV_DW_TILE_OFF) != 0 && !p.pool;   // developer A/B (yl_set_option "dev_select")
-  if (p.pool && (p.res || p.pool_wpi != yl_dw_pool_wpi(p.k, p.stride, p.Cin, p.N, p.OH, p.OW) || p.pool_wpi < 1)) return hipErrorInvalidValue;
-  if (!tile_off && (p.Cin & 3) == 0 && p.N == p.Cin) {
-    if (p.k == 3 && p.stride == 1) return yl_launch_dw_tile<3, 1>(p, st);
-    if (p.k == 3 && p.stride == 2) return yl_launch_dw_tile<3, 2>(p, st);
-    if (p.k == 5 && p.stride == 1) return yl_launch_dw_tile<5, 1>(p, st);
-    if (p.k == 5 && p.stride == 2) return yl_launch_dw_tile<5, 2>(p, st);
+  if (p.pool && (p.res || p.pool_wpi != yl_dw_pool_wpi(p.k, p.stride, p.Cin, p.N, p.OH, p.OW) || p.pool_wpi < 1))
+    return {YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
+  if (!tile_off && (p.Cin & 3) == 0 && p.N == p.Cin && (p.k == 3 || p.k == 5) && (p.stride == 1 || p.stride == 2))
+    return {YL_DWF_DW_TILE, {p.k, p.stride, 0, 0, 0, 0}};
+  return {YL_DWF_DW, {0, 0, 0, 0, 0, 0}};
+}
+
+hipError_t yl_launch_dw(const YlConvP& p, hipStream_t st) {
+  const YlDwForm f = yl_dw_alone_form(p);
+  if (f.family == YL_DWF_NONE) return hipErrorInvalidValue;
+  if (f.family == YL_DWF_DW_TILE) {
+    if (f.a[0] == 3 && f.a[1] == 1) return yl_launch_dw_tile<3, 1>(p, st);
+    if (f.a[0] == 3 && f.a[1] == 2) return yl_launch_dw_tile<3, 2>(p, st);
+    if (f.a[0] == 5 && f.a[1] == 1) return yl_launch_dw_tile<5, 1>(p, st);
+    if (f.a[0] == 5 && f.a[1] == 2) return yl_launch_dw_tile<5, 2>(p, st);
   }
   const size_t total = (size_t)p.M * (p.Cin >> 2);
   hipLaunchKernelGGL(yl_dw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, p);

@@ -28,6 +28,10 @@
 #if YL_BF16
 #define yl_conv_dwc_kernel YL_LP_NAME(yl_conv_dwc_kernel)
 #define yl_launch_conv_dwc YL_LP_NAME(yl_launch_conv_dwc)
+#define yl_dwc_form YL_LP_NAME(yl_dwc_form)
+#define yl_dwt_form YL_LP_NAME(yl_dwt_form)
+#define yl_dwk_form YL_LP_NAME(yl_dwk_form)
+#define yl_dws_form YL_LP_NAME(yl_dws_form)
 #define yl_convc_init YL_LP_NAME(yl_convc_init)
 #define yl_conv_pwt_kernel YL_LP_NAME(yl_conv_pwt_kernel)
 #define yl_launch_conv_pwt YL_LP_NAME(yl_launch_conv_pwt)
@@ -887,12 +891,16 @@ static const YlMultiKernel dwt_splitk_kernels[2][2] = {
     {yl_conv_dwt_kernel<4, 3, 1, 1, false, 4>, yl_conv_dwt_kernel<4, 3, 2, 1, false, 4>},
     {yl_conv_dwt_kernel<4, 5, 1, 1, false, 4>, nullptr}};
 
-// NT, WL, SK: the template arguments of `kern` (DK and DS are the layer's)
+// dynamic LDS of yl_conv_dwt_kernel<NT, p.dw_k, p.dw_stride, 1, WL, SK> on the layer p
+static size_t dwt_lds(const YlConvP& p, int NT, bool WL, int SK) {
+  return YlDwtLds{p.dw_k, p.dw_stride, 1, SK, NT, p.KB, p.Cin, WL ? p.NTtot : 0}.bytes();
+}
+
+// NT, WL, SK: the template arguments of `kern` (DK and DS are the layer's); yl_dwt_form has held its LDS to the limit
 static hipError_t dwt_go(YlConvMulti& m, hipStream_t st, YlMultiKernel kern, int NT, bool WL, int SK) {
   constexpr int MT = 1;
   const YlConvP& p = m.p[0];
-  const size_t lds = YlDwtLds{p.dw_k, p.dw_stride, MT, SK, NT, p.KB, p.Cin, WL ? p.NTtot : 0}.bytes();
-  if (lds > YlDwtLds::LIMIT) return hipErrorNotSupported;
+  const size_t lds = dwt_lds(p, NT, WL, SK);
   const int res = yl_resident_blocks((const void*)kern, 256, lds, 8);
   long tiles[4];
   for (int k = 0; k < m.n; ++k)
@@ -904,32 +912,40 @@ static hipError_t dwt_go(YlConvMulti& m, hipStream_t st, YlMultiKernel kern, int
 }
 
 // depthwise (3x3 / 5x5, stride 1 / 2) -> 1x1 with N % 4 == 0, N <= 96 (all n-tiles in one wave), OH % 4 == 0,
-// OW % 4 == 0.  hipErrorNotSupported otherwise (yl_conv_dwh_kernel then runs the layer).
-hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st) {
+// OW % 4 == 0.  Family 0 otherwise (yl_conv_dwh_kernel then runs the layer).
+YlDwForm yl_dwt_form(const YlConvMulti& m) {
+  const YlDwForm none = {YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
   const YlConvP& p = m.p[0];
-  if (p.dw_k == 0 || (p.N & 3) || p.NTtot > 6 || p.dec_boxes || p.C1 > 0) return hipErrorNotSupported;
-  if ((p.dw_k != 3 && p.dw_k != 5) || (p.dw_stride != 1 && p.dw_stride != 2)) return hipErrorNotSupported;
+  if (p.dw_k == 0 || (p.N & 3) || p.NTtot > 6 || p.dec_boxes || p.C1 > 0) return none;
+  if ((p.dw_k != 3 && p.dw_k != 5) || (p.dw_stride != 1 && p.dw_stride != 2)) return none;
   // Per-layer measurements (edge_n, B = 64, us; dwh = yl_conv_dwh_kernel, <mt><wl> = this kernel):
   //   K=N=96 dw3 80x80:  dwh 143 | 10: 163 | 11: 137 | 20: 147 | 21: 141        K=96 N=48 dw3: dwh 32.9 | 11: 29.2
   //   K=256 N=64 dw5:    dwh 49.7 | 10: 35.1 | 11: 49.3 | 20: 34.9             K=32 N=96 dw5 s2: dwh 76 | 11: 70
   // -> one m-tile per wave (the 4x8 tile needs ~190 VGPRs: 2 waves per SIMD), LDS weight image while it is <= 36 KB.
   // ("dev_select" bit 4 disables the kernel: developer A/B)
-  if (p.dev & YL_DEV_DWT_OFF) return hipErrorNotSupported;
+  if (p.dev & YL_DEV_DWT_OFF) return none;
   const bool wl = p.KB * p.NTtot <= 36;
   for (int k = 0; k < m.n; ++k) {
-    if ((m.p[k].OH & 3) || (m.p[k].OW & 3)) return hipErrorNotSupported;
-    if ((size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
+    if ((m.p[k].OH & 3) || (m.p[k].OW & 3)) return none;
+    if ((size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return none;   // 32-bit byte offsets
   }
   const int nts[5] = {1, 2, 3, 4, 6};
   int NT = 6;
   for (int i = 0; i < 5; ++i) if (nts[i] >= p.NTtot) { NT = nts[i]; break; }
   const int dk5 = p.dw_k == 5, ds2 = p.dw_stride == 2;
   // split-K: chosen by the layer's SHAPE only (batch-invariant results); "dev_select" bit 10 keeps the one-wave-per-tile form
-  if (m.n == 1 && NT == 4 && !wl && p.KB >= 8 && p.OH * p.OW <= 400 && !(p.dev & YL_DEV_DWT_NOSPLIT) && dwt_splitk_kernels[dk5][ds2]) {
-    const hipError_t e = dwt_go(m, st, dwt_splitk_kernels[dk5][ds2], 4, false, 4);
-    if (e != hipErrorNotSupported) return e;
-  }
-  return dwt_go(m, st, dwt_kernels[NT <= 4 ? NT - 1 : 4][dk5][ds2][wl], NT, wl, 1);
+  if (m.n == 1 && NT == 4 && !wl && p.KB >= 8 && p.OH * p.OW <= 400 && !(p.dev & YL_DEV_DWT_NOSPLIT) && dwt_splitk_kernels[dk5][ds2] &&
+      dwt_lds(p, 4, false, 4) <= YlDwtLds::LIMIT)
+    return {YL_DWF_DWT_SPLITK, {4, p.dw_k, p.dw_stride, 1, 0, 4}};
+  if (dwt_lds(p, NT, wl, 1) > YlDwtLds::LIMIT) return none;
+  return {YL_DWF_DWT, {NT, p.dw_k, p.dw_stride, 1, wl, 1}};
+}
+
+hipError_t yl_launch_conv_dwt(YlConvMulti& m, const YlDwForm& f, hipStream_t st) {
+  const int NT = f.a[0], dk5 = f.a[1] == 5, ds2 = f.a[2] == 2;
+  if (f.family == YL_DWF_DWT_SPLITK) return dwt_go(m, st, dwt_splitk_kernels[dk5][ds2], 4, false, 4);
+  if (f.family == YL_DWF_DWT) return dwt_go(m, st, dwt_kernels[NT <= 4 ? NT - 1 : 4][dk5][ds2][f.a[4]], NT, f.a[4] != 0, 1);
+  return hipErrorNotSupported;
 }
 
 #if !YL_BF16
@@ -2165,6 +2181,7 @@ static YlConvKernel dwk_kernel_of(int NT, int GW, int NW) {
   return nullptr;
 }
 
+// yl_dwk_form has looked the instantiation up and held its LDS to the limit
 static hipError_t dwk_go(const YlConvP& p0, hipStream_t st, int NT, int GW) {
   constexpr int NW = 4;
   const YlConvKernel kern = dwk_kernel_of(NT, GW, NW);
@@ -2172,7 +2189,6 @@ static hipError_t dwk_go(const YlConvP& p0, hipStream_t st, int NT, int GW) {
   YlConvP p = p0;
   p.ntiles = (int)(((long)p.M + 16 * NW - 1) / (16 * NW));
   const size_t lds = YlDwkLds(NT, GW, p.Cin).bytes;
-  if (lds > YlDwkLds::LIMIT) return hipErrorNotSupported;
   const int G = p.NTtot / (NT * GW);
   const int gx = yl_band_grid(yl_resident_blocks((const void*)kern, NW * 64, lds, 8), (long)p.ntiles * G);
   hipLaunchKernelGGL(kern, dim3(gx), dim3(NW * 64), lds, st, p);
@@ -2181,16 +2197,18 @@ static hipError_t dwk_go(const YlConvP& p0, hipStream_t st, int NT, int GW) {
 
 static YlConvKernel dwl_kernel_of(int NTT);
 static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, YlConvKernel kern);
+static bool dwl_fits(int NTT, int KB);            // the window form's LDS within its limit
 
 // depthwise 3x3 (stride 1 / 2) -> 1x1 with K >= 192, N % 4 == 0 and an n-tile count that is a multiple of 7 or 8,
-// single problem.  hipErrorNotSupported otherwise (yl_conv_mfma_kernel's streamed mode then runs the layer).
-hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st) {
-  if (p.dw_k != 3 || (p.N & 3) || p.dec_boxes || p.C1 > 0 || p.KB < 12 || p.NTtot <= 8) return hipErrorNotSupported;
-  if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
+// single problem.  Family 0 otherwise (yl_conv_mfma_kernel's streamed mode then runs the layer).
+YlDwForm yl_dwk_form(const YlConvP& p) {
+  const YlDwForm none = {YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
+  if (p.dw_k != 3 || (p.N & 3) || p.dec_boxes || p.C1 > 0 || p.KB < 12 || p.NTtot <= 8) return none;
+  if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return none;   // 32-bit byte offsets
   // developer A/B ("dev_select" bits 5-6): 2 = off, 1 = one n-group per item (depthwise recomputed per group),
   // 0 = default: a wave holds every n-group
   const int sel = YL_DEV_DWK(p.dev) == 2 ? 0 : (YL_DEV_DWK(p.dev) == 1 ? 1 : 2);
-  if (sel == 0) return hipErrorNotSupported;
+  if (sel == 0) return none;
   // window-in-LDS form (yl_conv_dwl_kernel): stride 1, pad 1, grids that fill the 8 x 8-pixel windows to >= 80 % (20 x 20: 69 %, slower than the tap-load kernel), >= 1.5 items
   // per CU (40 x 40 at B = 32: 0.116 -> 0.098 ms); "dev_select" bit 14 = off, bit 15 = on every grid (the bitwise test)
   // (the fp16-storage unit keeps the tap-load kernel: the windows are raw LDS-DMA copies of the tensor's bytes)
@@ -2198,13 +2216,22 @@ hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st) {
       (size_t)p.B * p.H * p.W * p.Cin < ((size_t)1 << 31)) {
     const long wins = (long)p.B * ((p.OW + 7) >> 3) * ((p.OH + 7) >> 3);
     if (((long)p.B * p.OH * p.OW * 10 >= wins * 64 * 8 && wins >= 3 * YL_NUM_CU) || (p.dev & YL_DEV_DWL_ALL)) {
-      if (const YlConvKernel kl = dwl_kernel_of(p.NTtot)) return dwl_go(p, st, kl);
+      // (a window form beyond its LDS limit leaves the layer to the kernels behind this family, not to the tap-load form)
+      if (dwl_kernel_of(p.NTtot)) return dwl_fits(p.NTtot, p.KB) ? YlDwForm{YL_DWF_DWL, {p.NTtot, 0, 0, 0, 0, 0}} : none;
     }
   }
-  if (p.NTtot == 21) return dwk_go(p, st, 7, sel == 2 ? 3 : 1);
-  if (p.NTtot == 16) return dwk_go(p, st, 8, sel == 2 ? 2 : 1);
-  if (p.NTtot % 7 == 0) return dwk_go(p, st, 7, 1);
-  if (p.NTtot % 8 == 0) return dwk_go(p, st, 8, 1);
+  int NT = 0, GW = 1;
+  if (p.NTtot == 21) { NT = 7; GW = sel == 2 ? 3 : 1; }
+  else if (p.NTtot == 16) { NT = 8; GW = sel == 2 ? 2 : 1; }
+  else if (p.NTtot % 7 == 0) NT = 7;
+  else if (p.NTtot % 8 == 0) NT = 8;
+  if (!NT || !dwk_kernel_of(NT, GW, 4) || YlDwkLds(NT, GW, p.Cin).bytes > YlDwkLds::LIMIT) return none;
+  return {YL_DWF_DWK, {NT, GW, 4, 0, 0, 0}};
+}
+
+hipError_t yl_launch_conv_dwk(const YlConvP& p, const YlDwForm& f, hipStream_t st) {
+  if (f.family == YL_DWF_DWL) return dwl_go(p, st, dwl_kernel_of(f.a[0]));
+  if (f.family == YL_DWF_DWK) return dwk_go(p, st, f.a[0], f.a[1]);
   return hipErrorNotSupported;
 }
 
@@ -2481,13 +2508,14 @@ static YlConvKernel dwl_kernel_of(int NTT) {
   return nullptr;
 }
 
+static bool dwl_fits(int NTT, int KB) { return YlDwlLds(NTT, KB).bytes <= YlDwlLds::LIMIT; }
+
+// yl_dwk_form has held the LDS to the limit and the tensor to 32-bit byte offsets
 static hipError_t dwl_go(const YlConvP& p0, hipStream_t st, YlConvKernel kern) {
   YlConvP p = p0;
   const long WTOT = (long)p.B * ((p.OW + 7) >> 3) * ((p.OH + 7) >> 3);
   p.ntiles = (int)((WTOT + 1) / 2);
   const size_t lds = YlDwlLds(p.NTtot, p.KB).bytes;
-  if (lds > YlDwlLds::LIMIT) return hipErrorNotSupported;
-  if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
   const int gx = yl_band_grid(yl_resident_blocks((const void*)kern, 512, lds, 8), p.ntiles);
   hipLaunchKernelGGL(kern, dim3(gx), dim3(512), lds, st, p);
   return hipGetLastError();
@@ -2744,15 +2772,25 @@ bool yl_dws_supported(int cin, int n, int dk, int ds, int oh, int ow) {
 }
 #endif
 
-hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st) {
-  if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return hipErrorNotSupported;   // 32-bit byte offsets
+// family 0: not a layer of this kernel (yl_dws_supported), or a configuration or tensor size it does not take
+YlDwForm yl_dws_form(const YlConvP& p) {
+  const YlDwForm none = {YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
+  if ((size_t)p.B * p.H * p.W * p.Cin * sizeof(yl_act_t) >= ((size_t)1 << 31)) return none;   // 32-bit byte offsets
   if (p.dw_k == 0 || p.k != 1 || p.stride != 1 || p.dec_boxes || p.C1 > 0 || p.scale || p.in_shift || p.w3p ||
       !yl_dws_supported(p.Cin, p.N, p.dw_k, p.dw_stride, p.OH, p.OW) ||
       (size_t)p.B * p.H * p.W * p.Cin >= ((size_t)1 << 40))
-    return hipErrorNotSupported;
+    return none;
   const int ntt = p.NTtot;
-#define YL_DWS_RUN(A, G, K, S_) \
-  if (p.dw_k == K && p.dw_stride == S_ && ntt <= A * G && ntt > (A * G == 8 ? 6 : A * G == 13 ? 8 : 13)) return dws_go<A, G, K, S_, 4>(p, st);
+#define YL_DWS_IS(A, G, K, S_) \
+  if (p.dw_k == K && p.dw_stride == S_ && ntt <= A * G && ntt > (A * G == 8 ? 6 : A * G == 13 ? 8 : 13)) return {YL_DWF_DWS, {A, G, K, S_, 4, 0}};
+  YL_DWS_SHAPES(YL_DWS_IS)
+#undef YL_DWS_IS
+  return none;
+}
+
+hipError_t yl_launch_conv_dws(const YlConvP& p, const YlDwForm& f, hipStream_t st) {
+  if (f.family != YL_DWF_DWS) return hipErrorNotSupported;
+#define YL_DWS_RUN(A, G, K, S_) if (f.a[0] == A && f.a[1] == G && f.a[2] == K && f.a[3] == S_) return dws_go<A, G, K, S_, 4>(p, st);
   YL_DWS_SHAPES(YL_DWS_RUN)
 #undef YL_DWS_RUN
   return hipErrorNotSupported;
@@ -3352,29 +3390,37 @@ hipError_t yl_convc_init() {
   return e;
 }
 
-// n problems of identical configuration (m.p[0..n-1] filled like for yl_conv_dwh_kernel).  Returns
-// hipErrorNotSupported when the shape is outside this kernel's limits (the caller then takes the halo kernel).
-hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st) {
+// n problems of identical configuration (m.p[0..n-1] filled like for yl_conv_dwh_kernel).  Family 0 when the shape is
+// outside this kernel's limits (the caller then takes the halo kernel).
+YlDwForm yl_dwc_form(const YlConvMulti& m) {
+  const YlDwForm none = {YL_DWF_NONE, {0, 0, 0, 0, 0, 0}};
   const YlConvP& p = m.p[0];
   const int ntw = (p.NTtot + 3) / 4;
-  if (ntw < 1 || ntw > 5 || p.KB > kbmax_of(ntw) || (p.N & 3)) return hipErrorNotSupported;
+  if (ntw < 1 || ntw > 5 || p.KB > kbmax_of(ntw) || (p.N & 3)) return none;
   // Measured per layer (edge_n, B = 64, eager): the producer / consumer split pays where the depthwise phase is
   // long -- K >= 192 channels on a stride-1 depthwise (28 vs 38 us for 3x3, 44 vs 50 us for 5x5 at 20x20) -- and
   // loses on the short-K layers, where two or three of the four depthwise waves idle and the per-tile barrier costs
   // more than the weight prologue it replaces.  "dev_select" bit 3 lifts the restriction (A/B runs).
   const bool all = (p.dev & YL_DEV_DWC_ALL) != 0;       // "dev_select" bit 3: the bitwise-equivalence test
-  if (!all && (p.KB < 12 || p.dw_stride != 1)) return hipErrorNotSupported;
-  if (!((p.dw_k == 3 || p.dw_k == 5) && (p.dw_stride == 1 || p.dw_stride == 2))) return hipErrorNotSupported;
+  if (!all && (p.KB < 12 || p.dw_stride != 1)) return none;
+  if (!((p.dw_k == 3 || p.dw_k == 5) && (p.dw_stride == 1 || p.dw_stride == 2))) return none;
+  if (YlDwcLds{p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes() > YlDwcLds::LIMIT) return none;
+  for (int k = 0; k < m.n; ++k)
+    if ((m.p[k].OH & 3) || (m.p[k].OW & 3) || (size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * 4 >= ((size_t)1 << 31))
+      return none;
+  return {YL_DWF_DWC, {p.dw_k, p.dw_stride, ntw, 0, 0, 0}};
+}
+
+hipError_t yl_launch_conv_dwc(YlConvMulti& m, const YlDwForm& f, hipStream_t st) {
+  if (f.family != YL_DWF_DWC) return hipErrorNotSupported;
+  const YlConvP& p = m.p[0];
   const size_t lds = YlDwcLds{p.dw_k, p.dw_stride, p.KB, p.Cin}.bytes();
-  if (lds > YlDwcLds::LIMIT) return hipErrorNotSupported;
   long tiles[4], total = 0;
   for (int k = 0; k < m.n; ++k) {
-    if ((m.p[k].OH & 3) || (m.p[k].OW & 3) || (size_t)m.p[k].B * m.p[k].H * m.p[k].W * m.p[k].Cin * 4 >= ((size_t)1 << 31))
-      return hipErrorNotSupported;
     tiles[k] = (long)m.p[k].B * (m.p[k].OH >> 2) * (m.p[k].OW >> 2);
     total += tiles[k];
   }
-  const YlMultiKernel kern = dwc_kernels[ntw - 1][p.dw_k == 5][p.dw_stride == 2];
+  const YlMultiKernel kern = dwc_kernels[f.a[2] - 1][f.a[0] == 5][f.a[1] == 2];
   const int res = yl_resident_blocks((const void*)kern, 512, lds, 4);
   // grid: a multiple of 8 workgroups (XCD-aware tile bands, see the kernel), at most what is co-resident and one per tile
   long gx = yl_band_grid(res, total);

@@ -364,8 +364,28 @@ hipError_t yl_launch_conv_dpq(const YlConvP& p, hipStream_t st);
 // dense 3x3 with 16 / 32 -> <= 16 channels on large grids, window in LDS (yl_dpp.hip, round 6; fp32 only)
 hipError_t yl_launch_conv_k3w(const YlConvP& p, hipStream_t st);
 bool yl_dpq_supported(int cin, int cmid, int cout, int oh, int ow);
-// block-cooperative depthwise -> 1x1 kernel (yl_convc.hip); hipErrorNotSupported = shape outside its limits
-hipError_t yl_launch_conv_dwc(YlConvMulti& m, hipStream_t st);
+// ---- which kernel runs a depthwise k x k -> 1x1 layer (or a stand-alone depthwise one): the decision, apart from the launch ----
+// A family and the template arguments of its instantiation.  Each family's "is the layer mine, and which instantiation" is one
+// function next to its kernel (yl_dwk_form, yl_dws_form, yl_dwt_form, yl_dwc_form: family 0 = not mine); the order in which
+// they are asked, the tile_hint switches and the two kernels of yl_conv.hip are yl_dw_form.  yl_launch_conv_multi launches what
+// yl_dw_form names, yl_launch_dw what yl_dw_alone_form names, and yl_query_dw_form (yl_api.hip) reports both.  Grid sizes are
+// not part of it: they stay with the launchers.  The ids are those of include/yololite_hip.h (YL_DWF_*).
+struct YlDwForm {
+  int family;   // YL_DWF_*
+  int a[6];     // DWK: NT, GW, NW | DWL: NTT | DWS: NT, GW, DK, DS, NW | DWT, DWT_SPLITK: NT, DK, DS, MT, WL, SK | DWC: DK, DS, NTW |
+                // DWH: NT, DK, DS | MFMA: NT, MT, mode (YL_CM_*), CH (k-steps of weights resident in LDS) | DW_TILE: K, S | DW: none
+};
+YlDwForm yl_dwk_form(const YlConvP& p);            // YL_DWF_DWK or YL_DWF_DWL
+YlDwForm yl_dws_form(const YlConvP& p);
+YlDwForm yl_dwt_form(const YlConvMulti& m);        // YL_DWF_DWT or YL_DWF_DWT_SPLITK
+YlDwForm yl_dwc_form(const YlConvMulti& m);
+// m: the problems of one launch (C1 == 0, dw_k > 0), big: the index of the largest, which the decisions follow; family 0: no
+// kernel runs the launch (yl_launch_conv_multi returns hipErrorInvalidValue)
+YlDwForm yl_dw_form(const YlConvMulti& m, int big, int tile_hint);
+YlDwForm yl_dw_alone_form(const YlConvP& p);       // YL_OP_DW: YL_DWF_DW_TILE or YL_DWF_DW; 0: refused
+
+// block-cooperative depthwise -> 1x1 kernel (yl_convc.hip); f: yl_dwc_form's answer (a family of its own)
+hipError_t yl_launch_conv_dwc(YlConvMulti& m, const YlDwForm& f, hipStream_t st);
 // wave-autonomous 1x1 conv for small pixel counts (yl_convc.hip); hipErrorNotSupported = not a plain 1x1 layer
 hipError_t yl_launch_conv_pwt(const YlConvP& p, hipStream_t st);
 hipError_t yl_launch_conv_pwt_multi(const YlConvP* ps, int n, hipStream_t st);
@@ -375,8 +395,8 @@ hipError_t yl_launch_conv_ir(const YlConvP& p, hipStream_t st);
 hipError_t yl_launch_conv_pws(const YlConvP& p, hipStream_t st);
 // dense k x k conv with a double-buffered weight stream (yl_convc.hip); hipErrorNotSupported = other kernel runs it
 hipError_t yl_launch_conv_kxk(const YlConvP& p, hipStream_t st);
-// wave-autonomous depthwise -> 1x1 kernel (yl_convc.hip); hipErrorNotSupported = shape outside its limits
-hipError_t yl_launch_conv_dwt(YlConvMulti& m, hipStream_t st);
+// wave-autonomous depthwise -> 1x1 kernel (yl_convc.hip); f: yl_dwt_form's answer (a family of its own)
+hipError_t yl_launch_conv_dwt(YlConvMulti& m, const YlDwForm& f, hipStream_t st);
 // the same projection (depthwise stride 1 -> 64 channels) with the next layer's plain 1x1 (out3) chained behind it
 // (yl_convc.hip, fp32 unit only); hipErrorNotSupported = shape / configuration not instantiated
 hipError_t yl_launch_conv_dwx(const YlConvP& pd, float* out3, hipStream_t st);
@@ -385,10 +405,11 @@ bool yl_dwx_supported(int cin, int cout, int dw_k, int dw_stride, int cout1, int
 // layer's weights as w3p / b3 / C3 / act3, out3 is its output; hipErrorNotSupported = shape / configuration not instantiated
 hipError_t yl_launch_conv_pwx(const YlConvP& p1, float* out3, hipStream_t st);
 bool yl_pwx_supported(int cin, int cmid, int cout);
-// streamed-weight depthwise 3x3 -> 1x1 kernel for K >= 192 and more than 8 n-tiles (yl_convc.hip)
-hipError_t yl_launch_conv_dwk(const YlConvP& p, hipStream_t st);
+// streamed-weight depthwise 3x3 -> 1x1 kernel for K >= 192 and more than 8 n-tiles, taps from L1/L2 or the window in LDS
+// (yl_convc.hip); f: yl_dwk_form's answer (a family of its own)
+hipError_t yl_launch_conv_dwk(const YlConvP& p, const YlDwForm& f, hipStream_t st);
 // depthwise k x k -> 1x1 for >= 192 depthwise channels: streamed 1x1 weights AND tap weights, halo patch through LDS (yl_convc.hip,
-// round 5); hipErrorNotSupported = shape not instantiated
-hipError_t yl_launch_conv_dws(const YlConvP& p, hipStream_t st);
+// round 5); f: yl_dws_form's answer (a family of its own)
+hipError_t yl_launch_conv_dws(const YlConvP& p, const YlDwForm& f, hipStream_t st);
 // Winograd F(2x2,3x3) dense 3x3 (yl_convc.hip); hipErrorNotSupported = not this layer
 hipError_t yl_launch_conv_wino(const YlConvP& p, hipStream_t st);
